@@ -17,7 +17,12 @@ Weak scaling either way (P candidates per GPU fixed).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
   python bench.py --gpus N --group ...  # one process, N devices
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`, `cpu_baseline` and `parity_gate` objects.
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full               # + every side measurement below
+
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and reports them;
+--full adds the other evaluation order, the `roofline` object (profiled steps, the unfused launches, PMC traffic), `cpu_baseline`
+and `parity_gate`.
 """
 from __future__ import annotations
 
@@ -73,16 +78,23 @@ def parse_args(argv=None):
     ap.add_argument("--resolution", type=float, default=1.0)
     ap.add_argument("--order", type=int, default=1, choices=(0, 1),
                     help="NDT evaluation order of the TIMED mode (dgs_params.ndt_strict_order): 1 = upstream's operation order, the mode that "
-                         "reproduces the reference's transforms (default); 0 = the re-associated fast order, reported beside it as fast_value")
+                         "reproduces the reference's transforms (default); 0 = the re-associated fast order, reported beside it as fast_value (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the other evaluation order, the roofline leg (profiled steps, unfused launches, "
+                         "PMC traffic), the cpu_baseline and the parity gate; a plain run reports the timed steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (the gathered candidate records and the loop it selected) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU budget of the cpu_baseline sample (the child process's timed work)")
     ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)   # internal: the cpu_baseline leg's own process
     ap.add_argument("--traffic", dest="traffic", action="store_true", default=True,
-                    help="measure HBM traffic of the dominant kernel: two short child runs under rocprofv3 (--pmc FETCH_SIZE, then "
-                         "WRITE_SIZE); default at N=1 when rocprofv3 is on PATH")
+                    help="with --full, measure HBM traffic of the dominant kernel: two short child runs under rocprofv3 (--pmc FETCH_SIZE, "
+                         "then WRITE_SIZE); default at N=1 when rocprofv3 is on PATH")
     ap.add_argument("--no-traffic", dest="traffic", action="store_false", help="leave roofline.traffic null (no rocprofv3 child runs)")
     ap.add_argument("--traffic-dir", default=os.path.join(ROOT, "gpurun_out", "traffic"))
     args = ap.parse_args(argv)
+    if args.steps < 1 and not args.dry_run:
+        ap.error("--steps must be at least 1: ms_per_step is the wall time of the timed steps over their number")
     if args.distinct_scans <= 0:
         args.distinct_scans = args.pairs
     return args
@@ -229,9 +241,10 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
+    loop = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()            # nothing but the detector's own work inside the timed region
+        loop = step()     # nothing but the detector's own work inside the timed region
     barrier()
     dt = time.perf_counter() - t0
     dt_own = dt
@@ -249,11 +262,13 @@ def main():
     regs = n_dev * P * args.steps
     value = regs / dt
     records = det.last_records
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, records, loop)
 
     # ---- the other evaluation order on the same step, timed the same way (rank-local: no collective inside it)
     other = 1 - args.order
     other_line = None
-    if not args.group:
+    if args.full and not args.group:
         reg_o = Registration("NDT_OMP", device=local_rank, **dict(reg_kw, ndt_strict_order=other))
         det_o = LoopDetector({"fitness_score_thresh": 1e9}, registration=reg_o, local_only=True)
         for _ in range(min(args.warmup, 3)):
@@ -288,65 +303,68 @@ def main():
                    "collective_backend": collective, "collective_world_size": n_dev},
     }
 
-    # ---- roofline leg: the same steps with every ndt_derivatives launch bracketed by HIP events on its stream.  Every rank
-    # runs it (the step contains the all_gather), rank 0 reports its own kernel timings (group mode: member 0's).
-    prof_reg.profile_enable(True)
-    prof_reg.profile_reset()
-    ev2 = 0
-    for _ in range(args.steps):
-        step()
-        ev2 += prof_reg.counts()["evaluations"]
-    ms, launches = prof_reg.profile_get(L.K_NDT_DERIVATIVES)
-    ms_solve, l_solve = prof_reg.profile_get(L.K_NDT_SOLVE)
-    ms_nn, l_nn = prof_reg.profile_get(L.K_NN_SEARCH)
-    ms_vox, l_vox = prof_reg.profile_get(L.K_NDT_VOXEL_BUILD)
-    prof_reg.profile_enable(False)
-
+    # ---- --full only from here on: the side measurements beside the timed steps
     alone = None
-    if not args.group:
-        # the same workload through (derivatives, solve) launch pairs: the derivative phase alone, for continuity with round 1's figure
-        os.environ["DGS_NDT_FUSED"] = "0"
-        reg_u = Registration("NDT_OMP", device=local_rank, **timed_kw)
-        del os.environ["DGS_NDT_FUSED"]
-        det_u = LoopDetector({"fitness_score_thresh": 1e9}, registration=reg_u, local_only=True)
-        det_u.matching(cands, new_kf)
-        reg_u.profile_enable(True)
-        reg_u.profile_reset()
-        ev_u = 0
+    if args.full:
+        # ---- roofline leg: the same steps with every ndt_derivatives launch bracketed by HIP events on its stream.  Every rank
+        # runs it (the step contains the all_gather), rank 0 reports its own kernel timings (group mode: member 0's).
+        prof_reg.profile_enable(True)
+        prof_reg.profile_reset()
+        ev2 = 0
         for _ in range(args.steps):
+            step()
+            ev2 += prof_reg.counts()["evaluations"]
+        ms, launches = prof_reg.profile_get(L.K_NDT_DERIVATIVES)
+        ms_solve, l_solve = prof_reg.profile_get(L.K_NDT_SOLVE)
+        ms_nn, l_nn = prof_reg.profile_get(L.K_NN_SEARCH)
+        ms_vox, l_vox = prof_reg.profile_get(L.K_NDT_VOXEL_BUILD)
+        prof_reg.profile_enable(False)
+
+        if not args.group:
+            # the same workload through (derivatives, solve) launch pairs: the derivative phase alone, for continuity with round 1's figure
+            os.environ["DGS_NDT_FUSED"] = "0"
+            reg_u = Registration("NDT_OMP", device=local_rank, **timed_kw)
+            del os.environ["DGS_NDT_FUSED"]
+            det_u = LoopDetector({"fitness_score_thresh": 1e9}, registration=reg_u, local_only=True)
             det_u.matching(cands, new_kf)
-            ev_u += reg_u.counts()["evaluations"]
-        ms_u, launches_u = reg_u.profile_get(L.K_NDT_DERIVATIVES)
-        ms_su, launches_su = reg_u.profile_get(L.K_NDT_SOLVE)
-        reg_u.close()
-        alone = (ev_u, ms_u, launches_u, ms_su, launches_su)
+            reg_u.profile_enable(True)
+            reg_u.profile_reset()
+            ev_u = 0
+            for _ in range(args.steps):
+                det_u.matching(cands, new_kf)
+                ev_u += reg_u.counts()["evaluations"]
+            ms_u, launches_u = reg_u.profile_get(L.K_NDT_DERIVATIVES)
+            ms_su, launches_su = reg_u.profile_get(L.K_NDT_SOLVE)
+            reg_u.close()
+            alone = (ev_u, ms_u, launches_u, ms_su, launches_su)
 
     if rank == 0:
-        cnt = prof_reg.counts()
-        Ns, Nt, V = args.points, cnt["target_points"], cnt["valid_voxels"]
-        shard_regs = P if not args.group else len(range(0, n_dev * P, n_dev))   # registrations behind ev2 (rank 0's / member 0's share)
-        out["ms_per_iter"] = 1e3 * dt / max(ev2, 1) * shard_regs   # wall ms per derivative evaluation of one pair stream (P run concurrently)
-        out["evaluations_per_registration"] = ev2 / (shard_regs * args.steps)
         out["converged_fraction"] = float(np.mean(records[:, 1] > 0.5)) if records is not None else None
-        rec_bytes = 64 if args.order == 1 else 48          # voxel record the kernel reads: 3 double means + 9 floats (upstream order) / 6 floats (fast order)
-        bytes_per_eval = 16 * Ns + rec_bytes * V + 344     # stream source once, table once, 43 doubles out
-        total_bytes = ev2 * bytes_per_eval
-        achieved = total_bytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-        out["roofline"] = {"bound": "hbm", "kernel": KERNEL[args.order] + " (derivatives of every active pair + the optimiser step of each pair in "
-                                                     "its closing workgroup)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                           "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                           "avg_launch_us": 1e3 * ms / max(launches, 1), "launches": launches,
-                           "algorithmic_bytes_per_launch": total_bytes / max(launches, 1),
-                           "bytes_per_evaluation": bytes_per_eval, "valid_voxels": V,
-                           "other_kernels_ms_per_step": {"ndt_solve": ms_solve / args.steps, "nn_fitness": ms_nn / args.steps,
-                                                         "voxel_build": ms_vox / args.steps, "ndt_derivatives": ms / args.steps}}
-        if alone is not None:
-            ev_u, ms_u, launches_u, ms_su, launches_su = alone
-            ach_u = ev_u * bytes_per_eval / (ms_u * 1e-3) / 1e9 if ms_u > 0 else 0.0
-            out["roofline"]["derivative_phase_alone"] = {
-                "kernel": KERNEL[args.order].replace(", fused", "") + " as its own launch (DGS_NDT_FUSED=0, followed by ndt_solve_kernel)",
-                "avg_launch_us": 1e3 * ms_u / max(launches_u, 1), "achieved": ach_u, "frac": ach_u / HBM_PEAK_GBS,
-                "ndt_solve_avg_launch_us": 1e3 * ms_su / max(launches_su, 1)}
+        if args.full:
+            cnt = prof_reg.counts()
+            Ns, Nt, V = args.points, cnt["target_points"], cnt["valid_voxels"]
+            shard_regs = P if not args.group else len(range(0, n_dev * P, n_dev))   # registrations behind ev2 (rank 0's / member 0's share)
+            out["ms_per_iter"] = 1e3 * dt / max(ev2, 1) * shard_regs   # wall ms per derivative evaluation of one pair stream (P run concurrently)
+            out["evaluations_per_registration"] = ev2 / (shard_regs * args.steps)
+            rec_bytes = 64 if args.order == 1 else 48          # voxel record the kernel reads: 3 double means + 9 floats (upstream order) / 6 floats (fast order)
+            bytes_per_eval = 16 * Ns + rec_bytes * V + 344     # stream source once, table once, 43 doubles out
+            total_bytes = ev2 * bytes_per_eval
+            achieved = total_bytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+            out["roofline"] = {"bound": "hbm", "kernel": KERNEL[args.order] + " (derivatives of every active pair + the optimiser step of each pair in "
+                                                         "its closing workgroup)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                               "avg_launch_us": 1e3 * ms / max(launches, 1), "launches": launches,
+                               "algorithmic_bytes_per_launch": total_bytes / max(launches, 1),
+                               "bytes_per_evaluation": bytes_per_eval, "valid_voxels": V,
+                               "other_kernels_ms_per_step": {"ndt_solve": ms_solve / args.steps, "nn_fitness": ms_nn / args.steps,
+                                                             "voxel_build": ms_vox / args.steps, "ndt_derivatives": ms / args.steps}}
+            if alone is not None:
+                ev_u, ms_u, launches_u, ms_su, launches_su = alone
+                ach_u = ev_u * bytes_per_eval / (ms_u * 1e-3) / 1e9 if ms_u > 0 else 0.0
+                out["roofline"]["derivative_phase_alone"] = {
+                    "kernel": KERNEL[args.order].replace(", fused", "") + " as its own launch (DGS_NDT_FUSED=0, followed by ndt_solve_kernel)",
+                    "avg_launch_us": 1e3 * ms_u / max(launches_u, 1), "achieved": ach_u, "frac": ach_u / HBM_PEAK_GBS,
+                    "ndt_solve_avg_launch_us": 1e3 * ms_su / max(launches_su, 1)}
 
         # ---- CPU baseline (a child process with pinned OpenMP threads) + the parity gate against its poses
         if other_line is not None:
@@ -360,7 +378,7 @@ def main():
             out["exchange_step_us"] = ex_us_own
         if args.group:
             out["config"]["rccl_communicator_ranks"] = getattr(reg, "rccl_ranks", None)
-        if not args.no_cpu_baseline and not args.group:
+        if args.full and not args.no_cpu_baseline and not args.group:
             # N = 1: the cpu_baseline leg (the contract's) + the parity gate on all its pairs.  N > 1: the contract reports cpu_baseline at
             # N = 1 only, but a multi-GPU line must still say how its transforms compare with the reference: rank 0 runs the oracle on ITS
             # shard (same child process) and states the gate for it.
@@ -379,7 +397,7 @@ def main():
                                                                               records_other if other_line is not None else None)
                 if n_dev > 1:
                     out["parity_gate"]["scope"] = "rank 0's shard of the step (%d of %d candidates)" % (len(cands), n_dev * P)
-        if n_dev == 1 and args.traffic and not args.group:
+        if args.full and n_dev == 1 and args.traffic and not args.group:
             try:
                 out["roofline"]["traffic"], out["roofline"]["traffic_detail"] = measure_traffic(args, bytes_per_eval, "ndt_strict3_kernel" if args.order == 1 else "ndt_derivatives_kernel")
             except Exception as e:  # profiler missing / refused: the counter stays null, the bench line is still valid
@@ -388,6 +406,21 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, records, loop):
+    """--dump-outputs: what a caller of LoopDetector.matching received from the last timed step, one float64 .npy per array --
+    the gathered [candidates, 20] result records (candidate, converged, fitness, status, row-major transform) and the Loop it
+    selected (candidate index and score; the relative pose in 3-D and 2-D).  No loop: the index is -1 and the rest NaN."""
+    from delta_graph_slam_amd.loop_detector import LoopDetector
+    best, _ = LoopDetector.select_best(records)   # the candidate matching() picked (its Loop holds the keyframe, not the index)
+    arrays = {"records": records,
+              "loop_candidate_score": [-1.0, np.nan] if loop is None else [best, loop.score],
+              "loop_relative_pose": np.full((4, 4), np.nan) if loop is None else loop.relative_pose,
+              "loop_relative_pose2D": np.full((3, 3), np.nan) if loop is None else loop.relative_pose2D}
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, np.float64))
 
 
 # ================================================================================================ CPU baseline (child process)
@@ -697,7 +730,7 @@ def measure_traffic(args, bytes_per_eval, kernel_substring="ndt_derivatives_kern
         shutil.rmtree(d, ignore_errors=True)
         os.makedirs(d, exist_ok=True)
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable,
-               os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-traffic", "--pairs", str(args.pairs),
+               os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-traffic", "--pairs", str(args.pairs),
                "--points", str(args.points), "--distinct-scans", str(args.distinct_scans), "--order", str(args.order)]
         env = {k: v for k, v in os.environ.items() if not k.startswith(PROFILER_ENV_PREFIXES)}
         if "rocprof" in env.get("LD_PRELOAD", "") or "roctracer" in env.get("LD_PRELOAD", ""):

@@ -84,3 +84,37 @@ def test_cpu_baseline_child_times_the_oracle_with_pinned_threads(tmp_path):
     o.set_target(tgt)
     o.set_source(sources[0])
     assert np.array_equal(o.align(guesses[0])["T"], res["T"][0])                          # same poses as an in-process run
+
+
+def test_side_measurements_are_behind_full_and_steps_must_be_positive():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert bench.parse_args(["--full", "--dump-outputs", "x"]).full is True
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_dump_outputs_writes_what_matching_returned(tmp_path):
+    """--dump-outputs: the gathered records and the Loop matching() selected from them, float64 .npy files."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from delta_graph_slam_amd.loop_detector import KeyFrame, Loop
+    rec = np.zeros((3, 20))
+    rec[:, 0] = np.arange(3)
+    rec[:, 1] = [1.0, 1.0, 0.0]
+    rec[:, 2] = [0.5, 0.25, 0.1]                      # candidate 2 has the lowest score but did not converge
+    rec[:, 4:20] = np.eye(4).reshape(16)
+    rec[1, 7] = 2.5
+    rel = rec[1, 4:20].reshape(4, 4).astype(np.float32)
+    kf = KeyFrame(cloud=None, estimate=np.eye(3))
+    bench.dump_outputs(str(tmp_path / "a"), rec, Loop(kf, kf, rel, np.eye(3, dtype=np.float32), 0.25))
+    assert np.array_equal(np.load(tmp_path / "a" / "records.npy"), rec)
+    assert np.load(tmp_path / "a" / "loop_candidate_score.npy").tolist() == [1.0, 0.25]
+    T = np.load(tmp_path / "a" / "loop_relative_pose.npy")
+    assert T.dtype == np.float64 and T[0, 3] == 2.5
+    bench.dump_outputs(str(tmp_path / "b"), rec, None)
+    none = np.load(tmp_path / "b" / "loop_candidate_score.npy")
+    assert none[0] == -1.0 and np.isnan(none[1]) and np.isnan(np.load(tmp_path / "b" / "loop_relative_pose.npy")).all()
