@@ -356,6 +356,10 @@ __device__ __forceinline__ float det_expf(float xf) {
 // std::exp(float) as glibc >= 2.27 computes it on an FMA-capable x86-64 (sysdeps/ieee754/flt-32/e_expf.c: x N / ln2 = k + r, N = 32, a table of
 // 2^(i/32), a cubic in r, all in double, one rounding to float): the exponential of upstream's updateDerivatives bit for bit -- the CPU checker
 // carries the same sequence and compares IT with its libm on every float in [-104, 0].  `tab`: the 32 table words (kGlibcExp2fTab, or a copy in LDS).
+// C1_AT_USE: C1 made by two v_mov_b32 at its use (a volatile asm statement the optimiser cannot hoist).  Hoisted out of the upstream-order item loop
+// (ndt_strict.h) it is a register pair the allocator spills at 256 VGPRs: a scratch reload per item, whose vmcnt(0) would also retire the loop's
+// LDS-DMA of the next round's records ~80 instructions after their issue.  Same value, same operations.
+template <bool C1_AT_USE = false>
 __device__ __forceinline__ float glibc_expf_dev(float xf, const unsigned long long* __restrict__ tab) {
 #pragma clang fp contract(off)
   if (xf != xf) return xf;
@@ -370,7 +374,14 @@ __device__ __forceinline__ float glibc_expf_dev(float xf, const unsigned long lo
   kd -= kShift;
   const double r = __builtin_fma(kInvLn2N, xd, -kd);
   const double s = __longlong_as_double((long long)(tab[ki & 31ull] + (ki << 47)));
-  const double z = __builtin_fma(C0, r, C1);
+  double c1 = C1;
+  if (C1_AT_USE) {
+    static_assert(C1 == 0x1.ebfce50fac4f3p-13, "the literal below");
+    unsigned lo, hi;
+    asm volatile("v_mov_b32 %0, 0x50fac4f3\n\tv_mov_b32 %1, 0x3f2ebfce" : "=v"(lo), "=v"(hi));
+    c1 = __hiloint2double((int)hi, (int)lo);
+  }
+  const double z = __builtin_fma(C0, r, c1);
   const double r2 = r * r;
   double y = __builtin_fma(C2, r, 1.0);
   y = __builtin_fma(z, r2, y);

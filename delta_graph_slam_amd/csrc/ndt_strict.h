@@ -249,13 +249,13 @@ __device__ __forceinline__ void strict_item_back(const float (&xj)[8], const Str
 }
 
 // One function, straight line (the front / back halves above are the same operations cut in two for the hand-pipelined A/B build).
+// w: the voxel's record, loaded by the caller (from L2, or from the item loop's LDS ring).
 template <bool NEED_H, bool GLIBC_ONLY = false>
-__device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&xj)[8], const float (&xh)[15], const VoxelStrictRec* __restrict__ rec,
+__device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&xj)[8], const float (&xh)[15], const StrictRecWords& w,
                                             const double gauss_d1, const float gd2, double (&acc)[kStrictAccum], const unsigned long long* __restrict__ exptab) {
   const float pg13 = xj[0], pg23 = xj[1];
   const float pg4[3] = {xj[2], xj[3], xj[4]}, pg5[3] = {xj[5], xj[6], xj[7]};
-  const float4* __restrict__ r4 = reinterpret_cast<const float4*>(rec);
-  const float4 ra = r4[0], rb = r4[1], rc = r4[2], rd = r4[3];
+  const float4 ra = w.a, rb = w.b, rc = w.c, rd = w.d;
   const double m0 = __hiloint2double(__float_as_int(ra.y), __float_as_int(ra.x)), m1 = __hiloint2double(__float_as_int(ra.w), __float_as_int(ra.z)),
                m2 = __hiloint2double(__float_as_int(rb.y), __float_as_int(rb.x));
   const float q0 = (float)((double)xt[0] - m0), q1 = (float)((double)xt[1] - m1), q2 = (float)((double)xt[2] - m2);
@@ -268,7 +268,7 @@ __device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&
                      // against 5.38 with glibc's expf (same box, two runs each): the exact libm exponential costs nothing
   float e = det_expf(e_arg);
 #else
-  float e = (GLIBC_ONLY || exptab) ? glibc_expf_dev(e_arg, exptab) : det_expf(e_arg);   // std::exp(float) as glibc computes it / rounds 1-3's polynomial
+  float e = (GLIBC_ONLY || exptab) ? glibc_expf_dev<GLIBC_ONLY>(e_arg, exptab) : det_expf(e_arg);   // std::exp(float) as glibc computes it / rounds 1-3's polynomial
 #endif
   const float score_inc = (float)(-gauss_d1 * (double)e);
   e = gd2 * e;
@@ -319,6 +319,11 @@ __device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&
     }
   }
   acc[0] += (double)score_inc;
+}
+template <bool NEED_H, bool GLIBC_ONLY = false>
+__device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&xj)[8], const float (&xh)[15], const VoxelStrictRec* __restrict__ rec,
+                                            const double gauss_d1, const float gd2, double (&acc)[kStrictAccum], const unsigned long long* __restrict__ exptab) {
+  strict_item<NEED_H, GLIBC_ONLY>(xt, xj, xh, strict_load_rec(rec), gauss_d1, gd2, acc, exptab);
 }
 
 // the point's products with the float angle tables (computePointDerivatives).  As in the default order's kernel: rows 5..7 of the first
@@ -722,33 +727,94 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict_kernel(const float4* con
 // WITH_HD = false: the kernel serves the float kinds only (64-point tiles, a third of the LDS, no double tables in registers: three waves
 // per SIMD instead of two); the pairs waiting for kind 2 are served by ndt_strict_kernel<SEARCH, FUSED, HD = true> as the round's second launch.
 
+// The float point table: 20 fields per point, field-major ([field][slot]): xt[3], xj[8], xh[6..14].  xh[0..5] are xj entries or their
+// negations (strict_point_tables: -xj1, xj0, -xj4, xj3, -xj7, xj6) and are rebuilt here from the same bits -- negation is exact, so
+// strict_item sees the 15 values it saw when all 26 fields were stored.
+constexpr int kStrictFields = 20;
+template <bool NEED_H, int PTS>
+__device__ __forceinline__ void strict_table_read(const float* __restrict__ tf, const int slot, float (&xt)[3], float (&xj)[8], float (&xh)[15]) {
+#pragma unroll
+  for (int f = 0; f < 3; f++) xt[f] = tf[f * PTS + slot];
+#pragma unroll
+  for (int f = 0; f < 8; f++) xj[f] = tf[(3 + f) * PTS + slot];
+  if (NEED_H) {
+    xh[0] = -xj[1]; xh[1] = xj[0]; xh[2] = -xj[4]; xh[3] = xj[3]; xh[4] = -xj[7]; xh[5] = xj[6];
+#pragma unroll
+    for (int f = 6; f < 15; f++) xh[f] = tf[(5 + f) * PTS + slot];
+  } else {
+#pragma unroll
+    for (int f = 0; f < 15; f++) xh[f] = 0.f;
+  }
+}
+
+// The voxel records of one round of items go through a per-wave LDS ring of four 1-KiB words ([4][64] float4, inside the wave's table region):
+// word k of lane l's record at ring[k * 64 + l].  Four 16-byte LDS-DMA loads (global_load_lds_dwordx4): the source address is per lane, the
+// destination wave-uniform base + 16 * lane, and no VGPR holds the data in flight.
+constexpr int kStrictRingBytes = 4 * 64 * 16;
+__device__ __forceinline__ void strict_rec_dma(float4* ring, const VoxelStrictRec* __restrict__ rec) {
+  const float4* src = reinterpret_cast<const float4*>(rec);
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + k), (__attribute__((address_space(3))) void*)(ring + k * 64), 16, 0, 0);
+}
+
 // The float items of one tile, 64 per round, lane <-> item.
+// DGS_STRICT_ITEMS = 3 (the default): the records one round ahead through the LDS ring.  At the top of round r the wave retires round r's DMA
+// (vmcnt(0)), reads its records and the queue entries of rounds r and r + 1 from LDS, waits for those reads (lgkmcnt(0): the ring is free again),
+// issues round r + 1's DMA and runs round r's items while it is in flight.  Same items on the same lanes, same operations: bit-identical to the
+// plain loop.  RING = false (the fixed-slices instantiations, whose per-slice column sums leave no LDS for the ring at two workgroups per CU):
+// the plain loop.
+// A/B build `make ab AB=-DDGS_STRICT_ITEMS=2`: the plain loop, the record loaded from L2 where it is used.
 // A/B build `make ab AB=-DDGS_STRICT_ITEMS=1`: the loop software-pipelined by hand -- the NEXT round's queue entry read at the top, its voxel record
 // (four 16-byte gathers from L2) requested between the two halves of the current item, the 36-entry Hessian block behind covering the latency.
 // Measured on the bench step (same box, two runs each): 5.65 ms against 5.48 for the plain loop -- the 15 more live registers turn 4 spilled
 // registers into 29 in a kernel that sits at 256; the wave next door on the SIMD was hiding most of that latency already.  Not the default.
-template <bool NEED_H, int PTS>
-__device__ __forceinline__ void strict_items_float(const float* __restrict__ tf, const unsigned* __restrict__ queue, const int qn, const int lane,
+#ifndef DGS_STRICT_ITEMS
+#define DGS_STRICT_ITEMS 3
+#endif
+template <bool NEED_H, int PTS, bool RING>
+__device__ __forceinline__ void strict_items_float(const float* __restrict__ tf, float4* ring, const unsigned* __restrict__ queue, const int qn, const int lane,
                                                    const VoxelStrictRec* __restrict__ vs, const double gauss_d1, const float gd2, double (&acc)[kStrictAccum],
                                                    const unsigned long long* __restrict__ exptab) {
-#if !defined(DGS_STRICT_ITEMS) || DGS_STRICT_ITEMS != 1   // the plain loop: the record loaded where it is used
+#if DGS_STRICT_ITEMS == 3
+  if (RING) {
+    if (lane < qn) strict_rec_dma(ring, vs + (queue[lane] & 0x1FFFFFFu));
+#pragma unroll 1
+    for (int h = 0; h < qn; h += 64) {
+      const int idx = h + lane, idx_n = idx + 64;
+      __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this round's records are in the ring
+      StrictRecWords w;
+      unsigned entry = 0, entry_n = 0;
+      if (idx < qn) {
+        entry = queue[idx];
+        w = StrictRecWords{ring[lane], ring[64 + lane], ring[128 + lane], ring[192 + lane]};
+      }
+      if (idx_n < qn) entry_n = queue[idx_n];
+      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the ring has been read before the next round's DMA overwrites it
+      if (idx_n < qn) strict_rec_dma(ring, vs + (entry_n & 0x1FFFFFFu));
+      if (idx < qn) {
+        float xt[3], xj[8], xh[15];
+        strict_table_read<NEED_H, PTS>(tf, (int)(entry >> 25), xt, xj, xh);
+        strict_item<NEED_H, true>(xt, xj, xh, w, gauss_d1, gd2, acc, exptab);
+      }
+    }
+    return;
+  }
+#endif
+#if DGS_STRICT_ITEMS != 1   // the plain loop: the record loaded where it is used
+  (void)ring;
 #pragma unroll 1
   for (int h = 0; h < qn; h += 64) {
     const int idx = h + lane;
     if (idx < qn) {
       const unsigned entry = queue[idx];
-      const int slot = (int)(entry >> 25);
       float xt[3], xj[8], xh[15];
-#pragma unroll
-      for (int f = 0; f < 3; f++) xt[f] = tf[f * PTS + slot];
-#pragma unroll
-      for (int f = 0; f < 8; f++) xj[f] = tf[(3 + f) * PTS + slot];
-#pragma unroll
-      for (int f = 0; f < 15; f++) xh[f] = NEED_H ? tf[(11 + f) * PTS + slot] : 0.f;
+      strict_table_read<NEED_H, PTS>(tf, (int)(entry >> 25), xt, xj, xh);
       strict_item<NEED_H, true>(xt, xj, xh, vs + (entry & 0x1FFFFFFu), gauss_d1, gd2, acc, exptab);
     }
   }
 #else
+  (void)ring;
   bool have = lane < qn;
   unsigned entry = have ? queue[lane] : 0u;
   StrictRecWords w = strict_load_rec(vs + (entry & 0x1FFFFFFu));   // (entry 0: voxel 0, a valid address; its words are not used)
@@ -761,19 +827,8 @@ __device__ __forceinline__ void strict_items_float(const float* __restrict__ tf,
     StrictMid m;
     bool alive = false;
     if (have) {
-      const int slot = (int)(entry >> 25);
       float xt[3], xh[15];
-#pragma unroll
-      for (int f = 0; f < 3; f++) xt[f] = tf[f * PTS + slot];
-#pragma unroll
-      for (int f = 0; f < 8; f++) xj[f] = tf[(3 + f) * PTS + slot];
-      if (NEED_H) {
-#pragma unroll
-        for (int f = 0; f < 15; f++) xh[f] = tf[(11 + f) * PTS + slot];
-      } else {
-#pragma unroll
-        for (int f = 0; f < 15; f++) xh[f] = 0.f;
-      }
+      strict_table_read<NEED_H, PTS>(tf, (int)(entry >> 25), xt, xj, xh);
       alive = strict_item_front<NEED_H, true>(xt, xj, xh, w, gauss_d1, gd2, acc, m, exptab);
     }
     StrictRecWords wn = w;
@@ -786,7 +841,7 @@ __device__ __forceinline__ void strict_items_float(const float* __restrict__ tf,
 #endif
 }
 
-template <int SEARCH, bool WITH_HD>
+template <int SEARCH, bool WITH_HD, bool RING>
 struct StrictTile {
   static constexpr int NB = Offsets<SEARCH>::N;
 #ifndef DGS_STRICT_PTS_FLOAT_ONLY
@@ -794,8 +849,9 @@ struct StrictTile {
 #endif
   static constexpr int PTS = (NB <= 7) ? (WITH_HD ? 128 : DGS_STRICT_PTS_FLOAT_ONLY) : 64;   // points per wave and tile (float kinds)
   static constexpr int PTS_HD = 64;                  // double pass: 23 doubles + 3 floats per point
-  static constexpr int kFields = 26;                 // xt[3], xj[8], xh[15]
-  static constexpr int kTableBytes = (!WITH_HD || kFields * PTS * 4 > (23 * 8 + 3 * 4) * PTS_HD) ? kFields * PTS * 4 : (23 * 8 + 3 * 4) * PTS_HD;
+  static constexpr int kRingOffset = kStrictFields * PTS * 4;   // float kinds: the point table, then the record ring
+  static constexpr int kFloatBytes = kRingOffset + (RING ? kStrictRingBytes : 0);
+  static constexpr int kTableBytes = (!WITH_HD || kFloatBytes > (23 * 8 + 3 * 4) * PTS_HD) ? kFloatBytes : (23 * 8 + 3 * 4) * PTS_HD;
   static constexpr int kQueue = PTS * NB;            // items of a tile at most
 };
 
@@ -821,7 +877,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
                                                                const double gauss_d1, const double gauss_d2, const int leaf_pow2, double* __restrict__ partials,
                                                                const int n_pairs, const int cap_blocks, int* __restrict__ pair_blocks, const NdtConsts consts,
                                                                int* __restrict__ done_flags, const int launch, const int solve_min_active, const int speculate) {
-  using TL = StrictTile<SEARCH, WITH_HD>;
+  using TL = StrictTile<SEARCH, WITH_HD, !FIXED>;
   constexpr int NB = TL::NB;
   int pair, slice, blocks_per_pair;
   int n_active = 0;
@@ -870,7 +926,8 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   const unsigned long long* __restrict__ exptab = s_exp2f;   // this kernel serves consts.exp_libm = 1 only (strict_kernel_version, ndt_align.hip)
   const unsigned long long* __restrict__ exptab_d = kGlibcExpTab;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* tf = reinterpret_cast<float*>(s_tab[wave]);            // float kinds: [26][PTS]
+  float* tf = reinterpret_cast<float*>(s_tab[wave]);            // float kinds: [20][PTS], then the record ring
+  float4* ring = reinterpret_cast<float4*>(s_tab[wave] + TL::kRingOffset);
   double* td = reinterpret_cast<double*>(s_tab[wave]);          // double pass: [23][PTS_HD] doubles, then [3][PTS_HD] floats
   float* tdx = reinterpret_cast<float*>(s_tab[wave] + 23 * 8 * TL::PTS_HD);
   unsigned* queue = s_queue[wave];
@@ -948,7 +1005,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
             for (int f = 0; f < 8; f++) tf[(3 + f) * TL::PTS + slot] = xj[f];
             if (kind == 1) {
 #pragma unroll
-              for (int f = 0; f < 15; f++) tf[(11 + f) * TL::PTS + slot] = xh[f];
+              for (int f = 6; f < 15; f++) tf[(5 + f) * TL::PTS + slot] = xh[f];   // xh[0..5]: rebuilt from xj (strict_table_read)
             }
           }
         }
@@ -964,16 +1021,13 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes have landed
     __builtin_amdgcn_wave_barrier();
-    // ---- the items, 64 at a time.  The float kinds run strict_items_float, a loop specialised per kind (the default, DGS_STRICT_ITEMS = 2); the
+    // ---- the items, 64 at a time.  The float kinds run strict_items_float, a loop specialised per kind (DGS_STRICT_ITEMS = 1, 2, 3); the
     // loop below serves the double pass -- and, in the A/B build DGS_STRICT_ITEMS = 0, all three kinds with the kind tested per round: that form
     // has 7 spilled registers instead of 25 and is 1 % SLOWER on the bench step (5.35 against 5.27-5.30 ms, same box, two runs each).
-#ifndef DGS_STRICT_ITEMS
-#define DGS_STRICT_ITEMS 2
-#endif
 #if DGS_STRICT_ITEMS != 0
     if (!(WITH_HD && kind == 2)) {
-      if (kind == 1) strict_items_float<true, TL::PTS>(tf, queue, qn, lane, vs, gauss_d1, gd2, acc, exptab);
-      else strict_items_float<false, TL::PTS>(tf, queue, qn, lane, vs, gauss_d1, gd2, acc, exptab);
+      if (kind == 1) strict_items_float<true, TL::PTS, !FIXED>(tf, ring, queue, qn, lane, vs, gauss_d1, gd2, acc, exptab);
+      else strict_items_float<false, TL::PTS, !FIXED>(tf, ring, queue, qn, lane, vs, gauss_d1, gd2, acc, exptab);
       qn = 0;
     }
 #endif
@@ -995,17 +1049,11 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
           (void)strict_item_hd<false>(xt, xj, xh, vtab + (size_t)vid * 12, gauss_d1, gauss_d2, acc, nullptr, 0, exptab_d);
         } else {
           float xt[3], xj[8], xh[15];
-#pragma unroll
-          for (int f = 0; f < 3; f++) xt[f] = tf[f * TL::PTS + slot];
-#pragma unroll
-          for (int f = 0; f < 8; f++) xj[f] = tf[(3 + f) * TL::PTS + slot];
           if (kind == 1) {
-#pragma unroll
-            for (int f = 0; f < 15; f++) xh[f] = tf[(11 + f) * TL::PTS + slot];
+            strict_table_read<true, TL::PTS>(tf, slot, xt, xj, xh);
             strict_item<true, true>(xt, xj, xh, vs + vid, gauss_d1, gd2, acc, exptab);
           } else {
-#pragma unroll
-            for (int f = 0; f < 15; f++) xh[f] = 0.f;
+            strict_table_read<false, TL::PTS>(tf, slot, xt, xj, xh);
             strict_item<false, true>(xt, xj, xh, vs + vid, gauss_d1, gd2, acc, exptab);
           }
         }
