@@ -211,7 +211,9 @@ int NdtCpu::neighbours(const float xt[3], const Leaf** out) const {
           }
       break;
     case NDT_KDTREE: {
-      const float r2 = static_cast<float>(prm.resolution * prm.resolution);
+      // upstream's resolution_ is a float: radiusSearch squares it in double and rounds to float -- the float product of the leaf size
+      // (exact in double), which is not float(resolution^2) at a non-power-of-two resolution (0.7: 0x3EFAE147 against 0x3EFAE148)
+      const float r2 = static_cast<float>(static_cast<double>(leaf_size[0]) * static_cast<double>(leaf_size[0]));
       for (int dx = -1; dx <= 1; dx++)
         for (int dy = -1; dy <= 1; dy++)
           for (int dz = -1; dz <= 1; dz++) {
