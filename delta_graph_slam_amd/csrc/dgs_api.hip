@@ -282,13 +282,43 @@ int dgs_params_init(dgs_params* p, int32_t method) {
   p->gicp_lm_max_iterations = 10;
   p->vgicp_search_method = DGS_VGICP_DIRECT1;
   p->vgicp_resolution = 1.0;
-  if (method != DGS_METHOD_NDT && method != DGS_METHOD_GICP && method != DGS_METHOD_VGICP) return DGS_ERR_INVALID_ARGUMENT;
+  if (method != DGS_METHOD_NDT && method != DGS_METHOD_GICP && method != DGS_METHOD_VGICP && method != DGS_METHOD_ICP) return DGS_ERR_INVALID_ARGUMENT;
   return DGS_OK;
+}
+
+int dgs_icp_options_init(dgs_icp_options* o) {
+  if (!o) return DGS_ERR_INVALID_ARGUMENT;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = sizeof(dgs_icp_options);
+  o->use_reciprocal_correspondences = 0;
+  o->euclidean_fitness_epsilon = -DBL_MAX;   // pcl::Registration's default: the relative MSE test never fires
+  o->rotation_epsilon = 0.0;                 // 0: rotation threshold 1 - transformation_epsilon
+  return DGS_OK;
+}
+
+int dgs_set_icp_options(dgs_handle* h, const dgs_icp_options* o) {
+  if (!h || !o || o->struct_size != sizeof(dgs_icp_options)) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (h->prm.method != DGS_METHOD_ICP) { h->err = "dgs_set_icp_options: not an ICP handle"; return DGS_ERR_UNSUPPORTED; }
+  h->icp_opt = *o;
+  return DGS_OK;
+}
+
+int dgs_icp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, double* mse, int32_t* n_corr, int32_t capacity, int32_t* len) {
+  if (!h || !len || pair < 0 || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  if (h->prm.method != DGS_METHOD_ICP) return DGS_ERR_UNSUPPORTED;
+  int n = 0;
+  int rc = icp_trajectory(h, pair, T16s, mse, n_corr, capacity, &n);
+  *len = n;
+  return rc;
 }
 
 int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (!params || !out || params->struct_size != sizeof(dgs_params)) return DGS_ERR_INVALID_ARGUMENT;
-  if (params->method != DGS_METHOD_NDT && params->method != DGS_METHOD_GICP && params->method != DGS_METHOD_VGICP) return DGS_ERR_INVALID_ARGUMENT;
+  if (params->method != DGS_METHOD_NDT && params->method != DGS_METHOD_GICP && params->method != DGS_METHOD_VGICP && params->method != DGS_METHOD_ICP)
+    return DGS_ERR_INVALID_ARGUMENT;
   if (params->method == DGS_METHOD_VGICP && (!(params->vgicp_resolution > 0) || params->vgicp_search_method < 0 || params->vgicp_search_method > DGS_VGICP_DIRECT27))
     return DGS_ERR_INVALID_ARGUMENT;
   if (!(params->ndt_resolution > 0) || params->maximum_iterations < 0 || params->gicp_correspondence_randomness < 1) return DGS_ERR_INVALID_ARGUMENT;
@@ -338,6 +368,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (const char* e = std::getenv("DGS_NN_GRID_FACTOR")) h->grid_spacing_factor = std::max(0.5f, (float)std::atof(e));
   std::memset(h->final_T, 0, sizeof(h->final_T));
   h->final_T[0] = h->final_T[5] = h->final_T[10] = h->final_T[15] = 1.f;
+  (void)dgs_icp_options_init(&h->icp_opt);
   *out = h;
   return DGS_OK;
 }
@@ -367,6 +398,7 @@ void dgs_destroy(dgs_handle* h) {
   }
   h->batch_slab.release();
   for (auto& c : h->batch_clouds) c.release();
+  icp_release(h);
   h->gitems.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
   h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();
@@ -534,6 +566,8 @@ int dgs_align(dgs_handle* h, const float* guess16, dgs_result* out, float* align
     const float4* src = h->src->pts.ptr;
     const int n = (int)h->ns;
     rc = ndt_align_pairs(h, 1, &src, &n, guess16, out);
+  } else if (h->prm.method == DGS_METHOD_ICP) {
+    rc = icp_align(h, guess16, out);
   } else {
     rc = gicp_align(h, guess16, out);
   }
@@ -641,7 +675,7 @@ int dgs_nn_fitness_distances(dgs_handle* h, const float* queries, int64_t m, int
   return rc;
 }
 
-// FAST_GICP over a batch of sources (loop_detector.hpp:137-156): batched align, then one fitness launch for all candidates
+// FAST_GICP / FAST_VGICP / ICP over a batch of sources (loop_detector.hpp:137-156): batched align, then one fitness launch for all candidates
 static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* guesses16, int compute_fitness, double fitness_max_range,
                       dgs_result* results) {
   struct KdScope { dgs_handle* h; ~KdScope() { h->batch_kd = false; } } kd_scope{h};
@@ -650,7 +684,8 @@ static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* 
   // 12: 2.08 / 2.16, 32: 3.30 / 4.23)
   static const int kd_min = std::getenv("DGS_GICP_KD_MIN_CANDIDATES") ? std::atoi(std::getenv("DGS_GICP_KD_MIN_CANDIDATES")) : 10;
   h->batch_kd = h->nn_kd && n >= kd_min;
-  int rc = gicp_align_batch(h, n, cs, guesses16, results);
+  const bool icp = h->prm.method == DGS_METHOD_ICP;
+  int rc = icp ? icp_align_batch(h, n, cs, guesses16, results) : gicp_align_batch(h, n, cs, guesses16, results);
   if (rc == DGS_OK && compute_fitness) {
     DGS_HIP_TRY(h, h->src_ptrs.reserve(n));
     DGS_HIP_TRY(h, h->src_sizes.reserve(n));
@@ -664,7 +699,7 @@ static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* 
     std::vector<double> sums(n);
     std::vector<int64_t> cnts(n), inl(n);
     size_t stride = 0;
-    const float* dT = gicp_final_transforms(h, &stride);
+    const float* dT = icp ? icp_final_transforms(h, &stride) : gicp_final_transforms(h, &stride);
     rc = nn_fitness_batch(h, n, h->src_ptrs.ptr, h->src_sizes.ptr, max_n, dT, stride, fitness_max_range, 0.0, sums.data(), cnts.data(), inl.data());
     if (rc == DGS_OK)
       for (int i = 0; i < n; i++) results[i].fitness = cnts[i] > 0 ? sums[i] / (double)cnts[i] : DBL_MAX;
@@ -689,7 +724,7 @@ int dgs_align_batch(dgs_handle* h, int32_t n, const float* const* sources, const
     return DGS_ERR_NO_TARGET;
   }
   if (h->prm.method != DGS_METHOD_NDT) {
-    // FAST_GICP: every candidate needs its own index + covariances; they live in per-slot CloudStates the handle re-uses
+    // FAST_GICP / ICP: every candidate needs its own index (+ covariances: GICP); they live in per-slot CloudStates the handle re-uses
     if (h->batch_clouds.size() < (size_t)n) h->batch_clouds.resize(n);
     std::vector<CloudState*> cs(n);
     for (int i = 0; i < n; i++) {
@@ -790,7 +825,7 @@ int dgs_align_batch_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* sources, 
     for (int i = 0; i < n; i++) { ptrs[i] = reinterpret_cast<const float*>(sources[i]->st.pts.ptr); sizes[i] = sources[i]->st.n; }
     return dgs_align_batch(h, n, ptrs.data(), sizes.data(), 1, guesses16, compute_fitness, fitness_max_range, results);
   }
-  // FAST_GICP: one batched LM loop; each resident cloud keeps its index and covariances across calls
+  // FAST_GICP / ICP: one batched loop; each resident cloud keeps its index (and GICP covariances) across calls
   for (int i = 0; i < n; i++) fail_result(&results[i], guesses16 ? guesses16 + 16 * i : nullptr, DGS_OK);
   if (!h->have_target || h->nt == 0) {
     for (int i = 0; i < n; i++) results[i].status = DGS_ERR_NO_TARGET;

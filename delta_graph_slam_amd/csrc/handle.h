@@ -17,6 +17,9 @@ struct Profiler {
   int64_t launches[DGS_K_COUNT] = {0};
 };
 
+struct IcpPair;   // icp.hip
+struct IcpItem;
+
 // Exact-NN index over a point cloud (nn_bvh.hip): Hilbert-sorted points, implicit complete 8-ary tree of AABBs.
 struct Bvh {
   int64_t n = 0;            // points
@@ -81,12 +84,15 @@ struct CloudState {
   DevBuf<double> cov;  // 6 doubles per point: xx, xy, xz, yy, yz, zz
   bool cov_valid = false;
   int cov_k = 0, cov_reg = -1;
-  void invalidate() { bvh.valid = false; cov_valid = false; }
+  Bvh walk;            // ICP: a Hilbert-ordered index kept for the correspondence walk when `bvh` is k-d ordered (the cloud was a batch target)
+  void invalidate() { bvh.valid = false; cov_valid = false; walk.valid = false; }
   void release() {
     pts.release(); cov.release();
-    bvh.sorted.release(); bvh.node_lo.release(); bvh.node_hi.release();
-    bvh.keys.release(); bvh.keys_alt.release(); bvh.vals.release(); bvh.vals_alt.release();
-    bvh.kd_bbox.release();
+    for (Bvh* b : {&bvh, &walk}) {
+      b->sorted.release(); b->node_lo.release(); b->node_hi.release();
+      b->keys.release(); b->keys_alt.release(); b->vals.release(); b->vals_alt.release();
+      b->kd_bbox.release();
+    }
     n = 0;
     invalidate();
   }
@@ -255,6 +261,21 @@ struct dgs_handle {
   std::vector<dgs::CloudState> batch_clouds;   // index + covariances of sources handed to dgs_align_batch as raw arrays
   dgs::GicpConsts gconsts{};
 
+  // ---- ICP (pcl::IterativeClosestPoint, icp.hip): the target's exact-NN index only -- no covariances, for the target or any source
+  dgs_icp_options icp_opt{};                   // dgs_set_icp_options; read at every align
+  dgs::DevBuf<dgs::IcpPair> ipairs;
+  dgs::DevBuf<dgs::IcpItem> iitems;
+  dgs::DevBuf<float4> icp_w;                   // working copies (input_transformed) of every source of the batch
+  dgs::DevBuf<int> icp_blk_pair;
+  dgs::DevBuf<int> icp_origin;                 // index of the target's first finite point (the origin of the moment sums)               // workgroup -> pair of the iteration launch (fixed slices per pair)
+  dgs::DevBuf<double> icp_rows;                // one partial row per (pair, slice)
+  dgs::DevBuf<float> icp_traj_T;               // per pair and iteration: T_k (column-major 16 floats)
+  dgs::DevBuf<double> icp_traj_mse;
+  dgs::DevBuf<int> icp_traj_n;
+  std::vector<dgs::Bvh> icp_w_bvh;             // reciprocal mode: index over each working copy, rebuilt every round
+  std::vector<int> icp_last_iters;             // iterations per pair of the last align / batch (dgs_icp_get_trajectory)
+  int icp_traj_cap = 0;
+
   dgs::Profiler prof;
 };
 
@@ -323,6 +344,12 @@ int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float*
 const float* gicp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int gicp_covariances(dgs_handle* h, int which, double* host_out6, int64_t n);
 int gicp_probe(dgs_handle* h, const double* T16_rowmajor, int error_only, double* err, double* H36, double* b6);
+// icp.hip
+int icp_align(dgs_handle* h, const float* guess16, dgs_result* out);
+int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);
+const float* icp_final_transforms(dgs_handle* h, size_t* stride_bytes);
+int icp_trajectory(dgs_handle* h, int pair, float* T16s, double* mse, int32_t* n_corr, int capacity, int* len);
+void icp_release(dgs_handle* h);
 // transform
 int transform_cloud(dgs_handle* h, const float4* in, float4* out, int64_t n, const float* T16_colmajor_host);
 // dgs_api.hip: a copy of `src` (points only) on dst_h's device, device to device (peer copy over xGMI when the devices differ)

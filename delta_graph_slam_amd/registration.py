@@ -66,6 +66,26 @@ _RESULT_DTYPE = np.dtype([("T", np.float32, (16,)), ("converged", np.int32), ("i
 assert _RESULT_DTYPE.itemsize == C.sizeof(L.Result)
 
 
+_ICP_KEYS = {"icp_use_reciprocal_correspondences": "use_reciprocal_correspondences",
+             "icp_euclidean_fitness_epsilon": "euclidean_fitness_epsilon", "icp_rotation_epsilon": "rotation_epsilon"}
+
+
+def _icp_options(lib, method, params):
+    """Split the icp_* keywords off `params` into a dgs_icp_options (None for a method other than ICP_HIP)."""
+    picked = {k: params.pop(k) for k in list(params) if k in _ICP_KEYS}
+    if method != "ICP_HIP":
+        if picked:
+            raise TypeError(f"{sorted(picked)} apply to ICP_HIP only")
+        return None
+    o = L.IcpOptions()
+    rc = lib.dgs_icp_options_init(C.byref(o))
+    if rc:
+        raise DgsError(rc, "dgs_icp_options_init")
+    for k, v in picked.items():
+        setattr(o, _ICP_KEYS[k], int(bool(v)) if k == "icp_use_reciprocal_correspondences" else float(v))
+    return o
+
+
 class DeviceCloud:
     """A cloud resident in HBM (dgs_cloud): KeyFrame::cloud of the loop detector kept on the device together with its
     NN index / GICP covariances, so a keyframe that is a loop candidate tick after tick is uploaded and indexed once."""
@@ -104,10 +124,12 @@ class Registration:
             self._converged, self._final, self.last_result, self._keep = False, np.eye(4, dtype=np.float32), None, {}
             return
         exact = {"NDT_OMP": L.METHOD_NDT, "NDT_HIP": L.METHOD_NDT, "FAST_GICP": L.METHOD_GICP, "FAST_GICP_HIP": L.METHOD_GICP,
-                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP}
+                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP}
         if method not in exact:   # pcl::ICP / GICP / NDT, pclomp::GICP, FAST_VGICP_CUDA are other algorithms: not served here
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends (served: {sorted(exact)})")
         m = exact[method]
+        params = dict(params)
+        icp_opt = _icp_options(lib, method, params)
         p = L.Params()
         rc = lib.dgs_params_init(C.byref(p), m)
         if rc:
@@ -124,6 +146,9 @@ class Registration:
         rc = lib.dgs_create(C.byref(p), C.byref(self._h))
         if rc:
             raise DgsError(rc, "dgs_create failed (this package has no CPU fallback): " + (lib.dgs_last_error(None) or b"").decode())
+        self.icp_options = icp_opt
+        if icp_opt is not None:
+            self._check(lib.dgs_set_icp_options(self._h, C.byref(icp_opt)))
         self._converged = False
         self._final = np.eye(4, dtype=np.float32)
         self.last_result = None
@@ -337,6 +362,34 @@ class Registration:
         out[:, 4:20] = a["T"].reshape(n, 4, 4).transpose(0, 2, 1).reshape(n, 16)   # column-major -> row-major
         return out
 
+    # -- pcl::IterativeClosestPoint setters (ICP_HIP) ----------------------------------------------------------
+    def _set_icp(self, field, value):
+        if self.method != "ICP_HIP":
+            raise NotImplementedError(f"{field} is an ICP_HIP setting")
+        setattr(self.icp_options, field, value)
+        self._check(self._lib.dgs_set_icp_options(self._h, C.byref(self.icp_options)))
+
+    def setUseReciprocalCorrespondences(self, on: bool):
+        self._set_icp("use_reciprocal_correspondences", 1 if on else 0)
+
+    def setEuclideanFitnessEpsilon(self, eps: float):
+        self._set_icp("euclidean_fitness_epsilon", float(eps))
+
+    def setTransformationRotationEpsilon(self, eps: float):
+        self._set_icp("rotation_epsilon", float(eps))
+
+    def icp_trajectory(self, pair: int = 0):
+        """ICP_HIP test hook: per iteration of pair `pair` of the last align / batch -> (T_k [m,4,4] float32, mse [m], kept pairs [m])."""
+        cap = max(1, int(self.params.maximum_iterations)) if self.params is not None else 1024
+        T = np.zeros((cap, 16), np.float32)
+        mse = np.zeros(cap, np.float64)
+        nc = np.zeros(cap, np.int32)
+        ln = C.c_int32(0)
+        self._check(self._lib.dgs_icp_get_trajectory(self._h, pair, T.ctypes.data_as(C.c_void_p), mse.ctypes.data_as(C.c_void_p),
+                                                     nc.ctypes.data_as(C.c_void_p), cap, C.byref(ln)))
+        m = min(ln.value, cap)
+        return T[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy(), mse[:m].copy(), nc[:m].copy()
+
     # -- measurement / test hooks ---------------------------------------------------------------------------
     def profile_enable(self, on: bool = True):
         self._check(self._lib.dgs_profile_enable(self._h, 1 if on else 0))
@@ -473,9 +526,11 @@ class RegistrationGroup:
         lib = L.load()
         self._lib = lib
         exact = {"NDT_OMP": L.METHOD_NDT, "NDT_HIP": L.METHOD_NDT, "FAST_GICP": L.METHOD_GICP, "FAST_GICP_HIP": L.METHOD_GICP,
-                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP}
+                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP}
         if method not in exact:
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends")
+        params = dict(params)
+        icp_opt = _icp_options(lib, method, params)
         p = L.Params()
         rc = lib.dgs_params_init(C.byref(p), exact[method])
         if rc:
@@ -491,6 +546,9 @@ class RegistrationGroup:
         rc = lib.dgs_group_create(C.byref(p), dv, len(self.devices), C.byref(self._g))
         if rc:
             raise DgsError(rc, "dgs_group_create failed (this package has no CPU fallback): " + (lib.dgs_last_error(None) or b"").decode())
+        self.icp_options = icp_opt
+        if icp_opt is not None:
+            self._check(lib.dgs_group_set_icp_options(self._g, C.byref(icp_opt)))
         self.best_index = -1
         self.best_score = float("inf")
 
@@ -508,6 +566,22 @@ class RegistrationGroup:
     def _check(self, rc: int):
         if rc:
             raise DgsError(rc, (self._lib.dgs_group_last_error(self._g) or b"").decode())
+
+    # -- pcl::IterativeClosestPoint setters (ICP_HIP), applied to every member ----------------------------------------------
+    def _set_icp(self, field, value):
+        if self.method != "ICP_HIP":
+            raise NotImplementedError(f"{field} is an ICP_HIP setting")
+        setattr(self.icp_options, field, value)
+        self._check(self._lib.dgs_group_set_icp_options(self._g, C.byref(self.icp_options)))
+
+    def setUseReciprocalCorrespondences(self, on: bool):
+        self._set_icp("use_reciprocal_correspondences", 1 if on else 0)
+
+    def setEuclideanFitnessEpsilon(self, eps: float):
+        self._set_icp("euclidean_fitness_epsilon", float(eps))
+
+    def setTransformationRotationEpsilon(self, eps: float):
+        self._set_icp("rotation_epsilon", float(eps))
 
     @property
     def uses_rccl(self) -> bool:
@@ -613,7 +687,7 @@ def select_registration_method(params: dict | None = None, device: int | None = 
     `params` plays the role of the private NodeHandle: keys are the reference's rosparam names
     (registration_method, reg_num_threads, reg_transformation_epsilon, reg_maximum_iterations,
     reg_max_correspondence_distance, reg_correspondence_randomness, reg_resolution, reg_nn_search_method).
-    "NDT_HIP" selects the HIP NDT; "FAST_GICP_HIP" / "FAST_GICP" select GICP (:27-36); "FAST_VGICP_HIP" / "FAST_VGICP" the voxelised
+    "NDT_HIP" selects the HIP NDT; "ICP_HIP" the HIP pcl::IterativeClosestPoint (:59-64, + reg_use_reciprocal_correspondences); "FAST_GICP_HIP" / "FAST_GICP" select GICP (:27-36); "FAST_VGICP_HIP" / "FAST_VGICP" the voxelised
     GICP (:48-56).  Every other name goes through the reference's own chain of tests, in its order: "ICP" (:59-64) and any name
     containing "GICP" (:66-87: pcl::GICP, or pclomp::GICP when it also contains "OMP") are different algorithms -> NotImplementedError;
     what is left is the NDT branch (:88-123): a name without "NDT" warns "unknown registration type ... use NDT" (:89-92), and then
@@ -633,6 +707,10 @@ def select_registration_method(params: dict | None = None, device: int | None = 
     if method in ("FAST_VGICP", "FAST_VGICP_HIP"):      # registrations.cpp:48-56
         return Registration("FAST_VGICP", device=device, vgicp_resolution=float(pr.get("reg_resolution", 1.0)),
                             gicp_correspondence_randomness=int(pr.get("reg_correspondence_randomness", 20)), **common)
+    if method == "ICP_HIP":                             # :59-64 on the GPU: pcl::IterativeClosestPoint (before the "GICP" test below)
+        return Registration("ICP_HIP", device=device,
+                            gicp_max_correspondence_distance=float(pr.get("reg_max_correspondence_distance", 2.5)),
+                            icp_use_reciprocal_correspondences=bool(pr.get("reg_use_reciprocal_correspondences", False)), **common)
     if method == "ICP" or "GICP" in method:             # :59-64, :66-87 (FAST_VGICP_CUDA lands here too when the reference is built without CUDA)
         raise NotImplementedError(f"registration_method {method!r} is served by the reference's own factory branch, not by the HIP back-ends")
     if method != "NDT_HIP":

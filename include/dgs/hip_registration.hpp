@@ -45,8 +45,10 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
 
   explicit HipRegistration(dgs_method method) {
     dgs_params_init(&params_, method);
+    dgs_icp_options_init(&icp_options_);
     this->reg_name_ = (method == DGS_METHOD_GICP) ? "dgs::HipRegistration<FAST_GICP>" : (method == DGS_METHOD_VGICP) ? "dgs::HipRegistration<FAST_VGICP>"
-                                                                                        : "dgs::HipRegistration<NDT>";
+                      : (method == DGS_METHOD_ICP)  ? "dgs::HipRegistration<ICP>"
+                                                    : "dgs::HipRegistration<NDT>";
     // the reference's setters below write into params_; PCL's own setters (epsilon, iterations, distance) are read at align()
     this->transformation_epsilon_ = params_.transformation_epsilon;
     this->max_iterations_ = params_.maximum_iterations;
@@ -81,6 +83,12 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   void setRotationEpsilon(double e) { params_.gicp_rotation_epsilon = e; dirty_ = true; }
   void setRegularizationMethod(int m) { params_.gicp_regularization = m; dirty_ = true; }
   void setDevice(int ordinal) { params_.device = ordinal; dirty_ = true; }
+  // pcl::IterativeClosestPoint (DGS_METHOD_ICP): registrations.cpp:63, and the criteria settings dgs_params has no field for
+  // (applied to a live handle in place: its target stays uploaded and indexed)
+  void setUseReciprocalCorrespondences(bool on) { icp_options_.use_reciprocal_correspondences = on ? 1 : 0; apply_icp_options(); }
+  void setIcpOptions(const dgs_icp_options& o) { icp_options_ = o; icp_options_.struct_size = sizeof(dgs_icp_options); apply_icp_options(); }
+  const dgs_icp_options& icpOptions() const { return icp_options_; }
+  const std::string& registrationName() const { return this->reg_name_; }   // pcl::Registration::getClassName()
   // false: skip PCL's CPU kd-tree rebuild in initCompute() on every new target (then use getInlierFraction() instead of
   // getSearchMethodTarget()->nearestKSearch())
   void setKeepPclTree(bool keep) {
@@ -117,6 +125,9 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   dgs_handle* handle() { return handle_; }
 
  protected:
+  void apply_icp_options() {
+    if (handle_ && params_.method == DGS_METHOD_ICP && dgs_set_icp_options(handle_, &icp_options_) != DGS_OK) dirty_ = true;   // else: at the next dgs_create
+  }
   bool ensure_handle() {
     params_.transformation_epsilon = this->transformation_epsilon_;
     params_.maximum_iterations = this->max_iterations_;
@@ -128,6 +139,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     if (handle_) dgs_destroy(handle_);
     handle_ = nullptr;
     if (dgs_create(&params_, &handle_) != DGS_OK) return false;
+    if (params_.method == DGS_METHOD_ICP && dgs_set_icp_options(handle_, &icp_options_) != DGS_OK) return false;
     applied_ = params_;
     dirty_ = false;
     target_dirty_ = source_dirty_ = true;
@@ -170,6 +182,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   typename pcl::PointCloud<PointTarget>::ConstPtr sentinel_;
   dgs_params params_{};
   dgs_params applied_{};
+  dgs_icp_options icp_options_{};
   dgs_handle* handle_ = nullptr;
   dgs_result last_{};
   bool dirty_ = true, target_dirty_ = true, source_dirty_ = true, keep_pcl_tree_ = true;

@@ -10,10 +10,23 @@
 
 #include <iostream>
 #include <string>
+#include <utility>
 
 #include "hip_registration.hpp"
 
 namespace dgs {
+
+// pnh.param<bool>(name, def) where the handle has a typed getParam (ros::NodeHandle); otherwise the value read as an int (parameter
+// sources that only know numbers and strings)
+template <typename Params>
+auto param_bool(Params& pnh, const std::string& name, bool def, int) -> decltype(pnh.getParam(name, std::declval<bool&>()), bool()) {
+  bool v = def;
+  return pnh.getParam(name, v) ? v : def;
+}
+template <typename Params>
+bool param_bool(Params& pnh, const std::string& name, bool def, long) {
+  return pnh.template param<int>(name, def ? 1 : 0) != 0;
+}
 
 template <typename PointT, typename Params>
 typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration(const std::string& registration_method, Params& pnh) {
@@ -38,6 +51,16 @@ typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration(const st
     vgicp->setTransformationEpsilon(pnh.template param<double>("reg_transformation_epsilon", 0.01));      // :53
     vgicp->setMaximumIterations(pnh.template param<int>("reg_maximum_iterations", 64));                   // :54
     vgicp->setCorrespondenceRandomness(pnh.template param<int>("reg_correspondence_randomness", 20));     // :55
+    return base;
+  }
+  if (registration_method == "ICP_HIP") {   // registrations.cpp:59-64 on the GPU (the reference's own "ICP" string keeps its branch)
+    std::cout << "registration: ICP_HIP" << std::endl;
+    typename pcl::Registration<PointT, PointT>::Ptr base(new Reg(DGS_METHOD_ICP));
+    Reg* icp = static_cast<Reg*>(base.get());
+    icp->setTransformationEpsilon(pnh.template param<double>("reg_transformation_epsilon", 0.01));          // :60
+    icp->setMaximumIterations(pnh.template param<int>("reg_maximum_iterations", 64));                       // :61
+    icp->setMaxCorrespondenceDistance(pnh.template param<double>("reg_max_correspondence_distance", 2.5));  // :62
+    icp->setUseReciprocalCorrespondences(param_bool(pnh, "reg_use_reciprocal_correspondences", false, 0));  // :63
     return base;
   }
   if (registration_method == "NDT_HIP") {

@@ -50,7 +50,10 @@ enum dgs_status {
 enum dgs_method {
   DGS_METHOD_NDT = 0,  /* "NDT_OMP": pclomp::NormalDistributionsTransform, registrations.cpp:101-120 */
   DGS_METHOD_GICP = 1, /* "FAST_GICP": fast_gicp::FastGICP, registrations.cpp:27-36 */
-  DGS_METHOD_VGICP = 2 /* "FAST_VGICP": fast_gicp::FastVGICP, registrations.cpp:48-56 */
+  DGS_METHOD_VGICP = 2, /* "FAST_VGICP": fast_gicp::FastVGICP, registrations.cpp:48-56 */
+  DGS_METHOD_ICP = 3    /* "ICP_HIP": pcl::IterativeClosestPoint, registrations.cpp:59-64 (point-to-point, DESIGN.md "ICP_HIP").  Reads
+                           transformation_epsilon, maximum_iterations and gicp_max_correspondence_distance (= setMaxCorrespondenceDistance);
+                           the rest of its settings are dgs_icp_options.  The reference's own "ICP" string is not this method. */
 };
 
 /* fast_gicp::NeighborSearchMethod of FastVGICP (voxel offsets searched around the voxel of T * p) */
@@ -109,7 +112,8 @@ typedef struct dgs_params {
   int32_t ndt_strict_order;         /* dgs_ndt_strict_order, default DGS_NDT_ORDER_UPSTREAM */
 
   /* ---- GICP (fast_gicp::FastGICP) ---- */
-  double gicp_max_correspondence_distance; /* setMaxCorrespondenceDistance; factory default 2.5 (registrations.cpp:33) */
+  double gicp_max_correspondence_distance; /* setMaxCorrespondenceDistance; factory default 2.5 (registrations.cpp:33); also ICP's
+                                              setMaxCorrespondenceDistance (DGS_METHOD_ICP, registrations.cpp:62) */
   double gicp_rotation_epsilon;            /* upstream default 2e-3 */
   double gicp_lm_init_lambda_factor;       /* upstream default 1e-9 */
   int32_t gicp_correspondence_randomness;  /* setCorrespondenceRandomness (k), default 20 (registrations.cpp:34) */
@@ -160,11 +164,26 @@ typedef struct dgs_result {
 /* Defaults = the reference factory's defaults for `method` (registrations.cpp:27-36 / 93-120). */
 int dgs_params_init(dgs_params* params, int32_t method);
 
+/* pcl::IterativeClosestPoint settings that dgs_params has no field for (DGS_METHOD_ICP only; dgs_params keeps its size).
+ * use_reciprocal_correspondences: setUseReciprocalCorrespondences (registrations.cpp:63), default 0.
+ * euclidean_fitness_epsilon: setEuclideanFitnessEpsilon, the relative MSE threshold of DefaultConvergenceCriteria; default -DBL_MAX (never fires).
+ * rotation_epsilon: setTransformationRotationEpsilon; 0 (default) = the rotation threshold is 1 - transformation_epsilon. */
+typedef struct dgs_icp_options {
+  uint32_t struct_size; /* sizeof(dgs_icp_options), set by dgs_icp_options_init */
+  int32_t use_reciprocal_correspondences;
+  double euclidean_fitness_epsilon;
+  double rotation_epsilon;
+} dgs_icp_options;
+int dgs_icp_options_init(dgs_icp_options* options);
+
 /* new pclomp::NormalDistributionsTransform / fast_gicp::FastGICP + setters (registrations.cpp:29-35,105-119) */
 int dgs_create(const dgs_params* params, dgs_handle** out);
 void dgs_destroy(dgs_handle* h);
 const char* dgs_last_error(const dgs_handle* h); /* never NULL; "" when the last call succeeded */
 int dgs_abi_version(void);
+
+/* Settings of an ICP handle, taking effect at the next align; DGS_ERR_UNSUPPORTED on a handle of another method. */
+int dgs_set_icp_options(dgs_handle* h, const dgs_icp_options* options);
 
 /* Run all of this handle's work on a caller-owned hipStream_t (NULL = a stream the handle owns). */
 int dgs_set_stream(dgs_handle* h, void* hip_stream);
@@ -284,6 +303,7 @@ int32_t dgs_group_rccl_ranks(const dgs_group* g);              /* ncclCommCount 
 int32_t dgs_group_last_gather_used_rccl(const dgs_group* g);   /* 1: the last dgs_group_align_batch exchanged its records with ncclAllGather */
 dgs_handle* dgs_group_member(dgs_group* g, int32_t k);         /* member k's handle (e.g. for dgs_profile_*); owned by the group */
 int dgs_group_set_input_target(dgs_group* g, const float* xyz16, int64_t n);
+int dgs_group_set_icp_options(dgs_group* g, const dgs_icp_options* options);   /* dgs_set_icp_options on every member */
 int dgs_group_align_batch(dgs_group* g, int32_t n, const float* const* sources, const int64_t* sizes, const float* guesses16,
                           int32_t compute_fitness, double fitness_max_range, dgs_result* results, int32_t* best_index, double* best_score);
 
@@ -323,7 +343,7 @@ int dgs_profile_get(dgs_handle* h, int32_t kernel_id, double* total_ms, int64_t*
 int dgs_profile_reset(dgs_handle* h);
 /* Counts describing the current problem, for algorithmic-byte accounting:
  * out[0] = target points, out[1] = source points, out[2] = valid voxels V, out[3] = occupied voxels,
- * out[4] = voxel grid cells, out[5] = derivative evaluations of the last align / batch (sum over pairs). */
+ * out[4] = voxel grid cells, out[5] = derivative evaluations of the last align / batch (sum over pairs; ICP: correspondence passes). */
 int dgs_get_counts(dgs_handle* h, int64_t out[8]);
 
 /* Test hooks: single evaluations on the device, so tests can compare kernels with the oracle directly. */
@@ -335,6 +355,9 @@ int dgs_ndt_hessian_double(dgs_handle* h, const double* p6, double* hess36);
 /* NDT pose (x, y, z, rx, ry, rz) after every outer iteration of pair `pair` of the last align / align_batch;
  * poses6 holds up to 72 x 6 doubles, *len receives the number written (entry 0 is the initial guess). */
 int dgs_ndt_get_trajectory(dgs_handle* h, int32_t pair, double* poses6, int32_t* len);
+/* ICP: for every iteration of pair `pair` of the last align / align_batch, the incremental transform T_k (16 floats, column-major),
+ * that iteration's MSE and its number of kept correspondences.  Up to `capacity` entries are written; *len receives the iteration count. */
+int dgs_icp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, double* mse, int32_t* n_corr, int32_t capacity, int32_t* len);
 /* NDT voxel table dump.  First call with NULL arrays returns the number of occupied voxels in *n. */
 int dgs_ndt_get_voxels(dgs_handle* h, int64_t* n, int64_t* keys, int32_t* counts, int32_t* valid, double* mean3,
                        double* icov9);
