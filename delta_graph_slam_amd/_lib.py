@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("DGS_REG_LIB") or os.path.join(_HERE, "libdgs_reg.so")
 DGS_OK = 0
 STATUS = {0: "DGS_OK", 1: "DGS_ERR_INVALID_ARGUMENT", 2: "DGS_ERR_HIP", 3: "DGS_ERR_NO_TARGET", 4: "DGS_ERR_NO_SOURCE",
           5: "DGS_ERR_GRID_TOO_LARGE", 6: "DGS_ERR_UNSUPPORTED"}
-METHOD_NDT, METHOD_GICP, METHOD_VGICP, METHOD_ICP = 0, 1, 2, 3
+METHOD_NDT, METHOD_GICP, METHOD_VGICP, METHOD_ICP, METHOD_PCL_GICP = 0, 1, 2, 3, 4
 VGICP_SEARCH = {"DIRECT1": 0, "DIRECT7": 1, "DIRECT27": 2}
 NDT_SEARCH = {"KDTREE": 0, "DIRECT26": 1, "DIRECT7": 2, "DIRECT1": 3}
 NDT_ORDER = {"FAST": 0, "UPSTREAM": 1, "UPSTREAM_SEQUENTIAL": 2}
@@ -48,6 +48,11 @@ class IcpOptions(C.Structure):
                 ("rotation_epsilon", C.c_double)]
 
 
+class PclGicpOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_optimizer_iterations", C.c_int32), ("rotation_epsilon", C.c_double),
+                ("gicp_epsilon", C.c_double), ("use_reciprocal_correspondences", C.c_int32)]
+
+
 class Result(C.Structure):
     _fields_ = [("final_transformation", C.c_float * 16), ("converged", C.c_int32), ("iterations", C.c_int32),
                 ("evaluations", C.c_int32), ("status", C.c_int32), ("score", C.c_double), ("fitness", C.c_double)]
@@ -66,6 +71,8 @@ SYMBOLS = [
     "dgs_group_cloud_create", "dgs_group_cloud_destroy", "dgs_group_cloud_size", "dgs_group_cloud_copies", "dgs_group_cloud_trim", "dgs_group_set_input_target_cloud",
     "dgs_group_align_batch_clouds",
     "dgs_icp_options_init", "dgs_set_icp_options", "dgs_group_set_icp_options", "dgs_icp_get_trajectory",
+    "dgs_pcl_gicp_options_init", "dgs_set_pcl_gicp_options", "dgs_group_set_pcl_gicp_options", "dgs_pcl_gicp_get_trajectory",
+    "dgs_pcl_gicp_set_probe", "dgs_pcl_gicp_evaluate", "dgs_pcl_gicp_set_correspondence_randomness",
 ]
 
 _libs = {}
@@ -153,5 +160,13 @@ def load(path=None):
     lib.dgs_set_icp_options.argtypes = [C.c_void_p, P(IcpOptions)]
     lib.dgs_group_set_icp_options.argtypes = [C.c_void_p, P(IcpOptions)]
     lib.dgs_icp_get_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, P(C.c_int32)]
+    lib.dgs_pcl_gicp_options_init.argtypes = [P(PclGicpOptions)]
+    lib.dgs_set_pcl_gicp_options.argtypes = [C.c_void_p, P(PclGicpOptions)]
+    lib.dgs_group_set_pcl_gicp_options.argtypes = [C.c_void_p, P(PclGicpOptions)]
+    lib.dgs_pcl_gicp_get_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                P(C.c_int32)]
+    lib.dgs_pcl_gicp_set_correspondence_randomness.argtypes = [C.c_void_p, C.c_int32]
+    lib.dgs_pcl_gicp_set_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dgs_pcl_gicp_evaluate.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int32), P(C.c_double), C.c_void_p]
     _libs[path] = lib
     return lib

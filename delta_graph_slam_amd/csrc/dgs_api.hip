@@ -282,8 +282,72 @@ int dgs_params_init(dgs_params* p, int32_t method) {
   p->gicp_lm_max_iterations = 10;
   p->vgicp_search_method = DGS_VGICP_DIRECT1;
   p->vgicp_resolution = 1.0;
-  if (method != DGS_METHOD_NDT && method != DGS_METHOD_GICP && method != DGS_METHOD_VGICP && method != DGS_METHOD_ICP) return DGS_ERR_INVALID_ARGUMENT;
+  if (method != DGS_METHOD_NDT && method != DGS_METHOD_GICP && method != DGS_METHOD_VGICP && method != DGS_METHOD_ICP && method != DGS_METHOD_PCL_GICP)
+    return DGS_ERR_INVALID_ARGUMENT;
   return DGS_OK;
+}
+
+int dgs_pcl_gicp_options_init(dgs_pcl_gicp_options* o) {
+  if (!o) return DGS_ERR_INVALID_ARGUMENT;
+  std::memset(o, 0, sizeof(*o));
+  o->struct_size = sizeof(dgs_pcl_gicp_options);
+  o->max_optimizer_iterations = 20;   // registrations.cpp:74's reg_max_optimizer_iterations default
+  o->rotation_epsilon = 2e-3;         // the GeneralizedIterativeClosestPoint constructor's value
+  o->gicp_epsilon = 1e-3;
+  o->use_reciprocal_correspondences = 0;
+  return DGS_OK;
+}
+
+int dgs_set_pcl_gicp_options(dgs_handle* h, const dgs_pcl_gicp_options* o) {
+  if (!h || !o || o->struct_size != sizeof(dgs_pcl_gicp_options)) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (h->prm.method != DGS_METHOD_PCL_GICP) { h->err = "dgs_set_pcl_gicp_options: not a GICP_HIP handle"; return DGS_ERR_UNSUPPORTED; }
+  if (o->max_optimizer_iterations < 1 || !(o->rotation_epsilon > 0) || !(o->gicp_epsilon >= 0)) {
+    h->err = "dgs_set_pcl_gicp_options: max_optimizer_iterations >= 1, rotation_epsilon > 0 and gicp_epsilon >= 0 are required";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  h->pg_opt = *o;
+  return DGS_OK;
+}
+
+int dgs_pcl_gicp_set_correspondence_randomness(dgs_handle* h, int32_t k) {
+  if (!h || k < 1) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (h->prm.method != DGS_METHOD_PCL_GICP) { h->err = "dgs_pcl_gicp_set_correspondence_randomness: not a GICP_HIP handle"; return DGS_ERR_UNSUPPORTED; }
+  h->prm.gicp_correspondence_randomness = k;   // CloudState::pcov is keyed by k: every cloud recomputes at its next use
+  return DGS_OK;
+}
+
+int dgs_pcl_gicp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, int32_t* n_corr, int32_t* inner, int32_t* passes, double* f, int32_t capacity,
+                                int32_t* len) {
+  if (!h || !len || pair < 0 || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  if (h->prm.method != DGS_METHOD_PCL_GICP) return DGS_ERR_UNSUPPORTED;
+  int n = 0;
+  int rc = pcl_gicp_trajectory(h, pair, T16s, n_corr, inner, passes, f, capacity, &n);
+  *len = n;
+  return rc;
+}
+
+int dgs_pcl_gicp_set_probe(dgs_handle* h, const float* T16, const float* guess16) {
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (h->prm.method != DGS_METHOD_PCL_GICP) return DGS_ERR_UNSUPPORTED;
+  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::memcpy(h->pg_probe_T, T16 ? T16 : ident, sizeof(h->pg_probe_T));
+  std::memcpy(h->pg_probe_guess, guess16 ? guess16 : ident, sizeof(h->pg_probe_guess));
+  return DGS_OK;
+}
+
+int dgs_pcl_gicp_evaluate(dgs_handle* h, const double* x6, int32_t* m, double* f, double* g6) {
+  if (!h || !x6 || !m || !f || !g6) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  if (h->prm.method != DGS_METHOD_PCL_GICP) return DGS_ERR_UNSUPPORTED;
+  if (!h->have_target || h->nt == 0) return DGS_ERR_NO_TARGET;
+  if (!h->have_source || h->ns == 0) return DGS_ERR_NO_SOURCE;
+  return pcl_gicp_evaluate(h, x6, m, f, g6);
 }
 
 int dgs_icp_options_init(dgs_icp_options* o) {
@@ -317,7 +381,8 @@ int dgs_icp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, double* mse
 
 int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (!params || !out || params->struct_size != sizeof(dgs_params)) return DGS_ERR_INVALID_ARGUMENT;
-  if (params->method != DGS_METHOD_NDT && params->method != DGS_METHOD_GICP && params->method != DGS_METHOD_VGICP && params->method != DGS_METHOD_ICP)
+  if (params->method != DGS_METHOD_NDT && params->method != DGS_METHOD_GICP && params->method != DGS_METHOD_VGICP && params->method != DGS_METHOD_ICP &&
+      params->method != DGS_METHOD_PCL_GICP)
     return DGS_ERR_INVALID_ARGUMENT;
   if (params->method == DGS_METHOD_VGICP && (!(params->vgicp_resolution > 0) || params->vgicp_search_method < 0 || params->vgicp_search_method > DGS_VGICP_DIRECT27))
     return DGS_ERR_INVALID_ARGUMENT;
@@ -369,6 +434,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   std::memset(h->final_T, 0, sizeof(h->final_T));
   h->final_T[0] = h->final_T[5] = h->final_T[10] = h->final_T[15] = 1.f;
   (void)dgs_icp_options_init(&h->icp_opt);
+  (void)dgs_pcl_gicp_options_init(&h->pg_opt);
   *out = h;
   return DGS_OK;
 }
@@ -399,6 +465,7 @@ void dgs_destroy(dgs_handle* h) {
   h->batch_slab.release();
   for (auto& c : h->batch_clouds) c.release();
   icp_release(h);
+  pcl_gicp_release(h);
   h->gitems.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
   h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();
@@ -568,6 +635,8 @@ int dgs_align(dgs_handle* h, const float* guess16, dgs_result* out, float* align
     rc = ndt_align_pairs(h, 1, &src, &n, guess16, out);
   } else if (h->prm.method == DGS_METHOD_ICP) {
     rc = icp_align(h, guess16, out);
+  } else if (h->prm.method == DGS_METHOD_PCL_GICP) {
+    rc = pcl_gicp_align(h, guess16, out);
   } else {
     rc = gicp_align(h, guess16, out);
   }
@@ -684,8 +753,10 @@ static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* 
   // 12: 2.08 / 2.16, 32: 3.30 / 4.23)
   static const int kd_min = std::getenv("DGS_GICP_KD_MIN_CANDIDATES") ? std::atoi(std::getenv("DGS_GICP_KD_MIN_CANDIDATES")) : 10;
   h->batch_kd = h->nn_kd && n >= kd_min;
-  const bool icp = h->prm.method == DGS_METHOD_ICP;
-  int rc = icp ? icp_align_batch(h, n, cs, guesses16, results) : gicp_align_batch(h, n, cs, guesses16, results);
+  const bool icp = h->prm.method == DGS_METHOD_ICP, pcl = h->prm.method == DGS_METHOD_PCL_GICP;
+  int rc = icp   ? icp_align_batch(h, n, cs, guesses16, results)
+           : pcl ? pcl_gicp_align_batch(h, n, cs, guesses16, results)
+                 : gicp_align_batch(h, n, cs, guesses16, results);
   if (rc == DGS_OK && compute_fitness) {
     DGS_HIP_TRY(h, h->src_ptrs.reserve(n));
     DGS_HIP_TRY(h, h->src_sizes.reserve(n));
@@ -699,7 +770,7 @@ static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* 
     std::vector<double> sums(n);
     std::vector<int64_t> cnts(n), inl(n);
     size_t stride = 0;
-    const float* dT = icp ? icp_final_transforms(h, &stride) : gicp_final_transforms(h, &stride);
+    const float* dT = icp ? icp_final_transforms(h, &stride) : pcl ? pcl_gicp_final_transforms(h, &stride) : gicp_final_transforms(h, &stride);
     rc = nn_fitness_batch(h, n, h->src_ptrs.ptr, h->src_sizes.ptr, max_n, dT, stride, fitness_max_range, 0.0, sums.data(), cnts.data(), inl.data());
     if (rc == DGS_OK)
       for (int i = 0; i < n; i++) results[i].fitness = cnts[i] > 0 ? sums[i] / (double)cnts[i] : DBL_MAX;
@@ -1032,8 +1103,9 @@ int dgs_gicp_get_covariances(dgs_handle* h, int32_t which, double* cov9) {
   if (!h || !cov9) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   if (set_device(h)) return DGS_ERR_HIP;
-  if (h->prm.method != DGS_METHOD_GICP && h->prm.method != DGS_METHOD_VGICP) return DGS_ERR_UNSUPPORTED;
+  if (h->prm.method != DGS_METHOD_GICP && h->prm.method != DGS_METHOD_VGICP && h->prm.method != DGS_METHOD_PCL_GICP) return DGS_ERR_UNSUPPORTED;
   if (which ? (!h->have_target || h->nt == 0) : (!h->have_source || h->ns == 0)) return which ? DGS_ERR_NO_TARGET : DGS_ERR_NO_SOURCE;
+  if (h->prm.method == DGS_METHOD_PCL_GICP) return pcl_gicp_covariances(h, which, cov9, which ? h->nt : h->ns);   // PCL-style, 9 stored entries
   return gicp_covariances(h, which, cov9, which ? h->nt : h->ns);
 }
 

@@ -417,6 +417,19 @@ int dgs_group_set_icp_options(dgs_group* g, const dgs_icp_options* options) {
   return DGS_OK;
 }
 
+int dgs_group_set_pcl_gicp_options(dgs_group* g, const dgs_pcl_gicp_options* options) {
+  if (!g || !options) return DGS_ERR_INVALID_ARGUMENT;
+  g->err.clear();
+  for (size_t k = 0; k < g->members.size(); k++) {   // host-side settings only: no device work, no member thread needed
+    const int rc = dgs_set_pcl_gicp_options(g->members[k], options);
+    if (rc != DGS_OK) {
+      g->err = "member " + std::to_string(k) + ": " + dgs_last_error(g->members[k]);
+      return rc;
+    }
+  }
+  return DGS_OK;
+}
+
 int dgs_group_align_batch(dgs_group* g, int32_t n, const float* const* sources, const int64_t* sizes, const float* guesses16, int32_t compute_fitness,
                           double fitness_max_range, dgs_result* results, int32_t* best_index, double* best_score) {
   if (!g || n < 0 || (n > 0 && (!sources || !sizes || !results))) return DGS_ERR_INVALID_ARGUMENT;

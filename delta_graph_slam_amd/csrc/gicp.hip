@@ -1106,9 +1106,10 @@ int gicp_ensure_target_covariance(dgs_handle* h) {
   return ensure_covariance(h, *h->tgt);
 }
 
-static int ensure_covariance(dgs_handle* h, CloudState& c) {
-  if (c.cov_valid && c.cov_k == h->gconsts.k && c.cov_reg == h->gconsts.regularization) return DGS_OK;
-  if (h->gconsts.k > kKnnMax) {
+// Exact k-NN of every point of `c` in `c` itself (the point included) -> h->knn_nbr (nbr[pos * kKnnMax + slot], pos in c.bvh's order).
+// Shared by FAST_GICP's covariances and GICP_HIP's (pcl_gicp.hip).
+int knn_lists(dgs_handle* h, CloudState& c, int k) {
+  if (k > kKnnMax) {
     h->err = "reg_correspondence_randomness > 32 is not supported by the HIP k-NN";
     return DGS_ERR_UNSUPPORTED;
   }
@@ -1117,14 +1118,12 @@ static int ensure_covariance(dgs_handle* h, CloudState& c) {
     int rc = bvh_build(h, c.bvh, c.pts.ptr, c.n, nullptr, h->batch_kd && &c == h->tgt);
     if (rc) return rc;
   }
-  DGS_HIP_TRY(h, c.cov.reserve((size_t)c.n * 6));
   const BvhView v = make_bvh_view(c.bvh);
   DGS_HIP_TRY(h, h->knn_nbr.reserve((size_t)c.n * kKnnMax));
   DGS_HIP_TRY(h, h->knn_stats.reserve(8));
   // rounds per wave: enough waves to fill the chip several times over, and stretches long enough for the warm bounds to pay
   const int run = (int)std::max<int64_t>(1, std::min<int64_t>(h->knn_rounds, (c.n + 8 * (int64_t)h->knn_min_waves - 1) / (8 * (int64_t)h->knn_min_waves)));
   const int64_t waves = (c.n + 8 * (int64_t)run - 1) / (8 * (int64_t)run);
-  int slot = prof_begin(h, DGS_K_GICP_COVARIANCE);
   if (h->knn_leaf) {
     const int64_t n_leaves = (c.n + kLeaf - 1) / kLeaf;
     // waves per leaf (each answers 8 / parts of the leaf's queries after its own walk, whose loops run over ITS queries only): measured
@@ -1136,11 +1135,29 @@ static int ensure_covariance(dgs_handle* h, CloudState& c) {
     (void)hipMemsetAsync(h->knn_stats.ptr, 0, 8 * sizeof(int), h->stream);
 #endif
     hipLaunchKernelGGL(gicp_knn_leaf_kernel, dim3((unsigned)((n_leaves * parts + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, h->stream, v, (int)c.n,
-                       h->gconsts.k, parts, h->knn_nbr.ptr, h->knn_stats.ptr);
+                       k, parts, h->knn_nbr.ptr, h->knn_stats.ptr);
   } else {
-    hipLaunchKernelGGL(gicp_knn_kernel, dim3((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, h->stream, v, (int)c.n, h->gconsts.k, run,
+    hipLaunchKernelGGL(gicp_knn_kernel, dim3((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, h->stream, v, (int)c.n, k, run,
                        h->knn_nbr.ptr);
   }
+  return DGS_OK;
+}
+
+static int ensure_covariance(dgs_handle* h, CloudState& c) {
+  if (c.cov_valid && c.cov_k == h->gconsts.k && c.cov_reg == h->gconsts.regularization) return DGS_OK;
+  if (h->gconsts.k > kKnnMax) {
+    h->err = "reg_correspondence_randomness > 32 is not supported by the HIP k-NN";
+    return DGS_ERR_UNSUPPORTED;
+  }
+  if (!c.bvh.valid) {
+    int rc = bvh_build(h, c.bvh, c.pts.ptr, c.n, nullptr, h->batch_kd && &c == h->tgt);
+    if (rc) return rc;
+  }
+  DGS_HIP_TRY(h, c.cov.reserve((size_t)c.n * 6));
+  const BvhView v = make_bvh_view(c.bvh);
+  int slot = prof_begin(h, DGS_K_GICP_COVARIANCE);
+  int rc = knn_lists(h, c, h->gconsts.k);
+  if (rc) return rc;
   constexpr int kCovPerBlock = kCovPerWave * (kBlock / kWave);
   hipLaunchKernelGGL(gicp_cov_from_knn_kernel, dim3((unsigned)(((int64_t)c.n + kCovPerBlock - 1) / kCovPerBlock)), dim3(kBlock), 0, h->stream, v, c.pts.ptr, (int)c.n,
                      h->gconsts.k, h->gconsts.regularization | (h->prm.gicp_cov_jacobi_svd ? 0x100 : 0), h->knn_nbr.ptr, c.cov.ptr);

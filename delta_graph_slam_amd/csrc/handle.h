@@ -19,6 +19,9 @@ struct Profiler {
 
 struct IcpPair;   // icp.hip
 struct IcpItem;
+struct PgPair;    // pcl_gicp.hip
+struct PgItem;
+struct PgInit;
 
 // Exact-NN index over a point cloud (nn_bvh.hip): Hilbert-sorted points, implicit complete 8-ary tree of AABBs.
 struct Bvh {
@@ -85,9 +88,13 @@ struct CloudState {
   bool cov_valid = false;
   int cov_k = 0, cov_reg = -1;
   Bvh walk;            // ICP: a Hilbert-ordered index kept for the correspondence walk when `bvh` is k-d ordered (the cloud was a batch target)
-  void invalidate() { bvh.valid = false; cov_valid = false; walk.valid = false; }
+  DevBuf<double> pcov; // GICP_HIP: pcl::GeneralizedIterativeClosestPoint's covariances, 9 doubles per point (row-major), keyed by (k, epsilon)
+  bool pcov_valid = false;
+  int pcov_k = 0;
+  double pcov_eps = 0.0;
+  void invalidate() { bvh.valid = false; cov_valid = false; walk.valid = false; pcov_valid = false; }
   void release() {
-    pts.release(); cov.release();
+    pts.release(); cov.release(); pcov.release();
     for (Bvh* b : {&bvh, &walk}) {
       b->sorted.release(); b->node_lo.release(); b->node_hi.release();
       b->keys.release(); b->keys_alt.release(); b->vals.release(); b->vals_alt.release();
@@ -276,6 +283,24 @@ struct dgs_handle {
   std::vector<int> icp_last_iters;             // iterations per pair of the last align / batch (dgs_icp_get_trajectory)
   int icp_traj_cap = 0;
 
+  // ---- GICP_HIP (pcl::GeneralizedIterativeClosestPoint, pcl_gicp.hip): PCL-style covariances of target and sources (CloudState::pcov)
+  dgs_pcl_gicp_options pg_opt{};               // dgs_set_pcl_gicp_options; read at every align
+  dgs::DevBuf<dgs::PgPair> pgpairs;
+  dgs::DevBuf<dgs::PgItem> pgitems;
+  dgs::DevBuf<dgs::PgInit> pginits;
+  dgs::DevBuf<float4> pg_w;                    // per source slot (walk order): output = guess * source, w = original index
+  dgs::DevBuf<float4> pg_q;                    // per source slot: the target point of this outer iteration's pair, w = 1 kept / 0 not
+  dgs::DevBuf<double> pg_m;                    // per source slot: M_i, 9 planes of doubles (structure of arrays)
+  dgs::DevBuf<int> pg_blk_pair;                // workgroup -> pair of the round launch (fixed slices per pair)
+  dgs::DevBuf<double> pg_rows;                 // one partial row per (pair, slice)
+  dgs::DevBuf<float> pg_traj_T;                // per pair and outer iteration: transformation_ (column-major 16 floats)
+  dgs::DevBuf<int> pg_traj_i;                  // per pair and outer iteration: kept pairs, inner iterations, evaluation passes
+  dgs::DevBuf<double> pg_traj_f;
+  std::vector<int> pg_last_iters;              // outer iterations per pair of the last align / batch (dgs_pcl_gicp_get_trajectory)
+  int pg_traj_cap = 0;
+  float pg_probe_T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};       // dgs_pcl_gicp_set_probe: transformation_, column-major
+  float pg_probe_guess[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // and the guess
+
   dgs::Profiler prof;
 };
 
@@ -350,6 +375,16 @@ int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* 
 const float* icp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int icp_trajectory(dgs_handle* h, int pair, float* T16s, double* mse, int32_t* n_corr, int capacity, int* len);
 void icp_release(dgs_handle* h);
+// gicp.hip: exact k-NN lists of a cloud in itself -> h->knn_nbr
+int knn_lists(dgs_handle* h, CloudState& c, int k);
+// pcl_gicp.hip
+int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
+int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);
+const float* pcl_gicp_final_transforms(dgs_handle* h, size_t* stride_bytes);
+int pcl_gicp_covariances(dgs_handle* h, int which, double* host_out9, int64_t n);
+int pcl_gicp_evaluate(dgs_handle* h, const double* x6, int32_t* m, double* f, double* g6);
+int pcl_gicp_trajectory(dgs_handle* h, int pair, float* T16s, int32_t* n_corr, int32_t* inner, int32_t* passes, double* f, int capacity, int* len);
+void pcl_gicp_release(dgs_handle* h);
 // transform
 int transform_cloud(dgs_handle* h, const float4* in, float4* out, int64_t n, const float* T16_colmajor_host);
 // dgs_api.hip: a copy of `src` (points only) on dst_h's device, device to device (peer copy over xGMI when the devices differ)

@@ -70,6 +70,30 @@ _ICP_KEYS = {"icp_use_reciprocal_correspondences": "use_reciprocal_correspondenc
              "icp_euclidean_fitness_epsilon": "euclidean_fitness_epsilon", "icp_rotation_epsilon": "rotation_epsilon"}
 
 
+_PG_KEYS = {"gicp_max_optimizer_iterations": "max_optimizer_iterations", "gicp_rotation_epsilon": "rotation_epsilon",
+            "gicp_epsilon": "gicp_epsilon", "gicp_use_reciprocal_correspondences": "use_reciprocal_correspondences"}
+_PG_METHODS = ("GICP_HIP", "GICP_OMP_HIP")
+
+
+def _pcl_gicp_options(lib, method, params):
+    """Split the GICP_HIP keywords off `params` into a dgs_pcl_gicp_options (None for another method).  gicp_rotation_epsilon keeps
+    its dgs_params meaning (FAST_GICP's) on the other methods."""
+    if method not in _PG_METHODS:
+        picked = [k for k in params if k in _PG_KEYS and k != "gicp_rotation_epsilon"]
+        if picked:
+            raise TypeError(f"{sorted(picked)} apply to GICP_HIP / GICP_OMP_HIP only")
+        return None
+    picked = {k: params.pop(k) for k in list(params) if k in _PG_KEYS}
+    o = L.PclGicpOptions()
+    rc = lib.dgs_pcl_gicp_options_init(C.byref(o))
+    if rc:
+        raise DgsError(rc, "dgs_pcl_gicp_options_init")
+    for k, v in picked.items():
+        f = _PG_KEYS[k]
+        setattr(o, f, int(v) if f == "max_optimizer_iterations" else int(bool(v)) if f == "use_reciprocal_correspondences" else float(v))
+    return o
+
+
 def _icp_options(lib, method, params):
     """Split the icp_* keywords off `params` into a dgs_icp_options (None for a method other than ICP_HIP)."""
     picked = {k: params.pop(k) for k in list(params) if k in _ICP_KEYS}
@@ -124,12 +148,14 @@ class Registration:
             self._converged, self._final, self.last_result, self._keep = False, np.eye(4, dtype=np.float32), None, {}
             return
         exact = {"NDT_OMP": L.METHOD_NDT, "NDT_HIP": L.METHOD_NDT, "FAST_GICP": L.METHOD_GICP, "FAST_GICP_HIP": L.METHOD_GICP,
-                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP}
+                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP,
+                 "GICP_HIP": L.METHOD_PCL_GICP, "GICP_OMP_HIP": L.METHOD_PCL_GICP}
         if method not in exact:   # pcl::ICP / GICP / NDT, pclomp::GICP, FAST_VGICP_CUDA are other algorithms: not served here
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends (served: {sorted(exact)})")
         m = exact[method]
         params = dict(params)
         icp_opt = _icp_options(lib, method, params)
+        pg_opt = _pcl_gicp_options(lib, method, params)
         p = L.Params()
         rc = lib.dgs_params_init(C.byref(p), m)
         if rc:
@@ -149,6 +175,9 @@ class Registration:
         self.icp_options = icp_opt
         if icp_opt is not None:
             self._check(lib.dgs_set_icp_options(self._h, C.byref(icp_opt)))
+        self.pcl_gicp_options = pg_opt
+        if pg_opt is not None:
+            self._check(lib.dgs_set_pcl_gicp_options(self._h, C.byref(pg_opt)))
         self._converged = False
         self._final = np.eye(4, dtype=np.float32)
         self.last_result = None
@@ -369,8 +398,11 @@ class Registration:
         setattr(self.icp_options, field, value)
         self._check(self._lib.dgs_set_icp_options(self._h, C.byref(self.icp_options)))
 
-    def setUseReciprocalCorrespondences(self, on: bool):
-        self._set_icp("use_reciprocal_correspondences", 1 if on else 0)
+    def setUseReciprocalCorrespondences(self, on: bool):   # ICP_HIP: reciprocal mode; GICP_HIP: accepted, without effect (as upstream)
+        if self.method in _PG_METHODS:
+            self._set_pg("use_reciprocal_correspondences", 1 if on else 0)
+        else:
+            self._set_icp("use_reciprocal_correspondences", 1 if on else 0)
 
     def setEuclideanFitnessEpsilon(self, eps: float):
         self._set_icp("euclidean_fitness_epsilon", float(eps))
@@ -389,6 +421,56 @@ class Registration:
                                                      nc.ctypes.data_as(C.c_void_p), cap, C.byref(ln)))
         m = min(ln.value, cap)
         return T[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy(), mse[:m].copy(), nc[:m].copy()
+
+    # -- pcl::GeneralizedIterativeClosestPoint setters (GICP_HIP / GICP_OMP_HIP) -------------------------------------
+    def _set_pg(self, field, value):
+        if self.method not in _PG_METHODS:
+            raise NotImplementedError(f"{field} is a GICP_HIP setting")
+        setattr(self.pcl_gicp_options, field, value)
+        self._check(self._lib.dgs_set_pcl_gicp_options(self._h, C.byref(self.pcl_gicp_options)))
+
+    def setMaximumOptimizerIterations(self, n: int):
+        self._set_pg("max_optimizer_iterations", int(n))
+
+    def setRotationEpsilon(self, eps: float):
+        self._set_pg("rotation_epsilon", float(eps))
+
+    def setCorrespondenceRandomness(self, k: int):
+        """k_correspondences_ of a GICP_HIP handle: the covariances are recomputed at the next align."""
+        if self.method not in _PG_METHODS:
+            raise NotImplementedError("setCorrespondenceRandomness on a live handle is a GICP_HIP setting")
+        self._check(self._lib.dgs_pcl_gicp_set_correspondence_randomness(self._h, int(k)))
+        self.params.gicp_correspondence_randomness = int(k)
+
+    def pcl_gicp_trajectory(self, pair: int = 0):
+        """GICP_HIP test hook: per outer iteration of pair `pair` of the last align / batch -> dict of transformation_ [m,4,4] float32,
+        kept pairs, BFGS inner iterations, evaluation passes [m] and the last f [m]."""
+        cap = max(1, int(self.params.maximum_iterations)) if self.params is not None else 1024
+        T = np.zeros((cap, 16), np.float32)
+        nc, inner, passes = (np.zeros(cap, np.int32) for _ in range(3))
+        f = np.zeros(cap, np.float64)
+        ln = C.c_int32(0)
+        self._check(self._lib.dgs_pcl_gicp_get_trajectory(self._h, pair, T.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
+                                                          inner.ctypes.data_as(C.c_void_p), passes.ctypes.data_as(C.c_void_p),
+                                                          f.ctypes.data_as(C.c_void_p), cap, C.byref(ln)))
+        m = min(ln.value, cap)
+        return dict(T=T[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy(), n=nc[:m].copy(), inner=inner[:m].copy(), passes=passes[:m].copy(),
+                    f=f[:m].copy())
+
+    def pcl_gicp_evaluate(self, x, transformation=None, guess=None):
+        """GICP_HIP test hook: one correspondence pass at (transformation_, guess) over the current source and target, then
+        (kept pairs m, f, gradient [6]) at state x = (tx, ty, tz, roll, pitch, yaw)."""
+        def colmajor(T):
+            return None if T is None else np.ascontiguousarray(np.asarray(T, np.float32).T)
+        Tc, Gc = colmajor(transformation), colmajor(guess)
+        self._check(self._lib.dgs_pcl_gicp_set_probe(self._h, None if Tc is None else Tc.ctypes.data_as(C.c_void_p),
+                                                     None if Gc is None else Gc.ctypes.data_as(C.c_void_p)))
+        x = np.ascontiguousarray(x, np.float64)
+        m = C.c_int32(0)
+        f = C.c_double(0)
+        g = np.zeros(6)
+        self._check(self._lib.dgs_pcl_gicp_evaluate(self._h, x.ctypes.data_as(C.c_void_p), C.byref(m), C.byref(f), g.ctypes.data_as(C.c_void_p)))
+        return int(m.value), float(f.value), g
 
     # -- measurement / test hooks ---------------------------------------------------------------------------
     def profile_enable(self, on: bool = True):
@@ -526,11 +608,13 @@ class RegistrationGroup:
         lib = L.load()
         self._lib = lib
         exact = {"NDT_OMP": L.METHOD_NDT, "NDT_HIP": L.METHOD_NDT, "FAST_GICP": L.METHOD_GICP, "FAST_GICP_HIP": L.METHOD_GICP,
-                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP}
+                 "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP,
+                 "GICP_HIP": L.METHOD_PCL_GICP, "GICP_OMP_HIP": L.METHOD_PCL_GICP}
         if method not in exact:
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends")
         params = dict(params)
         icp_opt = _icp_options(lib, method, params)
+        pg_opt = _pcl_gicp_options(lib, method, params)
         p = L.Params()
         rc = lib.dgs_params_init(C.byref(p), exact[method])
         if rc:
@@ -549,6 +633,9 @@ class RegistrationGroup:
         self.icp_options = icp_opt
         if icp_opt is not None:
             self._check(lib.dgs_group_set_icp_options(self._g, C.byref(icp_opt)))
+        self.pcl_gicp_options = pg_opt
+        if pg_opt is not None:
+            self._check(lib.dgs_group_set_pcl_gicp_options(self._g, C.byref(pg_opt)))
         self.best_index = -1
         self.best_score = float("inf")
 
@@ -574,14 +661,30 @@ class RegistrationGroup:
         setattr(self.icp_options, field, value)
         self._check(self._lib.dgs_group_set_icp_options(self._g, C.byref(self.icp_options)))
 
-    def setUseReciprocalCorrespondences(self, on: bool):
-        self._set_icp("use_reciprocal_correspondences", 1 if on else 0)
+    def setUseReciprocalCorrespondences(self, on: bool):   # ICP_HIP: reciprocal mode; GICP_HIP: accepted, without effect (as upstream)
+        if self.method in _PG_METHODS:
+            self._set_pg("use_reciprocal_correspondences", 1 if on else 0)
+        else:
+            self._set_icp("use_reciprocal_correspondences", 1 if on else 0)
 
     def setEuclideanFitnessEpsilon(self, eps: float):
         self._set_icp("euclidean_fitness_epsilon", float(eps))
 
     def setTransformationRotationEpsilon(self, eps: float):
         self._set_icp("rotation_epsilon", float(eps))
+
+    # -- pcl::GeneralizedIterativeClosestPoint setters (GICP_HIP / GICP_OMP_HIP), applied to every member ---------------------------------
+    def _set_pg(self, field, value):
+        if self.method not in _PG_METHODS:
+            raise NotImplementedError(f"{field} is a GICP_HIP setting")
+        setattr(self.pcl_gicp_options, field, value)
+        self._check(self._lib.dgs_group_set_pcl_gicp_options(self._g, C.byref(self.pcl_gicp_options)))
+
+    def setMaximumOptimizerIterations(self, n: int):
+        self._set_pg("max_optimizer_iterations", int(n))
+
+    def setRotationEpsilon(self, eps: float):
+        self._set_pg("rotation_epsilon", float(eps))
 
     @property
     def uses_rccl(self) -> bool:
@@ -687,7 +790,8 @@ def select_registration_method(params: dict | None = None, device: int | None = 
     `params` plays the role of the private NodeHandle: keys are the reference's rosparam names
     (registration_method, reg_num_threads, reg_transformation_epsilon, reg_maximum_iterations,
     reg_max_correspondence_distance, reg_correspondence_randomness, reg_resolution, reg_nn_search_method).
-    "NDT_HIP" selects the HIP NDT; "ICP_HIP" the HIP pcl::IterativeClosestPoint (:59-64, + reg_use_reciprocal_correspondences); "FAST_GICP_HIP" / "FAST_GICP" select GICP (:27-36); "FAST_VGICP_HIP" / "FAST_VGICP" the voxelised
+    "NDT_HIP" selects the HIP NDT; "ICP_HIP" the HIP pcl::IterativeClosestPoint (:59-64, + reg_use_reciprocal_correspondences); "GICP_HIP" / "GICP_OMP_HIP" the HIP
+    pcl::GeneralizedIterativeClosestPoint (:65-87, + reg_max_optimizer_iterations); "FAST_GICP_HIP" / "FAST_GICP" select GICP (:27-36); "FAST_VGICP_HIP" / "FAST_VGICP" the voxelised
     GICP (:48-56).  Every other name goes through the reference's own chain of tests, in its order: "ICP" (:59-64) and any name
     containing "GICP" (:66-87: pcl::GICP, or pclomp::GICP when it also contains "OMP") are different algorithms -> NotImplementedError;
     what is left is the NDT branch (:88-123): a name without "NDT" warns "unknown registration type ... use NDT" (:89-92), and then
@@ -711,6 +815,12 @@ def select_registration_method(params: dict | None = None, device: int | None = 
         return Registration("ICP_HIP", device=device,
                             gicp_max_correspondence_distance=float(pr.get("reg_max_correspondence_distance", 2.5)),
                             icp_use_reciprocal_correspondences=bool(pr.get("reg_use_reciprocal_correspondences", False)), **common)
+    if method in ("GICP_HIP", "GICP_OMP_HIP"):         # :65-87 on the GPU: pcl::GeneralizedIterativeClosestPoint (before the "GICP" test)
+        return Registration(method, device=device,
+                            gicp_max_correspondence_distance=float(pr.get("reg_max_correspondence_distance", 2.5)),
+                            gicp_correspondence_randomness=int(pr.get("reg_correspondence_randomness", 20)),
+                            gicp_max_optimizer_iterations=int(pr.get("reg_max_optimizer_iterations", 20)),
+                            gicp_use_reciprocal_correspondences=bool(pr.get("reg_use_reciprocal_correspondences", False)), **common)
     if method == "ICP" or "GICP" in method:             # :59-64, :66-87 (FAST_VGICP_CUDA lands here too when the reference is built without CUDA)
         raise NotImplementedError(f"registration_method {method!r} is served by the reference's own factory branch, not by the HIP back-ends")
     if method != "NDT_HIP":

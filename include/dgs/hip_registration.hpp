@@ -46,9 +46,11 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   explicit HipRegistration(dgs_method method) {
     dgs_params_init(&params_, method);
     dgs_icp_options_init(&icp_options_);
+    dgs_pcl_gicp_options_init(&pg_options_);
     this->reg_name_ = (method == DGS_METHOD_GICP) ? "dgs::HipRegistration<FAST_GICP>" : (method == DGS_METHOD_VGICP) ? "dgs::HipRegistration<FAST_VGICP>"
-                      : (method == DGS_METHOD_ICP)  ? "dgs::HipRegistration<ICP>"
-                                                    : "dgs::HipRegistration<NDT>";
+                      : (method == DGS_METHOD_ICP)       ? "dgs::HipRegistration<ICP>"
+                      : (method == DGS_METHOD_PCL_GICP)  ? "dgs::HipRegistration<PCL_GICP>"
+                                                         : "dgs::HipRegistration<NDT>";
     // the reference's setters below write into params_; PCL's own setters (epsilon, iterations, distance) are read at align()
     this->transformation_epsilon_ = params_.transformation_epsilon;
     this->max_iterations_ = params_.maximum_iterations;
@@ -80,14 +82,33 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     dirty_ = true;
   }
   void setOulierRatio(double r) { params_.ndt_outlier_ratio = r; dirty_ = true; }  // (sic) upstream spelling
-  void setRotationEpsilon(double e) { params_.gicp_rotation_epsilon = e; dirty_ = true; }
+  void setRotationEpsilon(double e) {   // FAST_GICP's dgs_params field; GICP_HIP's rotation_epsilon_ (applied to a live handle)
+    if (params_.method == DGS_METHOD_PCL_GICP) { pg_options_.rotation_epsilon = e; apply_pg_options(); }
+    else { params_.gicp_rotation_epsilon = e; dirty_ = true; }
+  }
   void setRegularizationMethod(int m) { params_.gicp_regularization = m; dirty_ = true; }
   void setDevice(int ordinal) { params_.device = ordinal; dirty_ = true; }
   // pcl::IterativeClosestPoint (DGS_METHOD_ICP): registrations.cpp:63, and the criteria settings dgs_params has no field for
   // (applied to a live handle in place: its target stays uploaded and indexed)
-  void setUseReciprocalCorrespondences(bool on) { icp_options_.use_reciprocal_correspondences = on ? 1 : 0; apply_icp_options(); }
+  void setUseReciprocalCorrespondences(bool on) {   // ICP: reciprocal mode; GICP_HIP: accepted and without effect, as upstream
+    icp_options_.use_reciprocal_correspondences = on ? 1 : 0;
+    pg_options_.use_reciprocal_correspondences = on ? 1 : 0;
+    apply_icp_options();
+    apply_pg_options();
+  }
   void setIcpOptions(const dgs_icp_options& o) { icp_options_ = o; icp_options_.struct_size = sizeof(dgs_icp_options); apply_icp_options(); }
   const dgs_icp_options& icpOptions() const { return icp_options_; }
+  // pcl::GeneralizedIterativeClosestPoint (DGS_METHOD_PCL_GICP): registrations.cpp:74 and the settings dgs_params has no field for
+  void setMaximumOptimizerIterations(int n) { pg_options_.max_optimizer_iterations = n; apply_pg_options(); }
+  void setPclGicpOptions(const dgs_pcl_gicp_options& o) { pg_options_ = o; pg_options_.struct_size = sizeof(dgs_pcl_gicp_options); apply_pg_options(); }
+  const dgs_pcl_gicp_options& pclGicpOptions() const { return pg_options_; }
+  dgs_params params() const {   // the dgs_params the next dgs_create gets (PCL's own setters are read at align())
+    dgs_params p = params_;
+    p.transformation_epsilon = this->transformation_epsilon_;
+    p.maximum_iterations = this->max_iterations_;
+    p.gicp_max_correspondence_distance = this->corr_dist_threshold_;
+    return p;
+  }
   const std::string& registrationName() const { return this->reg_name_; }   // pcl::Registration::getClassName()
   // false: skip PCL's CPU kd-tree rebuild in initCompute() on every new target (then use getInlierFraction() instead of
   // getSearchMethodTarget()->nearestKSearch())
@@ -128,6 +149,9 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   void apply_icp_options() {
     if (handle_ && params_.method == DGS_METHOD_ICP && dgs_set_icp_options(handle_, &icp_options_) != DGS_OK) dirty_ = true;   // else: at the next dgs_create
   }
+  void apply_pg_options() {
+    if (handle_ && params_.method == DGS_METHOD_PCL_GICP && dgs_set_pcl_gicp_options(handle_, &pg_options_) != DGS_OK) dirty_ = true;
+  }
   bool ensure_handle() {
     params_.transformation_epsilon = this->transformation_epsilon_;
     params_.maximum_iterations = this->max_iterations_;
@@ -140,6 +164,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     handle_ = nullptr;
     if (dgs_create(&params_, &handle_) != DGS_OK) return false;
     if (params_.method == DGS_METHOD_ICP && dgs_set_icp_options(handle_, &icp_options_) != DGS_OK) return false;
+    if (params_.method == DGS_METHOD_PCL_GICP && dgs_set_pcl_gicp_options(handle_, &pg_options_) != DGS_OK) return false;
     applied_ = params_;
     dirty_ = false;
     target_dirty_ = source_dirty_ = true;
@@ -183,6 +208,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   dgs_params params_{};
   dgs_params applied_{};
   dgs_icp_options icp_options_{};
+  dgs_pcl_gicp_options pg_options_{};
   dgs_handle* handle_ = nullptr;
   dgs_result last_{};
   bool dirty_ = true, target_dirty_ = true, source_dirty_ = true, keep_pcl_tree_ = true;

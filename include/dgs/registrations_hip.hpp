@@ -63,6 +63,19 @@ typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration(const st
     icp->setUseReciprocalCorrespondences(param_bool(pnh, "reg_use_reciprocal_correspondences", false, 0));  // :63
     return base;
   }
+  if (registration_method == "GICP_HIP" || registration_method == "GICP_OMP_HIP") {   // registrations.cpp:65-87 on the GPU (pcl:: and
+    // pclomp::GeneralizedIterativeClosestPoint are one algorithm; the reference's own "GICP" / "GICP_OMP" strings keep their branches)
+    std::cout << "registration: " << registration_method << std::endl;
+    typename pcl::Registration<PointT, PointT>::Ptr base(new Reg(DGS_METHOD_PCL_GICP));
+    Reg* gicp = static_cast<Reg*>(base.get());
+    gicp->setTransformationEpsilon(pnh.template param<double>("reg_transformation_epsilon", 0.01));                // :69 / :79
+    gicp->setMaximumIterations(pnh.template param<int>("reg_maximum_iterations", 64));                             // :70 / :80
+    gicp->setUseReciprocalCorrespondences(param_bool(pnh, "reg_use_reciprocal_correspondences", false, 0));        // :71 / :81
+    gicp->setMaxCorrespondenceDistance(pnh.template param<double>("reg_max_correspondence_distance", 2.5));        // :72 / :82
+    gicp->setCorrespondenceRandomness(pnh.template param<int>("reg_correspondence_randomness", 20));               // :73 / :83
+    gicp->setMaximumOptimizerIterations(pnh.template param<int>("reg_max_optimizer_iterations", 20));              // :74 / :84
+    return base;
+  }
   if (registration_method == "NDT_HIP") {
     const double ndt_resolution = pnh.template param<double>("reg_resolution", 0.5);                      // :93
     const std::string nn_search_method = pnh.template param<std::string>("reg_nn_search_method", "DIRECT7");  // :103

@@ -51,9 +51,13 @@ enum dgs_method {
   DGS_METHOD_NDT = 0,  /* "NDT_OMP": pclomp::NormalDistributionsTransform, registrations.cpp:101-120 */
   DGS_METHOD_GICP = 1, /* "FAST_GICP": fast_gicp::FastGICP, registrations.cpp:27-36 */
   DGS_METHOD_VGICP = 2, /* "FAST_VGICP": fast_gicp::FastVGICP, registrations.cpp:48-56 */
-  DGS_METHOD_ICP = 3    /* "ICP_HIP": pcl::IterativeClosestPoint, registrations.cpp:59-64 (point-to-point, DESIGN.md "ICP_HIP").  Reads
+  DGS_METHOD_ICP = 3,   /* "ICP_HIP": pcl::IterativeClosestPoint, registrations.cpp:59-64 (point-to-point, DESIGN.md "ICP_HIP").  Reads
                            transformation_epsilon, maximum_iterations and gicp_max_correspondence_distance (= setMaxCorrespondenceDistance);
                            the rest of its settings are dgs_icp_options.  The reference's own "ICP" string is not this method. */
+  DGS_METHOD_PCL_GICP = 4 /* "GICP_HIP" / "GICP_OMP_HIP": pcl::GeneralizedIterativeClosestPoint, registrations.cpp:65-87 (DESIGN.md
+                             "GICP_HIP").  Reads transformation_epsilon, maximum_iterations, gicp_max_correspondence_distance and
+                             gicp_correspondence_randomness (k_correspondences_); the rest is dgs_pcl_gicp_options.  The reference's own
+                             "GICP" / "GICP_OMP" strings are not this method. */
 };
 
 /* fast_gicp::NeighborSearchMethod of FastVGICP (voxel offsets searched around the voxel of T * p) */
@@ -176,6 +180,21 @@ typedef struct dgs_icp_options {
 } dgs_icp_options;
 int dgs_icp_options_init(dgs_icp_options* options);
 
+/* pcl::GeneralizedIterativeClosestPoint settings that dgs_params has no field for (DGS_METHOD_PCL_GICP only; dgs_params keeps its size).
+ * max_optimizer_iterations: setMaximumOptimizerIterations (registrations.cpp:74), default 20.
+ * rotation_epsilon: setRotationEpsilon, default 2e-3 (the GICP constructor's value).
+ * gicp_epsilon: the smallest singular value of every regularised covariance, default 1e-3.
+ * use_reciprocal_correspondences: setUseReciprocalCorrespondences (registrations.cpp:72), default 0; accepted and without effect, as
+ *   upstream (GICP's computeTransformation never reads it). */
+typedef struct dgs_pcl_gicp_options {
+  uint32_t struct_size; /* sizeof(dgs_pcl_gicp_options), set by dgs_pcl_gicp_options_init */
+  int32_t max_optimizer_iterations;
+  double rotation_epsilon;
+  double gicp_epsilon;
+  int32_t use_reciprocal_correspondences;
+} dgs_pcl_gicp_options;
+int dgs_pcl_gicp_options_init(dgs_pcl_gicp_options* options);
+
 /* new pclomp::NormalDistributionsTransform / fast_gicp::FastGICP + setters (registrations.cpp:29-35,105-119) */
 int dgs_create(const dgs_params* params, dgs_handle** out);
 void dgs_destroy(dgs_handle* h);
@@ -184,6 +203,11 @@ int dgs_abi_version(void);
 
 /* Settings of an ICP handle, taking effect at the next align; DGS_ERR_UNSUPPORTED on a handle of another method. */
 int dgs_set_icp_options(dgs_handle* h, const dgs_icp_options* options);
+/* Settings of a GICP_HIP handle, taking effect at the next align; DGS_ERR_UNSUPPORTED on a handle of another method. */
+int dgs_set_pcl_gicp_options(dgs_handle* h, const dgs_pcl_gicp_options* options);
+/* setCorrespondenceRandomness on a live GICP_HIP handle (dgs_params.gicp_correspondence_randomness): the covariances of the target and
+ * of every source are recomputed for the new k at the next align.  DGS_ERR_UNSUPPORTED on a handle of another method. */
+int dgs_pcl_gicp_set_correspondence_randomness(dgs_handle* h, int32_t k);
 
 /* Run all of this handle's work on a caller-owned hipStream_t (NULL = a stream the handle owns). */
 int dgs_set_stream(dgs_handle* h, void* hip_stream);
@@ -304,6 +328,7 @@ int32_t dgs_group_last_gather_used_rccl(const dgs_group* g);   /* 1: the last dg
 dgs_handle* dgs_group_member(dgs_group* g, int32_t k);         /* member k's handle (e.g. for dgs_profile_*); owned by the group */
 int dgs_group_set_input_target(dgs_group* g, const float* xyz16, int64_t n);
 int dgs_group_set_icp_options(dgs_group* g, const dgs_icp_options* options);   /* dgs_set_icp_options on every member */
+int dgs_group_set_pcl_gicp_options(dgs_group* g, const dgs_pcl_gicp_options* options);   /* dgs_set_pcl_gicp_options on every member */
 int dgs_group_align_batch(dgs_group* g, int32_t n, const float* const* sources, const int64_t* sizes, const float* guesses16,
                           int32_t compute_fitness, double fitness_max_range, dgs_result* results, int32_t* best_index, double* best_score);
 
@@ -358,6 +383,16 @@ int dgs_ndt_get_trajectory(dgs_handle* h, int32_t pair, double* poses6, int32_t*
 /* ICP: for every iteration of pair `pair` of the last align / align_batch, the incremental transform T_k (16 floats, column-major),
  * that iteration's MSE and its number of kept correspondences.  Up to `capacity` entries are written; *len receives the iteration count. */
 int dgs_icp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, double* mse, int32_t* n_corr, int32_t capacity, int32_t* len);
+/* GICP_HIP: the next dgs_pcl_gicp_evaluate runs its correspondence pass at transformation_ = T16 and guess = guess16 (column-major; NULL =
+ * identity).  Both stay set until changed. */
+int dgs_pcl_gicp_set_probe(dgs_handle* h, const float* T16, const float* guess16);
+/* GICP_HIP: one correspondence pass over the handle's source and target at the probe's transformation_ / guess, then f and its gradient
+ * at state x6 = (tx, ty, tz, roll, pitch, yaw) over that pass's *m kept pairs (OptimizationFunctorWithIndices, on the device). */
+int dgs_pcl_gicp_evaluate(dgs_handle* h, const double* x6, int32_t* m, double* f, double* g6);
+/* GICP_HIP: for every outer iteration of pair `pair` of the last align / align_batch: transformation_ (16 floats, column-major), the kept
+ * pairs, BFGS inner iterations, evaluation passes and the last f.  Up to `capacity` entries; *len receives the outer iteration count. */
+int dgs_pcl_gicp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, int32_t* n_corr, int32_t* inner, int32_t* passes, double* f,
+                                int32_t capacity, int32_t* len);
 /* NDT voxel table dump.  First call with NULL arrays returns the number of occupied voxels in *n. */
 int dgs_ndt_get_voxels(dgs_handle* h, int64_t* n, int64_t* keys, int32_t* counts, int32_t* valid, double* mean3,
                        double* icov9);
@@ -367,7 +402,7 @@ int dgs_ndt_get_voxels(dgs_handle* h, int64_t* n, int64_t* keys, int32_t* counts
 int dgs_nn_fitness_distances(dgs_handle* h, const float* queries_xyz16, int64_t m, int32_t on_device, float* sq_dists);
 
 /* GICP regularised k-NN covariances (FastGICP::calculate_covariances): which = 0 source, 1 target;
- * cov9 receives 9 doubles (row-major 3x3) per point. */
+ * cov9 receives 9 doubles (row-major 3x3) per point.  On a GICP_HIP handle: pcl::GeneralizedIterativeClosestPoint's covariances. */
 int dgs_gicp_get_covariances(dgs_handle* h, int32_t which, double* cov9);
 /* GICP FastGICP::linearize (error_only = 0: new correspondences at the pose; returns sum of errors, H 6x6, b 6) or
  * FastGICP::compute_error (error_only = 1: correspondences / Mahalanobis matrices of the last linearisation).
