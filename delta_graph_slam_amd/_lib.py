@@ -53,6 +53,18 @@ class PclGicpOptions(C.Structure):
                 ("gicp_epsilon", C.c_double), ("use_reciprocal_correspondences", C.c_int32)]
 
 
+class PrefilterParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("downsample_method", C.c_int32), ("downsample_resolution", C.c_double),
+                ("outlier_removal_method", C.c_int32), ("statistical_mean_k", C.c_int32), ("statistical_stddev", C.c_double),
+                ("radius_radius", C.c_double), ("radius_min_neighbors", C.c_int32), ("use_distance_filter", C.c_int32),
+                ("distance_near_thresh", C.c_double), ("distance_far_thresh", C.c_double), ("radius_inclusive", C.c_int32),
+                ("statistical_sqrt_float", C.c_int32)]
+
+
+PF_DOWNSAMPLE = {"NONE": 0, "VOXELGRID": 1, "APPROX_VOXELGRID": 2}
+PF_OUTLIER = {"NONE": 0, "STATISTICAL": 1, "RADIUS": 2}
+
+
 class Result(C.Structure):
     _fields_ = [("final_transformation", C.c_float * 16), ("converged", C.c_int32), ("iterations", C.c_int32),
                 ("evaluations", C.c_int32), ("status", C.c_int32), ("score", C.c_double), ("fitness", C.c_double)]
@@ -73,6 +85,8 @@ SYMBOLS = [
     "dgs_icp_options_init", "dgs_set_icp_options", "dgs_group_set_icp_options", "dgs_icp_get_trajectory",
     "dgs_pcl_gicp_options_init", "dgs_set_pcl_gicp_options", "dgs_group_set_pcl_gicp_options", "dgs_pcl_gicp_get_trajectory",
     "dgs_pcl_gicp_set_probe", "dgs_pcl_gicp_evaluate", "dgs_pcl_gicp_set_correspondence_randomness",
+    "dgs_prefilter_params_init", "dgs_prefilter", "dgs_prefilter_distance", "dgs_prefilter_radius", "dgs_prefilter_statistical",
+    "dgs_prefilter_normal", "dgs_prefilter_get_statistics", "dgs_prefilter_get_normals",
 ]
 
 _libs = {}
@@ -168,5 +182,17 @@ def load(path=None):
     lib.dgs_pcl_gicp_set_correspondence_randomness.argtypes = [C.c_void_p, C.c_int32]
     lib.dgs_pcl_gicp_set_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dgs_pcl_gicp_evaluate.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int32), P(C.c_double), C.c_void_p]
+    lib.dgs_prefilter_params_init.argtypes = [P(PrefilterParams)]
+    lib.dgs_prefilter.argtypes = [C.c_void_p, P(PrefilterParams), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_int64, C.c_int32, P(C.c_int64), P(C.c_int64)]
+    lib.dgs_prefilter_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_int32,
+                                           P(C.c_int64)]
+    lib.dgs_prefilter_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                         C.c_int32, P(C.c_int64)]
+    lib.dgs_prefilter_statistical.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
+                                              C.c_int64, C.c_int32, P(C.c_int64)]
+    lib.dgs_prefilter_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
+    lib.dgs_prefilter_get_statistics.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(C.c_int64)]
+    lib.dgs_prefilter_get_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
     _libs[path] = lib
     return lib

@@ -1107,8 +1107,9 @@ int gicp_ensure_target_covariance(dgs_handle* h) {
 }
 
 // Exact k-NN of every point of `c` in `c` itself (the point included) -> h->knn_nbr (nbr[pos * kKnnMax + slot], pos in c.bvh's order).
-// Shared by FAST_GICP's covariances and GICP_HIP's (pcl_gicp.hip).
-int knn_lists(dgs_handle* h, CloudState& c, int k) {
+// Shared by FAST_GICP's covariances, GICP_HIP's (pcl_gicp.hip) and the prefilter (prefilter.hip, which passes a buffer of its own).
+int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out) {
+  DevBuf<int>& nbr = out ? *out : h->knn_nbr;
   if (k > kKnnMax) {
     h->err = "reg_correspondence_randomness > 32 is not supported by the HIP k-NN";
     return DGS_ERR_UNSUPPORTED;
@@ -1119,7 +1120,7 @@ int knn_lists(dgs_handle* h, CloudState& c, int k) {
     if (rc) return rc;
   }
   const BvhView v = make_bvh_view(c.bvh);
-  DGS_HIP_TRY(h, h->knn_nbr.reserve((size_t)c.n * kKnnMax));
+  DGS_HIP_TRY(h, nbr.reserve((size_t)c.n * kKnnMax));
   DGS_HIP_TRY(h, h->knn_stats.reserve(8));
   // rounds per wave: enough waves to fill the chip several times over, and stretches long enough for the warm bounds to pay
   const int run = (int)std::max<int64_t>(1, std::min<int64_t>(h->knn_rounds, (c.n + 8 * (int64_t)h->knn_min_waves - 1) / (8 * (int64_t)h->knn_min_waves)));
@@ -1135,10 +1136,10 @@ int knn_lists(dgs_handle* h, CloudState& c, int k) {
     (void)hipMemsetAsync(h->knn_stats.ptr, 0, 8 * sizeof(int), h->stream);
 #endif
     hipLaunchKernelGGL(gicp_knn_leaf_kernel, dim3((unsigned)((n_leaves * parts + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, h->stream, v, (int)c.n,
-                       k, parts, h->knn_nbr.ptr, h->knn_stats.ptr);
+                       k, parts, nbr.ptr, h->knn_stats.ptr);
   } else {
     hipLaunchKernelGGL(gicp_knn_kernel, dim3((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, h->stream, v, (int)c.n, k, run,
-                       h->knn_nbr.ptr);
+                       nbr.ptr);
   }
   return DGS_OK;
 }

@@ -105,6 +105,23 @@ struct CloudState {
   }
 };
 
+// PrefilteringNodelet::cloud_callback (prefilter.hip): the chain's stage buffers, its own NN index and k-NN lists, and what the test
+// hooks read back.  Separate from everything a registration uses.
+struct PfScratch {
+  DevBuf<float4> in, a, b, c, d, e;    // staged host input; distance / down-sampling / outlier / height / flatten outputs
+  DevBuf<unsigned char> flags;         // keep flag per point of the pass being compacted
+  DevBuf<int> blk;                     // per-workgroup kept counts, scanned in place to offsets
+  DevBuf<int> cnt;                     // [0] kept points of the last compaction
+  CloudState cloud;                    // cloud of the k-NN pass being run (radius, statistical, normal) with its index
+  DevBuf<int> nbr;                     // its k-NN lists: [position in index order * 32 + slot]
+  DevBuf<float> mean_d;                // statistical pass: mean neighbour distance per point (input order)
+  DevBuf<double> stats;                // statistical pass: mean, stddev, threshold, variance
+  int64_t stat_n = 0;
+  DevBuf<float4> normals;              // normal pass: normalised flipped normal per point (input order)
+  DevBuf<float> cov9;                  // normal pass: computeMeanAndCovarianceMatrix's 9 floats per point
+  int64_t normal_n = 0;
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -301,6 +318,9 @@ struct dgs_handle {
   float pg_probe_T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};       // dgs_pcl_gicp_set_probe: transformation_, column-major
   float pg_probe_guess[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // and the guess
 
+  // ---- prefilter (prefilter.hip): own buffers and index; the registration's target / source / model / results are left untouched
+  dgs::PfScratch pf;
+
   dgs::Profiler prof;
 };
 
@@ -376,7 +396,9 @@ const float* icp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int icp_trajectory(dgs_handle* h, int pair, float* T16s, double* mse, int32_t* n_corr, int capacity, int* len);
 void icp_release(dgs_handle* h);
 // gicp.hip: exact k-NN lists of a cloud in itself -> h->knn_nbr
-int knn_lists(dgs_handle* h, CloudState& c, int k);
+int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out = nullptr);   // out: default h->knn_nbr
+// prefilter.hip
+void prefilter_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

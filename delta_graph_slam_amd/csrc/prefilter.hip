@@ -1,0 +1,723 @@
+// PrefilteringNodelet::cloud_callback (/root/reference/apps/prefiltering_nodelet.cpp:111-164) from the distance filter to flatten.
+//
+//   distance filter (:275-291) -> down-sampling (:249-260) -> outlier removal (:262-273)   = /filtered_points
+//   height filter (:192-212) -> normal filter (:217-245) -> flatten (:166-188)            = /flat_filtered_points
+//
+// MI355X design
+//   * Every pass-through filter is a keep flag per point followed by one stable compaction: a count pass (wave ballot + popcount per
+//     workgroup), one workgroup scanning the counts, and a scatter pass (ballot prefix inside the wave, the wave totals of the
+//     workgroup, the scanned workgroup offset).  The whole 16-byte point is copied, pad lane included.
+//   * Down-sampling is dgs_voxel_grid_filter's / dgs_approx_voxel_grid_filter's code path, unchanged (ndt_voxel.hip).
+//   * The outlier passes and the normal pass run on gicp.hip's exact k-NN lists (knn_lists, k <= 32) over an index of the
+//     prefilter's own (PfScratch::cloud).  A list is the k smallest (float FLANN distance, index) keys, ties to the lower index; each
+//     lane sorts its list (bitonic network in registers) before any order-dependent sum.
+//   * StatisticalOutlierRemoval's mean and standard deviation are a fixed-order reduction in one workgroup; the threshold is
+//     compared on the device.
+//   * The host reads a count back after each compaction that a later pass needs as a size (the NN index and the voxel filters are
+//     shaped on the host), and once at the end.
+// Semantics and the PCL 1.10 details recalled from upstream: DESIGN.md §6c.
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+#include "handle.h"
+#include "nn_group.h"
+
+namespace dgs {
+
+constexpr int kPfNormalK = 10;             // normal_filtering: ne.setKSearch(10) (:227)
+constexpr float kPfNormalThresh = 0.2f;    // normal_filter_thresh (:235)
+constexpr int kPfScanBlock = 1024;
+
+// ================================================================================================ stable compaction
+__global__ __launch_bounds__(kBlock) void pf_count_kernel(const unsigned char* __restrict__ flags, const int n, int* __restrict__ blk) {
+  __shared__ int s_w[kBlock / kWave];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const bool f = i < n && flags[i] != 0;
+  const unsigned long long m = __ballot(f);
+  if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; w++) t += s_w[w];
+    blk[blockIdx.x] = t;
+  }
+}
+
+// One workgroup: exclusive scan of the nb workgroup counts in place, total -> *total.  Chunks of 1024 in order, so the result is the
+// same whatever the hardware schedule.
+__global__ __launch_bounds__(kPfScanBlock) void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restrict__ total) {
+  __shared__ int s_w[kPfScanBlock / kWave];
+  __shared__ int s_carry;
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  if (threadIdx.x == 0) s_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nb; base += kPfScanBlock) {
+    const int i = base + threadIdx.x;
+    const int v = i < nb ? blk[i] : 0;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+      const int y = __shfl_up(x, o, kWave);
+      if (lane >= o) x += y;
+    }
+    if (lane == kWave - 1) s_w[wv] = x;
+    __syncthreads();
+    if (wv == 0) {
+      int w = lane < kPfScanBlock / kWave ? s_w[lane] : 0;
+#pragma unroll
+      for (int o = 1; o < kPfScanBlock / kWave; o <<= 1) {
+        const int y = __shfl_up(w, o, kWave);
+        if (lane >= o) w += y;
+      }
+      if (lane < kPfScanBlock / kWave) s_w[lane] = w;
+    }
+    __syncthreads();
+    const int carry = s_carry;
+    const int before = carry + (wv ? s_w[wv - 1] : 0) + x - v;
+    if (i < nb) blk[i] = before;
+    __syncthreads();
+    if (threadIdx.x == kPfScanBlock - 1) s_carry = before + v;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *total = s_carry;
+}
+
+__global__ __launch_bounds__(kBlock) void pf_scatter_kernel(const float4* __restrict__ in, const unsigned char* __restrict__ flags, const int n,
+                                                            const int* __restrict__ blk, float4* __restrict__ out, const int flatten) {
+  __shared__ int s_w[kBlock / kWave];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const bool f = i < n && flags[i] != 0;
+  const unsigned long long m = __ballot(f);
+  if (lane == 0) s_w[wv] = __popcll(m);
+  __syncthreads();
+  if (!f) return;
+  int off = blk[blockIdx.x];
+  for (int w = 0; w < wv; w++) off += s_w[w];
+  off += __popcll(m & ((1ull << lane) - 1ull));
+  float4 p = in[i];
+  if (flatten) p.z = 0.f;   // flatten (:181): point.z = 0
+  out[off] = p;             // off < number of kept points <= n: `out` holds n points
+}
+
+// ================================================================================================ predicates
+// distance_filter: d = p.getVector3fMap().norm() in float, (x*x + y*y) + z*z without FMA; kept iff d > near && d < far in double.
+// A non-finite point gives a NaN or infinite d and fails one of the two comparisons.
+__global__ __launch_bounds__(kBlock) void pf_distance_kernel(const float4* __restrict__ in, const int n, const double near_t, const double far_t,
+                                                             unsigned char* __restrict__ flags) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = in[i];
+  const float d = sqrtf(add_rn(add_rn(mul_rn(p.x, p.x), mul_rn(p.y, p.y)), mul_rn(p.z, p.z)));
+  const double dd = (double)d;
+  flags[i] = (dd > near_t && dd < far_t) ? 1 : 0;
+}
+
+// height_filtering: kept iff cloud->at(i).z > lidar_position.z(), compared in double
+__global__ __launch_bounds__(kBlock) void pf_height_kernel(const float4* __restrict__ in, const int n, const double lz, unsigned char* __restrict__ flags) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  flags[i] = ((double)in[i].z > lz) ? 1 : 0;
+}
+
+// ================================================================================================ k-NN passes
+// The list of query `pos` (index order) as sorted keys (float distance bits << 32 | index), empty slots last.
+template <int N>
+__device__ __forceinline__ int pf_sorted_list(const float4* __restrict__ pts, const int n, const int k, const int* __restrict__ nbr, const int pos,
+                                              const float4 q, unsigned long long (&key)[N]) {
+  int found = 0;
+#pragma unroll
+  for (int s = 0; s < N; s++) {
+    const int j = (s < k) ? nbr[(size_t)pos * kKnnMax + s] : -1;
+    if (j >= 0 && j < n) {
+      const float4 p = pts[j];
+      const float d = sqdist_rn(q.x, q.y, q.z, p.x, p.y, p.z);   // FLANN L2_Simple: (dx*dx + dy*dy) + dz*dz in float
+      key[s] = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j;
+      found++;
+    } else {
+      key[s] = ~0ull;
+    }
+  }
+  // bitonic sorting network: constant indices only, the keys stay in registers
+#pragma unroll
+  for (int size = 2; size <= N; size <<= 1)
+#pragma unroll
+    for (int stride = size >> 1; stride > 0; stride >>= 1)
+#pragma unroll
+      for (int a = 0; a < N; a++) {
+        const int b = a ^ stride;
+        if (b > a) {
+          const unsigned long long x = key[a], y = key[b];
+          const bool up = (a & size) == 0;
+          if ((x > y) == up) { key[a] = y; key[b] = x; }
+        }
+      }
+  return found;
+}
+
+__device__ __forceinline__ float pf_key_dist(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
+
+// RadiusOutlierRemoval (PCL 1.10, dense input): nearestKSearch with k = min_neighbors + 1 (the query counts); kept iff k points were
+// found and the k-th smallest squared distance is <= r^2 (inclusive) or < r^2, compared in double.  The k-th smallest distance of the
+// exact k-set is its largest: no sort needed.
+__global__ __launch_bounds__(kBlock) void pf_radius_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k,
+                                                           const int* __restrict__ nbr, const double r2, const int inclusive,
+                                                           unsigned char* __restrict__ flags) {
+  const int pos = blockIdx.x * kBlock + threadIdx.x;
+  if (pos >= n) return;
+  const int i = (int)__float_as_uint(b.sorted[pos].w);
+  if (i < 0 || i >= n) return;
+  const float4 q = pts[i];
+  int found = 0;
+  float dmax = 0.f;
+  for (int s = 0; s < k; s++) {
+    const int j = nbr[(size_t)pos * kKnnMax + s];
+    if (j >= 0 && j < n) {
+      const float4 p = pts[j];
+      dmax = fmaxf(dmax, sqdist_rn(q.x, q.y, q.z, p.x, p.y, p.z));
+      found++;
+    }
+  }
+  const double dk = (double)dmax;
+  const bool keep = found == k && (inclusive ? dk <= r2 : dk < r2);
+  flags[i] = keep ? 1 : 0;
+}
+
+// StatisticalOutlierRemoval, first pass: nearestKSearch(mean_k + 1), index 0 is the query; dist_sum (double) += sqrt(d^2) over
+// j = 1..mean_k in ascending order; distances[i] = (float)(dist_sum / mean_k).
+__global__ __launch_bounds__(kBlock) void pf_sor_distance_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k,
+                                                                 const int* __restrict__ nbr, const int sqrt_float, float* __restrict__ mean_d) {
+  const int pos = blockIdx.x * kBlock + threadIdx.x;
+  if (pos >= n) return;
+  const int i = (int)__float_as_uint(b.sorted[pos].w);
+  if (i < 0 || i >= n) return;
+  unsigned long long key[kKnnMax];
+  pf_sorted_list<kKnnMax>(pts, n, k, nbr, pos, pts[i], key);
+  double dist_sum = 0.0;
+#pragma unroll
+  for (int s = 1; s < kKnnMax; s++) {
+    if (s < k) {
+      const float d2 = pf_key_dist(key[s]);
+      dist_sum += sqrt_float ? (double)sqrtf(d2) : sqrt((double)d2);
+    }
+  }
+  mean_d[i] = (float)(dist_sum / (double)(k - 1));
+}
+
+// mean / stddev / threshold: sum and sq_sum as double sums (sq_sum adds the float product d*d), reduced in a fixed order in one
+// workgroup; variance = (sq_sum - sum*sum/n) / (n-1), threshold = mean + mul * sqrt(variance).
+__global__ __launch_bounds__(kPfScanBlock) void pf_sor_stats_kernel(const float* __restrict__ mean_d, const int n, const double mul,
+                                                                    double* __restrict__ stats) {
+#pragma clang fp contract(off)
+  __shared__ double s_s[kPfScanBlock], s_q[kPfScanBlock];
+  double s = 0.0, q = 0.0;
+  for (int i = threadIdx.x; i < n; i += kPfScanBlock) {
+    const float d = mean_d[i];
+    s += (double)d;
+    q += (double)mul_rn(d, d);
+  }
+  s_s[threadIdx.x] = s;
+  s_q[threadIdx.x] = q;
+  __syncthreads();
+  for (int h = kPfScanBlock / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      s_s[threadIdx.x] += s_s[threadIdx.x + h];
+      s_q[threadIdx.x] += s_q[threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double sum = s_s[0], sq_sum = s_q[0], nn = (double)n;
+    const double mean = sum / nn;
+    const double variance = (sq_sum - sum * sum / nn) / (nn - 1.0);
+    const double stddev = sqrt(variance);
+    stats[0] = mean;
+    stats[1] = stddev;
+    stats[2] = mean + mul * stddev;
+    stats[3] = variance;
+  }
+}
+
+// second pass: removed iff distances[i] > threshold (a NaN threshold removes nothing, as upstream)
+__global__ __launch_bounds__(kBlock) void pf_sor_flag_kernel(const float* __restrict__ mean_d, const int n, const double* __restrict__ stats,
+                                                             unsigned char* __restrict__ flags) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  flags[i] = ((double)mean_d[i] > stats[2]) ? 0 : 1;
+}
+
+// ---- pcl::eigen33 (common/impl/eigen.hpp) in float, operation for operation, no contraction
+__device__ void pf_compute_roots2(const float b, const float c, float* r) {
+#pragma clang fp contract(off)
+  r[0] = 0.f;
+  float d = (float)((double)(b * b) - 4.0 * (double)c);   // Scalar (b * b - 4.0 * c): the double literal promotes the difference
+  if (d < 0.f) d = 0.f;
+  const float sd = sqrtf(d);
+  r[2] = 0.5f * (b + sd);
+  r[1] = 0.5f * (b - sd);
+}
+
+__device__ void pf_compute_roots(const float* m, float* r) {   // m row-major 3 x 3, symmetric
+#pragma clang fp contract(off)
+  const float m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[4], m12 = m[5], m22 = m[8];
+  const float c0 = m00 * m11 * m22 + 2.f * m01 * m02 * m12 - m00 * m12 * m12 - m11 * m02 * m02 - m22 * m01 * m01;
+  const float c1 = m00 * m11 - m01 * m01 + m00 * m22 - m02 * m02 + m11 * m22 - m12 * m12;
+  const float c2 = m00 + m11 + m22;
+  if (fabsf(c0) < FLT_EPSILON) {
+    pf_compute_roots2(c2, c1, r);
+    return;
+  }
+  const float s_inv3 = (float)(1.0 / 3.0);
+  const float s_sqrt3 = sqrtf(3.f);
+  const float c2_over_3 = c2 * s_inv3;
+  float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
+  if (a_over_3 > 0.f) a_over_3 = 0.f;
+  const float half_b = 0.5f * (c0 + c2_over_3 * (2.f * c2_over_3 * c2_over_3 - c1));
+  float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
+  if (q > 0.f) q = 0.f;
+  const float rho = sqrtf(-a_over_3);
+  const float theta = atan2f(sqrtf(-q), half_b) * s_inv3;
+  const float cos_theta = cosf(theta);
+  const float sin_theta = sinf(theta);
+  r[0] = c2_over_3 + 2.f * rho * cos_theta;
+  r[1] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
+  r[2] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
+  float t;
+  if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
+  if (r[1] >= r[2]) {
+    t = r[1]; r[1] = r[2]; r[2] = t;
+    if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
+  }
+  if (r[0] <= 0.f) pf_compute_roots2(c2, c1, r);
+}
+
+// eigenvector of the smallest eigenvalue
+__device__ void pf_eigen33(const float* mat, float* ev) {
+#pragma clang fp contract(off)
+  float scale = 0.f;
+#pragma unroll
+  for (int a = 0; a < 9; a++) scale = fmaxf(scale, fabsf(mat[a]));
+  if (scale <= FLT_MIN) scale = 1.f;
+  float m[9];
+#pragma unroll
+  for (int a = 0; a < 9; a++) m[a] = mat[a] / scale;
+  float r[3];
+  pf_compute_roots(m, r);
+  m[0] -= r[0]; m[4] -= r[0]; m[8] -= r[0];
+  auto cross = [](const float* u, const float* v, float* o) {
+#pragma clang fp contract(off)
+    o[0] = u[1] * v[2] - u[2] * v[1];
+    o[1] = u[2] * v[0] - u[0] * v[2];
+    o[2] = u[0] * v[1] - u[1] * v[0];
+  };
+  auto sq = [](const float* u) {
+#pragma clang fp contract(off)
+    return (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+  };
+  float v1[3], v2[3], v3[3];
+  cross(m + 0, m + 3, v1);
+  cross(m + 0, m + 6, v2);
+  cross(m + 3, m + 6, v3);
+  const float l1 = sq(v1), l2 = sq(v2), l3 = sq(v3);
+  const float* v = v3;
+  float l = l3;
+  if (l1 >= l2 && l1 >= l3) { v = v1; l = l1; }
+  else if (l2 >= l1 && l2 >= l3) { v = v2; l = l2; }
+  const float sl = sqrtf(l);
+  ev[0] = v[0] / sl; ev[1] = v[1] / sl; ev[2] = v[2] / sl;
+}
+
+// normal_filtering: NormalEstimation (k = 10 on this cloud) -> computeMeanAndCovarianceMatrix (9-float raw moments in neighbour order,
+// divided by the float count, cov = E[ab] - mean_a * mean_b) -> eigen33 -> flipNormalTowardsViewpoint -> .normalized(); kept iff
+// |n.z| < 0.2f.  Fewer than 3 neighbours: NaN normal, dropped.
+__global__ __launch_bounds__(kBlock) void pf_normal_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k,
+                                                           const int* __restrict__ nbr, const float vx, const float vy, const float vz,
+                                                           unsigned char* __restrict__ flags, float4* __restrict__ normals,
+                                                           float* __restrict__ cov9) {
+#pragma clang fp contract(off)
+  const int pos = blockIdx.x * kBlock + threadIdx.x;
+  if (pos >= n) return;
+  const int i = (int)__float_as_uint(b.sorted[pos].w);
+  if (i < 0 || i >= n) return;
+  const float4 q = pts[i];
+  unsigned long long key[16];
+  const int found = pf_sorted_list<16>(pts, n, k, nbr, pos, q, key);
+  float* C = cov9 + (size_t)i * 9;
+  const float qnan = __int_as_float(0x7fc00000);
+  if (found < 3) {
+#pragma unroll
+    for (int a = 0; a < 9; a++) C[a] = qnan;
+    normals[i] = make_float4(qnan, qnan, qnan, qnan);
+    flags[i] = 0;
+    return;
+  }
+  float acc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 16; s++) {
+    if (s < found) {
+      const float4 p = pts[(int)(unsigned)(key[s] & 0xffffffffull)];
+      acc[0] += p.x * p.x; acc[1] += p.x * p.y; acc[2] += p.x * p.z;
+      acc[3] += p.y * p.y; acc[4] += p.y * p.z; acc[5] += p.z * p.z;
+      acc[6] += p.x; acc[7] += p.y; acc[8] += p.z;
+    }
+  }
+  const float cnt = (float)found;
+#pragma unroll
+  for (int a = 0; a < 9; a++) acc[a] = acc[a] / cnt;
+  float m[9];
+  m[0] = acc[0] - acc[6] * acc[6];
+  m[1] = acc[1] - acc[6] * acc[7];
+  m[2] = acc[2] - acc[6] * acc[8];
+  m[4] = acc[3] - acc[7] * acc[7];
+  m[5] = acc[4] - acc[7] * acc[8];
+  m[8] = acc[5] - acc[8] * acc[8];
+  m[3] = m[1]; m[6] = m[2]; m[7] = m[5];
+#pragma unroll
+  for (int a = 0; a < 9; a++) C[a] = m[a];
+  float nv[3];
+  pf_eigen33(m, nv);
+  // flipNormalTowardsViewpoint: (vp - p) . n < 0 -> n = -n
+  const float cos_theta = ((vx - q.x) * nv[0] + (vy - q.y) * nv[1]) + (vz - q.z) * nv[2];
+  if (cos_theta < 0.f) { nv[0] = -nv[0]; nv[1] = -nv[1]; nv[2] = -nv[2]; }
+  // Eigen's normalized(): n / sqrt(squaredNorm) when squaredNorm > 0
+  const float z = (nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2];
+  if (z > 0.f) {
+    const float s = sqrtf(z);
+    nv[0] = nv[0] / s; nv[1] = nv[1] / s; nv[2] = nv[2] / s;
+  }
+  normals[i] = make_float4(nv[0], nv[1], nv[2], 0.f);
+  flags[i] = (fabsf(nv[2]) < kPfNormalThresh) ? 1 : 0;
+}
+
+// ================================================================================================ host side
+namespace {
+
+inline unsigned pf_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+// compact `in` (n points) by pf.flags into `out` (reserved for n points); *m = kept points (read back: the host waits here)
+int pf_compact(dgs_handle* h, const float4* in, int64_t n, DevBuf<float4>& out, bool flatten, int64_t* m) {
+  PfScratch& pf = h->pf;
+  *m = 0;
+  if (n == 0) return DGS_OK;
+  const unsigned nb = pf_blocks(n);
+  DGS_HIP_TRY(h, out.reserve((size_t)n));
+  DGS_HIP_TRY(h, pf.blk.reserve(nb));
+  DGS_HIP_TRY(h, pf.cnt.reserve(4));
+  hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, pf.flags.ptr, (int)n, pf.blk.ptr);
+  hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kPfScanBlock), 0, h->stream, pf.blk.ptr, (int)nb, pf.cnt.ptr);
+  hipLaunchKernelGGL(pf_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, in, pf.flags.ptr, (int)n, pf.blk.ptr, out.ptr, flatten ? 1 : 0);
+  DGS_HIP_TRY(h, hipGetLastError());
+  if (ensure_pinned(h, 4096) != DGS_OK) return DGS_ERR_HIP;
+  int* hc = reinterpret_cast<int*>(h->pinned);
+  DGS_HIP_TRY(h, hipMemcpyAsync(hc, pf.cnt.ptr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  *m = hc[0];
+  return DGS_OK;
+}
+
+int pf_reserve_flags(dgs_handle* h, int64_t n) {
+  DGS_HIP_TRY(h, h->pf.flags.reserve((size_t)std::max<int64_t>(n, 1)));
+  return DGS_OK;
+}
+
+// the cloud of a k-NN pass: a copy in PfScratch::cloud with a fresh index, and its k-NN lists in PfScratch::nbr
+int pf_knn(dgs_handle* h, const float4* in, int64_t n, int k) {
+  CloudState& c = h->pf.cloud;
+  DGS_HIP_TRY(h, c.pts.reserve((size_t)n));
+  DGS_HIP_TRY(h, hipMemcpyAsync(c.pts.ptr, in, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+  c.n = n;
+  c.invalidate();
+  return knn_lists(h, c, k, &h->pf.nbr);
+}
+
+int pf_distance(dgs_handle* h, const float4* in, int64_t n, double near_t, double far_t, DevBuf<float4>& out, int64_t* m) {
+  *m = 0;
+  if (n == 0) return DGS_OK;
+  if (int rc = pf_reserve_flags(h, n)) return rc;
+  hipLaunchKernelGGL(pf_distance_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, in, (int)n, near_t, far_t, h->pf.flags.ptr);
+  return pf_compact(h, in, n, out, false, m);
+}
+
+int pf_radius(dgs_handle* h, const float4* in, int64_t n, double radius, int min_neighbors, int inclusive, DevBuf<float4>& out, int64_t* m) {
+  *m = 0;
+  const int k = min_neighbors + 1;
+  if (min_neighbors < 0 || k > kKnnMax) {
+    h->err = "RadiusOutlierRemoval: min_neighbors + 1 must lie in 1..32 (the k-NN of the HIP index)";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 0) return DGS_OK;
+  if (n < k) return DGS_OK;   // fewer than k points: no point finds k neighbours, all are removed
+  if (int rc = pf_reserve_flags(h, n)) return rc;
+  if (int rc = pf_knn(h, in, n, k)) return rc;
+  const CloudState& c = h->pf.cloud;
+  hipLaunchKernelGGL(pf_radius_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, h->pf.nbr.ptr,
+                     radius * radius, inclusive, h->pf.flags.ptr);
+  return pf_compact(h, in, n, out, false, m);
+}
+
+int pf_statistical(dgs_handle* h, const float4* in, int64_t n, int mean_k, double mul, int sqrt_float, DevBuf<float4>& out, int64_t* m) {
+  *m = 0;
+  PfScratch& pf = h->pf;
+  if (mean_k < 1 || mean_k + 1 > kKnnMax) {
+    h->err = "StatisticalOutlierRemoval: mean_k + 1 must lie in 2..32 (the k-NN of the HIP index)";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  pf.stat_n = 0;
+  if (n == 0) return DGS_OK;
+  if (n <= mean_k) {
+    h->err = "StatisticalOutlierRemoval: the cloud has no more points than mean_k (upstream reads past its neighbour lists)";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  if (int rc = pf_reserve_flags(h, n)) return rc;
+  DGS_HIP_TRY(h, pf.mean_d.reserve((size_t)n));
+  DGS_HIP_TRY(h, pf.stats.reserve(4));
+  const int k = mean_k + 1;
+  if (int rc = pf_knn(h, in, n, k)) return rc;
+  const CloudState& c = pf.cloud;
+  hipLaunchKernelGGL(pf_sor_distance_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, pf.nbr.ptr,
+                     sqrt_float, pf.mean_d.ptr);
+  hipLaunchKernelGGL(pf_sor_stats_kernel, dim3(1), dim3(kPfScanBlock), 0, h->stream, pf.mean_d.ptr, (int)n, mul, pf.stats.ptr);
+  hipLaunchKernelGGL(pf_sor_flag_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, pf.mean_d.ptr, (int)n, pf.stats.ptr, pf.flags.ptr);
+  pf.stat_n = n;
+  return pf_compact(h, in, n, out, false, m);
+}
+
+int pf_normal(dgs_handle* h, const float4* in, int64_t n, const double* lidar, DevBuf<float4>& out, bool flatten, int64_t* m) {
+  *m = 0;
+  PfScratch& pf = h->pf;
+  pf.normal_n = 0;
+  if (n == 0) return DGS_OK;
+  if (int rc = pf_reserve_flags(h, n)) return rc;
+  DGS_HIP_TRY(h, pf.normals.reserve((size_t)n));
+  DGS_HIP_TRY(h, pf.cov9.reserve((size_t)n * 9));
+  const int k = (int)std::min<int64_t>(kPfNormalK, n);   // FLANN returns min(k, n) neighbours
+  if (int rc = pf_knn(h, in, n, k)) return rc;
+  const CloudState& c = pf.cloud;
+  // ne.setViewPoint(float, float, float)
+  hipLaunchKernelGGL(pf_normal_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, pf.nbr.ptr,
+                     (float)lidar[0], (float)lidar[1], (float)lidar[2], pf.flags.ptr, pf.normals.ptr, pf.cov9.ptr);
+  pf.normal_n = n;
+  return pf_compact(h, in, n, out, flatten, m);
+}
+
+int pf_begin(dgs_handle* h) {
+  h->err.clear();
+  DGS_HIP_TRY(h, hipSetDevice(h->device));
+  return DGS_OK;
+}
+
+// the input on the device: the caller's pointer, or a copy of the host array in PfScratch::in
+int pf_input(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t on_device, const float4** d) {
+  *d = reinterpret_cast<const float4*>(in_xyz16);
+  if (on_device || n == 0) return DGS_OK;
+  DGS_HIP_TRY(h, h->pf.in.reserve((size_t)n));
+  DGS_HIP_TRY(h, hipMemcpyAsync(h->pf.in.ptr, in_xyz16, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+  *d = h->pf.in.ptr;
+  return DGS_OK;
+}
+
+// result of a stage / the chain to the caller's buffer; the host waits for the stream before returning
+int pf_output(dgs_handle* h, const float4* src, int64_t m, float* out_xyz16, int64_t cap, int32_t on_device) {
+  if (m > cap) {
+    h->err = "output buffer too small for the filtered cloud";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  if (m > 0)
+    DGS_HIP_TRY(h, hipMemcpyAsync(out_xyz16, src, (size_t)m * sizeof(float4), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  return DGS_OK;
+}
+
+int pf_finish(dgs_handle* h, int rc) {
+  if (rc != DGS_OK) {
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  DGS_HIP_TRY(h, hipGetLastError());
+  return DGS_OK;
+}
+
+bool pf_bad_io(const float* in_xyz16, int64_t n, const float* out, const int64_t* n_out, int64_t cap) {
+  return !n_out || n < 0 || n > INT32_MAX || (n > 0 && !in_xyz16) || cap < 0 || (cap > 0 && !out);
+}
+
+}  // namespace
+
+void prefilter_release(dgs_handle* h) {
+  PfScratch& pf = h->pf;
+  for (DevBuf<float4>* b : {&pf.in, &pf.a, &pf.b, &pf.c, &pf.d, &pf.e, &pf.normals}) b->release();
+  pf.flags.release(); pf.blk.release(); pf.cnt.release(); pf.nbr.release(); pf.mean_d.release(); pf.stats.release(); pf.cov9.release();
+  pf.cloud.release();
+  pf.stat_n = pf.normal_n = 0;
+}
+
+}  // namespace dgs
+
+using namespace dgs;
+
+extern "C" {
+
+int dgs_prefilter_params_init(dgs_prefilter_params* p) {
+  if (!p) return DGS_ERR_INVALID_ARGUMENT;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->downsample_method = DGS_PF_DOWNSAMPLE_VOXELGRID;
+  p->downsample_resolution = 0.1;
+  p->outlier_removal_method = DGS_PF_OUTLIER_STATISTICAL;
+  p->statistical_mean_k = 20;
+  p->statistical_stddev = 1.0;
+  p->radius_radius = 0.8;
+  p->radius_min_neighbors = 2;
+  p->use_distance_filter = 1;
+  p->distance_near_thresh = 1.0;
+  p->distance_far_thresh = 100.0;
+  p->radius_inclusive = 1;
+  p->statistical_sqrt_float = 1;
+  return DGS_OK;
+}
+
+int dgs_prefilter(dgs_handle* h, const dgs_prefilter_params* p, const float* in_xyz16, int64_t n, int32_t in_on_device, const double* lidar_xyz,
+                  float* out3d, int64_t cap3d, float* out2d, int64_t cap2d, int32_t out_on_device, int64_t* n3d_out, int64_t* n2d_out) {
+  if (!h || !p || p->struct_size != sizeof(dgs_prefilter_params) || pf_bad_io(in_xyz16, n, out3d, n3d_out, cap3d) || !n2d_out || cap2d < 0 ||
+      (cap2d > 0 && !out2d))
+    return DGS_ERR_INVALID_ARGUMENT;
+  if (p->downsample_method < DGS_PF_DOWNSAMPLE_NONE || p->downsample_method > DGS_PF_DOWNSAMPLE_APPROX_VOXELGRID ||
+      p->outlier_removal_method < DGS_PF_OUTLIER_NONE || p->outlier_removal_method > DGS_PF_OUTLIER_RADIUS ||
+      (p->downsample_method != DGS_PF_DOWNSAMPLE_NONE && !(p->downsample_resolution > 0)))
+    return DGS_ERR_INVALID_ARGUMENT;
+  *n3d_out = 0;
+  *n2d_out = 0;
+  if (int rc = pf_begin(h)) return rc;
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  const double* lidar = lidar_xyz ? lidar_xyz : zero3;
+  PfScratch& pf = h->pf;
+  pf.stat_n = pf.normal_n = 0;
+  if (n == 0) return DGS_OK;   // cloud_callback returns on an empty cloud (:116-118): nothing is published
+  const float4* in = nullptr;
+  int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
+  // 1. distance filter (applied whatever use_distance_filter says, :153)
+  int64_t n1 = 0;
+  if (rc == DGS_OK) rc = pf_distance(h, in, n, p->distance_near_thresh, p->distance_far_thresh, pf.a, &n1);
+  // 2. down-sampling: the voxel filters' own code paths (ndt_voxel.hip)
+  const float4* s2 = pf.a.ptr;
+  int64_t n2 = n1;
+  if (rc == DGS_OK && n1 > 0 && p->downsample_method != DGS_PF_DOWNSAMPLE_NONE) {
+    if (pf.b.reserve((size_t)n1) != hipSuccess) { h->err = "hipMalloc failed"; return pf_finish(h, DGS_ERR_HIP); }
+    const float leaf = (float)p->downsample_resolution;   // setLeafSize(float, float, float)
+    rc = p->downsample_method == DGS_PF_DOWNSAMPLE_VOXELGRID ? voxel_grid_filter(h, pf.a.ptr, n1, leaf, pf.b.ptr, n1, &n2)
+                                                             : approx_voxel_grid_filter(h, pf.a.ptr, n1, leaf, pf.b.ptr, n1, &n2);
+    s2 = pf.b.ptr;
+  }
+  // 3. outlier removal -> /filtered_points
+  const float4* s3 = s2;
+  int64_t n3 = n2;
+  if (rc == DGS_OK && p->outlier_removal_method == DGS_PF_OUTLIER_STATISTICAL) {
+    rc = pf_statistical(h, s2, n2, p->statistical_mean_k, p->statistical_stddev, p->statistical_sqrt_float, pf.c, &n3);
+    s3 = pf.c.ptr;
+  } else if (rc == DGS_OK && p->outlier_removal_method == DGS_PF_OUTLIER_RADIUS) {
+    rc = pf_radius(h, s2, n2, p->radius_radius, p->radius_min_neighbors, p->radius_inclusive, pf.c, &n3);
+    s3 = pf.c.ptr;
+  }
+  // 4. height filter, 5. normal filter + 6. flatten (the scatter of the normal pass writes z = 0)
+  int64_t n4 = 0, n5 = 0;
+  if (rc == DGS_OK && n3 > 0) {
+    if ((rc = pf_reserve_flags(h, n3)) == DGS_OK) {
+      hipLaunchKernelGGL(pf_height_kernel, dim3(pf_blocks(n3)), dim3(kBlock), 0, h->stream, s3, (int)n3, lidar[2], pf.flags.ptr);
+      rc = pf_compact(h, s3, n3, pf.d, false, &n4);
+    }
+  }
+  if (rc == DGS_OK && n4 > 0) rc = pf_normal(h, pf.d.ptr, n4, lidar, pf.e, true, &n5);
+  if (rc == DGS_OK) {
+    *n3d_out = n3;
+    *n2d_out = n5;
+    rc = pf_output(h, s3, n3, out3d, cap3d, out_on_device);
+    if (rc == DGS_OK) rc = pf_output(h, pf.e.ptr, n5, out2d, cap2d, out_on_device);
+  }
+  return pf_finish(h, rc);
+}
+
+int dgs_prefilter_distance(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, double near_t, double far_t, float* out_xyz16,
+                           int64_t cap, int32_t out_on_device, int64_t* n_out) {
+  if (!h || pf_bad_io(in_xyz16, n, out_xyz16, n_out, cap)) return DGS_ERR_INVALID_ARGUMENT;
+  *n_out = 0;
+  if (int rc = pf_begin(h)) return rc;
+  const float4* in = nullptr;
+  int64_t m = 0;
+  int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
+  if (rc == DGS_OK) rc = pf_distance(h, in, n, near_t, far_t, h->pf.a, &m);
+  if (rc == DGS_OK) { *n_out = m; rc = pf_output(h, h->pf.a.ptr, m, out_xyz16, cap, out_on_device); }
+  return pf_finish(h, rc);
+}
+
+int dgs_prefilter_radius(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, double radius, int32_t min_neighbors, int32_t inclusive,
+                         float* out_xyz16, int64_t cap, int32_t out_on_device, int64_t* n_out) {
+  if (!h || pf_bad_io(in_xyz16, n, out_xyz16, n_out, cap)) return DGS_ERR_INVALID_ARGUMENT;
+  *n_out = 0;
+  if (int rc = pf_begin(h)) return rc;
+  const float4* in = nullptr;
+  int64_t m = 0;
+  int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
+  if (rc == DGS_OK) rc = pf_radius(h, in, n, radius, min_neighbors, inclusive, h->pf.c, &m);
+  if (rc == DGS_OK) { *n_out = m; rc = pf_output(h, h->pf.c.ptr, m, out_xyz16, cap, out_on_device); }
+  return pf_finish(h, rc);
+}
+
+int dgs_prefilter_statistical(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, int32_t mean_k, double stddev_mul,
+                              int32_t sqrt_float, float* out_xyz16, int64_t cap, int32_t out_on_device, int64_t* n_out) {
+  if (!h || pf_bad_io(in_xyz16, n, out_xyz16, n_out, cap)) return DGS_ERR_INVALID_ARGUMENT;
+  *n_out = 0;
+  if (int rc = pf_begin(h)) return rc;
+  const float4* in = nullptr;
+  int64_t m = 0;
+  int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
+  if (rc == DGS_OK) rc = pf_statistical(h, in, n, mean_k, stddev_mul, sqrt_float, h->pf.c, &m);
+  if (rc == DGS_OK) { *n_out = m; rc = pf_output(h, h->pf.c.ptr, m, out_xyz16, cap, out_on_device); }
+  return pf_finish(h, rc);
+}
+
+int dgs_prefilter_normal(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, const double* lidar_xyz, float* out_xyz16,
+                         int64_t cap, int32_t out_on_device, int64_t* n_out) {
+  if (!h || pf_bad_io(in_xyz16, n, out_xyz16, n_out, cap)) return DGS_ERR_INVALID_ARGUMENT;
+  *n_out = 0;
+  if (int rc = pf_begin(h)) return rc;
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  const float4* in = nullptr;
+  int64_t m = 0;
+  int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
+  if (rc == DGS_OK) rc = pf_normal(h, in, n, lidar_xyz ? lidar_xyz : zero3, h->pf.e, false, &m);
+  if (rc == DGS_OK) { *n_out = m; rc = pf_output(h, h->pf.e.ptr, m, out_xyz16, cap, out_on_device); }
+  return pf_finish(h, rc);
+}
+
+int dgs_prefilter_get_statistics(dgs_handle* h, float* mean_distances, int64_t capacity, double* stats4, int64_t* n) {
+  if (!h || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
+  if (int rc = pf_begin(h)) return rc;
+  const int64_t m = h->pf.stat_n;
+  *n = m;
+  if (m == 0) return DGS_OK;
+  if (mean_distances && capacity >= m)
+    DGS_HIP_TRY(h, hipMemcpyAsync(mean_distances, h->pf.mean_d.ptr, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (stats4) {
+    DGS_HIP_TRY(h, hipMemcpyAsync(stats4, h->pf.stats.ptr, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    stats4[3] = (double)m;
+  }
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return DGS_OK;
+}
+
+int dgs_prefilter_get_normals(dgs_handle* h, float* normals4, float* cov9, int64_t capacity, int64_t* n) {
+  if (!h || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
+  if (int rc = pf_begin(h)) return rc;
+  const int64_t m = h->pf.normal_n;
+  *n = m;
+  if (m == 0 || capacity < m) return DGS_OK;
+  if (normals4) DGS_HIP_TRY(h, hipMemcpyAsync(normals4, h->pf.normals.ptr, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+  if (cov9) DGS_HIP_TRY(h, hipMemcpyAsync(cov9, h->pf.cov9.ptr, (size_t)m * 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return DGS_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,159 @@
+"""PrefilteringNodelet's filter chain on the device: /root/reference/apps/prefiltering_nodelet.cpp:111-164 from the distance filter
+to flatten, over dgs_prefilter (include/dgs_reg.h).
+
+`Prefilter(params)` takes the nodelet's private parameter names with initialize_params' defaults (:55-109);
+`cloud_callback(cloud, lidar_position)` returns (/filtered_points, /flat_filtered_points).  Deskewing and the base_link transform stay
+with the caller, which passes lidar_position.  Clouds are float32 [N,4]: numpy in gives numpy out, a device tensor in gives device
+tensors out.  Like InformationMatrixCalculator, a Prefilter may share a Registration's handle: it uses buffers and an NN index of
+its own, so the registration's target, source and results are untouched.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import _lib as L
+from .registration import Registration, _cloud_ptr, torch
+
+__all__ = ["Prefilter", "params_from_dict"]
+
+
+def params_from_dict(params: Optional[dict] = None) -> L.PrefilterParams:
+    """initialize_params (:55-109): the nodelet's parameter names and defaults.  An unknown downsample_method is NONE (:71-76), an
+    unknown outlier_removal_method is NONE (:97-99); use_distance_filter is read (:100) and ignored, as upstream (:153)."""
+    pr = dict(params or {})
+    lib = L.load()
+    p = L.PrefilterParams()
+    rc = lib.dgs_prefilter_params_init(C.byref(p))
+    if rc:
+        raise L.DgsError(rc, "dgs_prefilter_params_init")
+    p.downsample_method = L.PF_DOWNSAMPLE.get(str(pr.get("downsample_method", "VOXELGRID")), L.PF_DOWNSAMPLE["NONE"])
+    p.downsample_resolution = float(pr.get("downsample_resolution", p.downsample_resolution))
+    p.outlier_removal_method = L.PF_OUTLIER.get(str(pr.get("outlier_removal_method", "STATISTICAL")), L.PF_OUTLIER["NONE"])
+    p.statistical_mean_k = int(pr.get("statistical_mean_k", p.statistical_mean_k))
+    p.statistical_stddev = float(pr.get("statistical_stddev", p.statistical_stddev))
+    p.radius_radius = float(pr.get("radius_radius", p.radius_radius))
+    p.radius_min_neighbors = int(pr.get("radius_min_neighbors", p.radius_min_neighbors))
+    p.use_distance_filter = 1 if pr.get("use_distance_filter", True) else 0
+    p.distance_near_thresh = float(pr.get("distance_near_thresh", p.distance_near_thresh))
+    p.distance_far_thresh = float(pr.get("distance_far_thresh", p.distance_far_thresh))
+    p.radius_inclusive = 1 if pr.get("radius_inclusive", True) else 0
+    p.statistical_sqrt_float = 1 if pr.get("statistical_sqrt_float", True) else 0
+    return p
+
+
+class Prefilter:
+    def __init__(self, params: Optional[dict] = None, registration: Optional[Registration] = None, device: Optional[int] = None):
+        self.params = params_from_dict(params)
+        if registration is None:
+            registration = Registration("NDT_OMP", device=device)   # any handle: only its stream and the prefilter's own buffers are used
+        self.registration = registration
+        self._lib = registration._lib
+
+    @property
+    def _h(self):
+        return self.registration._h
+
+    def _check(self, rc: int):
+        self.registration._check(rc)
+
+    @staticmethod
+    def _lidar(lidar_position):
+        return (C.c_double * 3)(*[float(v) for v in lidar_position])
+
+    def _new(self, like, n: int):
+        if _is_device(like):
+            return torch.empty((max(n, 1), 4), dtype=torch.float32, device=like.device)
+        return np.empty((max(n, 1), 4), dtype=np.float32)
+
+    @staticmethod
+    def _ptr(out):
+        return C.c_void_p(out.data_ptr()) if _is_device(out) else out.ctypes.data_as(C.c_void_p)
+
+    @staticmethod
+    def _take(out, m: int):
+        return out[:m] if _is_device(out) else out[:m].copy()
+
+    def cloud_callback(self, cloud, lidar_position=(0.0, 0.0, 0.0)):
+        """-> (filtered3d, filtered2d): what cloud_callback publishes on /filtered_points and /flat_filtered_points."""
+        ptr, n, dev, keep = _cloud_ptr(cloud)
+        o3, o2 = self._new(cloud, n), self._new(cloud, n)
+        m3, m2 = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dgs_prefilter(self._h, C.byref(self.params), ptr, n, dev, self._lidar(lidar_position), self._ptr(o3), n,
+                                            self._ptr(o2), n, dev, C.byref(m3), C.byref(m2)))
+        return self._take(o3, m3.value), self._take(o2, m2.value)
+
+    def _stage(self, fn, cloud, *args):
+        ptr, n, dev, keep = _cloud_ptr(cloud)
+        out = self._new(cloud, n)
+        m = C.c_int64(0)
+        self._check(fn(self._h, ptr, n, dev, *args, self._ptr(out), n, dev, C.byref(m)))
+        return self._take(out, m.value)
+
+    # -- single stages ------------------------------------------------------------------------------------------------------
+    def distance_filter(self, cloud):
+        p = self.params
+        return self._stage(self._lib.dgs_prefilter_distance, cloud, p.distance_near_thresh, p.distance_far_thresh)
+
+    def downsample(self, cloud):
+        p = self.params
+        if p.downsample_method == L.PF_DOWNSAMPLE["NONE"]:
+            return cloud
+        return self.registration.voxel_grid_filter(cloud, p.downsample_resolution, approximate=p.downsample_method == L.PF_DOWNSAMPLE["APPROX_VOXELGRID"])
+
+    def radius_outlier_removal(self, cloud):
+        p = self.params
+        return self._stage(self._lib.dgs_prefilter_radius, cloud, p.radius_radius, p.radius_min_neighbors, p.radius_inclusive)
+
+    def statistical_outlier_removal(self, cloud):
+        p = self.params
+        return self._stage(self._lib.dgs_prefilter_statistical, cloud, p.statistical_mean_k, p.statistical_stddev, p.statistical_sqrt_float)
+
+    def outlier_removal(self, cloud):
+        m = self.params.outlier_removal_method
+        if m == L.PF_OUTLIER["STATISTICAL"]:
+            return self.statistical_outlier_removal(cloud)
+        if m == L.PF_OUTLIER["RADIUS"]:
+            return self.radius_outlier_removal(cloud)
+        return cloud
+
+    def height_filtering(self, cloud, lidar_position=(0.0, 0.0, 0.0)):
+        """:192-212, a plain predicate: kept iff z > lidar_position.z in double (on the host side of the caller's array)."""
+        if _is_device(cloud):
+            return cloud[cloud[:, 2].double() > float(lidar_position[2])]
+        a = np.asarray(cloud, np.float32)
+        return a[a[:, 2].astype(np.float64) > float(lidar_position[2])].copy()
+
+    def normal_filtering(self, cloud, lidar_position=(0.0, 0.0, 0.0)):
+        return self._stage(self._lib.dgs_prefilter_normal, cloud, self._lidar(lidar_position))
+
+    @staticmethod
+    def flatten(cloud):
+        out = cloud.clone() if _is_device(cloud) else np.array(cloud, np.float32, copy=True)
+        out[:, 2] = 0.0
+        return out
+
+    # -- test hooks ----------------------------------------------------------------------------------------------------------
+    def statistics(self):
+        """Last statistical pass: (per-point mean distances float32 [n], {mean, stddev, threshold, n})."""
+        n = C.c_int64(0)
+        self._check(self._lib.dgs_prefilter_get_statistics(self._h, None, 0, None, C.byref(n)))
+        d = np.empty(n.value, np.float32)
+        s = np.zeros(4, np.float64)
+        self._check(self._lib.dgs_prefilter_get_statistics(self._h, d.ctypes.data_as(C.c_void_p), n.value, s.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return d, dict(mean=s[0], stddev=s[1], threshold=s[2], n=int(s[3]))
+
+    def normals(self):
+        """Last normal pass: (normals float32 [n,4] normalised and flipped, covariances float32 [n,9] row-major)."""
+        n = C.c_int64(0)
+        self._check(self._lib.dgs_prefilter_get_normals(self._h, None, None, 0, C.byref(n)))
+        nv = np.empty((n.value, 4), np.float32)
+        cv = np.empty((n.value, 9), np.float32)
+        self._check(self._lib.dgs_prefilter_get_normals(self._h, nv.ctypes.data_as(C.c_void_p), cv.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return nv, cv
+
+
+def _is_device(x) -> bool:
+    return torch is not None and isinstance(x, torch.Tensor) and x.is_cuda

@@ -1,0 +1,94 @@
+// dgs::HipPrefilter -- PrefilteringNodelet::cloud_callback's filter chain (apps/prefiltering_nodelet.cpp:111-164, distance filter
+// to flatten) over libdgs_reg.so (include/dgs_reg.h, dgs_prefilter).  INTEGRATION.md shows the patch to the nodelet.
+// Header-only; needs pcl::PointCloud at the user's build.  Built from the nodelet's private parameters (initialize_params,
+// :55-109, same names and defaults); filter(src, lidar_position, filtered3d, filtered2d) gives what cloud_callback publishes on
+// /filtered_points and /flat_filtered_points.  Deskewing and the base_link transform stay in the nodelet.  The handle is created
+// at the first filter call; a failure of any kind never throws: filter() returns false and leaves both outputs empty.
+#pragma once
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include <pcl/point_cloud.h>
+
+#include "../dgs_reg.h"
+
+namespace dgs {
+
+template <typename PointT>
+class HipPrefilter {
+ public:
+  // NodeHandle: anything with param<T>(name, default), e.g. ros::NodeHandle (private_nh)
+  template <typename NodeHandle>
+  explicit HipPrefilter(NodeHandle& private_nh, int device = 0) : device_(device) {
+    dgs_prefilter_params_init(&p_);
+    const std::string ds = private_nh.template param<std::string>("downsample_method", "VOXELGRID");
+    p_.downsample_method = ds == "VOXELGRID" ? DGS_PF_DOWNSAMPLE_VOXELGRID : ds == "APPROX_VOXELGRID" ? DGS_PF_DOWNSAMPLE_APPROX_VOXELGRID : DGS_PF_DOWNSAMPLE_NONE;
+    p_.downsample_resolution = private_nh.template param<double>("downsample_resolution", 0.1);
+    const std::string om = private_nh.template param<std::string>("outlier_removal_method", "STATISTICAL");
+    p_.outlier_removal_method = om == "STATISTICAL" ? DGS_PF_OUTLIER_STATISTICAL : om == "RADIUS" ? DGS_PF_OUTLIER_RADIUS : DGS_PF_OUTLIER_NONE;
+    p_.statistical_mean_k = private_nh.template param<int>("statistical_mean_k", 20);
+    p_.statistical_stddev = private_nh.template param<double>("statistical_stddev", 1.0);
+    p_.radius_radius = private_nh.template param<double>("radius_radius", 0.8);
+    p_.radius_min_neighbors = private_nh.template param<int>("radius_min_neighbors", 2);
+    p_.use_distance_filter = private_nh.template param<bool>("use_distance_filter", true) ? 1 : 0;   // read and ignored, as upstream (:153)
+    p_.distance_near_thresh = private_nh.template param<double>("distance_near_thresh", 1.0);
+    p_.distance_far_thresh = private_nh.template param<double>("distance_far_thresh", 100.0);
+  }
+  ~HipPrefilter() {
+    if (h_) dgs_destroy(h_);
+  }
+  HipPrefilter(const HipPrefilter&) = delete;
+  HipPrefilter& operator=(const HipPrefilter&) = delete;
+
+  const dgs_prefilter_params& params() const { return p_; }
+  const char* last_error() const { return dgs_last_error(h_); }
+
+  bool filter(const pcl::PointCloud<PointT>& src, const double lidar_position[3], pcl::PointCloud<PointT>& filtered3d, pcl::PointCloud<PointT>& filtered2d) {
+    filtered3d.points.clear();
+    filtered2d.points.clear();
+    const size_t n = src.points.size();
+    if (!ensure_handle()) return false;
+    in_.resize(4 * n);
+    for (size_t i = 0; i < n; i++) {   // pcl::PointXYZ: x, y, z and the pad lane
+      std::memcpy(&in_[4 * i], &src.points[i], 3 * sizeof(float));
+      in_[4 * i + 3] = 1.f;
+    }
+    out3_.resize(4 * (n ? n : 1));
+    out2_.resize(4 * (n ? n : 1));
+    int64_t n3 = 0, n2 = 0;
+    if (dgs_prefilter(h_, &p_, in_.data(), (int64_t)n, 0, lidar_position, out3_.data(), (int64_t)n, out2_.data(), (int64_t)n, 0, &n3, &n2) != DGS_OK)
+      return false;
+    unpack(out3_, n3, filtered3d);
+    unpack(out2_, n2, filtered2d);
+    return true;
+  }
+
+ private:
+  bool ensure_handle() {
+    if (h_) return true;
+    dgs_params prm;
+    if (dgs_params_init(&prm, DGS_METHOD_NDT) != DGS_OK) return false;
+    prm.device = device_;
+    return dgs_create(&prm, &h_) == DGS_OK;
+  }
+  static void unpack(const std::vector<float>& buf, int64_t m, pcl::PointCloud<PointT>& out) {
+    out.points.resize((size_t)m);
+    for (int64_t i = 0; i < m; i++) {
+      out.points[i].x = buf[4 * i];
+      out.points[i].y = buf[4 * i + 1];
+      out.points[i].z = buf[4 * i + 2];
+    }
+    out.width = (uint32_t)m;
+    out.height = 1;
+    out.is_dense = false;
+  }
+
+  dgs_prefilter_params p_{};
+  dgs_handle* h_ = nullptr;
+  int device_ = 0;
+  std::vector<float> in_, out3_, out2_;
+};
+
+}  // namespace dgs

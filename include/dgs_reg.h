@@ -412,6 +412,57 @@ int dgs_gicp_linearize(dgs_handle* h, const double* T16_rowmajor, int32_t error_
  * mean double[3], cov double[9] per voxel; *n_voxels is always set, arrays are filled when capacity suffices. */
 int dgs_vgicp_get_voxels(dgs_handle* h, int64_t capacity, int32_t* coord3, int32_t* counts, double* mean3, double* cov9, int64_t* n_voxels);
 
+/* ---- PrefilteringNodelet::cloud_callback on the device (/root/reference/apps/prefiltering_nodelet.cpp:111-164) ---------------
+ * The chain from the distance filter to flatten: distance filter (:275-291) -> down-sampling (:249-260) -> outlier removal
+ * (:262-273) = /filtered_points; then height filter (:192-212) -> normal filter (:217-245) -> flatten (:166-188) =
+ * /flat_filtered_points.  Deskewing and the base_link transform stay with the caller, which passes lidar_position
+ * (Eigen::Vector3d, 3 doubles; NULL = origin).  Every pass-through filter keeps the input order and copies the whole 16-byte point.
+ * The prefilter works in buffers and an NN index of its own: the handle's registration target / source / NDT model / results are
+ * untouched (as dgs_calc_fitness_score).  Semantics, including the PCL 1.10 details recalled from upstream: DESIGN.md §6c. */
+enum dgs_prefilter_downsample { DGS_PF_DOWNSAMPLE_NONE = 0, DGS_PF_DOWNSAMPLE_VOXELGRID = 1, DGS_PF_DOWNSAMPLE_APPROX_VOXELGRID = 2 };
+enum dgs_prefilter_outlier { DGS_PF_OUTLIER_NONE = 0, DGS_PF_OUTLIER_STATISTICAL = 1, DGS_PF_OUTLIER_RADIUS = 2 };
+/* Defaults (dgs_prefilter_params_init) = initialize_params (:55-109): VOXELGRID 0.1, STATISTICAL 20 / 1.0, RADIUS 0.8 / 2,
+ * distance 1.0 .. 100.0.  use_distance_filter is read upstream (:100) but the filter runs unconditionally (:153): accepted, ignored.
+ * radius_inclusive: RadiusOutlierRemoval keeps a point iff its k-th neighbour distance d^2 <= r^2 (1, PCL 1.10) or < r^2 (0).
+ * statistical_sqrt_float: StatisticalOutlierRemoval sums sqrt of the float d^2 in float (1, PCL 1.10's sqrt(float)) or in double (0). */
+typedef struct dgs_prefilter_params {
+  uint32_t struct_size;             /* sizeof(dgs_prefilter_params), set by dgs_prefilter_params_init */
+  int32_t downsample_method;        /* dgs_prefilter_downsample */
+  double downsample_resolution;
+  int32_t outlier_removal_method;   /* dgs_prefilter_outlier */
+  int32_t statistical_mean_k;
+  double statistical_stddev;
+  double radius_radius;
+  int32_t radius_min_neighbors;
+  int32_t use_distance_filter;
+  double distance_near_thresh;
+  double distance_far_thresh;
+  int32_t radius_inclusive;
+  int32_t statistical_sqrt_float;
+} dgs_prefilter_params;
+int dgs_prefilter_params_init(dgs_prefilter_params* params);
+/* The whole chain.  out3d receives /filtered_points, out2d /flat_filtered_points (host arrays, or device pointers with
+ * out_on_device); *n3d_out / *n2d_out are always the full counts, DGS_ERR_INVALID_ARGUMENT when one exceeds its capacity.
+ * DGS_ERR_INVALID_ARGUMENT also for STATISTICAL with 0 < points <= statistical_mean_k, and for k-NN sizes above 32
+ * (statistical_mean_k + 1, radius_min_neighbors + 1). */
+int dgs_prefilter(dgs_handle* h, const dgs_prefilter_params* params, const float* in_xyz16, int64_t n, int32_t in_on_device, const double* lidar_xyz,
+                  float* out3d_xyz16, int64_t cap3d, float* out2d_xyz16, int64_t cap2d, int32_t out_on_device, int64_t* n3d_out, int64_t* n2d_out);
+/* Single stages (same argument conventions; the inputs of the k-NN stages must be finite, as the chain guarantees). */
+int dgs_prefilter_distance(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, double near_thresh, double far_thresh, float* out_xyz16,
+                           int64_t out_capacity, int32_t out_on_device, int64_t* n_out);
+int dgs_prefilter_radius(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, double radius, int32_t min_neighbors, int32_t inclusive,
+                         float* out_xyz16, int64_t out_capacity, int32_t out_on_device, int64_t* n_out);
+int dgs_prefilter_statistical(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, int32_t mean_k, double stddev_mul, int32_t sqrt_float,
+                              float* out_xyz16, int64_t out_capacity, int32_t out_on_device, int64_t* n_out);
+/* normal_filtering (:217-245) alone: NormalEstimation with k = 10 over the given cloud, viewpoint lidar_xyz, keep |n.z| < 0.2f. */
+int dgs_prefilter_normal(dgs_handle* h, const float* in_xyz16, int64_t n, int32_t in_on_device, const double* lidar_xyz, float* out_xyz16,
+                         int64_t out_capacity, int32_t out_on_device, int64_t* n_out);
+/* Test hooks over the last statistical pass: per-point mean neighbour distances (input order) and stats4 = {mean, stddev, threshold,
+ * points}; and over the last normal pass: per-point normals4 (the normalised, flipped normal; NaN where upstream's is NaN) and the
+ * 9 floats of computeMeanAndCovarianceMatrix (row-major).  *n is always set; arrays (nullable) are filled when capacity suffices. */
+int dgs_prefilter_get_statistics(dgs_handle* h, float* mean_distances, int64_t capacity, double* stats4, int64_t* n);
+int dgs_prefilter_get_normals(dgs_handle* h, float* normals4, float* cov9, int64_t capacity, int64_t* n);
+
 #ifdef __cplusplus
 }
 #endif
