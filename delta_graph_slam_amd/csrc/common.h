@@ -18,6 +18,7 @@ constexpr int kMaxPartialBlocks = 1024;  // per pair
 constexpr int kStrictAccum = 43;   // ndt_strict_order: score + 6 gradient + the full 6x6 Hessian (upstream's is not exactly symmetric)
 constexpr int kStrictPad = 48;
 constexpr int kTrajCap = 72;
+constexpr float kIdentity16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // the guess of a caller that gives none
 
 // ---- NDT voxel-Gaussian target model in HBM ------------------------------------------------------------
 // One 48-byte record per occupied voxel (three 16-byte loads): the mean stays double because upstream forms
@@ -239,7 +240,7 @@ __device__ inline bool deal_workgroup(const int n_pairs, const int cap_blocks, P
 }
 #endif
 
-// ---- in-launch hand-off of partial rows to a pair's closing workgroup (fused NDT / GICP launches) ------------------------------------
+// ---- in-launch hand-off of partial rows to a pair's closing workgroup (fused NDT / GICP launches; ICP_HIP / GICP_HIP: slice_rows.h) ----
 // Default = the WRITE-THROUGH form of the agent-scope recipe: every byte of a row is stored with an agent-scope atomic store
 // (sc1: written through to memory, never left dirty in this XCD's L2), the storing wave drains its stores (s_waitcnt vmcnt(0)), a
 // workgroup barrier, then ONE lane takes the pair's ticket with an agent-scope atomic add; the workgroup whose add came last reads

@@ -35,6 +35,22 @@ int ensure_poll_events(dgs_handle* h) {
   return DGS_OK;
 }
 
+// The methods a handle can be made for (dgs_method), and what dgs_align / the batch calls run for each.  NDT keeps its own branch there.
+static bool valid_method(int32_t m) { return m >= DGS_METHOD_NDT && m <= DGS_METHOD_PCL_GICP; }
+struct MethodOps {
+  int (*align)(dgs_handle*, const float* guess16, dgs_result*);
+  int (*align_batch)(dgs_handle*, int n, CloudState* const* srcs, const float* guesses16, dgs_result*);
+  const float* (*final_transforms)(dgs_handle*, size_t* stride_bytes);
+};
+static const MethodOps kMethodOps[] = {
+    {nullptr, nullptr, nullptr},                                                // DGS_METHOD_NDT
+    {gicp_align, gicp_align_batch, gicp_final_transforms},                      // DGS_METHOD_GICP
+    {gicp_align, gicp_align_batch, gicp_final_transforms},                      // DGS_METHOD_VGICP
+    {icp_align, icp_align_batch, icp_final_transforms},                         // DGS_METHOD_ICP
+    {pcl_gicp_align, pcl_gicp_align_batch, pcl_gicp_final_transforms},          // DGS_METHOD_PCL_GICP
+};
+static_assert(sizeof(kMethodOps) / sizeof(kMethodOps[0]) == DGS_METHOD_PCL_GICP + 1, "one row per dgs_method");
+
 // The side stream is created together with the handle's own stream (dgs_create), not at first use: HIP deals streams to a small number
 // of hardware queues (GPU_MAX_HW_QUEUES, 4 by default) in creation order, and two streams on one hardware queue run one after the
 // other.  Created back to back the two get neighbouring queues; created lazily -- after RCCL had made its streams for a dgs_group --
@@ -282,9 +298,7 @@ int dgs_params_init(dgs_params* p, int32_t method) {
   p->gicp_lm_max_iterations = 10;
   p->vgicp_search_method = DGS_VGICP_DIRECT1;
   p->vgicp_resolution = 1.0;
-  if (method != DGS_METHOD_NDT && method != DGS_METHOD_GICP && method != DGS_METHOD_VGICP && method != DGS_METHOD_ICP && method != DGS_METHOD_PCL_GICP)
-    return DGS_ERR_INVALID_ARGUMENT;
-  return DGS_OK;
+  return valid_method(method) ? DGS_OK : DGS_ERR_INVALID_ARGUMENT;
 }
 
 int dgs_pcl_gicp_options_init(dgs_pcl_gicp_options* o) {
@@ -334,9 +348,8 @@ int dgs_pcl_gicp_set_probe(dgs_handle* h, const float* T16, const float* guess16
   if (!h) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   if (h->prm.method != DGS_METHOD_PCL_GICP) return DGS_ERR_UNSUPPORTED;
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  std::memcpy(h->pg_probe_T, T16 ? T16 : ident, sizeof(h->pg_probe_T));
-  std::memcpy(h->pg_probe_guess, guess16 ? guess16 : ident, sizeof(h->pg_probe_guess));
+  std::memcpy(h->pg_probe_T, T16 ? T16 : kIdentity16, sizeof(h->pg_probe_T));
+  std::memcpy(h->pg_probe_guess, guess16 ? guess16 : kIdentity16, sizeof(h->pg_probe_guess));
   return DGS_OK;
 }
 
@@ -381,9 +394,7 @@ int dgs_icp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, double* mse
 
 int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (!params || !out || params->struct_size != sizeof(dgs_params)) return DGS_ERR_INVALID_ARGUMENT;
-  if (params->method != DGS_METHOD_NDT && params->method != DGS_METHOD_GICP && params->method != DGS_METHOD_VGICP && params->method != DGS_METHOD_ICP &&
-      params->method != DGS_METHOD_PCL_GICP)
-    return DGS_ERR_INVALID_ARGUMENT;
+  if (!valid_method(params->method)) return DGS_ERR_INVALID_ARGUMENT;
   if (params->method == DGS_METHOD_VGICP && (!(params->vgicp_resolution > 0) || params->vgicp_search_method < 0 || params->vgicp_search_method > DGS_VGICP_DIRECT27))
     return DGS_ERR_INVALID_ARGUMENT;
   if (!(params->ndt_resolution > 0) || params->maximum_iterations < 0 || params->gicp_correspondence_randomness < 1) return DGS_ERR_INVALID_ARGUMENT;
@@ -474,9 +485,8 @@ void dgs_destroy(dgs_handle* h) {
   h->pairs.release(); h->inits.release(); h->partials.release(); h->done_counter.release(); h->ndt_queue.release(); h->ndt_ring.release(); h->pair_blocks.release(); h->src_ptrs.release(); h->src_sizes.release();
   h->nn_partials.release(); h->scratch_cloud.release(); h->strict_rows.release(); h->strict_totals.release(); h->tgt_grid.release(); h->aux_grid.release();
   h->fc_in.release(); h->fc_out.release(); h->fc_cnt.release();
-  h->aux_cloud1.release(); h->aux_cloud2.release(); h->aux_out.release(); h->aux_bvh.sorted.release(); h->aux_bvh.node_lo.release(); h->aux_bvh.node_hi.release();
-  h->aux_bvh.keys.release(); h->aux_bvh.keys_alt.release(); h->aux_bvh.vals.release(); h->aux_bvh.vals_alt.release();
-  h->corr.release(); h->corr_sq.release(); h->mahal.release(); h->gpairs.release();
+  h->aux_cloud1.release(); h->aux_cloud2.release(); h->aux_out.release(); h->aux_bvh.release();
+  h->corr.release(); h->corr_sq.release(); h->mahal.release(); h->gpairs.release(); h->slice_blk_pair.release(); h->slice_rows.release();
   for (auto& ep : h->prof.pool) { (void)hipEventDestroy(ep.start); (void)hipEventDestroy(ep.stop); }
   if (h->pinned) (void)hipHostFree(h->pinned);
   if (h->done_flags) (void)hipHostFree(h->done_flags);
@@ -612,8 +622,7 @@ int dgs_set_input_source_cloud(dgs_handle* h, dgs_cloud* c) {
 }
 
 static void fail_result(dgs_result* r, const float* guess, int status) {
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  std::memcpy(r->final_transformation, guess ? guess : ident, sizeof(float) * 16);
+  std::memcpy(r->final_transformation, guess ? guess : kIdentity16, sizeof(float) * 16);
   r->converged = 0;
   r->iterations = 0;
   r->evaluations = 0;
@@ -634,12 +643,8 @@ int dgs_align(dgs_handle* h, const float* guess16, dgs_result* out, float* align
     const float4* src = h->src->pts.ptr;
     const int n = (int)h->ns;
     rc = ndt_align_pairs(h, 1, &src, &n, guess16, out);
-  } else if (h->prm.method == DGS_METHOD_ICP) {
-    rc = icp_align(h, guess16, out);
-  } else if (h->prm.method == DGS_METHOD_PCL_GICP) {
-    rc = pcl_gicp_align(h, guess16, out);
   } else {
-    rc = gicp_align(h, guess16, out);
+    rc = kMethodOps[h->prm.method].align(h, guess16, out);
   }
   if (rc != DGS_OK) {
     fail_result(out, guess16, rc);
@@ -754,10 +759,8 @@ static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* 
   // 12: 2.08 / 2.16, 32: 3.30 / 4.23)
   static const int kd_min = std::getenv("DGS_GICP_KD_MIN_CANDIDATES") ? std::atoi(std::getenv("DGS_GICP_KD_MIN_CANDIDATES")) : 10;
   h->batch_kd = h->nn_kd && n >= kd_min;
-  const bool icp = h->prm.method == DGS_METHOD_ICP, pcl = h->prm.method == DGS_METHOD_PCL_GICP;
-  int rc = icp   ? icp_align_batch(h, n, cs, guesses16, results)
-           : pcl ? pcl_gicp_align_batch(h, n, cs, guesses16, results)
-                 : gicp_align_batch(h, n, cs, guesses16, results);
+  const MethodOps& ops = kMethodOps[h->prm.method];
+  int rc = ops.align_batch(h, n, cs, guesses16, results);
   if (rc == DGS_OK && compute_fitness) {
     DGS_HIP_TRY(h, h->src_ptrs.reserve(n));
     DGS_HIP_TRY(h, h->src_sizes.reserve(n));
@@ -771,7 +774,7 @@ static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* 
     std::vector<double> sums(n);
     std::vector<int64_t> cnts(n), inl(n);
     size_t stride = 0;
-    const float* dT = icp ? icp_final_transforms(h, &stride) : pcl ? pcl_gicp_final_transforms(h, &stride) : gicp_final_transforms(h, &stride);
+    const float* dT = ops.final_transforms(h, &stride);
     rc = nn_fitness_batch(h, n, h->src_ptrs.ptr, h->src_sizes.ptr, max_n, dT, stride, fitness_max_range, 0.0, sums.data(), cnts.data(), inl.data());
     if (rc == DGS_OK)
       for (int i = 0; i < n; i++) results[i].fitness = cnts[i] > 0 ? sums[i] / (double)cnts[i] : DBL_MAX;
@@ -1024,7 +1027,6 @@ int dgs_calc_fitness_score(dgs_handle* h, const float* cloud1, int64_t n1, const
   if (set_device(h)) return DGS_ERR_HIP;
   *score = DBL_MAX;
   if (n1 == 0 || n2 == 0) return DGS_OK;  // no neighbour / no query: "nr == 0" branch of the reference
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   int rc = upload_cloud(h, h->aux_cloud1, cloud1, n1, on_device);
   if (rc == DGS_OK) rc = upload_cloud(h, h->aux_cloud2, cloud2, n2, on_device);
   if (rc == DGS_OK) rc = bvh_build(h, h->aux_bvh, h->aux_cloud1.ptr, n1);
@@ -1042,7 +1044,7 @@ int dgs_calc_fitness_score(dgs_handle* h, const float* cloud1, int64_t n1, const
   const int ni = (int)n2;
   std::memcpy(base, &src, sizeof(void*));
   std::memcpy(base + 16, &ni, sizeof(int));
-  std::memcpy(base + 64, relpose16 ? relpose16 : ident, sizeof(float) * 16);
+  std::memcpy(base + 64, relpose16 ? relpose16 : kIdentity16, sizeof(float) * 16);
   DGS_HIP_TRY(h, hipMemcpyAsync(h->src_ptrs.ptr, base, sizeof(void*), hipMemcpyHostToDevice, st));
   DGS_HIP_TRY(h, hipMemcpyAsync(h->src_sizes.ptr, base + 16, sizeof(int), hipMemcpyHostToDevice, st));
   DGS_HIP_TRY(h, hipMemcpyAsync(h->inits.ptr, base + 64, sizeof(float) * 16, hipMemcpyHostToDevice, st));

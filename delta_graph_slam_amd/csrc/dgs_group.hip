@@ -187,9 +187,8 @@ bool ensure_buffers(dgs_group* g, size_t per_member) {
 }
 
 void fail_share(std::vector<dgs_result>& res, const float* gs, int rc) {
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   for (size_t j = 0; j < res.size(); j++) {
-    std::memcpy(res[j].final_transformation, gs ? gs + 16 * j : ident, sizeof(float) * 16);
+    std::memcpy(res[j].final_transformation, gs ? gs + 16 * j : dgs::kIdentity16, sizeof(float) * 16);
     res[j].converged = 0; res[j].iterations = 0; res[j].evaluations = 0; res[j].status = rc;
     res[j].score = 0.0; res[j].fitness = NAN;
   }

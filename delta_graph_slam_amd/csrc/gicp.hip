@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "batch_rounds.h"
 #include "handle.h"
 #include "nn_group.h"
 #include "small_linalg.h"
@@ -1232,19 +1233,7 @@ static void gicp_launch_round(dgs_handle* h, const GicpLaunch& L, const int laun
                        h->gconsts, h->done_counter.ptr);
 }
 
-// pinned staging: [0,64) done flags | inits | items | pairs read back
-static size_t gicp_pinned_layout(int n, size_t* off_init, size_t* off_items, size_t* off_pairs) {
-  size_t o = 64;
-  *off_init = o;
-  o += (size_t)n * sizeof(GicpInit);
-  o = (o + 63) & ~(size_t)63;
-  *off_items = o;
-  o += (size_t)n * sizeof(GicpItem);
-  o = (o + 63) & ~(size_t)63;
-  *off_pairs = o;
-  o += (size_t)n * sizeof(GicpPair);
-  return o;
-}
+using GicpStaging = BatchStaging<GicpInit, GicpItem, GicpPair>;
 
 // Covariances and indices of every cloud, work arrays, per-pair state: everything a batch needs before its first round.
 static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const double* x0_rows, int probe_kind, GicpLaunch* L_out, int* n_live) {
@@ -1280,12 +1269,10 @@ static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const doubl
   DGS_HIP_TRY(h, h->pair_blocks.reserve(n));
   DGS_HIP_TRY(h, h->done_counter.reserve(16));
   DGS_HIP_TRY(h, h->partials.reserve((size_t)n * L.cap_l * kAccumPad + 64));
-  size_t oi, ot, op;
-  const size_t bytes = gicp_pinned_layout(n, &oi, &ot, &op);
-  if (ensure_pinned(h, bytes) != DGS_OK) return DGS_ERR_HIP;
-  char* base = reinterpret_cast<char*>(h->pinned);
-  GicpInit* hin = reinterpret_cast<GicpInit*>(base + oi);
-  GicpItem* hit = reinterpret_cast<GicpItem*>(base + ot);
+  const GicpStaging stg(h, n);
+  if (stg.ensure() != DGS_OK) return DGS_ERR_HIP;
+  GicpInit* hin = stg.inits();
+  GicpItem* hit = stg.items();
   int64_t off = 0;
   for (int i = 0; i < n; i++) {
     const CloudState& c = *srcs[i];
@@ -1310,27 +1297,12 @@ static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const doubl
   return DGS_OK;
 }
 
-static GicpPair* gicp_read_back(dgs_handle* h, int n, int* rc) {
-  size_t oi, ot, op;
-  (void)gicp_pinned_layout(n, &oi, &ot, &op);
-  GicpPair* hp = reinterpret_cast<GicpPair*>(reinterpret_cast<char*>(h->pinned) + op);
-  *rc = DGS_OK;
-  if (hipMemcpyAsync(hp, h->gpairs.ptr, (size_t)n * sizeof(GicpPair), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-    h->err = "reading the GICP optimiser state back failed";
-    *rc = DGS_ERR_HIP;
-  }
-  return hp;
-}
-
 // FastGICP::align for every source of a batch against the handle's target; the LM loops of all pairs advance together,
 // one (correspond, linearize, solve) launch triple per round, and pairs that finish hand their workgroups to the rest.
 int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out) {
-  hipStream_t st = h->stream;
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<double> x0((size_t)n * 12);
   for (int i = 0; i < n; i++) {
-    const float* G = guesses16 ? guesses16 + 16 * i : ident;
+    const float* G = guesses16 ? guesses16 + 16 * i : kIdentity16;
     for (int r = 0; r < 3; r++)
       for (int c = 0; c < 4; c++) x0[(size_t)i * 12 + r * 4 + c] = (double)G[c * 4 + r];  // Eigen::Isometry3d(guess.cast<double>())
   }
@@ -1340,37 +1312,16 @@ int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float*
   if (rc) return rc;
 
   if (n_live > 0) {
-    volatile int* flags = reinterpret_cast<volatile int*>(h->pinned);
-    flags[0] = flags[1] = 0;
-    if (ensure_poll_events(h) != DGS_OK) return DGS_ERR_HIP;
-    hipEvent_t* ev = h->ev_poll;
-    const long max_rounds = (long)h->prm.maximum_iterations * (h->prm.gicp_lm_max_iterations + 1) + 4;
-    const int chunk = 4;
-    long queued = 0;
+    // whole chunks of 4 rounds: the bound rounded up
+    const long max_rounds = ((long)h->prm.maximum_iterations * (h->prm.gicp_lm_max_iterations + 1) + 4 + 3) / 4 * 4;
     int launch_no = 0;
-    auto enqueue_chunk = [&](int slot) -> int {
-      for (int e = 0; e < chunk; e++) gicp_launch_round(h, L, launch_no++);
-      queued += chunk;
-      DGS_HIP_TRY(h, hipMemcpyAsync(const_cast<int*>(&flags[slot]), h->done_counter.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
-      DGS_HIP_TRY(h, hipEventRecord(ev[slot], st));
-      return DGS_OK;
-    };
-    int cur = 0;
-    rc = enqueue_chunk(0);
-    while (rc == DGS_OK) {
-      const bool more = queued < max_rounds;
-      if (more) rc = enqueue_chunk(cur ^ 1);
-      if (rc != DGS_OK) break;
-      hipError_t e = hipEventSynchronize(ev[cur]);
-      if (e != hipSuccess) { h->err = std::string("hipEventSynchronize: ") + hipGetErrorString(e); rc = DGS_ERR_HIP; break; }
-      if (flags[cur] >= n_live) break;
-      if (!more) break;
-      cur ^= 1;
-    }
+    rc = run_rounds_polled(h, n_live, max_rounds, 4, [&] { gicp_launch_round(h, L, launch_no++); });
     if (rc != DGS_OK) return rc;
   }
-  GicpPair* hp = gicp_read_back(h, n, &rc);
+  const GicpStaging stg(h, n);
+  rc = stg.read_back(h->gpairs, n, "GICP optimiser state");
   if (rc) return rc;
+  const GicpPair* hp = stg.pairs();
   long evals = 0;
   for (int i = 0; i < n; i++) {
     std::memcpy(out[i].final_transformation, hp[i].final_T, sizeof(float) * 16);
@@ -1423,8 +1374,10 @@ int gicp_probe(dgs_handle* h, const double* T16, int error_only, double* err, do
   if (rc) return rc;
   if (n_live == 0) return DGS_ERR_NO_SOURCE;
   gicp_launch_round(h, L, 0);
-  GicpPair* hp = gicp_read_back(h, 1, &rc);
+  const GicpStaging stg(h, 1);
+  rc = stg.read_back(h->gpairs, 1, "GICP optimiser state");
   if (rc) return rc;
+  const GicpPair* hp = stg.pairs();
   *err = error_only ? hp->s.yi : hp->s.y0;
   if (!error_only) {
     for (int k = 0; k < 36; k++) H36[k] = hp->s.H[k];

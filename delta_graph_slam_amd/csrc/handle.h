@@ -36,6 +36,10 @@ struct Bvh {
   DevBuf<unsigned> kd_bbox;   // k-d order build: boxes of the ranges of the current level
   bool kd = false;          // points are in k-d (median split) order instead of Hilbert order
   bool valid = false;
+  void release() {
+    sorted.release(); node_lo.release(); node_hi.release(); keys.release(); keys_alt.release(); vals.release(); vals_alt.release(); kd_bbox.release();
+    valid = false;
+  }
 };
 
 // Sparse 64-ary voxel hierarchy over a target cloud for one-lane-per-query exact 1-NN distances (nn_grid.hip).  Belongs to a
@@ -87,19 +91,14 @@ struct CloudState {
   DevBuf<double> cov;  // 6 doubles per point: xx, xy, xz, yy, yz, zz
   bool cov_valid = false;
   int cov_k = 0, cov_reg = -1;
-  Bvh walk;            // ICP: a Hilbert-ordered index kept for the correspondence walk when `bvh` is k-d ordered (the cloud was a batch target)
+  Bvh walk;            // ICP_HIP / GICP_HIP (batch_rounds.h ensure_walk_order): a Hilbert-ordered index kept for the correspondence walk when `bvh` is k-d ordered (the cloud was a batch target)
   DevBuf<double> pcov; // GICP_HIP: pcl::GeneralizedIterativeClosestPoint's covariances, 9 doubles per point (row-major), keyed by (k, epsilon)
   bool pcov_valid = false;
   int pcov_k = 0;
   double pcov_eps = 0.0;
   void invalidate() { bvh.valid = false; cov_valid = false; walk.valid = false; pcov_valid = false; }
   void release() {
-    pts.release(); cov.release(); pcov.release();
-    for (Bvh* b : {&bvh, &walk}) {
-      b->sorted.release(); b->node_lo.release(); b->node_hi.release();
-      b->keys.release(); b->keys_alt.release(); b->vals.release(); b->vals_alt.release();
-      b->kd_bbox.release();
-    }
+    pts.release(); cov.release(); pcov.release(); bvh.release(); walk.release();
     n = 0;
     invalidate();
   }
@@ -285,14 +284,16 @@ struct dgs_handle {
   std::vector<dgs::CloudState> batch_clouds;   // index + covariances of sources handed to dgs_align_batch as raw arrays
   dgs::GicpConsts gconsts{};
 
+  // ---- fixed slices of ICP_HIP / GICP_HIP round launches (batch_rounds.h SliceTable, slice_rows.h): one set, a handle has one method for life
+  dgs::DevBuf<int> slice_blk_pair;             // workgroup -> pair of the round launch
+  dgs::DevBuf<double> slice_rows;              // one partial row per (pair, slice): kIcpPad / kPgPad doubles
+
   // ---- ICP (pcl::IterativeClosestPoint, icp.hip): the target's exact-NN index only -- no covariances, for the target or any source
   dgs_icp_options icp_opt{};                   // dgs_set_icp_options; read at every align
   dgs::DevBuf<dgs::IcpPair> ipairs;
   dgs::DevBuf<dgs::IcpItem> iitems;
   dgs::DevBuf<float4> icp_w;                   // working copies (input_transformed) of every source of the batch
-  dgs::DevBuf<int> icp_blk_pair;
-  dgs::DevBuf<int> icp_origin;                 // index of the target's first finite point (the origin of the moment sums)               // workgroup -> pair of the iteration launch (fixed slices per pair)
-  dgs::DevBuf<double> icp_rows;                // one partial row per (pair, slice)
+  dgs::DevBuf<int> icp_origin;                 // index of the target's first finite point (the origin of the moment sums)
   dgs::DevBuf<float> icp_traj_T;               // per pair and iteration: T_k (column-major 16 floats)
   dgs::DevBuf<double> icp_traj_mse;
   dgs::DevBuf<int> icp_traj_n;
@@ -308,8 +309,6 @@ struct dgs_handle {
   dgs::DevBuf<float4> pg_w;                    // per source slot (walk order): output = guess * source, w = original index
   dgs::DevBuf<float4> pg_q;                    // per source slot: the target point of this outer iteration's pair, w = 1 kept / 0 not
   dgs::DevBuf<double> pg_m;                    // per source slot: M_i, 9 planes of doubles (structure of arrays)
-  dgs::DevBuf<int> pg_blk_pair;                // workgroup -> pair of the round launch (fixed slices per pair)
-  dgs::DevBuf<double> pg_rows;                 // one partial row per (pair, slice)
   dgs::DevBuf<float> pg_traj_T;                // per pair and outer iteration: transformation_ (column-major 16 floats)
   dgs::DevBuf<int> pg_traj_i;                  // per pair and outer iteration: kept pairs, inner iterations, evaluation passes
   dgs::DevBuf<double> pg_traj_f;

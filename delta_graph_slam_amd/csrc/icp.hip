@@ -19,8 +19,10 @@
 #include <cstring>
 #include <vector>
 
+#include "batch_rounds.h"
 #include "handle.h"
 #include "nn_group.h"
+#include "slice_rows.h"
 #include "small_linalg.h"
 
 namespace dgs {
@@ -220,43 +222,9 @@ __global__ __launch_bounds__(kBlock, 4) void icp_iterate_kernel(const BvhView tv
       acc[14] += a2 * b0; acc[15] += a2 * b1; acc[16] += a2 * b2;
     }
   }
-  // wave DPP sums -> LDS -> this slice's row (write-through), then the pair's ticket
-  __shared__ double sm[kBlock / kWave][kIcpAccum];
-#pragma unroll
-  for (int k = 0; k < kIcpAccum; k++) {
-    const double v = wave_sum_to_lane63(acc[k]);
-    if (lane == 63) sm[wave][k] = v;
-  }
-  __syncthreads();
-  double* row = rows + (size_t)blockIdx.x * kIcpPad;
-  if (threadIdx.x < kIcpPad) {
-    double v = 0.0;
-    if (threadIdx.x < kIcpAccum) v = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
-    handoff_store_row(row + threadIdx.x, v);
-    handoff_drain_stores();
-  }
-  __shared__ int s_last;
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = handoff_take_ticket(&st->ticket, it.n_slices) ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  // the pair's closing workgroup: rows summed in slice order (8 strided partial sums per column, then those 8 in order)
-  constexpr int G = kBlock / kIcpPad;
-  __shared__ double part[G][kIcpPad];
+  // this slice's row, the pair's ticket; in the pair's closing workgroup the rows summed in slice order (slice_rows.h)
   __shared__ double tot[kIcpPad];
-  const int col = threadIdx.x % kIcpPad, grp = threadIdx.x / kIcpPad;
-  double v = 0.0;
-  const double* base = rows + (size_t)it.slice0 * kIcpPad + col;
-  for (int b = grp; b < it.n_slices; b += G) v += handoff_load_row(base + (size_t)b * kIcpPad);
-  part[grp][col] = v;
-  __syncthreads();
-  if (threadIdx.x < kIcpPad) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < G; k++) t += part[k][threadIdx.x];
-    tot[threadIdx.x] = t;
-  }
-  __syncthreads();
+  if (!slice_rows_close(acc, kIcpAccum, rows, it.slice0, it.n_slices, &st->ticket, tot)) return;
   if (threadIdx.x == 0) {
     const double o[3] = {ox, oy, oz};
     icp_close_pair(st, tot, o, c, done_counter, traj_T, traj_mse, traj_n, pair);
@@ -337,32 +305,7 @@ static IcpConsts icp_consts(const dgs_handle* h) {
   return c;
 }
 
-// pinned staging: [0,64) done flags | inits | items | pairs read back
-static size_t icp_pinned_layout(int n, size_t* off_init, size_t* off_items, size_t* off_pairs) {
-  size_t o = 64;
-  *off_init = o;
-  o += (size_t)n * sizeof(IcpInit);
-  o = (o + 63) & ~(size_t)63;
-  *off_items = o;
-  o += (size_t)n * sizeof(IcpItem);
-  o = (o + 63) & ~(size_t)63;
-  *off_pairs = o;
-  o += (size_t)n * sizeof(IcpPair);
-  return o;
-}
-
-static int icp_read_back(dgs_handle* h, int n, IcpPair** out) {
-  size_t oi, ot, op;
-  (void)icp_pinned_layout(n, &oi, &ot, &op);
-  IcpPair* hp = reinterpret_cast<IcpPair*>(reinterpret_cast<char*>(h->pinned) + op);
-  if (hipMemcpyAsync(hp, h->ipairs.ptr, (size_t)n * sizeof(IcpPair), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-    h->err = "reading the ICP state back failed";
-    return DGS_ERR_HIP;
-  }
-  *out = hp;
-  return DGS_OK;
-}
+using IcpStaging = BatchStaging<IcpInit, IcpItem, IcpPair>;
 
 // IterativeClosestPoint::align for every source of a batch against the handle's target.  The target needs its exact-NN index only;
 // every source its own index (for the spatial order of the correspondence walk).  No covariances anywhere.
@@ -372,64 +315,47 @@ int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* 
   int rc = ensure_target_index(h);
   if (rc) return rc;
   int64_t total = 0;
-  int total_slices = 0, n_live = 0;
-  std::vector<int> slice0(n), n_slices(n);
+  int n_live = 0;
+  SliceTable slices(n, srcs, kIcpSlicePoints);
+  const int total_slices = slices.total_slices;
   for (int i = 0; i < n; i++) {
     CloudState& s = *srcs[i];
-    slice0[i] = total_slices;
-    n_slices[i] = (int)((s.n + kIcpSlicePoints - 1) / kIcpSlicePoints);
-    total_slices += n_slices[i];
     total += s.n;
     if (s.n <= 0) continue;
     n_live++;
-    // the walk takes the source in Hilbert order whatever other index the cloud carries (a resident cloud that was the target of a large
-    // batch holds a k-d ordered one): the order of a pair's double sums is a function of its points alone
-    if (!s.bvh.valid) {
-      rc = bvh_build(h, s.bvh, s.pts.ptr, s.n);
-      if (rc) return rc;
-    }
-    if (s.bvh.kd && !s.walk.valid) {
-      rc = bvh_build(h, s.walk, s.pts.ptr, s.n);
-      if (rc) return rc;
-    }
+    rc = ensure_walk_order(h, s);
+    if (rc) return rc;
   }
   DGS_HIP_TRY(h, h->ipairs.reserve(n));
   DGS_HIP_TRY(h, h->iitems.reserve(n));
   DGS_HIP_TRY(h, h->icp_w.reserve((size_t)std::max<int64_t>(total, 1)));
-  DGS_HIP_TRY(h, h->icp_blk_pair.reserve((size_t)std::max(total_slices, 1)));
-  DGS_HIP_TRY(h, h->icp_rows.reserve((size_t)std::max(total_slices, 1) * kIcpPad));
   DGS_HIP_TRY(h, h->icp_traj_T.reserve((size_t)n * c.traj_cap * 16));
   DGS_HIP_TRY(h, h->icp_traj_mse.reserve((size_t)n * c.traj_cap));
   DGS_HIP_TRY(h, h->icp_traj_n.reserve((size_t)n * c.traj_cap));
   DGS_HIP_TRY(h, h->done_counter.reserve(16));
   DGS_HIP_TRY(h, h->icp_origin.reserve(1));
   if (c.reciprocal && h->icp_w_bvh.size() < (size_t)n) h->icp_w_bvh.resize(n);
-  size_t oi, ot, op;
-  const size_t bytes = icp_pinned_layout(n, &oi, &ot, &op);
-  if (ensure_pinned(h, bytes) != DGS_OK) return DGS_ERR_HIP;
-  char* base = reinterpret_cast<char*>(h->pinned);
-  IcpInit* hin = reinterpret_cast<IcpInit*>(base + oi);
-  IcpItem* hit = reinterpret_cast<IcpItem*>(base + ot);
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const IcpStaging stg(h, n);
+  if (stg.ensure() != DGS_OK) return DGS_ERR_HIP;
+  IcpInit* hin = stg.inits();
+  IcpItem* hit = stg.items();
   int64_t off = 0;
   for (int i = 0; i < n; i++) {
     const CloudState& s = *srcs[i];
-    std::memcpy(hin[i].guess, guesses16 ? guesses16 + 16 * i : ident, sizeof(float) * 16);
+    std::memcpy(hin[i].guess, guesses16 ? guesses16 + 16 * i : kIdentity16, sizeof(float) * 16);
     hin[i].n = (int)s.n;
     hit[i].src = s.pts.ptr;
-    hit[i].src_sorted = (s.bvh.valid && s.bvh.kd) ? s.walk.sorted.ptr : s.bvh.sorted.ptr;
+    hit[i].src_sorted = walk_sorted(s);
     hit[i].W = h->icp_w.ptr + off;
     std::memset(&hit[i].wv, 0, sizeof(BvhView));
     hit[i].n = (int)s.n;
-    hit[i].slice0 = slice0[i];
-    hit[i].n_slices = n_slices[i];
+    hit[i].slice0 = slices.slice0[i];
+    hit[i].n_slices = slices.n_slices[i];
     hit[i].pad = 0;
     off += s.n;
   }
-  std::vector<int> blk((size_t)std::max(total_slices, 1), 0);
-  for (int i = 0; i < n; i++)
-    for (int k = 0; k < n_slices[i]; k++) blk[(size_t)slice0[i] + k] = i;
-  DGS_HIP_TRY(h, hipMemcpyAsync(h->icp_blk_pair.ptr, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  rc = slices.upload(h, kIcpPad);
+  if (rc) return rc;
   DGS_HIP_TRY(h, h->inits.reserve((size_t)n));   // staging shared with NDT / GICP
   static_assert(sizeof(NdtInit) >= sizeof(IcpInit), "init staging buffer is shared with NDT");
   DGS_HIP_TRY(h, hipMemcpyAsync(h->inits.ptr, hin, (size_t)n * sizeof(IcpInit), hipMemcpyHostToDevice, st));
@@ -439,58 +365,33 @@ int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* 
   const int nt = (int)h->nt;
   if (nt > 0) hipLaunchKernelGGL(icp_origin_kernel, dim3((nt + kBlock - 1) / kBlock), dim3(kBlock), 0, st, h->tgt->pts.ptr, nt, h->icp_origin.ptr);
   hipLaunchKernelGGL(icp_init_kernel, dim3((n + 63) / 64), dim3(64), 0, st, h->ipairs.ptr, reinterpret_cast<const IcpInit*>(h->inits.ptr), n);
-  DGS_HIP_TRY(h, hipStreamSynchronize(st));   // blk is pageable host memory going out of scope
+  DGS_HIP_TRY(h, hipStreamSynchronize(st));   // slices.blk is pageable host memory
   const BvhView tv = make_bvh_view(h->tgt->bvh);
   const long max_rounds = std::max(1, h->prm.maximum_iterations);
   auto launch_round = [&](bool reciprocal) {
     int slot = prof_begin(h, DGS_K_NN_SEARCH);
     if (reciprocal)
-      hipLaunchKernelGGL(icp_iterate_kernel<true>, dim3(total_slices), dim3(kBlock), 0, st, tv, h->tgt->pts.ptr, h->icp_origin.ptr, nt, h->iitems.ptr, h->ipairs.ptr, h->icp_blk_pair.ptr,
-                         h->icp_rows.ptr, c, h->done_counter.ptr, h->icp_traj_T.ptr, h->icp_traj_mse.ptr, h->icp_traj_n.ptr);
+      hipLaunchKernelGGL(icp_iterate_kernel<true>, dim3(total_slices), dim3(kBlock), 0, st, tv, h->tgt->pts.ptr, h->icp_origin.ptr, nt, h->iitems.ptr, h->ipairs.ptr, h->slice_blk_pair.ptr,
+                         h->slice_rows.ptr, c, h->done_counter.ptr, h->icp_traj_T.ptr, h->icp_traj_mse.ptr, h->icp_traj_n.ptr);
     else
-      hipLaunchKernelGGL(icp_iterate_kernel<false>, dim3(total_slices), dim3(kBlock), 0, st, tv, h->tgt->pts.ptr, h->icp_origin.ptr, nt, h->iitems.ptr, h->ipairs.ptr, h->icp_blk_pair.ptr,
-                         h->icp_rows.ptr, c, h->done_counter.ptr, h->icp_traj_T.ptr, h->icp_traj_mse.ptr, h->icp_traj_n.ptr);
+      hipLaunchKernelGGL(icp_iterate_kernel<false>, dim3(total_slices), dim3(kBlock), 0, st, tv, h->tgt->pts.ptr, h->icp_origin.ptr, nt, h->iitems.ptr, h->ipairs.ptr, h->slice_blk_pair.ptr,
+                         h->slice_rows.ptr, c, h->done_counter.ptr, h->icp_traj_T.ptr, h->icp_traj_mse.ptr, h->icp_traj_n.ptr);
     prof_end(h, DGS_K_NN_SEARCH, slot);
   };
   if (n_live > 0 && !c.reciprocal) {
-    // chunks of launches with a done-counter poll between them (gicp_align_batch's scheme): no host round trip per iteration
-    volatile int* flags = reinterpret_cast<volatile int*>(h->pinned);
-    flags[0] = flags[1] = 0;
-    if (ensure_poll_events(h) != DGS_OK) return DGS_ERR_HIP;
-    hipEvent_t* ev = h->ev_poll;
-    const int chunk = 4;
-    long queued = 0;
-    auto enqueue_chunk = [&](int slot) -> int {
-      for (int e = 0; e < chunk && queued < max_rounds; e++, queued++) launch_round(false);
-      DGS_HIP_TRY(h, hipGetLastError());
-      DGS_HIP_TRY(h, hipMemcpyAsync(const_cast<int*>(&flags[slot]), h->done_counter.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
-      DGS_HIP_TRY(h, hipEventRecord(ev[slot], st));
-      return DGS_OK;
-    };
-    int cur = 0;
-    rc = enqueue_chunk(0);
-    while (rc == DGS_OK) {
-      const bool more = queued < max_rounds;
-      if (more) rc = enqueue_chunk(cur ^ 1);
-      if (rc != DGS_OK) break;
-      hipError_t e = hipEventSynchronize(ev[cur]);
-      if (e != hipSuccess) { h->err = std::string("hipEventSynchronize: ") + hipGetErrorString(e); rc = DGS_ERR_HIP; break; }
-      if (flags[cur] >= n_live) break;
-      if (!more) break;
-      cur ^= 1;
-    }
+    rc = run_rounds_polled(h, n_live, max_rounds, 4, [&] { launch_round(false); });
     if (rc != DGS_OK) return rc;
   } else if (n_live > 0) {
     // reciprocal mode: one round at a time -- move the working copies, index them, then the iteration launch with the reverse query
     for (long r = 0; r < max_rounds; r++) {
-      IcpPair* hp = nullptr;
-      rc = icp_read_back(h, n, &hp);
+      rc = stg.read_back(h->ipairs, n, "ICP state");
       if (rc) return rc;
+      const IcpPair* hp = stg.pairs();
       std::vector<char> act(n);
       int live = 0;
       for (int i = 0; i < n; i++) { act[i] = hp[i].active != 0; live += act[i]; }
       if (live == 0) break;
-      hipLaunchKernelGGL(icp_apply_kernel, dim3(total_slices), dim3(kBlock), 0, st, h->iitems.ptr, h->ipairs.ptr, h->icp_blk_pair.ptr);
+      hipLaunchKernelGGL(icp_apply_kernel, dim3(total_slices), dim3(kBlock), 0, st, h->iitems.ptr, h->ipairs.ptr, h->slice_blk_pair.ptr);
       DGS_HIP_TRY(h, hipGetLastError());
       for (int i = 0; i < n; i++) {
         if (!act[i]) continue;
@@ -503,9 +404,9 @@ int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* 
       DGS_HIP_TRY(h, hipGetLastError());
     }
   }
-  IcpPair* hp = nullptr;
-  rc = icp_read_back(h, n, &hp);
+  rc = stg.read_back(h->ipairs, n, "ICP state");
   if (rc) return rc;
+  const IcpPair* hp = stg.pairs();
   long evals = 0;
   h->icp_last_iters.assign(n, 0);
   h->icp_traj_cap = c.traj_cap;
@@ -537,12 +438,10 @@ const float* icp_final_transforms(dgs_handle* h, size_t* stride_bytes) {
 }
 
 int icp_trajectory(dgs_handle* h, int pair, float* T16s, double* mse, int32_t* n_corr, int capacity, int* len) {
-  if (pair < 0 || (size_t)pair >= h->icp_last_iters.size()) return DGS_ERR_INVALID_ARGUMENT;
-  const int iters = std::min(h->icp_last_iters[pair], h->icp_traj_cap);
-  *len = iters;
-  const int m = std::min(iters, std::max(capacity, 0));
-  if (m == 0) return DGS_OK;
-  const size_t e = (size_t)pair * h->icp_traj_cap;
+  int m;
+  size_t e;
+  int rc = traj_window(h->icp_last_iters, h->icp_traj_cap, pair, capacity, len, &m, &e);
+  if (rc || m == 0) return rc;
   DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (T16s) DGS_HIP_TRY(h, hipMemcpy(T16s, h->icp_traj_T.ptr + e * 16, (size_t)m * 16 * sizeof(float), hipMemcpyDeviceToHost));
   if (mse) DGS_HIP_TRY(h, hipMemcpy(mse, h->icp_traj_mse.ptr + e, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
@@ -551,11 +450,9 @@ int icp_trajectory(dgs_handle* h, int pair, float* T16s, double* mse, int32_t* n
 }
 
 void icp_release(dgs_handle* h) {
-  h->ipairs.release(); h->iitems.release(); h->icp_w.release(); h->icp_blk_pair.release(); h->icp_origin.release(); h->icp_rows.release();
+  h->ipairs.release(); h->iitems.release(); h->icp_w.release(); h->icp_origin.release();
   h->icp_traj_T.release(); h->icp_traj_mse.release(); h->icp_traj_n.release();
-  for (auto& b : h->icp_w_bvh) {
-    b.sorted.release(); b.node_lo.release(); b.node_hi.release(); b.keys.release(); b.keys_alt.release(); b.vals.release(); b.vals_alt.release(); b.kd_bbox.release();
-  }
+  for (auto& b : h->icp_w_bvh) b.release();
   h->icp_w_bvh.clear();
 }
 

@@ -22,8 +22,10 @@
 #include <cstring>
 #include <vector>
 
+#include "batch_rounds.h"
 #include "handle.h"
 #include "nn_group.h"
+#include "slice_rows.h"
 #include "small_linalg.h"
 
 namespace dgs {
@@ -649,45 +651,9 @@ __global__ __launch_bounds__(kBlock) void pg_round_kernel(const BvhView tv, cons
       }
     }
   }
-  // wave DPP sums -> LDS -> this slice's row (write-through), then the pair's ticket
-  __shared__ double sm[kBlock / kWave][kPgAccum];
-#pragma unroll
-  for (int k = 0; k < kPgAccum; k++) {
-    if (k == 0 || !correspond) {
-      const double v = wave_sum_to_lane63(acc[k]);
-      if (lane == 63) sm[wave][k] = v;
-    }
-  }
-  __syncthreads();
-  double* row = rows + (size_t)blockIdx.x * kPgPad;
-  if (threadIdx.x < kPgPad) {
-    double v = 0.0;
-    if (threadIdx.x < (correspond ? 1 : kPgAccum)) v = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
-    handoff_store_row(row + threadIdx.x, v);
-    handoff_drain_stores();
-  }
-  __shared__ int s_last;
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = handoff_take_ticket(&st->ticket, it.n_slices) ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  // the pair's closing workgroup: rows summed in slice order (16 strided partial sums per column, then those 16 in order)
-  constexpr int G = kBlock / kPgPad;
-  __shared__ double part[G][kPgPad];
+  // this slice's row, the pair's ticket; in the pair's closing workgroup the rows summed in slice order (slice_rows.h)
   __shared__ double tot[kPgPad];
-  const int col = threadIdx.x % kPgPad, grp = threadIdx.x / kPgPad;
-  double v = 0.0;
-  const double* base = rows + (size_t)it.slice0 * kPgPad + col;
-  for (int b = grp; b < it.n_slices; b += G) v += handoff_load_row(base + (size_t)b * kPgPad);
-  part[grp][col] = v;
-  __syncthreads();
-  if (threadIdx.x < kPgPad) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < G; k++) t += part[k][threadIdx.x];
-    tot[threadIdx.x] = t;
-  }
-  __syncthreads();
+  if (!slice_rows_close(acc, correspond ? 1 : kPgAccum, rows, it.slice0, it.n_slices, &st->ticket, tot)) return;
   if (threadIdx.x == 0) pg_close(st, tot, c, done_counter, traj_T, traj_i, traj_f, pair);
 }
 
@@ -769,19 +735,7 @@ static int ensure_pcov(dgs_handle* h, CloudState& c) {
   return DGS_OK;
 }
 
-// pinned staging: [0,64) done flags | inits | items | pairs read back
-static size_t pg_pinned_layout(int n, size_t* off_init, size_t* off_items, size_t* off_pairs) {
-  size_t o = 64;
-  *off_init = o;
-  o += (size_t)n * sizeof(PgInit);
-  o = (o + 63) & ~(size_t)63;
-  *off_items = o;
-  o += (size_t)n * sizeof(PgItem);
-  o = (o + 63) & ~(size_t)63;
-  *off_pairs = o;
-  o += (size_t)n * sizeof(PgPair);
-  return o;
-}
+using PgStaging = BatchStaging<PgInit, PgItem, PgPair>;
 
 // computeTransformation for every source of a batch against the handle's target (probe != nullptr: one pair, the test hook's single
 // correspondence + evaluation pass).  Per-pair status in out[i].status.
@@ -795,27 +749,19 @@ static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const flo
   if (rc) return rc;
   const int k = h->prm.gicp_correspondence_randomness;
   int64_t total = 0;
-  int total_slices = 0, n_live = 0;
-  std::vector<int> slice0(n), n_slices(n), skip(n, 0);
+  int n_live = 0;
+  SliceTable slices(n, srcs, kPgSlicePoints);
+  const int total_slices = slices.total_slices;
+  std::vector<int> skip(n, 0);
   std::vector<long long> off(n);
   for (int i = 0; i < n; i++) {
     CloudState& s = *srcs[i];
-    slice0[i] = total_slices;
     off[i] = total;
-    n_slices[i] = (int)((s.n + kPgSlicePoints - 1) / kPgSlicePoints);
-    total_slices += n_slices[i];
     total += s.n;
     if (s.n <= 0) continue;
     if ((int64_t)k > s.n) { skip[i] = 1; continue; }   // computeCovariances refuses the cloud: this registration fails
-    // the walk takes the source in Hilbert order whatever other index the cloud carries (ICP_HIP's rule)
-    if (!s.bvh.valid) {
-      rc = bvh_build(h, s.bvh, s.pts.ptr, s.n);
-      if (rc) return rc;
-    }
-    if (s.bvh.kd && !s.walk.valid) {
-      rc = bvh_build(h, s.walk, s.pts.ptr, s.n);
-      if (rc) return rc;
-    }
+    rc = ensure_walk_order(h, s);
+    if (rc) return rc;
     rc = ensure_pcov(h, s);
     if (rc) return rc;
     n_live++;
@@ -827,55 +773,48 @@ static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const flo
   DGS_HIP_TRY(h, h->pg_w.reserve((size_t)c.total));
   DGS_HIP_TRY(h, h->pg_q.reserve((size_t)c.total));
   DGS_HIP_TRY(h, h->pg_m.reserve((size_t)c.total * 9));
-  DGS_HIP_TRY(h, h->pg_blk_pair.reserve((size_t)std::max(total_slices, 1)));
-  DGS_HIP_TRY(h, h->pg_rows.reserve((size_t)std::max(total_slices, 1) * kPgPad));
   DGS_HIP_TRY(h, h->pg_traj_T.reserve((size_t)n * c.traj_cap * 16));
   DGS_HIP_TRY(h, h->pg_traj_i.reserve((size_t)n * c.traj_cap * 3));
   DGS_HIP_TRY(h, h->pg_traj_f.reserve((size_t)n * c.traj_cap));
   DGS_HIP_TRY(h, h->done_counter.reserve(16));
-  size_t oi, ot, op;
-  const size_t bytes = pg_pinned_layout(n, &oi, &ot, &op);
-  if (ensure_pinned(h, bytes) != DGS_OK) return DGS_ERR_HIP;
-  char* base = reinterpret_cast<char*>(h->pinned);
-  PgInit* hin = reinterpret_cast<PgInit*>(base + oi);
-  PgItem* hit = reinterpret_cast<PgItem*>(base + ot);
-  const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const PgStaging stg(h, n);
+  if (stg.ensure() != DGS_OK) return DGS_ERR_HIP;
+  PgInit* hin = stg.inits();
+  PgItem* hit = stg.items();
   for (int i = 0; i < n; i++) {
     const CloudState& s = *srcs[i];
     std::memset(&hin[i], 0, sizeof(PgInit));
-    std::memcpy(hin[i].guess, probe_x ? h->pg_probe_guess : (guesses16 ? guesses16 + 16 * i : ident), sizeof(float) * 16);
-    std::memcpy(hin[i].T, probe_x ? h->pg_probe_T : ident, sizeof(float) * 16);
+    std::memcpy(hin[i].guess, probe_x ? h->pg_probe_guess : (guesses16 ? guesses16 + 16 * i : kIdentity16), sizeof(float) * 16);
+    std::memcpy(hin[i].T, probe_x ? h->pg_probe_T : kIdentity16, sizeof(float) * 16);
     if (probe_x)
       for (int a = 0; a < 6; a++) hin[i].x[a] = probe_x[a];
     hin[i].n = (int)s.n;
     hin[i].skip = skip[i];
     hin[i].probe = probe_x ? 1 : 0;
     hit[i].src = s.pts.ptr;
-    hit[i].src_sorted = (s.bvh.valid && s.bvh.kd) ? s.walk.sorted.ptr : s.bvh.sorted.ptr;
+    hit[i].src_sorted = walk_sorted(s);
     hit[i].cs = s.pcov.ptr;
     hit[i].off = off[i];
     hit[i].n = (skip[i] || s.n <= 0) ? 0 : (int)s.n;   // a skipped pair has no slot to walk (its workgroups return at once anyway)
-    hit[i].slice0 = slice0[i];
-    hit[i].n_slices = n_slices[i];
+    hit[i].slice0 = slices.slice0[i];
+    hit[i].n_slices = slices.n_slices[i];
     hit[i].pad = 0;
   }
-  std::vector<int> blk((size_t)std::max(total_slices, 1), 0);
-  for (int i = 0; i < n; i++)
-    for (int s = 0; s < n_slices[i]; s++) blk[(size_t)slice0[i] + s] = i;
-  DGS_HIP_TRY(h, hipMemcpyAsync(h->pg_blk_pair.ptr, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  rc = slices.upload(h, kPgPad);
+  if (rc) return rc;
   DGS_HIP_TRY(h, hipMemcpyAsync(h->pginits.ptr, hin, (size_t)n * sizeof(PgInit), hipMemcpyHostToDevice, st));
   DGS_HIP_TRY(h, hipMemcpyAsync(h->pgitems.ptr, hit, (size_t)n * sizeof(PgItem), hipMemcpyHostToDevice, st));
   DGS_HIP_TRY(h, hipMemsetAsync(h->done_counter.ptr, 0, 16 * sizeof(int), st));
   hipLaunchKernelGGL(pg_init_kernel, dim3((n + 63) / 64), dim3(64), 0, st, h->pgpairs.ptr, h->pginits.ptr, n);
   if (total_slices > 0)
-    hipLaunchKernelGGL(pg_prepare_kernel, dim3(total_slices), dim3(kBlock), 0, st, h->pgitems.ptr, h->pgpairs.ptr, h->pg_blk_pair.ptr, h->pg_w.ptr);
+    hipLaunchKernelGGL(pg_prepare_kernel, dim3(total_slices), dim3(kBlock), 0, st, h->pgitems.ptr, h->pgpairs.ptr, h->slice_blk_pair.ptr, h->pg_w.ptr);
   DGS_HIP_TRY(h, hipGetLastError());
-  DGS_HIP_TRY(h, hipStreamSynchronize(st));   // blk is pageable host memory going out of scope
+  DGS_HIP_TRY(h, hipStreamSynchronize(st));   // slices.blk is pageable host memory
   const BvhView tv = make_bvh_view(h->tgt->bvh);
   auto launch_round = [&]() {
     int slot = prof_begin(h, DGS_K_NN_SEARCH);
     hipLaunchKernelGGL(pg_round_kernel, dim3(total_slices), dim3(kBlock), 0, st, tv, h->tgt->pts.ptr, h->tgt->pcov.ptr, h->pgitems.ptr, h->pgpairs.ptr,
-                       h->pg_blk_pair.ptr, h->pg_w.ptr, h->pg_q.ptr, h->pg_m.ptr, h->pg_rows.ptr, c, h->done_counter.ptr, h->pg_traj_T.ptr, h->pg_traj_i.ptr,
+                       h->slice_blk_pair.ptr, h->pg_w.ptr, h->pg_q.ptr, h->pg_m.ptr, h->slice_rows.ptr, c, h->done_counter.ptr, h->pg_traj_T.ptr, h->pg_traj_i.ptr,
                        h->pg_traj_f.ptr);
     prof_end(h, DGS_K_NN_SEARCH, slot);
   };
@@ -883,39 +822,12 @@ static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const flo
     // every round is one pass of every live pair: at most 1 correspondence pass, 1 start and 2 * kPgLsIters + 1 trial points per inner
     // iteration, per outer iteration
     const long max_rounds = probe_x ? 2 : (long)std::max(1, c.max_iterations) * (2 + (long)std::max(1, c.max_inner) * (2 * kPgLsIters + 1));
-    volatile int* flags = reinterpret_cast<volatile int*>(h->pinned);
-    flags[0] = flags[1] = 0;
-    if (ensure_poll_events(h) != DGS_OK) return DGS_ERR_HIP;
-    hipEvent_t* ev = h->ev_poll;
-    const int chunk = 8;
-    long queued = 0;
-    auto enqueue_chunk = [&](int slot) -> int {
-      for (int e = 0; e < chunk && queued < max_rounds; e++, queued++) launch_round();
-      DGS_HIP_TRY(h, hipGetLastError());
-      DGS_HIP_TRY(h, hipMemcpyAsync(const_cast<int*>(&flags[slot]), h->done_counter.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
-      DGS_HIP_TRY(h, hipEventRecord(ev[slot], st));
-      return DGS_OK;
-    };
-    int cur = 0;
-    rc = enqueue_chunk(0);
-    while (rc == DGS_OK) {
-      const bool more = queued < max_rounds;
-      if (more) rc = enqueue_chunk(cur ^ 1);
-      if (rc != DGS_OK) break;
-      hipError_t e = hipEventSynchronize(ev[cur]);
-      if (e != hipSuccess) { h->err = std::string("hipEventSynchronize: ") + hipGetErrorString(e); rc = DGS_ERR_HIP; break; }
-      if (flags[cur] >= n_live) break;
-      if (!more) break;
-      cur ^= 1;
-    }
+    rc = run_rounds_polled(h, n_live, max_rounds, 8, launch_round);
     if (rc != DGS_OK) return rc;
   }
-  PgPair* hp = reinterpret_cast<PgPair*>(base + op);
-  if (hipMemcpyAsync(hp, h->pgpairs.ptr, (size_t)n * sizeof(PgPair), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
-      hipGetLastError() != hipSuccess) {
-    h->err = "reading the GICP_HIP state back failed";
-    return DGS_ERR_HIP;
-  }
+  rc = stg.read_back(h->pgpairs, n, "GICP_HIP state");
+  if (rc) return rc;
+  const PgPair* hp = stg.pairs();
   if (probe_out) {
     *probe_out = hp[0];
     return DGS_OK;
@@ -986,12 +898,10 @@ int pcl_gicp_evaluate(dgs_handle* h, const double* x6, int32_t* m, double* f, do
 }
 
 int pcl_gicp_trajectory(dgs_handle* h, int pair, float* T16s, int32_t* n_corr, int32_t* inner, int32_t* passes, double* f, int capacity, int* len) {
-  if (pair < 0 || (size_t)pair >= h->pg_last_iters.size()) return DGS_ERR_INVALID_ARGUMENT;
-  const int iters = std::min(h->pg_last_iters[pair], h->pg_traj_cap);
-  *len = iters;
-  const int m = std::min(iters, std::max(capacity, 0));
-  if (m == 0) return DGS_OK;
-  const size_t e = (size_t)pair * h->pg_traj_cap;
+  int m;
+  size_t e;
+  int rc = traj_window(h->pg_last_iters, h->pg_traj_cap, pair, capacity, len, &m, &e);
+  if (rc || m == 0) return rc;
   DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (T16s) DGS_HIP_TRY(h, hipMemcpy(T16s, h->pg_traj_T.ptr + e * 16, (size_t)m * 16 * sizeof(float), hipMemcpyDeviceToHost));
   if (f) DGS_HIP_TRY(h, hipMemcpy(f, h->pg_traj_f.ptr + e, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
@@ -1009,7 +919,7 @@ int pcl_gicp_trajectory(dgs_handle* h, int pair, float* T16s, int32_t* n_corr, i
 
 void pcl_gicp_release(dgs_handle* h) {
   h->pgpairs.release(); h->pgitems.release(); h->pginits.release(); h->pg_w.release(); h->pg_q.release(); h->pg_m.release();
-  h->pg_blk_pair.release(); h->pg_rows.release(); h->pg_traj_T.release(); h->pg_traj_i.release(); h->pg_traj_f.release();
+  h->pg_traj_T.release(); h->pg_traj_i.release(); h->pg_traj_f.release();
 }
 
 }  // namespace dgs

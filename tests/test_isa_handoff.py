@@ -25,6 +25,8 @@ KERNELS = {
                    + ["_ZN3dgs18ndt_strict3_kernelILi%dELb1ELb1ELb%dEE" % (s, f) for s in (0, 1, 2, 3) for f in (0, 1)]   # upstream order, item-compacted: <search, fused, with the double pass, fixed slices>
                    + ["_ZN3dgs17ndt_strict_kernelILi2ELb1ELb%dEE" % hd for hd in (0, 1)],                  # upstream order, lane-per-point: <DIRECT7, fused, float kinds / double pass>
     "gicp.s": ["_ZN3dgs21gicp_linearize_kernelILb1EE", "_ZN3dgs22vgicp_linearize_kernelILb1EE"],
+    "icp.s": ["_ZN3dgs18icp_iterate_kernelILb%dEE" % r for r in (0, 1)],                                  # fixed slices (slice_rows.h): <reciprocal>
+    "pcl_gicp.s": ["_ZN3dgs15pg_round_kernelE"],
 }
 
 
