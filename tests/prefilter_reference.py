@@ -1,10 +1,13 @@
 """numpy restatement of PrefilteringNodelet's filter chain (apps/prefiltering_nodelet.cpp:111-291, PCL 1.10), float op for op.
 
-k-NN sets: candidates from scipy's cKDTree with a margin, the float32 FLANN distance (tests/helpers.py::f32_sqdist) recomputed and
-sorted by (distance, index) -- the order relation of the HIP k-NN.  The switches are the ABI's (dgs_prefilter_params): same names.
+k-NN sets: candidates by brute force (small clouds) or from scipy's cKDTree, in a window that grows until no tie group of a k-th
+distance is cut; the float32 FLANN distance (tests/helpers.py::f32_sqdist) recomputed and sorted by (distance, index) -- the order
+relation of the HIP k-NN.  The switches are the ABI's (dgs_prefilter_params): same names.
 Down-sampling is the oracle's VoxelGrid / ApproximateVoxelGrid restatement (oracle/oracle.py), which the device matches bit for bit.
 """
 from __future__ import annotations
+
+import hashlib
 
 import numpy as np
 from scipy.spatial import cKDTree
@@ -35,23 +38,59 @@ def distance_filter(cloud, near=1.0, far=100.0):
     return c[keep].copy()
 
 
-def knn(pts, k, margin=8):
-    """-> (idx [n,k] int64 (-1 none), d2 [n,k] float32 (inf none), tie [n] bool: k-th and (k+1)-th distances are equal)."""
-    p = np.asarray(pts, F)[:, :3]
+_KNN_MEMO = {}
+KNN_BRUTE_MAX = 8192          # up to here the candidates come from all n float32 distances, not from the tree
+
+
+def _candidates(p, m, brute):
+    """[n, m] indices holding, per point, m points none of the others is nearer than: in the float32 FLANN distance (brute force) or in
+    cKDTree's float64 one.  Which members of a tie group at the m-th place are taken is arbitrary: knn() checks that it does not matter."""
     n = p.shape[0]
-    m = min(n, k + margin)
-    _, cand = cKDTree(p.astype(np.float64)).query(p.astype(np.float64), k=m)
-    cand = np.asarray(cand).reshape(n, m)
-    d2 = f32_sqdist(p[:, None, :], p[cand])
-    order = np.lexsort((cand, d2), axis=-1)
-    cand = np.take_along_axis(cand, order, 1)
-    d2 = np.take_along_axis(d2, order, 1)
+    if not brute:
+        _, cand = cKDTree(p.astype(np.float64)).query(p.astype(np.float64), k=m)
+        return np.asarray(cand).reshape(n, m)
+    cand = np.empty((n, m), np.int64)
+    for a in range(0, n, 512):
+        d2 = f32_sqdist(p[a:a + 512, None, :], p[None, :, :])
+        cand[a:a + 512] = np.argpartition(d2, m - 1, axis=1)[:, :m] if m < n else np.arange(n)[None, :]
+    return cand
+
+
+def knn(pts, k, margin=8, brute=None):
+    """-> (idx [n,k] int64 (-1 none), d2 [n,k] float32 (inf none), tie [n] bool: k-th and (k+1)-th distances are equal).
+
+    Safe under ties: the candidate window grows until, for every point, its last candidate is strictly farther than the k-th neighbour
+    (or the window is the whole cloud), so the whole tie group of the k-th distance is inside the window and the (distance, index) order
+    decides its members.  brute: all n distances in float32 (default up to KNN_BRUTE_MAX points), else cKDTree candidates."""
+    p = np.ascontiguousarray(np.asarray(pts, F)[:, :3])
+    n = p.shape[0]
     kk = min(k, n)
+    if brute is None:
+        brute = n <= KNN_BRUTE_MAX
+    memo = (hashlib.sha1(p.tobytes()).digest(), n, k, margin, bool(brute))   # the tests ask for the same lists under both switch values
+    if memo in _KNN_MEMO:
+        return _KNN_MEMO[memo]
+    with np.errstate(invalid="ignore", over="ignore"):
+        while True:
+            m = min(n, k + margin)
+            cand = _candidates(p, m, brute)
+            d2 = f32_sqdist(p[:, None, :], p[cand])
+            order = np.lexsort((cand, d2), axis=-1)
+            cand = np.take_along_axis(cand, order, 1)
+            d2 = np.take_along_axis(d2, order, 1)
+            cut = int(np.count_nonzero(~(d2[:, m - 1] > d2[:, kk - 1]))) if m < n else 0
+            if cut == 0:
+                break
+            margin *= 2
+    assert cut == 0                  # a condition, not a tolerance: no point's k-th tie group may be cut by the window
     idx = np.full((n, k), -1, np.int64)
     dd = np.full((n, k), np.inf, F)
     idx[:, :kk] = cand[:, :kk]
     dd[:, :kk] = d2[:, :kk]
     tie = (d2[:, kk - 1] == d2[:, kk]) if m > kk else np.zeros(n, bool)
+    if len(_KNN_MEMO) >= 8:
+        _KNN_MEMO.pop(next(iter(_KNN_MEMO)))
+    _KNN_MEMO[memo] = (idx, dd, tie)
     return idx, dd, tie
 
 
@@ -113,7 +152,7 @@ def _roots2(b, c):
     return np.zeros_like(b), F(0.5) * (b - sd), F(0.5) * (b + sd)
 
 
-def _roots(m):
+def _roots(m, census=None):
     m00, m01, m02, m11, m12, m22 = m[:, 0], m[:, 1], m[:, 2], m[:, 4], m[:, 5], m[:, 8]
     c0 = m00 * m11 * m22 + F(2) * m01 * m02 * m12 - m00 * m12 * m12 - m11 * m02 * m02 - m22 * m01 * m01
     c1 = m00 * m11 - m01 * m01 + m00 * m22 - m02 * m02 + m11 * m22 - m12 * m12
@@ -140,15 +179,21 @@ def _roots(m):
     r0, r1 = np.where(sw2, r1, r0), np.where(sw2, r0, r1)
     q0, q1, q2 = _roots2(c2, c1)
     use2 = (np.abs(c0) < FLT_EPSILON) | (r0 <= 0)
+    if census is not None:
+        census["c0_small"] = np.abs(c0) < FLT_EPSILON
+        census["root_nonpositive"] = ~census["c0_small"] & (r0 <= 0)
     return np.where(use2, q0, r0)
 
 
-def eigen33_smallest(cov9):
+def eigen33_smallest(cov9, census=None):
+    """census: a dict that receives one boolean mask per branch of eigen33 (which points took it); the arithmetic is the same."""
     cov9 = np.asarray(cov9, F)
     scale = np.abs(cov9).max(axis=1)
+    if census is not None:
+        census["scale_tiny"] = scale <= FLT_MIN
     scale = np.where(scale <= FLT_MIN, F(1), scale)
     m = cov9 / scale[:, None]
-    r0 = _roots(m)
+    r0 = _roots(m, census)
     m = m.copy()
     for a in (0, 4, 8):
         m[:, a] = m[:, a] - r0
@@ -163,10 +208,12 @@ def eigen33_smallest(cov9):
     pick2 = ~pick1 & (l2 >= l1) & (l2 >= l3)
     v = np.where(pick1[:, None], v1, np.where(pick2[:, None], v2, v3))
     ln = np.where(pick1, l1, np.where(pick2, l2, l3))
+    if census is not None:
+        census["pick1"], census["pick2"], census["pick3"] = pick1, pick2, ~pick1 & ~pick2
     return v / np.sqrt(ln)[:, None]
 
 
-def normals(cloud, lidar=(0.0, 0.0, 0.0)):
+def normals(cloud, lidar=(0.0, 0.0, 0.0), census=None):
     """-> (normals [n,3] normalised and flipped, cov9 [n,9], keep [n], band [n], tie [n])."""
     c = np.asarray(cloud, F)
     n = c.shape[0]
@@ -188,7 +235,7 @@ def normals(cloud, lidar=(0.0, 0.0, 0.0)):
         cov[:, 5] = acc[:, 4] - acc[:, 7] * acc[:, 8]
         cov[:, 8] = acc[:, 5] - acc[:, 8] * acc[:, 8]
         cov[:, 3], cov[:, 6], cov[:, 7] = cov[:, 1], cov[:, 2], cov[:, 5]
-        nv = eigen33_smallest(cov)
+        nv = eigen33_smallest(cov, census)
         vp = np.asarray([F(lidar[0]), F(lidar[1]), F(lidar[2])], F)
         d = vp[None, :] - c[:, :3]
         cos_t = (d[:, 0] * nv[:, 0] + d[:, 1] * nv[:, 1]) + d[:, 2] * nv[:, 2]
@@ -228,10 +275,11 @@ def cloud_callback(cloud, params=None, lidar=(0.0, 0.0, 0.0), orc=None):
     elif c.shape[0] and pr["downsample_method"] == "APPROX_VOXELGRID":
         c = orc.approx_voxel_grid(c, pr["downsample_resolution"])
     if pr["outlier_removal_method"] == "STATISTICAL":
-        c, st = statistical_outlier_removal(c, pr["statistical_mean_k"], pr["statistical_stddev"])
+        c, st = statistical_outlier_removal(c, pr["statistical_mean_k"], pr["statistical_stddev"],
+                                                pr.get("statistical_sqrt_float", STATISTICAL_SQRT_FLOAT))
         info["statistical_near"] = int(np.count_nonzero(st["near"]))
     elif pr["outlier_removal_method"] == "RADIUS":
-        c, tie = radius_outlier_removal(c, pr["radius_radius"], pr["radius_min_neighbors"])
+        c, tie = radius_outlier_removal(c, pr["radius_radius"], pr["radius_min_neighbors"], pr.get("radius_inclusive", RADIUS_INCLUSIVE))
         info["radius_ties"] = int(np.count_nonzero(tie))
     f3 = c
     h = height_filter(f3, lidar[2])
