@@ -1,1 +1,10 @@
 """delta_graph_slam_amd -- MI355X-native scan registration (NDT / GICP) hot path."""
+
+__all__ = ["MapCloudGenerator"]
+
+
+def __getattr__(name):   # resolved on first use: importing the package alone loads neither torch nor the HIP library
+    if name == "MapCloudGenerator":
+        from .map_cloud import MapCloudGenerator
+        return MapCloudGenerator
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

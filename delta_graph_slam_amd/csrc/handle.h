@@ -121,6 +121,30 @@ struct PfScratch {
   int64_t normal_n = 0;
 };
 
+// MapCloudGenerator::generate (map_cloud.hip): the keyframe / chunk tables, the chunk boxes, the key table and the last map.
+// Separate from everything a registration or the prefilter uses.
+struct McFrame;   // map_cloud.hip
+struct McChunk;
+struct McEpoch;
+struct McScratch {
+  DevBuf<float4> in;                   // staged host input, all keyframes back to back
+  DevBuf<McFrame> frames;              // per keyframe: points, size, float pose
+  DevBuf<McChunk> chunks;              // per chunk of a keyframe: keyframe, first point, points
+  DevBuf<float> boxes;                 // per chunk: transformed min3, max3, finite points, pad
+  DevBuf<McEpoch> epochs;              // growth replay: per run of points inserted under one box, its min and the later key offsets
+  DevBuf<int> found;                   // [0] running minimum of the find-first pass; [4..7] its result: index, x, y, z (bit-cast)
+  DevBuf<unsigned long long> table;    // open-addressing key table / all keys of the sort path
+  DevBuf<unsigned long long> keys, keys_alt;   // unique keys, unsorted and sorted
+  DevBuf<long long> cnt;               // [0] selected keys, [1] table overflow flag
+  DevBuf<unsigned char> temp;          // rocPRIM temporary storage
+  DevBuf<float4> out;                  // the last map
+  int64_t n_out = 0;
+  double bb_min[3] = {0, 0, 0}, bb_max[3] = {0, 0, 0};
+  int depth = 0, growths = 0;
+  int find_launches = 0;               // find-first launches of the last map (growth events + the first point + stale boxes)
+  int used_sort = 0;                   // the last map took the sort path
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -320,6 +344,9 @@ struct dgs_handle {
   // ---- prefilter (prefilter.hip): own buffers and index; the registration's target / source / model / results are left untouched
   dgs::PfScratch pf;
 
+  // ---- map cloud (map_cloud.hip): own buffers; registration and prefilter state are left untouched
+  dgs::McScratch mc;
+
   dgs::Profiler prof;
 };
 
@@ -398,6 +425,8 @@ void icp_release(dgs_handle* h);
 int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out = nullptr);   // out: default h->knn_nbr
 // prefilter.hip
 void prefilter_release(dgs_handle* h);
+// map_cloud.hip
+void map_cloud_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -463,6 +463,54 @@ int dgs_prefilter_normal(dgs_handle* h, const float* in_xyz16, int64_t n, int32_
 int dgs_prefilter_get_statistics(dgs_handle* h, float* mean_distances, int64_t capacity, double* stats4, int64_t* n);
 int dgs_prefilter_get_normals(dgs_handle* h, float* normals4, float* cov9, int64_t capacity, int64_t* n);
 
+/* ---- MapCloudGenerator::generate on the device (src/hdl_graph_slam/map_cloud_generator.cpp:13-50) ------------
+ * Every keyframe cloud transformed by its pose (pose.matrix().cast<float>(), w = 1, no FMA), concatenated in keyframe and point
+ * order, inserted into a pcl::octree::OctreePointCloud of `resolution` and replaced by the centres of the occupied voxels in the
+ * octree's depth-first order; with resolution <= 0 the concatenation itself is the result.  The keyframe clouds are read in place
+ * (the concatenation is never built when resolution > 0); only the poses travel.  The map works in buffers of its own: the
+ * handle's registration target / source / NDT model / results and the prefilter's scratch are untouched.
+ * Semantics, including the PCL 1.10 details recalled from upstream ([UPSTREAM-RECALL]): DESIGN.md §6d.  Each recalled detail whose
+ * error would change the output is a field here (1 = as recalled, the default):
+ *   first_box_oversize:       the first finite point p defines [p - res/2, p + res/2]; getKeyBitSize, with no leaves yet, widens it
+ *                             by the oversize res/2 on both sides to [p - res, p + res] (1), or sets max = min + 2 res (0).
+ *   grow_shift_without_upper: a growth moves min by the side length on every axis WITHOUT an upper violation (1), or only on the
+ *                             axes with a lower violation (0).
+ *   max_minus_epsilon:        after a growth max = min + (side - FLT_EPSILON) (1), or min + side (0).
+ *   child_index_x_msb:        child index (x_bit << 2) | (y_bit << 1) | z_bit (1), or (z_bit << 2) | (y_bit << 1) | x_bit (0).
+ *   key_at_insertion:         a leaf stays where genOctreeKeyforPoint put it under the box of the moment it was inserted, and later
+ *                             growths move it by whole voxels (1); or every key is made with the final min (0).
+ * dedup_method: DGS_MAP_DEDUP_AUTO = the hash table when twice the points fit 2^26 slots, else the sort of all keys; a table that
+ * overflows (a probe sequence longer than 4,096) is also redone by the sort.  HASH: the table, clamped to 2^26 slots; SORT: the sort.
+ * hash_slots (test hook): slots of the table, rounded up to a power of two; 0 = sized from the point count. */
+enum dgs_map_dedup { DGS_MAP_DEDUP_AUTO = 0, DGS_MAP_DEDUP_HASH = 1, DGS_MAP_DEDUP_SORT = 2 };
+typedef struct dgs_map_cloud_params {
+  uint32_t struct_size; /* sizeof(dgs_map_cloud_params), set by dgs_map_cloud_params_init */
+  int32_t first_box_oversize;
+  int32_t grow_shift_without_upper;
+  int32_t max_minus_epsilon;
+  int32_t child_index_x_msb;
+  int32_t key_at_insertion;
+  int32_t dedup_method; /* dgs_map_dedup */
+  int64_t hash_slots;
+} dgs_map_cloud_params;
+int dgs_map_cloud_params_init(dgs_map_cloud_params* params);
+/* clouds[k]: xyz16 points of keyframe k (sizes[k] <= INT32_MAX of them; host arrays, or device pointers with in_on_device; NULL
+ * allowed where sizes[k] == 0); poses16: 16 doubles per keyframe, COLUMN-major (Eigen::Isometry3d::matrix()), cast to float here.
+ * *n_out = points of the map, which stays on the handle until the next map call: read it with dgs_map_cloud_get.
+ * n_keyframes == 0 is not an error and gives 0 (the callers' layers return null, as upstream :14-17).  A span that needs an octree
+ * deeper than 21 levels is DGS_ERR_GRID_TOO_LARGE: nothing is produced, the handle stays usable. */
+int dgs_map_cloud_generate(dgs_handle* h, const dgs_map_cloud_params* params, int32_t n_keyframes, const float* const* clouds, const int64_t* sizes,
+                           int32_t in_on_device, const double* poses16, double resolution, int64_t* n_out);
+/* The same over resident clouds (on the handle's device); they are not modified, their indices and covariances stay valid. */
+int dgs_map_cloud_generate_clouds(dgs_handle* h, const dgs_map_cloud_params* params, int32_t n_keyframes, dgs_cloud* const* clouds,
+                                  const double* poses16, double resolution, int64_t* n_out);
+/* Copies the last map out (host array, or device pointer with out_on_device).  *n is always the full count;
+ * DGS_ERR_INVALID_ARGUMENT when it exceeds `capacity` (capacity 0 with a NULL array asks for the count alone). */
+int dgs_map_cloud_get(dgs_handle* h, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n);
+/* Test hook over the last map with resolution > 0: the octree's final bounding box (3 + 3 doubles), depth and the number of
+ * growths (new roots); all zero after a concatenation or an empty map.  Every pointer is nullable. */
+int dgs_map_cloud_get_grid(dgs_handle* h, double* min3, double* max3, int32_t* depth, int32_t* growths);
+
 #ifdef __cplusplus
 }
 #endif
