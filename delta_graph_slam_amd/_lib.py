@@ -61,6 +61,12 @@ class PrefilterParams(C.Structure):
                 ("statistical_sqrt_float", C.c_int32)]
 
 
+class PrefilterScanParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("has_angular_velocity", C.c_int32), ("angular_velocity", C.c_double * 3),
+                ("scan_period", C.c_double), ("has_transform", C.c_int32), ("transform", C.c_double * 16), ("deskew_norm_order", C.c_int32),
+                ("transform_sets_w", C.c_int32)]
+
+
 class MapCloudParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("first_box_oversize", C.c_int32), ("grow_shift_without_upper", C.c_int32),
                 ("max_minus_epsilon", C.c_int32), ("child_index_x_msb", C.c_int32), ("key_at_insertion", C.c_int32), ("dedup_method", C.c_int32), ("hash_slots", C.c_int64)]
@@ -69,6 +75,7 @@ class MapCloudParams(C.Structure):
 MAP_DEDUP = {"AUTO": 0, "HASH": 1, "SORT": 2}
 PF_DOWNSAMPLE = {"NONE": 0, "VOXELGRID": 1, "APPROX_VOXELGRID": 2}
 PF_OUTLIER = {"NONE": 0, "STATISTICAL": 1, "RADIUS": 2}
+PF_NORM_ORDER = {"PAIRS_XY_ZW": 0, "PAIRS_XZ_YW": 1, "SEQUENTIAL": 2}
 
 
 class Result(C.Structure):
@@ -93,6 +100,7 @@ SYMBOLS = [
     "dgs_pcl_gicp_set_probe", "dgs_pcl_gicp_evaluate", "dgs_pcl_gicp_set_correspondence_randomness",
     "dgs_prefilter_params_init", "dgs_prefilter", "dgs_prefilter_distance", "dgs_prefilter_radius", "dgs_prefilter_statistical",
     "dgs_prefilter_normal", "dgs_prefilter_get_statistics", "dgs_prefilter_get_normals",
+    "dgs_prefilter_scan_params_init", "dgs_prefilter_scan", "dgs_prefilter_deskew",
     "dgs_map_cloud_params_init", "dgs_map_cloud_generate", "dgs_map_cloud_generate_clouds", "dgs_map_cloud_get", "dgs_map_cloud_get_grid",
 ]
 
@@ -201,6 +209,11 @@ def load(path=None):
     lib.dgs_prefilter_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_prefilter_get_statistics.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, P(C.c_int64)]
     lib.dgs_prefilter_get_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_prefilter_scan_params_init.argtypes = [P(PrefilterScanParams)]
+    lib.dgs_prefilter_scan.argtypes = [C.c_void_p, P(PrefilterParams), P(PrefilterScanParams), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64), P(C.c_int64), C.c_void_p]
+    lib.dgs_prefilter_deskew.argtypes = [C.c_void_p, P(PrefilterScanParams), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                         P(C.c_int64)]
     lib.dgs_map_cloud_params_init.argtypes = [P(MapCloudParams)]
     lib.dgs_map_cloud_generate.argtypes = [C.c_void_p, P(MapCloudParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double,
                                            P(C.c_int64)]

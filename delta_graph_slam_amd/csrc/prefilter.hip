@@ -1,5 +1,7 @@
-// PrefilteringNodelet::cloud_callback (/root/reference/apps/prefiltering_nodelet.cpp:111-164) from the distance filter to flatten.
+// PrefilteringNodelet::cloud_callback (/root/reference/apps/prefiltering_nodelet.cpp:111-164) from the distance filter to flatten,
+// and, through dgs_prefilter_scan, from the raw scan: deskewing (:293-354) and the base_link transform (:122-150) in front of it.
 //
+//   deskewing (:340-351) -> base_link transform (:137-149) -> [the raw-scan head, fused into the distance filter's pass]
 //   distance filter (:275-291) -> down-sampling (:249-260) -> outlier removal (:262-273)   = /filtered_points
 //   height filter (:192-212) -> normal filter (:217-245) -> flatten (:166-188)            = /flat_filtered_points
 //
@@ -13,6 +15,9 @@
 //     lane sorts its list (bitonic network in registers) before any order-dependent sum.
 //   * StatisticalOutlierRemoval's mean and standard deviation are a fixed-order reduction in one workgroup; the threshold is
 //     compared on the device.
+//   * The raw-scan head is two kernels over the raw cloud: pf_head_flag_kernel deskews, transforms and takes the distance decision per
+//     point, and pf_head_scatter_kernel recomputes the point and writes it at its compacted place.  No cloud-sized deskewed or
+//     transformed intermediate exists; the count and scan kernels between the two are the compaction's own.
 //   * The host reads a count back after each compaction that a later pass needs as a size (the NN index and the voxel filters are
 //     shaped on the host), and once at the end.
 // Semantics and the PCL 1.10 details recalled from upstream: DESIGN.md §6c.
@@ -121,6 +126,100 @@ __global__ __launch_bounds__(kBlock) void pf_height_kernel(const float4* __restr
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   flags[i] = ((double)in[i].z > lz) ? 1 : 0;
+}
+
+// ================================================================================================ raw-scan head
+// What the head does to a point; by value in the kernel arguments.
+struct PfHead {
+  int deskew;          // an angular velocity was given (the IMU queue was not empty, :295-297)
+  int transform;       // a base_link transform was given (:123)
+  int norm_order;      // dgs_prefilter_scan_params::deskew_norm_order
+  int sets_w;          // dgs_prefilter_scan_params::transform_sets_w
+  float ang_v[3];      // (float)angular_velocity * -1.0f (:330-331)
+  double scan_period;  // :340
+  double m[12];        // rows 0..2 of the 4 x 4 double matrix (:146)
+};
+
+// deskewing (:345-350) then pcl::transformPointCloud (:146) of point i of n.  Float where upstream is float, double where it is double,
+// operation for operation, no contraction.  DESIGN.md 6c restates every line.
+__device__ __forceinline__ float4 pf_head_point(float4 p, const long long i, const long long n, const PfHead& hd) {
+#pragma clang fp contract(off)
+  if (hd.deskew) {
+    // double delta_t = scan_period * static_cast<double>(i) / cloud->size();
+    const double half_t = hd.scan_period * (double)i / (double)n / 2.0;
+    // Eigen::Quaternionf delta_q(1, delta_t / 2.0 * ang_v[0], ...): the double products narrowed to float
+    const float qw = 1.0f;
+    const float qx = (float)(half_t * (double)hd.ang_v[0]);
+    const float qy = (float)(half_t * (double)hd.ang_v[1]);
+    const float qz = (float)(half_t * (double)hd.ang_v[2]);
+    // delta_q.inverse(): conjugate / squaredNorm when that is > 0, else the zero quaternion
+    const float xx = qx * qx, yy = qy * qy, zz = qz * qz, ww = qw * qw;
+    const float n2 = hd.norm_order == 0 ? (xx + yy) + (zz + ww) : hd.norm_order == 1 ? (xx + zz) + (yy + ww) : ((xx + yy) + zz) + ww;
+    float ix = 0.f, iy = 0.f, iz = 0.f, iw = 0.f;
+    if (n2 > 0.f) {
+      ix = -qx / n2;
+      iy = -qy / n2;
+      iz = -qz / n2;
+      iw = qw / n2;
+    }
+    // q * v, Eigen's _transformVector: uv = q.vec x v; uv += uv; v + w * uv + q.vec x uv
+    float ux = iy * p.z - iz * p.y;
+    float uy = iz * p.x - ix * p.z;
+    float uz = ix * p.y - iy * p.x;
+    ux = ux + ux;
+    uy = uy + uy;
+    uz = uz + uz;
+    const float rx = (p.x + iw * ux) + (iy * uz - iz * uy);
+    const float ry = (p.y + iw * uy) + (iz * ux - ix * uz);
+    const float rz = (p.z + iw * uz) + (ix * uy - iy * ux);
+    p.x = rx;
+    p.y = ry;
+    p.z = rz;   // the fourth float is copied (:349)
+  }
+  // the non-dense branch of transformPointCloud copies a non-finite point as it is
+  if (hd.transform && isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+    p.x = (float)(((hd.m[0] * x + hd.m[1] * y) + hd.m[2] * z) + hd.m[3]);
+    p.y = (float)(((hd.m[4] * x + hd.m[5] * y) + hd.m[6] * z) + hd.m[7]);
+    p.z = (float)(((hd.m[8] * x + hd.m[9] * y) + hd.m[10] * z) + hd.m[11]);
+    if (hd.sets_w) p.w = 1.0f;
+  }
+  return p;
+}
+
+// head + distance_filter's decision (pf_distance_kernel's, on the transformed point)
+__global__ __launch_bounds__(kBlock) void pf_head_flag_kernel(const float4* __restrict__ in, const long long n, const PfHead hd, const double near_t,
+                                                              const double far_t, unsigned char* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pf_head_point(in[i], i, n, hd);
+  const float d = sqrtf(add_rn(add_rn(mul_rn(p.x, p.x), mul_rn(p.y, p.y)), mul_rn(p.z, p.z)));
+  const double dd = (double)d;
+  flags[i] = (dd > near_t && dd < far_t) ? 1 : 0;
+}
+
+// pf_scatter_kernel over the raw cloud: the kept point is recomputed from the raw one and written at its compacted place
+__global__ __launch_bounds__(kBlock) void pf_head_scatter_kernel(const float4* __restrict__ in, const unsigned char* __restrict__ flags, const long long n,
+                                                                 const PfHead hd, const int* __restrict__ blk, float4* __restrict__ out) {
+  __shared__ int s_w[kBlock / kWave];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const bool f = i < n && flags[i] != 0;
+  const unsigned long long m = __ballot(f);
+  if (lane == 0) s_w[wv] = __popcll(m);
+  __syncthreads();
+  if (!f) return;
+  int off = blk[blockIdx.x];
+  for (int w = 0; w < wv; w++) off += s_w[w];
+  off += __popcll(m & ((1ull << lane) - 1ull));
+  out[off] = pf_head_point(in[i], i, n, hd);   // off < number of kept points <= n: `out` holds n points
+}
+
+// the two steps alone (dgs_prefilter_deskew): every point, non-finite ones included, at its own place
+__global__ __launch_bounds__(kBlock) void pf_head_apply_kernel(const float4* __restrict__ in, const long long n, const PfHead hd, float4* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  out[i] = pf_head_point(in[i], i, n, hd);
 }
 
 // ================================================================================================ k-NN passes
@@ -397,8 +496,9 @@ namespace {
 
 inline unsigned pf_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-// compact `in` (n points) by pf.flags into `out` (reserved for n points); *m = kept points (read back: the host waits here)
-int pf_compact(dgs_handle* h, const float4* in, int64_t n, DevBuf<float4>& out, bool flatten, int64_t* m) {
+// compact `in` (n points) by pf.flags into `out` (reserved for n points); *m = kept points (read back: the host waits here).
+// With a head, `in` is the raw cloud and the scatter writes the deskewed, transformed point.
+int pf_compact(dgs_handle* h, const float4* in, int64_t n, DevBuf<float4>& out, bool flatten, int64_t* m, const PfHead* head = nullptr) {
   PfScratch& pf = h->pf;
   *m = 0;
   if (n == 0) return DGS_OK;
@@ -408,7 +508,10 @@ int pf_compact(dgs_handle* h, const float4* in, int64_t n, DevBuf<float4>& out, 
   DGS_HIP_TRY(h, pf.cnt.reserve(4));
   hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, pf.flags.ptr, (int)n, pf.blk.ptr);
   hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kPfScanBlock), 0, h->stream, pf.blk.ptr, (int)nb, pf.cnt.ptr);
-  hipLaunchKernelGGL(pf_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, in, pf.flags.ptr, (int)n, pf.blk.ptr, out.ptr, flatten ? 1 : 0);
+  if (head)
+    hipLaunchKernelGGL(pf_head_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, in, pf.flags.ptr, (long long)n, *head, pf.blk.ptr, out.ptr);
+  else
+    hipLaunchKernelGGL(pf_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, in, pf.flags.ptr, (int)n, pf.blk.ptr, out.ptr, flatten ? 1 : 0);
   DGS_HIP_TRY(h, hipGetLastError());
   if (ensure_pinned(h, 4096) != DGS_OK) return DGS_ERR_HIP;
   int* hc = reinterpret_cast<int*>(h->pinned);
@@ -439,6 +542,15 @@ int pf_distance(dgs_handle* h, const float4* in, int64_t n, double near_t, doubl
   if (int rc = pf_reserve_flags(h, n)) return rc;
   hipLaunchKernelGGL(pf_distance_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, in, (int)n, near_t, far_t, h->pf.flags.ptr);
   return pf_compact(h, in, n, out, false, m);
+}
+
+// the raw-scan head in front of the distance filter: one flag pass and one compaction over the raw cloud, as pf_distance
+int pf_head_distance(dgs_handle* h, const float4* in, int64_t n, const PfHead& head, double near_t, double far_t, DevBuf<float4>& out, int64_t* m) {
+  *m = 0;
+  if (n == 0) return DGS_OK;
+  if (int rc = pf_reserve_flags(h, n)) return rc;
+  hipLaunchKernelGGL(pf_head_flag_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, in, (long long)n, head, near_t, far_t, h->pf.flags.ptr);
+  return pf_compact(h, in, n, out, false, m, &head);
 }
 
 int pf_radius(dgs_handle* h, const float4* in, int64_t n, double radius, int min_neighbors, int inclusive, DevBuf<float4>& out, int64_t* m) {
@@ -544,6 +656,87 @@ bool pf_bad_io(const float* in_xyz16, int64_t n, const float* out, const int64_t
   return !n_out || n < 0 || n > INT32_MAX || (n > 0 && !in_xyz16) || cap < 0 || (cap > 0 && !out);
 }
 
+// dgs_prefilter_scan_params -> the head's kernel argument and lidar_position (:113, :143)
+bool pf_make_head(const dgs_prefilter_scan_params* sp, PfHead* head, double* lidar) {
+  if (!sp || sp->struct_size != sizeof(dgs_prefilter_scan_params) || sp->deskew_norm_order < DGS_PF_NORM_PAIRS_XY_ZW ||
+      sp->deskew_norm_order > DGS_PF_NORM_SEQUENTIAL)
+    return false;
+  std::memset(head, 0, sizeof(*head));
+  head->deskew = sp->has_angular_velocity ? 1 : 0;
+  head->transform = sp->has_transform ? 1 : 0;
+  head->norm_order = sp->deskew_norm_order;
+  head->sets_w = sp->transform_sets_w ? 1 : 0;
+  for (int a = 0; a < 3; a++) head->ang_v[a] = (float)sp->angular_velocity[a] * -1.0f;   // Eigen::Vector3f ang_v(...); ang_v *= -1 (:330-331)
+  head->scan_period = sp->scan_period;
+  for (int a = 0; a < 12; a++) head->m[a] = sp->transform[a];
+  lidar[0] = lidar[1] = lidar[2] = 0.0;   // Eigen::Vector3d::Zero() (:113)
+  if (sp->has_transform) { lidar[0] = sp->transform[3]; lidar[1] = sp->transform[7]; lidar[2] = sp->transform[11]; }   // .translation() (:143)
+  return true;
+}
+
+// cloud_callback from :120 (with a head) or from :153 (without) to :160
+int pf_chain(dgs_handle* h, const dgs_prefilter_params* p, const PfHead* head, const float* in_xyz16, int64_t n, int32_t in_on_device,
+             const double* lidar_xyz, float* out3d, int64_t cap3d, float* out2d, int64_t cap2d, int32_t out_on_device, int64_t* n3d_out, int64_t* n2d_out) {
+  if (!h || !p || p->struct_size != sizeof(dgs_prefilter_params) || pf_bad_io(in_xyz16, n, out3d, n3d_out, cap3d) || !n2d_out || cap2d < 0 ||
+      (cap2d > 0 && !out2d))
+    return DGS_ERR_INVALID_ARGUMENT;
+  if (p->downsample_method < DGS_PF_DOWNSAMPLE_NONE || p->downsample_method > DGS_PF_DOWNSAMPLE_APPROX_VOXELGRID ||
+      p->outlier_removal_method < DGS_PF_OUTLIER_NONE || p->outlier_removal_method > DGS_PF_OUTLIER_RADIUS ||
+      (p->downsample_method != DGS_PF_DOWNSAMPLE_NONE && !(p->downsample_resolution > 0)))
+    return DGS_ERR_INVALID_ARGUMENT;
+  *n3d_out = 0;
+  *n2d_out = 0;
+  if (int rc = pf_begin(h)) return rc;
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  const double* lidar = lidar_xyz ? lidar_xyz : zero3;
+  PfScratch& pf = h->pf;
+  pf.stat_n = pf.normal_n = 0;
+  if (n == 0) return DGS_OK;   // cloud_callback returns on an empty cloud (:116-118): nothing is published
+  const float4* in = nullptr;
+  int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
+  // 1. distance filter (applied whatever use_distance_filter says, :153), behind the raw-scan head when there is one
+  int64_t n1 = 0;
+  if (rc == DGS_OK)
+    rc = head ? pf_head_distance(h, in, n, *head, p->distance_near_thresh, p->distance_far_thresh, pf.a, &n1)
+              : pf_distance(h, in, n, p->distance_near_thresh, p->distance_far_thresh, pf.a, &n1);
+  // 2. down-sampling: the voxel filters' own code paths (ndt_voxel.hip)
+  const float4* s2 = pf.a.ptr;
+  int64_t n2 = n1;
+  if (rc == DGS_OK && n1 > 0 && p->downsample_method != DGS_PF_DOWNSAMPLE_NONE) {
+    if (pf.b.reserve((size_t)n1) != hipSuccess) { h->err = "hipMalloc failed"; return pf_finish(h, DGS_ERR_HIP); }
+    const float leaf = (float)p->downsample_resolution;   // setLeafSize(float, float, float)
+    rc = p->downsample_method == DGS_PF_DOWNSAMPLE_VOXELGRID ? voxel_grid_filter(h, pf.a.ptr, n1, leaf, pf.b.ptr, n1, &n2)
+                                                             : approx_voxel_grid_filter(h, pf.a.ptr, n1, leaf, pf.b.ptr, n1, &n2);
+    s2 = pf.b.ptr;
+  }
+  // 3. outlier removal -> /filtered_points
+  const float4* s3 = s2;
+  int64_t n3 = n2;
+  if (rc == DGS_OK && p->outlier_removal_method == DGS_PF_OUTLIER_STATISTICAL) {
+    rc = pf_statistical(h, s2, n2, p->statistical_mean_k, p->statistical_stddev, p->statistical_sqrt_float, pf.c, &n3);
+    s3 = pf.c.ptr;
+  } else if (rc == DGS_OK && p->outlier_removal_method == DGS_PF_OUTLIER_RADIUS) {
+    rc = pf_radius(h, s2, n2, p->radius_radius, p->radius_min_neighbors, p->radius_inclusive, pf.c, &n3);
+    s3 = pf.c.ptr;
+  }
+  // 4. height filter, 5. normal filter + 6. flatten (the scatter of the normal pass writes z = 0)
+  int64_t n4 = 0, n5 = 0;
+  if (rc == DGS_OK && n3 > 0) {
+    if ((rc = pf_reserve_flags(h, n3)) == DGS_OK) {
+      hipLaunchKernelGGL(pf_height_kernel, dim3(pf_blocks(n3)), dim3(kBlock), 0, h->stream, s3, (int)n3, lidar[2], pf.flags.ptr);
+      rc = pf_compact(h, s3, n3, pf.d, false, &n4);
+    }
+  }
+  if (rc == DGS_OK && n4 > 0) rc = pf_normal(h, pf.d.ptr, n4, lidar, pf.e, true, &n5);
+  if (rc == DGS_OK) {
+    *n3d_out = n3;
+    *n2d_out = n5;
+    rc = pf_output(h, s3, n3, out3d, cap3d, out_on_device);
+    if (rc == DGS_OK) rc = pf_output(h, pf.e.ptr, n5, out2d, cap2d, out_on_device);
+  }
+  return pf_finish(h, rc);
+}
+
 }  // namespace
 
 void prefilter_release(dgs_handle* h) {
@@ -581,60 +774,45 @@ int dgs_prefilter_params_init(dgs_prefilter_params* p) {
 
 int dgs_prefilter(dgs_handle* h, const dgs_prefilter_params* p, const float* in_xyz16, int64_t n, int32_t in_on_device, const double* lidar_xyz,
                   float* out3d, int64_t cap3d, float* out2d, int64_t cap2d, int32_t out_on_device, int64_t* n3d_out, int64_t* n2d_out) {
-  if (!h || !p || p->struct_size != sizeof(dgs_prefilter_params) || pf_bad_io(in_xyz16, n, out3d, n3d_out, cap3d) || !n2d_out || cap2d < 0 ||
-      (cap2d > 0 && !out2d))
-    return DGS_ERR_INVALID_ARGUMENT;
-  if (p->downsample_method < DGS_PF_DOWNSAMPLE_NONE || p->downsample_method > DGS_PF_DOWNSAMPLE_APPROX_VOXELGRID ||
-      p->outlier_removal_method < DGS_PF_OUTLIER_NONE || p->outlier_removal_method > DGS_PF_OUTLIER_RADIUS ||
-      (p->downsample_method != DGS_PF_DOWNSAMPLE_NONE && !(p->downsample_resolution > 0)))
-    return DGS_ERR_INVALID_ARGUMENT;
-  *n3d_out = 0;
-  *n2d_out = 0;
+  return pf_chain(h, p, nullptr, in_xyz16, n, in_on_device, lidar_xyz, out3d, cap3d, out2d, cap2d, out_on_device, n3d_out, n2d_out);
+}
+
+int dgs_prefilter_scan_params_init(dgs_prefilter_scan_params* p) {
+  if (!p) return DGS_ERR_INVALID_ARGUMENT;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->scan_period = 0.1;
+  for (int a = 0; a < 4; a++) p->transform[5 * a] = 1.0;
+  p->deskew_norm_order = DGS_PF_NORM_PAIRS_XY_ZW;
+  p->transform_sets_w = 1;
+  return DGS_OK;
+}
+
+int dgs_prefilter_scan(dgs_handle* h, const dgs_prefilter_params* p, const dgs_prefilter_scan_params* sp, const float* in_xyz16, int64_t n,
+                       int32_t in_on_device, float* out3d, int64_t cap3d, float* out2d, int64_t cap2d, int32_t out_on_device, int64_t* n3d_out,
+                       int64_t* n2d_out, double* lidar_xyz_out) {
+  PfHead head;
+  double lidar[3];
+  if (!pf_make_head(sp, &head, lidar)) return DGS_ERR_INVALID_ARGUMENT;
+  if (lidar_xyz_out) std::memcpy(lidar_xyz_out, lidar, sizeof(lidar));
+  return pf_chain(h, p, &head, in_xyz16, n, in_on_device, lidar, out3d, cap3d, out2d, cap2d, out_on_device, n3d_out, n2d_out);
+}
+
+int dgs_prefilter_deskew(dgs_handle* h, const dgs_prefilter_scan_params* sp, const float* in_xyz16, int64_t n, int32_t in_on_device, float* out_xyz16,
+                         int64_t cap, int32_t out_on_device, int64_t* n_out) {
+  PfHead head;
+  double lidar[3];
+  if (!h || !pf_make_head(sp, &head, lidar) || pf_bad_io(in_xyz16, n, out_xyz16, n_out, cap)) return DGS_ERR_INVALID_ARGUMENT;
+  *n_out = 0;
   if (int rc = pf_begin(h)) return rc;
-  const double zero3[3] = {0.0, 0.0, 0.0};
-  const double* lidar = lidar_xyz ? lidar_xyz : zero3;
-  PfScratch& pf = h->pf;
-  pf.stat_n = pf.normal_n = 0;
-  if (n == 0) return DGS_OK;   // cloud_callback returns on an empty cloud (:116-118): nothing is published
+  if (n == 0) return DGS_OK;
   const float4* in = nullptr;
   int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
-  // 1. distance filter (applied whatever use_distance_filter says, :153)
-  int64_t n1 = 0;
-  if (rc == DGS_OK) rc = pf_distance(h, in, n, p->distance_near_thresh, p->distance_far_thresh, pf.a, &n1);
-  // 2. down-sampling: the voxel filters' own code paths (ndt_voxel.hip)
-  const float4* s2 = pf.a.ptr;
-  int64_t n2 = n1;
-  if (rc == DGS_OK && n1 > 0 && p->downsample_method != DGS_PF_DOWNSAMPLE_NONE) {
-    if (pf.b.reserve((size_t)n1) != hipSuccess) { h->err = "hipMalloc failed"; return pf_finish(h, DGS_ERR_HIP); }
-    const float leaf = (float)p->downsample_resolution;   // setLeafSize(float, float, float)
-    rc = p->downsample_method == DGS_PF_DOWNSAMPLE_VOXELGRID ? voxel_grid_filter(h, pf.a.ptr, n1, leaf, pf.b.ptr, n1, &n2)
-                                                             : approx_voxel_grid_filter(h, pf.a.ptr, n1, leaf, pf.b.ptr, n1, &n2);
-    s2 = pf.b.ptr;
-  }
-  // 3. outlier removal -> /filtered_points
-  const float4* s3 = s2;
-  int64_t n3 = n2;
-  if (rc == DGS_OK && p->outlier_removal_method == DGS_PF_OUTLIER_STATISTICAL) {
-    rc = pf_statistical(h, s2, n2, p->statistical_mean_k, p->statistical_stddev, p->statistical_sqrt_float, pf.c, &n3);
-    s3 = pf.c.ptr;
-  } else if (rc == DGS_OK && p->outlier_removal_method == DGS_PF_OUTLIER_RADIUS) {
-    rc = pf_radius(h, s2, n2, p->radius_radius, p->radius_min_neighbors, p->radius_inclusive, pf.c, &n3);
-    s3 = pf.c.ptr;
-  }
-  // 4. height filter, 5. normal filter + 6. flatten (the scatter of the normal pass writes z = 0)
-  int64_t n4 = 0, n5 = 0;
-  if (rc == DGS_OK && n3 > 0) {
-    if ((rc = pf_reserve_flags(h, n3)) == DGS_OK) {
-      hipLaunchKernelGGL(pf_height_kernel, dim3(pf_blocks(n3)), dim3(kBlock), 0, h->stream, s3, (int)n3, lidar[2], pf.flags.ptr);
-      rc = pf_compact(h, s3, n3, pf.d, false, &n4);
-    }
-  }
-  if (rc == DGS_OK && n4 > 0) rc = pf_normal(h, pf.d.ptr, n4, lidar, pf.e, true, &n5);
+  if (rc == DGS_OK && h->pf.a.reserve((size_t)n) != hipSuccess) { h->err = "hipMalloc failed"; rc = DGS_ERR_HIP; }
   if (rc == DGS_OK) {
-    *n3d_out = n3;
-    *n2d_out = n5;
-    rc = pf_output(h, s3, n3, out3d, cap3d, out_on_device);
-    if (rc == DGS_OK) rc = pf_output(h, pf.e.ptr, n5, out2d, cap2d, out_on_device);
+    hipLaunchKernelGGL(pf_head_apply_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, in, (long long)n, head, h->pf.a.ptr);
+    *n_out = n;
+    rc = pf_output(h, h->pf.a.ptr, n, out_xyz16, cap, out_on_device);
   }
   return pf_finish(h, rc);
 }

@@ -1,9 +1,11 @@
-"""PrefilteringNodelet's filter chain on the device: /root/reference/apps/prefiltering_nodelet.cpp:111-164 from the distance filter
-to flatten, over dgs_prefilter (include/dgs_reg.h).
+"""PrefilteringNodelet's cloud_callback on the device: /root/reference/apps/prefiltering_nodelet.cpp:111-164, from the raw scan
+(dgs_prefilter_scan) or from the distance filter (dgs_prefilter) to flatten (include/dgs_reg.h).
 
-`Prefilter(params)` takes the nodelet's private parameter names with initialize_params' defaults (:55-109);
-`cloud_callback(cloud, lidar_position)` returns (/filtered_points, /flat_filtered_points).  Deskewing and the base_link transform stay
-with the caller, which passes lidar_position.  Clouds are float32 [N,4]: numpy in gives numpy out, a device tensor in gives device
+`Prefilter(params)` takes the nodelet's private parameter names with initialize_params' defaults (:55-109).
+`filter_scan(cloud, angular_velocity, base_link_transform)` takes the scan as the driver delivers it: deskewing (:293-354) and the
+base_link transform (:122-150) run fused into the distance filter's pass, and it returns (/filtered_points, /flat_filtered_points,
+lidar_position).  `ImuQueue` is the nodelet's IMU queue (:107-109, :318-328).  `cloud_callback(cloud, lidar_position)` is the chain
+alone, for a caller that has done the two steps itself.  Clouds are float32 [N,4]: numpy in gives numpy out, a device tensor in gives device
 tensors out.  Like InformationMatrixCalculator, a Prefilter may share a Registration's handle: it uses buffers and an NN index of
 its own, so the registration's target, source and results are untouched.
 """
@@ -17,7 +19,7 @@ import numpy as np
 from . import _lib as L
 from .registration import Registration, _cloud_ptr, torch
 
-__all__ = ["Prefilter", "params_from_dict"]
+__all__ = ["Prefilter", "ImuQueue", "params_from_dict"]
 
 
 def params_from_dict(params: Optional[dict] = None) -> L.PrefilterParams:
@@ -44,9 +46,41 @@ def params_from_dict(params: Optional[dict] = None) -> L.PrefilterParams:
     return p
 
 
+class ImuQueue:
+    """The nodelet's imu_queue: imu_callback (:107-109) is push, the search in deskewing (:318-328) is select."""
+
+    def __init__(self):
+        self.queue = []                      # (stamp, angular_velocity) in arrival order
+
+    def __len__(self):
+        return len(self.queue)
+
+    def push(self, stamp, angular_velocity):
+        self.queue.append((stamp, tuple(float(v) for v in angular_velocity)))
+
+    def select(self, scan_stamp):
+        """-> the angular velocity deskewing uses for a scan stamped scan_stamp, or None when the queue is empty (:295-297).
+        The first message stamped after the scan (strictly) is chosen, else the last one; everything before the position where
+        the search stopped is erased (:328).  So when no message is later than the scan the queue is emptied, and the next scan
+        goes through without deskewing unless a message arrives first: upstream's behaviour, kept."""
+        if not self.queue:
+            return None
+        loc = 0
+        chosen = self.queue[0]
+        while loc < len(self.queue):
+            chosen = self.queue[loc]
+            if chosen[0] > scan_stamp:
+                break
+            loc += 1
+        del self.queue[:loc]
+        return chosen[1]
+
+
 class Prefilter:
     def __init__(self, params: Optional[dict] = None, registration: Optional[Registration] = None, device: Optional[int] = None):
         self.params = params_from_dict(params)
+        self.deskew_norm_order = 0           # dgs_prefilter_scan_params.deskew_norm_order (L.PF_NORM_ORDER)
+        self.transform_sets_w = 1            # dgs_prefilter_scan_params.transform_sets_w
         if registration is None:
             registration = Registration("NDT_OMP", device=device)   # any handle: only its stream and the prefilter's own buffers are used
         self.registration = registration
@@ -84,6 +118,45 @@ class Prefilter:
         self._check(self._lib.dgs_prefilter(self._h, C.byref(self.params), ptr, n, dev, self._lidar(lidar_position), self._ptr(o3), n,
                                             self._ptr(o2), n, dev, C.byref(m3), C.byref(m2)))
         return self._take(o3, m3.value), self._take(o2, m2.value)
+
+    def _scan_params(self, angular_velocity, base_link_transform, scan_period) -> L.PrefilterScanParams:
+        sp = L.PrefilterScanParams()
+        self._check(self._lib.dgs_prefilter_scan_params_init(C.byref(sp)))
+        sp.scan_period = float(scan_period)
+        sp.deskew_norm_order = int(self.deskew_norm_order)
+        sp.transform_sets_w = 1 if self.transform_sets_w else 0
+        if angular_velocity is not None:     # None is the empty IMU queue (:295-297), not a zero angular velocity
+            sp.has_angular_velocity = 1
+            sp.angular_velocity[:] = [float(v) for v in angular_velocity]
+        if base_link_transform is not None:
+            m = np.array(base_link_transform, np.float64).reshape(4, 4)
+            m[0, 3] = 0.0                    # lidar scans should be centered in base_link (:141-142)
+            m[1, 3] = 0.0
+            sp.has_transform = 1
+            sp.transform[:] = m.reshape(16).tolist()
+        return sp
+
+    def filter_scan(self, cloud, angular_velocity=None, base_link_transform=None, scan_period=0.1):
+        """cloud_callback from the raw scan (:120-160) -> (filtered3d, filtered2d, lidar_position).  angular_velocity: the IMU
+        message's, as ImuQueue.select returns it, or None (no deskewing); base_link_transform: the 4 x 4 matrix of the tf lookup
+        (:131-138) or None; lidar_position: float64 [3], (0, 0, m[2,3]) with a transform, zero without."""
+        ptr, n, dev, keep = _cloud_ptr(cloud)
+        sp = self._scan_params(angular_velocity, base_link_transform, scan_period)
+        o3, o2 = self._new(cloud, n), self._new(cloud, n)
+        m3, m2 = C.c_int64(0), C.c_int64(0)
+        lidar = np.zeros(3, np.float64)
+        self._check(self._lib.dgs_prefilter_scan(self._h, C.byref(self.params), C.byref(sp), ptr, n, dev, self._ptr(o3), n, self._ptr(o2), n, dev,
+                                                 C.byref(m3), C.byref(m2), lidar.ctypes.data_as(C.c_void_p)))
+        return self._take(o3, m3.value), self._take(o2, m2.value), lidar
+
+    def deskew(self, cloud, angular_velocity=None, base_link_transform=None, scan_period=0.1):
+        """Deskewing and the base_link transform alone (dgs_prefilter_deskew): every point at its own place, non-finite ones included."""
+        ptr, n, dev, keep = _cloud_ptr(cloud)
+        sp = self._scan_params(angular_velocity, base_link_transform, scan_period)
+        out = self._new(cloud, n)
+        m = C.c_int64(0)
+        self._check(self._lib.dgs_prefilter_deskew(self._h, C.byref(sp), ptr, n, dev, self._ptr(out), n, dev, C.byref(m)))
+        return self._take(out, m.value)
 
     def _stage(self, fn, cloud, *args):
         ptr, n, dev, keep = _cloud_ptr(cloud)

@@ -463,6 +463,46 @@ int dgs_prefilter_normal(dgs_handle* h, const float* in_xyz16, int64_t n, int32_
 int dgs_prefilter_get_statistics(dgs_handle* h, float* mean_distances, int64_t capacity, double* stats4, int64_t* n);
 int dgs_prefilter_get_normals(dgs_handle* h, float* normals4, float* cov9, int64_t capacity, int64_t* n);
 
+/* ---- The raw scan: deskewing (apps/prefiltering_nodelet.cpp:293-354) and the base_link_frame transform (:122-150) in front of the
+ * chain, fused into the distance filter's pass over the raw cloud.  Semantics: DESIGN.md §6c.
+ * deskew_norm_order replaces the squaredNorm inside delta_q.inverse() (:347): its association over the quaternion coefficients
+ *   stored (x, y, z, w) [UPSTREAM-RECALL, Eigen 3.3 with SSE3]. */
+enum dgs_prefilter_norm_order {
+  DGS_PF_NORM_PAIRS_XY_ZW = 0, /* (x² + y²) + (z² + w²): hadd(hadd), the default */
+  DGS_PF_NORM_PAIRS_XZ_YW = 1, /* (x² + z²) + (y² + w²) */
+  DGS_PF_NORM_SEQUENTIAL = 2   /* ((x² + y²) + z²) + w² */
+};
+/* Replaces the per-scan state of deskewing (:330-331 ang_v, :340 scan_period) and of the transform (:137-146 transform_isometry).
+ * has_angular_velocity = 0 is the nodelet's empty IMU queue (:295-297): the input bits pass untouched, which a zero angular velocity
+ * does not promise (-0.0f comes out +0.0f).  transform is the row-major 4 x 4 double matrix handed to pcl::transformPointCloud
+ * (:146), taken as given: the caller zeroes m(0,3) and m(1,3) (:141-142).  transform_sets_w: the transformed point's fourth float is
+ * 1.0f (1, PCL 1.10 [UPSTREAM-RECALL]) or the input's (0); a non-finite point is copied whole either way.
+ * Defaults (dgs_prefilter_scan_params_init): neither step, scan_period 0.1, identity, norm order 0, sets_w 1. */
+typedef struct dgs_prefilter_scan_params {
+  uint32_t struct_size;          /* sizeof(dgs_prefilter_scan_params), set by dgs_prefilter_scan_params_init */
+  int32_t has_angular_velocity;
+  double angular_velocity[3];    /* imu_msg->angular_velocity x, y, z as received (the sign flip of :331 is applied inside) */
+  double scan_period;
+  int32_t has_transform;
+  double transform[16];
+  int32_t deskew_norm_order;     /* dgs_prefilter_norm_order */
+  int32_t transform_sets_w;
+} dgs_prefilter_scan_params;
+/* Replaces the defaults deskewing reads: scan_period 0.1 (:340), no IMU message (:295), an empty base_link_frame (:104, :123). */
+int dgs_prefilter_scan_params_init(dgs_prefilter_scan_params* params);
+/* Replaces cloud_callback from :120 to :160: deskewing, the base_link transform, then dgs_prefilter's chain with
+ * lidar_position = transform.translation() (:143; zero without a transform, :113), which lidar_xyz_out (3 doubles, nullable)
+ * receives.  Argument and error conventions are dgs_prefilter's; a wrong struct_size of either struct or a deskew_norm_order
+ * outside 0..2 is DGS_ERR_INVALID_ARGUMENT.  The raw cloud is read by the head's two kernels only and no deskewed or transformed
+ * cloud is stored; with neither step enabled the result is dgs_prefilter's with a zero lidar_xyz. */
+int dgs_prefilter_scan(dgs_handle* h, const dgs_prefilter_params* chain_params, const dgs_prefilter_scan_params* scan_params, const float* in_xyz16,
+                       int64_t n, int32_t in_on_device, float* out3d_xyz16, int64_t cap3d, float* out2d_xyz16, int64_t cap2d, int32_t out_on_device,
+                       int64_t* n3d_out, int64_t* n2d_out, double* lidar_xyz_out);
+/* Replaces deskewing (:340-351) and pcl::transformPointCloud (:146) alone: every point at its own place, non-finite ones included,
+ * *n_out == n.  For tests, and for callers that publish the deskewed cloud. */
+int dgs_prefilter_deskew(dgs_handle* h, const dgs_prefilter_scan_params* scan_params, const float* in_xyz16, int64_t n, int32_t in_on_device,
+                         float* out_xyz16, int64_t out_capacity, int32_t out_on_device, int64_t* n_out);
+
 /* ---- MapCloudGenerator::generate on the device (src/hdl_graph_slam/map_cloud_generator.cpp:13-50) ------------
  * Every keyframe cloud transformed by its pose (pose.matrix().cast<float>(), w = 1, no FMA), concatenated in keyframe and point
  * order, inserted into a pcl::octree::OctreePointCloud of `resolution` and replaced by the centres of the occupied voxels in the

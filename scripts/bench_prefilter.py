@@ -4,6 +4,9 @@
   HDL-64 (64 x 4096 rays) and VLP-16 (16 x 1875 rays), with the launch file's parameters (RADIUS 0.5 / 2) and the code defaults
   (STATISTICAL 20 / 1.0), both with VOXELGRID 0.1; and a per-stage split from the single-stage entry points on the chain's
   intermediate clouds.  Kernel times: run `--chain-only` under `rocprofv3 --kernel-trace --stats`.
+  Raw-scan row (`*_scan_ms`): filter_scan (dgs_prefilter_scan) on the same frame with an angular velocity and a base_link transform
+  given; `*_scan_chain_ms` is dgs_prefilter alone on that frame deskewed and transformed beforehand (the same work behind the head),
+  and `*_head_ms` the difference: what deskewing and the transform cost per frame.  `*_ms` stays dgs_prefilter on the raw frame.
 
 usage: python scripts/bench_prefilter.py [--warmup W] [--steps K] [--chain-only]
 """
@@ -22,6 +25,8 @@ from delta_graph_slam_amd.prefilter import Prefilter  # noqa: E402
 DEFAULTS = {}
 LAUNCH = dict(distance_near_thresh=0.1, outlier_removal_method="RADIUS", radius_radius=0.5, radius_min_neighbors=2, statistical_mean_k=30,
               statistical_stddev=1.2)
+IMU = (0.3, -0.8, 1.1)                      # rad/s
+BASE_LINK = np.array([[0.954, -0.2955, -0.0478, 0.4], [0.2951, 0.9553, -0.0148, -0.2], [0.05, 0.0, 0.9988, 1.7], [0.0, 0.0, 0.0, 1.0]])
 
 
 def ev_ms(fn, warmup, steps):
@@ -57,6 +62,13 @@ def main():
             f3, f2 = pf.cloud_callback(c)
             out[f"{key}_n3d"], out[f"{key}_n2d"] = int(f3.shape[0]), int(f2.shape[0])
             out[f"{key}_ms"] = round(ev_ms(lambda: pf.cloud_callback(c), a.warmup, a.steps), 4)
+            if hasattr(pf, "filter_scan"):   # absent from a build of an earlier commit run for comparison
+                s3, s2, lidar = pf.filter_scan(c, IMU, BASE_LINK)
+                out[f"{key}_scan_n3d"], out[f"{key}_scan_n2d"] = int(s3.shape[0]), int(s2.shape[0])
+                out[f"{key}_scan_ms"] = round(ev_ms(lambda: pf.filter_scan(c, IMU, BASE_LINK), a.warmup, a.steps), 4)
+                mid = pf.deskew(c, IMU, BASE_LINK)       # the same work behind the head: the chain alone on the deskewed, transformed frame
+                out[f"{key}_scan_chain_ms"] = round(ev_ms(lambda: pf.cloud_callback(mid, lidar), a.warmup, a.steps), 4)
+                out[f"{key}_head_ms"] = round(out[f"{key}_scan_ms"] - out[f"{key}_scan_chain_ms"], 4)
             if a.chain_only:
                 continue
             d = pf.distance_filter(c)
