@@ -1,10 +1,13 @@
 """delta_graph_slam_amd -- MI355X-native scan registration (NDT / GICP) hot path."""
 
-__all__ = ["MapCloudGenerator"]
+__all__ = ["MapCloudGenerator", "LineExtractor"]
 
 
 def __getattr__(name):   # resolved on first use: importing the package alone loads neither torch nor the HIP library
     if name == "MapCloudGenerator":
         from .map_cloud import MapCloudGenerator
         return MapCloudGenerator
+    if name == "LineExtractor":
+        from .line_extraction import LineExtractor
+        return LineExtractor
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

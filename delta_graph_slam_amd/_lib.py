@@ -72,6 +72,25 @@ class MapCloudParams(C.Structure):
                 ("max_minus_epsilon", C.c_int32), ("child_index_x_msb", C.c_int32), ("key_at_insertion", C.c_int32), ("dedup_method", C.c_int32), ("hash_slots", C.c_int64)]
 
 
+class LineExtractionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_cluster_size", C.c_int32), ("max_cluster_size", C.c_int32), ("cluster_tolerance", C.c_float),
+                ("sac_distance_threshold", C.c_float), ("max_iterations", C.c_int32), ("merror_threshold", C.c_float),
+                ("line_length_threshold", C.c_float), ("sac_method_type", C.c_int32), ("sample_good_any_axis", C.c_int32),
+                ("sqnorm_order", C.c_int32), ("cluster_inclusive", C.c_int32), ("max_rounds", C.c_int32), ("record_lists", C.c_int32)]
+
+
+class LineFeatureC(C.Structure):
+    _fields_ = [("point_a", C.c_double * 3), ("point_b", C.c_double * 3), ("mean_error", C.c_double), ("std_sigma", C.c_double),
+                ("max_error", C.c_double), ("min_error", C.c_double)]
+
+
+class LineExtractionRound(C.Structure):
+    _fields_ = [("n_before", C.c_int32), ("draws", C.c_int32), ("iterations", C.c_int32), ("sample0", C.c_int32), ("sample1", C.c_int32),
+                ("inliers", C.c_int32), ("cluster", C.c_int32), ("emitted", C.c_int32)]
+
+
+LE_STATUS = {0: "DONE", 1: "RANSAC_FAILED", 2: "STALL", 3: "MAX_ROUNDS", 4: "RNG_EXHAUSTED"}
+SAC_METHODS = ["SAC_RANSAC", "SAC_LMEDS", "SAC_MSAC", "SAC_RRANSAC", "SAC_RMSAC", "SAC_MLESAC", "SAC_PROSAC"]
 MAP_DEDUP = {"AUTO": 0, "HASH": 1, "SORT": 2}
 PF_DOWNSAMPLE = {"NONE": 0, "VOXELGRID": 1, "APPROX_VOXELGRID": 2}
 PF_OUTLIER = {"NONE": 0, "STATISTICAL": 1, "RADIUS": 2}
@@ -102,6 +121,7 @@ SYMBOLS = [
     "dgs_prefilter_normal", "dgs_prefilter_get_statistics", "dgs_prefilter_get_normals",
     "dgs_prefilter_scan_params_init", "dgs_prefilter_scan", "dgs_prefilter_deskew",
     "dgs_map_cloud_params_init", "dgs_map_cloud_generate", "dgs_map_cloud_generate_clouds", "dgs_map_cloud_get", "dgs_map_cloud_get_grid",
+    "dgs_line_extraction_params_init", "dgs_line_extraction", "dgs_line_extraction_get_rounds",
 ]
 
 _libs = {}
@@ -220,5 +240,9 @@ def load(path=None):
     lib.dgs_map_cloud_generate_clouds.argtypes = [C.c_void_p, P(MapCloudParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_double, P(C.c_int64)]
     lib.dgs_map_cloud_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_map_cloud_get_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int32), P(C.c_int32)]
+    lib.dgs_line_extraction_params_init.argtypes = [P(LineExtractionParams)]
+    lib.dgs_line_extraction.argtypes = [C.c_void_p, P(LineExtractionParams), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_int64, P(C.c_int64), P(C.c_int32)]
+    lib.dgs_line_extraction_get_rounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib

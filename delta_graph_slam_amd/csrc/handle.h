@@ -145,6 +145,31 @@ struct McScratch {
   int used_sort = 0;                   // the last map took the sort path
 };
 
+// LineBasedScanmatcher::line_extraction (line_extraction.hip): the two round clouds, the draw list and hypotheses of a round, the
+// inlier / cluster lists, the clustering's sort and union-find arrays, and what the test hook reads back.  Separate from everything
+// a registration, the prefilter or the map cloud uses.
+struct LnHyp;     // line_extraction.hip
+struct LnRound;
+struct LnScratch {
+  DevBuf<float4> a, b;                 // the remaining points of this round and of the next
+  DevBuf<float4> inl, clu, sorted;     // inliers / cluster members (w = position in the round's cloud); inliers in projection order
+  DevBuf<unsigned char> flags, cflags; // inlier / keep flag per point; cluster flag per point
+  DevBuf<int> blk, cnt;                // compaction offsets; [0] inliers, [1] cluster members, [2] points kept
+  DevBuf<int> draws;                   // two point indices per draw
+  DevBuf<LnHyp> hyps;                  // the good draws in order, at most max_iterations + 1
+  DevBuf<int> counts, meta;            // inliers per hypothesis; [0] good draws, [1] draw that completes 1000 bad ones in a row
+  DevBuf<LnRound> round;
+  DevBuf<uint32_t> keys, keys_alt, vals, vals_alt;
+  DevBuf<float> sproj;                 // projection on the line per sorted inlier
+  DevBuf<int> parent, csize, cminpos;  // union-find over sorted inliers; members and lowest position per root
+  DevBuf<unsigned char> temp;          // sort temporary storage
+  std::vector<dgs_line_extraction_round> rounds;        // the last extraction
+  std::vector<std::vector<int32_t>> inlier_lists, cluster_lists;   // with record_lists
+  std::vector<uint32_t> mt_raw;        // mt19937(12345)() >> 1, extended on demand
+  std::vector<int> perm;               // identity between rounds: shuffled_indices_
+  int64_t counts4[4] = {0, 0, 0, 0};
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -347,6 +372,9 @@ struct dgs_handle {
   // ---- map cloud (map_cloud.hip): own buffers; registration and prefilter state are left untouched
   dgs::McScratch mc;
 
+  // ---- line extraction (line_extraction.hip): own buffers; registration, prefilter and map cloud state are left untouched
+  dgs::LnScratch ln;
+
   dgs::Profiler prof;
 };
 
@@ -427,6 +455,8 @@ int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out = nullptr); 
 void prefilter_release(dgs_handle* h);
 // map_cloud.hip
 void map_cloud_release(dgs_handle* h);
+// line_extraction.hip
+void line_extraction_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -551,6 +551,75 @@ int dgs_map_cloud_get(dgs_handle* h, float* out_xyz16, int64_t capacity, int32_t
  * growths (new roots); all zero after a concatenation or an empty map.  Every pointer is nullable. */
 int dgs_map_cloud_get_grid(dgs_handle* h, double* min3, double* max3, int32_t* depth, int32_t* growths);
 
+/* ---- LineBasedScanmatcher::line_extraction on the device (src/hdl_graph_slam/line_based_scanmatcher.cpp:299-457) --------------
+ * Repeats, while at least min_cluster_size points remain: a RANSAC line fit (pcl::SACSegmentation, SACMODEL_LINE, optimised
+ * coefficients), a Euclidean clustering of its inliers, the distance statistics of the biggest cluster and its removal.  Semantics,
+ * the PCL 1.10 details recalled from upstream and the two places where this differs on purpose (stalls): DESIGN.md 6e.
+ * The extractor works in buffers of its own: the handle's registration target / source / results, the prefilter's scratch and the
+ * map are untouched.  Additions only: DGS_ABI_VERSION is unchanged. */
+enum dgs_line_extraction_status {
+  DGS_LE_DONE = 0,          /* fewer than min_cluster_size points remain: upstream's loop condition */
+  DGS_LE_RANSAC_FAILED = 1, /* a round drew 1000 bad samples in a row (upstream reads an empty coefficient vector there) */
+  DGS_LE_STALL = 2,         /* every cluster of a round was larger than max_cluster_size (upstream loops forever there) */
+  DGS_LE_MAX_ROUNDS = 3,    /* the max_rounds safety cap */
+  DGS_LE_RNG_EXHAUSTED = 4  /* the caller's rng_raw stream ran out */
+};
+/* Defaults (dgs_line_extraction_params_init) = LineBasedScanmatcher's constructor (line_based_scanmatcher.hpp:80-89): 25, 25000,
+ * 1.0f, 0.1f, 500, 150, 1.0, SAC_RANSAC; any-axis sample test, norm order 0, inclusive clustering, 4096 rounds. */
+typedef struct dgs_line_extraction_params {
+  uint32_t struct_size;          /* sizeof(dgs_line_extraction_params), set by dgs_line_extraction_params_init */
+  int32_t min_cluster_size;
+  int32_t max_cluster_size;
+  float cluster_tolerance;
+  float sac_distance_threshold;
+  int32_t max_iterations;
+  float merror_threshold;        /* a line is emitted iff mean_error < merror_threshold ... */
+  float line_length_threshold;   /* ... and |A - B| > line_length_threshold (upstream spells it line_lenght_threshold) */
+  int32_t sac_method_type;       /* only 0 (pcl::SAC_RANSAC) is served: anything else is DGS_ERR_INVALID_ARGUMENT */
+  int32_t sample_good_any_axis;  /* 1: a sample is good when its points differ in x OR y OR z (later PCL); 0: x AND y AND z (recalled
+                                    for PCL 1.10), which never accepts a sample of a flattened cloud */
+  int32_t sqnorm_order;          /* dgs_prefilter_norm_order of the squared norm in the inlier test (its w term is 0).  For a flattened
+                                    cloud (z = 0 everywhere) two of the three terms are +-0 and every association gives the same bits */
+  int32_t cluster_inclusive;     /* 1: two points are linked iff d2 <= tolerance^2, 0: d2 < tolerance^2 (dgs_prefilter_radius' convention) */
+  int32_t max_rounds;            /* safety cap on the rounds of one extraction */
+  int32_t record_lists;          /* test hook: keep every round's inlier and cluster index lists (one more host wait per round) */
+} dgs_line_extraction_params;
+int dgs_line_extraction_params_init(dgs_line_extraction_params* params);
+/* upstream's LineFeature: pointA, pointB, mean_error, std_sigma, max_error, min_error */
+typedef struct dgs_line_feature {
+  double point_a[3];
+  double point_b[3];
+  double mean_error;
+  double std_sigma;
+  double max_error;
+  double min_error;
+} dgs_line_feature;
+/* in_xyz16: n xyz16 points (host array, or device pointer with in_on_device), e.g. dgs_prefilter's 2-D output; it is not modified.
+ * rng_raw (nullable): rng_len values that stand in for boost::mt19937(12345)() >> 1, restarted every round like the generator;
+ * running past its end ends the extraction with DGS_LE_RNG_EXHAUSTED.  lines: room for `capacity` features; more lines than that is
+ * DGS_ERR_INVALID_ARGUMENT.  *status_out (nullable): dgs_line_extraction_status.  Whatever the status, the lines found so far are
+ * returned with DGS_OK. */
+int dgs_line_extraction(dgs_handle* h, const dgs_line_extraction_params* params, const float* in_xyz16, int64_t n, int32_t in_on_device,
+                        const uint32_t* rng_raw, int64_t rng_len, dgs_line_feature* lines, int64_t capacity, int64_t* n_lines,
+                        int32_t* status_out);
+/* Test hook: one record per round of the last extraction. */
+typedef struct dgs_line_extraction_round {
+  int32_t n_before;    /* points the round started with */
+  int32_t draws;       /* samples drawn (two raw values each) */
+  int32_t iterations;  /* hypotheses walked */
+  int32_t sample0;     /* the winner's two point indices (-1 when the round failed) */
+  int32_t sample1;
+  int32_t inliers;
+  int32_t cluster;     /* size of the cluster taken (0: none) */
+  int32_t emitted;
+} dgs_line_extraction_round;
+/* rounds: room for `capacity` records (nullable); *n_rounds is always the full count.  With record_lists, the inlier and cluster
+ * index lists (positions in the round's cloud, ascending) of round `list_round` are copied to inlier_idx / cluster_idx when those
+ * are non-NULL (room for the round's `inliers` / `cluster` entries).  counts4 (nullable): kernel launches, host waits, rounds
+ * launched (re-launches with a longer draw list included) and library sort calls of the last extraction. */
+int dgs_line_extraction_get_rounds(dgs_handle* h, dgs_line_extraction_round* rounds, int64_t capacity, int64_t* n_rounds, int32_t list_round,
+                                   int32_t* inlier_idx, int32_t* cluster_idx, int64_t* counts4);
+
 #ifdef __cplusplus
 }
 #endif
