@@ -1,6 +1,6 @@
 """delta_graph_slam_amd -- MI355X-native scan registration (NDT / GICP) hot path."""
 
-__all__ = ["MapCloudGenerator", "LineExtractor"]
+__all__ = ["MapCloudGenerator", "LineExtractor", "LineScanMatcher"]
 
 
 def __getattr__(name):   # resolved on first use: importing the package alone loads neither torch nor the HIP library
@@ -10,4 +10,7 @@ def __getattr__(name):   # resolved on first use: importing the package alone lo
     if name == "LineExtractor":
         from .line_extraction import LineExtractor
         return LineExtractor
+    if name == "LineScanMatcher":
+        from .line_align import LineScanMatcher
+        return LineScanMatcher
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

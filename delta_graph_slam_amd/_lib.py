@@ -89,6 +89,30 @@ class LineExtractionRound(C.Structure):
                 ("inliers", C.c_int32), ("cluster", C.c_int32), ("emitted", C.c_int32)]
 
 
+class LineAlignParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("angle_gate_float_chain", C.c_int32), ("g_avg_distance_weight", C.c_double),
+                ("g_coverage_weight", C.c_double), ("g_transform_weight", C.c_double), ("g_max_score_distance", C.c_double),
+                ("g_max_score_translation", C.c_double), ("max_distance", C.c_double), ("max_angle", C.c_double),
+                ("nn_tie_highest_index", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LineAlignment(C.Structure):
+    _fields_ = [("transformation", C.c_double * 16), ("fitness_score", C.c_double * 4), ("score", C.c_double), ("winner", C.c_int64),
+                ("n_hypotheses", C.c_int64), ("n_survivors", C.c_int64), ("n_edges_source", C.c_int32), ("n_edges_target", C.c_int32),
+                ("n_lines_target", C.c_int32), ("refine_steps", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EdgeFeatureC(C.Structure):
+    _fields_ = [("edge_point", C.c_double * 3), ("point_a", C.c_double * 3), ("point_b", C.c_double * 3)]
+
+
+class LineAlignHypothesis(C.Structure):
+    _fields_ = [("gate", C.c_int32), ("slot", C.c_int32), ("rotation", C.c_double * 4), ("translation", C.c_double * 3),
+                ("fitness_score", C.c_double * 4), ("score", C.c_double)]
+
+
+LA_STATUS = {0: "ALIGNED", 1: "NO_HYPOTHESES", 2: "ALL_GATED", 3: "NONE_BETTER"}
+LA_GATE = {0: "PASS", 1: "DISTANCE", 2: "IDENTITY", 3: "ANGLE"}
 LE_STATUS = {0: "DONE", 1: "RANSAC_FAILED", 2: "STALL", 3: "MAX_ROUNDS", 4: "RNG_EXHAUSTED"}
 SAC_METHODS = ["SAC_RANSAC", "SAC_LMEDS", "SAC_MSAC", "SAC_RRANSAC", "SAC_RMSAC", "SAC_MLESAC", "SAC_PROSAC"]
 MAP_DEDUP = {"AUTO": 0, "HASH": 1, "SORT": 2}
@@ -122,6 +146,7 @@ SYMBOLS = [
     "dgs_prefilter_scan_params_init", "dgs_prefilter_scan", "dgs_prefilter_deskew",
     "dgs_map_cloud_params_init", "dgs_map_cloud_generate", "dgs_map_cloud_generate_clouds", "dgs_map_cloud_get", "dgs_map_cloud_get_grid",
     "dgs_line_extraction_params_init", "dgs_line_extraction", "dgs_line_extraction_get_rounds",
+    "dgs_line_align_params_init", "dgs_line_align_global", "dgs_line_merge", "dgs_line_edges", "dgs_line_align_get_hypotheses",
 ]
 
 _libs = {}
@@ -244,5 +269,11 @@ def load(path=None):
     lib.dgs_line_extraction.argtypes = [C.c_void_p, P(LineExtractionParams), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_int64, P(C.c_int64), P(C.c_int32)]
     lib.dgs_line_extraction_get_rounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dgs_line_align_params_init.argtypes = [P(LineAlignParams)]
+    lib.dgs_line_align_global.argtypes = [C.c_void_p, P(LineAlignParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_double,
+                                          C.c_void_p, P(LineAlignment)]
+    lib.dgs_line_merge.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, P(C.c_int64)]
+    lib.dgs_line_edges.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_line_align_get_hypotheses.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib

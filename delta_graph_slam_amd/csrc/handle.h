@@ -170,6 +170,22 @@ struct LnScratch {
   int64_t counts4[4] = {0, 0, 0, 0};
 };
 
+// LineBasedScanmatcher::align_global (line_align.hip): the uploaded lines and edges, one record, gate code and fitness per hypothesis,
+// the survivor list and the result record.  Separate from everything a registration, the prefilter, the map cloud or the line
+// extraction uses.
+struct LaHyp;     // line_align.hip
+struct LaResult;
+struct LaScratch {
+  DevBuf<double> in;                   // source lines, target table, source edges, target edges: one upload
+  DevBuf<LaHyp> hyps;                  // per hypothesis h = es * Et + et
+  DevBuf<unsigned char> keep, gate;    // survivor flag and gate code per hypothesis
+  DevBuf<int> blk, cnt, surv, slot;    // compaction offsets; [0] survivors; survivors' h in order; position in that list per h (-1: gated)
+  DevBuf<double> fit;                  // 5 doubles per hypothesis: the four fitness values and the score
+  DevBuf<LaResult> result;
+  int64_t n_hyp = 0;                   // of the last call: what the test hook may read
+  int64_t counts4[4] = {0, 0, 0, 0};   // launches, host waits, hypotheses, survivors
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -374,6 +390,7 @@ struct dgs_handle {
 
   // ---- line extraction (line_extraction.hip): own buffers; registration, prefilter and map cloud state are left untouched
   dgs::LnScratch ln;
+  dgs::LaScratch la;
 
   dgs::Profiler prof;
 };
@@ -457,6 +474,7 @@ void prefilter_release(dgs_handle* h);
 void map_cloud_release(dgs_handle* h);
 // line_extraction.hip
 void line_extraction_release(dgs_handle* h);
+void line_align_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -1,0 +1,436 @@
+// LineBasedScanmatcher::align_global's scalar pieces (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp), restated once for the host
+// and the device: the kernels of line_align.hip, the host-side merge / edge extraction and the refinement pass all call these functions,
+// so a value computed on either side has the same bits but for the trigonometric functions.  Everything is double and must not be
+// contracted (the including file is built with -ffp-contract=off); the float steps are LineFeature::lenght() and the angle gate's
+// transform3Dto2D chain.  Eigen details recalled from memory are tagged [UPSTREAM-RECALL]; DESIGN.md 6f lists them.
+#pragma once
+
+#include <cfloat>
+#include <cmath>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define LA_HD __host__ __device__ __forceinline__
+#else
+#define LA_HD inline
+#endif
+
+namespace dgs {
+namespace la {
+
+struct V3 {
+  double x, y, z;
+};
+struct Line {
+  V3 a, b;
+};
+struct Edge {
+  V3 e, a, b;   // edgePoint, pointA, pointB
+};
+// a planar rigid transform: the upper-left 2 x 2 of the rotation (the rest of the 4 x 4 is the identity's) and the translation
+struct Tf {
+  double r00, r01, r10, r11, tx, ty, tz;
+};
+struct Fitness {
+  double real_avg_distance, avg_distance, coverage, coverage_percentage;
+};
+struct Pair {   // line_to_line_distance's result as nearest_neighbor keeps it
+  double real, dist, cov;
+};
+struct Weights {
+  double avg_distance_weight, coverage_weight, transform_weight, max_score_distance, max_score_translation;
+};
+
+LA_HD V3 v3(double x, double y, double z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
+LA_HD V3 sub(const V3 a, const V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+LA_HD V3 add(const V3 a, const V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+LA_HD V3 scale(const V3 a, const double s) { return v3(a.x * s, a.y * s, a.z * s); }
+// Eigen's 3-term reductions: (x + y) + z [UPSTREAM-RECALL]
+LA_HD double dot(const V3 a, const V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+LA_HD double norm(const V3 a) { return sqrt(dot(a, a)); }
+// MatrixBase::normalized(): divided by sqrt(squaredNorm) when that is > 0 [UPSTREAM-RECALL]
+LA_HD V3 normalized(const V3 a) {
+  const double z = dot(a, a);
+  if (z > 0.0) {
+    const double s = sqrt(z);
+    return v3(a.x / s, a.y / s, a.z / s);
+  }
+  return a;
+}
+LA_HD float lenght(const V3 a, const V3 b) { return (float)norm(sub(a, b)); }   // LineFeature::lenght() returns float
+
+LA_HD Tf tf_identity() { Tf t; t.r00 = 1.0; t.r01 = 0.0; t.r10 = 0.0; t.r11 = 1.0; t.tx = t.ty = t.tz = 0.0; return t; }
+// Matrix3d * Vector3d with rows (r00 r01 0), (r10 r11 0), (0 0 1): ((m0 x + m1 y) + m2 z)
+LA_HD V3 rotate(const Tf t, const V3 p) { return v3((t.r00 * p.x + t.r01 * p.y) + 0.0 * p.z, (t.r10 * p.x + t.r11 * p.y) + 0.0 * p.z, (0.0 * p.x + 0.0 * p.y) + 1.0 * p.z); }
+// transform_lines (:985-1010): the last column of T * [I | p], (((m0 x + m1 y) + m2 z) + m3 * 1).  The third term is +-0 for every
+// planar transform, so Eigen's other association ((m0 x + m1 y) + (m2 z + m3)) gives the same bits [UPSTREAM-RECALL].
+LA_HD V3 apply(const Tf t, const V3 p) {
+  return v3(((t.r00 * p.x + t.r01 * p.y) + 0.0 * p.z) + t.tx, ((t.r10 * p.x + t.r11 * p.y) + 0.0 * p.z) + t.ty, ((0.0 * p.x + 0.0 * p.y) + 1.0 * p.z) + t.tz);
+}
+// AngleAxisd(0, X) * AngleAxisd(0, Y) * AngleAxisd(angle, Z): the quaternion product (1,0,0,0) * (1,0,0,0) * (cos(a/2), 0, 0, sin(a/2)),
+// exact, then Quaternion::toRotationMatrix() -- not cos / sin of the angle itself [UPSTREAM-RECALL]
+LA_HD Tf rot_z(const double angle) {
+  const double ha = 0.5 * angle;
+  const double w = cos(ha), z = sin(ha);
+  const double tz = 2.0 * z, twz = tz * w, tzz = tz * z;
+  Tf t = tf_identity();
+  t.r00 = 1.0 - (0.0 + tzz);
+  t.r01 = 0.0 - twz;
+  t.r10 = 0.0 + twz;
+  t.r11 = 1.0 - (0.0 + tzz);
+  return t;
+}
+// best_trans * transform of two planar 4 x 4 matrices (:196), every entry (((a0 b0 + a1 b1) + a2 b2) + a3 b3) with its zero terms
+LA_HD Tf compose(const Tf a, const Tf b) {
+  Tf r;
+  r.r00 = ((a.r00 * b.r00 + a.r01 * b.r10) + 0.0) + 0.0;
+  r.r01 = ((a.r00 * b.r01 + a.r01 * b.r11) + 0.0) + 0.0;
+  r.r10 = ((a.r10 * b.r00 + a.r11 * b.r10) + 0.0) + 0.0;
+  r.r11 = ((a.r10 * b.r01 + a.r11 * b.r11) + 0.0) + 0.0;
+  r.tx = ((a.r00 * b.tx + a.r01 * b.ty) + 0.0 * b.tz) + a.tx;
+  r.ty = ((a.r10 * b.tx + a.r11 * b.ty) + 0.0 * b.tz) + a.ty;
+  r.tz = ((0.0 * b.tx + 0.0 * b.ty) + 1.0 * b.tz) + a.tz;
+  return r;
+}
+
+// lines_intersection (:473-499); the parallel case yields DBL_MAX coordinates (and does not print)
+LA_HD V3 lines_intersection(const V3 p1a, const V3 p1b, const V3 p2a, const V3 p2b) {
+  const double a1 = p1b.y - p1a.y, b1 = p1a.x - p1b.x, c1 = a1 * p1a.x + b1 * p1a.y;
+  const double a2 = p2b.y - p2a.y, b2 = p2a.x - p2b.x, c2 = a2 * p2a.x + b2 * p2a.y;
+  const double det = a1 * b2 - a2 * b1;
+  if (det != 0.0) return v3((b2 * c1 - b1 * c2) / det, (a1 * c2 - a2 * c1) / det, 0.0);
+  return v3(DBL_MAX, DBL_MAX, 0.0);
+}
+// is_point_on_line (:800-809)
+LA_HD bool is_point_on_line(const V3 p, const V3 a, const V3 b) {
+  const double dot1 = dot(sub(p, a), sub(b, a));
+  const double dot2 = dot(sub(p, b), sub(a, b));
+  return dot1 >= 0.0 && dot2 >= 0.0;
+}
+// point_to_line_distance, the segment form (:776-798); `d` is (B - A).normalized().  Upstream falls off the end when a dot product is
+// NaN; that case returns NaN here.
+LA_HD double point_to_segment(const V3 p, const V3 a, const V3 b, const V3 d) {
+  const V3 proj = add(a, scale(d, dot(sub(p, a), d)));
+  const double dot1 = dot(sub(proj, a), sub(b, a));
+  const double dot2 = dot(sub(proj, b), sub(a, b));
+  if (dot1 >= 0.0 && dot2 >= 0.0) return norm(sub(p, proj));
+  if (dot1 < 0.0) return norm(sub(p, a));
+  if (dot2 < 0.0) return norm(sub(p, b));
+  return NAN;
+}
+// line_to_line_distance (:811-903): source (sa, sb) of float length slen, target (ta, tb) with d = (tb - ta).normalized()
+LA_HD Pair line_to_line(const V3 sa, const V3 sb, const float slen, const V3 ta, const V3 tb, const V3 d) {
+  Pair r;
+  double real = 0.0;
+  real += point_to_segment(sa, ta, tb, d);
+  real += point_to_segment(sb, ta, tb, d);
+  r.real = real / 2.0;
+  double distance1 = 0.0, distance2 = 0.0;
+  V3 point1 = v3(0.0, 0.0, 0.0);
+  bool found = false;
+  V3 proj = add(ta, scale(d, dot(sub(sa, ta), d)));
+  if (is_point_on_line(proj, ta, tb)) {
+    point1 = sa;
+    distance1 = norm(sub(sa, proj));
+    found = true;
+  }
+  proj = add(ta, scale(d, dot(sub(sb, ta), d)));
+  if (is_point_on_line(proj, ta, tb)) {
+    if (!found) {
+      point1 = sb;
+      distance1 = norm(sub(sb, proj));
+      found = true;
+    } else {
+      distance2 = norm(sub(sb, proj));
+      r.dist = (distance1 + distance2) / 2.0;
+      r.cov = norm(sub(sb, point1));
+      return r;
+    }
+  }
+  const V3 f = v3(d.y, -d.x, d.z);   // the direction turned by 90 degrees
+  proj = lines_intersection(sa, sb, ta, add(ta, f));
+  if (is_point_on_line(proj, sa, sb)) {
+    if (!found) {
+      point1 = proj;
+      distance1 = norm(sub(ta, proj));
+      found = true;
+    } else {
+      distance2 = norm(sub(ta, proj));
+      r.dist = (distance1 + distance2) / 2.0;
+      r.cov = norm(sub(proj, point1));
+      return r;
+    }
+  }
+  proj = lines_intersection(sa, sb, tb, add(tb, f));
+  if (is_point_on_line(proj, sa, sb)) {
+    if (found) {
+      distance2 = norm(sub(tb, proj));
+      r.dist = (distance1 + distance2) / 2.0;
+      r.cov = norm(sub(proj, point1));
+      return r;
+    }
+  }
+  (void)slen;   // coverage_percentage = coverage / lenght() is computed upstream and never read by nearest_neighbor
+  r.dist = DBL_MAX;
+  r.cov = 0.0;
+  return r;
+}
+// nearest_neighbor's order (:975-980): the smallest real_distance; equal ones go to the lowest (tie_highest: highest) target index
+// [UPSTREAM-RECALL: std::sort is an insertion sort below 16 elements].  A NaN distance compares like +infinity.
+LA_HD bool nn_better(const double key_b, const int jb, const double key_a, const int ja, const int tie_highest) {
+  if (ja < 0) return jb >= 0;
+  if (jb < 0) return false;
+  if (key_b < key_a) return true;
+  if (key_b > key_a) return false;
+  return tie_highest ? jb > ja : jb < ja;
+}
+LA_HD double nn_key(const double real) { return real != real ? (double)INFINITY : real; }
+
+// calc_fitness_score's running sums (:905-955), is_local = false
+struct Sums {
+  double real_distance, real_distance_lenght, distance, coverage_lenght, total_lenght;
+};
+LA_HD Sums sums_zero() { Sums s; s.real_distance = s.real_distance_lenght = s.distance = s.coverage_lenght = s.total_lenght = 0.0; return s; }
+LA_HD void sums_add(Sums& s, const bool has_nn, const Pair nn, const float slen, const double max_range) {
+  if (has_nn && nn.real < max_range) {
+    s.real_distance += nn.real * (double)slen;
+    s.real_distance_lenght += (double)slen;
+    s.distance += nn.dist * nn.cov;
+    s.coverage_lenght += nn.cov;
+  }
+  s.total_lenght += (double)slen;
+}
+LA_HD Fitness sums_finish(const Sums s) {
+  Fitness f;
+  f.coverage = s.coverage_lenght;
+  f.real_avg_distance = s.real_distance_lenght > 0.0 ? s.real_distance / s.real_distance_lenght : DBL_MAX;
+  f.avg_distance = s.coverage_lenght > 0.0 ? s.distance / s.coverage_lenght : DBL_MAX;
+  f.coverage_percentage = s.total_lenght > 0.0 ? s.coverage_lenght / s.total_lenght * 100.0 : 0.0;
+  return f;
+}
+LA_HD double min_std(const double a, const double b) { return b < a ? b : a; }   // std::min(a, b)
+// weight_global (line_based_scanmatcher.hpp:155-160)
+LA_HD double weight_global(const Weights w, const double avg_distance, const double coverage_percentage, const double translation_distance) {
+  return -w.avg_distance_weight * (min_std(w.max_score_distance, avg_distance) / w.max_score_distance) * 100. + w.coverage_weight * coverage_percentage -
+         w.transform_weight * (min_std(w.max_score_translation, translation_distance) / w.max_score_translation) * 100.;
+}
+
+// angle_between_vectors (:684-691)
+LA_HD double angle_between(const V3 a, const V3 b) {
+  const double dt = a.x * b.x + a.y * b.y;
+  const double det = a.x * b.y - a.y * b.x;
+  return atan2(det, dt);
+}
+// align_edges (:693-740); *used_rot1 says which of the two rotations was taken
+LA_HD Tf align_edges(const Edge e1, const Edge e2, int* used_rot1) {
+  const V3 side1A = sub(e1.a, e1.e), side1B = sub(e1.b, e1.e);
+  V3 side2A = sub(e2.a, e2.e), side2B = sub(e2.b, e2.e);
+  if (norm(side2A) < norm(side2B)) {
+    const V3 t = side2A;
+    side2A = side2B;
+    side2B = t;
+  }
+  const double angle1 = angle_between(side1A, side2A);
+  const double angle2 = angle_between(side1B, side2A);
+  const Tf rot1 = rot_z(angle1), rot2 = rot_z(angle2);
+  const double angle3 = angle_between(rotate(rot1, side1B), side2B);
+  const double angle4 = angle_between(rotate(rot2, side1A), side2B);
+  const bool first = fabs(angle3) < fabs(angle4);
+  Tf t = first ? rot1 : rot2;
+  const V3 tr = sub(e2.e, rotate(t, e1.e));
+  t.tx = tr.x; t.ty = tr.y; t.tz = tr.z;
+  if (used_rot1) *used_rot1 = first ? 1 : 0;
+  return t;
+}
+// align_lines (:742-767)
+LA_HD Tf align_lines(const Line l1, const Line l2) {
+  double angle = angle_between(sub(l1.a, l1.b), sub(l2.a, l2.b));
+  if (angle > M_PI / 2) angle -= M_PI;
+  else if (angle < -M_PI / 2) angle += M_PI;
+  const V3 d = normalized(sub(l2.a, l2.b));
+  const V3 proj = add(l2.a, scale(d, dot(sub(l1.a, l2.a), d)));
+  Tf t = rot_z(angle);
+  const V3 tr = sub(proj, rotate(t, l1.a));
+  t.tx = tr.x; t.ty = tr.y; t.tz = tr.z;
+  return t;
+}
+LA_HD bool is_identity(const Tf t) { return t.r00 == 1.0 && t.r01 == 0.0 && t.r10 == 0.0 && t.r11 == 1.0 && t.tx == 0.0 && t.ty == 0.0 && t.tz == 0.0; }
+
+// The angle gate's Rotation2Dd(transform3Dto2D(transform.cast<float>()).cast<double>().block<2,2>(0,0)).angle() (:139; ros_utils.cpp:95-144),
+// the one place where the chain is restated [UPSTREAM-RECALL: Eigen 3.3's Quaternionf(Matrix3f), toRotationMatrix, eulerAngles(0,1,2),
+// Rotation2D::fromRotationMatrix].  float_chain = 0 takes atan2(r10, r00) in double instead.
+LA_HD double gate_angle(const Tf t, const int float_chain) {
+  if (!float_chain) return atan2(t.r10, t.r00);
+  const float m00 = (float)t.r00, m01 = (float)t.r01, m10 = (float)t.r10, m11 = (float)t.r11, m22 = 1.f;
+  // Quaternionf(rotation matrix): x = y = 0 for a rotation about z
+  float tr = (m00 + m11) + m22, qw, qz;
+  if (tr > 0.f) {
+    tr = sqrtf(tr + 1.f);
+    qw = 0.5f * tr;
+    tr = 0.5f / tr;
+    qz = (m10 - m01) * tr;
+  } else {   // m00 + m11 <= -1 < m22: the branch of the largest diagonal entry, i = 2
+    tr = sqrtf(((m22 - m00) - m11) + 1.f);
+    qz = 0.5f * tr;
+    tr = 0.5f / tr;
+    qw = (m10 - m01) * tr;
+  }
+  // toRotationMatrix()
+  const float tz = 2.f * qz, twz = tz * qw, tzz = tz * qz;
+  const float n00 = 1.f - (0.f + tzz), n01 = 0.f - twz, n10 = 0.f + twz, n11 = 1.f - (0.f + tzz);
+  const float n02 = 0.f, n12 = 0.f, n20 = 0.f, n21 = 0.f, n22 = 1.f;
+  // eulerAngles(0, 1, 2): odd = 0, i = 0, j = 1, k = 2
+  float e0 = atan2f(n12, n22);
+  const float c2 = sqrtf(n00 * n00 + n01 * n01);
+  float e1;
+  if (e0 > 0.f) {
+    e0 -= (float)M_PI;
+    e1 = atan2f(-n02, -c2);
+  } else {
+    e1 = atan2f(-n02, c2);
+  }
+  const float s1 = sinf(e0), c1 = cosf(e0);
+  float e2 = atan2f(s1 * n20 - c1 * n10, c1 * n11 - s1 * n21);
+  e0 = -e0; e1 = -e1; e2 = -e2;
+  // normalize_euler_angs: float - double -> rounded to float
+  const float g0 = (float)((double)e0 - M_PI * (e0 >= .0f ? 1 : -1));
+  const float g1 = (float)((double)e1 - M_PI * (e1 >= .0f ? 1 : -1));
+  const float g2 = (float)((double)e2 - M_PI * (e2 >= .0f ? 1 : -1));
+  const float nn = sqrtf((g0 * g0 + g1 * g1) + g2 * g2), no = sqrtf((e0 * e0 + e1 * e1) + e2 * e2);
+  const float yaw = nn < no ? g2 : e2;
+  // Rotation2Df(yaw).toRotationMatrix() -> double -> Rotation2Dd(matrix).angle()
+  const float s = sinf(yaw), c = cosf(yaw);
+  return atan2((double)s, (double)c);
+}
+
+enum { GATE_PASS = 0, GATE_DISTANCE = 1, GATE_IDENTITY = 2, GATE_ANGLE = 3 };
+// the three gates of :133-143 in upstream's order; *tn receives translation.norm()
+LA_HD int gate(const Tf t, const double max_distance, const int constrain_angle, const double cos_max_angle, const int float_chain, double* tn) {
+  *tn = norm(v3(t.tx, t.ty, t.tz));
+  if (*tn > max_distance) return GATE_DISTANCE;
+  if (is_identity(t)) return GATE_IDENTITY;
+  if (constrain_angle && cos(gate_angle(t, float_chain)) < cos_max_angle) return GATE_ANGLE;
+  return GATE_PASS;
+}
+
+// ---- host only -----------------------------------------------------------------------------------------------------------------
+// are_lines_aligned (:1012-1084): 0 = no merge, 1 = line1 stays (identical lines), 2 = *merged
+inline int are_lines_aligned(const Line l1, const Line l2, Line* merged) {
+  const double cosine = dot(normalized(sub(l1.a, l1.b)), normalized(sub(l2.a, l2.b)));
+  if (fabs(cosine) < 0.9995) return 0;
+  const double thr = 0.3;
+  const double aa = norm(sub(l1.a, l2.a)), bb = norm(sub(l1.b, l2.b)), ab = norm(sub(l1.a, l2.b)), ba = norm(sub(l1.b, l2.a));
+  if ((aa < thr && bb < thr) || (ab < thr && ba < thr)) return 1;
+  if (aa < thr) {
+    if (is_point_on_line(l1.b, l2.a, l2.b) || is_point_on_line(l2.b, l1.a, l1.b)) return 0;
+    merged->a = l1.b; merged->b = l2.b;
+    return 2;
+  } else if (ab < thr) {
+    if (is_point_on_line(l1.b, l2.a, l2.b) || is_point_on_line(l2.a, l1.a, l1.b)) return 0;
+    merged->a = l1.b; merged->b = l2.a;
+    return 2;
+  } else if (ba < thr) {
+    if (is_point_on_line(l1.a, l2.a, l2.b) || is_point_on_line(l2.b, l1.a, l1.b)) return 0;
+    merged->a = l1.a; merged->b = l2.b;
+    return 2;
+  } else if (bb < thr) {
+    if (is_point_on_line(l1.a, l2.a, l2.b) || is_point_on_line(l2.a, l1.a, l1.b)) return 0;
+    merged->a = l1.a; merged->b = l2.a;
+    return 2;
+  }
+  return 0;
+}
+// merge_lines (:1086-1103): erase, i-- and break as upstream; `fresh[i]` marks a line that merging created (its statistics are not set)
+inline void merge_lines(std::vector<Line>& lines, std::vector<int>& origin) {
+  for (int i = 0; i < (int)lines.size(); i++) {
+    for (int j = i + 1; j < (int)lines.size(); j++) {
+      Line m;
+      const int k = are_lines_aligned(lines[(size_t)i], lines[(size_t)j], &m);
+      if (k) {
+        lines.erase(lines.begin() + j);
+        origin.erase(origin.begin() + j);
+        if (k == 2) {
+          lines[(size_t)i] = m;
+          origin[(size_t)i] = -1;
+        }
+        i--;
+        break;
+      }
+    }
+  }
+}
+// get_edges (:501-682) with only_angular_edges = false
+inline void get_edges(const Line l1, const Line l2, std::vector<Edge>& out) {
+  const double cosine = dot(normalized(sub(l1.a, l1.b)), normalized(sub(l2.a, l2.b)));
+  if (fabs(cosine) > 0.5) return;
+  const double min_side = 1.0;
+  const V3 ep = lines_intersection(l1.a, l1.b, l2.a, l2.b);
+  const V3 s1a = sub(l1.a, ep), s1b = sub(l1.b, ep), s2a = sub(l2.a, ep), s2b = sub(l2.b, ep);
+  const double n1a = norm(s1a), n1b = norm(s1b), n2a = norm(s2a), n2b = norm(s2b);
+  const bool same1 = n1a < 0.01 || n1b < 0.01 || norm(sub(normalized(s1a), normalized(s1b))) < 1.;
+  const bool same2 = n2a < 0.01 || n2b < 0.01 || norm(sub(normalized(s2a), normalized(s2b))) < 1.;
+  Edge e;
+  e.e = ep;
+  if (same1 && same2) {
+    if (fmax(n1a, n1b) < min_side || fmax(n2a, n2b) < min_side) return;
+    e.a = n1a > n1b ? l1.a : l1.b;
+    e.b = n2a > n2b ? l2.a : l2.b;
+    out.push_back(e);
+  } else if (same1 && !same2) {
+    if (fmax(n1a, n1b) < min_side) return;
+    e.a = n1a > n1b ? l1.a : l1.b;
+    if (n2a > min_side) { e.b = l2.a; out.push_back(e); }
+    if (n2b > min_side) { e.b = l2.b; out.push_back(e); }
+  } else if (!same1 && same2) {
+    if (fmax(n2a, n2b) < min_side) return;
+    e.a = n1a > n1b ? l2.a : l2.b;   // upstream compares side1A with side1B here and takes the point from line2
+    if (n1a > min_side) { e.b = l1.a; out.push_back(e); }
+    if (n1b > min_side) { e.b = l1.b; out.push_back(e); }
+  } else {
+    if (n1a > min_side) {
+      e.a = l1.a;
+      if (n2a > min_side) { e.b = l2.a; out.push_back(e); }
+      if (n2b > min_side) { e.b = l2.b; out.push_back(e); }
+    }
+    if (n1b > min_side) {
+      e.a = l1.b;
+      if (n2a > min_side) { e.b = l2.a; out.push_back(e); }
+      if (n2b > min_side) { e.b = l2.b; out.push_back(e); }
+    }
+  }
+}
+// edge_extraction (:459-471); fewer than two lines give no edges (upstream's unsigned `size() - 1` reads out of bounds there)
+inline void edge_extraction(const std::vector<Line>& lines, std::vector<Edge>& out) {
+  const int n = (int)lines.size();
+  for (int i = 0; i + 1 < n; i++)
+    for (int j = i + 1; j < n; j++) get_edges(lines[(size_t)i], lines[(size_t)j], out);
+}
+// nearest_neighbor's first entry: index of the nearest target (-1: none) and its record
+inline int nearest(const V3 sa, const V3 sb, const std::vector<Line>& trg, const std::vector<V3>& dir, const int tie_highest, Pair* out) {
+  int best = -1;
+  double key = 0.0;
+  const float sl = lenght(sa, sb);
+  for (int j = 0; j < (int)trg.size(); j++) {
+    const Pair p = line_to_line(sa, sb, sl, trg[(size_t)j].a, trg[(size_t)j].b, dir[(size_t)j]);
+    if (nn_better(nn_key(p.real), j, key, best, tie_highest)) {
+      best = j;
+      key = nn_key(p.real);
+      *out = p;
+    }
+  }
+  return best;
+}
+inline Fitness calc_fitness(const std::vector<Line>& src, const std::vector<Line>& trg, const std::vector<V3>& dir, const double max_range,
+                            const int tie_highest) {
+  Sums s = sums_zero();
+  for (const Line& l : src) {
+    Pair nn;
+    nn.real = nn.dist = nn.cov = 0.0;
+    const int j = nearest(l.a, l.b, trg, dir, tie_highest, &nn);
+    sums_add(s, j >= 0, nn, lenght(l.a, l.b), max_range);
+  }
+  return sums_finish(s);
+}
+
+}  // namespace la
+}  // namespace dgs

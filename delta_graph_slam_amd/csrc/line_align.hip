@@ -1,0 +1,536 @@
+// LineBasedScanmatcher::align_global (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp:109-203) on the device: every
+// (source edge, target edge) pair is a hypothesis h = es * Et + et; align_edges, the three gates, calc_fitness_score of the
+// transformed source lines against the merged target lines and the strict arg-max run there.  merge_lines, edge_extraction and the
+// refinement pass are sequential and small and run on the host from the same functions (line_align.h).
+//
+// MI355X design
+//   * One upload: source lines, the target table (A, B, (B - A).normalized() per merged line) and both edge lists.
+//   * la_hypothesis_kernel: one lane per h; transform, gate code, survivor flag.  Survivors are compacted in h order with the
+//     prefilter's stable compaction (pf_count_kernel, pf_scan_kernel) and la_scatter_kernel.
+//   * la_score_kernel: one wavefront per survivor (item 0 is the identity, the baseline).  The target table sits in LDS (72 bytes per
+//     line, 36 KiB at the limit of 512 lines); lanes stride over the target lines, the arg-min of (real_distance, index) per source
+//     line is a butterfly of cross-lane shuffles, the owner lane's record is broadcast and the five sums are added in source order by
+//     every lane alike, so their association is upstream's whatever the launch shape.  FP64 throughout: the loop is bound by the
+//     FP64 divide and square-root sequences of line_to_line_distance, not by memory.
+//   * la_argmax_kernel: one workgroup; a strictly greater score takes over, equal scores go to the lower h, NaN never wins.
+//   * The grid of la_score_kernel is fixed and its waves stride over the survivor count read on the device: one host wait per call.
+// Semantics and the Eigen details recalled from upstream: DESIGN.md §6f.
+#include <algorithm>
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "handle.h"
+#include "line_align.h"
+
+namespace dgs {
+
+// the prefilter's stable compaction (prefilter.hip)
+__global__ void pf_count_kernel(const unsigned char* __restrict__ flags, const int n, int* __restrict__ blk);
+__global__ void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restrict__ total);
+
+constexpr int kLaScanBlock = 1024;      // pf_scan_kernel's workgroup
+constexpr int kLaArgmaxBlock = 1024;
+constexpr int kLaScoreBlocks = 2048;    // la_score_kernel's fixed grid: 8192 waves, 8 per SIMD of 256 CUs
+constexpr int kLaTableDoubles = 9;      // A, B, direction per target line
+constexpr int kLaWavesPerBlock = kBlock / kWave;
+
+struct LaHyp {
+  la::Tf t;
+  double tn;   // translation.norm()
+};
+
+struct LaResult {
+  long long winner;        // h, -1: the baseline stays
+  int survivors, pad;
+  double fit[5];           // the winner's (or the baseline's) fitness and score
+  double base[5];          // the baseline's
+  LaHyp hyp;               // the winner's transform
+};
+
+struct LaArgs {
+  int Ls, Lt, Es, Et;
+  int constrain_angle, float_chain, tie_highest, pad;
+  double max_distance, cos_max_angle, max_range;
+  la::Weights w;
+};
+
+__device__ __forceinline__ la::V3 la_load3(const double* p) { return la::v3(p[0], p[1], p[2]); }
+
+// ================================================================================================ hypotheses
+__global__ __launch_bounds__(kBlock) void la_hypothesis_kernel(const double* __restrict__ es, const double* __restrict__ et, const LaArgs a,
+                                                               LaHyp* __restrict__ hyps, unsigned char* __restrict__ keep,
+                                                               unsigned char* __restrict__ gate, double* __restrict__ fit) {
+  const long long h = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const long long H = (long long)a.Es * a.Et;
+  if (h >= H) return;
+  const int is = (int)(h / a.Et), it = (int)(h % a.Et);   // is < Es, it < Et: both edge lists are read inside their bounds
+  la::Edge e1, e2;
+  e1.e = la_load3(es + 9 * is); e1.a = la_load3(es + 9 * is + 3); e1.b = la_load3(es + 9 * is + 6);
+  e2.e = la_load3(et + 9 * it); e2.a = la_load3(et + 9 * it + 3); e2.b = la_load3(et + 9 * it + 6);
+  LaHyp hy;
+  hy.t = la::align_edges(e1, e2, nullptr);
+  const int g = la::gate(hy.t, a.max_distance, a.constrain_angle, a.cos_max_angle, a.float_chain, &hy.tn);
+  hyps[h] = hy;
+  gate[h] = (unsigned char)g;
+  keep[h] = g == la::GATE_PASS ? 1 : 0;
+#pragma unroll
+  for (int k = 0; k < 5; k++) fit[5 * h + k] = 0.0;
+}
+
+// the survivors' h in order, and every h's position in that list
+__global__ __launch_bounds__(kBlock) void la_scatter_kernel(const unsigned char* __restrict__ keep, const int n, const int* __restrict__ blk,
+                                                            int* __restrict__ surv, int* __restrict__ slot) {
+  __shared__ int s_w[kLaWavesPerBlock];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const bool f = i < n && keep[i] != 0;
+  const unsigned long long m = __ballot(f);
+  if (lane == 0) s_w[wv] = __popcll(m);
+  __syncthreads();
+  if (i < n && !f) slot[i] = -1;
+  if (!f) return;
+  int off = blk[blockIdx.x];
+  for (int w = 0; w < wv; w++) off += s_w[w];
+  off += __popcll(m & ((1ull << lane) - 1ull));
+  surv[off] = i;   // off < number of survivors <= n: `surv` holds n entries
+  slot[i] = off;
+}
+
+// ================================================================================================ scores
+// One wavefront per item: item 0 is the untransformed source (the baseline), item s + 1 the s-th survivor.
+__global__ __launch_bounds__(kBlock) void la_score_kernel(const double* __restrict__ src, const double* __restrict__ tbl, const LaArgs a,
+                                                          const LaHyp* __restrict__ hyps, const int* __restrict__ surv, const int* __restrict__ cnt,
+                                                          double* __restrict__ fit, LaResult* __restrict__ res) {
+  __shared__ double s_t[DGS_LA_MAX_LINES_TARGET * kLaTableDoubles];
+  for (int k = threadIdx.x; k < a.Lt * kLaTableDoubles; k += kBlock) s_t[k] = tbl[k];   // Lt <= DGS_LA_MAX_LINES_TARGET (checked on the host)
+  __syncthreads();
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = blockIdx.x * kLaWavesPerBlock + threadIdx.x / kWave;
+  const int n_waves = gridDim.x * kLaWavesPerBlock;
+  const int items = cnt[0] + 1;
+  for (int item = wave; item < items; item += n_waves) {   // uniform per wave
+    const bool base = item == 0;
+    const int h = base ? -1 : surv[item - 1];
+    LaHyp hy;
+    hy.t = la::tf_identity();
+    hy.tn = 0.0;
+    if (!base) hy = hyps[h];
+    la::Sums sums = la::sums_zero();
+    for (int i = 0; i < a.Ls; i++) {
+      la::V3 sa = la_load3(src + 6 * i), sb = la_load3(src + 6 * i + 3);
+      if (!base) {
+        sa = la::apply(hy.t, sa);
+        sb = la::apply(hy.t, sb);
+      }
+      const float sl = la::lenght(sa, sb);
+      int bj = -1;
+      double bkey = 0.0;
+      la::Pair bp;
+      bp.real = bp.dist = bp.cov = 0.0;
+      for (int j = lane; j < a.Lt; j += kWave) {
+        const double* t = s_t + j * kLaTableDoubles;
+        const la::Pair p = la::line_to_line(sa, sb, sl, la_load3(t), la_load3(t + 3), la_load3(t + 6));
+        const double key = la::nn_key(p.real);
+        if (la::nn_better(key, j, bkey, bj, a.tie_highest)) {
+          bj = j;
+          bkey = key;
+          bp = p;
+        }
+      }
+      // arg-min of (key, index) over the wave: after the butterfly every lane holds the winner
+      int wj = bj;
+      double wkey = bkey;
+#pragma unroll
+      for (int o = kWave / 2; o > 0; o >>= 1) {
+        const int oj = __shfl_xor(wj, o, kWave);
+        const double okey = __shfl_xor(wkey, o, kWave);
+        if (la::nn_better(okey, oj, wkey, wj, a.tie_highest)) {
+          wj = oj;
+          wkey = okey;
+        }
+      }
+      la::Pair nn;
+      nn.real = nn.dist = nn.cov = 0.0;
+      if (wj >= 0) {   // the lane that owns target wj holds its record as its own best
+        const int owner = wj & (kWave - 1);
+        nn.real = __shfl(bp.real, owner, kWave);
+        nn.dist = __shfl(bp.dist, owner, kWave);
+        nn.cov = __shfl(bp.cov, owner, kWave);
+      }
+      la::sums_add(sums, wj >= 0, nn, sl, a.max_range);
+    }
+    const la::Fitness f = la::sums_finish(sums);
+    const double score = la::weight_global(a.w, f.real_avg_distance, f.coverage_percentage, hy.tn);
+    if (lane == 0) {
+      double* o = base ? res->base : fit + 5 * (long long)h;
+      o[0] = f.real_avg_distance; o[1] = f.avg_distance; o[2] = f.coverage; o[3] = f.coverage_percentage; o[4] = score;
+    }
+  }
+}
+
+// ================================================================================================ arg-max
+__device__ __forceinline__ bool la_takes_over(const double sb, const int hb, const double sa, const int ha) {
+  return sb > sa || (sb == sa && (unsigned)hb < (unsigned)ha);   // -1 is the baseline: the largest unsigned value
+}
+
+// result_score starts at the identity's; a hypothesis takes over iff its score is strictly greater, in h order: the winner is the
+// lowest h among the maxima above the baseline.  A NaN score compares false and never wins.
+__global__ __launch_bounds__(kLaArgmaxBlock) void la_argmax_kernel(const int* __restrict__ surv, const int* __restrict__ cnt, const double* __restrict__ fit,
+                                                                   const LaHyp* __restrict__ hyps, LaResult* __restrict__ res) {
+  __shared__ double s_s[kLaArgmaxBlock / kWave];
+  __shared__ int s_h[kLaArgmaxBlock / kWave];
+  const int S = cnt[0];
+  const double base = res->base[4];
+  double best = base;
+  int bh = -1;
+  for (int s = threadIdx.x; s < S; s += kLaArgmaxBlock) {   // s ascends per lane, and so does h: the first of equal scores stays
+    const int h = surv[s];
+    const double sc = fit[5 * (long long)h + 4];
+    if (sc > best) { best = sc; bh = h; }
+  }
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const double os = __shfl_xor(best, o, kWave);
+    const int oh = __shfl_xor(bh, o, kWave);
+    if (la_takes_over(os, oh, best, bh)) { best = os; bh = oh; }
+  }
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  if (lane == 0) { s_s[wv] = best; s_h[wv] = bh; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < kLaArgmaxBlock / kWave; w++)
+    if (la_takes_over(s_s[w], s_h[w], best, bh)) { best = s_s[w]; bh = s_h[w]; }
+  res->winner = bh;
+  res->survivors = S;
+  res->pad = 0;
+  LaHyp hy;
+  hy.t = la::tf_identity();
+  hy.tn = 0.0;
+  if (bh >= 0) hy = hyps[bh];
+  res->hyp = hy;
+  for (int k = 0; k < 5; k++) res->fit[k] = bh >= 0 ? fit[5 * (long long)bh + k] : res->base[k];
+}
+
+// ================================================================================================ host side
+namespace {
+
+inline la::Line la_line(const dgs_line_feature& f) {
+  la::Line l;
+  l.a = la::v3(f.point_a[0], f.point_a[1], f.point_a[2]);
+  l.b = la::v3(f.point_b[0], f.point_b[1], f.point_b[2]);
+  return l;
+}
+inline void la_put(const la::V3 v, double* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+inline bool la_finite(const dgs_line_feature* l, int64_t n) {
+  for (int64_t i = 0; i < n; i++)
+    for (int a = 0; a < 3; a++)
+      if (!std::isfinite(l[i].point_a[a]) || !std::isfinite(l[i].point_b[a])) return false;
+  return true;
+}
+void la_merge(const dgs_line_feature* lines, int64_t n, std::vector<la::Line>* out, std::vector<int>* origin) {
+  out->clear();
+  origin->clear();
+  for (int64_t i = 0; i < n; i++) {
+    out->push_back(la_line(lines[i]));
+    origin->push_back((int)i);
+  }
+  la::merge_lines(*out, *origin);
+}
+
+const char* la_bad_params(const dgs_line_align_params* p) {
+  if (!p) return "line align: params is NULL";
+  if (p->struct_size != sizeof(dgs_line_align_params)) return "line align: wrong struct_size";
+  if (!(p->g_max_score_distance > 0.0) || !(p->g_max_score_translation > 0.0)) return "line align: the max_score values must be positive";
+  // +infinity is a legal weight (that term alone decides); against a zero term it gives a NaN score, which never wins
+  for (const double w : {p->g_avg_distance_weight, p->g_coverage_weight, p->g_transform_weight})
+    if (!(w >= 0.0)) return "line align: a g_* weight is negative or NaN";
+  if (std::isnan(p->max_distance) || std::isnan(p->max_angle)) return "line align: max_distance / max_angle is NaN";
+  return nullptr;
+}
+
+struct LaOut {
+  la::Tf t;
+  la::Fitness fit;
+  double score;
+};
+
+// phase 1 on the device: -> the winner (or the baseline) with one host wait
+int la_search(dgs_handle* h, const LaArgs& a, const std::vector<la::Line>& src, const std::vector<la::Line>& trg, const std::vector<la::V3>& dir,
+              const std::vector<la::Edge>& es, const std::vector<la::Edge>& et, LaResult* out) {
+  LaScratch& s = h->la;
+  const int64_t H = (int64_t)a.Es * a.Et;
+  const size_t n_src = (size_t)a.Ls * 6, n_tbl = (size_t)a.Lt * kLaTableDoubles, n_es = (size_t)a.Es * 9, n_et = (size_t)a.Et * 9;
+  const size_t n_in = n_src + n_tbl + n_es + n_et;
+  const size_t hh = (size_t)std::max<int64_t>(H, 1);
+  const unsigned nb = (unsigned)((hh + kBlock - 1) / kBlock);
+  DGS_HIP_TRY(h, s.in.reserve(std::max<size_t>(n_in, 1)));
+  DGS_HIP_TRY(h, s.hyps.reserve(hh));
+  DGS_HIP_TRY(h, s.keep.reserve(hh));
+  DGS_HIP_TRY(h, s.gate.reserve(hh));
+  DGS_HIP_TRY(h, s.blk.reserve(nb));
+  DGS_HIP_TRY(h, s.cnt.reserve(4));
+  DGS_HIP_TRY(h, s.surv.reserve(hh));
+  DGS_HIP_TRY(h, s.slot.reserve(hh));
+  DGS_HIP_TRY(h, s.fit.reserve(hh * 5));
+  DGS_HIP_TRY(h, s.result.reserve(1));
+  if (ensure_pinned(h, 4096 + n_in * sizeof(double)) != DGS_OK) return DGS_ERR_HIP;
+  static_assert(sizeof(LaResult) <= 4096, "the read-back block must fit in front of the upload");
+  double* up = reinterpret_cast<double*>(static_cast<char*>(h->pinned) + 4096);
+  double* o = up;
+  for (const la::Line& l : src) { la_put(l.a, o); la_put(l.b, o + 3); o += 6; }
+  for (size_t j = 0; j < trg.size(); j++) { la_put(trg[j].a, o); la_put(trg[j].b, o + 3); la_put(dir[j], o + 6); o += kLaTableDoubles; }
+  for (const std::vector<la::Edge>* ev : {&es, &et})
+    for (const la::Edge& e : *ev) { la_put(e.e, o); la_put(e.a, o + 3); la_put(e.b, o + 6); o += 9; }
+  if (n_in) DGS_HIP_TRY(h, hipMemcpyAsync(s.in.ptr, up, n_in * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  const double* d_src = s.in.ptr;
+  const double* d_tbl = d_src + n_src;
+  const double* d_es = d_tbl + n_tbl;
+  const double* d_et = d_es + n_es;
+  if (H > 0) {
+    hipLaunchKernelGGL(la_hypothesis_kernel, dim3(nb), dim3(kBlock), 0, h->stream, d_es, d_et, a, s.hyps.ptr, s.keep.ptr, s.gate.ptr, s.fit.ptr);
+    hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, s.keep.ptr, (int)H, s.blk.ptr);
+    hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kLaScanBlock), 0, h->stream, s.blk.ptr, (int)nb, s.cnt.ptr);
+    hipLaunchKernelGGL(la_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, s.keep.ptr, (int)H, s.blk.ptr, s.surv.ptr, s.slot.ptr);
+    s.counts4[0] += 4;
+  } else {
+    DGS_HIP_TRY(h, hipMemsetAsync(s.cnt.ptr, 0, sizeof(int), h->stream));
+  }
+  const unsigned blocks = (unsigned)std::min<int64_t>(kLaScoreBlocks, (H + 1 + kLaWavesPerBlock - 1) / kLaWavesPerBlock);
+  hipLaunchKernelGGL(la_score_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, d_src, d_tbl, a, s.hyps.ptr, s.surv.ptr, s.cnt.ptr, s.fit.ptr, s.result.ptr);
+  hipLaunchKernelGGL(la_argmax_kernel, dim3(1), dim3(kLaArgmaxBlock), 0, h->stream, s.surv.ptr, s.cnt.ptr, s.fit.ptr, s.hyps.ptr, s.result.ptr);
+  s.counts4[0] += 2;
+  DGS_HIP_TRY(h, hipGetLastError());
+  DGS_HIP_TRY(h, hipMemcpyAsync(h->pinned, s.result.ptr, sizeof(LaResult), hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  s.counts4[1] += 1;
+  std::memcpy(out, h->pinned, sizeof(LaResult));
+  s.n_hyp = H;
+  s.counts4[2] = H;
+  s.counts4[3] = out->survivors;
+  return DGS_OK;
+}
+
+// the refinement pass (:160-200): the range-for walks the vector the body reassigns, so later iterations see the new lines while
+// best_trans stays the first phase's transform [UPSTREAM-RECALL: vector assignment of equal size keeps the storage]
+int la_refine(const dgs_line_align_params& p, const LaArgs& a, const std::vector<la::Line>& trg, const std::vector<la::V3>& dir,
+              std::vector<la::Line>* aligned, LaOut* r) {
+  const la::Tf best_trans = r->t;
+  const double cos_max = a.cos_max_angle;
+  int steps = 0;
+  for (size_t i = 0; i < aligned->size(); i++) {
+    const la::Line ls = (*aligned)[i];
+    la::Pair nn;
+    const int j = la::nearest(ls.a, ls.b, trg, dir, a.tie_highest, &nn);
+    if (j < 0) continue;
+    const la::V3 sd = la::normalized(la::sub(ls.a, ls.b)), td = la::normalized(la::sub(trg[(size_t)j].a, trg[(size_t)j].b));
+    const double cosine = la::dot(sd, td);
+    if (std::fabs(cosine) < cos_max) continue;
+    const la::Tf tf = la::align_lines(ls, trg[(size_t)j]);
+    const double tn = la::norm(la::v3(tf.tx, tf.ty, tf.tz));
+    if (tn > p.max_distance) continue;
+    std::vector<la::Line> cand(aligned->size());
+    for (size_t k = 0; k < cand.size(); k++) {
+      cand[k].a = la::apply(tf, (*aligned)[k].a);
+      cand[k].b = la::apply(tf, (*aligned)[k].b);
+    }
+    const la::Fitness f = la::calc_fitness(cand, trg, dir, a.max_range, a.tie_highest);
+    const double score = la::weight_global(a.w, f.real_avg_distance, f.coverage_percentage, tn);
+    if (score > r->score) {
+      *aligned = cand;
+      r->t = la::compose(best_trans, tf);
+      r->fit = f;
+      r->score = score;
+      steps++;
+    }
+  }
+  return steps;
+}
+
+}  // namespace
+
+void line_align_release(dgs_handle* h) {
+  LaScratch& s = h->la;
+  s.in.release(); s.hyps.release(); s.keep.release(); s.gate.release(); s.blk.release(); s.cnt.release(); s.surv.release(); s.slot.release();
+  s.fit.release(); s.result.release();
+  s.n_hyp = 0;
+}
+
+}  // namespace dgs
+
+using namespace dgs;
+
+extern "C" {
+
+int dgs_line_align_params_init(dgs_line_align_params* p) {
+  if (!p) return DGS_ERR_INVALID_ARGUMENT;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(*p);
+  p->angle_gate_float_chain = 1;
+  p->g_avg_distance_weight = 0.6;
+  p->g_coverage_weight = 1.0;
+  p->g_transform_weight = 0.2;
+  p->g_max_score_distance = 5.0;
+  p->g_max_score_translation = 5.0;
+  p->max_distance = 2.0;
+  p->max_angle = M_PI / 9.0;
+  p->nn_tie_highest_index = 0;
+  return DGS_OK;
+}
+
+int dgs_line_merge(const dgs_line_feature* lines, int64_t n, dgs_line_feature* out, int64_t* n_out) {
+  if (n < 0 || !n_out || (n > 0 && (!lines || !out))) return DGS_ERR_INVALID_ARGUMENT;
+  std::vector<la::Line> m;
+  std::vector<int> origin;
+  la_merge(lines, n, &m, &origin);
+  for (size_t i = 0; i < m.size(); i++) {
+    dgs_line_feature f{};
+    if (origin[i] >= 0) f = lines[origin[i]];
+    la_put(m[i].a, f.point_a);
+    la_put(m[i].b, f.point_b);
+    out[i] = f;
+  }
+  *n_out = (int64_t)m.size();
+  return DGS_OK;
+}
+
+int dgs_line_edges(const dgs_line_feature* lines, int64_t n, dgs_edge_feature* edges, int64_t capacity, int64_t* n_edges) {
+  if (n < 0 || !n_edges || (n > 0 && !lines) || capacity < 0 || (capacity > 0 && !edges)) return DGS_ERR_INVALID_ARGUMENT;
+  std::vector<la::Line> l;
+  for (int64_t i = 0; i < n; i++) l.push_back(la_line(lines[i]));
+  std::vector<la::Edge> e;
+  la::edge_extraction(l, e);
+  *n_edges = (int64_t)e.size();
+  if (*n_edges > capacity) return DGS_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0; i < e.size(); i++) {
+    la_put(e[i].e, edges[i].edge_point);
+    la_put(e[i].a, edges[i].point_a);
+    la_put(e[i].b, edges[i].point_b);
+  }
+  return DGS_OK;
+}
+
+int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, const dgs_line_feature* src_lines, int64_t n_src,
+                          const dgs_line_feature* trg_lines, int64_t n_trg, int32_t constrain_angle, double max_range,
+                          dgs_line_feature* aligned_lines, dgs_line_alignment* alignment) {
+  if (const char* why = la_bad_params(params)) {   // before anything touches a device
+    if (h) h->err = why;
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  if (!h || !alignment || n_src < 0 || n_trg < 0 || (n_src > 0 && !src_lines) || (n_trg > 0 && !trg_lines)) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  std::memset(alignment, 0, sizeof(*alignment));
+  const char* why = nullptr;
+  if (n_src > DGS_LA_MAX_LINES_SOURCE) why = "line align: more than DGS_LA_MAX_LINES_SOURCE source lines";
+  else if (n_trg > (1 << 20)) why = "line align: more than 2^20 target lines";
+  else if (std::isnan(max_range)) why = "line align: max_range is NaN";
+  else if (!la_finite(src_lines, n_src) || !la_finite(trg_lines, n_trg)) why = "line align: a line coordinate is not finite";
+  if (why) {
+    h->err = why;
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  std::vector<la::Line> src, trg;
+  std::vector<int> origin;
+  for (int64_t i = 0; i < n_src; i++) src.push_back(la_line(src_lines[i]));
+  la_merge(trg_lines, n_trg, &trg, &origin);
+  if ((int64_t)trg.size() > DGS_LA_MAX_LINES_TARGET) {
+    h->err = "line align: more than DGS_LA_MAX_LINES_TARGET target lines after merging";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  std::vector<la::V3> dir;
+  for (const la::Line& l : trg) dir.push_back(la::normalized(la::sub(l.b, l.a)));
+  std::vector<la::Edge> es, et;
+  la::edge_extraction(src, es);
+  la::edge_extraction(trg, et);
+  const int64_t H = (int64_t)es.size() * (int64_t)et.size();
+  if (H > DGS_LA_MAX_HYPOTHESES) {
+    h->err = "line align: more than DGS_LA_MAX_HYPOTHESES edge-pair hypotheses";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  LaArgs a{};
+  a.Ls = (int)src.size(); a.Lt = (int)trg.size(); a.Es = (int)es.size(); a.Et = (int)et.size();
+  a.constrain_angle = constrain_angle ? 1 : 0;
+  a.float_chain = params->angle_gate_float_chain ? 1 : 0;
+  a.tie_highest = params->nn_tie_highest_index ? 1 : 0;
+  a.max_distance = params->max_distance;
+  a.cos_max_angle = std::cos(params->max_angle);
+  a.max_range = max_range;
+  a.w.avg_distance_weight = params->g_avg_distance_weight;
+  a.w.coverage_weight = params->g_coverage_weight;
+  a.w.transform_weight = params->g_transform_weight;
+  a.w.max_score_distance = params->g_max_score_distance;
+  a.w.max_score_translation = params->g_max_score_translation;
+  for (int k = 0; k < 4; k++) h->la.counts4[k] = 0;
+  DGS_HIP_TRY(h, hipSetDevice(h->device));
+  LaResult res{};
+  const int rc = la_search(h, a, src, trg, dir, es, et, &res);
+  if (rc != DGS_OK) {
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  LaOut r;
+  r.t = res.hyp.t;
+  r.fit.real_avg_distance = res.fit[0]; r.fit.avg_distance = res.fit[1]; r.fit.coverage = res.fit[2]; r.fit.coverage_percentage = res.fit[3];
+  r.score = res.fit[4];
+  std::vector<la::Line> aligned = src;
+  if (res.winner >= 0)
+    for (la::Line& l : aligned) { l.a = la::apply(r.t, l.a); l.b = la::apply(r.t, l.b); }
+  const int steps = la_refine(*params, a, trg, dir, &aligned, &r);
+  const double T[16] = {r.t.r00, r.t.r01, 0.0, r.t.tx, r.t.r10, r.t.r11, 0.0, r.t.ty, 0.0, 0.0, 1.0, r.t.tz, 0.0, 0.0, 0.0, 1.0};
+  std::memcpy(alignment->transformation, T, sizeof(T));
+  alignment->fitness_score[0] = r.fit.real_avg_distance; alignment->fitness_score[1] = r.fit.avg_distance;
+  alignment->fitness_score[2] = r.fit.coverage; alignment->fitness_score[3] = r.fit.coverage_percentage;
+  alignment->score = r.score;
+  alignment->winner = res.winner;
+  alignment->n_hypotheses = H;
+  alignment->n_survivors = res.survivors;
+  alignment->n_edges_source = a.Es;
+  alignment->n_edges_target = a.Et;
+  alignment->n_lines_target = a.Lt;
+  alignment->refine_steps = steps;
+  alignment->status = res.winner >= 0 ? DGS_LA_ALIGNED : H == 0 ? DGS_LA_NO_HYPOTHESES : res.survivors == 0 ? DGS_LA_ALL_GATED : DGS_LA_NONE_BETTER;
+  if (aligned_lines)
+    for (size_t i = 0; i < aligned.size(); i++) {
+      aligned_lines[i] = src_lines[i];   // transform_lines copies the line and replaces its two points
+      la_put(aligned[i].a, aligned_lines[i].point_a);
+      la_put(aligned[i].b, aligned_lines[i].point_b);
+    }
+  return DGS_OK;
+}
+
+int dgs_line_align_get_hypotheses(dgs_handle* h, int64_t first, int64_t count, dgs_line_align_hypothesis* records, int64_t* counts4) {
+  if (!h || first < 0 || count < 0) return DGS_ERR_INVALID_ARGUMENT;
+  LaScratch& s = h->la;
+  if (counts4)
+    for (int k = 0; k < 4; k++) counts4[k] = s.counts4[k];
+  if (!records || count == 0) return DGS_OK;
+  if (first + count > s.n_hyp) {
+    h->err = "line align: the range lies beyond the last call's hypotheses";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  const size_t n = (size_t)count;
+  std::vector<LaHyp> hy(n);
+  std::vector<unsigned char> g(n);
+  std::vector<int> sl(n);
+  std::vector<double> f(n * 5);
+  DGS_HIP_TRY(h, hipSetDevice(h->device));
+  DGS_HIP_TRY(h, hipMemcpyAsync(hy.data(), s.hyps.ptr + first, n * sizeof(LaHyp), hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipMemcpyAsync(g.data(), s.gate.ptr + first, n, hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipMemcpyAsync(sl.data(), s.slot.ptr + first, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipMemcpyAsync(f.data(), s.fit.ptr + first * 5, n * 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < n; i++) {
+    dgs_line_align_hypothesis& r = records[i];
+    r.gate = g[i];
+    r.slot = sl[i];
+    r.rotation[0] = hy[i].t.r00; r.rotation[1] = hy[i].t.r01; r.rotation[2] = hy[i].t.r10; r.rotation[3] = hy[i].t.r11;
+    r.translation[0] = hy[i].t.tx; r.translation[1] = hy[i].t.ty; r.translation[2] = hy[i].t.tz;
+    for (int k = 0; k < 4; k++) r.fitness_score[k] = f[5 * i + k];
+    r.score = f[5 * i + 4];
+  }
+  return DGS_OK;
+}
+
+}  // extern "C"

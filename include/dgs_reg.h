@@ -620,6 +620,93 @@ typedef struct dgs_line_extraction_round {
 int dgs_line_extraction_get_rounds(dgs_handle* h, dgs_line_extraction_round* rounds, int64_t capacity, int64_t* n_rounds, int32_t list_round,
                                    int32_t* inlier_idx, int32_t* cluster_idx, int64_t* counts4);
 
+/* ---- LineBasedScanmatcher::align_global on the device (src/hdl_graph_slam/line_based_scanmatcher.cpp:109-203) ------------------
+ * The target lines are merged, the edges of both sides are extracted (host, order-dependent), every (source edge, target edge)
+ * hypothesis h = es * Et + et is aligned, gated and scored on the device, the strict arg-max over h is taken there, and the
+ * refinement pass over the aligned lines runs on the host.  Semantics, the Eigen details recalled from upstream and the limits:
+ * DESIGN.md 6f.  The aligner works in buffers of its own: registration, prefilter, map and line-extraction state are untouched.
+ * Additions only: DGS_ABI_VERSION is unchanged. */
+enum dgs_line_align_status {
+  DGS_LA_ALIGNED = 0,       /* an edge-pair hypothesis beat the identity's score */
+  DGS_LA_NO_HYPOTHESES = 1, /* one side has no edges */
+  DGS_LA_ALL_GATED = 2,     /* every hypothesis failed a gate */
+  DGS_LA_NONE_BETTER = 3    /* no surviving hypothesis scored strictly above the identity */
+};
+enum dgs_line_align_gate {
+  DGS_LA_GATE_PASS = 0,
+  DGS_LA_GATE_DISTANCE = 1, /* translation.norm() > max_distance */
+  DGS_LA_GATE_IDENTITY = 2, /* transform == Identity */
+  DGS_LA_GATE_ANGLE = 3     /* constrain_angle and cos(angle) < cos(max_angle) */
+};
+#define DGS_LA_MAX_LINES_SOURCE 256       /* what limits Ls, Lt and the hypothesis count */
+#define DGS_LA_MAX_LINES_TARGET 512       /* after merging */
+#define DGS_LA_MAX_HYPOTHESES (1 << 21)
+/* Defaults (dgs_line_align_params_init) = LineBasedScanmatcher's constructor (line_based_scanmatcher.hpp:91-95): 0.6, 1.0, 0.2, 5.0,
+ * 5.0; align_global's constants 2.0 and pi / 9 (:115-116); the float angle chain; ties to the lowest target index. */
+typedef struct dgs_line_align_params {
+  uint32_t struct_size;            /* sizeof(dgs_line_align_params), set by dgs_line_align_params_init */
+  int32_t angle_gate_float_chain;  /* 1: the angle gate's angle through transform3Dto2D on the float cast, as upstream (recalled Eigen
+                                      3.3); 0: atan2(r10, r00) in double */
+  double g_avg_distance_weight;    /* the three weights: >= 0; +infinity is accepted and makes a hypothesis whose term is 0 score NaN, */
+  double g_coverage_weight;        /* which never wins; a negative or NaN weight is DGS_ERR_INVALID_ARGUMENT */
+  double g_transform_weight;
+  double g_max_score_distance;     /* > 0 */
+  double g_max_score_translation;
+  double max_distance;
+  double max_angle;
+  int32_t nn_tie_highest_index;    /* 0: equal real_distances go to the lowest target index (recalled: std::sort's insertion sort
+                                      below 16 elements keeps the order); 1: to the highest */
+  int32_t reserved;
+} dgs_line_align_params;
+int dgs_line_align_params_init(dgs_line_align_params* params);
+/* upstream's BestFitAlignment without the two line vectors, and what the search saw */
+typedef struct dgs_line_alignment {
+  double transformation[16];   /* row-major 4 x 4 */
+  double fitness_score[4];     /* FitnessScore: real_avg_distance, avg_distance, coverage, coverage_percentage */
+  double score;                /* weight_global of the result */
+  int64_t winner;              /* the winning h = es * Et + et; -1 when none beat the identity */
+  int64_t n_hypotheses;        /* Es * Et */
+  int64_t n_survivors;         /* hypotheses that passed the gates */
+  int32_t n_edges_source;
+  int32_t n_edges_target;
+  int32_t n_lines_target;      /* after merge_lines */
+  int32_t refine_steps;        /* iterations of the refinement pass (:160-200) that took over */
+  int32_t status;              /* dgs_line_align_status */
+  int32_t reserved;
+} dgs_line_alignment;
+/* align_global (:109-203) from the extracted source lines on (line_extraction stays with dgs_line_extraction).  aligned_lines:
+ * room for n_src features (nullable); not_aligned_lines are src_lines themselves.  More than DGS_LA_MAX_LINES_SOURCE source lines,
+ * DGS_LA_MAX_LINES_TARGET merged target lines or DGS_LA_MAX_HYPOTHESES hypotheses, or a coordinate that is not finite, is
+ * DGS_ERR_INVALID_ARGUMENT with a message: nothing is truncated. */
+int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, const dgs_line_feature* src_lines, int64_t n_src,
+                          const dgs_line_feature* trg_lines, int64_t n_trg, int32_t constrain_angle, double max_range,
+                          dgs_line_feature* aligned_lines, dgs_line_alignment* alignment);
+/* merge_lines (:1086-1103) with are_lines_aligned (:1012-1084) on the host, no handle and no device.  out: room for n features; a
+ * merged line has zero statistics (upstream leaves them unset). */
+int dgs_line_merge(const dgs_line_feature* lines, int64_t n, dgs_line_feature* out, int64_t* n_out);
+/* upstream's EdgeFeature */
+typedef struct dgs_edge_feature {
+  double edge_point[3];
+  double point_a[3];
+  double point_b[3];
+} dgs_edge_feature;
+/* edge_extraction (:459-471) with get_edges (:501-682) and lines_intersection (:473-499) on the host, no handle and no device;
+ * only_angular_edges = false.  Fewer than two lines give no edges.  *n_edges is always the full count, DGS_ERR_INVALID_ARGUMENT
+ * when it exceeds `capacity` (capacity 0 with a NULL array asks for the count alone). */
+int dgs_line_edges(const dgs_line_feature* lines, int64_t n, dgs_edge_feature* edges, int64_t capacity, int64_t* n_edges);
+/* Test hook: what the device computed per hypothesis in the last dgs_line_align_global call. */
+typedef struct dgs_line_align_hypothesis {
+  int32_t gate;           /* dgs_line_align_gate */
+  int32_t slot;           /* position among the survivors, in h order; -1 when gated */
+  double rotation[4];     /* r00 r01 r10 r11 of align_edges' transform (:693-740) */
+  double translation[3];
+  double fitness_score[4];/* calc_fitness_score (:905-955) of the transformed source lines; zeros when gated */
+  double score;           /* weight_global; 0 when gated */
+} dgs_line_align_hypothesis;
+/* records: room for `count` records of h = first .. first + count - 1 (nullable).  counts4 (nullable): kernel launches, host waits,
+ * hypotheses and survivors of the last call's device phase. */
+int dgs_line_align_get_hypotheses(dgs_handle* h, int64_t first, int64_t count, dgs_line_align_hypothesis* records, int64_t* counts4);
+
 #ifdef __cplusplus
 }
 #endif
