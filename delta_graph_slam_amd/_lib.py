@@ -93,13 +93,31 @@ class LineAlignParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("angle_gate_float_chain", C.c_int32), ("g_avg_distance_weight", C.c_double),
                 ("g_coverage_weight", C.c_double), ("g_transform_weight", C.c_double), ("g_max_score_distance", C.c_double),
                 ("g_max_score_translation", C.c_double), ("max_distance", C.c_double), ("max_angle", C.c_double),
-                ("nn_tie_highest_index", C.c_int32), ("reserved", C.c_int32)]
+                ("nn_tie_highest_index", C.c_int32), ("reserved", C.c_int32),
+                # appended for align_local
+                ("l_avg_distance_weight", C.c_double), ("l_coverage_weight", C.c_double), ("l_transform_weight", C.c_double),
+                ("l_max_score_distance", C.c_double), ("l_max_score_translation", C.c_double), ("l_max_distance", C.c_double),
+                ("l_max_angle", C.c_double), ("refine_three_nearest", C.c_int32), ("reserved2", C.c_int32)]
 
 
 class LineAlignment(C.Structure):
     _fields_ = [("transformation", C.c_double * 16), ("fitness_score", C.c_double * 4), ("score", C.c_double), ("winner", C.c_int64),
                 ("n_hypotheses", C.c_int64), ("n_survivors", C.c_int64), ("n_edges_source", C.c_int32), ("n_edges_target", C.c_int32),
                 ("n_lines_target", C.c_int32), ("refine_steps", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LineLocalAlignment(C.Structure):
+    _fields_ = [("transformation", C.c_double * 16), ("fitness_score", C.c_double * 4), ("score", C.c_double),
+                ("edge_transformation", C.c_double * 16), ("edge_fitness_score", C.c_double * 4), ("edge_score", C.c_double),
+                ("baseline_fitness_score", C.c_double * 4), ("baseline_score", C.c_double), ("winner_edge", C.c_int64),
+                ("winner_line", C.c_int64), ("n_hypotheses_edge", C.c_int64), ("n_survivors_edge", C.c_int64),
+                ("n_hypotheses_line", C.c_int64), ("n_survivors_line", C.c_int64), ("n_edges_source", C.c_int32),
+                ("n_edges_target", C.c_int32), ("is_edge_aligned", C.c_int32), ("status", C.c_int32)]
+
+
+class LineAlignLocalHypothesis(C.Structure):
+    _fields_ = [("gate", C.c_int32), ("target", C.c_int32), ("rotation", C.c_double * 4), ("translation", C.c_double * 3),
+                ("fitness_score", C.c_double * 4), ("score", C.c_double)]
 
 
 class EdgeFeatureC(C.Structure):
@@ -111,8 +129,8 @@ class LineAlignHypothesis(C.Structure):
                 ("fitness_score", C.c_double * 4), ("score", C.c_double)]
 
 
-LA_STATUS = {0: "ALIGNED", 1: "NO_HYPOTHESES", 2: "ALL_GATED", 3: "NONE_BETTER"}
-LA_GATE = {0: "PASS", 1: "DISTANCE", 2: "IDENTITY", 3: "ANGLE"}
+LA_STATUS = {0: "ALIGNED", 1: "NO_HYPOTHESES", 2: "ALL_GATED", 3: "NONE_BETTER", 4: "LINE_ALIGNED"}
+LA_GATE = {0: "PASS", 1: "DISTANCE", 2: "IDENTITY", 3: "ANGLE", 4: "LINE_DIRECTION", 5: "LINE_DISTANCE", 6: "RANK"}
 LE_STATUS = {0: "DONE", 1: "RANSAC_FAILED", 2: "STALL", 3: "MAX_ROUNDS", 4: "RNG_EXHAUSTED"}
 SAC_METHODS = ["SAC_RANSAC", "SAC_LMEDS", "SAC_MSAC", "SAC_RRANSAC", "SAC_RMSAC", "SAC_MLESAC", "SAC_PROSAC"]
 MAP_DEDUP = {"AUTO": 0, "HASH": 1, "SORT": 2}
@@ -147,6 +165,7 @@ SYMBOLS = [
     "dgs_map_cloud_params_init", "dgs_map_cloud_generate", "dgs_map_cloud_generate_clouds", "dgs_map_cloud_get", "dgs_map_cloud_get_grid",
     "dgs_line_extraction_params_init", "dgs_line_extraction", "dgs_line_extraction_get_rounds",
     "dgs_line_align_params_init", "dgs_line_align_global", "dgs_line_merge", "dgs_line_edges", "dgs_line_align_get_hypotheses",
+    "dgs_line_align_local_batch", "dgs_line_align_local", "dgs_line_edges_angular", "dgs_line_align_local_get_hypotheses",
 ]
 
 _libs = {}
@@ -275,5 +294,11 @@ def load(path=None):
     lib.dgs_line_merge.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, P(C.c_int64)]
     lib.dgs_line_edges.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, P(C.c_int64)]
     lib.dgs_line_align_get_hypotheses.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.dgs_line_align_local_batch.argtypes = [C.c_void_p, P(LineAlignParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_double, C.c_void_p, C.c_void_p]
+    lib.dgs_line_align_local.argtypes = [C.c_void_p, P(LineAlignParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
+                                         P(LineLocalAlignment)]
+    lib.dgs_line_edges_angular.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_line_align_local_get_hypotheses.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib

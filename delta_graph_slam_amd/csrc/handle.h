@@ -185,6 +185,18 @@ struct LaScratch {
   int64_t n_hyp = 0;                   // of the last call: what the test hook may read
   int64_t counts4[4] = {0, 0, 0, 0};   // launches, host waits, hypotheses, survivors
 };
+// LineBasedScanmatcher::align_local, batched (line_align_local.hip): scratch of its own, nothing shared with align_global's.
+struct LalHyp;    // line_align_local.hip
+struct LalScratch {
+  DevBuf<unsigned char> in;            // one upload: item table, workgroup tables, source lines, target tables, both edge lists
+  DevBuf<LalHyp> hyps;                 // per hypothesis of both phases, at the item's offsets
+  DevBuf<double> fit;                  // 5 doubles per hypothesis
+  DevBuf<double> keys;                 // line pairs: nn_key(real_distance) per (snapshot line, target line)
+  DevBuf<double> base;                 // the first phase's aligned lines per item (the snapshot), laid out like the source lines
+  DevBuf<unsigned char> out;           // one download: a record per item, then the aligned lines
+  std::vector<int64_t> off1, off2;     // of the last call: first hypothesis per item and phase (n_items + 1 entries; phase 1 after all of phase 0)
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
 
 }  // namespace dgs
 
@@ -391,6 +403,7 @@ struct dgs_handle {
   // ---- line extraction (line_extraction.hip): own buffers; registration, prefilter and map cloud state are left untouched
   dgs::LnScratch ln;
   dgs::LaScratch la;
+  dgs::LalScratch lal;
 
   dgs::Profiler prof;
 };
@@ -475,6 +488,8 @@ void map_cloud_release(dgs_handle* h);
 // line_extraction.hip
 void line_extraction_release(dgs_handle* h);
 void line_align_release(dgs_handle* h);
+// line_align_local.hip
+void line_align_local_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -215,6 +215,23 @@ LA_HD double weight_global(const Weights w, const double avg_distance, const dou
          w.transform_weight * (min_std(w.max_score_translation, translation_distance) / w.max_score_translation) * 100.;
 }
 
+// calc_fitness_score's is_local = true comparison (:925): nn.distance < max_range.  A neighbour without coverage has distance DBL_MAX
+// and is left out of the four sums however small its real_distance; total_lenght always grows.
+LA_HD void sums_add_local(Sums& s, const bool has_nn, const Pair nn, const float slen, const double max_range) {
+  if (has_nn && nn.dist < max_range) {
+    s.real_distance += nn.real * (double)slen;
+    s.real_distance_lenght += (double)slen;
+    s.distance += nn.dist * nn.cov;
+    s.coverage_lenght += nn.cov;
+  }
+  s.total_lenght += (double)slen;
+}
+// weight_local (line_based_scanmatcher.hpp:161-166): weight_global's expression over the l_* members
+LA_HD double weight_local(const Weights w, const double avg_distance, const double coverage_percentage, const double translation_distance) {
+  return -w.avg_distance_weight * (min_std(w.max_score_distance, avg_distance) / w.max_score_distance) * 100. + w.coverage_weight * coverage_percentage -
+         w.transform_weight * (min_std(w.max_score_translation, translation_distance) / w.max_score_translation) * 100.;
+}
+
 // angle_between_vectors (:684-691)
 LA_HD double angle_between(const V3 a, const V3 b) {
   const double dt = a.x * b.x + a.y * b.y;
@@ -313,6 +330,39 @@ LA_HD int gate(const Tf t, const double max_distance, const int constrain_angle,
   return GATE_PASS;
 }
 
+// ---- align_local (:205-297) ----------------------------------------------------------------------------------------------------------
+// GATE_LINE_*: the two gates of the line-pair phase (:270-280); GATE_RANK: a neighbour rank the walk does not visit (refine_three_nearest)
+enum { GATE_LINE_DIRECTION = 4, GATE_LINE_DISTANCE = 5, GATE_RANK = 6 };
+// the edge-pair phase's gates (:227-235) in upstream's order: the distance, then always the angle; there is no identity gate
+LA_HD int gate_local(const Tf t, const double max_distance, const double cos_max_angle, const int float_chain, double* tn) {
+  *tn = norm(v3(t.tx, t.ty, t.tz));
+  if (*tn > max_distance) return GATE_DISTANCE;
+  if (cos(gate_angle(t, float_chain)) < cos_max_angle) return GATE_ANGLE;
+  return GATE_PASS;
+}
+// one line-pair hypothesis (:267-280): the direction gate, align_lines, the distance gate.  A gated hypothesis keeps the identity.
+LA_HD int line_hypothesis(const Line ls, const Line lt, const double max_distance, const double cos_max_angle, Tf* t, double* tn) {
+  *t = tf_identity();
+  *tn = 0.0;
+  const double cosine = dot(normalized(sub(ls.a, ls.b)), normalized(sub(lt.a, lt.b)));
+  if (fabs(cosine) < cos_max_angle) return GATE_LINE_DIRECTION;
+  *t = align_lines(ls, lt);
+  *tn = norm(v3(t->tx, t->ty, t->tz));
+  if (*tn > max_distance) return GATE_LINE_DISTANCE;
+  return GATE_PASS;
+}
+// the neighbour order of the line-pair phase: all target lines by (nn_key(real_distance), target index), the index order flipped under
+// tie_highest.  std::sort's order among equal keys above 16 elements is unspecified upstream; this is the project's definition.
+LA_HD bool rank_before(const double key_a, const int ja, const double key_b, const int jb, const int tie_highest) {
+  if (key_a < key_b) return true;
+  if (key_a > key_b) return false;
+  return tie_highest ? ja > jb : ja < jb;
+}
+// arg-max order: a strictly greater score takes over, equal scores go to the lower index, -1 (nothing took over) is the largest; NaN never wins
+LA_HD bool takes_over(const double sb, const int hb, const double sa, const int ha) {
+  return sb > sa || (sb == sa && (unsigned)hb < (unsigned)ha);
+}
+
 // ---- host only -----------------------------------------------------------------------------------------------------------------
 // are_lines_aligned (:1012-1084): 0 = no merge, 1 = line1 stays (identical lines), 2 = *merged
 inline int are_lines_aligned(const Line l1, const Line l2, Line* merged) {
@@ -359,8 +409,10 @@ inline void merge_lines(std::vector<Line>& lines, std::vector<int>& origin) {
     }
   }
 }
-// get_edges (:501-682) with only_angular_edges = false
-inline void get_edges(const Line l1, const Line l2, std::vector<Edge>& out) {
+// get_edges (:501-682).  only_angular_edges drops an edge whose lines end further than max_dist_angular_edge from the corner (cases 1, 2
+// and 3; case 4 has no such check upstream).  The defaults are align_global's call.
+inline void get_edges(const Line l1, const Line l2, std::vector<Edge>& out, const bool only_angular_edges = false,
+                      const double max_dist_angular_edge = 7.0) {
   const double cosine = dot(normalized(sub(l1.a, l1.b)), normalized(sub(l2.a, l2.b)));
   if (fabs(cosine) > 0.5) return;
   const double min_side = 1.0;
@@ -373,16 +425,19 @@ inline void get_edges(const Line l1, const Line l2, std::vector<Edge>& out) {
   e.e = ep;
   if (same1 && same2) {
     if (fmax(n1a, n1b) < min_side || fmax(n2a, n2b) < min_side) return;
+    if (only_angular_edges && (fmin(n1a, n1b) > max_dist_angular_edge || fmin(n2a, n2b) > max_dist_angular_edge)) return;
     e.a = n1a > n1b ? l1.a : l1.b;
     e.b = n2a > n2b ? l2.a : l2.b;
     out.push_back(e);
   } else if (same1 && !same2) {
     if (fmax(n1a, n1b) < min_side) return;
+    if (only_angular_edges && fmin(n1a, n1b) > max_dist_angular_edge) return;
     e.a = n1a > n1b ? l1.a : l1.b;
     if (n2a > min_side) { e.b = l2.a; out.push_back(e); }
     if (n2b > min_side) { e.b = l2.b; out.push_back(e); }
   } else if (!same1 && same2) {
     if (fmax(n2a, n2b) < min_side) return;
+    if (only_angular_edges && fmin(n2a, n2b) > max_dist_angular_edge) return;
     e.a = n1a > n1b ? l2.a : l2.b;   // upstream compares side1A with side1B here and takes the point from line2
     if (n1a > min_side) { e.b = l1.a; out.push_back(e); }
     if (n1b > min_side) { e.b = l1.b; out.push_back(e); }
@@ -400,10 +455,11 @@ inline void get_edges(const Line l1, const Line l2, std::vector<Edge>& out) {
   }
 }
 // edge_extraction (:459-471); fewer than two lines give no edges (upstream's unsigned `size() - 1` reads out of bounds there)
-inline void edge_extraction(const std::vector<Line>& lines, std::vector<Edge>& out) {
+inline void edge_extraction(const std::vector<Line>& lines, std::vector<Edge>& out, const bool only_angular_edges = false,
+                            const double max_dist_angular_edge = 7.0) {
   const int n = (int)lines.size();
   for (int i = 0; i + 1 < n; i++)
-    for (int j = i + 1; j < n; j++) get_edges(lines[(size_t)i], lines[(size_t)j], out);
+    for (int j = i + 1; j < n; j++) get_edges(lines[(size_t)i], lines[(size_t)j], out, only_angular_edges, max_dist_angular_edge);
 }
 // nearest_neighbor's first entry: index of the nearest target (-1: none) and its record
 inline int nearest(const V3 sa, const V3 sb, const std::vector<Line>& trg, const std::vector<V3>& dir, const int tie_highest, Pair* out) {
@@ -430,6 +486,125 @@ inline Fitness calc_fitness(const std::vector<Line>& src, const std::vector<Line
     sums_add(s, j >= 0, nn, lenght(l.a, l.b), max_range);
   }
   return sums_finish(s);
+}
+
+// ---- align_local (:205-297) on the host: the restatement the device path of line_align_local.hip is tested against, and the CPU side of
+// scripts/bench_line_align_local.py.  The semantics are DESIGN.md 6g's.
+struct LocalParams {
+  Weights w;                 // the l_* members
+  double max_distance, cos_max_angle, max_range;
+  int float_chain, tie_highest, three_nearest;
+};
+struct LocalHyp {
+  int gate, target;          // target: the target line of a line-pair hypothesis, -1 for an edge pair
+  Tf t;
+  double tn;
+  double fit[5];             // the four fitness values and the score; zeros when gated
+};
+struct LocalResult {
+  Tf t, t_edge;              // the final transformation and the edge-pair phase's (best_trans)
+  double fit[5], fit_edge[5], fit_base[5];
+  long long winner_edge, winner_line, survivors_edge, survivors_line;
+  int n_edges_source, n_edges_target;
+};
+inline Fitness calc_fitness_local(const std::vector<Line>& src, const std::vector<Line>& trg, const std::vector<V3>& dir, const double max_range,
+                                  const int tie_highest) {
+  Sums s = sums_zero();
+  for (const Line& l : src) {
+    Pair nn;
+    nn.real = nn.dist = nn.cov = 0.0;
+    const int j = nearest(l.a, l.b, trg, dir, tie_highest, &nn);
+    sums_add_local(s, j >= 0, nn, lenght(l.a, l.b), max_range);
+  }
+  return sums_finish(s);
+}
+inline void local_fit(const Fitness f, const double score, double* o) {
+  o[0] = f.real_avg_distance; o[1] = f.avg_distance; o[2] = f.coverage; o[3] = f.coverage_percentage; o[4] = score;
+}
+inline void transform_lines(const std::vector<Line>& in, const Tf t, std::vector<Line>* out) {
+  out->resize(in.size());
+  for (size_t k = 0; k < in.size(); k++) {
+    (*out)[k].a = apply(t, in[k].a);
+    (*out)[k].b = apply(t, in[k].b);
+  }
+}
+inline void align_local(const std::vector<Line>& src, const std::vector<Line>& trg, const LocalParams& P, LocalResult* r, std::vector<Line>* aligned,
+                        std::vector<LocalHyp>* hyps_edge, std::vector<LocalHyp>* hyps_line) {
+  std::vector<V3> dir;
+  for (const Line& l : trg) dir.push_back(normalized(sub(l.b, l.a)));
+  std::vector<Edge> es, et;
+  edge_extraction(src, es, true, 0.01);
+  edge_extraction(trg, et, true);
+  r->n_edges_source = (int)es.size();
+  r->n_edges_target = (int)et.size();
+  const Fitness fb = calc_fitness_local(src, trg, dir, P.max_range, P.tie_highest);
+  local_fit(fb, weight_local(P.w, fb.avg_distance, fb.coverage_percentage, 0.0), r->fit_base);
+  for (int k = 0; k < 5; k++) r->fit_edge[k] = r->fit_base[k];
+  r->t_edge = tf_identity();
+  r->winner_edge = r->winner_line = -1;
+  r->survivors_edge = r->survivors_line = 0;
+  std::vector<Line> base = src, cand;
+  if (hyps_edge) hyps_edge->clear();
+  if (hyps_line) hyps_line->clear();
+  // the edge pairs, h = es * Et + et
+  for (size_t a = 0; a < es.size(); a++)
+    for (size_t b = 0; b < et.size(); b++) {
+      LocalHyp hy;
+      hy.target = -1;
+      for (int k = 0; k < 5; k++) hy.fit[k] = 0.0;
+      hy.t = align_edges(es[a], et[b], nullptr);
+      hy.gate = gate_local(hy.t, P.max_distance, P.cos_max_angle, P.float_chain, &hy.tn);
+      if (hy.gate == GATE_PASS) {
+        r->survivors_edge++;
+        transform_lines(src, hy.t, &cand);
+        const Fitness f = calc_fitness_local(cand, trg, dir, P.max_range, P.tie_highest);
+        local_fit(f, weight_local(P.w, f.avg_distance, f.coverage_percentage, hy.tn), hy.fit);
+        if (hy.fit[4] > r->fit_edge[4]) {
+          for (int k = 0; k < 5; k++) r->fit_edge[k] = hy.fit[k];
+          r->t_edge = hy.t;
+          r->winner_edge = (long long)(a * et.size() + b);
+          base = cand;
+        }
+      }
+      if (hyps_edge) hyps_edge->push_back(hy);
+    }
+  // the line pairs over the snapshot, k = i * Lt + r
+  for (int k = 0; k < 5; k++) r->fit[k] = r->fit_edge[k];
+  r->t = r->t_edge;
+  *aligned = base;
+  const int Lt = (int)trg.size();
+  std::vector<double> key((size_t)Lt);
+  std::vector<int> order((size_t)Lt);
+  for (size_t i = 0; i < base.size(); i++) {
+    const float sl = lenght(base[i].a, base[i].b);
+    for (int j = 0; j < Lt; j++) key[(size_t)j] = nn_key(line_to_line(base[i].a, base[i].b, sl, trg[(size_t)j].a, trg[(size_t)j].b, dir[(size_t)j]).real);
+    for (int j = 0; j < Lt; j++) {
+      int rank = 0;
+      for (int q = 0; q < Lt; q++) rank += rank_before(key[(size_t)q], q, key[(size_t)j], j, P.tie_highest) ? 1 : 0;
+      order[(size_t)rank] = j;
+    }
+    for (int rk = 0; rk < Lt; rk++) {
+      LocalHyp hy;
+      hy.target = order[(size_t)rk];
+      for (int k = 0; k < 5; k++) hy.fit[k] = 0.0;
+      hy.t = tf_identity();
+      hy.tn = 0.0;
+      hy.gate = P.three_nearest && rk >= 3 ? (int)GATE_RANK : line_hypothesis(base[i], trg[(size_t)hy.target], P.max_distance, P.cos_max_angle, &hy.t, &hy.tn);
+      if (hy.gate == GATE_PASS) {
+        r->survivors_line++;
+        transform_lines(base, hy.t, &cand);
+        const Fitness f = calc_fitness_local(cand, trg, dir, P.max_range, P.tie_highest);
+        local_fit(f, weight_local(P.w, f.avg_distance, f.coverage_percentage, hy.tn), hy.fit);
+        if (hy.fit[4] > r->fit[4]) {
+          for (int k = 0; k < 5; k++) r->fit[k] = hy.fit[k];
+          r->t = compose(r->t_edge, hy.t);
+          r->winner_line = (long long)i * Lt + rk;
+          *aligned = cand;
+        }
+      }
+      if (hyps_line) hyps_line->push_back(hy);
+    }
+  }
 }
 
 }  // namespace la

@@ -19,6 +19,7 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -242,7 +243,9 @@ void la_merge(const dgs_line_feature* lines, int64_t n, std::vector<la::Line>* o
 
 const char* la_bad_params(const dgs_line_align_params* p) {
   if (!p) return "line align: params is NULL";
-  if (p->struct_size != sizeof(dgs_line_align_params)) return "line align: wrong struct_size";
+  // the struct as it was before align_local's members were appended, or the whole of it
+  if (p->struct_size != offsetof(dgs_line_align_params, l_avg_distance_weight) && p->struct_size != sizeof(dgs_line_align_params))
+    return "line align: wrong struct_size";
   if (!(p->g_max_score_distance > 0.0) || !(p->g_max_score_translation > 0.0)) return "line align: the max_score values must be positive";
   // +infinity is a legal weight (that term alone decides); against a zero term it gives a NaN score, which never wins
   for (const double w : {p->g_avg_distance_weight, p->g_coverage_weight, p->g_transform_weight})
@@ -377,6 +380,14 @@ int dgs_line_align_params_init(dgs_line_align_params* p) {
   p->max_distance = 2.0;
   p->max_angle = M_PI / 9.0;
   p->nn_tie_highest_index = 0;
+  p->l_avg_distance_weight = 0.6;
+  p->l_coverage_weight = 1.0;
+  p->l_transform_weight = 0.2;
+  p->l_max_score_distance = 5.0;
+  p->l_max_score_translation = 5.0;
+  p->l_max_distance = 2.5;
+  p->l_max_angle = M_PI / 9.0;
+  p->refine_three_nearest = 0;
   return DGS_OK;
 }
 

@@ -7,6 +7,12 @@ parameters.  `align_global(source, lines_target, constrain_angle, max_range)` ta
 flat cloud (float32 [N,4], numpy or device tensor), which goes through a `LineExtractor` on the same handle first; an extraction that
 yields no lines falls through as upstream does (the identity with the empty score).  `merge_lines` and `edge_extraction` are the
 host-only pieces and need no GPU.
+
+`align_local(lines_source, lines_target, max_range)` and `align_local_batch(items, max_range)` are LineBasedScanmatcher::align_local
+(:205-297; dgs_line_align_local_batch): a batch of independent (source lines, target lines) items -- a keyframe's near
+buildings -- goes to the device in one call.  The matcher's `l_*` members and the nodelet's `delta_local_*` names set weight_local,
+except `delta_local_avg_distance_weight`: upstream's setter of that name writes the global member, so the nodelet never changes
+l_avg_distance_weight; the name is accepted and ignored here, as dgs::HipLineAligner does not read it (INTEGRATION.md 4f).
 """
 from __future__ import annotations
 
@@ -20,14 +26,21 @@ import numpy as np
 from . import _lib as L
 from .line_extraction import LineFeature
 
-__all__ = ["LineScanMatcher", "BestFitAlignment", "FitnessScore", "EdgeFeature", "merge_lines", "edge_extraction", "params_from_dict"]
+__all__ = ["LineScanMatcher", "BestFitAlignment", "LocalAlignment", "FitnessScore", "EdgeFeature", "merge_lines", "edge_extraction",
+           "params_from_dict"]
 
 _NAMES = {   # member name -> the nodelet's parameter name
     "g_avg_distance_weight": "delta_global_avg_distance_weight", "g_coverage_weight": "delta_global_coverage_weight",
     "g_transform_weight": "delta_global_transform_weight", "g_max_score_distance": "delta_global_max_score_distance",
     "g_max_score_translation": "delta_global_max_score_translation",
+    # delta_local_avg_distance_weight does not set l_avg_distance_weight: upstream's setter of that name (line_based_scanmatcher.hpp:117)
+    # writes the global member, so the nodelet never changes the local one; dgs::HipLineAligner does not read it either.  params_from_dict
+    # accepts and ignores the name; the member name sets the weight.
+    "l_avg_distance_weight": None, "l_coverage_weight": "delta_local_coverage_weight",
+    "l_transform_weight": "delta_local_transform_weight", "l_max_score_distance": "delta_local_max_score_distance",
+    "l_max_score_translation": "delta_local_max_score_translation",
 }
-_EXTRA = ("max_distance", "max_angle", "angle_gate_float_chain", "nn_tie_highest_index")
+_EXTRA = ("max_distance", "max_angle", "l_max_distance", "l_max_angle", "angle_gate_float_chain", "nn_tie_highest_index", "refine_three_nearest")
 
 
 @dataclass
@@ -58,22 +71,35 @@ class BestFitAlignment:
     counts: dict = field(default_factory=dict)   # hypotheses, survivors, edges_source, edges_target, lines_target
 
 
+@dataclass
+class LocalAlignment(BestFitAlignment):
+    """align_local's BestFitAlignment; `winner` is the edge-pair phase's h, `winner_line` the line-pair phase's k = i * Lt + r."""
+    isEdgeAligned: bool = False
+    winner_line: int = -1
+    edge_transformation: Optional[np.ndarray] = None      # best_trans: the edge-pair phase's result
+    edge_fitness_score: Optional[FitnessScore] = None
+    edge_score: float = 0.0
+    baseline_fitness_score: Optional[FitnessScore] = None
+    baseline_score: float = 0.0
+
+
 def params_from_dict(params: Optional[dict] = None):
     """-> (LineAlignParams, the remaining entries): the constructor's defaults (line_based_scanmatcher.hpp:91-95), align_global's 2.0 and
     pi / 9, overridden by `params`; what is not an alignment parameter is left for the line extraction."""
     pr = dict(params or {})
+    pr.pop("delta_local_avg_distance_weight", None)
     p = L.LineAlignParams()
     rc = L.load().dgs_line_align_params_init(C.byref(p))
     if rc:
         raise L.DgsError(rc, "dgs_line_align_params_init")
     for member, ros in _NAMES.items():
         for k in (ros, member):
-            if k in pr:
+            if k is not None and k in pr:
                 setattr(p, member, float(pr.pop(k)))
     for k in _EXTRA:
         if k in pr:
             v = pr.pop(k)
-            setattr(p, k, float(v) if k.startswith("max_") else int(v))
+            setattr(p, k, float(v) if "max_" in k else int(v))
     return p, pr
 
 
@@ -104,16 +130,22 @@ def merge_lines(lines: List[LineFeature]) -> List[LineFeature]:
     return _from_c(out, n.value)
 
 
-def edge_extraction(lines: List[LineFeature]) -> List[EdgeFeature]:
-    """edge_extraction (:459-471) on the host; no handle, no device."""
+def edge_extraction(lines: List[LineFeature], only_angular_edges: Optional[bool] = None, max_dist_angular_edge: float = 7.0) -> List[EdgeFeature]:
+    """edge_extraction (:459-471) on the host; no handle, no device.  With `only_angular_edges` given, upstream's two further arguments
+    go through dgs_line_edges_angular."""
     lib = L.load()
     arr = _to_c(lines)
     n = C.c_int64(0)
-    rc = lib.dgs_line_edges(C.cast(arr, C.c_void_p), len(lines), None, 0, C.byref(n))
+    if only_angular_edges is None:
+        call = lambda buf, cap: lib.dgs_line_edges(C.cast(arr, C.c_void_p), len(lines), buf, cap, C.byref(n))
+    else:
+        call = lambda buf, cap: lib.dgs_line_edges_angular(C.cast(arr, C.c_void_p), len(lines), 1 if only_angular_edges else 0,
+                                                           float(max_dist_angular_edge), buf, cap, C.byref(n))
+    rc = call(None, 0)
     if rc and n.value == 0:
         _check(rc, "dgs_line_edges")
     out = (L.EdgeFeatureC * max(n.value, 1))()
-    _check(lib.dgs_line_edges(C.cast(arr, C.c_void_p), len(lines), C.cast(out, C.c_void_p), n.value, C.byref(n)), "dgs_line_edges")
+    _check(call(C.cast(out, C.c_void_p), n.value), "dgs_line_edges")
     return [EdgeFeature(np.array(e.edge_point[:]), np.array(e.point_a[:]), np.array(e.point_b[:])) for e in out[:n.value]]
 
 
@@ -127,6 +159,7 @@ class LineScanMatcher:
         self.registration = registration
         self._lib = registration._lib
         self.extractor = LineExtractor(rest, registration=registration)
+        self._local_sizes = []
 
     @property
     def _h(self):
@@ -151,6 +184,42 @@ class LineScanMatcher:
             counts=dict(hypotheses=al.n_hypotheses, survivors=al.n_survivors, edges_source=al.n_edges_source, edges_target=al.n_edges_target,
                         lines_target=al.n_lines_target))
 
+    def align_local(self, lines_source: List[LineFeature], lines_target: List[LineFeature], max_range: float = 0.5) -> "LocalAlignment":
+        """align_local (:205-297) of one item: a batch of one."""
+        return self.align_local_batch([(lines_source, lines_target)], max_range)[0]
+
+    def align_local_batch(self, items, max_range: float = 0.5) -> List["LocalAlignment"]:
+        """`items`: a sequence of (lines_source, lines_target) pairs, e.g. (building lines, the keyframe's lines in that building's frame)
+        for every near building.  One device call: one upload, one download, one host wait, a fixed number of launches."""
+        items = [(list(s), list(t)) for s, t in items]
+        n = len(items)
+        so = (C.c_int64 * (n + 1))()
+        to = (C.c_int64 * (n + 1))()
+        for b, (s, t) in enumerate(items):
+            so[b + 1], to[b + 1] = so[b] + len(s), to[b] + len(t)
+        src = _to_c([l for s, _ in items for l in s])
+        trg = _to_c([l for _, t in items for l in t])
+        out = (L.LineFeatureC * max(so[n], 1))()
+        al = (L.LineLocalAlignment * max(n, 1))()
+        self.registration._check(self._lib.dgs_line_align_local_batch(
+            self._h, C.byref(self.params), n, C.cast(src, C.c_void_p), C.cast(so, C.c_void_p), C.cast(trg, C.c_void_p), C.cast(to, C.c_void_p),
+            float(max_range), C.cast(out, C.c_void_p), C.cast(al, C.c_void_p)))
+        aligned = _from_c(out, so[n])
+        self._local_sizes = [(al[b].n_hypotheses_edge, al[b].n_hypotheses_line) for b in range(n)]   # what local_hypotheses may read
+        res = []
+        for b, (s, t) in enumerate(items):
+            a = al[b]
+            res.append(LocalAlignment(
+                not_aligned_lines=s, aligned_lines=aligned[so[b]:so[b + 1]], transformation=np.array(a.transformation[:], np.float64).reshape(4, 4),
+                fitness_score=FitnessScore(*a.fitness_score[:]), score=a.score, winner=a.winner_edge, status=L.LA_STATUS[a.status],
+                counts=dict(hypotheses_edge=a.n_hypotheses_edge, survivors_edge=a.n_survivors_edge, hypotheses_line=a.n_hypotheses_line,
+                            survivors_line=a.n_survivors_line, edges_source=a.n_edges_source, edges_target=a.n_edges_target),
+                isEdgeAligned=bool(a.is_edge_aligned), winner_line=a.winner_line,
+                edge_transformation=np.array(a.edge_transformation[:], np.float64).reshape(4, 4),
+                edge_fitness_score=FitnessScore(*a.edge_fitness_score[:]), edge_score=a.edge_score,
+                baseline_fitness_score=FitnessScore(*a.baseline_fitness_score[:]), baseline_score=a.baseline_score))
+        return res
+
     # -- test hooks ----------------------------------------------------------------------------------------------------------
     def hypotheses(self, first: int = 0, count: Optional[int] = None):
         """Per-hypothesis records of the last call as arrays: gate, slot, rotation [n,4], translation [n,3], fitness [n,4], score."""
@@ -167,3 +236,23 @@ class LineScanMatcher:
         c = (C.c_int64 * 4)()
         self.registration._check(self._lib.dgs_line_align_get_hypotheses(self._h, 0, 0, None, C.cast(c, C.c_void_p)))
         return dict(launches=c[0], host_waits=c[1], hypotheses=c[2], survivors=c[3])
+
+    def local_hypotheses(self, item: int, phase: int, first: int = 0, count: Optional[int] = None):
+        """Per-hypothesis records of the last align_local / align_local_batch call for one item and phase (0: edge pairs, 1: line pairs)
+        as arrays: gate, target, rotation [n,4], translation [n,3], fitness [n,4], score.  `count` None: all of the item's hypotheses of
+        that phase from `first` on."""
+        if count is None:
+            count = self._local_sizes[item][phase] - first
+        rec = (L.LineAlignLocalHypothesis * max(count, 1))()
+        self.registration._check(self._lib.dgs_line_align_local_get_hypotheses(self._h, item, phase, first, count, C.cast(rec, C.c_void_p), None))
+        a = np.frombuffer(rec, dtype=np.dtype([("gate", "<i4"), ("target", "<i4"), ("rotation", "<f8", 4), ("translation", "<f8", 3),
+                                               ("fitness", "<f8", 4), ("score", "<f8")]))[:count]
+        return {k: a[k].copy() for k in a.dtype.names}
+
+    def local_counts(self):
+        """-> dict(launches, host_waits, items, hypotheses_edge, hypotheses_line, survivors_edge, survivors_line, workgroups) of the last
+        align_local / align_local_batch call."""
+        c = (C.c_int64 * 8)()
+        self.registration._check(self._lib.dgs_line_align_local_get_hypotheses(self._h, 0, 0, 0, 0, None, C.cast(c, C.c_void_p)))
+        return dict(launches=c[0], host_waits=c[1], items=c[2], hypotheses_edge=c[3], hypotheses_line=c[4], survivors_edge=c[5],
+                    survivors_line=c[6], workgroups=c[7])

@@ -6,8 +6,13 @@
 // (real_avg_distance, avg_distance, coverage, coverage_percentage).  Built from the nodelet's private parameters
 // (apps/delta_graph_slam_nodelet.cpp:98-102, same names and defaults).  The handle is created at the first call.  A failure of any kind
 // never throws: alignGlobal() returns false (last_error() says why) and the caller falls back to the scalar loop.
+// alignLocal() / alignLocalBatch() are LineBasedScanmatcher::align_local (:205-297; dgs_line_align_local_batch): one call for
+// all near buildings of a keyframe.  They also set BestFitAlignmentT::isEdgeAligned.  The l_* weights come from the
+// nodelet's delta_local_* parameters (apps/delta_graph_slam_nodelet.cpp:105-108); delta_local_avg_distance_weight is not read, because
+// upstream's setter of that name writes the global member, so l_avg_distance_weight keeps the constructor's 0.6.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <memory>
 #include <vector>
@@ -30,6 +35,10 @@ class HipLineAligner {
     p_.g_transform_weight = private_nh.template param<double>("delta_global_transform_weight", 0.5);
     p_.g_max_score_distance = private_nh.template param<double>("delta_global_max_score_distance", 3.5);
     p_.g_max_score_translation = private_nh.template param<double>("delta_global_max_score_translation", 3.5);
+    p_.l_coverage_weight = private_nh.template param<double>("delta_local_coverage_weight", 1.5);
+    p_.l_transform_weight = private_nh.template param<double>("delta_local_transform_weight", 0.1);
+    p_.l_max_score_distance = private_nh.template param<double>("delta_local_max_score_distance", 1.0);
+    p_.l_max_score_translation = private_nh.template param<double>("delta_local_max_score_translation", 3.5);
   }
   ~HipLineAligner() {
     if (h_) dgs_destroy(h_);
@@ -70,7 +79,67 @@ class HipLineAligner {
     return true;
   }
 
+  struct LocalItem {   // one near building: align_local(linesSource, linesTarget, max_range)
+    const std::vector<LinePtr>* linesSource;
+    const std::vector<LinePtr>* linesTarget;
+  };
+  const std::vector<dgs_line_local_alignment>& lastLocal() const { return lal_; }   // winners, counts and statuses of the last batch
+
+  // One device call for all items.  false: *results is untouched.
+  bool alignLocalBatch(const std::vector<LocalItem>& items, double max_range, std::vector<BestFitAlignmentT>* results) {
+    if (!results || !ensure_handle()) return false;
+    src_.clear();
+    trg_.clear();
+    so_.assign(1, 0);
+    to_.assign(1, 0);
+    for (const LocalItem& it : items) {
+      append(*it.linesSource, &src_);
+      append(*it.linesTarget, &trg_);
+      so_.push_back((int64_t)src_.size());
+      to_.push_back((int64_t)trg_.size());
+    }
+    out_.resize(src_.size() ? src_.size() : 1);
+    lal_.assign(items.size() ? items.size() : 1, dgs_line_local_alignment{});
+    if (dgs_line_align_local_batch(h_, &p_, (int64_t)items.size(), src_.data(), so_.data(), trg_.data(), to_.data(), max_range, out_.data(),
+                                   lal_.data()) != DGS_OK)
+      return false;
+    lal_.resize(items.size());
+    results->assign(items.size(), BestFitAlignmentT());
+    for (size_t b = 0; b < items.size(); b++) {
+      BestFitAlignmentT& r = (*results)[b];
+      const std::vector<LinePtr>& ls = *items[b].linesSource;
+      r.not_aligned_lines = ls;
+      for (size_t i = 0; i < ls.size(); i++) {
+        auto line = std::make_shared<LineFeatureT>(*ls[i]);
+        for (int a = 0; a < 3; a++) {
+          line->pointA[a] = out_[(size_t)so_[b] + i].point_a[a];
+          line->pointB[a] = out_[(size_t)so_[b] + i].point_b[a];
+        }
+        r.aligned_lines.push_back(line);
+      }
+      for (int rr = 0; rr < 4; rr++)
+        for (int c = 0; c < 4; c++) r.transformation(rr, c) = lal_[b].transformation[4 * rr + c];
+      r.fitness_score.real_avg_distance = lal_[b].fitness_score[0];
+      r.fitness_score.avg_distance = lal_[b].fitness_score[1];
+      r.fitness_score.coverage = lal_[b].fitness_score[2];
+      r.fitness_score.coverage_percentage = lal_[b].fitness_score[3];
+      r.isEdgeAligned = lal_[b].is_edge_aligned != 0;
+    }
+    return true;
+  }
+  bool alignLocal(const std::vector<LinePtr>& linesSource, const std::vector<LinePtr>& linesTarget, double max_range, BestFitAlignmentT* result) {
+    std::vector<BestFitAlignmentT> r;
+    if (!result || !alignLocalBatch({LocalItem{&linesSource, &linesTarget}}, max_range, &r)) return false;
+    *result = r[0];
+    return true;
+  }
+
  private:
+  static void append(const std::vector<LinePtr>& lines, std::vector<dgs_line_feature>* out) {
+    std::vector<dgs_line_feature> one;
+    pack(lines, &one);
+    out->insert(out->end(), one.begin(), one.begin() + (std::ptrdiff_t)lines.size());
+  }
   static void pack(const std::vector<LinePtr>& lines, std::vector<dgs_line_feature>* out) {
     out->resize(lines.size() ? lines.size() : 1);
     for (size_t i = 0; i < lines.size(); i++) {
@@ -98,6 +167,8 @@ class HipLineAligner {
   dgs_handle* h_ = nullptr;
   int device_ = 0;
   std::vector<dgs_line_feature> src_, trg_, out_;
+  std::vector<int64_t> so_, to_;
+  std::vector<dgs_line_local_alignment> lal_;
 };
 
 }  // namespace dgs

@@ -630,13 +630,17 @@ enum dgs_line_align_status {
   DGS_LA_ALIGNED = 0,       /* an edge-pair hypothesis beat the identity's score */
   DGS_LA_NO_HYPOTHESES = 1, /* one side has no edges */
   DGS_LA_ALL_GATED = 2,     /* every hypothesis failed a gate */
-  DGS_LA_NONE_BETTER = 3    /* no surviving hypothesis scored strictly above the identity */
+  DGS_LA_NONE_BETTER = 3,   /* no surviving hypothesis scored strictly above the identity */
+  DGS_LA_LINE_ALIGNED = 4   /* align_local: no edge pair took over, a line pair of the second phase did */
 };
 enum dgs_line_align_gate {
   DGS_LA_GATE_PASS = 0,
   DGS_LA_GATE_DISTANCE = 1, /* translation.norm() > max_distance */
   DGS_LA_GATE_IDENTITY = 2, /* transform == Identity */
-  DGS_LA_GATE_ANGLE = 3     /* constrain_angle and cos(angle) < cos(max_angle) */
+  DGS_LA_GATE_ANGLE = 3,    /* constrain_angle (align_local: always) and cos(angle) < cos(max_angle) */
+  DGS_LA_GATE_LINE_DIRECTION = 4, /* align_local's line pairs: |cos| between the two directions < cos(max_angle) */
+  DGS_LA_GATE_LINE_DISTANCE = 5,  /* align_local's line pairs: align_lines' translation.norm() > max_distance */
+  DGS_LA_GATE_RANK = 6      /* align_local's line pairs with refine_three_nearest: a neighbour of rank >= 3, not visited */
 };
 #define DGS_LA_MAX_LINES_SOURCE 256       /* what limits Ls, Lt and the hypothesis count */
 #define DGS_LA_MAX_LINES_TARGET 512       /* after merging */
@@ -657,6 +661,17 @@ typedef struct dgs_line_align_params {
   int32_t nn_tie_highest_index;    /* 0: equal real_distances go to the lowest target index (recalled: std::sort's insertion sort
                                       below 16 elements keeps the order); 1: to the highest */
   int32_t reserved;
+  /* ---- appended for align_local.  A caller whose struct_size ends at `reserved` gets the defaults below. */
+  double l_avg_distance_weight;    /* weight_local's members (line_based_scanmatcher.hpp:96-100): 0.6, 1.0, 0.2, 5.0, 5.0; same rules as g_* */
+  double l_coverage_weight;
+  double l_transform_weight;
+  double l_max_score_distance;
+  double l_max_score_translation;
+  double l_max_distance;           /* align_local's constants (:208-209): 2.5 and pi / 9 */
+  double l_max_angle;
+  int32_t refine_three_nearest;    /* 0: the line-pair phase visits every neighbour rank (what upstream's `i<3 || i<size` does for three or
+                                      more); 1: ranks 0..2 only, what its comment intends */
+  int32_t reserved2;
 } dgs_line_align_params;
 int dgs_line_align_params_init(dgs_line_align_params* params);
 /* upstream's BestFitAlignment without the two line vectors, and what the search saw */
@@ -706,6 +721,66 @@ typedef struct dgs_line_align_hypothesis {
 /* records: room for `count` records of h = first .. first + count - 1 (nullable).  counts4 (nullable): kernel launches, host waits,
  * hypotheses and survivors of the last call's device phase. */
 int dgs_line_align_get_hypotheses(dgs_handle* h, int64_t first, int64_t count, dgs_line_align_hypothesis* records, int64_t* counts4);
+
+/* ---- LineBasedScanmatcher::align_local on the device, batched (src/hdl_graph_slam/line_based_scanmatcher.cpp:205-297) -----------
+ * One call takes n_items independent (source lines, target lines) pairs -- a keyframe's near buildings.  Per item: the baseline
+ * (calc_fitness_score with is_local, weight_local), the edge pairs h = es * Et + et of edge_extraction(src, true, 0.01) x
+ * edge_extraction(trg, true) gated by distance then angle, the strict arg-max, then the line pairs k = i * Lt + r over the snapshot
+ * of the first phase's result (i: line of the snapshot, r: rank of a target line by (real_distance, index)), and the second
+ * arg-max.  Edges are extracted on the host; everything else runs on the device with one upload, one download, one host wait and a
+ * number of kernel launches that does not depend on n_items.  Nothing is merged: the target lines are used as given.  Semantics,
+ * the deliberate differences from upstream and the limits: DESIGN.md 6g.  Additions only: DGS_ABI_VERSION is unchanged. */
+#define DGS_LA_MAX_ITEMS 4096             /* items per batch call; the summed hypotheses of both phases: DGS_LA_MAX_HYPOTHESES */
+typedef struct dgs_line_local_alignment {
+  double transformation[16];       /* row-major 4 x 4: best_trans * transform, or best_trans when no line pair took over */
+  double fitness_score[4];         /* FitnessScore of the result */
+  double score;                    /* weight_local of the result */
+  double edge_transformation[16];  /* best_trans: the first phase's result (the identity when no edge pair took over) */
+  double edge_fitness_score[4];
+  double edge_score;
+  double baseline_fitness_score[4];
+  double baseline_score;
+  int64_t winner_edge;             /* the winning h = es * Et + et, -1: none */
+  int64_t winner_line;             /* the winning k = i * Lt + r, -1: none */
+  int64_t n_hypotheses_edge;       /* Es * Et */
+  int64_t n_survivors_edge;
+  int64_t n_hypotheses_line;       /* Ls * Lt */
+  int64_t n_survivors_line;
+  int32_t n_edges_source;
+  int32_t n_edges_target;
+  int32_t is_edge_aligned;         /* upstream's isEdgeAligned */
+  int32_t status;                  /* dgs_line_align_status: ALIGNED (an edge pair took over), LINE_ALIGNED, NO_HYPOTHESES (neither phase
+                                      has one), ALL_GATED, NONE_BETTER */
+} dgs_line_local_alignment;
+/* src_lines / trg_lines: the lines of all items back to back; src_offsets / trg_offsets: n_items + 1 ascending offsets into them
+ * (item b owns [offsets[b], offsets[b + 1])).  aligned_lines (nullable): room for src_offsets[n_items] features, laid out like
+ * src_lines; the statistics of a source line are carried through.  alignments: n_items records.  More than DGS_LA_MAX_ITEMS items,
+ * DGS_LA_MAX_LINES_SOURCE / DGS_LA_MAX_LINES_TARGET lines in an item, DGS_LA_MAX_HYPOTHESES hypotheses summed over items and both
+ * phases, a NaN max_range or a coordinate that is not finite is DGS_ERR_INVALID_ARGUMENT with a message: nothing is truncated. */
+int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* params, int64_t n_items, const dgs_line_feature* src_lines,
+                               const int64_t* src_offsets, const dgs_line_feature* trg_lines, const int64_t* trg_offsets, double max_range,
+                               dgs_line_feature* aligned_lines, dgs_line_local_alignment* alignments);
+/* a batch of one */
+int dgs_line_align_local(dgs_handle* h, const dgs_line_align_params* params, const dgs_line_feature* src_lines, int64_t n_src,
+                         const dgs_line_feature* trg_lines, int64_t n_trg, double max_range, dgs_line_feature* aligned_lines,
+                         dgs_line_local_alignment* alignment);
+/* edge_extraction with its two upstream arguments (dgs_line_edges is only_angular_edges = 0, max_dist_angular_edge = 7.0) */
+int dgs_line_edges_angular(const dgs_line_feature* lines, int64_t n, int32_t only_angular_edges, double max_dist_angular_edge,
+                           dgs_edge_feature* edges, int64_t capacity, int64_t* n_edges);
+/* Test hook: what the device computed per hypothesis in the last dgs_line_align_local_batch call. */
+typedef struct dgs_line_align_local_hypothesis {
+  int32_t gate;           /* dgs_line_align_gate */
+  int32_t target;         /* phase 1: the target line of rank r; phase 0: -1 */
+  double rotation[4];     /* r00 r01 r10 r11 of this hypothesis's own transform (align_edges / align_lines) */
+  double translation[3];
+  double fitness_score[4];/* zeros when gated */
+  double score;           /* weight_local; 0 when gated */
+} dgs_line_align_local_hypothesis;
+/* records: room for `count` records of hypotheses first .. first + count - 1 of `item` in `phase` (0: edge pairs, 1: line pairs)
+ * (nullable).  counts8 (nullable): kernel launches, host waits, items, summed hypotheses of phase 0 and of phase 1, summed survivors of
+ * phase 0 and of phase 1, and workgroups of the two scoring launches together, all of the last call. */
+int dgs_line_align_local_get_hypotheses(dgs_handle* h, int64_t item, int32_t phase, int64_t first, int64_t count,
+                                        dgs_line_align_local_hypothesis* records, int64_t* counts8);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,353 @@
+"""numpy float64 restatement of LineBasedScanmatcher::align_local (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp:205-297), written
+from the upstream source on the primitives of tests/line_align_reference.py (Trig, line_to_line, get_edges, align_edges, _align_lines,
+gate_angle) and independent of the library's header.  DESIGN.md 6g states the semantics; the two deliberate differences from upstream are
+the walk over every neighbour rank r < Lt (upstream's `i<3 || i<size` reads past the end below three) with the `refine_three_nearest`
+switch, and the rank rule (real_distance, then target index) where std::sort leaves equal keys unordered."""
+import numpy as np
+
+import line_align_reference as R
+
+DBL_MAX = R.DBL_MAX
+DEFAULTS = dict(l_avg_distance_weight=0.6, l_coverage_weight=1.0, l_transform_weight=0.2, l_max_score_distance=5.0, l_max_score_translation=5.0,
+                l_max_distance=2.5, l_max_angle=np.pi / 9.0, angle_gate_float_chain=1, nn_tie_highest_index=0, refine_three_nearest=0)
+GATE_PASS, GATE_DISTANCE, GATE_ANGLE, GATE_LINE_DIRECTION, GATE_LINE_DISTANCE, GATE_RANK = 0, 1, 3, 4, 5, 6
+
+
+def weight_local(p, avg_distance, coverage_percentage, translation_distance):
+    mn = lambda a, b: np.where(b < a, b, a)   # std::min(a, b)
+    with np.errstate(all="ignore"):
+        return (-p["l_avg_distance_weight"] * (mn(p["l_max_score_distance"], avg_distance) / p["l_max_score_distance"]) * 100.
+                + p["l_coverage_weight"] * coverage_percentage
+                - p["l_transform_weight"] * (mn(p["l_max_score_translation"], translation_distance) / p["l_max_score_translation"]) * 100.)
+
+
+def get_edges(l1, l2, only_angular_edges=False, max_dist_angular_edge=7.0):
+    """R.get_edges with upstream's two further arguments: in cases 1, 2 and 3 the angular check sits between the side-length check and the
+    first push_back, so it can be applied to what the plain function returns; case 4 has none."""
+    out, case = R.get_edges(l1, l2)
+    if not only_angular_edges or not out or case == 4:
+        return out, case
+    ep = out[0][0]
+    n = lambda q: float(R._norm(R._sub(R._s(q), ep)))
+    m1, m2 = min(n(l1[0]), n(l1[1])), min(n(l2[0]), n(l2[1]))
+    drop = (m1 > max_dist_angular_edge or m2 > max_dist_angular_edge) if case == 1 else m1 > max_dist_angular_edge if case == 2 \
+        else m2 > max_dist_angular_edge
+    return ([] if drop else out), case
+
+
+def edge_extraction(lines, only_angular_edges=False, max_dist_angular_edge=7.0, cases=None):
+    out = []
+    for i in range(len(lines) - 1):
+        for j in range(i + 1, len(lines)):
+            e, c = get_edges(lines[i], lines[j], only_angular_edges, max_dist_angular_edge)
+            if cases is not None:
+                cases.append((c, len(e)))
+            out += e
+    return np.array(out, np.float64).reshape(-1, 3, 3)
+
+
+def pair_records(src, trg):
+    """src [S, Ls, 2, 3], trg [Lt, 2, 3] -> real, dist, cov [S, Ls, Lt] and the sort key (NaN -> inf)"""
+    ta, tb = R._v(trg[None, None, :, 0]), R._v(trg[None, None, :, 1])
+    d = R._normalized(R._sub(tb, ta))
+    sa, sb = R._v(src[:, :, None, 0]), R._v(src[:, :, None, 1])
+    real, dist, cov = R.line_to_line(sa, sb, ta, tb, d)
+    return real, dist, cov, np.where(np.isnan(real), np.inf, real)
+
+
+def calc_fitness(src, trg, p, max_range):
+    """calc_fitness_score(is_local = true): src [S, Ls, 2, 3] -> fitness [S, 4], picks [S, Ls], included [S, Ls]"""
+    S, Ls = src.shape[:2]
+    Lt = trg.shape[0]
+    sums = np.zeros((5, S))
+    picks = np.full((S, Ls), -1, np.int64)
+    inc = np.zeros((S, Ls), bool)
+    with np.errstate(all="ignore"):
+        if Lt and Ls:
+            real, dist, cov, key = pair_records(src, trg)
+            picks = Lt - 1 - np.argmin(key[:, :, ::-1], axis=2) if p["nn_tie_highest_index"] else np.argmin(key, axis=2)
+            take = lambda a: np.take_along_axis(a, picks[:, :, None], 2)[:, :, 0]
+            real, dist, cov = take(real), take(dist), take(cov)
+            inc = dist < max_range
+        sl = R.lenght(R._v(src[:, :, 0]), R._v(src[:, :, 1]))
+        for i in range(Ls):
+            if Lt:
+                m = inc[:, i]
+                sums[0] = np.where(m, sums[0] + real[:, i] * sl[:, i], sums[0])
+                sums[1] = np.where(m, sums[1] + sl[:, i], sums[1])
+                sums[2] = np.where(m, sums[2] + dist[:, i] * cov[:, i], sums[2])
+                sums[3] = np.where(m, sums[3] + cov[:, i], sums[3])
+            sums[4] = sums[4] + sl[:, i]
+        fit = np.empty((S, 4))
+        fit[:, 2] = sums[3]
+        fit[:, 0] = np.where(sums[1] > 0, sums[0] / np.where(sums[1] > 0, sums[1], 1.0), DBL_MAX)
+        fit[:, 1] = np.where(sums[3] > 0, sums[2] / np.where(sums[3] > 0, sums[3], 1.0), DBL_MAX)
+        fit[:, 3] = np.where(sums[4] > 0, sums[3] / np.where(sums[4] > 0, sums[4], 1.0) * 100.0, 0.0)
+    return fit, picks, inc
+
+
+def _score_all(lines, rot, tr, tn, gate, trg, p, max_range, batch=64):
+    H, Ls = gate.shape[0], lines.shape[0]
+    fit, score, picks = np.zeros((H, 4)), np.zeros(H), np.full((H, Ls), -1, np.int64)
+    surv = np.nonzero(gate == GATE_PASS)[0]
+    for b0 in range(0, surv.size, batch):
+        hs = surv[b0:b0 + batch]
+        f, pk, _ = calc_fitness(R.transform_lines(lines, rot[hs], tr[hs]), trg, p, max_range)
+        fit[hs], picks[hs] = f, pk
+        score[hs] = weight_local(p, f[:, 1], f[:, 3], tn[hs])
+    return fit, score, picks, surv
+
+
+def _argmax(score, surv, start):
+    winner, best = -1, start
+    for h in surv:                                   # strict > in index order; a NaN compares false
+        if score[h] > best:
+            winner, best = int(h), float(score[h])
+    return winner, best
+
+
+def align_local(src, trg, params=None, max_range=0.5, seed=None):
+    p = dict(DEFAULTS, **(params or {}))
+    T = R.Trig(seed)
+    src = np.asarray(src, np.float64).reshape(-1, 2, 3)
+    trg = np.asarray(trg, np.float64).reshape(-1, 2, 3)
+    Ls, Lt = src.shape[0], trg.shape[0]
+    cos_max = np.cos(p["l_max_angle"])
+    base_fit, base_picks, base_inc = calc_fitness(src[None], trg, p, max_range)
+    base_score = float(weight_local(p, base_fit[0, 1], base_fit[0, 3], 0.0))
+    es, et = edge_extraction(src, True, 0.01), edge_extraction(trg, True)
+    # ---- the edge pairs, h = es * Et + et: the distance gate, then always the angle gate
+    Es, Et = es.shape[0], et.shape[0]
+    a, b = np.repeat(np.arange(Es), Et), np.tile(np.arange(Et), Es)
+    with np.errstate(all="ignore"):
+        r, t, rot1 = R.align_edges(T, tuple(R._v(es[a, k]) for k in range(3)), tuple(R._v(et[b, k]) for k in range(3)))
+        tn1 = R._norm(t)
+        gate1 = np.zeros(Es * Et, np.int32)
+        if Es * Et:
+            ang = T.cos(R.gate_angle(T, r, p["angle_gate_float_chain"])) < cos_max
+            gate1[ang] = GATE_ANGLE
+            gate1[tn1 > p["l_max_distance"]] = GATE_DISTANCE
+    rot1_, tr1 = np.stack(r, 1).reshape(-1, 4), np.stack(t, 1).reshape(-1, 3)
+    fit1, score1, picks1, surv1 = _score_all(src, rot1_, tr1, tn1, gate1, trg, p, max_range)
+    w1, best1 = _argmax(score1, surv1, base_score)
+    if w1 >= 0:
+        r1, t1 = rot1_[w1], tr1[w1]
+        snap = R.transform_lines(src, r1[None], t1[None])[0]
+        fit_e = fit1[w1].copy()
+    else:
+        r1, t1 = np.array([1.0, 0.0, 0.0, 1.0]), np.zeros(3)
+        snap = src.copy()
+        fit_e = base_fit[0].copy()
+    T_edge = R._mat(r1, t1)
+    # ---- the line pairs over the snapshot, k = i * Lt + r
+    H2 = Ls * Lt
+    gate2, target2 = np.zeros(H2, np.int32), np.full(H2, -1, np.int64)
+    rot2, tr2, tn2 = np.tile([1.0, 0.0, 0.0, 1.0], (H2, 1)), np.zeros((H2, 3)), np.zeros(H2)
+    if H2:
+        with np.errstate(all="ignore"):
+            key = pair_records(snap[None], trg)[3][0]                       # [Ls, Lt]
+        idx = np.arange(Lt)
+        for i in range(Ls):
+            order = np.lexsort((-idx if p["nn_tie_highest_index"] else idx, key[i]))
+            for rk in range(Lt):
+                k, j = i * Lt + rk, int(order[rk])
+                target2[k] = j
+                if p["refine_three_nearest"] and rk >= 3:
+                    gate2[k] = GATE_RANK
+                    continue
+                sd = R._normalized(R._sub(R._v(snap[i, 0]), R._v(snap[i, 1])))
+                td = R._normalized(R._sub(R._v(trg[j, 0]), R._v(trg[j, 1])))
+                if abs(float(R._dot(sd, td))) < cos_max:
+                    gate2[k] = GATE_LINE_DIRECTION
+                    continue
+                rr, tt = R._align_lines(T, snap[i], trg[j])
+                rot2[k], tr2[k] = rr[0], tt[0]
+                tn2[k] = float(R._norm(R._v(tt[0])))
+                if tn2[k] > p["l_max_distance"]:
+                    gate2[k] = GATE_LINE_DISTANCE
+    fit2, score2, picks2, surv2 = _score_all(snap, rot2, tr2, tn2, gate2, trg, p, max_range)
+    w2, best2 = _argmax(score2, surv2, best1)
+    if w2 >= 0:
+        final_T = R._compose(T_edge, R._mat(rot2[w2], tr2[w2]))
+        aligned = R.transform_lines(snap, rot2[w2][None], tr2[w2][None])[0]
+        fit_f = fit2[w2].copy()
+    else:
+        final_T, aligned, fit_f = T_edge.copy(), snap.copy(), fit_e.copy()
+    return dict(
+        edges_source=es, edges_target=et, base_fitness=base_fit[0], base_score=base_score, base_picks=base_picks[0], base_included=base_inc[0],
+        gate1=gate1, rot1=np.asarray(rot1, bool).reshape(-1), rotation1=rot1_, translation1=tr1, tn1=np.asarray(tn1).reshape(-1), fitness1=fit1,
+        score1=score1, picks1=picks1, survivors1=surv1, winner_edge=w1, edge_transformation=T_edge, edge_fitness=fit_e, edge_score=best1,
+        snapshot=snap, gate2=gate2, target2=target2, rotation2=rot2, translation2=tr2, tn2=tn2, fitness2=fit2, score2=score2, picks2=picks2,
+        survivors2=surv2, winner_line=w2, transformation=final_T, fitness_final=fit_f, score_final=best2, aligned_lines=aligned)
+
+
+def _spread(x, y):
+    x, y = np.asarray(x, np.float64).ravel(), np.asarray(y, np.float64).ravel()
+    same = (x == y) | (np.isnan(x) & np.isnan(y))
+    with np.errstate(all="ignore"):
+        return float(np.max(np.where(same, 0.0, np.abs(x - y)), initial=0.0))
+
+
+def compare_runs(a, b):
+    """Two runs of one item (plain and nudged trigonometry) -> (unstable h of phase 0, unstable k of phase 1, spread of the per-hypothesis
+    fitness and scores, spread of the final record).  A hypothesis is unstable when its gate outcome, its rot1 / rot2 choice, a
+    nearest-neighbour pick or (phase 1) the target at its rank differs."""
+    un1 = (a["gate1"] != b["gate1"]) | (a["rot1"] != b["rot1"]) | np.any(a["picks1"] != b["picks1"], axis=1)
+    un2 = (a["gate2"] != b["gate2"]) | (a["target2"] != b["target2"]) | np.any(a["picks2"] != b["picks2"], axis=1)
+    ok1, ok2 = ~un1 & (a["gate1"] == GATE_PASS), ~un2 & (a["gate2"] == GATE_PASS)
+    s_hyp = max(_spread(a["score1"][ok1], b["score1"][ok1]), _spread(a["fitness1"][ok1], b["fitness1"][ok1]),
+                _spread(a["score2"][ok2], b["score2"][ok2]), _spread(a["fitness2"][ok2], b["fitness2"][ok2]))
+    s_final = max(_spread(a[k], b[k]) for k in ("transformation", "edge_transformation", "fitness_final", "score_final", "edge_fitness",
+                                                "edge_score", "aligned_lines", "base_fitness", "base_score"))
+    return np.nonzero(un1)[0], np.nonzero(un2)[0], s_hyp, s_final
+
+
+def margins(r):
+    """(phase 0, phase 1): the winner's score minus the best other surviving score of its phase with a different transform and minus
+    the score it had to beat; with no winner, the score to beat minus the best surviving score.  inf when there is nothing to compare."""
+    out = []
+    for w, score, surv, rot, tr, start in ((r["winner_edge"], r["score1"], r["survivors1"], r["rotation1"], r["translation1"], r["base_score"]),
+                                           (r["winner_line"], r["score2"], r["survivors2"], r["rotation2"], r["translation2"], r["edge_score"])):
+        sc = score[surv]
+        if w >= 0:
+            other = np.any(rot[surv] != rot[w], axis=1) | np.any(tr[surv] != tr[w], axis=1)
+            sc = sc[other]
+            sc = sc[~np.isnan(sc)]
+            out.append(float(min(score[w] - start, score[w] - sc.max() if sc.size else np.inf)))
+        else:
+            sc = sc[~np.isnan(sc)]
+            with np.errstate(all="ignore"):
+                m = float(start - sc.max()) if sc.size else np.inf
+            out.append(np.inf if np.isnan(m) else m)                  # NaN or equal infinities: no comparison can come out true
+    return out
+
+
+# ---- scenes ----------------------------------------------------------------------------------------------------------------------
+def staircase(n_edges, step=1.5, x0=0.0, y0=0.0, stretch=0.0):
+    """n_edges + 1 axis-parallel segments that share their end points: consecutive ones meet in an exact corner (one edge each, kept at
+    max_dist_angular_edge = 0.01), every other perpendicular pair ends at least one step from its intersection (dropped at 0.01 and,
+    beyond four steps, at 7.0).  Binary-exact coordinates."""
+    pts = [(x0, y0)]
+    for k in range(n_edges + 1):
+        x, y = pts[-1]
+        d = (step + 0.375 * ((7 * k) % 5)) * (1.0 + stretch * k)   # uneven steps: no two target lines are equally far from a source line
+        pts.append((x + d, y) if k % 2 == 0 else (x, y + d))
+    return np.array([R.seg(*pts[k], *pts[k + 1]) for k in range(n_edges + 1)], np.float64) if n_edges > 0 else np.zeros((0, 2, 3))
+
+
+def stairs_item(es, et, motion=(0.3, -0.2, 2.0), step=8.0):
+    """An item with exactly es x et edge pairs: steps longer than 7 m leave the target side only its consecutive corners too.  The source
+    lines end 4 mm short of their corners (kept at 0.01) and the target lines 5 cm: an aligned source end then lies 4.6 cm beyond the end
+    of its target line, so that no is_point_on_line decision sits on a rounding error.  The target's steps grow by 1/256 per step: every
+    corner pair leaves the other corners a different residual, so the winner among them is decided by far more than rounding."""
+    return R.trim(staircase(es, step), 0.004), R.move(R.trim(staircase(et, step, stretch=1.0 / 256), 0.05), motion[0], motion[1], np.deg2rad(motion[2]))
+
+
+_CACHE = {}
+BOX = R.rectangle(0.0, 0.0, 10.0, 6.0)
+ELL = BOX[:2]                                                # two walls that meet in an exact corner
+ELL_T = R.trim(ELL, 0.05)                                    # the same seen as a target: its lines end 5 cm short of the corner
+
+
+def scenes():
+    """name -> (source lines, target lines, keyword arguments of align_local)"""
+    if "scenes" in _CACHE:
+        return _CACHE["scenes"]
+    sc = {}
+    sc["empty_source"] = (np.zeros((0, 2, 3)), BOX, {})
+    sc["one_line_each"] = (np.array([R.seg(0, 0, 5, 0)], np.float64), np.array([R.seg(0.2, 0.3, 5.2, 0.35)], np.float64), {})
+    far = np.array([R.seg(-4, 9, -4, 14), R.seg(12, -9, 17, -9), R.seg(-8, -7, -8, -1)], np.float64)
+    ell = R.move(ELL_T, 0.3, 0.2, np.deg2rad(2.0))
+    for name, trg in (("two_targets", ell), ("three_targets", np.concatenate([ell, far[:1]])), ("five_targets", np.concatenate([ell, far]))):
+        sc[name] = (ELL, trg, {})
+        sc[name + "_three"] = (ELL, trg, dict(params=dict(refine_three_nearest=1)))
+    sc["corner"] = (BOX, R.move(ELL_T, 0.4, 0.25, np.deg2rad(3.0)), {})
+    short = R.trim(BOX, 0.02)                                 # lines that end 0.02 m short of their corners
+    sc["angular_dist"] = (short, R.move(short, 0.2, 0.1, np.deg2rad(1.0)), {})
+    cross = np.array([R.seg(-3, 0, 4, 0), R.seg(0, -2, 0, 5)], np.float64)
+    sc["case4_crossing"] = (cross, R.move(cross, 0.3, 0.2, np.deg2rad(2.0)), {})
+    sc["local_range"] = (np.array([R.seg(0.5, 0.49, 4.5, 0.49), R.seg(0.5, 10.51, 4.5, 10.51), R.seg(5.05, 0.02, 5.25, 0.02)], np.float64),
+                         np.array([R.seg(0, 0, 5, 0), R.seg(0, 10, 5, 10), R.seg(20, 0, 20, 5)], np.float64), {})
+    # the target holds the source's own corner (the identity, which align_global's identity gate would drop) and copies of it 2.4 m and
+    # 2.6 m away
+    sc["distance_gate"] = (ELL, np.concatenate([ELL_T, R.move(ELL_T, 0.0, -2.4, 0.0), R.move(ELL_T, 2.6, 0.0, 0.0)]), {})
+    sc["angle_gate"] = (ELL, np.concatenate([ELL_T, R.move(ELL_T, 0.1, 0.1, np.deg2rad(19.0)), R.move(ELL_T, 0.2, 0.1, np.deg2rad(21.0))]), {})
+    par = np.array([R.seg(0, 0, 6, 0), R.seg(1, 4, 7, 4)], np.float64)
+    sc["refine_only"] = (par, R.move(par, 0.1, 0.3, np.deg2rad(1.0)), {})
+    sc["refine_rank"] = (np.array([R.seg(2.9, 0, 3.1, 0)], np.float64), np.array([R.seg(3.0, 0.05, 3.0, 0.25), R.seg(0, 0.3, 6, 0.3)], np.float64), {})
+    bent = R.move(ELL_T, 0.4, 0.25, np.deg2rad(3.0))
+    bent[1] = R.move(bent[1:2], 0.15, 0.0, np.deg2rad(1.5))[0]
+    sc["refine_on_winner"] = (BOX, bent, {})
+    src, trg, _ = R.scenes()["ties"]
+    off, src = src, src.copy()
+    src[..., 0] += 1.5                                       # the design geometry itself: S0 is 2.5 from T0 and from T1 bit for bit, with
+    src[..., 1] += 0.75                                      # different records, in the baseline's pick and in the line pairs' ranks
+    sc["rank_ties"] = (src, trg, dict(max_range=3.0))
+    sc["rank_ties_high"] = (src, trg, dict(max_range=3.0, params=dict(nn_tie_highest_index=1)))
+    # off the walls by (-1.5, -0.75) the baseline scores -inf under an infinite distance weight and the line pairs that put a line on
+    # its wall score NaN; with an infinite coverage weight and nothing in range the baseline itself is NaN
+    sc["nan_scores"] = (off[1:4], trg, dict(max_range=3.0, params=dict(l_avg_distance_weight=np.inf)))
+    sc["nan_baseline"] = (off[1:4], trg, dict(max_range=0.001, params=dict(l_coverage_weight=np.inf)))
+    _CACHE["scenes"] = sc
+    return sc
+
+
+# batch_mixed: 33 items under the default parameters and max_range 0.5.  Edge-pair counts 0, 1, 63, 64, 65, 255, 256, 257 and more;
+# empty items first, last and in the middle.
+BATCH_STAIRS = [(1, 1), (7, 9), (2, 5), (8, 8), (5, 13), (2, 2), (15, 17), (4, 3), (16, 16), (1, 257), (6, 1), (3, 3), (9, 2), (2, 7), (5, 5),
+                (1, 3), (4, 4), (11, 3)]
+BATCH_NAMED = ["corner", "one_line_each", "two_targets", "angular_dist", "case4_crossing", "local_range", "distance_gate", "angle_gate",
+               "refine_only", "refine_rank", "refine_on_winner", "three_targets"]
+
+
+def batch_mixed():
+    if "batch" in _CACHE:
+        return _CACHE["batch"]
+    sc = scenes()
+    empty = (np.zeros((0, 2, 3)), np.zeros((0, 2, 3)))
+    named = [sc[n][:2] for n in BATCH_NAMED]
+    stairs = [stairs_item(a, b, motion=(0.3 + 0.01 * k, -0.2, 2.0 - 0.1 * k)) for k, (a, b) in enumerate(BATCH_STAIRS)]
+    seq = []
+    for k in range(max(len(named), len(stairs))):
+        seq += stairs[k:k + 1] + named[k:k + 1]
+    items = [empty] + seq[:15] + [(np.zeros((0, 2, 3)), BOX)] + seq[15:] + [empty]
+    assert len(items) == 33
+    _CACHE["batch"] = items
+    return items
+
+
+def cached(key, src, trg, params=None, max_range=0.5, seed=None):
+    """align_local's result, computed once per key and shared between tests (read-only)."""
+    k = (key, seed)
+    if k not in _CACHE:
+        _CACHE[k] = align_local(src, trg, params, max_range, seed)
+    return _CACHE[k]
+
+
+def scene_result(name, seed=None):
+    src, trg, kw = scenes()[name]
+    return cached(name, src, trg, kw.get("params"), kw.get("max_range", 0.5), seed)
+
+
+def batch_result(b, seed=None):
+    src, trg = batch_mixed()[b]
+    return cached(("batch", b), src, trg, None, 0.5, seed)
+
+
+# ---- the file format of tests/cpp/line_align_local_driver.cpp ---------------------------------------------------------------------------
+def feature_lines(arr):
+    """[L, 2, 3] -> LineFeature objects with distinct statistics"""
+    from delta_graph_slam_amd.line_extraction import LineFeature
+    return [LineFeature(np.array(l[0], np.float64), np.array(l[1], np.float64), 0.1 * k, 0.2, 0.3, 0.0) for k, l in enumerate(arr)]
+
+
+def write_items(path, items):
+    so = np.cumsum([0] + [s.shape[0] for s, _ in items]).astype(np.int64)
+    to = np.cumsum([0] + [t.shape[0] for _, t in items]).astype(np.int64)
+    with open(path, "wb") as f:
+        np.array([len(items)], np.int64).tofile(f)
+        so.tofile(f)
+        to.tofile(f)
+        for k in (0, 1):
+            for it in items:
+                np.asarray(it[k], np.float64).tofile(f)
