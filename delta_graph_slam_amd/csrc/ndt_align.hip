@@ -731,9 +731,10 @@ template <bool WAVE>
 __device__ __forceinline__ void trig6(const double* ang, double* sn, double* cs) {
   if (WAVE) {
     const int lane = threadIdx.x & 63;
-    double a = ang[0];
-#pragma unroll
-    for (int k = 1; k < 6; k++) a = (lane == k) ? ang[k] : a;
+    // the six angles as values, chosen by selects: chosen by index, `ang` is a stack array read at a per-lane offset (48 B of scratch per lane
+    // in every kernel that inlines this)
+    const double a0 = ang[0], a1 = ang[1], a2 = ang[2], a3 = ang[3], a4 = ang[4], a5 = ang[5];
+    const double a = (lane == 5) ? a5 : (lane == 4) ? a4 : (lane == 3) ? a3 : (lane == 2) ? a2 : (lane == 1) ? a1 : a0;
     double sv, cv;
     sincos(a, &sv, &cv);
 #pragma unroll

@@ -906,7 +906,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   const int n_slices = FIXED ? strict_slices_of(n, cap_blocks) : blocks_per_pair;   // (FIXED: its own instantiation -- as a run-time switch the default path lost 5 %)
   if (!solver && slice == 0 && threadIdx.x == 0) pair_blocks[pair] = n_slices;
   const int kind = WITH_HD ? st.need_hessian : (st.need_hessian != 0 ? 1 : 0);
-  const float gd2 = (float)gauss_d2;
+  const float gd2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)gauss_d2)));   // the conversion is a VALU operation: back to an SGPR
   float T[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) T[k] = st.T[k];
@@ -925,7 +925,9 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   __syncthreads();
   const unsigned long long* __restrict__ exptab = s_exp2f;   // this kernel serves consts.exp_libm = 1 only (strict_kernel_version, ndt_align.hip)
   const unsigned long long* __restrict__ exptab_d = kGlibcExpTab;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the wave's number as a scalar: its LDS regions' bases, its first point and the tile loop's counter then live in SGPRs, and a per-lane address
+  // is base + lane offset at its use -- as per-lane values they were VGPRs live across the item loops, which the allocator spilled at 256
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   float* tf = reinterpret_cast<float*>(s_tab[wave]);            // float kinds: [20][PTS], then the record ring
   float4* ring = reinterpret_cast<float4*>(s_tab[wave] + TL::kRingOffset);
   double* td = reinterpret_cast<double*>(s_tab[wave]);          // double pass: [23][PTS_HD] doubles, then [3][PTS_HD] floats
@@ -957,8 +959,8 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
     if (lane == 0) __hip_atomic_store(&pairs[pair].spec_result, same ? 1 : 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_wave_barrier();
   }
-  const int subs = pts / 64;
-  const int stride = n_slices * kBlock;
+  const int subs = __builtin_amdgcn_readfirstlane(pts / 64);
+  const int stride = __builtin_amdgcn_readfirstlane(n_slices * kBlock);
   static_assert(TL::kTableBytes >= kStrictRowScratch * 8, "the wave's table region doubles as its reduction scratch");
   // this workgroup's slices q = slice, slice + blocks_per_pair, ...: each its own sums and its own row
   __shared__ double s_cols[FIXED ? kStrictSlots : 1][FIXED ? kBlock / kWave : 1][FIXED ? kStrictPad : 1];
