@@ -371,8 +371,14 @@ __device__ __forceinline__ void strict_point(const float4 x, const float (&xt)[3
 // ---- kind 2: computeHessian / updateHessian in PCL's double form, ONE (point, voxel) item.
 // xj / xh: the point's products with the DOUBLE angle vectors.  Returns false when the voxel's weight fails upstream's test.
 // ROWS = false: the 36 terms are added to acc[7 ..]; ROWS = true (ndt_strict_order 2): written to rows[entry * row_stride].
-template <bool ROWS>
-__device__ __forceinline__ bool strict_item_hd(const float (&xt)[3], const double (&xj)[8], const double (&xh)[15], const double* __restrict__ rec,
+// rec: the voxel's vtab row -- mean[3], icov[9] -- as a pointer into vtab or, for the loop that brings the rows in ahead of time
+// (strict_items_hd), as the twelve values (StrictHdRow); the same code either way.
+struct StrictHdRow {
+  double v[12];
+  __device__ __forceinline__ double operator[](const int i) const { return v[i]; }
+};
+template <bool ROWS, class REC>
+__device__ __forceinline__ bool strict_item_hd_rec(const float (&xt)[3], const double (&xj)[8], const double (&xh)[15], const REC rec,
                                                const double gauss_d1, const double gauss_d2, double (&acc)[kStrictAccum], double* __restrict__ rows, const size_t row_stride,
                                                const unsigned long long* __restrict__ exptab_d) {
   const double pg13 = xj[0], pg23 = xj[1];
@@ -432,6 +438,19 @@ __device__ __forceinline__ bool strict_item_hd(const float (&xt)[3], const doubl
     }
   }
   return true;
+}
+
+template <bool ROWS>
+__device__ __forceinline__ bool strict_item_hd(const float (&xt)[3], const double (&xj)[8], const double (&xh)[15], const double* __restrict__ rec,
+                                               const double gauss_d1, const double gauss_d2, double (&acc)[kStrictAccum], double* __restrict__ rows, const size_t row_stride,
+                                               const unsigned long long* __restrict__ exptab_d) {
+  return strict_item_hd_rec<ROWS, const double* __restrict__>(xt, xj, xh, rec, gauss_d1, gauss_d2, acc, rows, row_stride, exptab_d);
+}
+template <bool ROWS>
+__device__ __forceinline__ bool strict_item_hd(const float (&xt)[3], const double (&xj)[8], const double (&xh)[15], const StrictHdRow& row,
+                                               const double gauss_d1, const double gauss_d2, double (&acc)[kStrictAccum], double* __restrict__ rows, const size_t row_stride,
+                                               const unsigned long long* __restrict__ exptab_d) {
+  return strict_item_hd_rec<ROWS, const StrictHdRow&>(xt, xj, xh, row, gauss_d1, gauss_d2, acc, rows, row_stride, exptab_d);
 }
 
 __device__ __forceinline__ void strict_point_tables_hd(const float4 xf, const NdtPair& st, double (&xj)[8], double (&xh)[15]) {
@@ -841,6 +860,86 @@ __device__ __forceinline__ void strict_items_float(const float* __restrict__ tf,
 #endif
 }
 
+// The double pass's point table.  As stored by the plain loop: 23 double fields, xj[8] and xh[15], and the three floats of xt.  With the
+// ring: 17 -- xh[0..5] are xj entries or their negations here too (-xj1, xj0, -xj4, xj3, -xj7, xj6): write_evaluation forms hang_d rows
+// 0..5 from the expressions of jang_d rows 1, 0, 4, 3, 7, 6 or their negations, term by term, every operation rounded on its own (no
+// contraction below the optimiser), and strict_point_tables_hd multiplies both the same way; rounding is symmetric, so the products are
+// the same bits or their negations.  (A sum that cancels to an exact zero would carry the other sign of zero: x * 0.0 terms and sums of
+// opposite terms give +0 either way.  Such a zero is multiplied and added to non-zero terms downstream and leaves no bit behind.)
+constexpr int kStrictHdFields = 17;
+template <int FIELDS, int PTS>
+__device__ __forceinline__ void strict_table_read_hd(const double* __restrict__ td, const float* __restrict__ tdx, const int slot, float (&xt)[3], double (&xj)[8],
+                                                     double (&xh)[15]) {
+#pragma unroll
+  for (int f = 0; f < 8; f++) xj[f] = td[f * PTS + slot];
+  if (FIELDS == kStrictHdFields) {
+    xh[0] = -xj[1]; xh[1] = xj[0]; xh[2] = -xj[4]; xh[3] = xj[3]; xh[4] = -xj[7]; xh[5] = xj[6];
+#pragma unroll
+    for (int f = 6; f < 15; f++) xh[f] = td[(2 + f) * PTS + slot];
+  } else {
+#pragma unroll
+    for (int f = 0; f < 15; f++) xh[f] = td[(8 + f) * PTS + slot];
+  }
+#pragma unroll
+  for (int f = 0; f < 3; f++) xt[f] = tdx[f * PTS + slot];
+}
+
+// The double pass's items of one tile, 64 per round, lane <-> item: strict_items_float's ring loop for the 96-byte vtab rows.  Six 16-byte
+// LDS-DMA loads per lane bring the NEXT round's rows into the wave's ring -- words 0..4 at ring[k * 64 + lane], word 5 at ring5[lane] -- while
+// this round's items run.  The buffer form of the load (buffer_load_dwordx4 ... lds): vtab's base sits in the descriptor's SGPRs and a lane
+// gives a 32-bit byte offset, one VGPR instead of an address pair, in a loop that lives at 256 VGPRs.  The word's offset goes in as the scalar
+// offset, which moves the memory address alone.  Same items on the same lanes, the same strict_item_hd on the same twelve doubles.
+// A/B build `make ab AB=-DDGS_STRICT_HD_ITEMS=0`: the 23-field table and the plain loop, the row gathered from L2 where it is used.
+#ifndef DGS_STRICT_HD_ITEMS
+#define DGS_STRICT_HD_ITEMS 1
+#endif
+__device__ __forceinline__ void strict_row_dma(float4* ring, float4* ring5, const __amdgpu_buffer_rsrc_t vrows, const unsigned vid) {
+  // a queue entry keeps 25 bits of voxel number, and this kernel is launched only for models of fewer than 2^25 voxels
+  // (n_occupied_bound < (1 << 25), ndt_align.hip): the last byte of the last row stays inside the 32-bit offset
+  static_assert((0x1FFFFFFull + 1) * 96 <= 0xFFFFFFFFull, "a vtab row's byte offset in 32 bits");
+  const int off = (int)(vid * 96u);
+  typedef __attribute__((address_space(3))) void* lds_t;
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(vrows, (lds_t)(ring), 16, off, 0, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(vrows, (lds_t)(ring + 64), 16, off, 16, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(vrows, (lds_t)(ring + 128), 16, off, 32, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(vrows, (lds_t)(ring + 192), 16, off, 48, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(vrows, (lds_t)(ring + 256), 16, off, 64, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(vrows, (lds_t)(ring5), 16, off, 80, 0, 0);
+}
+template <int PTS>
+__device__ __forceinline__ void strict_items_hd(const double* __restrict__ td, const float* __restrict__ tdx, float4* ring, float4* ring5, const unsigned* __restrict__ queue,
+                                                const int qn, const int lane, const double* __restrict__ vtab, const double gauss_d1, const double gauss_d2,
+                                                double (&acc)[kStrictAccum], const unsigned long long* __restrict__ exptab_d) {
+  // a raw buffer over the whole 32-bit offset range: a lane's offset is a valid row of vtab as the plain loop's pointer is
+  const __amdgpu_buffer_rsrc_t vrows = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(vtab), 0, -1, 0x00020000);
+  if (lane < qn) strict_row_dma(ring, ring5, vrows, queue[lane] & 0x1FFFFFFu);
+#pragma unroll 1
+  for (int h = 0; h < qn; h += 64) {
+    const int idx = h + lane, idx_n = idx + 64;
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this round's rows are in the ring
+    StrictHdRow row;
+    unsigned entry = 0, entry_n = 0;
+    if (idx < qn) {
+      entry = queue[idx];
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        const double2 w = *reinterpret_cast<const double2*>((k < 5) ? ring + k * 64 + lane : ring5 + lane);
+        row.v[2 * k] = w.x;
+        row.v[2 * k + 1] = w.y;
+      }
+    }
+    if (idx_n < qn) entry_n = queue[idx_n];
+    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the ring has been read before the next round's DMA overwrites it
+    if (idx_n < qn) strict_row_dma(ring, ring5, vrows, entry_n & 0x1FFFFFFu);
+    if (idx < qn) {
+      float xt[3];
+      double xj[8], xh[15];
+      strict_table_read_hd<kStrictHdFields, PTS>(td, tdx, (int)(entry >> 25), xt, xj, xh);
+      (void)strict_item_hd<false>(xt, xj, xh, row, gauss_d1, gauss_d2, acc, nullptr, 0, exptab_d);
+    }
+  }
+}
+
 template <int SEARCH, bool WITH_HD, bool RING>
 struct StrictTile {
   static constexpr int NB = Offsets<SEARCH>::N;
@@ -851,8 +950,17 @@ struct StrictTile {
   static constexpr int PTS_HD = 64;                  // double pass: 23 doubles + 3 floats per point
   static constexpr int kRingOffset = kStrictFields * PTS * 4;   // float kinds: the point table, then the record ring
   static constexpr int kFloatBytes = kRingOffset + (RING ? kStrictRingBytes : 0);
-  static constexpr int kTableBytes = (!WITH_HD || kFloatBytes > (23 * 8 + 3 * 4) * PTS_HD) ? kFloatBytes : (23 * 8 + 3 * 4) * PTS_HD;
   static constexpr int kQueue = PTS * NB;            // items of a tile at most
+  // The double pass with its vtab rows through the ring (strict_items_hd): 17 double fields in the table region, then five of the row's six
+  // 1-KiB ring words; the sixth word and the three float fields of xt behind the double pass's queue entries -- its tile is PTS_HD points,
+  // so of the queue's PTS * NB entries it fills PTS_HD * NB.  Taken only where all of that fits what the float kinds reserve anyway
+  // (DIRECT7: 8,704 + 5,120 of 14,336 B and 1,792 + 1,024 + 768 of 3,584 B); elsewhere the 23-field table and the plain loop.
+  static constexpr int kHdQueueBytes = PTS_HD * NB * 4;
+  static constexpr bool kHdRing = RING && WITH_HD && DGS_STRICT_HD_ITEMS != 0 && kStrictHdFields * 8 * PTS_HD + 5 * 1024 <= kFloatBytes &&
+                                  kHdQueueBytes % 16 == 0 && kHdQueueBytes + 1024 + 3 * 4 * PTS_HD <= kQueue * 4;
+  static constexpr int kHdFields = kHdRing ? kStrictHdFields : 23;
+  static constexpr int kHdBytes = kHdRing ? kStrictHdFields * 8 * PTS_HD + 5 * 1024 : (23 * 8 + 3 * 4) * PTS_HD;
+  static constexpr int kTableBytes = (!WITH_HD || kFloatBytes > kHdBytes) ? kFloatBytes : kHdBytes;
 };
 
 // DGS_NDT_FIXED_SLICES=1 (dgs_handle::ndt_fixed_slices; off by default): the slices of a pair as a function of its OWN point count -- 512 points
@@ -915,7 +1023,9 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   for (int k = 0; k < kStrictAccum; k++) acc[k] = 0.0;
 
   __shared__ __attribute__((aligned(16))) unsigned char s_tab[kBlock / kWave][TL::kTableBytes];
-  __shared__ unsigned s_queue[kBlock / kWave][TL::kQueue];
+  __shared__ __attribute__((aligned(16))) unsigned s_queue[kBlock / kWave][TL::kQueue];
+  static_assert(!TL::kHdRing || TL::kTableBytes == TL::kFloatBytes, "the double pass's ring lives in what the float kinds reserve: no more LDS than without it");
+  static_assert(SEARCH != 2 || !WITH_HD || FIXED || sizeof(s_tab) + sizeof(s_queue) == 4 * (14336 + 3584), "the timed instantiation: 78,208 B of LDS per workgroup in all");
   // glibc's 2^(i/32) table in LDS: the item loop looks it up per lane (an LDS read instead of a gather through the vector cache).  Measured
   // alternatives on the bench step, same box: one copy per wave written by the wave itself, no workgroup barrier: 5.45-5.46 ms against 5.37-5.39
   // for this shared copy; the double pass's 2 x 128 table in LDS as well: 5.37 / 3.342 against 5.38 / 3.342 ms (bench step / 8 x 200,000
@@ -930,9 +1040,14 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   float* tf = reinterpret_cast<float*>(s_tab[wave]);            // float kinds: [20][PTS], then the record ring
   float4* ring = reinterpret_cast<float4*>(s_tab[wave] + TL::kRingOffset);
-  double* td = reinterpret_cast<double*>(s_tab[wave]);          // double pass: [23][PTS_HD] doubles, then [3][PTS_HD] floats
-  float* tdx = reinterpret_cast<float*>(s_tab[wave] + 23 * 8 * TL::PTS_HD);
   unsigned* queue = s_queue[wave];
+  // double pass: [23][PTS_HD] doubles, then [3][PTS_HD] floats; with the row ring (TL::kHdRing) [17][PTS_HD] doubles, ring words 0..4, and
+  // behind the queue entries of a PTS_HD-point tile ring word 5 and the [3][PTS_HD] floats
+  double* td = reinterpret_cast<double*>(s_tab[wave]);
+  float4* ring_hd = reinterpret_cast<float4*>(s_tab[wave] + TL::kHdFields * 8 * TL::PTS_HD);
+  float4* ring_hd5 = reinterpret_cast<float4*>(reinterpret_cast<unsigned char*>(queue) + TL::kHdQueueBytes);
+  float* tdx = TL::kHdRing ? reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(queue) + TL::kHdQueueBytes + 1024)
+                           : reinterpret_cast<float*>(s_tab[wave] + 23 * 8 * TL::PTS_HD);
   // wave-uniform.  (Keeping it opaque to the optimiser -- asm volatile("" : "+s"(pts)) -- takes the kernel from 256 VGPRs + 4 spilled to 239
   // without spills, and the step from 6.25 to 6.6 ms: the loops specialised per tile size are worth more than the registers.)
   const int pts = (WITH_HD && kind == 2) ? TL::PTS_HD : TL::PTS;
@@ -994,7 +1109,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
 #pragma unroll
             for (int f = 0; f < 8; f++) td[f * TL::PTS_HD + slot] = xj[f];
 #pragma unroll
-            for (int f = 0; f < 15; f++) td[(8 + f) * TL::PTS_HD + slot] = xh[f];
+            for (int f = TL::kHdRing ? 6 : 0; f < 15; f++) td[(TL::kHdFields - 15 + f) * TL::PTS_HD + slot] = xh[f];   // ring: xh[0..5] rebuilt from xj
 #pragma unroll
             for (int f = 0; f < 3; f++) tdx[f * TL::PTS_HD + slot] = xt[f];
           } else {
@@ -1033,6 +1148,10 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
       qn = 0;
     }
 #endif
+    if (TL::kHdRing && kind == 2) {
+      strict_items_hd<TL::PTS_HD>(td, tdx, ring_hd, ring_hd5, queue, qn, lane, vtab, gauss_d1, gauss_d2, acc, exptab_d);
+      qn = 0;
+    }
 #pragma unroll 1
     for (int h = 0; h < qn; h += 64) {
       const int idx = h + lane;
@@ -1042,12 +1161,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
         if (WITH_HD && kind == 2) {
           double xj[8], xh[15];
           float xt[3];
-#pragma unroll
-          for (int f = 0; f < 8; f++) xj[f] = td[f * TL::PTS_HD + slot];
-#pragma unroll
-          for (int f = 0; f < 15; f++) xh[f] = td[(8 + f) * TL::PTS_HD + slot];
-#pragma unroll
-          for (int f = 0; f < 3; f++) xt[f] = tdx[f * TL::PTS_HD + slot];
+          strict_table_read_hd<23, TL::PTS_HD>(td, tdx, slot, xt, xj, xh);
           (void)strict_item_hd<false>(xt, xj, xh, vtab + (size_t)vid * 12, gauss_d1, gauss_d2, acc, nullptr, 0, exptab_d);
         } else {
           float xt[3], xj[8], xh[15];
