@@ -1,5 +1,6 @@
 // ndt_strict_order = 1 (UPSTREAM): computeDerivatives / updateDerivatives in upstream's own operation order, as ONE launch per
-// evaluation (derivatives + the pair's optimiser step in its closing workgroup).  Included by ndt_align.hip below the optimiser.
+// evaluation (derivatives + the pair's optimiser step in its closing workgroup).  Included by ndt_align.hip below ndt_optimiser.h (it calls ndt_advance,
+// write_evaluation and begin_iteration) and ndt_exp_tables.h; Offsets / neighbour_offset come from ndt_fast.h.
 //
 // What the mode promises (include/dgs_reg.h): every FLOAT operation of upstream's per-voxel update -- the CPU
 // checker states the same sequence -- individually rounded, in upstream's order; the float increments are
@@ -155,11 +156,6 @@ __device__ __forceinline__ int strict_pick(const int (&vids)[NB], const int k) {
 
 // ---- kinds 0 / 1: updateDerivatives in float for ONE (point, voxel) item; acc = [score, g 0..5, H 0..35 row-major].
 // xt: the transformed point; xj / xh: the point's 8 + 15 products with the angle tables (computePointDerivatives).
-// Two halves, so that the item-compacted kernel can issue the NEXT item's voxel record between them (the Hessian block behind covers its L2 latency):
-// front = Mahalanobis term, exp, the weight test, gradient increments, the x^T C H vectors; back = the 36 Hessian increments and the score.
-struct StrictMid {
-  float C[3][3], cPG[3][3], g6[6], xch[6], e, score_inc;
-};
 
 // the 64-byte voxel record as four 16-byte words: mean (3 doubles), then the 9 floats of float(icov) row-major, one pad
 struct StrictRecWords {
@@ -170,85 +166,10 @@ __device__ __forceinline__ StrictRecWords strict_load_rec(const VoxelStrictRec* 
   return StrictRecWords{r4[0], r4[1], r4[2], r4[3]};
 }
 
-template <bool NEED_H, bool GLIBC_ONLY = false>
-__device__ __forceinline__ bool strict_item_front(const float (&xt)[3], const float (&xj)[8], const float (&xh)[15], const StrictRecWords& w,
-                                                  const double gauss_d1, const float gd2, double (&acc)[kStrictAccum], StrictMid& m,
-                                                  const unsigned long long* __restrict__ exptab) {
-  const float pg13 = xj[0], pg23 = xj[1];
-  const float pg4[3] = {xj[2], xj[3], xj[4]}, pg5[3] = {xj[5], xj[6], xj[7]};
-  const float4 ra = w.a, rb = w.b, rc = w.c, rd = w.d;
-  const double m0 = __hiloint2double(__float_as_int(ra.y), __float_as_int(ra.x)), m1 = __hiloint2double(__float_as_int(ra.w), __float_as_int(ra.z)),
-               m2 = __hiloint2double(__float_as_int(rb.y), __float_as_int(rb.x));
-  const float q0 = (float)((double)xt[0] - m0), q1 = (float)((double)xt[1] - m1), q2 = (float)((double)xt[2] - m2);
-  m.C[0][0] = rb.z; m.C[0][1] = rb.w; m.C[0][2] = rc.x;
-  m.C[1][0] = rc.y; m.C[1][1] = rc.z; m.C[1][2] = rc.w;
-  m.C[2][0] = rd.x; m.C[2][1] = rd.y; m.C[2][2] = rd.z;
-  float qC[3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) qC[c] = q0 * m.C[0][c] + q1 * m.C[1][c] + q2 * m.C[2][c];
-  const float e_arg = -gd2 * (q0 * qC[0] + q1 * qC[1] + q2 * qC[2]) * 0.5f;
-  float e = (GLIBC_ONLY || exptab) ? glibc_expf_dev(e_arg, exptab) : det_expf(e_arg);   // std::exp(float) as glibc computes it / rounds 1-3's polynomial (NdtConsts::exp_libm)
-  m.score_inc = (float)(-gauss_d1 * (double)e);
-  e = gd2 * e;
-  if (e > 1 || e < 0 || e != e) return false;
-  m.e = (float)((double)e * gauss_d1);
-  // C * point gradient: columns 0..2 are C itself (unit columns), column 3 has a zero first factor
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    m.cPG[r][0] = m.C[r][1] * pg13 + m.C[r][2] * pg23;
-    m.cPG[r][1] = m.C[r][0] * pg4[0] + m.C[r][1] * pg4[1] + m.C[r][2] * pg4[2];
-    m.cPG[r][2] = m.C[r][0] * pg5[0] + m.C[r][1] * pg5[1] + m.C[r][2] * pg5[2];
-  }
-  m.g6[0] = qC[0]; m.g6[1] = qC[1]; m.g6[2] = qC[2];   // q^T (C * unit column) is q^T C: the same operations
-#pragma unroll
-  for (int c = 0; c < 3; c++) m.g6[3 + c] = q0 * m.cPG[0][c] + q1 * m.cPG[1][c] + q2 * m.cPG[2][c];
-#pragma unroll
-  for (int c = 0; c < 6; c++) acc[1 + c] += (double)(m.e * m.g6[c]);
-  if (NEED_H) {
-    // x^T C H for the six distinct vectors: a = (0, xh0, xh1) b = (0, xh2, xh3) c = (0, xh4, xh5) d = xh6..8 e = xh9..11 f = xh12..14
-    m.xch[0] = qC[1] * xh[0] + qC[2] * xh[1];
-    m.xch[1] = qC[1] * xh[2] + qC[2] * xh[3];
-    m.xch[2] = qC[1] * xh[4] + qC[2] * xh[5];
-    m.xch[3] = qC[0] * xh[6] + qC[1] * xh[7] + qC[2] * xh[8];
-    m.xch[4] = qC[0] * xh[9] + qC[1] * xh[10] + qC[2] * xh[11];
-    m.xch[5] = qC[0] * xh[12] + qC[1] * xh[13] + qC[2] * xh[14];
-  }
-  return true;
-}
-
 // (A packed-FP32 form of this block -- v_pk_mul_f32 / v_pk_add_f32, entries (i, 2m) and (i, 2m + 1) of a row in one instruction, 383 -> 320
 //  instructions, bit-identical -- measured 5.25-5.28 ms on the bench step against 5.22 for this scalar form and was removed: the item loop was
 //  not bound by issue slots.)
-template <bool NEED_H>
-__device__ __forceinline__ void strict_item_back(const float (&xj)[8], const StrictMid& m, const float gd2, double (&acc)[kStrictAccum]) {
-  if (NEED_H) {
-    const float pg13 = xj[0], pg23 = xj[1];
-    const float pg4[3] = {xj[2], xj[3], xj[4]}, pg5[3] = {xj[5], xj[6], xj[7]};
-    // full C * J (3 x 6) as a lookup: column i < 3 -> C[r][i], else cPG[r][i - 3]
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-      const float ng = -gd2 * m.g6[i];
-      const float cj0 = (i < 3) ? m.C[0][i < 3 ? i : 0] : m.cPG[0][i < 3 ? 0 : i - 3];
-      const float cj1 = (i < 3) ? m.C[1][i < 3 ? i : 0] : m.cPG[1][i < 3 ? 0 : i - 3];
-      const float cj2 = (i < 3) ? m.C[2][i < 3 ? i : 0] : m.cPG[2][i < 3 ? 0 : i - 3];
-#pragma unroll
-      for (int j = 0; j < 6; j++) {
-        float t = ng * m.g6[j];
-        if (i >= 3 && j >= 3) {
-          const int lo = (i < j ? i : j) - 3, hi = (i < j ? j : i) - 3;
-          t = t + m.xch[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
-        }
-        // J_j^T (C J_i): column j of J is a unit vector for j < 3 and has a zero first entry for j == 3
-        const float pcp = (j == 0) ? cj0 : (j == 1) ? cj1 : (j == 2) ? cj2 : (j == 3) ? (pg13 * cj1 + pg23 * cj2)
-                        : (j == 4) ? (pg4[0] * cj0 + pg4[1] * cj1 + pg4[2] * cj2) : (pg5[0] * cj0 + pg5[1] * cj1 + pg5[2] * cj2);
-        acc[7 + i * 6 + j] += (double)(m.e * (t + pcp));
-      }
-    }
-  }
-  acc[0] += (double)m.score_inc;
-}
-
-// One function, straight line (the front / back halves above are the same operations cut in two for the hand-pipelined A/B build).
+// One function, straight line: Mahalanobis term, exp, the weight test, gradient increments, the x^T C H vectors, the 36 Hessian increments, the score.
 // w: the voxel's record, loaded by the caller (from L2, or from the item loop's LDS ring).
 template <bool NEED_H, bool GLIBC_ONLY = false>
 __device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&xj)[8], const float (&xh)[15], const StrictRecWords& w,
@@ -264,12 +185,9 @@ __device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&
 #pragma unroll
   for (int c = 0; c < 3; c++) qC[c] = q0 * C[0][c] + q1 * C[1][c] + q2 * C[2][c];
   const float e_arg = -gd2 * (q0 * qC[0] + q1 * qC[1] + q2 * qC[2]) * 0.5f;
-#ifdef DGS_AB_DETF   // timing A/B only (`make ab AB=-DDGS_AB_DETF`): the rounds 1-3 polynomial in the item-compacted kernel -- 5.39-5.41 ms per bench step
-                     // against 5.38 with glibc's expf (same box, two runs each): the exact libm exponential costs nothing
-  float e = det_expf(e_arg);
-#else
+  // (Timed with the rounds 1-3 polynomial alone in the item-compacted kernel: 5.39-5.41 ms per bench step against 5.38 with glibc's expf, same box, two
+  //  runs each -- the exact libm exponential costs nothing.  That A/B build is removed; see history.)
   float e = (GLIBC_ONLY || exptab) ? glibc_expf_dev<GLIBC_ONLY>(e_arg, exptab) : det_expf(e_arg);   // std::exp(float) as glibc computes it / rounds 1-3's polynomial
-#endif
   const float score_inc = (float)(-gauss_d1 * (double)e);
   e = gd2 * e;
   if (e > 1 || e < 0 || e != e) return;
@@ -570,13 +488,8 @@ __device__ __forceinline__ void strict_rows_flush(const double (*cols)[kBlock / 
 #else
 #define STRICT_STAMP(k)
 #endif
-#ifdef DGS_STRICT_CLOSE_NOINLINE
-#define DGS_CLOSE_INLINE __noinline__
-#else
-#define DGS_CLOSE_INLINE __forceinline__
-#endif
 template <bool HD, bool ONE_KERNEL = false>
-__device__ DGS_CLOSE_INLINE void ndt_close_strict(NdtPair* st, const double* rows_of_pair, const int blocks_per_pair, const NdtConsts& c, int* done_flag, const int launch,
+__device__ __forceinline__ void ndt_close_strict(NdtPair* st, const double* rows_of_pair, const int blocks_per_pair, const NdtConsts& c, int* done_flag, const int launch,
                                                  const int hd_lag = 1, const bool defer_solve = false, const bool speculate = false) {
   STRICT_STAMP(0)
   __shared__ NdtSolver s_lds;
@@ -783,11 +696,11 @@ __device__ __forceinline__ void strict_rec_dma(float4* ring, const VoxelStrictRe
 // issues round r + 1's DMA and runs round r's items while it is in flight.  Same items on the same lanes, same operations: bit-identical to the
 // plain loop.  RING = false (the fixed-slices instantiations, whose per-slice column sums leave no LDS for the ring at two workgroups per CU):
 // the plain loop.
-// A/B build `make ab AB=-DDGS_STRICT_ITEMS=2`: the plain loop, the record loaded from L2 where it is used.
-// A/B build `make ab AB=-DDGS_STRICT_ITEMS=1`: the loop software-pipelined by hand -- the NEXT round's queue entry read at the top, its voxel record
-// (four 16-byte gathers from L2) requested between the two halves of the current item, the 36-entry Hessian block behind covering the latency.
-// Measured on the bench step (same box, two runs each): 5.65 ms against 5.48 for the plain loop -- the 15 more live registers turn 4 spilled
-// registers into 29 in a kernel that sits at 256; the wave next door on the SIMD was hiding most of that latency already.  Not the default.
+// A/B build `make ab AB=-DDGS_STRICT_ITEMS=2` (any value but 3): the plain loop, the record loaded from L2 where it is used.
+// (Measured and removed, see history: the loop software-pipelined by hand -- the NEXT round's queue entry read at the top, its voxel record (four
+// 16-byte gathers from L2) requested between two halves of the current item, the 36-entry Hessian block behind covering the latency.  On the bench
+// step, same box, two runs each: 5.65 ms against 5.48 for the plain loop -- the 15 more live registers turn 4 spilled registers into 29 in a kernel
+// that sits at 256; the wave next door on the SIMD was hiding most of that latency already.)
 #ifndef DGS_STRICT_ITEMS
 #define DGS_STRICT_ITEMS 3
 #endif
@@ -820,7 +733,7 @@ __device__ __forceinline__ void strict_items_float(const float* __restrict__ tf,
     return;
   }
 #endif
-#if DGS_STRICT_ITEMS != 1   // the plain loop: the record loaded where it is used
+  // the plain loop: the record loaded where it is used
   (void)ring;
 #pragma unroll 1
   for (int h = 0; h < qn; h += 64) {
@@ -832,32 +745,6 @@ __device__ __forceinline__ void strict_items_float(const float* __restrict__ tf,
       strict_item<NEED_H, true>(xt, xj, xh, vs + (entry & 0x1FFFFFFu), gauss_d1, gd2, acc, exptab);
     }
   }
-#else
-  (void)ring;
-  bool have = lane < qn;
-  unsigned entry = have ? queue[lane] : 0u;
-  StrictRecWords w = strict_load_rec(vs + (entry & 0x1FFFFFFu));   // (entry 0: voxel 0, a valid address; its words are not used)
-#pragma unroll 1
-  for (int h = 0; h < qn; h += 64) {
-    const int idx_n = h + 64 + lane;
-    const bool have_n = idx_n < qn;
-    const unsigned entry_n = have_n ? queue[idx_n] : 0u;
-    float xj[8];
-    StrictMid m;
-    bool alive = false;
-    if (have) {
-      float xt[3], xh[15];
-      strict_table_read<NEED_H, PTS>(tf, (int)(entry >> 25), xt, xj, xh);
-      alive = strict_item_front<NEED_H, true>(xt, xj, xh, w, gauss_d1, gd2, acc, m, exptab);
-    }
-    StrictRecWords wn = w;
-    if (have_n) wn = strict_load_rec(vs + (entry_n & 0x1FFFFFFu));
-    if (alive) strict_item_back<NEED_H>(xj, m, gd2, acc);
-    w = wn;
-    entry = entry_n;
-    have = have_n;
-  }
-#endif
 }
 
 // The double pass's point table.  As stored by the plain loop: 23 double fields, xj[8] and xh[15], and the three floats of xt.  With the
@@ -943,10 +830,7 @@ __device__ __forceinline__ void strict_items_hd(const double* __restrict__ td, c
 template <int SEARCH, bool WITH_HD, bool RING>
 struct StrictTile {
   static constexpr int NB = Offsets<SEARCH>::N;
-#ifndef DGS_STRICT_PTS_FLOAT_ONLY
-#define DGS_STRICT_PTS_FLOAT_ONLY 64
-#endif
-  static constexpr int PTS = (NB <= 7) ? (WITH_HD ? 128 : DGS_STRICT_PTS_FLOAT_ONLY) : 64;   // points per wave and tile (float kinds)
+  static constexpr int PTS = (NB <= 7) ? (WITH_HD ? 128 : 64) : 64;   // points per wave and tile (float kinds)
   static constexpr int PTS_HD = 64;                  // double pass: 23 doubles + 3 floats per point
   static constexpr int kRingOffset = kStrictFields * PTS * 4;   // float kinds: the point table, then the record ring
   static constexpr int kFloatBytes = kRingOffset + (RING ? kStrictRingBytes : 0);
@@ -972,10 +856,8 @@ struct StrictTile {
 // the values of a REPEATED trial point, found by the soak at transformation_epsilon = 0.1 -- is closed for free by NdtSolver::trial_x, so it
 // stays an option for callers that need batch-independent bits.
 __device__ __forceinline__ int strict_slices_of(const int n, const int cap_blocks) {
-#ifndef DGS_STRICT_SLICE_PPT
-#define DGS_STRICT_SLICE_PPT 2   // points per thread and slice (A/B: make ab AB=-DDGS_STRICT_SLICE_PPT=8)
-#endif
-  const int by_points = (n + DGS_STRICT_SLICE_PPT * kBlock - 1) / (DGS_STRICT_SLICE_PPT * kBlock), at_least = min(64 * 2 / DGS_STRICT_SLICE_PPT, (n + kBlock - 1) / kBlock);
+  constexpr int kPpt = 2;   // points per thread and slice
+  const int by_points = (n + kPpt * kBlock - 1) / (kPpt * kBlock), at_least = min(64 * 2 / kPpt, (n + kBlock - 1) / kBlock);
   return max(1, min(max(by_points, at_least), cap_blocks));
 }
 
@@ -1138,16 +1020,14 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes have landed
     __builtin_amdgcn_wave_barrier();
-    // ---- the items, 64 at a time.  The float kinds run strict_items_float, a loop specialised per kind (DGS_STRICT_ITEMS = 1, 2, 3); the
-    // loop below serves the double pass -- and, in the A/B build DGS_STRICT_ITEMS = 0, all three kinds with the kind tested per round: that form
-    // has 7 spilled registers instead of 25 and is 1 % SLOWER on the bench step (5.35 against 5.27-5.30 ms, same box, two runs each).
-#if DGS_STRICT_ITEMS != 0
+    // ---- the items, 64 at a time.  The float kinds run strict_items_float, a loop specialised per kind (DGS_STRICT_ITEMS); the
+    // loop below serves the double pass.  (Measured and removed, see history: that loop for all three kinds with the kind tested per round -- 7
+    // spilled registers instead of 25 and 1 % SLOWER on the bench step, 5.35 against 5.27-5.30 ms, same box, two runs each.)
     if (!(WITH_HD && kind == 2)) {
       if (kind == 1) strict_items_float<true, TL::PTS, !FIXED>(tf, ring, queue, qn, lane, vs, gauss_d1, gd2, acc, exptab);
       else strict_items_float<false, TL::PTS, !FIXED>(tf, ring, queue, qn, lane, vs, gauss_d1, gd2, acc, exptab);
       qn = 0;
     }
-#endif
     if (TL::kHdRing && kind == 2) {
       strict_items_hd<TL::PTS_HD>(td, tdx, ring_hd, ring_hd5, queue, qn, lane, vtab, gauss_d1, gauss_d2, acc, exptab_d);
       qn = 0;

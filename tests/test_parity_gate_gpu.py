@@ -9,7 +9,7 @@ north_star's gate is "final pose within 1e-4 m / 1e-5 rad of the reference CPU p
     amplifies that on a few ill-conditioned pairs per shard -- exactly where the oracle's own answer moves by more under perturbations
     that carry no information.  Round 3 asserted that with bounds fitted to the measurement ("measured - 1" pairs, twice the band): a
     regression of the same size would have stayed green.  Now the measurement itself is the assertion: the SET of pairs outside the gate
-    must equal the committed list (tests/golden/fast_order_gate.json, made by scripts/r4_fast_variants.py), every one of them must sit
+    must equal the committed list (tests/golden/fast_order_gate.json, made by scripts/make_fast_order_gate.py), every one of them must sit
     inside ONE times the oracle's own 34-twin band recorded there, the band of the first of them is re-derived here (6 twins, a lower
     bound of the 34), over all other pairs the gate holds pair by pair, and what the caller consumes -- converged flags, the chosen loop
     candidate and its score (loop_detector.hpp:149-155) -- is the reference's.  Any change to the kernel that moves a pair across the
