@@ -1,15 +1,26 @@
-// LineBasedScanmatcher::align_global's scalar pieces (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp), restated once for the host
-// and the device: the kernels of line_align.hip, the host-side merge / edge extraction and the refinement pass all call these functions,
-// so a value computed on either side has the same bits but for the trigonometric functions.  Everything is double and must not be
-// contracted (the including file is built with -ffp-contract=off); the float steps are LineFeature::lenght() and the angle gate's
-// transform3Dto2D chain.  Eigen details recalled from memory are tagged [UPSTREAM-RECALL]; DESIGN.md 6f lists them.
+// LineBasedScanmatcher::align_global's and align_local's pieces (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp), restated once
+// for the host and the device and shared by line_align.hip and line_align_local.hip.  Three sections:
+//   * host and device: the scalar functions.  The kernels, the host-side merge / edge extraction, the refinement pass and la::align_local
+//     all call them, so a value computed on either side has the same bits but for the trigonometric functions.
+//   * device only: the one wave scorer (fitness_wave<LOCAL>, calc_fitness_score on a wavefront) and the wave arg-max both aligners use.
+//   * host only: merge / edge extraction, calc_fitness<LOCAL>, la::align_local, and what both drivers need around the C ABI (feature to
+//     Line, the checks, the packing of the upload).
+// Everything is double and must not be contracted (the including file is built with -ffp-contract=off); the float steps are
+// LineFeature::lenght() and the angle gate's transform3Dto2D chain.  Eigen details recalled from memory are tagged [UPSTREAM-RECALL];
+// DESIGN.md 6f lists them.
 #pragma once
 
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
 #include <vector>
 
+#include "../../include/dgs_reg.h"
+
 #if defined(__HIPCC__)
+#include "common.h"   // kWave
 #define LA_HD __host__ __device__ __forceinline__
 #else
 #define LA_HD inline
@@ -41,7 +52,16 @@ struct Weights {
   double avg_distance_weight, coverage_weight, transform_weight, max_score_distance, max_score_translation;
 };
 
+constexpr int kTableDoubles = 9;   // a target line in the table the scorer reads: A, B, (B - A).normalized()
+
 LA_HD V3 v3(double x, double y, double z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
+LA_HD V3 load3(const double* p) { return v3(p[0], p[1], p[2]); }
+LA_HD void store3(double* p, const V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+LA_HD Edge load_edge(const double* p) { Edge e; e.e = load3(p); e.a = load3(p + 3); e.b = load3(p + 6); return e; }
+// the five doubles kept per hypothesis and per record: the four fitness values and the score
+LA_HD void store_fit(double* o, const Fitness f, const double score) {
+  o[0] = f.real_avg_distance; o[1] = f.avg_distance; o[2] = f.coverage; o[3] = f.coverage_percentage; o[4] = score;
+}
 LA_HD V3 sub(const V3 a, const V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
 LA_HD V3 add(const V3 a, const V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 LA_HD V3 scale(const V3 a, const double s) { return v3(a.x * s, a.y * s, a.z * s); }
@@ -186,13 +206,16 @@ LA_HD bool nn_better(const double key_b, const int jb, const double key_a, const
 }
 LA_HD double nn_key(const double real) { return real != real ? (double)INFINITY : real; }
 
-// calc_fitness_score's running sums (:905-955), is_local = false
+// calc_fitness_score's running sums (:905-955).  LOCAL is upstream's is_local, and the comparison (:925) is all it selects: the global
+// search takes a neighbour whose real_distance < max_range, the local one a neighbour whose distance < max_range.  A neighbour without
+// coverage has distance DBL_MAX, so the local rule leaves it out of the four sums however small its real_distance; total_lenght always grows.
 struct Sums {
   double real_distance, real_distance_lenght, distance, coverage_lenght, total_lenght;
 };
 LA_HD Sums sums_zero() { Sums s; s.real_distance = s.real_distance_lenght = s.distance = s.coverage_lenght = s.total_lenght = 0.0; return s; }
+template <bool LOCAL>
 LA_HD void sums_add(Sums& s, const bool has_nn, const Pair nn, const float slen, const double max_range) {
-  if (has_nn && nn.real < max_range) {
+  if (has_nn && (LOCAL ? nn.dist : nn.real) < max_range) {
     s.real_distance += nn.real * (double)slen;
     s.real_distance_lenght += (double)slen;
     s.distance += nn.dist * nn.cov;
@@ -209,25 +232,9 @@ LA_HD Fitness sums_finish(const Sums s) {
   return f;
 }
 LA_HD double min_std(const double a, const double b) { return b < a ? b : a; }   // std::min(a, b)
-// weight_global (line_based_scanmatcher.hpp:155-160)
-LA_HD double weight_global(const Weights w, const double avg_distance, const double coverage_percentage, const double translation_distance) {
-  return -w.avg_distance_weight * (min_std(w.max_score_distance, avg_distance) / w.max_score_distance) * 100. + w.coverage_weight * coverage_percentage -
-         w.transform_weight * (min_std(w.max_score_translation, translation_distance) / w.max_score_translation) * 100.;
-}
-
-// calc_fitness_score's is_local = true comparison (:925): nn.distance < max_range.  A neighbour without coverage has distance DBL_MAX
-// and is left out of the four sums however small its real_distance; total_lenght always grows.
-LA_HD void sums_add_local(Sums& s, const bool has_nn, const Pair nn, const float slen, const double max_range) {
-  if (has_nn && nn.dist < max_range) {
-    s.real_distance += nn.real * (double)slen;
-    s.real_distance_lenght += (double)slen;
-    s.distance += nn.dist * nn.cov;
-    s.coverage_lenght += nn.cov;
-  }
-  s.total_lenght += (double)slen;
-}
-// weight_local (line_based_scanmatcher.hpp:161-166): weight_global's expression over the l_* members
-LA_HD double weight_local(const Weights w, const double avg_distance, const double coverage_percentage, const double translation_distance) {
+// weight_global and weight_local (line_based_scanmatcher.hpp:155-166) are this one expression: the global search passes its g_* members
+// and real_avg_distance, the local one its l_* members and avg_distance
+LA_HD double weight(const Weights w, const double avg_distance, const double coverage_percentage, const double translation_distance) {
   return -w.avg_distance_weight * (min_std(w.max_score_distance, avg_distance) / w.max_score_distance) * 100. + w.coverage_weight * coverage_percentage -
          w.transform_weight * (min_std(w.max_score_translation, translation_distance) / w.max_score_translation) * 100.;
 }
@@ -363,6 +370,72 @@ LA_HD bool takes_over(const double sb, const int hb, const double sa, const int 
   return sb > sa || (sb == sa && (unsigned)hb < (unsigned)ha);
 }
 
+#if defined(__HIPCC__)
+// ---- device only ---------------------------------------------------------------------------------------------------------------
+// calc_fitness_score (:905-955) of `Ls` lines, moved by `t` or as they are, against the `Lt` rows of the target table in LDS, by one
+// wavefront: lanes stride over the target lines, the arg-min of (real_distance, index) per source line is a butterfly of cross-lane
+// shuffles, the owner lane's record is broadcast and the five sums are added in source order by every lane alike, so their association
+// is upstream's whatever the launch shape.  Every lane returns the same value.
+template <bool LOCAL>
+__device__ __forceinline__ Fitness fitness_wave(const double* __restrict__ lines, const int Ls, const bool move, const Tf t, const double* s_t,
+                                                const int Lt, const int lane, const int tie_highest, const double max_range) {
+  Sums sums = sums_zero();
+  for (int i = 0; i < Ls; i++) {
+    V3 sa = load3(lines + 6 * i), sb = load3(lines + 6 * i + 3);
+    if (move) {
+      sa = apply(t, sa);
+      sb = apply(t, sb);
+    }
+    const float sl = lenght(sa, sb);
+    int bj = -1;
+    double bkey = 0.0;
+    Pair bp;
+    bp.real = bp.dist = bp.cov = 0.0;
+    for (int j = lane; j < Lt; j += kWave) {
+      const double* tt = s_t + j * kTableDoubles;
+      const Pair p = line_to_line(sa, sb, sl, load3(tt), load3(tt + 3), load3(tt + 6));
+      const double key = nn_key(p.real);
+      if (nn_better(key, j, bkey, bj, tie_highest)) {
+        bj = j;
+        bkey = key;
+        bp = p;
+      }
+    }
+    // arg-min of (key, index) over the wave: after the butterfly every lane holds the winner
+    int wj = bj;
+    double wkey = bkey;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+      const int oj = __shfl_xor(wj, o, kWave);
+      const double okey = __shfl_xor(wkey, o, kWave);
+      if (nn_better(okey, oj, wkey, wj, tie_highest)) {
+        wj = oj;
+        wkey = okey;
+      }
+    }
+    Pair nn;
+    nn.real = nn.dist = nn.cov = 0.0;
+    if (wj >= 0) {   // the lane that owns target wj holds its record as its own best
+      const int owner = wj & (kWave - 1);
+      nn.real = __shfl(bp.real, owner, kWave);
+      nn.dist = __shfl(bp.dist, owner, kWave);
+      nn.cov = __shfl(bp.cov, owner, kWave);
+    }
+    sums_add<LOCAL>(sums, wj >= 0, nn, sl, max_range);
+  }
+  return sums_finish(sums);
+}
+// the arg-max of (score, index) over a wavefront in takes_over's order: afterwards every lane holds the winner
+__device__ __forceinline__ void argmax_wave(double& best, int& bh) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const double os = __shfl_xor(best, o, kWave);
+    const int oh = __shfl_xor(bh, o, kWave);
+    if (takes_over(os, oh, best, bh)) { best = os; bh = oh; }
+  }
+}
+#endif
+
 // ---- host only -----------------------------------------------------------------------------------------------------------------
 // are_lines_aligned (:1012-1084): 0 = no merge, 1 = line1 stays (identical lines), 2 = *merged
 inline int are_lines_aligned(const Line l1, const Line l2, Line* merged) {
@@ -476,6 +549,8 @@ inline int nearest(const V3 sa, const V3 sb, const std::vector<Line>& trg, const
   }
   return best;
 }
+// calc_fitness_score(is_local = LOCAL): what fitness_wave<LOCAL> computes on the device
+template <bool LOCAL>
 inline Fitness calc_fitness(const std::vector<Line>& src, const std::vector<Line>& trg, const std::vector<V3>& dir, const double max_range,
                             const int tie_highest) {
   Sums s = sums_zero();
@@ -483,9 +558,63 @@ inline Fitness calc_fitness(const std::vector<Line>& src, const std::vector<Line
     Pair nn;
     nn.real = nn.dist = nn.cov = 0.0;
     const int j = nearest(l.a, l.b, trg, dir, tie_highest, &nn);
-    sums_add(s, j >= 0, nn, lenght(l.a, l.b), max_range);
+    sums_add<LOCAL>(s, j >= 0, nn, lenght(l.a, l.b), max_range);
   }
   return sums_finish(s);
+}
+inline void transform_lines(const std::vector<Line>& in, const Tf t, std::vector<Line>* out) {
+  out->resize(in.size());
+  for (size_t k = 0; k < in.size(); k++) {
+    (*out)[k].a = apply(t, in[k].a);
+    (*out)[k].b = apply(t, in[k].b);
+  }
+}
+// the target table's third column
+inline std::vector<V3> directions(const std::vector<Line>& trg) {
+  std::vector<V3> dir;
+  for (const Line& l : trg) dir.push_back(normalized(sub(l.b, l.a)));
+  return dir;
+}
+
+// ---- host only, around the C ABI (include/dgs_reg.h): what dgs_line_align_global and dgs_line_align_local_batch both do
+inline std::vector<Line> lines_of(const dgs_line_feature* f, const int64_t n) {
+  std::vector<Line> out((size_t)n);
+  for (int64_t i = 0; i < n; i++) {
+    out[(size_t)i].a = load3(f[i].point_a);
+    out[(size_t)i].b = load3(f[i].point_b);
+  }
+  return out;
+}
+inline bool all_finite(const dgs_line_feature* l, const int64_t n) {
+  for (int64_t i = 0; i < n; i++)
+    for (int a = 0; a < 3; a++)
+      if (!std::isfinite(l[i].point_a[a]) || !std::isfinite(l[i].point_b[a])) return false;
+  return true;
+}
+// what is wrong with the struct itself (nullptr: nothing): it ends before align_local's members were appended, or it is the whole of it
+inline const char* params_guard(const dgs_line_align_params* p) {
+  if (!p) return "line align: params is NULL";
+  if (p->struct_size != offsetof(dgs_line_align_params, l_avg_distance_weight) && p->struct_size != sizeof(dgs_line_align_params))
+    return "line align: wrong struct_size";
+  return nullptr;
+}
+// the upload: 6 doubles per line, kTableDoubles per target line, 9 per edge; each returns the end of what it wrote
+inline double* pack_lines(const std::vector<Line>& lines, double* o) {
+  for (const Line& l : lines) { store3(o, l.a); store3(o + 3, l.b); o += 6; }
+  return o;
+}
+inline double* pack_target_table(const std::vector<Line>& trg, const std::vector<V3>& dir, double* o) {
+  for (size_t j = 0; j < trg.size(); j++) { store3(o, trg[j].a); store3(o + 3, trg[j].b); store3(o + 6, dir[j]); o += kTableDoubles; }
+  return o;
+}
+inline double* pack_edges(const std::vector<Edge>& edges, double* o) {
+  for (const Edge& e : edges) { store3(o, e.e); store3(o + 3, e.a); store3(o + 6, e.b); o += 9; }
+  return o;
+}
+// the 4 x 4 row-major matrix of a planar transform
+inline void matrix(const Tf t, double* T) {
+  const double m[16] = {t.r00, t.r01, 0.0, t.tx, t.r10, t.r11, 0.0, t.ty, 0.0, 0.0, 1.0, t.tz, 0.0, 0.0, 0.0, 1.0};
+  std::memcpy(T, m, sizeof(m));
 }
 
 // ---- align_local (:205-297) on the host: the restatement the device path of line_align_local.hip is tested against, and the CPU side of
@@ -507,38 +636,16 @@ struct LocalResult {
   long long winner_edge, winner_line, survivors_edge, survivors_line;
   int n_edges_source, n_edges_target;
 };
-inline Fitness calc_fitness_local(const std::vector<Line>& src, const std::vector<Line>& trg, const std::vector<V3>& dir, const double max_range,
-                                  const int tie_highest) {
-  Sums s = sums_zero();
-  for (const Line& l : src) {
-    Pair nn;
-    nn.real = nn.dist = nn.cov = 0.0;
-    const int j = nearest(l.a, l.b, trg, dir, tie_highest, &nn);
-    sums_add_local(s, j >= 0, nn, lenght(l.a, l.b), max_range);
-  }
-  return sums_finish(s);
-}
-inline void local_fit(const Fitness f, const double score, double* o) {
-  o[0] = f.real_avg_distance; o[1] = f.avg_distance; o[2] = f.coverage; o[3] = f.coverage_percentage; o[4] = score;
-}
-inline void transform_lines(const std::vector<Line>& in, const Tf t, std::vector<Line>* out) {
-  out->resize(in.size());
-  for (size_t k = 0; k < in.size(); k++) {
-    (*out)[k].a = apply(t, in[k].a);
-    (*out)[k].b = apply(t, in[k].b);
-  }
-}
 inline void align_local(const std::vector<Line>& src, const std::vector<Line>& trg, const LocalParams& P, LocalResult* r, std::vector<Line>* aligned,
                         std::vector<LocalHyp>* hyps_edge, std::vector<LocalHyp>* hyps_line) {
-  std::vector<V3> dir;
-  for (const Line& l : trg) dir.push_back(normalized(sub(l.b, l.a)));
+  const std::vector<V3> dir = directions(trg);
   std::vector<Edge> es, et;
   edge_extraction(src, es, true, 0.01);
   edge_extraction(trg, et, true);
   r->n_edges_source = (int)es.size();
   r->n_edges_target = (int)et.size();
-  const Fitness fb = calc_fitness_local(src, trg, dir, P.max_range, P.tie_highest);
-  local_fit(fb, weight_local(P.w, fb.avg_distance, fb.coverage_percentage, 0.0), r->fit_base);
+  const Fitness fb = calc_fitness<true>(src, trg, dir, P.max_range, P.tie_highest);
+  store_fit(r->fit_base, fb, weight(P.w, fb.avg_distance, fb.coverage_percentage, 0.0));
   for (int k = 0; k < 5; k++) r->fit_edge[k] = r->fit_base[k];
   r->t_edge = tf_identity();
   r->winner_edge = r->winner_line = -1;
@@ -557,8 +664,8 @@ inline void align_local(const std::vector<Line>& src, const std::vector<Line>& t
       if (hy.gate == GATE_PASS) {
         r->survivors_edge++;
         transform_lines(src, hy.t, &cand);
-        const Fitness f = calc_fitness_local(cand, trg, dir, P.max_range, P.tie_highest);
-        local_fit(f, weight_local(P.w, f.avg_distance, f.coverage_percentage, hy.tn), hy.fit);
+        const Fitness f = calc_fitness<true>(cand, trg, dir, P.max_range, P.tie_highest);
+        store_fit(hy.fit, f, weight(P.w, f.avg_distance, f.coverage_percentage, hy.tn));
         if (hy.fit[4] > r->fit_edge[4]) {
           for (int k = 0; k < 5; k++) r->fit_edge[k] = hy.fit[k];
           r->t_edge = hy.t;
@@ -593,8 +700,8 @@ inline void align_local(const std::vector<Line>& src, const std::vector<Line>& t
       if (hy.gate == GATE_PASS) {
         r->survivors_line++;
         transform_lines(base, hy.t, &cand);
-        const Fitness f = calc_fitness_local(cand, trg, dir, P.max_range, P.tie_highest);
-        local_fit(f, weight_local(P.w, f.avg_distance, f.coverage_percentage, hy.tn), hy.fit);
+        const Fitness f = calc_fitness<true>(cand, trg, dir, P.max_range, P.tie_highest);
+        store_fit(hy.fit, f, weight(P.w, f.avg_distance, f.coverage_percentage, hy.tn));
         if (hy.fit[4] > r->fit[4]) {
           for (int k = 0; k < 5; k++) r->fit[k] = hy.fit[k];
           r->t = compose(r->t_edge, hy.t);

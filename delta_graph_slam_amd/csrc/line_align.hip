@@ -1,17 +1,16 @@
 // LineBasedScanmatcher::align_global (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp:109-203) on the device: every
 // (source edge, target edge) pair is a hypothesis h = es * Et + et; align_edges, the three gates, calc_fitness_score of the
 // transformed source lines against the merged target lines and the strict arg-max run there.  merge_lines, edge_extraction and the
-// refinement pass are sequential and small and run on the host from the same functions (line_align.h).
+// refinement pass are sequential and small and run on the host from the same functions (line_align.h).  The scorer
+// (la::fitness_wave), the wave arg-max and the host's checks and packing are line_align.h's, shared with line_align_local.hip.
 //
 // MI355X design
 //   * One upload: source lines, the target table (A, B, (B - A).normalized() per merged line) and both edge lists.
 //   * la_hypothesis_kernel: one lane per h; transform, gate code, survivor flag.  Survivors are compacted in h order with the
 //     prefilter's stable compaction (pf_count_kernel, pf_scan_kernel) and la_scatter_kernel.
-//   * la_score_kernel: one wavefront per survivor (item 0 is the identity, the baseline).  The target table sits in LDS (72 bytes per
-//     line, 36 KiB at the limit of 512 lines); lanes stride over the target lines, the arg-min of (real_distance, index) per source
-//     line is a butterfly of cross-lane shuffles, the owner lane's record is broadcast and the five sums are added in source order by
-//     every lane alike, so their association is upstream's whatever the launch shape.  FP64 throughout: the loop is bound by the
-//     FP64 divide and square-root sequences of line_to_line_distance, not by memory.
+//   * la_score_kernel: one wavefront per survivor (item 0 is the identity, the baseline) runs la::fitness_wave<false> against the
+//     target table in LDS (72 bytes per line, 36 KiB at the limit of 512 lines).  FP64 throughout: the loop is bound by the FP64
+//     divide and square-root sequences of line_to_line_distance, not by memory.
 //   * la_argmax_kernel: one workgroup; a strictly greater score takes over, equal scores go to the lower h, NaN never wins.
 //   * The grid of la_score_kernel is fixed and its waves stride over the survivor count read on the device: one host wait per call.
 // Semantics and the Eigen details recalled from upstream: DESIGN.md §6f.
@@ -35,7 +34,6 @@ __global__ void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restr
 constexpr int kLaScanBlock = 1024;      // pf_scan_kernel's workgroup
 constexpr int kLaArgmaxBlock = 1024;
 constexpr int kLaScoreBlocks = 2048;    // la_score_kernel's fixed grid: 8192 waves, 8 per SIMD of 256 CUs
-constexpr int kLaTableDoubles = 9;      // A, B, direction per target line
 constexpr int kLaWavesPerBlock = kBlock / kWave;
 
 struct LaHyp {
@@ -58,8 +56,6 @@ struct LaArgs {
   la::Weights w;
 };
 
-__device__ __forceinline__ la::V3 la_load3(const double* p) { return la::v3(p[0], p[1], p[2]); }
-
 // ================================================================================================ hypotheses
 __global__ __launch_bounds__(kBlock) void la_hypothesis_kernel(const double* __restrict__ es, const double* __restrict__ et, const LaArgs a,
                                                                LaHyp* __restrict__ hyps, unsigned char* __restrict__ keep,
@@ -68,11 +64,8 @@ __global__ __launch_bounds__(kBlock) void la_hypothesis_kernel(const double* __r
   const long long H = (long long)a.Es * a.Et;
   if (h >= H) return;
   const int is = (int)(h / a.Et), it = (int)(h % a.Et);   // is < Es, it < Et: both edge lists are read inside their bounds
-  la::Edge e1, e2;
-  e1.e = la_load3(es + 9 * is); e1.a = la_load3(es + 9 * is + 3); e1.b = la_load3(es + 9 * is + 6);
-  e2.e = la_load3(et + 9 * it); e2.a = la_load3(et + 9 * it + 3); e2.b = la_load3(et + 9 * it + 6);
   LaHyp hy;
-  hy.t = la::align_edges(e1, e2, nullptr);
+  hy.t = la::align_edges(la::load_edge(es + 9 * is), la::load_edge(et + 9 * it), nullptr);
   const int g = la::gate(hy.t, a.max_distance, a.constrain_angle, a.cos_max_angle, a.float_chain, &hy.tn);
   hyps[h] = hy;
   gate[h] = (unsigned char)g;
@@ -105,8 +98,8 @@ __global__ __launch_bounds__(kBlock) void la_scatter_kernel(const unsigned char*
 __global__ __launch_bounds__(kBlock) void la_score_kernel(const double* __restrict__ src, const double* __restrict__ tbl, const LaArgs a,
                                                           const LaHyp* __restrict__ hyps, const int* __restrict__ surv, const int* __restrict__ cnt,
                                                           double* __restrict__ fit, LaResult* __restrict__ res) {
-  __shared__ double s_t[DGS_LA_MAX_LINES_TARGET * kLaTableDoubles];
-  for (int k = threadIdx.x; k < a.Lt * kLaTableDoubles; k += kBlock) s_t[k] = tbl[k];   // Lt <= DGS_LA_MAX_LINES_TARGET (checked on the host)
+  __shared__ double s_t[DGS_LA_MAX_LINES_TARGET * la::kTableDoubles];
+  for (int k = threadIdx.x; k < a.Lt * la::kTableDoubles; k += kBlock) s_t[k] = tbl[k];   // Lt <= DGS_LA_MAX_LINES_TARGET (checked on the host)
   __syncthreads();
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = blockIdx.x * kLaWavesPerBlock + threadIdx.x / kWave;
@@ -119,64 +112,13 @@ __global__ __launch_bounds__(kBlock) void la_score_kernel(const double* __restri
     hy.t = la::tf_identity();
     hy.tn = 0.0;
     if (!base) hy = hyps[h];
-    la::Sums sums = la::sums_zero();
-    for (int i = 0; i < a.Ls; i++) {
-      la::V3 sa = la_load3(src + 6 * i), sb = la_load3(src + 6 * i + 3);
-      if (!base) {
-        sa = la::apply(hy.t, sa);
-        sb = la::apply(hy.t, sb);
-      }
-      const float sl = la::lenght(sa, sb);
-      int bj = -1;
-      double bkey = 0.0;
-      la::Pair bp;
-      bp.real = bp.dist = bp.cov = 0.0;
-      for (int j = lane; j < a.Lt; j += kWave) {
-        const double* t = s_t + j * kLaTableDoubles;
-        const la::Pair p = la::line_to_line(sa, sb, sl, la_load3(t), la_load3(t + 3), la_load3(t + 6));
-        const double key = la::nn_key(p.real);
-        if (la::nn_better(key, j, bkey, bj, a.tie_highest)) {
-          bj = j;
-          bkey = key;
-          bp = p;
-        }
-      }
-      // arg-min of (key, index) over the wave: after the butterfly every lane holds the winner
-      int wj = bj;
-      double wkey = bkey;
-#pragma unroll
-      for (int o = kWave / 2; o > 0; o >>= 1) {
-        const int oj = __shfl_xor(wj, o, kWave);
-        const double okey = __shfl_xor(wkey, o, kWave);
-        if (la::nn_better(okey, oj, wkey, wj, a.tie_highest)) {
-          wj = oj;
-          wkey = okey;
-        }
-      }
-      la::Pair nn;
-      nn.real = nn.dist = nn.cov = 0.0;
-      if (wj >= 0) {   // the lane that owns target wj holds its record as its own best
-        const int owner = wj & (kWave - 1);
-        nn.real = __shfl(bp.real, owner, kWave);
-        nn.dist = __shfl(bp.dist, owner, kWave);
-        nn.cov = __shfl(bp.cov, owner, kWave);
-      }
-      la::sums_add(sums, wj >= 0, nn, sl, a.max_range);
-    }
-    const la::Fitness f = la::sums_finish(sums);
-    const double score = la::weight_global(a.w, f.real_avg_distance, f.coverage_percentage, hy.tn);
-    if (lane == 0) {
-      double* o = base ? res->base : fit + 5 * (long long)h;
-      o[0] = f.real_avg_distance; o[1] = f.avg_distance; o[2] = f.coverage; o[3] = f.coverage_percentage; o[4] = score;
-    }
+    const la::Fitness f = la::fitness_wave<false>(src, a.Ls, !base, hy.t, s_t, a.Lt, lane, a.tie_highest, a.max_range);
+    const double score = la::weight(a.w, f.real_avg_distance, f.coverage_percentage, hy.tn);
+    if (lane == 0) la::store_fit(base ? res->base : fit + 5 * (long long)h, f, score);
   }
 }
 
 // ================================================================================================ arg-max
-__device__ __forceinline__ bool la_takes_over(const double sb, const int hb, const double sa, const int ha) {
-  return sb > sa || (sb == sa && (unsigned)hb < (unsigned)ha);   // -1 is the baseline: the largest unsigned value
-}
-
 // result_score starts at the identity's; a hypothesis takes over iff its score is strictly greater, in h order: the winner is the
 // lowest h among the maxima above the baseline.  A NaN score compares false and never wins.
 __global__ __launch_bounds__(kLaArgmaxBlock) void la_argmax_kernel(const int* __restrict__ surv, const int* __restrict__ cnt, const double* __restrict__ fit,
@@ -192,18 +134,13 @@ __global__ __launch_bounds__(kLaArgmaxBlock) void la_argmax_kernel(const int* __
     const double sc = fit[5 * (long long)h + 4];
     if (sc > best) { best = sc; bh = h; }
   }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    const double os = __shfl_xor(best, o, kWave);
-    const int oh = __shfl_xor(bh, o, kWave);
-    if (la_takes_over(os, oh, best, bh)) { best = os; bh = oh; }
-  }
+  la::argmax_wave(best, bh);
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   if (lane == 0) { s_s[wv] = best; s_h[wv] = bh; }
   __syncthreads();
   if (threadIdx.x != 0) return;
   for (int w = 1; w < kLaArgmaxBlock / kWave; w++)
-    if (la_takes_over(s_s[w], s_h[w], best, bh)) { best = s_s[w]; bh = s_h[w]; }
+    if (la::takes_over(s_s[w], s_h[w], best, bh)) { best = s_s[w]; bh = s_h[w]; }
   res->winner = bh;
   res->survivors = S;
   res->pad = 0;
@@ -218,34 +155,15 @@ __global__ __launch_bounds__(kLaArgmaxBlock) void la_argmax_kernel(const int* __
 // ================================================================================================ host side
 namespace {
 
-inline la::Line la_line(const dgs_line_feature& f) {
-  la::Line l;
-  l.a = la::v3(f.point_a[0], f.point_a[1], f.point_a[2]);
-  l.b = la::v3(f.point_b[0], f.point_b[1], f.point_b[2]);
-  return l;
-}
-inline void la_put(const la::V3 v, double* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
-inline bool la_finite(const dgs_line_feature* l, int64_t n) {
-  for (int64_t i = 0; i < n; i++)
-    for (int a = 0; a < 3; a++)
-      if (!std::isfinite(l[i].point_a[a]) || !std::isfinite(l[i].point_b[a])) return false;
-  return true;
-}
 void la_merge(const dgs_line_feature* lines, int64_t n, std::vector<la::Line>* out, std::vector<int>* origin) {
-  out->clear();
+  *out = la::lines_of(lines, n);
   origin->clear();
-  for (int64_t i = 0; i < n; i++) {
-    out->push_back(la_line(lines[i]));
-    origin->push_back((int)i);
-  }
+  for (int64_t i = 0; i < n; i++) origin->push_back((int)i);
   la::merge_lines(*out, *origin);
 }
 
 const char* la_bad_params(const dgs_line_align_params* p) {
-  if (!p) return "line align: params is NULL";
-  // the struct as it was before align_local's members were appended, or the whole of it
-  if (p->struct_size != offsetof(dgs_line_align_params, l_avg_distance_weight) && p->struct_size != sizeof(dgs_line_align_params))
-    return "line align: wrong struct_size";
+  if (const char* why = la::params_guard(p)) return why;
   if (!(p->g_max_score_distance > 0.0) || !(p->g_max_score_translation > 0.0)) return "line align: the max_score values must be positive";
   // +infinity is a legal weight (that term alone decides); against a zero term it gives a NaN score, which never wins
   for (const double w : {p->g_avg_distance_weight, p->g_coverage_weight, p->g_transform_weight})
@@ -265,7 +183,7 @@ int la_search(dgs_handle* h, const LaArgs& a, const std::vector<la::Line>& src, 
               const std::vector<la::Edge>& es, const std::vector<la::Edge>& et, LaResult* out) {
   LaScratch& s = h->la;
   const int64_t H = (int64_t)a.Es * a.Et;
-  const size_t n_src = (size_t)a.Ls * 6, n_tbl = (size_t)a.Lt * kLaTableDoubles, n_es = (size_t)a.Es * 9, n_et = (size_t)a.Et * 9;
+  const size_t n_src = (size_t)a.Ls * 6, n_tbl = (size_t)a.Lt * la::kTableDoubles, n_es = (size_t)a.Es * 9, n_et = (size_t)a.Et * 9;
   const size_t n_in = n_src + n_tbl + n_es + n_et;
   const size_t hh = (size_t)std::max<int64_t>(H, 1);
   const unsigned nb = (unsigned)((hh + kBlock - 1) / kBlock);
@@ -282,11 +200,10 @@ int la_search(dgs_handle* h, const LaArgs& a, const std::vector<la::Line>& src, 
   if (ensure_pinned(h, 4096 + n_in * sizeof(double)) != DGS_OK) return DGS_ERR_HIP;
   static_assert(sizeof(LaResult) <= 4096, "the read-back block must fit in front of the upload");
   double* up = reinterpret_cast<double*>(static_cast<char*>(h->pinned) + 4096);
-  double* o = up;
-  for (const la::Line& l : src) { la_put(l.a, o); la_put(l.b, o + 3); o += 6; }
-  for (size_t j = 0; j < trg.size(); j++) { la_put(trg[j].a, o); la_put(trg[j].b, o + 3); la_put(dir[j], o + 6); o += kLaTableDoubles; }
-  for (const std::vector<la::Edge>* ev : {&es, &et})
-    for (const la::Edge& e : *ev) { la_put(e.e, o); la_put(e.a, o + 3); la_put(e.b, o + 6); o += 9; }
+  double* o = la::pack_lines(src, up);
+  o = la::pack_target_table(trg, dir, o);
+  o = la::pack_edges(es, o);
+  la::pack_edges(et, o);
   if (n_in) DGS_HIP_TRY(h, hipMemcpyAsync(s.in.ptr, up, n_in * sizeof(double), hipMemcpyHostToDevice, h->stream));
   const double* d_src = s.in.ptr;
   const double* d_tbl = d_src + n_src;
@@ -334,13 +251,10 @@ int la_refine(const dgs_line_align_params& p, const LaArgs& a, const std::vector
     const la::Tf tf = la::align_lines(ls, trg[(size_t)j]);
     const double tn = la::norm(la::v3(tf.tx, tf.ty, tf.tz));
     if (tn > p.max_distance) continue;
-    std::vector<la::Line> cand(aligned->size());
-    for (size_t k = 0; k < cand.size(); k++) {
-      cand[k].a = la::apply(tf, (*aligned)[k].a);
-      cand[k].b = la::apply(tf, (*aligned)[k].b);
-    }
-    const la::Fitness f = la::calc_fitness(cand, trg, dir, a.max_range, a.tie_highest);
-    const double score = la::weight_global(a.w, f.real_avg_distance, f.coverage_percentage, tn);
+    std::vector<la::Line> cand;
+    la::transform_lines(*aligned, tf, &cand);
+    const la::Fitness f = la::calc_fitness<false>(cand, trg, dir, a.max_range, a.tie_highest);
+    const double score = la::weight(a.w, f.real_avg_distance, f.coverage_percentage, tn);
     if (score > r->score) {
       *aligned = cand;
       r->t = la::compose(best_trans, tf);
@@ -399,8 +313,8 @@ int dgs_line_merge(const dgs_line_feature* lines, int64_t n, dgs_line_feature* o
   for (size_t i = 0; i < m.size(); i++) {
     dgs_line_feature f{};
     if (origin[i] >= 0) f = lines[origin[i]];
-    la_put(m[i].a, f.point_a);
-    la_put(m[i].b, f.point_b);
+    la::store3(f.point_a, m[i].a);
+    la::store3(f.point_b, m[i].b);
     out[i] = f;
   }
   *n_out = (int64_t)m.size();
@@ -408,19 +322,7 @@ int dgs_line_merge(const dgs_line_feature* lines, int64_t n, dgs_line_feature* o
 }
 
 int dgs_line_edges(const dgs_line_feature* lines, int64_t n, dgs_edge_feature* edges, int64_t capacity, int64_t* n_edges) {
-  if (n < 0 || !n_edges || (n > 0 && !lines) || capacity < 0 || (capacity > 0 && !edges)) return DGS_ERR_INVALID_ARGUMENT;
-  std::vector<la::Line> l;
-  for (int64_t i = 0; i < n; i++) l.push_back(la_line(lines[i]));
-  std::vector<la::Edge> e;
-  la::edge_extraction(l, e);
-  *n_edges = (int64_t)e.size();
-  if (*n_edges > capacity) return DGS_ERR_INVALID_ARGUMENT;
-  for (size_t i = 0; i < e.size(); i++) {
-    la_put(e[i].e, edges[i].edge_point);
-    la_put(e[i].a, edges[i].point_a);
-    la_put(e[i].b, edges[i].point_b);
-  }
-  return DGS_OK;
+  return dgs_line_edges_angular(lines, n, 0, 7.0, edges, capacity, n_edges);   // get_edges' defaults: align_global's call
 }
 
 int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, const dgs_line_feature* src_lines, int64_t n_src,
@@ -437,21 +339,20 @@ int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, co
   if (n_src > DGS_LA_MAX_LINES_SOURCE) why = "line align: more than DGS_LA_MAX_LINES_SOURCE source lines";
   else if (n_trg > (1 << 20)) why = "line align: more than 2^20 target lines";
   else if (std::isnan(max_range)) why = "line align: max_range is NaN";
-  else if (!la_finite(src_lines, n_src) || !la_finite(trg_lines, n_trg)) why = "line align: a line coordinate is not finite";
+  else if (!la::all_finite(src_lines, n_src) || !la::all_finite(trg_lines, n_trg)) why = "line align: a line coordinate is not finite";
   if (why) {
     h->err = why;
     return DGS_ERR_INVALID_ARGUMENT;
   }
-  std::vector<la::Line> src, trg;
+  const std::vector<la::Line> src = la::lines_of(src_lines, n_src);
+  std::vector<la::Line> trg;
   std::vector<int> origin;
-  for (int64_t i = 0; i < n_src; i++) src.push_back(la_line(src_lines[i]));
   la_merge(trg_lines, n_trg, &trg, &origin);
   if ((int64_t)trg.size() > DGS_LA_MAX_LINES_TARGET) {
     h->err = "line align: more than DGS_LA_MAX_LINES_TARGET target lines after merging";
     return DGS_ERR_INVALID_ARGUMENT;
   }
-  std::vector<la::V3> dir;
-  for (const la::Line& l : trg) dir.push_back(la::normalized(la::sub(l.b, l.a)));
+  const std::vector<la::V3> dir = la::directions(trg);
   std::vector<la::Edge> es, et;
   la::edge_extraction(src, es);
   la::edge_extraction(trg, et);
@@ -486,11 +387,9 @@ int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, co
   r.fit.real_avg_distance = res.fit[0]; r.fit.avg_distance = res.fit[1]; r.fit.coverage = res.fit[2]; r.fit.coverage_percentage = res.fit[3];
   r.score = res.fit[4];
   std::vector<la::Line> aligned = src;
-  if (res.winner >= 0)
-    for (la::Line& l : aligned) { l.a = la::apply(r.t, l.a); l.b = la::apply(r.t, l.b); }
+  if (res.winner >= 0) la::transform_lines(src, r.t, &aligned);
   const int steps = la_refine(*params, a, trg, dir, &aligned, &r);
-  const double T[16] = {r.t.r00, r.t.r01, 0.0, r.t.tx, r.t.r10, r.t.r11, 0.0, r.t.ty, 0.0, 0.0, 1.0, r.t.tz, 0.0, 0.0, 0.0, 1.0};
-  std::memcpy(alignment->transformation, T, sizeof(T));
+  la::matrix(r.t, alignment->transformation);
   alignment->fitness_score[0] = r.fit.real_avg_distance; alignment->fitness_score[1] = r.fit.avg_distance;
   alignment->fitness_score[2] = r.fit.coverage; alignment->fitness_score[3] = r.fit.coverage_percentage;
   alignment->score = r.score;
@@ -505,8 +404,8 @@ int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, co
   if (aligned_lines)
     for (size_t i = 0; i < aligned.size(); i++) {
       aligned_lines[i] = src_lines[i];   // transform_lines copies the line and replaces its two points
-      la_put(aligned[i].a, aligned_lines[i].point_a);
-      la_put(aligned[i].b, aligned_lines[i].point_b);
+      la::store3(aligned_lines[i].point_a, aligned[i].a);
+      la::store3(aligned_lines[i].point_b, aligned[i].b);
     }
   return DGS_OK;
 }

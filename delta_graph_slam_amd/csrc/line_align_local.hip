@@ -1,7 +1,8 @@
 // LineBasedScanmatcher::align_local (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp:205-297) on the device, for a batch of
 // independent items (a keyframe's near buildings): per item the baseline, the edge-pair hypotheses h = es * Et + et with their two
 // gates, the strict arg-max, then the line-pair hypotheses k = i * Lt + r over the snapshot of the first phase's result and the second
-// arg-max.  Edge extraction is sequential and small and runs on the host from the same functions (line_align.h).
+// arg-max.  Edge extraction is sequential and small and runs on the host from the same functions (line_align.h).  The scorer
+// (la::fitness_wave), the wave arg-max and the host's checks and packing are line_align.h's, shared with line_align.hip.
 //
 // MI355X design
 //   * One upload: the item table (sizes and offsets), the two workgroup tables, every item's source lines, target table (A, B,
@@ -11,9 +12,8 @@
 //     lal_line_hypothesis_kernel (a lane per (snapshot line, target line): the real_distance keys, then the counting rank, O(Lt) per
 //     lane, and the hypothesis at its rank), lal_score_kernel<1>, lal_argmax_line_kernel (a workgroup per item: the record and the
 //     aligned lines).  The second phase reads the first phase's winner on the device.
-//   * lal_score_kernel keeps align_global's association: one wavefront per hypothesis, lanes stride over the target
-//     lines, a butterfly arg-min of (real_distance, index), and the five sums added in source-line order by every lane alike.  Items
-//     have different target tables, so a workgroup serves one item: the host's table gives every workgroup its (item, first unit) and
+//   * lal_score_kernel runs the scorer align_global runs, la::fitness_wave, with the local comparison: one wavefront per hypothesis.
+//     Items have different target tables, so a workgroup serves one item: the host's table gives every workgroup its (item, first unit) and
 //     the workgroup's four waves walk kLalUnits consecutive units of that item against one LDS copy of its table (72 bytes per line,
 //     36 KiB at the limit of 512 lines).  A gated hypothesis costs its wave one load.  Nothing is accumulated across waves or with
 //     atomics, so an item's results do not depend on what else is in the batch.
@@ -32,7 +32,6 @@
 namespace dgs {
 
 constexpr int kLalUnits = 8;            // units (hypotheses; in phase 0 also the baseline) per workgroup of lal_score_kernel: two per wave
-constexpr int kLalTableDoubles = 9;     // A, B, direction per target line
 constexpr int kLalWaves = kBlock / kWave;
 
 struct LalHyp {
@@ -60,9 +59,6 @@ struct LalArgs {
   la::Weights w;
 };
 
-__device__ __forceinline__ la::V3 lal_load3(const double* p) { return la::v3(p[0], p[1], p[2]); }
-__device__ __forceinline__ void lal_store3(double* p, const la::V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
-
 // the item that owns hypothesis g of a phase: the last item whose first hypothesis is <= g (empty items share their successor's offset).
 // g < the phase's total, so the result's range holds g.
 template <int PHASE>
@@ -86,11 +82,8 @@ __global__ __launch_bounds__(kBlock) void lal_edge_hypothesis_kernel(const LalIt
   const LalItem it = items[lal_find_item<0>(items, a.n_items, g)];
   const long long h = g - it.h1_off;                                  // 0 <= h < Es * Et of this item
   const int is = it.es_off + (int)(h / it.Et), ie = it.et_off + (int)(h % it.Et);
-  la::Edge e1, e2;
-  e1.e = lal_load3(es + 9 * (long long)is); e1.a = lal_load3(es + 9 * (long long)is + 3); e1.b = lal_load3(es + 9 * (long long)is + 6);
-  e2.e = lal_load3(et + 9 * (long long)ie); e2.a = lal_load3(et + 9 * (long long)ie + 3); e2.b = lal_load3(et + 9 * (long long)ie + 6);
   LalHyp hy;
-  hy.t = la::align_edges(e1, e2, nullptr);
+  hy.t = la::align_edges(la::load_edge(es + 9 * (long long)is), la::load_edge(et + 9 * (long long)ie), nullptr);
   hy.gate = la::gate_local(hy.t, a.max_distance, a.cos_max_angle, a.float_chain, &hy.tn);
   hy.target = -1;
   hyps[g] = hy;
@@ -99,68 +92,18 @@ __global__ __launch_bounds__(kBlock) void lal_edge_hypothesis_kernel(const LalIt
 }
 
 // ================================================================================================ scores
-// calc_fitness_score(is_local = true) of the item's lines moved by `t` (or as they are) against the target table in LDS, by one wave;
-// every lane returns the same value
-__device__ __forceinline__ la::Fitness lal_fitness_wave(const double* __restrict__ lines, const int Ls, const bool move, const la::Tf t,
-                                                        const double* s_t, const int Lt, const int lane, const LalArgs& a) {
-  la::Sums sums = la::sums_zero();
-  for (int i = 0; i < Ls; i++) {
-    la::V3 sa = lal_load3(lines + 6 * i), sb = lal_load3(lines + 6 * i + 3);
-    if (move) {
-      sa = la::apply(t, sa);
-      sb = la::apply(t, sb);
-    }
-    const float sl = la::lenght(sa, sb);
-    int bj = -1;
-    double bkey = 0.0;
-    la::Pair bp;
-    bp.real = bp.dist = bp.cov = 0.0;
-    for (int j = lane; j < Lt; j += kWave) {
-      const double* tt = s_t + j * kLalTableDoubles;
-      const la::Pair p = la::line_to_line(sa, sb, sl, lal_load3(tt), lal_load3(tt + 3), lal_load3(tt + 6));
-      const double key = la::nn_key(p.real);
-      if (la::nn_better(key, j, bkey, bj, a.tie_highest)) {
-        bj = j;
-        bkey = key;
-        bp = p;
-      }
-    }
-    int wj = bj;
-    double wkey = bkey;
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      const int oj = __shfl_xor(wj, o, kWave);
-      const double okey = __shfl_xor(wkey, o, kWave);
-      if (la::nn_better(okey, oj, wkey, wj, a.tie_highest)) {
-        wj = oj;
-        wkey = okey;
-      }
-    }
-    la::Pair nn;
-    nn.real = nn.dist = nn.cov = 0.0;
-    if (wj >= 0) {   // the lane that owns target wj holds its record as its own best
-      const int owner = wj & (kWave - 1);
-      nn.real = __shfl(bp.real, owner, kWave);
-      nn.dist = __shfl(bp.dist, owner, kWave);
-      nn.cov = __shfl(bp.cov, owner, kWave);
-    }
-    la::sums_add_local(sums, wj >= 0, nn, sl, a.max_range);
-  }
-  return la::sums_finish(sums);
-}
-
 // PHASE 0: unit 0 of an item is its baseline (the source lines as they are), unit u > 0 the edge pair h = u - 1 over the source lines.
 // PHASE 1: unit u is the line pair k = u over the snapshot lines.
 template <int PHASE>
 __global__ __launch_bounds__(kBlock) void lal_score_kernel(const LalItem* __restrict__ items, const int2* __restrict__ wg, const int n_wg,
                                                            const double* __restrict__ lines, const double* __restrict__ tbl, const LalArgs a,
                                                            const LalHyp* __restrict__ hyps, double* __restrict__ fit, LalRecord* __restrict__ rec) {
-  __shared__ double s_t[DGS_LA_MAX_LINES_TARGET * kLalTableDoubles];
+  __shared__ double s_t[DGS_LA_MAX_LINES_TARGET * la::kTableDoubles];
   if ((int)blockIdx.x >= n_wg) return;                                // uniform: the grid is at least one workgroup
   const int2 w = wg[blockIdx.x];
   const LalItem it = items[w.x];
-  const double* t = tbl + (long long)it.trg_off * kLalTableDoubles;
-  for (int k = threadIdx.x; k < it.Lt * kLalTableDoubles; k += kBlock) s_t[k] = t[k];   // Lt <= DGS_LA_MAX_LINES_TARGET (checked on the host)
+  const double* t = tbl + (long long)it.trg_off * la::kTableDoubles;
+  for (int k = threadIdx.x; k < it.Lt * la::kTableDoubles; k += kBlock) s_t[k] = t[k];   // Lt <= DGS_LA_MAX_LINES_TARGET (checked on the host)
   __syncthreads();
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const long long units = PHASE == 0 ? (long long)it.Es * it.Et + 1 : (long long)it.Ls * it.Lt;
@@ -177,12 +120,9 @@ __global__ __launch_bounds__(kBlock) void lal_score_kernel(const LalItem* __rest
       tf = hy.t;
       tn = hy.tn;
     }
-    const la::Fitness f = lal_fitness_wave(src, it.Ls, !base, tf, s_t, it.Lt, lane, a);
-    const double score = la::weight_local(a.w, f.avg_distance, f.coverage_percentage, tn);
-    if (lane == 0) {
-      double* o = base ? rec[w.x].fit_base : fit + 5 * idx;
-      o[0] = f.real_avg_distance; o[1] = f.avg_distance; o[2] = f.coverage; o[3] = f.coverage_percentage; o[4] = score;
-    }
+    const la::Fitness f = la::fitness_wave<true>(src, it.Ls, !base, tf, s_t, it.Lt, lane, a.tie_highest, a.max_range);
+    const double score = la::weight(a.w, f.avg_distance, f.coverage_percentage, tn);
+    if (lane == 0) la::store_fit(base ? rec[w.x].fit_base : fit + 5 * idx, f, score);
   }
 }
 
@@ -202,13 +142,9 @@ __device__ __forceinline__ long long lal_argmax_block(const LalHyp* __restrict__
     const double sc = fit[5 * (off + h) + 4];
     if (sc > best) { best = sc; bh = (int)h; }
   }
+  la::argmax_wave(best, bh);
 #pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    const double os = __shfl_xor(best, o, kWave);
-    const int oh = __shfl_xor(bh, o, kWave);
-    n += __shfl_xor(n, o, kWave);
-    if (la::takes_over(os, oh, best, bh)) { best = os; bh = oh; }
-  }
+  for (int o = kWave / 2; o > 0; o >>= 1) n += __shfl_xor(n, o, kWave);
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   if (lane == 0) { s_s[wv] = best; s_h[wv] = bh; s_n[wv] = n; }
   __syncthreads();
@@ -243,9 +179,9 @@ __global__ __launch_bounds__(kBlock) void lal_argmax_edge_kernel(const LalItem* 
   // the snapshot (best_lines): transform_lines(linesSource, transform), or the source lines themselves
   for (int k = threadIdx.x; k < 2 * it.Ls; k += kBlock) {
     const long long p = 3 * (2 * (long long)it.src_off + k);
-    la::V3 v = lal_load3(src + p);
+    la::V3 v = la::load3(src + p);
     if (w >= 0) v = la::apply(t, v);
-    lal_store3(base + p, v);
+    la::store3(base + p, v);
   }
 }
 
@@ -271,9 +207,9 @@ __global__ __launch_bounds__(kBlock) void lal_argmax_line_kernel(const LalItem* 
   if (w >= 0) t = hyps[it.h2_off + w].t;
   for (int k = threadIdx.x; k < 2 * it.Ls; k += kBlock) {              // transform_lines(best_lines, transform)
     const long long p = 3 * (2 * (long long)it.src_off + k);
-    la::V3 v = lal_load3(base + p);
+    la::V3 v = la::load3(base + p);
     if (w >= 0) v = la::apply(t, v);
-    lal_store3(aligned + p, v);
+    la::store3(aligned + p, v);
   }
 }
 
@@ -287,9 +223,9 @@ __global__ __launch_bounds__(kBlock) void lal_key_kernel(const LalItem* __restri
   const long long local = a.H1 + q - it.h2_off;                       // 0 <= local < Ls * Lt of this item
   const int i = (int)(local / it.Lt), j = (int)(local % it.Lt);
   const double* s = base + 6 * ((long long)it.src_off + i);
-  const double* t = tbl + kLalTableDoubles * ((long long)it.trg_off + j);
-  const la::V3 sa = lal_load3(s), sb = lal_load3(s + 3);
-  keys[q] = la::nn_key(la::line_to_line(sa, sb, la::lenght(sa, sb), lal_load3(t), lal_load3(t + 3), lal_load3(t + 6)).real);
+  const double* t = tbl + la::kTableDoubles * ((long long)it.trg_off + j);
+  const la::V3 sa = la::load3(s), sb = la::load3(s + 3);
+  keys[q] = la::nn_key(la::line_to_line(sa, sb, la::lenght(sa, sb), la::load3(t), la::load3(t + 3), la::load3(t + 6)).real);
 }
 
 // the same lane layout: target j's rank r among the Lt keys of snapshot line i by counting, then hypothesis k = i * Lt + r.  The ranks
@@ -307,10 +243,10 @@ __global__ __launch_bounds__(kBlock) void lal_line_hypothesis_kernel(const LalIt
   int rank = 0;
   for (int o = 0; o < it.Lt; o++) rank += la::rank_before(row[o], o, key, j, a.tie_highest) ? 1 : 0;
   const double* s = base + 6 * ((long long)it.src_off + i);
-  const double* t = tbl + kLalTableDoubles * ((long long)it.trg_off + j);
+  const double* t = tbl + la::kTableDoubles * ((long long)it.trg_off + j);
   la::Line ls, lt;
-  ls.a = lal_load3(s); ls.b = lal_load3(s + 3);
-  lt.a = lal_load3(t); lt.b = lal_load3(t + 3);
+  ls.a = la::load3(s); ls.b = la::load3(s + 3);
+  lt.a = la::load3(t); lt.b = la::load3(t + 3);
   LalHyp hy;
   hy.t = la::tf_identity();
   hy.tn = 0.0;
@@ -325,19 +261,6 @@ __global__ __launch_bounds__(kBlock) void lal_line_hypothesis_kernel(const LalIt
 // ================================================================================================ host side
 namespace {
 
-inline la::Line lal_line(const dgs_line_feature& f) {
-  la::Line l;
-  l.a = la::v3(f.point_a[0], f.point_a[1], f.point_a[2]);
-  l.b = la::v3(f.point_b[0], f.point_b[1], f.point_b[2]);
-  return l;
-}
-inline void lal_put(const la::V3 v, double* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
-inline bool lal_finite(const dgs_line_feature* l, int64_t n) {
-  for (int64_t i = 0; i < n; i++)
-    for (int a = 0; a < 3; a++)
-      if (!std::isfinite(l[i].point_a[a]) || !std::isfinite(l[i].point_b[a])) return false;
-  return true;
-}
 inline size_t lal_align8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 // the l_* members of a struct that has them, upstream's defaults for one that ends before them
@@ -349,20 +272,13 @@ dgs_line_align_params lal_params(const dgs_line_align_params* p) {
   return q;
 }
 const char* lal_bad_params(const dgs_line_align_params* p) {
-  if (!p) return "line align: params is NULL";
-  if (p->struct_size != offsetof(dgs_line_align_params, l_avg_distance_weight) && p->struct_size != sizeof(dgs_line_align_params))
-    return "line align: wrong struct_size";
+  if (const char* why = la::params_guard(p)) return why;
   const dgs_line_align_params q = lal_params(p);
   if (!(q.l_max_score_distance > 0.0) || !(q.l_max_score_translation > 0.0)) return "line align: the max_score values must be positive";
   for (const double w : {q.l_avg_distance_weight, q.l_coverage_weight, q.l_transform_weight})
     if (!(w >= 0.0)) return "line align: an l_* weight is negative or NaN";
   if (std::isnan(q.l_max_distance) || std::isnan(q.l_max_angle)) return "line align: l_max_distance / l_max_angle is NaN";
   return nullptr;
-}
-
-void lal_matrix(const la::Tf t, double* T) {
-  const double m[16] = {t.r00, t.r01, 0.0, t.tx, t.r10, t.r11, 0.0, t.ty, 0.0, 0.0, 1.0, t.tz, 0.0, 0.0, 0.0, 1.0};
-  std::memcpy(T, m, sizeof(m));
 }
 
 }  // namespace
@@ -383,16 +299,14 @@ extern "C" {
 int dgs_line_edges_angular(const dgs_line_feature* lines, int64_t n, int32_t only_angular_edges, double max_dist_angular_edge,
                            dgs_edge_feature* edges, int64_t capacity, int64_t* n_edges) {
   if (n < 0 || !n_edges || (n > 0 && !lines) || capacity < 0 || (capacity > 0 && !edges) || std::isnan(max_dist_angular_edge)) return DGS_ERR_INVALID_ARGUMENT;
-  std::vector<la::Line> l;
-  for (int64_t i = 0; i < n; i++) l.push_back(lal_line(lines[i]));
   std::vector<la::Edge> e;
-  la::edge_extraction(l, e, only_angular_edges != 0, max_dist_angular_edge);
+  la::edge_extraction(la::lines_of(lines, n), e, only_angular_edges != 0, max_dist_angular_edge);
   *n_edges = (int64_t)e.size();
   if (*n_edges > capacity) return DGS_ERR_INVALID_ARGUMENT;
   for (size_t i = 0; i < e.size(); i++) {
-    lal_put(e[i].e, edges[i].edge_point);
-    lal_put(e[i].a, edges[i].point_a);
-    lal_put(e[i].b, edges[i].point_b);
+    la::store3(edges[i].edge_point, e[i].e);
+    la::store3(edges[i].point_a, e[i].a);
+    la::store3(edges[i].point_b, e[i].b);
   }
   return DGS_OK;
 }
@@ -423,7 +337,7 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
   }
   const int64_t n_src = why ? 0 : src_offsets[n_items], n_trg = why ? 0 : trg_offsets[n_items];
   if (!why && ((n_src > 0 && !src_lines) || (n_trg > 0 && !trg_lines))) why = "line align: a line array is NULL";
-  if (!why && (!lal_finite(src_lines, n_src) || !lal_finite(trg_lines, n_trg))) why = "line align: a line coordinate is not finite";
+  if (!why && (!la::all_finite(src_lines, n_src) || !la::all_finite(trg_lines, n_trg))) why = "line align: a line coordinate is not finite";
   if (why) {
     h->err = why;
     return DGS_ERR_INVALID_ARGUMENT;
@@ -431,9 +345,10 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
   const dgs_line_align_params prm = lal_params(params);
 
   // ---- the host's share: edges, offsets, the workgroup tables
+  const std::vector<la::Line> src = la::lines_of(src_lines, n_src), trg = la::lines_of(trg_lines, n_trg);
+  const auto part = [](const std::vector<la::Line>& v, int first, int n) { return std::vector<la::Line>(v.begin() + first, v.begin() + first + n); };
   std::vector<LalItem> items((size_t)n_items);
   std::vector<la::Edge> es, et;
-  std::vector<la::Line> lines;
   std::vector<int2> wg1, wg2;
   long long H1 = 0, H2 = 0;
   for (int64_t b = 0; b < n_items; b++) {
@@ -444,12 +359,8 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
     it.trg_off = (int)trg_offsets[b];
     it.es_off = (int)es.size();
     it.et_off = (int)et.size();
-    lines.clear();
-    for (int i = 0; i < it.Ls; i++) lines.push_back(lal_line(src_lines[it.src_off + i]));
-    la::edge_extraction(lines, es, true, 0.01);
-    lines.clear();
-    for (int j = 0; j < it.Lt; j++) lines.push_back(lal_line(trg_lines[it.trg_off + j]));
-    la::edge_extraction(lines, et, true);
+    la::edge_extraction(part(src, it.src_off, it.Ls), es, true, 0.01);
+    la::edge_extraction(part(trg, it.trg_off, it.Lt), et, true);
     it.Es = (int)es.size() - it.es_off;
     it.Et = (int)et.size() - it.et_off;
     it.h1_off = H1;
@@ -477,7 +388,7 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
 
   // ---- one upload
   const size_t b_items = lal_align8(items.size() * sizeof(LalItem)), b_wg1 = lal_align8(wg1.size() * sizeof(int2)), b_wg2 = lal_align8(wg2.size() * sizeof(int2));
-  const size_t n_srcd = (size_t)n_src * 6, n_tbl = (size_t)n_trg * kLalTableDoubles, n_es = es.size() * 9, n_et = et.size() * 9;
+  const size_t n_srcd = (size_t)n_src * 6, n_tbl = (size_t)n_trg * la::kTableDoubles, n_es = es.size() * 9, n_et = et.size() * 9;
   const size_t b_in = b_items + b_wg1 + b_wg2 + (n_srcd + n_tbl + n_es + n_et) * sizeof(double);
   const size_t b_rec = (size_t)n_items * sizeof(LalRecord), b_out = b_rec + n_srcd * sizeof(double);
   const size_t HH = (size_t)std::max<long long>(H1 + H2, 1);
@@ -495,14 +406,10 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
   if (!wg1.empty()) std::memcpy(up + b_items, wg1.data(), wg1.size() * sizeof(int2));
   if (!wg2.empty()) std::memcpy(up + b_items + b_wg1, wg2.data(), wg2.size() * sizeof(int2));
   double* o = reinterpret_cast<double*>(up + b_items + b_wg1 + b_wg2);
-  for (int64_t i = 0; i < n_src; i++) { std::memcpy(o, src_lines[i].point_a, 24); std::memcpy(o + 3, src_lines[i].point_b, 24); o += 6; }
-  for (int64_t j = 0; j < n_trg; j++) {
-    const la::Line l = lal_line(trg_lines[j]);
-    lal_put(l.a, o); lal_put(l.b, o + 3); lal_put(la::normalized(la::sub(l.b, l.a)), o + 6);
-    o += kLalTableDoubles;
-  }
-  for (const std::vector<la::Edge>* ev : {&es, &et})
-    for (const la::Edge& e : *ev) { lal_put(e.e, o); lal_put(e.a, o + 3); lal_put(e.b, o + 6); o += 9; }
+  o = la::pack_lines(src, o);
+  o = la::pack_target_table(trg, la::directions(trg), o);
+  o = la::pack_edges(es, o);
+  la::pack_edges(et, o);
   DGS_HIP_TRY(h, hipMemcpyAsync(s.in.ptr, up, b_in, hipMemcpyHostToDevice, h->stream));
   const LalItem* d_items = reinterpret_cast<const LalItem*>(s.in.ptr);
   const int2* d_wg1 = reinterpret_cast<const int2*>(s.in.ptr + b_items);
@@ -564,8 +471,8 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
     const LalRecord& r = rec[b];
     dgs_line_local_alignment& out = alignments[b];
     std::memset(&out, 0, sizeof(out));
-    lal_matrix(r.t, out.transformation);
-    lal_matrix(r.t_edge, out.edge_transformation);
+    la::matrix(r.t, out.transformation);
+    la::matrix(r.t_edge, out.edge_transformation);
     for (int k = 0; k < 4; k++) {
       out.fitness_score[k] = r.fit[k];
       out.edge_fitness_score[k] = r.fit_edge[k];

@@ -268,6 +268,11 @@ def scenes():
     sc["case4_crossing"] = (cross, R.move(cross, 0.3, 0.2, np.deg2rad(2.0)), {})
     sc["local_range"] = (np.array([R.seg(0.5, 0.49, 4.5, 0.49), R.seg(0.5, 10.51, 4.5, 10.51), R.seg(5.05, 0.02, 5.25, 0.02)], np.float64),
                          np.array([R.seg(0, 0, 5, 0), R.seg(0, 10, 5, 10), R.seg(20, 0, 20, 5)], np.float64), {})
+    # the wave scorer's owner lane wraps: 65 parallel targets, and the nearest of source line 0 by real_distance is index 64, lane 0's second
+    # target.  That pair is local_range's third: 5 cm past the target's end, near (real_distance 0.15 < max_range) and without coverage
+    # (distance DBL_MAX).  Source line 1 lies 0.15 from target 5, covered over its whole length.  Uneven spacing: no two keys are equal.
+    rows = np.array([R.seg(0, 3.0 + 0.37 * j, 5, 3.0 + 0.37 * j) for j in range(64)] + [R.seg(0, 0, 5, 0)], np.float64)
+    sc["owner_wrap"] = (np.array([R.seg(5.05, 0.02, 5.25, 0.02), R.seg(0.6, 5.0, 4.4, 5.0)], np.float64), rows, {})
     # the target holds the source's own corner (the identity, which align_global's identity gate would drop) and copies of it 2.4 m and
     # 2.6 m away
     sc["distance_gate"] = (ELL, np.concatenate([ELL_T, R.move(ELL_T, 0.0, -2.4, 0.0), R.move(ELL_T, 2.6, 0.0, 0.0)]), {})

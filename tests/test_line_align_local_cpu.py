@@ -75,6 +75,17 @@ def test_scenes_cover_what_the_issue_lists():
     assert real[0, 2, 0] < 0.5 and dist[0, 2, 0] == R.DBL_MAX and cov[0, 2, 0] == 0.0      # near, but no coverage: the global rule would count it
     g_fit, g_picks = R.calc_fitness(src[None], trg, R.DEFAULTS, 0.5)
     assert np.array_equal(g_picks[0], lr["base_picks"]) and g_fit[0, 2] == lr["base_fitness"][2] and g_fit[0, 0] != lr["base_fitness"][0]
+    ow = r["owner_wrap"]
+    src, trg, _ = s["owner_wrap"]
+    assert src.shape[0] == 2 and trg.shape[0] == 65
+    real, dist, cov, key = LR.pair_records(src[None], trg)
+    assert int(np.argmin(key[0, 0])) == 64 and np.count_nonzero(key[0, 0] == key[0, 0, 64]) == 1   # lane 0's second target, and no tie
+    assert real[0, 0, 64] < 0.5 and dist[0, 0, 64] == R.DBL_MAX and cov[0, 0, 64] == 0.0              # near, but no coverage
+    j1 = int(np.argmin(key[0, 1]))
+    assert j1 < 64 and dist[0, 1, j1] < 0.5 and cov[0, 1, j1] > 0.0                                   # an ordinary covered neighbour
+    assert np.array_equal(ow["base_picks"], [64, j1]) and np.array_equal(ow["base_included"], [False, True])
+    g_fit, g_picks = R.calc_fitness(src[None], trg, R.DEFAULTS, 0.5)                                  # the global rule counts line 0
+    assert np.array_equal(g_picks[0], ow["base_picks"]) and g_fit[0, 2] == ow["base_fitness"][2] and g_fit[0, 0] != ow["base_fitness"][0]
     d = r["distance_gate"]
     tn = d["tn1"]
     assert np.any((tn > 2.3) & (tn < 2.5) & (d["gate1"] == LR.GATE_PASS)) and np.any((tn > 2.5) & (tn < 2.7) & (d["gate1"] == LR.GATE_DISTANCE))
