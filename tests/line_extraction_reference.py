@@ -125,7 +125,7 @@ def walk(counts, n, max_iterations):
 
 
 def ransac(pts, prm, raw=None):
-    """-> dict(status 'ok' | 'failed' | 'stream_end', draws, iterations, sample, p0, u)."""
+    """-> dict(status 'ok' | 'failed' | 'stream_end', draws, iterations, sample, p0, u, winner_rank: the walk's `win`)."""
     n = pts.shape[0]
     stream = draw_stream(n, raw)
     hyps = []
@@ -153,7 +153,7 @@ def ransac(pts, prm, raw=None):
     except StreamEnd:
         return dict(status="stream_end", draws=state["draws"], iterations=len(hyps), sample=(-1, -1))
     i0, i1, p0, u = hyps[win]
-    return dict(status="ok", draws=state["draws"], iterations=it, sample=(i0, i1), p0=p0, u=u)
+    return dict(status="ok", draws=state["draws"], iterations=it, sample=(i0, i1), p0=p0, u=u, winner_rank=win)
 
 
 def _trig(theta_args, trig):
@@ -309,8 +309,8 @@ def statistics(pts, clu, line, d):
 
 
 def line_extraction(cloud, params=None, raw=None, trig="f32"):
-    """-> (lines, rounds, status).  lines: dicts A, B, mean, sigma, max, min; rounds: dicts with the trace, the index lists and, for an
-    evaluated cluster, mean and length (what the thresholds see)."""
+    """-> (lines, rounds, status).  lines: dicts A, B, mean, sigma, max, min; rounds: dicts with the trace, the index lists, for a round
+    with a winner its rank among the hypotheses (winner_rank) and, for an evaluated cluster, mean and length (what the thresholds see)."""
     prm = dict(DEFAULTS)
     prm.update(params or {})
     pts = np.ascontiguousarray(cloud, F).copy()
@@ -334,7 +334,7 @@ def line_extraction(cloud, params=None, raw=None, trig="f32"):
         inl = np.nonzero(inlier_mask(pts, r["p0"], r["u"], prm["sac_distance_threshold"], prm["sqnorm_order"]))[0]
         line, d = refit(pts, inl, r["p0"], r["u"], trig)
         clu = cluster(pts, inl, prm)
-        rec.update(sample=r["sample"], inliers=int(inl.size), inlier_idx=inl, cluster=0 if clu is None else int(clu.size),
+        rec.update(sample=r["sample"], winner_rank=r["winner_rank"], inliers=int(inl.size), inlier_idx=inl, cluster=0 if clu is None else int(clu.size),
                    cluster_idx=np.zeros(0, np.int64) if clu is None else clu)
         if clu is None:
             status = "STALL"
