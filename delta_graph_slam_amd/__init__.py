@@ -1,6 +1,6 @@
 """delta_graph_slam_amd -- MI355X-native scan registration (NDT / GICP) hot path."""
 
-__all__ = ["MapCloudGenerator", "LineExtractor", "LineScanMatcher"]
+__all__ = ["MapCloudGenerator", "LineExtractor", "LineScanMatcher", "BuildingOverlap"]
 
 
 def __getattr__(name):   # resolved on first use: importing the package alone loads neither torch nor the HIP library
@@ -13,4 +13,7 @@ def __getattr__(name):   # resolved on first use: importing the package alone lo
     if name == "LineScanMatcher":
         from .line_align import LineScanMatcher
         return LineScanMatcher
+    if name == "BuildingOverlap":
+        from .building_overlap import BuildingOverlap
+        return BuildingOverlap
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

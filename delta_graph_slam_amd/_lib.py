@@ -10,7 +10,8 @@ LIB_PATH = os.environ.get("DGS_REG_LIB") or os.path.join(_HERE, "libdgs_reg.so")
 
 DGS_OK = 0
 STATUS = {0: "DGS_OK", 1: "DGS_ERR_INVALID_ARGUMENT", 2: "DGS_ERR_HIP", 3: "DGS_ERR_NO_TARGET", 4: "DGS_ERR_NO_SOURCE",
-          5: "DGS_ERR_GRID_TOO_LARGE", 6: "DGS_ERR_UNSUPPORTED"}
+          5: "DGS_ERR_GRID_TOO_LARGE", 6: "DGS_ERR_UNSUPPORTED", 7: "DGS_ERR_CAPACITY"}
+DGS_ERR_CAPACITY = 7
 METHOD_NDT, METHOD_GICP, METHOD_VGICP, METHOD_ICP, METHOD_PCL_GICP = 0, 1, 2, 3, 4
 VGICP_SEARCH = {"DIRECT1": 0, "DIRECT7": 1, "DIRECT27": 2}
 NDT_SEARCH = {"KDTREE": 0, "DIRECT26": 1, "DIRECT7": 2, "DIRECT1": 3}
@@ -120,6 +121,18 @@ class LineAlignLocalHypothesis(C.Structure):
                 ("fitness_score", C.c_double * 4), ("score", C.c_double)]
 
 
+class LineOverlapAlignment(C.Structure):
+    _fields_ = [("transformation", C.c_double * 16), ("translation_norm", C.c_double), ("winner", C.c_int64),
+                ("n_hypotheses_edge", C.c_int64), ("n_hypotheses_line", C.c_int64), ("n_angle_passed", C.c_int64),
+                ("n_not_overlapped", C.c_int64), ("n_edges_source", C.c_int32), ("n_edges_target", C.c_int32),
+                ("is_identity", C.c_int32), ("status", C.c_int32)]
+
+
+class LineAlignOverlappedHypothesis(C.Structure):
+    _fields_ = [("gate", C.c_int32), ("reserved", C.c_int32), ("rotation", C.c_double * 4), ("translation", C.c_double * 3),
+                ("translation_norm", C.c_double)]
+
+
 class EdgeFeatureC(C.Structure):
     _fields_ = [("edge_point", C.c_double * 3), ("point_a", C.c_double * 3), ("point_b", C.c_double * 3)]
 
@@ -130,7 +143,8 @@ class LineAlignHypothesis(C.Structure):
 
 
 LA_STATUS = {0: "ALIGNED", 1: "NO_HYPOTHESES", 2: "ALL_GATED", 3: "NONE_BETTER", 4: "LINE_ALIGNED"}
-LA_GATE = {0: "PASS", 1: "DISTANCE", 2: "IDENTITY", 3: "ANGLE", 4: "LINE_DIRECTION", 5: "LINE_DISTANCE", 6: "RANK"}
+LA_GATE = {0: "PASS", 1: "DISTANCE", 2: "IDENTITY", 3: "ANGLE", 4: "LINE_DIRECTION", 5: "LINE_DISTANCE", 6: "RANK", 7: "OVERLAP"}
+BO_MAX_BUILDINGS = 1 << 14
 LE_STATUS = {0: "DONE", 1: "RANSAC_FAILED", 2: "STALL", 3: "MAX_ROUNDS", 4: "RNG_EXHAUSTED"}
 SAC_METHODS = ["SAC_RANSAC", "SAC_LMEDS", "SAC_MSAC", "SAC_RRANSAC", "SAC_RMSAC", "SAC_MLESAC", "SAC_PROSAC"]
 MAP_DEDUP = {"AUTO": 0, "HASH": 1, "SORT": 2}
@@ -166,6 +180,8 @@ SYMBOLS = [
     "dgs_line_extraction_params_init", "dgs_line_extraction", "dgs_line_extraction_get_rounds",
     "dgs_line_align_params_init", "dgs_line_align_global", "dgs_line_merge", "dgs_line_edges", "dgs_line_align_get_hypotheses",
     "dgs_line_align_local_batch", "dgs_line_align_local", "dgs_line_edges_angular", "dgs_line_align_local_get_hypotheses",
+    "dgs_building_overlap_pairs", "dgs_line_align_overlapped_batch", "dgs_line_align_overlapped", "dgs_line_align_overlapped_get_hypotheses",
+    "dgs_building_overlap_get_counts",
 ]
 
 _libs = {}
@@ -300,5 +316,12 @@ def load(path=None):
                                          P(LineLocalAlignment)]
     lib.dgs_line_edges_angular.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64, P(C.c_int64)]
     lib.dgs_line_align_local_get_hypotheses.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.dgs_building_overlap_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_line_align_overlapped_batch.argtypes = [C.c_void_p, P(LineAlignParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dgs_line_align_overlapped.argtypes = [C.c_void_p, P(LineAlignParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, P(LineOverlapAlignment)]
+    lib.dgs_line_align_overlapped_get_hypotheses.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
+    lib.dgs_building_overlap_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib

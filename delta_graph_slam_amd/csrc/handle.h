@@ -197,6 +197,20 @@ struct LalScratch {
   std::vector<int64_t> off1, off2;     // of the last call: first hypothesis per item and phase (n_items + 1 entries; phase 1 after all of phase 0)
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
+// are_buildings_overlapped over all pairs and align_overlapped_buildings, batched (building_overlap.hip): scratch of its own.
+struct BoHyp;     // building_overlap.hip
+struct BoScratch {
+  DevBuf<unsigned char> in;            // pair search, one upload: line offsets, centres, line end points
+  DevBuf<double> shr;                  // x1 y1 x2 y2 of every shrunken line
+  DevBuf<unsigned long long> bits;     // pair flags: row i, word j / 64, bit j % 64
+  DevBuf<int> row;                     // pairs per row, then their exclusive scan (n_buildings + 1 entries)
+  DevBuf<unsigned char> out;           // one download: the count, then the pairs
+  DevBuf<unsigned char> ain;           // alignment, one upload: item table, workgroup table, lines, edges
+  DevBuf<BoHyp> hyps;                  // per hypothesis of the batch, at the item's offset
+  DevBuf<unsigned char> aout;          // one download: a record per item, then the aligned lines
+  std::vector<int64_t> off;            // of the last alignment call: first hypothesis per item (n_items + 1 entries)
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
 
 }  // namespace dgs
 
@@ -404,6 +418,7 @@ struct dgs_handle {
   dgs::LnScratch ln;
   dgs::LaScratch la;
   dgs::LalScratch lal;
+  dgs::BoScratch bo;
 
   dgs::Profiler prof;
 };
@@ -490,6 +505,8 @@ void line_extraction_release(dgs_handle* h);
 void line_align_release(dgs_handle* h);
 // line_align_local.hip
 void line_align_local_release(dgs_handle* h);
+// building_overlap.hip
+void building_overlap_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -13,6 +13,11 @@ host-only pieces and need no GPU.
 buildings -- goes to the device in one call.  The matcher's `l_*` members and the nodelet's `delta_local_*` names set weight_local,
 except `delta_local_avg_distance_weight`: upstream's setter of that name writes the global member, so the nodelet never changes
 l_avg_distance_weight; the name is accepted and ignored here, as dgs::HipLineAligner does not read it (INTEGRATION.md 4f).
+
+`align_overlapped(lines_source, lines_target, center_source, center_target)` and `align_overlapped_batch(items)` are
+LineBasedScanmatcher::align_overlapped_buildings (:29-107; dgs_line_align_overlapped_batch, DESIGN.md 6h) from the building-frame lines
+on: the smallest move of the source building that passes the pi / 3 angle gate and leaves the two shrunken polygons apart.  The frame
+transforms around it stay with the caller.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ import numpy as np
 from . import _lib as L
 from .line_extraction import LineFeature
 
-__all__ = ["LineScanMatcher", "BestFitAlignment", "LocalAlignment", "FitnessScore", "EdgeFeature", "merge_lines", "edge_extraction",
+__all__ = ["LineScanMatcher", "BestFitAlignment", "LocalAlignment", "OverlapAlignment", "FitnessScore", "EdgeFeature", "merge_lines", "edge_extraction",
            "params_from_dict"]
 
 _NAMES = {   # member name -> the nodelet's parameter name
@@ -81,6 +86,19 @@ class LocalAlignment(BestFitAlignment):
     edge_score: float = 0.0
     baseline_fitness_score: Optional[FitnessScore] = None
     baseline_score: float = 0.0
+
+
+@dataclass
+class OverlapAlignment:
+    """align_overlapped_buildings' BestFitAlignment in the source building's frame (upstream sets no fitness score there)."""
+    not_aligned_lines: List[LineFeature]
+    aligned_lines: List[LineFeature]
+    transformation: np.ndarray            # 4 x 4 float64: the winner's transform, or the identity
+    translation_norm: float               # DBL_MAX without a winner
+    winner: int                           # h = es * Et + et, then Es * Et + i * Lt + j; -1: none
+    is_identity: bool                     # the nodelet adds no edge then (:875)
+    status: str                           # L.LA_STATUS
+    counts: dict = field(default_factory=dict)   # hypotheses_edge, hypotheses_line, angle_passed, not_overlapped, edges_source, edges_target
 
 
 def params_from_dict(params: Optional[dict] = None):
@@ -160,6 +178,7 @@ class LineScanMatcher:
         self._lib = registration._lib
         self.extractor = LineExtractor(rest, registration=registration)
         self._local_sizes = []
+        self._overlap_sizes = []
 
     @property
     def _h(self):
@@ -220,6 +239,38 @@ class LineScanMatcher:
                 baseline_fitness_score=FitnessScore(*a.baseline_fitness_score[:]), baseline_score=a.baseline_score))
         return res
 
+    def align_overlapped(self, lines_source: List[LineFeature], lines_target: List[LineFeature], center_source=(0.0, 0.0, 0.0),
+                         center_target=(0.0, 0.0, 0.0)) -> "OverlapAlignment":
+        """align_overlapped_buildings (:29-107) of one pair in the source building's frame: a batch of one."""
+        return self.align_overlapped_batch([(lines_source, lines_target, center_source, center_target)])[0]
+
+    def align_overlapped_batch(self, items) -> List["OverlapAlignment"]:
+        """`items`: a sequence of (lines_source, lines_target, center_source, center_target), e.g. every overlapped pair (A, B) of a round
+        in A's frame.  One device call: one upload, one download, one host wait, three launches."""
+        items = [(list(s), list(t), cs, ct) for s, t, cs, ct in items]
+        n = len(items)
+        so = (C.c_int64 * (n + 1))()
+        to = (C.c_int64 * (n + 1))()
+        for b, (s, t, _, _) in enumerate(items):
+            so[b + 1], to[b + 1] = so[b] + len(s), to[b] + len(t)
+        src = _to_c([l for it in items for l in it[0]])
+        trg = _to_c([l for it in items for l in it[1]])
+        cs = np.ascontiguousarray(np.array([np.asarray(it[2], np.float64).reshape(3) for it in items], np.float64).reshape(-1, 3))
+        ct = np.ascontiguousarray(np.array([np.asarray(it[3], np.float64).reshape(3) for it in items], np.float64).reshape(-1, 3))
+        out = (L.LineFeatureC * max(so[n], 1))()
+        al = (L.LineOverlapAlignment * max(n, 1))()
+        self.registration._check(self._lib.dgs_line_align_overlapped_batch(
+            self._h, C.byref(self.params), n, C.cast(src, C.c_void_p), C.cast(so, C.c_void_p), C.cast(trg, C.c_void_p), C.cast(to, C.c_void_p),
+            cs.ctypes.data if n else None, ct.ctypes.data if n else None, C.cast(out, C.c_void_p), C.cast(al, C.c_void_p)))
+        aligned = _from_c(out, so[n])
+        self._overlap_sizes = [al[b].n_hypotheses_edge + al[b].n_hypotheses_line for b in range(n)]   # what overlapped_hypotheses may read
+        return [OverlapAlignment(
+            not_aligned_lines=it[0], aligned_lines=aligned[so[b]:so[b + 1]], transformation=np.array(al[b].transformation[:], np.float64).reshape(4, 4),
+            translation_norm=al[b].translation_norm, winner=al[b].winner, is_identity=bool(al[b].is_identity), status=L.LA_STATUS[al[b].status],
+            counts=dict(hypotheses_edge=al[b].n_hypotheses_edge, hypotheses_line=al[b].n_hypotheses_line, angle_passed=al[b].n_angle_passed,
+                        not_overlapped=al[b].n_not_overlapped, edges_source=al[b].n_edges_source, edges_target=al[b].n_edges_target))
+            for b, it in enumerate(items)]
+
     # -- test hooks ----------------------------------------------------------------------------------------------------------
     def hypotheses(self, first: int = 0, count: Optional[int] = None):
         """Per-hypothesis records of the last call as arrays: gate, slot, rotation [n,4], translation [n,3], fitness [n,4], score."""
@@ -256,3 +307,20 @@ class LineScanMatcher:
         self.registration._check(self._lib.dgs_line_align_local_get_hypotheses(self._h, 0, 0, 0, 0, None, C.cast(c, C.c_void_p)))
         return dict(launches=c[0], host_waits=c[1], items=c[2], hypotheses_edge=c[3], hypotheses_line=c[4], survivors_edge=c[5],
                     survivors_line=c[6], workgroups=c[7])
+
+    def overlapped_hypotheses(self, item: int, first: int = 0, count: Optional[int] = None):
+        """Per-hypothesis records of the last align_overlapped / align_overlapped_batch call for one item as arrays: gate, rotation [n,4],
+        translation [n,3], tn.  `count` None: all of the item's hypotheses from `first` on."""
+        if count is None:
+            count = self._overlap_sizes[item] - first
+        rec = (L.LineAlignOverlappedHypothesis * max(count, 1))()
+        self.registration._check(self._lib.dgs_line_align_overlapped_get_hypotheses(self._h, item, first, count, C.cast(rec, C.c_void_p)))
+        a = np.frombuffer(rec, dtype=np.dtype([("gate", "<i4"), ("reserved", "<i4"), ("rotation", "<f8", 4), ("translation", "<f8", 3),
+                                               ("tn", "<f8")]))[:count]
+        return {k: a[k].copy() for k in ("gate", "rotation", "translation", "tn")}
+
+    def overlapped_counts(self):
+        """-> dict(launches, host_waits, items, hypotheses) of the last align_overlapped / align_overlapped_batch call."""
+        c = (C.c_int64 * 8)()
+        self.registration._check(self._lib.dgs_building_overlap_get_counts(self._h, C.cast(c, C.c_void_p)))
+        return dict(launches=c[4], host_waits=c[5], items=c[6], hypotheses=c[7])

@@ -10,6 +10,8 @@
 // all near buildings of a keyframe.  They also set BestFitAlignmentT::isEdgeAligned.  The l_* weights come from the
 // nodelet's delta_local_* parameters (apps/delta_graph_slam_nodelet.cpp:105-108); delta_local_avg_distance_weight is not read, because
 // upstream's setter of that name writes the global member, so l_avg_distance_weight keeps the constructor's 0.6.
+// alignOverlappedBatch() is LineBasedScanmatcher::align_overlapped_buildings (:29-107; dgs_line_align_overlapped_batch) from
+// the building-frame lines on, one call for all overlapped pairs of a round; the caller keeps the frame transforms.
 #pragma once
 
 #include <cstddef>
@@ -127,6 +129,57 @@ class HipLineAligner {
     }
     return true;
   }
+  struct OverlapItem {   // one overlapped pair (A, B) in A's frame: A's and B's lines, A's centre (upstream: zero) and B's
+    const std::vector<LinePtr>* linesSource;
+    const std::vector<LinePtr>* linesTarget;
+    double center_source[3];
+    double center_target[3];
+  };
+  const std::vector<dgs_line_overlap_alignment>& lastOverlapped() const { return lov_; }   // winners, counts, is_identity of the last batch
+
+  // One device call for all items.  Sets not_aligned_lines, aligned_lines and transformation; false: *results is untouched.
+  bool alignOverlappedBatch(const std::vector<OverlapItem>& items, std::vector<BestFitAlignmentT>* results) {
+    if (!results || !ensure_handle()) return false;
+    src_.clear();
+    trg_.clear();
+    so_.assign(1, 0);
+    to_.assign(1, 0);
+    cs_.clear();
+    ct_.clear();
+    for (const OverlapItem& it : items) {
+      append(*it.linesSource, &src_);
+      append(*it.linesTarget, &trg_);
+      so_.push_back((int64_t)src_.size());
+      to_.push_back((int64_t)trg_.size());
+      cs_.insert(cs_.end(), it.center_source, it.center_source + 3);
+      ct_.insert(ct_.end(), it.center_target, it.center_target + 3);
+    }
+    out_.resize(src_.size() ? src_.size() : 1);
+    lov_.assign(items.size() ? items.size() : 1, dgs_line_overlap_alignment{});
+    if (dgs_line_align_overlapped_batch(h_, &p_, (int64_t)items.size(), src_.data(), so_.data(), trg_.data(), to_.data(), cs_.data(), ct_.data(),
+                                        out_.data(), lov_.data()) != DGS_OK)
+      return false;
+    lov_.resize(items.size());
+    results->assign(items.size(), BestFitAlignmentT());
+    for (size_t b = 0; b < items.size(); b++) {
+      BestFitAlignmentT& r = (*results)[b];
+      const std::vector<LinePtr>& ls = *items[b].linesSource;
+      r.not_aligned_lines = ls;
+      for (size_t i = 0; i < ls.size(); i++) {
+        auto line = std::make_shared<LineFeatureT>(*ls[i]);
+        for (int a = 0; a < 3; a++) {
+          line->pointA[a] = out_[(size_t)so_[b] + i].point_a[a];
+          line->pointB[a] = out_[(size_t)so_[b] + i].point_b[a];
+        }
+        r.aligned_lines.push_back(line);
+      }
+      for (int rr = 0; rr < 4; rr++)
+        for (int c = 0; c < 4; c++) r.transformation(rr, c) = lov_[b].transformation[4 * rr + c];
+    }
+    return true;
+  }
+  dgs_handle* handle() { return ensure_handle() ? h_ : nullptr; }   // for the test hooks
+
   bool alignLocal(const std::vector<LinePtr>& linesSource, const std::vector<LinePtr>& linesTarget, double max_range, BestFitAlignmentT* result) {
     std::vector<BestFitAlignmentT> r;
     if (!result || !alignLocalBatch({LocalItem{&linesSource, &linesTarget}}, max_range, &r)) return false;
@@ -169,6 +222,8 @@ class HipLineAligner {
   std::vector<dgs_line_feature> src_, trg_, out_;
   std::vector<int64_t> so_, to_;
   std::vector<dgs_line_local_alignment> lal_;
+  std::vector<dgs_line_overlap_alignment> lov_;
+  std::vector<double> cs_, ct_;
 };
 
 }  // namespace dgs

@@ -43,7 +43,8 @@ enum dgs_status {
   DGS_ERR_NO_TARGET = 3,      /* align()/fitness before setInputTarget (PCL: "no input target dataset") */
   DGS_ERR_NO_SOURCE = 4,
   DGS_ERR_GRID_TOO_LARGE = 5, /* voxel index would overflow (pcl::VoxelGridCovariance: "Leaf size is too small") */
-  DGS_ERR_UNSUPPORTED = 6
+  DGS_ERR_UNSUPPORTED = 6,
+  DGS_ERR_CAPACITY = 7        /* dgs_building_overlap_pairs: more results than `capacity`; the first `capacity` are written, the count is full */
 };
 
 /* registration_method strings of registrations.cpp:26-124 that this library serves */
@@ -640,7 +641,8 @@ enum dgs_line_align_gate {
   DGS_LA_GATE_ANGLE = 3,    /* constrain_angle (align_local: always) and cos(angle) < cos(max_angle) */
   DGS_LA_GATE_LINE_DIRECTION = 4, /* align_local's line pairs: |cos| between the two directions < cos(max_angle) */
   DGS_LA_GATE_LINE_DISTANCE = 5,  /* align_local's line pairs: align_lines' translation.norm() > max_distance */
-  DGS_LA_GATE_RANK = 6      /* align_local's line pairs with refine_three_nearest: a neighbour of rank >= 3, not visited */
+  DGS_LA_GATE_RANK = 6,     /* align_local's line pairs with refine_three_nearest: a neighbour of rank >= 3, not visited */
+  DGS_LA_GATE_OVERLAP = 7   /* align_overlapped: the angle gate passed, the moved source still overlaps the target */
 };
 #define DGS_LA_MAX_LINES_SOURCE 256       /* what limits Ls, Lt and the hypothesis count */
 #define DGS_LA_MAX_LINES_TARGET 512       /* after merging */
@@ -781,6 +783,64 @@ typedef struct dgs_line_align_local_hypothesis {
  * phase 0 and of phase 1, and workgroups of the two scoring launches together, all of the last call. */
 int dgs_line_align_local_get_hypotheses(dgs_handle* h, int64_t item, int32_t phase, int64_t first, int64_t count,
                                         dgs_line_align_local_hypothesis* records, int64_t* counts8);
+
+/* ---- are_buildings_overlapped and LineBasedScanmatcher::align_overlapped_buildings on the device ---------------------------------
+ * (include/hdl_graph_slam/check_overlapping.hpp; src/hdl_graph_slam/line_based_scanmatcher.cpp:29-107; the loop of
+ * apps/delta_graph_slam_nodelet.cpp:846-900).  Semantics, the deliberate non-differences from the geometric predicate, the limits
+ * and the memory formula: DESIGN.md 6h.  Own buffers on the handle: registration, prefilter, map, line-extraction and the two
+ * aligners' state are untouched.  Additions only: DGS_ABI_VERSION is unchanged. */
+#define DGS_BO_MAX_BUILDINGS (1 << 14)    /* the pair flags take B * B / 8 bytes: 32 MiB here */
+#define DGS_LA_OVERLAP_MAX_ANGLE 1.0471975511965976 /* M_PI / 3.0 (:47) */
+/* getOverlappedBuildings (nodelet :767-787): every pair i < j of the n_buildings buildings whose shrunken polygons intersect
+ * (are_buildings_overlapped), i ascending, then j ascending.  lines: the lines of all buildings back to back; line_offsets:
+ * n_buildings + 1 ascending offsets; centers: double[n_buildings][3], x and y are read.  pairs: int32[capacity][2] (nullable with
+ * capacity 0).  *n_pairs is always the full count; with more pairs than `capacity` the first `capacity` are written and the call
+ * returns DGS_ERR_CAPACITY.  More than DGS_BO_MAX_BUILDINGS buildings, more than DGS_LA_MAX_LINES_TARGET lines in one building or a
+ * coordinate that is not finite is DGS_ERR_INVALID_ARGUMENT with a message.  One upload, one download, one host wait, five launches. */
+int dgs_building_overlap_pairs(dgs_handle* h, const dgs_line_feature* lines, const int64_t* line_offsets, const double* centers,
+                               int64_t n_buildings, int32_t* pairs, int64_t capacity, int64_t* n_pairs);
+typedef struct dgs_line_overlap_alignment {
+  double transformation[16];       /* row-major 4 x 4: the winner's transform, or the identity */
+  double translation_norm;         /* the winner's translation.norm(); DBL_MAX (upstream's start value) without a winner */
+  int64_t winner;                  /* h = es * Et + et for an edge pair, Es * Et + i * Lt + j for a line pair; -1: none */
+  int64_t n_hypotheses_edge;       /* Es * Et */
+  int64_t n_hypotheses_line;       /* Ls * Lt */
+  int64_t n_angle_passed;          /* hypotheses past the angle gate */
+  int64_t n_not_overlapped;        /* and past the overlap gate */
+  int32_t n_edges_source;
+  int32_t n_edges_target;
+  int32_t is_identity;             /* the transformation is bit-equal to the identity: the nodelet adds no edge then (:875) */
+  int32_t status;                  /* dgs_line_align_status: ALIGNED, NO_HYPOTHESES, ALL_GATED (no hypothesis passed both gates),
+                                      NONE_BETTER (one passed, but its norm is NaN or not below DBL_MAX) */
+} dgs_line_overlap_alignment;
+/* align_overlapped_buildings from the building-frame lines on, for n_items independent (source, target) pairs: the caller keeps the
+ * frame transforms around it.  Layout of lines, offsets and aligned_lines as in dgs_line_align_local_batch;
+ * centers_source / centers_target: double[n_items][3] (upstream: zero, and B's centre in A's frame).  Of `params` only
+ * angle_gate_float_chain is read; the angle is DGS_LA_OVERLAP_MAX_ANGLE.  Edges come from edge_extraction with its defaults on the
+ * host; one upload, one download, one host wait, three launches.  DGS_LA_MAX_ITEMS, DGS_LA_MAX_LINES_SOURCE / _TARGET per item and
+ * DGS_LA_MAX_HYPOTHESES summed over the batch as for align_local; 72 bytes of device memory per hypothesis. */
+int dgs_line_align_overlapped_batch(dgs_handle* h, const dgs_line_align_params* params, int64_t n_items, const dgs_line_feature* src_lines,
+                                    const int64_t* src_offsets, const dgs_line_feature* trg_lines, const int64_t* trg_offsets,
+                                    const double* centers_source, const double* centers_target, dgs_line_feature* aligned_lines,
+                                    dgs_line_overlap_alignment* alignments);
+/* a batch of one */
+int dgs_line_align_overlapped(dgs_handle* h, const dgs_line_align_params* params, const dgs_line_feature* src_lines, int64_t n_src,
+                              const dgs_line_feature* trg_lines, int64_t n_trg, const double* center_source, const double* center_target,
+                              dgs_line_feature* aligned_lines, dgs_line_overlap_alignment* alignment);
+/* Test hook: what the device computed per hypothesis in the last dgs_line_align_overlapped_batch call. */
+typedef struct dgs_line_align_overlapped_hypothesis {
+  int32_t gate;           /* DGS_LA_GATE_PASS, DGS_LA_GATE_ANGLE or DGS_LA_GATE_OVERLAP */
+  int32_t reserved;
+  double rotation[4];     /* r00 r01 r10 r11 of align_edges' / align_lines' transform */
+  double translation[3];
+  double translation_norm;
+} dgs_line_align_overlapped_hypothesis;
+/* records: room for `count` records of hypotheses first .. first + count - 1 of `item` (nullable) */
+int dgs_line_align_overlapped_get_hypotheses(dgs_handle* h, int64_t item, int64_t first, int64_t count,
+                                             dgs_line_align_overlapped_hypothesis* records);
+/* counts8: of the last dgs_building_overlap_pairs call kernel launches, host waits, buildings, pairs; of the last
+ * dgs_line_align_overlapped_batch call kernel launches, host waits, items, hypotheses. */
+int dgs_building_overlap_get_counts(dgs_handle* h, int64_t* counts8);
 
 #ifdef __cplusplus
 }
