@@ -12,7 +12,7 @@ DGS_OK = 0
 STATUS = {0: "DGS_OK", 1: "DGS_ERR_INVALID_ARGUMENT", 2: "DGS_ERR_HIP", 3: "DGS_ERR_NO_TARGET", 4: "DGS_ERR_NO_SOURCE",
           5: "DGS_ERR_GRID_TOO_LARGE", 6: "DGS_ERR_UNSUPPORTED", 7: "DGS_ERR_CAPACITY"}
 DGS_ERR_CAPACITY = 7
-METHOD_NDT, METHOD_GICP, METHOD_VGICP, METHOD_ICP, METHOD_PCL_GICP = 0, 1, 2, 3, 4
+METHOD_NDT, METHOD_GICP, METHOD_VGICP, METHOD_ICP, METHOD_PCL_GICP, METHOD_PCL_NDT = 0, 1, 2, 3, 4, 5
 VGICP_SEARCH = {"DIRECT1": 0, "DIRECT7": 1, "DIRECT27": 2}
 NDT_SEARCH = {"KDTREE": 0, "DIRECT26": 1, "DIRECT7": 2, "DIRECT1": 3}
 NDT_ORDER = {"FAST": 0, "UPSTREAM": 1, "UPSTREAM_SEQUENTIAL": 2}
@@ -164,7 +164,7 @@ SYMBOLS = [
     "dgs_synchronize", "dgs_set_input_target", "dgs_set_input_source", "dgs_align", "dgs_get_fitness_score",
     "dgs_get_inlier_fraction", "dgs_nearest_search_target", "dgs_nn_fitness_distances", "dgs_align_batch", "dgs_find_loop_candidates", "dgs_calc_fitness_score", "dgs_voxel_grid_filter", "dgs_approx_voxel_grid_filter", "dgs_cloud_create", "dgs_cloud_destroy", "dgs_cloud_size",
     "dgs_set_input_target_cloud", "dgs_set_input_source_cloud", "dgs_align_batch_clouds", "dgs_profile_enable",
-    "dgs_profile_get", "dgs_profile_reset", "dgs_get_counts", "dgs_ndt_derivatives", "dgs_ndt_hessian_double", "dgs_ndt_get_voxels",
+    "dgs_profile_get", "dgs_profile_reset", "dgs_get_counts", "dgs_ndt_derivatives", "dgs_ndt_hessian_double", "dgs_pcl_ndt_neighbours", "dgs_ndt_get_voxels",
     "dgs_ndt_get_trajectory", "dgs_gicp_get_covariances", "dgs_gicp_linearize", "dgs_vgicp_get_voxels",
     "dgs_group_create", "dgs_group_destroy", "dgs_group_last_error", "dgs_group_size", "dgs_group_uses_rccl", "dgs_group_rccl_ranks", "dgs_group_last_gather_used_rccl",
     "dgs_group_member", "dgs_group_set_input_target", "dgs_group_align_batch",
@@ -236,6 +236,7 @@ def load(path=None):
     lib.dgs_get_counts.argtypes = [C.c_void_p, P(C.c_int64)]
     lib.dgs_ndt_derivatives.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_double), C.c_void_p, C.c_void_p]
     lib.dgs_ndt_hessian_double.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dgs_pcl_ndt_neighbours.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     lib.dgs_ndt_get_voxels.argtypes = [C.c_void_p, P(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dgs_ndt_get_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, P(C.c_int32)]
     lib.dgs_gicp_get_covariances.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

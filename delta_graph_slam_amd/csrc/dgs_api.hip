@@ -36,7 +36,7 @@ int ensure_poll_events(dgs_handle* h) {
 }
 
 // The methods a handle can be made for (dgs_method), and what dgs_align / the batch calls run for each.  NDT keeps its own branch there.
-static bool valid_method(int32_t m) { return m >= DGS_METHOD_NDT && m <= DGS_METHOD_PCL_GICP; }
+static bool valid_method(int32_t m) { return m >= DGS_METHOD_NDT && m <= DGS_METHOD_PCL_NDT; }
 struct MethodOps {
   int (*align)(dgs_handle*, const float* guess16, dgs_result*);
   int (*align_batch)(dgs_handle*, int n, CloudState* const* srcs, const float* guesses16, dgs_result*);
@@ -48,8 +48,9 @@ static const MethodOps kMethodOps[] = {
     {gicp_align, gicp_align_batch, gicp_final_transforms},                      // DGS_METHOD_VGICP
     {icp_align, icp_align_batch, icp_final_transforms},                         // DGS_METHOD_ICP
     {pcl_gicp_align, pcl_gicp_align_batch, pcl_gicp_final_transforms},          // DGS_METHOD_PCL_GICP
+    {nullptr, nullptr, nullptr},                                                // DGS_METHOD_PCL_NDT: the NDT branch, with pcl_ndt.hip's evaluation kernel
 };
-static_assert(sizeof(kMethodOps) / sizeof(kMethodOps[0]) == DGS_METHOD_PCL_GICP + 1, "one row per dgs_method");
+static_assert(sizeof(kMethodOps) / sizeof(kMethodOps[0]) == DGS_METHOD_PCL_NDT + 1, "one row per dgs_method");
 
 // The side stream is created together with the handle's own stream (dgs_create), not at first use: HIP deals streams to a small number
 // of hardware queues (GPU_MAX_HW_QUEUES, 4 by default) in creation order, and two streams on one hardware queue run one after the
@@ -65,7 +66,7 @@ static int side_create(dgs_handle* h) {
   DGS_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   DGS_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
   // the computeHessian stream of the upstream NDT order: same priority as the main stream, its own hardware queue (created third)
-  if (h->prm.method == DGS_METHOD_NDT) {
+  if (h->prm.method == DGS_METHOD_NDT) {   // (PCL_NDT_HIP: one launch per round, no third stream)
     DGS_HIP_TRY(h, hipStreamCreateWithFlags(&h->hd_stream, hipStreamNonBlocking));
     for (int k = 0; k < dgs_handle::kHdEvents; k++) {
       DGS_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_hd_a[k], hipEventDisableTiming));
@@ -298,6 +299,7 @@ int dgs_params_init(dgs_params* p, int32_t method) {
   p->gicp_lm_max_iterations = 10;
   p->vgicp_search_method = DGS_VGICP_DIRECT1;
   p->vgicp_resolution = 1.0;
+  if (method == DGS_METHOD_PCL_NDT) p->ndt_search_method = DGS_NDT_KDTREE;   // registrations.cpp:93-99: resolution 0.5, epsilon 0.01, 64 iterations as above; the radius search
   return valid_method(method) ? DGS_OK : DGS_ERR_INVALID_ARGUMENT;
 }
 
@@ -403,6 +405,13 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   dgs_handle* h = new (std::nothrow) dgs_handle();
   if (!h) return DGS_ERR_HIP;
   h->prm = *params;
+  if (params->method == DGS_METHOD_PCL_NDT) {
+    // pcl::NDT has one neighbourhood (the radius search = ndt_omp's KDTREE walk) and one arithmetic (double): the three switches are
+    // accepted and without effect, and the NDT driver reads them as the upstream order with the double computeHessian pass
+    h->prm.ndt_search_method = DGS_NDT_KDTREE;
+    h->prm.ndt_strict_order = DGS_NDT_ORDER_UPSTREAM;
+    h->prm.ndt_hessian_recompute_double = 1;
+  }
   int dev = params->device;
   hipError_t e = hipSuccess;
   if (dev < 0) e = hipGetDevice(&dev);
@@ -540,7 +549,7 @@ int dgs_set_input_target(dgs_handle* h, const float* xyz16, int64_t n, int32_t o
   h->nt = n;
   int rc = upload_cloud(h, h->own_target.pts, xyz16, n, on_device);
   if (rc) return rc;
-  if (h->prm.method == DGS_METHOD_NDT) {
+  if (is_ndt_family(h)) {
     rc = ndt_build_target(h);
     if (rc) return rc;
   }
@@ -608,7 +617,7 @@ int dgs_set_input_target_cloud(dgs_handle* h, dgs_cloud* c) {
   bind(h, h->tgt_cloud, c);
   h->tgt = &c->st;
   h->nt = c->st.n;
-  if (h->prm.method == DGS_METHOD_NDT) {
+  if (is_ndt_family(h)) {
     int rc = ndt_build_target(h);
     if (rc) return rc;
   }
@@ -644,7 +653,7 @@ int dgs_align(dgs_handle* h, const float* guess16, dgs_result* out, float* align
   if (!h->have_target || h->nt == 0) { out->status = DGS_ERR_NO_TARGET; h->err = "no input target dataset was given"; return DGS_ERR_NO_TARGET; }
   if (!h->have_source || h->ns == 0) { out->status = DGS_ERR_NO_SOURCE; h->err = "no input source dataset was given"; return DGS_ERR_NO_SOURCE; }
   int rc;
-  if (h->prm.method == DGS_METHOD_NDT) {
+  if (is_ndt_family(h)) {
     const float4* src = h->src->pts.ptr;
     const int n = (int)h->ns;
     rc = ndt_align_pairs(h, 1, &src, &n, guess16, out);
@@ -803,7 +812,7 @@ int dgs_align_batch(dgs_handle* h, int32_t n, const float* const* sources, const
     h->err = "no input target dataset was given";
     return DGS_ERR_NO_TARGET;
   }
-  if (h->prm.method != DGS_METHOD_NDT) {
+  if (!is_ndt_family(h)) {
     // FAST_GICP / ICP: every candidate needs its own index (+ covariances: GICP); they live in per-slot CloudStates the handle re-uses
     if (h->batch_clouds.size() < (size_t)n) h->batch_clouds.resize(n);
     std::vector<CloudState*> cs(n);
@@ -898,7 +907,7 @@ int dgs_align_batch_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* sources, 
   if (n == 0) return DGS_OK;
   for (int i = 0; i < n; i++)
     if (!sources[i] || sources[i]->device != h->device) return DGS_ERR_INVALID_ARGUMENT;
-  if (h->prm.method == DGS_METHOD_NDT) {
+  if (is_ndt_family(h)) {
     // the batched NDT path already takes device pointers: hand it the resident clouds, nothing is copied
     std::vector<const float*> ptrs(n);
     std::vector<int64_t> sizes(n);
@@ -949,7 +958,7 @@ int dgs_get_counts(dgs_handle* h, int64_t out[8]) {
   for (int k = 0; k < 8; k++) out[k] = 0;
   out[0] = h->nt;
   out[1] = h->ns;
-  if (h->prm.method == DGS_METHOD_NDT && h->have_target && h->grid_cells > 0) {
+  if (is_ndt_family(h) && h->have_target && h->grid_cells > 0) {
     if (h->counts_stale) {
       int sc[2] = {0, 0};
       DGS_HIP_TRY(h, hipMemcpyAsync(sc, h->dev_scalars.ptr, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
@@ -967,20 +976,33 @@ int dgs_get_counts(dgs_handle* h, int64_t out[8]) {
 }
 
 int dgs_ndt_derivatives(dgs_handle* h, const double* p6, const float* T16, double* score, double* grad6, double* hess36) {
-  if (!h || !p6 || !score || !grad6 || !hess36) return DGS_ERR_INVALID_ARGUMENT;
+  if (!h || !p6 || !score || !grad6 || (!hess36 && !is_pcl_ndt(h))) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   if (set_device(h)) return DGS_ERR_HIP;
-  if (h->prm.method != DGS_METHOD_NDT) return DGS_ERR_UNSUPPORTED;
+  if (!is_ndt_family(h)) return DGS_ERR_UNSUPPORTED;
   if (!h->have_target || h->nt == 0) return DGS_ERR_NO_TARGET;
   if (!h->have_source || h->ns == 0) return DGS_ERR_NO_SOURCE;
+  if (!hess36) {   // PCL_NDT_HIP: the score + gradient evaluation of a line-search trial
+    double unused[36];
+    return ndt_probe(h, p6, T16, score, grad6, unused, 0);
+  }
   return ndt_probe(h, p6, T16, score, grad6, hess36);
+}
+
+int dgs_pcl_ndt_neighbours(dgs_handle* h, const float* queries_xyz16, int64_t m, int32_t on_device, int32_t* counts, int32_t* voxel_ids) {
+  if (!h || m < 0 || m > INT32_MAX || (m > 0 && (!queries_xyz16 || !counts || !voxel_ids))) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  if (!is_pcl_ndt(h)) { h->err = "dgs_pcl_ndt_neighbours: not a PCL_NDT_HIP handle"; return DGS_ERR_UNSUPPORTED; }
+  if (!h->have_target || h->nt == 0) return DGS_ERR_NO_TARGET;
+  return pcl_ndt_neighbours(h, queries_xyz16, m, on_device, counts, voxel_ids);
 }
 
 int dgs_ndt_hessian_double(dgs_handle* h, const double* p6, double* hess36) {
   if (!h || !p6 || !hess36) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   if (set_device(h)) return DGS_ERR_HIP;
-  if (h->prm.method != DGS_METHOD_NDT || h->prm.ndt_strict_order == DGS_NDT_ORDER_FAST || !h->prm.ndt_hessian_recompute_double) return DGS_ERR_UNSUPPORTED;
+  if (!is_ndt_family(h) || h->prm.ndt_strict_order == DGS_NDT_ORDER_FAST || !h->prm.ndt_hessian_recompute_double) return DGS_ERR_UNSUPPORTED;
   if (!h->have_target || h->nt == 0) return DGS_ERR_NO_TARGET;
   if (!h->have_source || h->ns == 0) return DGS_ERR_NO_SOURCE;
   double score, g6[6];
@@ -1140,7 +1162,7 @@ int dgs_ndt_get_trajectory(dgs_handle* h, int32_t pair, double* poses6, int32_t*
   if (!h || !poses6 || !len || pair < 0) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   if (set_device(h)) return DGS_ERR_HIP;
-  if (h->prm.method != DGS_METHOD_NDT || (size_t)pair >= h->pairs.cap) return DGS_ERR_UNSUPPORTED;
+  if (!is_ndt_family(h) || (size_t)pair >= h->pairs.cap) return DGS_ERR_UNSUPPORTED;
   int n = 0;
   int rc = ndt_trajectory(h, pair, poses6, &n);
   *len = n;
@@ -1151,7 +1173,7 @@ int dgs_ndt_get_voxels(dgs_handle* h, int64_t* n, int64_t* keys, int32_t* counts
   if (!h || !n) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   if (set_device(h)) return DGS_ERR_HIP;
-  if (h->prm.method != DGS_METHOD_NDT) return DGS_ERR_UNSUPPORTED;
+  if (!is_ndt_family(h)) return DGS_ERR_UNSUPPORTED;
   if (!h->have_target) return DGS_ERR_NO_TARGET;
   int64_t c[8];
   int rc = dgs_get_counts(h, c);

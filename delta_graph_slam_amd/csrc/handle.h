@@ -445,6 +445,12 @@ int ndt_align_pairs(dgs_handle* h, int n_pairs, const float4* const* d_src_ptrs_
                     const float* guesses16, dgs_result* results);
 int ndt_trajectory(dgs_handle* h, int pair, double* out, int* len);
 int ndt_probe(dgs_handle* h, const double* p6, const float* T16, double* score, double* g6, double* H36, int kind = 1);   // kind 2: the double-precision computeHessian pass
+// pcl_ndt.hip (DGS_METHOD_PCL_NDT): the evaluation kernel of pcl::NormalDistributionsTransform, launched by ndt_align.hip's driver in place of its own
+inline bool is_pcl_ndt(const dgs_handle* h) { return h->prm.method == DGS_METHOD_PCL_NDT; }
+inline bool is_ndt_family(const dgs_handle* h) { return h->prm.method == DGS_METHOD_NDT || h->prm.method == DGS_METHOD_PCL_NDT; }   // voxel model, NDT driver, NDT hooks
+void pcl_ndt_launch(dgs_handle* h, int n_pairs, int cap_blocks, int total_blocks, int launch, hipStream_t st);   // launch >= 0: fused round; < 0: rows only
+void pcl_ndt_init_tables(dgs_handle* h, int n_pairs, hipStream_t st);
+int pcl_ndt_neighbours(dgs_handle* h, const float* queries_xyz16, int64_t m, int on_device, int32_t* counts, int32_t* voxel_ids);
 // nn_bvh.hip
 int bvh_build(dgs_handle* h, Bvh& bvh, const float4* pts, int64_t n, hipStream_t st = nullptr, bool kd_order = false);  // st: default the handle's stream; kd_order: median-split order (slower build, faster queries)
 int nn_fitness(dgs_handle* h, const float4* src, int64_t n, const float* T16, double max_range, double inlier_sq,

@@ -102,7 +102,7 @@ __global__ void ndt_init_kernel(NdtPair* __restrict__ pairs, const NdtInit* __re
   for (int k = 0; k < 36; k++) s.hess[k] = 0;
   double x[6];
   for (int k = 0; k < 6; k++) x[k] = in.p0[k];
-  write_evaluation<false>(st, st, s, c, x, probe == 2 ? 2 : 1, false, true);   // probe 2: the test hook of the double-precision computeHessian pass
+  write_evaluation<false>(st, st, s, c, x, probe == 2 ? 2 : (probe == 3 ? 0 : 1), false, true);   // probe 2: the test hook of the double-precision computeHessian pass; 3: a score + gradient evaluation (PCL_NDT_HIP)
   // the first evaluation transforms the cloud by the GUESS matrix itself (computeTransformation)
   const float* G = in.guess;
   st->T[0] = G[0]; st->T[1] = G[4]; st->T[2] = G[8];  st->T[3] = G[12];
@@ -338,7 +338,17 @@ static NdtPlan plan_align(const dgs_handle* h) {
   in.ndt_speculate = h->ndt_speculate;
   in.ndt_fixed_slices = h->ndt_fixed_slices;
   in.solve_min_active = h->solve_min_active;
-  return plan_align(in);
+  NdtPlan p = plan_align(in);
+  if (is_pcl_ndt(h)) {
+    // PCL_NDT_HIP: the upstream order's driver with pcl_ndt.hip's kernel -- one launch per round serves every evaluation kind, the Newton
+    // step stays in the pair's closing workgroup and nothing is speculated (a pair's doubles must not depend on its batch)
+    p.item_kernel = true;
+    p.two_kinds = p.solve_beside = p.speculate = false;
+    p.fixed_slices = true;
+    p.fused = true;   // (DGS_NDT_FUSED=0 is the other methods' test hook: the stand-alone solve kernel leaves no double angle vectors)
+    p.evals_factor = 1;
+  }
+  return p;
 }
 
 static hipStream_t launch_stream(const dgs_handle* h, const NdtPlan& P, int launch, bool hd) { return plan_on_hd_stream(P, launch, hd) ? h->hd_stream : h->stream; }
@@ -402,6 +412,11 @@ static void launch_derivatives(dgs_handle* h, const NdtPlan& P, const NdtLaunch&
   const int leaf_pow2 = (std::frexp(h->grid.leaf, &fe) == 0.5f) ? 1 : 0;
   const hipStream_t st = launch_stream(h, P, launch, hd);
   int slot = prof_begin(h, DGS_K_NDT_DERIVATIVES, st);
+  if (is_pcl_ndt(h)) {
+    if (!(hd && launch >= 0)) pcl_ndt_launch(h, L.n_pairs, L.cap_blocks, L.total_blocks, launch, st);   // (hd with launch < 0: the test hook asks for the kind it has set up)
+    prof_end(h, DGS_K_NDT_DERIVATIVES, slot, st);
+    return;
+  }
   with_search(P.search, [&](auto S) {
     constexpr int SEARCH = decltype(S)::value;
     if (P.order == DGS_NDT_ORDER_UPSTREAM_SEQUENTIAL) {
@@ -539,6 +554,7 @@ static int ndt_setup(dgs_handle* h, int n_pairs, const float4* const* src_ptrs_h
                      reinterpret_cast<const int*>(dstage + (off_size - off_init)), h->src_ptrs.ptr, h->src_sizes.ptr,
                      L.queue_workers > 0 ? h->ndt_queue.ptr : nullptr, L.queue_workers > 0 ? ndt_queue_slices(0, L.queue_base, L.cap_blocks) : 0,
                      reinterpret_cast<char*>(h->ndt_ring.ptr), h->ndt_ring_rounds);
+  if (is_pcl_ndt(h)) pcl_ndt_init_tables(h, n_pairs, st);   // the first evaluation's double angle vectors
   return DGS_OK;
 }
 
@@ -811,7 +827,7 @@ int ndt_probe(dgs_handle* h, const double* p6, const float* T16, double* score, 
     T[10] = mul(cx, cy); T[14] = (float)p6[2];
     T[3] = T[7] = T[11] = 0.f; T[15] = 1.f;
   }
-  int rc = ndt_setup(h, 1, &src, &n, T, p6, &L, false, kind);
+  int rc = ndt_setup(h, 1, &src, &n, T, p6, &L, false, kind == 0 ? 3 : kind);   // kind 0 (PCL_NDT_HIP): score + gradient
   if (rc != DGS_OK) return rc;
   const NdtPlan P = plan_align(h);
   launch_derivatives(h, P, L, -1, kind == 2);

@@ -9,6 +9,13 @@
 // written to the pair's HBM record by lane 0 (`writer`); every lane computes the same values.
 // double sin/cos is software on the GPU (~100s of instructions per call) and an evaluation needs twelve of them; when the
 // whole wave runs this code with identical inputs (solve kernel), lane k evaluates angle k and the results are broadcast.
+// pcl_ndt.hip includes this file with DGS_NDT_PCL_DOUBLE defined: PCL_NDT_HIP evaluates every kind in double, so write_evaluation leaves the
+// double angle vectors with every evaluation, and the stand-alone kernels of this file and ndt_strict.h are left to ndt_align.hip.
+#ifdef DGS_NDT_PCL_DOUBLE
+constexpr bool kNdtDoubleTablesAlways = true;
+#else
+constexpr bool kNdtDoubleTablesAlways = false;
+#endif
 template <bool WAVE>
 __device__ __forceinline__ void trig6(const double* ang, double* sn, double* cs) {
   if (WAVE) {
@@ -101,7 +108,7 @@ __device__ __forceinline__ void write_evaluation(NdtPair* st, NdtPair* hdr, NdtS
     hdr_put<COH>(&H[13][0], (float)(-cx * sz - sx * sy * cz)); hdr_put<COH>(&H[13][1], (float)(-cx * cz + sx * sy * sz)); hdr_put<COH>(&H[13][2], 0.f);              // f2
     hdr_put<COH>(&H[14][0], (float)(-sx * sz + cx * sy * cz)); hdr_put<COH>(&H[14][1], (float)(-cx * sy * sz - sx * cz)); hdr_put<COH>(&H[14][2], 0.f);              // f3
     }
-    if (need_hessian == 2) {   // computeHessian in PCL's double form reads the double angle vectors (never inside the queue kernel: plain stores)
+    if (need_hessian == 2 || kNdtDoubleTablesAlways) {   // computeHessian in PCL's double form reads the double angle vectors (never inside the queue kernel: plain stores)
       double (*Jd)[3] = hdr->jang_d;
       Jd[0][0] = (-sx * sz + cx * sy * cz); Jd[0][1] = (-sx * cz - cx * sy * sz); Jd[0][2] = (-cx * cy);
       Jd[1][0] = (cx * sz + sx * sy * cz);  Jd[1][1] = (cx * cz - sx * sy * sz);  Jd[1][2] = (-sx * cy);
@@ -507,6 +514,7 @@ __device__ __forceinline__ bool ndt_close_evaluation(NdtPair* st, const double* 
   return s.phase == PH_DONE;
 }
 
+#ifndef DGS_NDT_PCL_DOUBLE
 __global__ __launch_bounds__(kBlock) void ndt_solve_kernel(NdtPair* __restrict__ pairs, const double* __restrict__ partials, const int cap_blocks,
                                                            int* __restrict__ pair_blocks, const NdtConsts c, int* __restrict__ done_counter,
                                                            const double* __restrict__ strict_totals, const int strict_from_rows) {
@@ -572,3 +580,4 @@ __global__ __launch_bounds__(kBlock) void ndt_solve_kernel(NdtPair* __restrict__
     }
   }
 }
+#endif

@@ -1089,6 +1089,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
 
 // The Newton steps that the closings of round `launch` left behind (NdtPair::serve[1] == launch, phase PH_SOLVE_PENDING): one wave per pair,
 // on its own stream beside the next round's derivative launch.  The pair re-enters the derivative launches at round launch + lag.
+#ifndef DGS_NDT_PCL_DOUBLE
 __global__ __launch_bounds__(kWave) void ndt_strict_solve_kernel(NdtPair* __restrict__ pairs, const int n_pairs, const NdtConsts c, int* __restrict__ done_flags, const int launch,
                                                                const int lag) {
   const int pair = blockIdx.x;
@@ -1117,3 +1118,4 @@ __global__ __launch_bounds__(kWave) void ndt_strict_solve_kernel(NdtPair* __rest
     }
   }
 }
+#endif

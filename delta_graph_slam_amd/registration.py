@@ -149,8 +149,8 @@ class Registration:
             return
         exact = {"NDT_OMP": L.METHOD_NDT, "NDT_HIP": L.METHOD_NDT, "FAST_GICP": L.METHOD_GICP, "FAST_GICP_HIP": L.METHOD_GICP,
                  "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP,
-                 "GICP_HIP": L.METHOD_PCL_GICP, "GICP_OMP_HIP": L.METHOD_PCL_GICP}
-        if method not in exact:   # pcl::ICP / GICP / NDT, pclomp::GICP, FAST_VGICP_CUDA are other algorithms: not served here
+                 "GICP_HIP": L.METHOD_PCL_GICP, "GICP_OMP_HIP": L.METHOD_PCL_GICP, "PCL_NDT_HIP": L.METHOD_PCL_NDT}
+        if method not in exact:   # the reference's own "ICP" / "GICP" / "NDT" strings, pclomp::GICP, FAST_VGICP_CUDA: not served under those names
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends (served: {sorted(exact)})")
         m = exact[method]
         params = dict(params)
@@ -503,15 +503,26 @@ class Registration:
                                                    means.ctypes.data_as(C.c_void_p), covs.ctypes.data_as(C.c_void_p), C.byref(n)))
         return coords, counts, means, covs
 
-    def ndt_derivatives(self, p, T=None):
+    def ndt_derivatives(self, p, T=None, hessian: bool = True):
+        """One computeDerivatives evaluation at pose p (cloud transformed by T when given).  hessian=False (PCL_NDT_HIP only): the
+        score + gradient evaluation of a More-Thuente trial; the Hessian comes back as zeros."""
         p = np.ascontiguousarray(p, dtype=np.float64)
         t16 = None if T is None else _col16(T)
         s = C.c_double(0)
         g = np.zeros(6)
         H = np.zeros((6, 6))
         self._check(self._lib.dgs_ndt_derivatives(self._h, p.ctypes.data_as(C.c_void_p), None if t16 is None else t16.ctypes.data_as(C.c_void_p),
-                                                   C.byref(s), g.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p)))
+                                                   C.byref(s), g.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p) if hessian else None))
         return s.value, g, H
+
+    def pcl_ndt_neighbours(self, queries):
+        """PCL_NDT_HIP test hook (dgs_pcl_ndt_neighbours): per query point, taken as it is, the number of valid voxels whose float
+        centroid lies within the resolution, and their numbers (rows of the device's voxel table) ascending, -1 padded: (m,), (m, 27)."""
+        ptr, m, dev, keep = _cloud_ptr(queries)
+        counts = np.zeros(m, np.int32)
+        ids = np.full((m, 27), -1, np.int32)
+        self._check(self._lib.dgs_pcl_ndt_neighbours(self._h, ptr, m, dev, counts.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
+        return counts, ids
 
     def ndt_hessian_double(self, p):
         """computeHessian in PCL's double form at pose p (dgs_ndt_hessian_double; upstream evaluation orders only)."""
@@ -542,7 +553,9 @@ class Registration:
         self._check(self._lib.dgs_ndt_get_trajectory(self._h, pair, buf.ctypes.data_as(C.c_void_p), C.byref(n)))
         return buf[:n.value].copy()
 
-    def ndt_voxels(self):
+    def ndt_voxels(self, raw: bool = False):
+        """The target's voxel table ordered by cell key; raw=True: in the device's own row order (the voxel numbers of pcl_ndt_neighbours),
+        the row of non-finite points (key -1) included."""
         n = C.c_int64(0)
         self._check(self._lib.dgs_ndt_get_voxels(self._h, C.byref(n), None, None, None, None, None))
         nv = n.value
@@ -555,6 +568,8 @@ class Registration:
             self._check(self._lib.dgs_ndt_get_voxels(self._h, C.byref(n), keys.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
                                                       valid.ctypes.data_as(C.c_void_p), mean.ctypes.data_as(C.c_void_p),
                                                       icov.ctypes.data_as(C.c_void_p)))
+        if raw:
+            return dict(keys=keys, counts=counts, valid=valid.astype(bool), mean=mean, icov=icov)
         keep = keys >= 0
         o = np.argsort(keys[keep])
         return dict(keys=keys[keep][o], counts=counts[keep][o], valid=valid[keep][o].astype(bool), mean=mean[keep][o], icov=icov[keep][o])
@@ -609,7 +624,7 @@ class RegistrationGroup:
         self._lib = lib
         exact = {"NDT_OMP": L.METHOD_NDT, "NDT_HIP": L.METHOD_NDT, "FAST_GICP": L.METHOD_GICP, "FAST_GICP_HIP": L.METHOD_GICP,
                  "FAST_VGICP": L.METHOD_VGICP, "FAST_VGICP_HIP": L.METHOD_VGICP, "ICP_HIP": L.METHOD_ICP,
-                 "GICP_HIP": L.METHOD_PCL_GICP, "GICP_OMP_HIP": L.METHOD_PCL_GICP}
+                 "GICP_HIP": L.METHOD_PCL_GICP, "GICP_OMP_HIP": L.METHOD_PCL_GICP, "PCL_NDT_HIP": L.METHOD_PCL_NDT}
         if method not in exact:
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends")
         params = dict(params)
@@ -797,7 +812,8 @@ def select_registration_method(params: dict | None = None, device: int | None = 
     what is left is the NDT branch (:88-123): a name without "NDT" warns "unknown registration type ... use NDT" (:89-92), and then
     a name without "OMP" -- plain "NDT" as well as an unknown name such as "FOO" -- is pcl::NormalDistributionsTransform (:94-100),
     another algorithm -> NotImplementedError, while a name containing "OMP" ("NDT_OMP", and e.g. "FOO_OMP" after the warning) is
-    pclomp::NormalDistributionsTransform (:101-120), which this library serves.
+    pclomp::NormalDistributionsTransform (:101-120), which this library serves.  "PCL_NDT_HIP" (tested before that chain) is the HIP
+    pcl::NormalDistributionsTransform of :94-100 with its three rosparams: reg_resolution, reg_transformation_epsilon, reg_maximum_iterations.
     """
     pr = dict(params or {})
     method = pr.get("registration_method", "NDT_OMP")
@@ -821,6 +837,10 @@ def select_registration_method(params: dict | None = None, device: int | None = 
                             gicp_correspondence_randomness=int(pr.get("reg_correspondence_randomness", 20)),
                             gicp_max_optimizer_iterations=int(pr.get("reg_max_optimizer_iterations", 20)),
                             gicp_use_reciprocal_correspondences=bool(pr.get("reg_use_reciprocal_correspondences", False)), **common)
+    if method == "PCL_NDT_HIP":                         # :94-100 on the GPU: pcl::NormalDistributionsTransform, its three rosparams (before the reference's chain)
+        return Registration("PCL_NDT_HIP", device=device, ndt_resolution=float(pr.get("reg_resolution", 0.5)),
+                            transformation_epsilon=float(pr.get("reg_transformation_epsilon", 0.01)),
+                            maximum_iterations=int(pr.get("reg_maximum_iterations", 64)))
     if method == "ICP" or "GICP" in method:             # :59-64, :66-87 (FAST_VGICP_CUDA lands here too when the reference is built without CUDA)
         raise NotImplementedError(f"registration_method {method!r} is served by the reference's own factory branch, not by the HIP back-ends")
     if method != "NDT_HIP":

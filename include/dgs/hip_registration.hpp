@@ -50,6 +50,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     this->reg_name_ = (method == DGS_METHOD_GICP) ? "dgs::HipRegistration<FAST_GICP>" : (method == DGS_METHOD_VGICP) ? "dgs::HipRegistration<FAST_VGICP>"
                       : (method == DGS_METHOD_ICP)       ? "dgs::HipRegistration<ICP>"
                       : (method == DGS_METHOD_PCL_GICP)  ? "dgs::HipRegistration<PCL_GICP>"
+                      : (method == DGS_METHOD_PCL_NDT)   ? "dgs::HipRegistration<PCL_NDT>"
                                                          : "dgs::HipRegistration<NDT>";
     // the reference's setters below write into params_; PCL's own setters (epsilon, iterations, distance) are read at align()
     this->transformation_epsilon_ = params_.transformation_epsilon;

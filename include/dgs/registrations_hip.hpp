@@ -76,6 +76,17 @@ typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration(const st
     gicp->setMaximumOptimizerIterations(pnh.template param<int>("reg_max_optimizer_iterations", 20));              // :74 / :84
     return base;
   }
+  if (registration_method == "PCL_NDT_HIP") {   // registrations.cpp:94-100 on the GPU: pcl::NormalDistributionsTransform (the reference's own
+    // "NDT" string and every unknown name keep that branch); setStepSize / setOulierRatio keep PCL's defaults (0.1, 0.55)
+    const double ndt_resolution = pnh.template param<double>("reg_resolution", 0.5);                      // :93
+    std::cout << "registration: PCL_NDT_HIP " << ndt_resolution << std::endl;
+    typename pcl::Registration<PointT, PointT>::Ptr base(new Reg(DGS_METHOD_PCL_NDT));
+    Reg* ndt = static_cast<Reg*>(base.get());
+    ndt->setTransformationEpsilon(pnh.template param<double>("reg_transformation_epsilon", 0.01));        // :97
+    ndt->setMaximumIterations(pnh.template param<int>("reg_maximum_iterations", 64));                     // :98
+    ndt->setResolution(static_cast<float>(ndt_resolution));                                                // :99
+    return base;
+  }
   if (registration_method == "NDT_HIP") {
     const double ndt_resolution = pnh.template param<double>("reg_resolution", 0.5);                      // :93
     const std::string nn_search_method = pnh.template param<std::string>("reg_nn_search_method", "DIRECT7");  // :103

@@ -55,10 +55,18 @@ enum dgs_method {
   DGS_METHOD_ICP = 3,   /* "ICP_HIP": pcl::IterativeClosestPoint, registrations.cpp:59-64 (point-to-point, DESIGN.md "ICP_HIP").  Reads
                            transformation_epsilon, maximum_iterations and gicp_max_correspondence_distance (= setMaxCorrespondenceDistance);
                            the rest of its settings are dgs_icp_options.  The reference's own "ICP" string is not this method. */
-  DGS_METHOD_PCL_GICP = 4 /* "GICP_HIP" / "GICP_OMP_HIP": pcl::GeneralizedIterativeClosestPoint, registrations.cpp:65-87 (DESIGN.md
+  DGS_METHOD_PCL_GICP = 4, /* "GICP_HIP" / "GICP_OMP_HIP": pcl::GeneralizedIterativeClosestPoint, registrations.cpp:65-87 (DESIGN.md
                              "GICP_HIP").  Reads transformation_epsilon, maximum_iterations, gicp_max_correspondence_distance and
                              gicp_correspondence_randomness (k_correspondences_); the rest is dgs_pcl_gicp_options.  The reference's own
                              "GICP" / "GICP_OMP" strings are not this method. */
+  DGS_METHOD_PCL_NDT = 5   /* "PCL_NDT_HIP": pcl::NormalDistributionsTransform, the factory's default branch (registrations.cpp:94-100;
+                             DESIGN.md 6i): score, gradient and Hessian in double, the neighbourhood always the radius search (centroids
+                             within ndt_resolution).  Reads transformation_epsilon, maximum_iterations, ndt_resolution, ndt_step_size,
+                             ndt_outlier_ratio, ndt_min_points_per_voxel, ndt_min_covar_eigvalue_mult, ndt_line_search,
+                             ndt_mt_max_step_iterations, ndt_fix_hessian_d1, ndt_newton_solver, ndt_guess_rotation_polar, ndt_exp_glibc and
+                             ndt_cov_eigensolver; num_threads, ndt_search_method, ndt_strict_order and ndt_hessian_recompute_double are
+                             accepted and without effect (the closing computeHessian is always PCL's double pass).  The reference's own
+                             strings for this branch ("NDT" and every unknown name) are not this method. */
 };
 
 /* fast_gicp::NeighborSearchMethod of FastVGICP (voxel offsets searched around the voxel of T * p) */
@@ -378,6 +386,13 @@ int dgs_ndt_derivatives(dgs_handle* h, const double* p6, const float* T16, doubl
 /* NDT computeHessian in PCL's double-precision form at pose p (the pass computeStepLengthMT ends with when a line search took extra
  * trials; dgs_params.ndt_hessian_recompute_double).  Upstream evaluation orders only (DGS_ERR_UNSUPPORTED otherwise). */
 int dgs_ndt_hessian_double(dgs_handle* h, const double* p6, double* hess36);
+/* DGS_METHOD_PCL_NDT handles are served by dgs_ndt_derivatives (its evaluation with the Hessian; hess36 == NULL asks for the score +
+ * gradient evaluation of a More-Thuente trial), dgs_ndt_hessian_double, dgs_ndt_get_trajectory and dgs_ndt_get_voxels as well.
+ * Test hook of such a handle: the neighbourhood of `m` query points (x y z pad, taken as they are: no transform) in the current
+ * target's voxel model as the evaluation kernel finds it -- counts[i] valid voxels whose float centroid lies within ndt_resolution of
+ * query i, their numbers (rows of dgs_ndt_get_voxels) in voxel_ids[27 i ..] in ascending order, the rest of the row -1.  counts and
+ * voxel_ids are host arrays.  DGS_ERR_UNSUPPORTED on a handle of another method. */
+int dgs_pcl_ndt_neighbours(dgs_handle* h, const float* queries_xyz16, int64_t m, int32_t on_device, int32_t* counts, int32_t* voxel_ids);
 /* NDT pose (x, y, z, rx, ry, rz) after every outer iteration of pair `pair` of the last align / align_batch;
  * poses6 holds up to 72 x 6 doubles, *len receives the number written (entry 0 is the initial guess). */
 int dgs_ndt_get_trajectory(dgs_handle* h, int32_t pair, double* poses6, int32_t* len);
