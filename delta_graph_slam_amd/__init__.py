@@ -1,6 +1,6 @@
 """delta_graph_slam_amd -- MI355X-native scan registration (NDT / GICP) hot path."""
 
-__all__ = ["MapCloudGenerator", "LineExtractor", "LineScanMatcher", "BuildingOverlap"]
+__all__ = ["MapCloudGenerator", "LineExtractor", "LineScanMatcher", "BuildingOverlap", "FloorDetector"]
 
 
 def __getattr__(name):   # resolved on first use: importing the package alone loads neither torch nor the HIP library
@@ -16,4 +16,7 @@ def __getattr__(name):   # resolved on first use: importing the package alone lo
     if name == "BuildingOverlap":
         from .building_overlap import BuildingOverlap
         return BuildingOverlap
+    if name == "FloorDetector":
+        from .floor_detection import FloorDetector
+        return FloorDetector
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

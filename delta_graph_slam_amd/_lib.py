@@ -90,6 +90,21 @@ class LineExtractionRound(C.Structure):
                 ("inliers", C.c_int32), ("cluster", C.c_int32), ("emitted", C.c_int32)]
 
 
+class FloorDetectionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("floor_pts_thresh", C.c_int32), ("tilt_deg", C.c_double), ("sensor_height", C.c_double),
+                ("height_clip_range", C.c_double), ("floor_normal_thresh", C.c_double), ("normal_filter_thresh", C.c_double),
+                ("distance_threshold", C.c_double), ("probability", C.c_double), ("use_normal_filtering", C.c_int32),
+                ("max_iterations", C.c_int32), ("max_sample_checks", C.c_int32), ("transform_order", C.c_int32),
+                ("plane_dot_order", C.c_int32), ("hyp_chunk_first", C.c_int32), ("hyp_chunk", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FloorDetectionTrace(C.Structure):
+    _fields_ = [("n_clipped", C.c_int32), ("n_filtered", C.c_int32), ("draws", C.c_int32), ("hypotheses_scored", C.c_int32),
+                ("iterations", C.c_int32), ("chunks_launched", C.c_int32), ("winner_rank", C.c_int32), ("sample", C.c_int32 * 3),
+                ("count", C.c_int32), ("ransac_failed", C.c_int32), ("raw_coeffs", C.c_float * 4), ("dot", C.c_float),
+                ("reserved", C.c_int32)]
+
+
 class LineAlignParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("angle_gate_float_chain", C.c_int32), ("g_avg_distance_weight", C.c_double),
                 ("g_coverage_weight", C.c_double), ("g_transform_weight", C.c_double), ("g_max_score_distance", C.c_double),
@@ -146,6 +161,7 @@ LA_STATUS = {0: "ALIGNED", 1: "NO_HYPOTHESES", 2: "ALL_GATED", 3: "NONE_BETTER",
 LA_GATE = {0: "PASS", 1: "DISTANCE", 2: "IDENTITY", 3: "ANGLE", 4: "LINE_DIRECTION", 5: "LINE_DISTANCE", 6: "RANK", 7: "OVERLAP"}
 BO_MAX_BUILDINGS = 1 << 14
 LE_STATUS = {0: "DONE", 1: "RANSAC_FAILED", 2: "STALL", 3: "MAX_ROUNDS", 4: "RNG_EXHAUSTED"}
+FD_STATUS = {0: "DETECTED", 1: "TOO_FEW_POINTS", 2: "TOO_FEW_INLIERS", 3: "NOT_VERTICAL", 4: "RNG_EXHAUSTED"}
 SAC_METHODS = ["SAC_RANSAC", "SAC_LMEDS", "SAC_MSAC", "SAC_RRANSAC", "SAC_RMSAC", "SAC_MLESAC", "SAC_PROSAC"]
 MAP_DEDUP = {"AUTO": 0, "HASH": 1, "SORT": 2}
 PF_DOWNSAMPLE = {"NONE": 0, "VOXELGRID": 1, "APPROX_VOXELGRID": 2}
@@ -182,6 +198,8 @@ SYMBOLS = [
     "dgs_line_align_local_batch", "dgs_line_align_local", "dgs_line_edges_angular", "dgs_line_align_local_get_hypotheses",
     "dgs_building_overlap_pairs", "dgs_line_align_overlapped_batch", "dgs_line_align_overlapped", "dgs_line_align_overlapped_get_hypotheses",
     "dgs_building_overlap_get_counts",
+    "dgs_floor_detection_params_init", "dgs_floor_detection", "dgs_floor_detection_get_filtered", "dgs_floor_detection_get_inliers",
+    "dgs_floor_detection_get_trace", "dgs_floor_detection_get_clipped", "dgs_floor_detection_draws", "dgs_floor_detection_walk",
 ]
 
 _libs = {}
@@ -324,5 +342,14 @@ def load(path=None):
                                               C.c_void_p, P(LineOverlapAlignment)]
     lib.dgs_line_align_overlapped_get_hypotheses.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
     lib.dgs_building_overlap_get_counts.argtypes = [C.c_void_p, C.c_void_p]
+    lib.dgs_floor_detection_params_init.argtypes = [P(FloorDetectionParams)]
+    lib.dgs_floor_detection.argtypes = [C.c_void_p, P(FloorDetectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                        C.c_int64, C.c_void_p, P(C.c_int32)]
+    lib.dgs_floor_detection_get_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
+    lib.dgs_floor_detection_get_inliers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_floor_detection_get_trace.argtypes = [C.c_void_p, P(FloorDetectionTrace)]
+    lib.dgs_floor_detection_get_clipped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_floor_detection_draws.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.dgs_floor_detection_walk.argtypes = [C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32)]
     _libs[path] = lib
     return lib

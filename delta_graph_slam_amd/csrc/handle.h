@@ -212,6 +212,30 @@ struct BoScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// FloorDetectionNodelet::detect (floor_detection.hip): the stage clouds, the normal pass's own index and lists, the draw list and
+// hypotheses of the RANSAC, and what the getters read back.  Separate from everything a registration, the prefilter, the map cloud
+// or the line code uses.
+struct FdHyp;     // floor_detection.hip
+struct FdScratch {
+  DevBuf<float4> in, tilted, clipped, kept, filtered;   // staged host input; after the tilt; after the clips; after the normal filter; back-transformed
+  DevBuf<unsigned char> flags, nflags; // keep flag per point of the pass being compacted; the prefilter rule's flags of pf_normal_kernel (unread)
+  DevBuf<int> blk, cnt;                // compaction offsets; [0] kept points of the last compaction
+  CloudState cloud;                    // the clipped cloud with its index (normal pass)
+  DevBuf<int> nbr;                     // its k-NN lists
+  DevBuf<float4> normals;
+  DevBuf<float> cov9;
+  DevBuf<int> draws;                   // three point indices per draw
+  DevBuf<FdHyp> hyps;                  // the good draws in order, at most max_iterations + 1
+  DevBuf<int> counts, meta;            // inliers per hypothesis; [0] good draws, [1] draw that completes max_sample_checks bad ones in a row
+  std::vector<float4> host_filtered;   // the filtered cloud on the host: final inlier flags and checks run there
+  std::vector<int32_t> inliers;
+  std::vector<uint32_t> mt_raw;        // mt19937(12345)() >> 1, extended on demand
+  std::vector<int> perm;               // identity between detects: shuffled_indices_
+  int64_t n_clipped = 0, n_filtered = 0;
+  bool have_normals = false;
+  dgs_floor_detection_trace trace{};
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -420,6 +444,9 @@ struct dgs_handle {
   dgs::LalScratch lal;
   dgs::BoScratch bo;
 
+  // ---- floor detection (floor_detection.hip): own buffers; everything above is left untouched
+  dgs::FdScratch fd;
+
   dgs::Profiler prof;
 };
 
@@ -513,6 +540,8 @@ void line_align_release(dgs_handle* h);
 void line_align_local_release(dgs_handle* h);
 // building_overlap.hip
 void building_overlap_release(dgs_handle* h);
+// floor_detection.hip
+void floor_detection_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

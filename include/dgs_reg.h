@@ -857,6 +857,80 @@ int dgs_line_align_overlapped_get_hypotheses(dgs_handle* h, int64_t item, int64_
  * dgs_line_align_overlapped_batch call kernel launches, host waits, items, hypotheses. */
 int dgs_building_overlap_get_counts(dgs_handle* h, int64_t* counts8);
 
+/* ---- FloorDetectionNodelet::detect on the device (apps/floor_detection_nodelet.cpp:110-238) -----------------------------------
+ * Tilt transform, the two plane clips, the k = 10 normal filter, the back-transform, a RANSAC plane fit
+ * (pcl::RandomSampleConsensus over pcl::SampleConsensusModelPlane, driven directly: no refit) and the nodelet's three checks.
+ * Semantics and the PCL 1.10 details recalled from upstream: DESIGN.md 6j.  The detector works in buffers of its own:
+ * registration, prefilter, map and line state are untouched.  Additions only: DGS_ABI_VERSION is unchanged. */
+enum dgs_floor_detection_status {
+  DGS_FD_DETECTED = 0,        /* coeffs4_out holds the plane, its normal upward */
+  DGS_FD_TOO_FEW_POINTS = 1,  /* the filtered cloud has fewer than floor_pts_thresh points (:133) */
+  DGS_FD_TOO_FEW_INLIERS = 2, /* the winner has fewer than floor_pts_thresh inliers (:147) */
+  DGS_FD_NOT_VERTICAL = 3,    /* the winner's normal is farther than floor_normal_thresh from the tilted z axis (:158) */
+  DGS_FD_RNG_EXHAUSTED = 4    /* the caller's rng_raw stream ran out */
+};
+/* Defaults (dgs_floor_detection_params_init) = the nodelet's (:57-63) and PCL's: 0, 2, 1, 512, 10, true, 20; 0.1, 1000, 0.99, 1000;
+ * orders 0; chunks of 64 then 512 hypotheses. */
+typedef struct dgs_floor_detection_params {
+  uint32_t struct_size;          /* sizeof(dgs_floor_detection_params), set by dgs_floor_detection_params_init */
+  int32_t floor_pts_thresh;      /* negative: DGS_ERR_INVALID_ARGUMENT (upstream compares it as size_t) */
+  double tilt_deg;               /* read by the adapters, which build tilt16 / tilt_inv16 from it; the library takes the matrices */
+  double sensor_height;
+  double height_clip_range;
+  double floor_normal_thresh;    /* degrees */
+  double normal_filter_thresh;   /* degrees */
+  double distance_threshold;     /* ransac.setDistanceThreshold(0.1) (:140) */
+  double probability;            /* SampleConsensus::probability_ */
+  int32_t use_normal_filtering;
+  int32_t max_iterations;        /* SampleConsensus::max_iterations_ */
+  int32_t max_sample_checks;     /* SampleConsensusModel::max_sample_checks_ */
+  int32_t transform_order;       /* 0: x*m0 + (y*m1 + (z*m2 + m3)) per coordinate, 1: ((m0*x + m1*y) + m2*z) + m3 */
+  int32_t plane_dot_order;       /* four-term dot products of the plane model: 0 (a+b)+(c+d), 1 (a+c)+(b+d), 2 left to right */
+  int32_t hyp_chunk_first;       /* hypotheses scored before the host first walks the counts */
+  int32_t hyp_chunk;             /* hypotheses per further launch while the walk is open; the result depends on neither */
+  int32_t reserved;
+} dgs_floor_detection_params;
+int dgs_floor_detection_params_init(dgs_floor_detection_params* params);
+/* tilt16 / tilt_inv16: the two 4 x 4 float matrices of detect(), column-major (Eigen's data()).  in_xyz16: n xyz16 points (host
+ * array, or device pointer with in_on_device), e.g. dgs_prefilter_scan's 3-D output; it is not modified.  rng_raw (nullable):
+ * rng_len values that stand in for boost::mt19937(12345)() >> 1, three per draw; running past its end is DGS_FD_RNG_EXHAUSTED.
+ * coeffs4_out: the four plane coefficients, written (zeros unless detected) whatever the status.  *status_out:
+ * dgs_floor_detection_status.  An empty cloud is DGS_FD_TOO_FEW_POINTS with DGS_OK. */
+int dgs_floor_detection(dgs_handle* h, const dgs_floor_detection_params* params, const float* tilt16, const float* tilt_inv16,
+                        const float* in_xyz16, int64_t n, int32_t in_on_device, const uint32_t* rng_raw, int64_t rng_len,
+                        float* coeffs4_out, int32_t* status_out);
+/* The filtered cloud of the last detect (/floor_detection/floor_filtered_points).  out_xyz16 (nullable): room for `capacity`
+ * points, written when capacity >= *n; *n is always the full count. */
+int dgs_floor_detection_get_filtered(dgs_handle* h, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n);
+/* The winner's inliers of the last detect: indices into the filtered cloud, ascending, and (nullable) the points themselves
+ * (/floor_detection/floor_points), both host arrays with room for `capacity` entries, written when capacity >= *n. */
+int dgs_floor_detection_get_inliers(dgs_handle* h, int32_t* indices, float* points_xyz16, int64_t capacity, int64_t* n);
+typedef struct dgs_floor_detection_trace {
+  int32_t n_clipped;          /* points after the two plane clips */
+  int32_t n_filtered;         /* points of the filtered cloud */
+  int32_t draws;              /* samples drawn (three raw values each) */
+  int32_t hypotheses_scored;  /* hypotheses the device scored against the cloud */
+  int32_t iterations;         /* hypotheses the walk consumed */
+  int32_t chunks_launched;    /* score launches = host waits of the RANSAC */
+  int32_t winner_rank;        /* rank of the winner among the good samples (-1: no model) */
+  int32_t sample[3];          /* the winner's three point indices (-1: no model) */
+  int32_t count;              /* the winner's inlier count */
+  int32_t ransac_failed;      /* max_sample_checks bad draws in a row (or fewer than three points) ended the walk */
+  float raw_coeffs[4];        /* the winner's coefficients before the upward flip (zeros: no model) */
+  float dot;                  /* the verticality check's dot product */
+  int32_t reserved;
+} dgs_floor_detection_trace;
+int dgs_floor_detection_get_trace(dgs_handle* h, dgs_floor_detection_trace* trace);
+/* Test hook: the clipped cloud of the last detect and, with use_normal_filtering, its normals (xyz0 per point; else untouched).
+ * Host arrays (nullable) with room for `capacity` points, written when capacity >= *n. */
+int dgs_floor_detection_get_clipped(dgs_handle* h, float* clipped_xyz16, float* normals4, int64_t capacity, int64_t* n);
+/* The two host pieces of the RANSAC, callable without a device.  Draws: the first n_draws index triples of the sample stream over n
+ * points (n >= 3), from rng_raw (3 * n_draws values) or, when NULL, from mt19937(12345)() >> 1.  Walk: RandomSampleConsensus::
+ * computeModel over inlier counts -> winner (-1: none), iterations consumed, and whether it ran past n_counts still open. */
+int dgs_floor_detection_draws(int64_t n, const uint32_t* rng_raw, int64_t n_draws, int32_t* triples_out);
+int dgs_floor_detection_walk(int64_t n, int32_t max_iterations, double probability, const int32_t* counts, int64_t n_counts,
+                             int32_t* winner_out, int32_t* iterations_out, int32_t* open_out);
+
 #ifdef __cplusplus
 }
 #endif
