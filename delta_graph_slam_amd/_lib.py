@@ -200,6 +200,7 @@ SYMBOLS = [
     "dgs_building_overlap_get_counts",
     "dgs_floor_detection_params_init", "dgs_floor_detection", "dgs_floor_detection_get_filtered", "dgs_floor_detection_get_inliers",
     "dgs_floor_detection_get_trace", "dgs_floor_detection_get_clipped", "dgs_floor_detection_draws", "dgs_floor_detection_walk",
+    "dgs_calc_fitness_score_batch_clouds", "dgs_cloud_build_indices", "dgs_fitness_batch_get_counts",
 ]
 
 _libs = {}
@@ -238,6 +239,9 @@ def load(path=None):
     lib.dgs_find_loop_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
                                              C.c_int64, P(C.c_int64)]
     lib.dgs_calc_fitness_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_double, P(C.c_double)]
+    lib.dgs_calc_fitness_score_batch_clouds.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    lib.dgs_cloud_build_indices.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.dgs_fitness_batch_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     lib.dgs_voxel_grid_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_approx_voxel_grid_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_cloud_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_void_p)]

@@ -493,6 +493,7 @@ void dgs_destroy(dgs_handle* h) {
   line_align_local_release(h);
   building_overlap_release(h);
   floor_detection_release(h);
+  fitness_batch_release(h);
   h->gitems.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
   h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();
@@ -1082,6 +1083,44 @@ int dgs_calc_fitness_score(dgs_handle* h, const float* cloud1, int64_t n1, const
                            &sum, &cnt, &inl);
   if (rc != DGS_OK) return rc;
   *score = cnt > 0 ? sum / (double)cnt : DBL_MAX;
+  return DGS_OK;
+}
+
+// the batched form between resident clouds (fitness_batch.hip)
+static int check_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* clouds, const char* what) {
+  for (int32_t i = 0; i < n; i++) {
+    if (!clouds[i]) { h->err = std::string(what) + ": NULL cloud at " + std::to_string(i); return DGS_ERR_INVALID_ARGUMENT; }
+    if (clouds[i]->device != h->device) { h->err = std::string(what) + ": cloud " + std::to_string(i) + " lives on another device"; return DGS_ERR_INVALID_ARGUMENT; }
+  }
+  return DGS_OK;
+}
+
+int dgs_calc_fitness_score_batch_clouds(dgs_handle* h, int32_t n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16,
+                                        double max_range, double* scores, int64_t* used) {
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (n_edges < 0 || (n_edges > 0 && (!cloud1s || !cloud2s || !scores))) { h->err = "dgs_calc_fitness_score_batch_clouds: bad arguments"; return DGS_ERR_INVALID_ARGUMENT; }
+  int rc = check_clouds(h, n_edges, cloud1s, "cloud1s");
+  if (rc == DGS_OK) rc = check_clouds(h, n_edges, cloud2s, "cloud2s");
+  if (rc != DGS_OK) return rc;
+  if (set_device(h)) return DGS_ERR_HIP;
+  return fitness_batch_clouds(h, n_edges, cloud1s, cloud2s, relposes16, max_range, scores, used);
+}
+
+int dgs_cloud_build_indices(dgs_handle* h, int32_t n, dgs_cloud* const* clouds) {
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (n < 0 || (n > 0 && !clouds)) { h->err = "dgs_cloud_build_indices: bad arguments"; return DGS_ERR_INVALID_ARGUMENT; }
+  const int rc = check_clouds(h, n, clouds, "clouds");
+  if (rc != DGS_OK) return rc;
+  if (set_device(h)) return DGS_ERR_HIP;
+  return fitness_batch_build_indices(h, n, clouds);
+}
+
+int dgs_fitness_batch_get_counts(dgs_handle* h, int64_t* counts8) {
+  if (!h || !counts8) return DGS_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 8; k++) counts8[k] = h->fb.counts8[k];
+  counts8[5] = h->bvh_builds;
   return DGS_OK;
 }
 

@@ -1,0 +1,424 @@
+// InformationMatrixCalculator::calc_fitness_score over all edges of an optimisation tick, between clouds that are resident in HBM
+// (dgs_calc_fitness_score_batch_clouds), and the batched build of the exact-NN indices those edges need (dgs_cloud_build_indices).
+//
+// The reference weighs every new odometry edge (apps/delta_graph_slam_nodelet.cpp:572, up to max_keyframes_per_update = 10 per tick)
+// and every accepted loop edge (:820) by the mean squared NN distance of cloud2, moved by the edge's relative pose, in cloud1
+// (src/hdl_graph_slam/information_matrix_calculator.cpp:77-108), building a kd-tree over cloud1 each time.  dgs_calc_fitness_score
+// is that call for one pair of raw arrays: two uploads, one index build, one walk, one wait -- per edge.  Here the clouds are
+// dgs_cloud objects, the index over cloud1 is the one the cloud keeps (CloudState::bvh: the loop detector's target index and the ICP
+// walks' a moment later), and a tick costs one batched index build for the clouds that have none, ONE walk launch over all edges, one
+// closing launch, one download and one host wait.
+//
+// Walk.  A workgroup is one slice of one edge: it finds its edge in a prefix table of rows (wave-uniform, scalar loads), reads the
+// edge's BvhView, source, size and transform from the edge table and then does exactly what nn_fitness_kernel does -- the same
+// nn_query_group<false> / nn_warm_bound_round calls (nn_group.h), so a distance is the very float the single call produces.  Index
+// depths differ between edges, never inside a workgroup.  FIXED SLICES: the rows of an edge and the stretch each wave walks are a
+// function of the edge's own cloud2 size (fb_rows_of), the rows are summed per edge in a fixed order by the closing launch, so an
+// edge's (sum, used) is bit-identical whatever else the batch holds, wherever the edge stands in it, and alone.
+//
+// Build.  bvh_build (nn_bvh.hip) restated over segments: per-cloud boxes (min / max: exact in any order), hilbert30 keys with the
+// cloud's number above bit 30, one stable radix sort of the 64-bit keys of all clouds (values = original indices, so each segment's
+// order is what the 30-bit sort gives that cloud alone), a gather into each cloud's own Bvh::sorted, and the node boxes level by
+// level over all clouds at once: the number of launches follows the deepest cloud, not the number of clouds.  No host wait.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "handle.h"
+#include "nn_group.h"
+
+namespace dgs {
+
+constexpr int kFbRowQueries = 128;   // cloud2 points per partial row: 4 waves x 4 rounds of 8 adjacent queries (warm bounds from round 2 on)
+constexpr int kFbMaxRows = 512;      // ... up to this many rows; beyond 65,536 points the stretches grow instead
+constexpr int kFbMmBlocks = 64;      // partial boxes per cloud = lanes of the wave that folds them
+
+inline int fb_rows_of(const int n) { return n <= 0 ? 0 : std::max(1, std::min(kFbMaxRows, (n + kFbRowQueries - 1) / kFbRowQueries)); }
+
+struct FbEdge {
+  BvhView b;          // index over cloud1
+  const float4* src;  // cloud2
+  int n, rows, row0, pad;
+  float T[16];        // column-major
+};
+static_assert(sizeof(FbEdge) == 128, "FbEdge is 128 bytes");
+
+struct FbSeg {
+  const float4* pts;
+  float4* sorted;
+  float4* box_lo;
+  float4* box_hi;
+  int n, n_pad, off, depth;
+};
+
+// ---- walk --------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void fb_walk_kernel(const int* __restrict__ row0s, const FbEdge* __restrict__ edges, const int n_edges,
+                                                         const float max_range, double* __restrict__ rows) {
+  // the edge of this workgroup: row0s[e] <= blockIdx.x < row0s[e + 1] (edges without rows have no workgroup)
+  int lo = 0, hi = n_edges;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (row0s[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+  }
+  const FbEdge* __restrict__ E = edges + __builtin_amdgcn_readfirstlane(lo);
+  const BvhView b = E->b;
+  const float4* __restrict__ src = E->src;
+  const int n = E->n, n_rows = E->rows, slice = (int)blockIdx.x - E->row0;
+  const float t00 = E->T[0], t10 = E->T[1], t20 = E->T[2], t01 = E->T[4], t11 = E->T[5], t21 = E->T[6], t02 = E->T[8], t12 = E->T[9], t22 = E->T[10],
+              t03 = E->T[12], t13 = E->T[13], t23 = E->T[14];
+  double s = 0.0, c = 0.0;
+  constexpr int QPB = kBlock / 8;  // queries per workgroup per round
+  const int sub = threadIdx.x & 7;
+  // every wave walks a contiguous stretch of cloud2, 8 adjacent points per round (nn_fitness_kernel); stretch and rows follow n alone
+  const int run = (n + n_rows * QPB - 1) / (n_rows * QPB);
+  const int first = (slice * (kBlock / kWave) + (threadIdx.x >> 6)) * (8 * run) + ((threadIdx.x & 63) >> 3);
+  float px = 0.f, py = 0.f, pz = 0.f, prev_best = INFINITY;
+  bool prev_found = false;
+  for (int r = 0; r < run; r++) {
+    const int i = first + r * 8;
+    const bool alive = i < n;
+    const float4 p = alive ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    // pcl::transformPointCloud: ((m0 x + m1 y) + m2 z) + m3 in float, every step rounded
+    const float x = affine_row_rn(t00, t01, t02, t03, p.x, p.y, p.z);
+    const float y = affine_row_rn(t10, t11, t12, t13, p.x, p.y, p.z);
+    const float z = affine_row_rn(t20, t21, t22, t23, p.x, p.y, p.z);
+    float best;
+    int bi;
+    nn_query_group<false>(b, x, y, z, alive, nn_warm_bound_round(prev_best, prev_found, x, y, z, px, py, pz), best, bi);
+    prev_found = alive && bi != 0x7FFFFFFF;
+    prev_best = best;
+    px = x; py = y; pz = z;
+    if (alive && sub == 0) {
+      if (bi == 0x7FFFFFFF) best = INFINITY;  // nothing found (non-finite query): as the unbounded search reports it
+      if (best <= max_range) {  // PCL compares the SQUARED distance with max_range
+        s += (double)best;
+        c += 1.0;
+      }
+    }
+  }
+  __shared__ double sm[kBlock / kWave][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  s = wave_sum(s); c = wave_sum(c);
+  if (lane == 0) { sm[wave][0] = s; sm[wave][1] = c; }
+  __syncthreads();
+  if (threadIdx.x < 2) rows[(size_t)blockIdx.x * 2 + threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+}
+
+// one wave per edge: lane l sums the edge's rows l, l + 64, ... in order, then the lanes are summed in a fixed order
+__global__ __launch_bounds__(kWave) void fb_close_kernel(const int* __restrict__ row0s, const double* __restrict__ rows, const int n_edges,
+                                                         double* __restrict__ out) {
+  const int e = blockIdx.x;
+  if (e >= n_edges) return;
+  const int r0 = row0s[e], nr = row0s[e + 1] - r0;
+  double s = 0.0, c = 0.0;
+  for (int k = threadIdx.x; k < nr; k += kWave) {
+    s += rows[(size_t)(r0 + k) * 2];
+    c += rows[(size_t)(r0 + k) * 2 + 1];
+  }
+  s = wave_sum(s); c = wave_sum(c);
+  if (threadIdx.x == 0) {
+    out[e * 2] = s;
+    out[e * 2 + 1] = c;
+  }
+}
+
+// ---- batched Hilbert index build ---------------------------------------------------------------------------------------------
+// blockIdx.y = cloud.  Boxes of the finite points (minmax_kernel / minmax_final_kernel of ndt_voxel.hip per segment; min and max
+// are exact, so the order of the folds does not show in the result).
+__global__ __launch_bounds__(kBlock) void fb_minmax_kernel(const FbSeg* __restrict__ segs, float* __restrict__ partial) {
+  const FbSeg& S = segs[blockIdx.y];
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < S.n; i += kFbMmBlocks * kBlock) {
+    const float4 p = S.pts[i];
+    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+      mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+      mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+    }
+  }
+  __shared__ float sm[kBlock / kWave][6];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      mn[a] = fminf(mn[a], __shfl_down(mn[a], off, 64));
+      mx[a] = fmaxf(mx[a], __shfl_down(mx[a], off, 64));
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0)
+    for (int a = 0; a < 3; a++) { sm[wave][a] = mn[a]; sm[wave][3 + a] = mx[a]; }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    float v = sm[0][threadIdx.x];
+    for (int w = 1; w < kBlock / kWave; w++) v = (threadIdx.x < 3) ? fminf(v, sm[w][threadIdx.x]) : fmaxf(v, sm[w][threadIdx.x]);
+    partial[((size_t)blockIdx.y * kFbMmBlocks + blockIdx.x) * 6 + threadIdx.x] = v;
+  }
+}
+
+__global__ __launch_bounds__(kWave) void fb_minmax_final_kernel(const float* __restrict__ partial, float* __restrict__ boxes) {
+  static_assert(kFbMmBlocks == kWave, "one partial box per lane");
+  const float* p = partial + ((size_t)blockIdx.x * kFbMmBlocks + threadIdx.x) * 6;
+  float v[6];
+#pragma unroll
+  for (int a = 0; a < 6; a++) v[a] = p[a];
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float o = __shfl_down(v[a], off, 64);
+      v[a] = (a < 3) ? fminf(v[a], o) : fmaxf(v[a], o);
+    }
+  }
+  if (threadIdx.x == 0)
+    for (int a = 0; a < 6; a++) boxes[(size_t)blockIdx.x * 6 + a] = v[a];
+}
+
+// hilbert_key_kernel (nn_bvh.hip) per segment, the cloud's number above the 30 key bits
+__global__ __launch_bounds__(kBlock) void fb_key_kernel(const FbSeg* __restrict__ segs, const float* __restrict__ boxes, unsigned long long* __restrict__ keys,
+                                                        uint32_t* __restrict__ vals) {
+  const FbSeg& S = segs[blockIdx.y];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= S.n) return;
+  const float* mm6 = boxes + (size_t)blockIdx.y * 6;
+  const float4 p = S.pts[i];
+  float org[3] = {mm6[0], mm6[1], mm6[2]};
+  float ext = fmaxf(fmaxf(mm6[3] - mm6[0], mm6[4] - mm6[1]), fmaxf(mm6[5] - mm6[2], 1e-6f));
+  if (!(mm6[0] <= mm6[3])) { org[0] = org[1] = org[2] = 0.f; ext = 1.f; }
+  const float scale = 1023.0f / ext;
+  const uint32_t k = (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) ? hilbert30(p.x, p.y, p.z, org, scale) : 0x3FFFFFFFu;
+  keys[(size_t)S.off + i] = ((unsigned long long)blockIdx.y << 30) | k;
+  vals[(size_t)S.off + i] = (uint32_t)i;
+}
+
+// gather_index_kernel (nn_bvh.hip) per segment, into the cloud's own Bvh::sorted
+__global__ __launch_bounds__(kBlock) void fb_gather_kernel(const FbSeg* __restrict__ segs, const uint32_t* __restrict__ order) {
+  const FbSeg& S = segs[blockIdx.y];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= S.n_pad) return;
+  if (i < S.n) {
+    const uint32_t o = order[(size_t)S.off + i];
+    float4 p = S.pts[o];
+    p.w = __uint_as_float(o);
+    S.sorted[i] = p;
+  } else {
+    S.sorted[i] = make_float4(NAN, NAN, NAN, __uint_as_float(0xFFFFFFFFu));  // padding: distance is NaN, never selected
+  }
+}
+
+// bvh_boxes_kernel (nn_bvh.hip) for step `step` of every cloud: step 0 its leaf slots, step k its level depth - k (none when that is the root)
+__global__ __launch_bounds__(kBlock) void fb_boxes_kernel(const FbSeg* __restrict__ segs, const int step) {
+  const FbSeg& S = segs[blockIdx.y];
+  const int level = S.depth - step;
+  if (level < 1) return;
+  const int count = 1 << (3 * level), first = (count - 1) / (kFan - 1);
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= count) return;
+  const int node = first + t;
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  if (step == 0) {
+#pragma unroll
+    for (int k = 0; k < kLeaf; k++) {
+      const int i = t * kLeaf + k;
+      if (i < S.n) {
+        const float4 p = S.sorted[i];
+        if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+          mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+          mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < kFan; k++) {
+      const float4 l = S.box_lo[node * kFan + k], h = S.box_hi[node * kFan + k];
+      mn[0] = fminf(mn[0], l.x); mn[1] = fminf(mn[1], l.y); mn[2] = fminf(mn[2], l.z);
+      mx[0] = fmaxf(mx[0], h.x); mx[1] = fmaxf(mx[1], h.y); mx[2] = fmaxf(mx[2], h.z);
+    }
+  }
+  // into the parent's child-box arrays: parent * kFan + slot = node - 1
+  S.box_lo[node - 1] = make_float4(mn[0], mn[1], mn[2], 0.f);
+  S.box_hi[node - 1] = make_float4(mx[0], mx[1], mx[2], 0.f);
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+static int fb_host_reserve(dgs_handle* h, void*& p, size_t& cap, size_t bytes) {
+  if (bytes <= cap) return DGS_OK;
+  if (p) (void)hipHostFree(p);
+  p = nullptr;
+  cap = 0;
+  const size_t want = bytes + bytes / 4 + 4096;
+  DGS_HIP_TRY(h, hipHostMalloc(&p, want, hipHostMallocDefault));
+  cap = want;
+  return DGS_OK;
+}
+
+int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, bool reset_counts) {
+  FbScratch& F = h->fb;
+  if (reset_counts) std::fill(F.counts8, F.counts8 + 8, 0);
+  if (side_join(h) != DGS_OK) return DGS_ERR_HIP;   // an index being built on the side stream
+  std::vector<dgs_cloud*> todo;
+  for (int i = 0; i < n; i++) {
+    dgs_cloud* c = clouds[i];
+    if (c->st.n > 0 && !c->st.bvh.valid && std::find(todo.begin(), todo.end(), c) == todo.end()) todo.push_back(c);
+  }
+  const int M = (int)todo.size();
+  if (M == 0) return DGS_OK;
+  hipStream_t st = h->stream;
+  // shapes first, for every cloud: a cloud that cannot be indexed fails the call before any Bvh has been touched
+  struct Shape { int n_pad, depth, first_leaf; int64_t slots; };
+  std::vector<Shape> shapes((size_t)M);
+  int64_t total = 0;
+  int max_n = 0, max_pad = 0, max_depth = 0;
+  for (int s = 0; s < M; s++) {
+    const int cn = (int)todo[s]->st.n, n_leaves = (cn + kLeaf - 1) / kLeaf;
+    int depth = 1;
+    int64_t slots = kFan;
+    while (slots < n_leaves) { slots *= kFan; depth++; }
+    if (depth > 8) { h->err = "cloud too large for the nearest-neighbour index (more than 8 levels)"; return DGS_ERR_UNSUPPORTED; }
+    shapes[s] = Shape{n_leaves * kLeaf, depth, (int)((slots - 1) / (kFan - 1)), slots};
+    total += cn;
+    max_n = std::max(max_n, cn);
+    max_pad = std::max(max_pad, shapes[s].n_pad);
+    max_depth = std::max(max_depth, depth);
+  }
+  if (total > INT32_MAX) { h->err = "dgs_cloud_build_indices: more than 2^31 points in one build"; return DGS_ERR_UNSUPPORTED; }
+  std::vector<FbSeg> segs((size_t)M);
+  int off = 0;
+  for (int s = 0; s < M; s++) {
+    CloudState& C = todo[s]->st;
+    Bvh& B = C.bvh;
+    const Shape& S = shapes[s];
+    B.valid = false;
+    B.n = C.n;
+    B.leaves = (int)S.slots;
+    B.levels = S.depth;
+    DGS_HIP_TRY(h, B.sorted.reserve((size_t)S.n_pad));
+    DGS_HIP_TRY(h, B.node_lo.reserve((size_t)S.first_leaf * kFan));
+    DGS_HIP_TRY(h, B.node_hi.reserve((size_t)S.first_leaf * kFan));
+    segs[s] = FbSeg{C.pts.ptr, B.sorted.ptr, B.node_lo.ptr, B.node_hi.ptr, (int)C.n, S.n_pad, off, S.depth};
+    off += (int)C.n;
+  }
+  DGS_HIP_TRY(h, F.segs.reserve((size_t)M));
+  DGS_HIP_TRY(h, F.mm.reserve((size_t)M * (kFbMmBlocks + 1) * 6));
+  DGS_HIP_TRY(h, F.keys.reserve((size_t)total));
+  DGS_HIP_TRY(h, F.keys_alt.reserve((size_t)total));
+  DGS_HIP_TRY(h, F.vals.reserve((size_t)total));
+  DGS_HIP_TRY(h, F.vals_alt.reserve((size_t)total));
+  int seg_bits = 0;
+  while ((1 << seg_bits) < M) seg_bits++;
+  size_t tb = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, F.keys.ptr, F.keys_alt.ptr, F.vals.ptr, F.vals_alt.ptr, (int)total, 0, 30 + seg_bits, st);
+  DGS_HIP_TRY(h, h->cub_temp.reserve(tb + 256));
+  // the table travels from a pinned block of its own, which the previous build's copy may still be reading
+  if (!F.ev_bstage) DGS_HIP_TRY(h, hipEventCreateWithFlags(&F.ev_bstage, hipEventDisableTiming));
+  if (F.bstage_pending && hipEventQuery(F.ev_bstage) != hipSuccess) {
+    DGS_HIP_TRY(h, hipEventSynchronize(F.ev_bstage));
+    F.counts8[1]++;
+  }
+  F.bstage_pending = false;
+  if (fb_host_reserve(h, F.bstage, F.bstage_bytes, sizeof(FbSeg) * (size_t)M) != DGS_OK) return DGS_ERR_HIP;
+  std::memcpy(F.bstage, segs.data(), sizeof(FbSeg) * (size_t)M);
+  DGS_HIP_TRY(h, hipMemcpyAsync(F.segs.ptr, F.bstage, sizeof(FbSeg) * (size_t)M, hipMemcpyHostToDevice, st));
+  DGS_HIP_TRY(h, hipEventRecord(F.ev_bstage, st));
+  F.bstage_pending = true;
+  float* boxes = F.mm.ptr + (size_t)M * kFbMmBlocks * 6;
+  hipLaunchKernelGGL(fb_minmax_kernel, dim3(kFbMmBlocks, M), dim3(kBlock), 0, st, F.segs.ptr, F.mm.ptr);
+  hipLaunchKernelGGL(fb_minmax_final_kernel, dim3(M), dim3(kWave), 0, st, F.mm.ptr, boxes);
+  hipLaunchKernelGGL(fb_key_kernel, dim3((max_n + kBlock - 1) / kBlock, M), dim3(kBlock), 0, st, F.segs.ptr, boxes, F.keys.ptr, F.vals.ptr);
+  tb = h->cub_temp.cap;
+  DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, F.keys.ptr, F.keys_alt.ptr, F.vals.ptr, F.vals_alt.ptr, (int)total, 0, 30 + seg_bits, st));
+  hipLaunchKernelGGL(fb_gather_kernel, dim3((max_pad + kBlock - 1) / kBlock, M), dim3(kBlock), 0, st, F.segs.ptr, F.vals_alt.ptr);
+  F.counts8[0] += 5;
+  // leaf slots first, then every internal level bottom-up (the root's own box is never needed)
+  for (int step = 0; step < max_depth; step++) {
+    const int64_t count = (int64_t)1 << (3 * (max_depth - step));
+    hipLaunchKernelGGL(fb_boxes_kernel, dim3((unsigned)((count + kBlock - 1) / kBlock), M), dim3(kBlock), 0, st, F.segs.ptr, step);
+    F.counts8[0]++;
+  }
+  DGS_HIP_TRY(h, hipGetLastError());
+  for (dgs_cloud* c : todo) {
+    c->st.bvh.kd = false;
+    c->st.bvh.valid = true;
+  }
+  F.counts8[3] += M;
+  return DGS_OK;
+}
+
+int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_range,
+                         double* scores, int64_t* used) {
+  FbScratch& F = h->fb;
+  std::fill(F.counts8, F.counts8 + 8, 0);
+  if (n_edges == 0) return DGS_OK;
+  F.counts8[2] = n_edges;
+  int rc = fitness_batch_build_indices(h, n_edges, cloud1s, false);
+  if (rc != DGS_OK) return rc;
+  // one pinned block: [row prefix | edge table] up, [sum, used per edge] down
+  const size_t pre_bytes = (((size_t)n_edges + 1) * sizeof(int) + 127) & ~(size_t)127;
+  const size_t up_bytes = pre_bytes + (size_t)n_edges * sizeof(FbEdge), down_bytes = (size_t)n_edges * 2 * sizeof(double);
+  if (fb_host_reserve(h, F.stage, F.stage_bytes, up_bytes + down_bytes) != DGS_OK) return DGS_ERR_HIP;
+  int* row0s = reinterpret_cast<int*>(F.stage);
+  FbEdge* edges = reinterpret_cast<FbEdge*>(reinterpret_cast<char*>(F.stage) + pre_bytes);
+  double* down = reinterpret_cast<double*>(reinterpret_cast<char*>(F.stage) + up_bytes);
+  int64_t total_rows = 0;
+  for (int e = 0; e < n_edges; e++) {
+    const CloudState& c1 = cloud1s[e]->st;
+    const CloudState& c2 = cloud2s[e]->st;
+    FbEdge& E = edges[e];
+    std::memset(&E, 0, sizeof(E));
+    const bool empty = c1.n == 0 || c2.n == 0;   // no neighbour / no query: the "nr == 0" branch of the reference
+    if (!empty) {
+      E.b = make_bvh_view(c1.bvh);
+      E.src = c2.pts.ptr;
+      E.n = (int)c2.n;
+      E.rows = fb_rows_of(E.n);
+    }
+    E.row0 = (int)total_rows;
+    std::memcpy(E.T, relposes16 ? relposes16 + (size_t)e * 16 : kIdentity16, sizeof(float) * 16);
+    row0s[e] = (int)total_rows;
+    total_rows += E.rows;
+  }
+  row0s[n_edges] = (int)total_rows;
+  F.counts8[4] = total_rows;
+  if (total_rows > 0) {
+    hipStream_t st = h->stream;
+    DGS_HIP_TRY(h, F.tab.reserve(up_bytes));
+    DGS_HIP_TRY(h, F.rows.reserve((size_t)total_rows * 2 + (size_t)n_edges * 2));
+    double* d_out = F.rows.ptr + (size_t)total_rows * 2;
+    DGS_HIP_TRY(h, hipMemcpyAsync(F.tab.ptr, F.stage, up_bytes, hipMemcpyHostToDevice, st));
+    const int* d_row0s = reinterpret_cast<const int*>(F.tab.ptr);
+    const FbEdge* d_edges = reinterpret_cast<const FbEdge*>(F.tab.ptr + pre_bytes);
+    // PCL's comparison is float(sq_dist) <= double(max_range); clamp so DBL_MAX keeps every finite distance
+    const float mr = (max_range >= (double)FLT_MAX) ? FLT_MAX : (float)max_range;
+    hipLaunchKernelGGL(fb_walk_kernel, dim3((unsigned)total_rows), dim3(kBlock), 0, st, d_row0s, d_edges, n_edges, mr, F.rows.ptr);
+    hipLaunchKernelGGL(fb_close_kernel, dim3(n_edges), dim3(kWave), 0, st, d_row0s, F.rows.ptr, n_edges, d_out);
+    F.counts8[0] += 2;
+    DGS_HIP_TRY(h, hipMemcpyAsync(down, d_out, down_bytes, hipMemcpyDeviceToHost, st));
+    DGS_HIP_TRY(h, hipStreamSynchronize(st));
+    F.counts8[1]++;
+    F.bstage_pending = false;   // the build's upload went first on the same stream
+    DGS_HIP_TRY(h, hipGetLastError());
+  }
+  for (int e = 0; e < n_edges; e++) {
+    const double sum = edges[e].rows ? down[e * 2] : 0.0, cnt = edges[e].rows ? down[e * 2 + 1] : 0.0;
+    scores[e] = cnt > 0.0 ? sum / cnt : DBL_MAX;
+    if (used) used[e] = (int64_t)cnt;
+  }
+  return DGS_OK;
+}
+
+void fitness_batch_release(dgs_handle* h) {
+  FbScratch& F = h->fb;
+  F.tab.release(); F.rows.release(); F.segs.release(); F.mm.release(); F.keys.release(); F.keys_alt.release(); F.vals.release(); F.vals_alt.release();
+  if (F.stage) (void)hipHostFree(F.stage);
+  if (F.bstage) (void)hipHostFree(F.bstage);
+  if (F.ev_bstage) (void)hipEventDestroy(F.ev_bstage);
+  F.stage = F.bstage = nullptr;
+  F.stage_bytes = F.bstage_bytes = 0;
+  F.ev_bstage = nullptr;
+}
+
+}  // namespace dgs

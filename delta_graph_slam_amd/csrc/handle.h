@@ -236,6 +236,26 @@ struct FdScratch {
   dgs_floor_detection_trace trace{};
 };
 
+// calc_fitness_score over a batch of (cloud1, cloud2, relpose) edges between resident clouds, and the batched Hilbert index build in
+// front of it (fitness_batch.hip): tables, keys and rows of its own; everything above is left untouched.
+struct FbEdge;    // fitness_batch.hip
+struct FbSeg;
+struct FbScratch {
+  DevBuf<unsigned char> tab;           // walk, one upload: the row prefix (n_edges + 1 ints), then the edge table
+  DevBuf<double> rows;                 // one partial row {sum, used} per (edge, slice); then {sum, used} per edge
+  void* stage = nullptr;               // pinned: the walk's upload, and behind it the download
+  size_t stage_bytes = 0;
+  DevBuf<FbSeg> segs;                  // build: per cloud to be indexed, its points, its index arrays and its offsets in the shared arrays
+  DevBuf<float> mm;                    // build: per cloud kFbMmBlocks partial boxes, then the boxes
+  DevBuf<unsigned long long> keys, keys_alt;   // build: (cloud number << 30) | hilbert30, all clouds back to back
+  DevBuf<uint32_t> vals, vals_alt;     // build: index of the point in its own cloud
+  void* bstage = nullptr;              // pinned: the build's upload; not written again before ev_bstage has passed
+  size_t bstage_bytes = 0;
+  hipEvent_t ev_bstage = nullptr;
+  bool bstage_pending = false;
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launches, host waits, edges, indices built, partial rows
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -382,6 +402,7 @@ struct dgs_handle {
   dgs::DevBuf<int> fc_out;
   dgs::DevBuf<long long> fc_cnt;
   dgs::Bvh aux_bvh;
+  int64_t bvh_builds = 0;           // bvh_build calls that built something, since dgs_create (dgs_fitness_batch_get_counts: who built an index is observable)
 
   // ---- GICP (fast_gicp::FastGICP): k-NN covariances of both clouds, correspondences, Mahalanobis matrices
   dgs::DevBuf<int> corr;
@@ -446,6 +467,9 @@ struct dgs_handle {
 
   // ---- floor detection (floor_detection.hip): own buffers; everything above is left untouched
   dgs::FdScratch fd;
+
+  // ---- batched calc_fitness_score between resident clouds (fitness_batch.hip): own buffers; everything above is left untouched
+  dgs::FbScratch fb;
 
   dgs::Profiler prof;
 };
@@ -542,6 +566,11 @@ void line_align_local_release(dgs_handle* h);
 void building_overlap_release(dgs_handle* h);
 // floor_detection.hip
 void floor_detection_release(dgs_handle* h);
+// fitness_batch.hip
+int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, bool reset_counts = true);
+int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_range,
+                         double* scores, int64_t* used);
+void fitness_batch_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -428,6 +428,7 @@ int bvh_build(dgs_handle* h, Bvh& bvh, const float4* pts, int64_t n64, hipStream
   bvh.valid = false;
   bvh.n = n;
   if (n == 0) return DGS_OK;
+  h->bvh_builds++;
   const int n_leaves = (n + kLeaf - 1) / kLeaf;
   int depth = 1;
   int64_t slots = kFan;

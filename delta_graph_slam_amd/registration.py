@@ -314,6 +314,61 @@ class Registration:
                                                       max_range, C.byref(s)))
         return s.value
 
+    def _cloud_array(self, clouds):
+        """-> (void* array of dgs_cloud, the DeviceClouds behind it); arrays and tensors become temporary DeviceClouds, one per object."""
+        made = {}
+        objs = []
+        for c in clouds:
+            if not isinstance(c, DeviceCloud):
+                if id(c) not in made:
+                    made[id(c)] = DeviceCloud(self, c)
+                c = made[id(c)]
+            objs.append(c)
+        arr = (C.c_void_p * max(len(objs), 1))(*[o._c.value for o in objs])
+        return arr, objs, list(made.values())
+
+    def calc_fitness_score_batch(self, cloud1s, cloud2s, relposes=None, max_range: float = 1.7976931348623157e308, return_used: bool = False):
+        """calc_fitness_score for every edge (cloud1s[e], cloud2s[e], relposes[e]) in one call (dgs_calc_fitness_score_batch_clouds): the
+        index over each cloud1 is the one its DeviceCloud keeps, all edges are walked by one launch.  -> float64 [E] (and int64 [E] with
+        return_used: the points within max_range).  numpy arrays and device tensors are wrapped in DeviceClouds for the call."""
+        cloud1s, cloud2s = list(cloud1s), list(cloud2s)
+        n = len(cloud1s)
+        if len(cloud2s) != n:
+            raise ValueError("cloud1s and cloud2s differ in length")
+        arr, objs, temps = self._cloud_array(cloud1s + cloud2s)
+        a1 = (C.c_void_p * max(n, 1))(*arr[:n])
+        a2 = (C.c_void_p * max(n, 1))(*arr[n:2 * n])
+        t = None
+        if relposes is not None:
+            if len(relposes) != n:
+                raise ValueError("relposes and the clouds differ in length")
+            t = np.ascontiguousarray(np.stack([_col16(r) for r in relposes]) if n else np.zeros((0, 16), np.float32), dtype=np.float32)
+        scores = np.empty(n, dtype=np.float64)
+        used = np.zeros(n, dtype=np.int64)
+        try:
+            self._check(self._lib.dgs_calc_fitness_score_batch_clouds(self._h, n, C.cast(a1, C.c_void_p), C.cast(a2, C.c_void_p),
+                                                                      None if t is None else t.ctypes.data_as(C.c_void_p), float(max_range),
+                                                                      scores.ctypes.data_as(C.c_void_p), used.ctypes.data_as(C.c_void_p)))
+        finally:
+            for c in temps:
+                c.close()
+        return (scores, used) if return_used else scores
+
+    def build_indices(self, clouds):
+        """dgs_cloud_build_indices: the Hilbert-ordered NN index of every listed DeviceCloud that has none, in one batched build."""
+        clouds = list(clouds)
+        if not all(isinstance(c, DeviceCloud) for c in clouds):
+            raise TypeError("build_indices takes DeviceClouds")
+        arr = (C.c_void_p * max(len(clouds), 1))(*[c._c.value for c in clouds])
+        self._check(self._lib.dgs_cloud_build_indices(self._h, len(clouds), C.cast(arr, C.c_void_p)))
+
+    def fitness_batch_counts(self) -> dict:
+        """Of the last calc_fitness_score_batch / build_indices: kernel launches, host waits, edges, indices built, partial rows; and
+        single_builds: the single-cloud index builds this handle made by any other path since it was created."""
+        c = (C.c_int64 * 8)()
+        self._check(self._lib.dgs_fitness_batch_get_counts(self._h, C.cast(c, C.c_void_p)))
+        return {"launches": c[0], "host_waits": c[1], "edges": c[2], "indices_built": c[3], "rows": c[4], "single_builds": c[5]}
+
     def voxel_grid_filter(self, cloud, leaf_size: float, approximate: bool = False):
         """pcl::VoxelGrid centroid filter (scan_matching_odometry_nodelet.cpp:83-89,155-165) -- or, with approximate=True,
         pcl::ApproximateVoxelGrid (:90-96) -- on the device.

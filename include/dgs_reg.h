@@ -295,6 +295,28 @@ int dgs_find_loop_candidates(dgs_handle* h, const double* accum_distance, const 
 int dgs_calc_fitness_score(dgs_handle* h, const float* cloud1_xyz16, int64_t n1, const float* cloud2_xyz16, int64_t n2,
                            int32_t on_device, const float* relpose16, double max_range, double* score);
 
+/* The same over a batch of edges between device-resident clouds: what one optimisation tick asks for (up to max_keyframes_per_update
+ * odometry edges, apps/delta_graph_slam_nodelet.cpp:572, and one per accepted loop, :820).  Edge e is calc_fitness_score(cloud1s[e],
+ * cloud2s[e], relpose e, max_range) with exactly dgs_calc_fitness_score's semantics; relposes16 holds n_edges x 16 column-major
+ * floats (NULL = identity everywhere); used[e] (nullable) receives the reference's nr, scores[e] DBL_MAX when nr == 0 or a cloud is
+ * empty.  A cloud may stand in any number of edges, on either side, on both sides of one edge.  The index over cloud1 is the one the
+ * dgs_cloud keeps: built here when it has none (all missing ones in one batched Hilbert-order build), kept for every later user
+ * (registration target, loop detection, ICP walks), used as it is when it exists (Hilbert or k-d order).  One walk launch over all
+ * edges, one closing launch, one download, one host wait.  An edge's partial rows are a function of its own cloud2 size and are summed
+ * in a fixed order, so its (score, used) is bit-identical in any batch, at any position, and alone.  DGS_NN_GRID has no effect here.
+ * The handle's registration target / source / result are untouched.  n_edges == 0: DGS_OK without a launch.  A NULL cloud or a cloud
+ * of another device: DGS_ERR_INVALID_ARGUMENT. */
+int dgs_calc_fitness_score_batch_clouds(dgs_handle* h, int32_t n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s,
+                                        const float* relposes16, double max_range, double* scores, int64_t* used);
+/* Builds the Hilbert-ordered exact-NN index of every listed cloud that has none, all of them together: a number of launches that
+ * follows the deepest cloud, not n; no host wait (the work is enqueued on the handle's stream).  The indices equal, bit for bit,
+ * what each cloud would get as a registration target. */
+int dgs_cloud_build_indices(dgs_handle* h, int32_t n, dgs_cloud* const* clouds);
+/* counts8: of the last dgs_calc_fitness_score_batch_clouds (or dgs_cloud_build_indices) call kernel launches (the radix sort
+ * counts as one), host waits, edges, indices built, partial rows; then, not of that call but since dgs_create, the single-cloud index
+ * builds this handle made by any other path (registration targets, the prefilter, dgs_calc_fitness_score ...); the rest 0. */
+int dgs_fitness_batch_get_counts(dgs_handle* h, int64_t* counts8);
+
 /* pcl::VoxelGrid<PointXYZ> centroid down-sampling, the step right before the path
  * (/root/reference/apps/scan_matching_odometry_nodelet.cpp:83-89,155-165; apps/prefiltering_nodelet.cpp:59-63):
  * cell = floor(p / leaf) as PCL indexes it, output = centroid of every occupied cell in cell-index order, pad lane = 1.
