@@ -205,6 +205,12 @@ struct NdtInit {  // host -> device per pair, per align
 // Deals the workgroups of a launch evenly to the pairs of a batch for which pred(pair index) holds (the pairs that still
 // iterate).  Every wave derives the same mapping: one strided load + ballot per 64 pairs, no inter-block traffic.
 // Returns false when this workgroup has nothing to do.  gridDim.x must be >= the number of pairs.
+// The counting pass keeps the ballots of the first kDealKept x 64 pairs in scalar registers and the choosing pass reads those instead of
+// evaluating pred -- a load from the pair's record and its round trip -- again; pairs beyond that are evaluated twice as before.  pred must
+// give the same answer both times, as ever.  (Both passes keep the shape of one loop over c0: with the kept chunks unrolled into passes of
+// their own, or the choice in a helper function, the compiler laid the fixed-slices kernels' row flush out in front of their tile loop, and
+// tests/test_isa_handoff.py reads the hand-off sequence in program text order.)  Test hook: dgs_deal_probe.
+constexpr int kDealKept = 4;
 #ifdef __HIPCC__
 template <class Pred>
 __device__ inline bool deal_workgroup(const int n_pairs, const int cap_blocks, Pred pred, int& pair, int& slice, int& blocks_per_pair, int* n_active_out = nullptr,
@@ -212,10 +218,16 @@ __device__ inline bool deal_workgroup(const int n_pairs, const int cap_blocks, P
   const int block_id = block_id_in >= 0 ? block_id_in : (int)blockIdx.x, grid = grid_in >= 0 ? grid_in : (int)gridDim.x;   // a kernel may keep some workgroups for other work
   const int lane_id = threadIdx.x & 63;
   int n_active = 0;
+  unsigned long long kept[kDealKept];
+#pragma unroll
+  for (int j = 0; j < kDealKept; j++) kept[j] = 0ull;
   for (int c0 = 0; c0 < n_pairs; c0 += 64) {
     const int pi = c0 + lane_id;
     const bool a = (pi < n_pairs) && pred(pi);
-    n_active += __popcll(__ballot(a));
+    const unsigned long long m = __ballot(a);
+#pragma unroll
+    for (int j = 0; j < kDealKept; j++) kept[j] = (c0 == j * 64) ? m : kept[j];
+    n_active += __popcll(m);
   }
   if (n_active_out) *n_active_out = n_active;
   if (n_active == 0) return false;
@@ -225,9 +237,14 @@ __device__ inline bool deal_workgroup(const int n_pairs, const int cap_blocks, P
   if (rank >= n_active) return false;
   int found = -1, seen = 0;
   for (int c0 = 0; c0 < n_pairs && found < 0; c0 += 64) {
-    const int pi = c0 + lane_id;
-    const bool a = (pi < n_pairs) && pred(pi);
-    unsigned long long m = __ballot(a);
+    unsigned long long m = 0ull;
+    if (c0 < kDealKept * 64) {
+#pragma unroll
+      for (int j = 0; j < kDealKept; j++) m = (c0 == j * 64) ? kept[j] : m;
+    } else {
+      const int pi = c0 + lane_id;
+      m = __ballot((pi < n_pairs) && pred(pi));
+    }
     const int cnt = __popcll(m);
     if (rank < seen + cnt) {
       for (int k = rank - seen; k > 0; k--) m &= m - 1ull;  // drop the (rank - seen) lowest set bits

@@ -257,6 +257,12 @@ int cloud_clone_to(dgs_handle* h, const dgs_cloud* src, dgs_cloud** out) {
   *out = c;
   return DGS_OK;
 }
+// dgs_deal_probe: what deal_workgroup (common.h) derives in every wave of every workgroup of a grid, for an activity mask given as data
+__global__ __launch_bounds__(kBlock) void deal_probe_kernel(const int* __restrict__ active, const int n_pairs, const int cap_blocks, int4* __restrict__ out) {
+  int pair = -1, slice = -1, blocks_per_pair = -1, n_active = -1;
+  const bool ok = deal_workgroup(n_pairs, cap_blocks, [&](int pi) { return active[pi] != 0; }, pair, slice, blocks_per_pair, &n_active);
+  if ((threadIdx.x & 63) == 0) out[blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)] = ok ? make_int4(pair, slice, blocks_per_pair, n_active) : make_int4(-1, -1, -1, n_active);
+}
 }  // namespace dgs
 
 static thread_local std::string g_create_error;  // dgs_last_error(NULL): why the last dgs_create on this thread failed
@@ -1009,6 +1015,42 @@ int dgs_ndt_hessian_double(dgs_handle* h, const double* p6, double* hess36) {
   if (!h->have_source || h->ns == 0) return DGS_ERR_NO_SOURCE;
   double score, g6[6];
   return ndt_probe(h, p6, nullptr, &score, g6, hess36, 2);
+}
+
+int dgs_ndt_score_gradient(dgs_handle* h, const double* p6, double* score, double* grad6) {
+  if (!h || !p6 || !score || !grad6) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  if (!is_ndt_family(h) || is_pcl_ndt(h) || h->prm.ndt_strict_order == DGS_NDT_ORDER_FAST) return DGS_ERR_UNSUPPORTED;
+  if (!h->have_target || h->nt == 0) return DGS_ERR_NO_TARGET;
+  if (!h->have_source || h->ns == 0) return DGS_ERR_NO_SOURCE;
+  double unused[36];
+  return ndt_probe(h, p6, nullptr, score, grad6, unused, 0);
+}
+
+int dgs_deal_probe(dgs_handle* h, const int32_t* active, int32_t n_pairs, int32_t cap_blocks, int32_t grid, int32_t* out) {
+  if (!h || !active || !out || n_pairs < 1 || cap_blocks < 1 || grid < n_pairs || grid > (1 << 20)) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  DevBuf<int> d_active;
+  DevBuf<int4> d_out;
+  const size_t n_out = (size_t)grid * (kBlock / kWave);
+  hipError_t e = d_active.reserve((size_t)n_pairs);
+  if (e == hipSuccess) e = d_out.reserve(n_out);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_active.ptr, active, sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(deal_probe_kernel, dim3(grid), dim3(kBlock), 0, h->stream, d_active.ptr, n_pairs, cap_blocks, d_out.ptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.ptr, sizeof(int4) * n_out, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  d_active.release();
+  d_out.release();
+  if (e != hipSuccess) {
+    h->err = std::string("dgs_deal_probe: ") + hipGetErrorString(e);
+    return DGS_ERR_HIP;
+  }
+  return DGS_OK;
 }
 
 int dgs_find_loop_candidates(dgs_handle* h, const double* accum_distance, const double* xy, int64_t n, int32_t on_device, double new_accum_distance,

@@ -244,27 +244,90 @@ __device__ __forceinline__ void strict_item(const float (&xt)[3], const float (&
   strict_item<NEED_H, GLIBC_ONLY>(xt, xj, xh, strict_load_rec(rec), gauss_d1, gd2, acc, exptab);
 }
 
+// The pair's evaluation header as the per-point phase reads it: the float angle tables and, for the double pass, the double angle vectors.
+// The values are wave-uniform and constant for a launch, but the compiler can neither keep 69 of them in registers at 256 VGPRs nor prove that
+// pairs[pair] does not alias the kernel's stores: read through the NdtPair record they were 38 vector loads from L2 per 64 points, issued in
+// groups behind s_waitcnt vmcnt -- 2 dependent round trips per sub-tile for a score + gradient evaluation, ~9 for the double pass.  The
+// item-compacted kernel therefore copies them ONCE per workgroup into this block in LDS (ndt_strict3_kernel, in front of its first barrier) and
+// every lane reads the same address (a broadcast read).  StrictHeader<false>: the record in global memory, as before -- the lane-per-point
+// kernel, the sequential order and the fixed-slices instantiations, whose LDS is spoken for (and which so stay the bit reference of the copy).
+// A/B build `make ab AB=-DDGS_STRICT_LDS_HEADER=0`: every kernel reads the record.
+#ifndef DGS_STRICT_LDS_HEADER
+#define DGS_STRICT_LDS_HEADER 1
+#endif
+struct StrictHeaderBlock {   // NdtPair's jang / hang and jang_d / hang_d, each pair of tables contiguous as in the record
+  float jang[8][3];
+  float hang[15][3];
+  float pad;
+  double jang_d[8][3];
+  double hang_d[15][3];
+};
+constexpr int kStrictHeaderFloatWords = 8 * 3 + 15 * 3;                          // 4-byte words 0..68: jang, hang
+constexpr int kStrictHeaderDoubleWord0 = kStrictHeaderFloatWords + 1;            // words 70..207: jang_d, hang_d
+constexpr int kStrictHeaderWords = kStrictHeaderDoubleWord0 + 2 * kStrictHeaderFloatWords;
+static_assert(sizeof(StrictHeaderBlock) == kStrictHeaderWords * 4 && sizeof(StrictHeaderBlock) <= 1024 && kStrictHeaderWords <= kBlock, "one word per thread, at most 1 KiB");
+static_assert(offsetof(StrictHeaderBlock, hang) == kStrictHeaderFloatWords * 4 - sizeof(float[15][3]) && offsetof(StrictHeaderBlock, jang_d) == kStrictHeaderDoubleWord0 * 4, "block layout");
+static_assert(offsetof(NdtPair, hang) == offsetof(NdtPair, jang) + sizeof(float[8][3]) && offsetof(NdtPair, hang_d) == offsetof(NdtPair, jang_d) + sizeof(double[8][3]),
+              "the record keeps each pair of tables contiguous: one run of words per precision");
+typedef const __attribute__((address_space(3))) StrictHeaderBlock* strict_header_lds_t;
+template <bool LDS>
+struct StrictHeader {
+  static constexpr bool kLds = LDS;
+  strict_header_lds_t blk;        // LDS = true: the workgroup's copy
+  const NdtPair* st;              // LDS = false: the record
+  // The same view behind a pointer the optimiser cannot see through, taken once per sub-tile.  The block is loop-invariant and provably not
+  // written in the tile loop, so the reads would otherwise be hoisted out of it: 69 values live across the item loops of a kernel that sits at
+  // 256 VGPRs (seen: 53 spilled VGPRs, 212 B of scratch).  No instruction: the address stays in its SGPR.
+  __device__ __forceinline__ StrictHeader per_use() const {
+    if (!LDS) return *this;
+    unsigned a = (unsigned)(unsigned long long)blk;
+    asm volatile("" : "+s"(a));
+    return StrictHeader{(strict_header_lds_t)(unsigned long long)a, st};
+  }
+  __device__ __forceinline__ float jang(const int i, const int c) const { return LDS ? blk->jang[i][c] : st->jang[i][c]; }
+  __device__ __forceinline__ float hang(const int i, const int c) const { return LDS ? blk->hang[i][c] : st->hang[i][c]; }
+  __device__ __forceinline__ double jang_d(const int i, const int c) const { return LDS ? blk->jang_d[i][c] : st->jang_d[i][c]; }
+  __device__ __forceinline__ double hang_d(const int i, const int c) const { return LDS ? blk->hang_d[i][c] : st->hang_d[i][c]; }
+};
+// Thread t of the workgroup copies word t of the block with a plain load: one round trip for the whole header.  The float tables share their
+// three cache lines with T and need_hessian, which the workgroup loads anyway, so they are copied whatever the kind; the double vectors (five
+// more lines) only for the double pass.  Cut in two -- the load, then the store -- so that the caller can put its other table loads between
+// them and pay one wait for all (as two `if (...) dst = src` blocks the compiler kept a vmcnt(0) in each).
+typedef unsigned __attribute__((may_alias)) strict_header_word_t;
+__device__ __forceinline__ bool strict_header_load(const NdtPair& st, const bool with_doubles, strict_header_word_t& w) {
+  const int t = threadIdx.x;
+  const bool f = t < kStrictHeaderFloatWords, d = with_doubles && t >= kStrictHeaderDoubleWord0 && t < kStrictHeaderWords;
+  const strict_header_word_t* src = f ? reinterpret_cast<const strict_header_word_t*>(&st.jang[0][0]) + t
+                                      : reinterpret_cast<const strict_header_word_t*>(&st.jang_d[0][0]) + (t - kStrictHeaderDoubleWord0);
+  w = 0u;
+  if (f || d) w = *src;
+  return f || d;
+}
+__device__ __forceinline__ void strict_header_store(StrictHeaderBlock* blk, const bool mine, const strict_header_word_t w) {
+  if (mine) reinterpret_cast<strict_header_word_t*>(blk)[threadIdx.x] = w;
+}
+
 // the point's products with the float angle tables (computePointDerivatives).  As in the default order's kernel: rows 5..7 of the first
 // table and rows 4, 5, 9..14 of the second have an exact zero z entry (the term adds +-0: skipped), and nine of the fifteen second-table rows
 // are first-table rows again -- the same double expressions or their exact negations (a2 = -b, a3 = a, b2 = -e, b3 = d, c2 = -h, c3 = g,
 // f1 / f2 / f3 = the xy parts of d1 / a2 / a3), so the float products are the same bits or their negations (IEEE rounding is symmetric).
-template <bool NEED_H>
-__device__ __forceinline__ void strict_point_tables(const float4 x, const NdtPair& st, float (&xj)[8], float (&xh)[15]) {
-  const float jxy0 = st.jang[0][0] * x.x + st.jang[0][1] * x.y, jxy1 = st.jang[1][0] * x.x + st.jang[1][1] * x.y;
-  xj[0] = jxy0 + st.jang[0][2] * x.z;
-  xj[1] = jxy1 + st.jang[1][2] * x.z;
+template <bool NEED_H, class HDR>
+__device__ __forceinline__ void strict_point_tables(const float4 x, const HDR& st, float (&xj)[8], float (&xh)[15]) {
+  const float jxy0 = st.jang(0, 0) * x.x + st.jang(0, 1) * x.y, jxy1 = st.jang(1, 0) * x.x + st.jang(1, 1) * x.y;
+  xj[0] = jxy0 + st.jang(0, 2) * x.z;
+  xj[1] = jxy1 + st.jang(1, 2) * x.z;
 #pragma unroll
-  for (int i = 2; i < 5; i++) xj[i] = st.jang[i][0] * x.x + st.jang[i][1] * x.y + st.jang[i][2] * x.z;
+  for (int i = 2; i < 5; i++) xj[i] = st.jang(i, 0) * x.x + st.jang(i, 1) * x.y + st.jang(i, 2) * x.z;
 #pragma unroll
-  for (int i = 5; i < 8; i++) xj[i] = st.jang[i][0] * x.x + st.jang[i][1] * x.y;
+  for (int i = 5; i < 8; i++) xj[i] = st.jang(i, 0) * x.x + st.jang(i, 1) * x.y;
   if (NEED_H) {
     xh[0] = -xj[1]; xh[1] = xj[0]; xh[2] = -xj[4]; xh[3] = xj[3]; xh[4] = -xj[7]; xh[5] = xj[6];
-    const float hxy6 = st.hang[6][0] * x.x + st.hang[6][1] * x.y;
-    xh[6] = hxy6 + st.hang[6][2] * x.z;
+    const float hxy6 = st.hang(6, 0) * x.x + st.hang(6, 1) * x.y;
+    xh[6] = hxy6 + st.hang(6, 2) * x.z;
 #pragma unroll
-    for (int i = 7; i < 9; i++) xh[i] = st.hang[i][0] * x.x + st.hang[i][1] * x.y + st.hang[i][2] * x.z;
+    for (int i = 7; i < 9; i++) xh[i] = st.hang(i, 0) * x.x + st.hang(i, 1) * x.y + st.hang(i, 2) * x.z;
 #pragma unroll
-    for (int i = 9; i < 12; i++) xh[i] = st.hang[i][0] * x.x + st.hang[i][1] * x.y;
+    for (int i = 9; i < 12; i++) xh[i] = st.hang(i, 0) * x.x + st.hang(i, 1) * x.y;
     xh[12] = hxy6; xh[13] = -jxy1; xh[14] = jxy0;
   } else {
 #pragma unroll
@@ -278,7 +341,7 @@ __device__ __forceinline__ void strict_point(const float4 x, const float (&xt)[3
                                              const VoxelStrictRec* __restrict__ vs, const double gauss_d1, const float gd2, double (&acc)[kStrictAccum],
                                              const unsigned long long* __restrict__ exptab) {
   float xj[8], xh[15];
-  strict_point_tables<NEED_H>(x, st, xj, xh);
+  strict_point_tables<NEED_H>(x, StrictHeader<false>{nullptr, &st}, xj, xh);
   while (mask) {
     const int k = __ffs(mask) - 1;
     mask &= mask - 1u;
@@ -371,12 +434,29 @@ __device__ __forceinline__ bool strict_item_hd(const float (&xt)[3], const doubl
   return strict_item_hd_rec<ROWS, const StrictHdRow&>(xt, xj, xh, row, gauss_d1, gauss_d2, acc, rows, row_stride, exptab_d);
 }
 
-__device__ __forceinline__ void strict_point_tables_hd(const float4 xf, const NdtPair& st, double (&xj)[8], double (&xh)[15]) {
+// With the block in LDS the rows are read in groups -- four or five rows' reads issued together, then their products -- with the scheduler held
+// to that order: left alone it interleaved one ds_read2_b64 and its multiplications, an lgkmcnt(0) behind every read (26 LDS round trips
+// one after the other per sub-tile).  Same products and sums in the same order.
+template <int I0, int N, bool JANG, class HDR>
+__device__ __forceinline__ void strict_rows_hd(const double (&x)[3], const HDR& st, double* out) {
+  double r[N][3];
+#pragma unroll
+  for (int k = 0; k < N; k++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) r[k][c] = JANG ? st.jang_d(I0 + k, c) : st.hang_d(I0 + k, c);
+  if (HDR::kLds) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < N; k++) out[I0 + k] = x[0] * r[k][0] + x[1] * r[k][1] + x[2] * r[k][2];
+  if (HDR::kLds) __builtin_amdgcn_sched_barrier(0);
+}
+template <class HDR>
+__device__ __forceinline__ void strict_point_tables_hd(const float4 xf, const HDR& st, double (&xj)[8], double (&xh)[15]) {
   const double x[3] = {(double)xf.x, (double)xf.y, (double)xf.z};
-#pragma unroll
-  for (int i = 0; i < 8; i++) xj[i] = x[0] * st.jang_d[i][0] + x[1] * st.jang_d[i][1] + x[2] * st.jang_d[i][2];
-#pragma unroll
-  for (int i = 0; i < 15; i++) xh[i] = x[0] * st.hang_d[i][0] + x[1] * st.hang_d[i][1] + x[2] * st.hang_d[i][2];
+  strict_rows_hd<0, 4, true>(x, st, xj);
+  strict_rows_hd<4, 4, true>(x, st, xj);
+  strict_rows_hd<0, 5, false>(x, st, xh);
+  strict_rows_hd<5, 5, false>(x, st, xh);
+  strict_rows_hd<10, 5, false>(x, st, xh);
 }
 
 // One point.  ROWS = true: every slot is visited and written -- zeros where a slot holds no voxel or the voxel's weight fails upstream's
@@ -387,7 +467,7 @@ __device__ __forceinline__ void strict_point_hd(const float4 xf, const float (&x
                                                 double* __restrict__ rows, const size_t row_stride, const unsigned long long* __restrict__ exptab_d) {
   constexpr int NB = Offsets<SEARCH>::N;
   double xj[8], xh[15];
-  strict_point_tables_hd(xf, st, xj, xh);
+  strict_point_tables_hd(xf, StrictHeader<false>{nullptr, &st}, xj, xh);
   unsigned mask = ROWS ? ((NB >= 32) ? 0xFFFFFFFFu : ((1u << NB) - 1u)) : mask_in;
   while (mask) {
     const int k = __ffs(mask) - 1;
@@ -498,12 +578,18 @@ __device__ __forceinline__ void ndt_close_strict(NdtPair* st, const double* rows
   constexpr int kWords = (int)(sizeof(NdtSolver) / 8);
   double word = 0.0;
   // a speculated step behind this evaluation (NdtPair::spec_s): the exact state and its verdict were left by a wave of THIS launch -> coherent loads
+  // The flags, the kind and BOTH candidate state words are requested together and chosen among afterwards: loaded one behind the other's
+  // test they were three dependent round trips at the head of every closing, on the launch's critical path.  (Without a speculated step the
+  // verdict and the exact state are stale words of the pair's own record: loaded, not used.)
   const int spec_pending = st->spec_pending;
-  const int spec_result = spec_pending ? __hip_atomic_load(&st->spec_result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-  if (threadIdx.x < kWords)
-    word = (spec_pending && spec_result != 0) ? __hip_atomic_load(reinterpret_cast<const double*>(&st->spec_s) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                        : reinterpret_cast<const double*>(&st->s)[threadIdx.x];
   const int kind = st->need_hessian;
+  const int spec_verdict = __hip_atomic_load(&st->spec_result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x < kWords) {
+    const double exact = __hip_atomic_load(reinterpret_cast<const double*>(&st->spec_s) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double own = reinterpret_cast<const double*>(&st->s)[threadIdx.x];
+    word = (spec_pending && spec_verdict != 0) ? exact : own;
+  }
+  const int spec_result = spec_pending ? spec_verdict : 0;
   __shared__ double tot[kStrictPad];
   constexpr int G = kBlock / kStrictPad;   // 5 groups of 48 columns; threads 240.. idle
   __shared__ double sm[G][kStrictPad];
@@ -599,9 +685,11 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict_kernel(const float4* con
                                                               const int n_pairs, const int cap_blocks, int* __restrict__ pair_blocks, const NdtConsts consts,
                                                               int* __restrict__ done_flags, const int launch, const int hd_lag) {
   int pair, slice, blocks_per_pair;
-  if (!deal_workgroup(n_pairs, cap_blocks, [&](int pi) {
+  if (!deal_workgroup(n_pairs, cap_blocks, [&](int pi) -> bool {
         if (!FUSED) return pairs[pi].active != 0 && (pairs[pi].need_hessian == 2) == HD;
-        return HD ? (launch == pairs[pi].serve[1]) : (launch <= pairs[pi].serve[0] || launch == pairs[pi].serve[2]);
+        if (HD) return launch == pairs[pi].serve[1];
+        const int s0 = pairs[pi].serve[0], s2 = pairs[pi].serve[2];   // both words requested before either is compared: one round trip
+        return (launch <= s0) | (launch == s2);
       }, pair, slice, blocks_per_pair)) return;
   if (slice == 0 && threadIdx.x == 0) pair_blocks[pair] = blocks_per_pair;
   const NdtPair& st = pairs[pair];
@@ -876,12 +964,19 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   // start of the launch; the remaining workgroups are dealt to the pairs of the round as ever.  A solver workgroup takes a ticket like a slice.
   const int n_solvers = (FUSED && speculate) ? n_pairs : 0;
   const bool solver = FUSED && (int)blockIdx.x < n_solvers;   // (FUSED spelled out: the unfused kernels carry no solver role, tests/test_isa_handoff.py)
-  auto in_round = [&](int pi) {
-    return FUSED ? (launch <= pairs[pi].serve[0] || launch == pairs[pi].serve[2]) : (pairs[pi].active != 0 && (WITH_HD || pairs[pi].need_hessian != 2));
+  // (both words of a pair requested before either is compared: `a || b` on two loads is a branch, and the second load waits for the first)
+  auto in_round = [&](int pi) -> bool {
+    if (FUSED) {
+      const int s0 = pairs[pi].serve[0], s2 = pairs[pi].serve[2];
+      return (launch <= s0) | (launch == s2);
+    }
+    const int active = pairs[pi].active, nh = pairs[pi].need_hessian;
+    return (active != 0) & (WITH_HD || nh != 2);
   };
   if (solver) {
     pair = (int)blockIdx.x;
-    if (!in_round(pair) || !pairs[pair].spec_pending) return;
+    const int pending = pairs[pair].spec_pending;
+    if (!(in_round(pair) & (pending != 0))) return;
     slice = -1;
     const int lane_id = threadIdx.x & 63;
     for (int c0 = 0; c0 < n_pairs; c0 += 64) n_active += __popcll(__ballot(c0 + lane_id < n_pairs && in_round(c0 + lane_id)));
@@ -913,7 +1008,19 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   // for this shared copy; the double pass's 2 x 128 table in LDS as well: 5.37 / 3.342 against 5.38 / 3.342 ms (bench step / 8 x 200,000
   // points) for constant memory, where it therefore stays.
   __shared__ unsigned long long s_exp2f[32];
-  if (threadIdx.x < 32) s_exp2f[threadIdx.x] = kGlibcExp2fTab[threadIdx.x];
+  // the pair's angle tables in LDS, one copy for the four waves (StrictHeader); the solver workgroup multiplies no point.  Both tables'
+  // loads are issued before either is stored: one round trip in front of the barrier.
+  constexpr bool kLdsHeader = DGS_STRICT_LDS_HEADER != 0 && !FIXED;
+  __shared__ __attribute__((aligned(16))) StrictHeaderBlock s_hdr;
+  {
+    unsigned long long e2 = 0ull;
+    if (threadIdx.x < 32) e2 = kGlibcExp2fTab[threadIdx.x];
+    strict_header_word_t hw = 0u;
+    const bool mine = kLdsHeader && !solver && strict_header_load(st, WITH_HD && kind == 2, hw);
+    if (threadIdx.x < 32) s_exp2f[threadIdx.x] = e2;
+    if (kLdsHeader) strict_header_store(&s_hdr, mine, hw);
+  }
+  const StrictHeader<kLdsHeader> hdr_wg{(strict_header_lds_t)&s_hdr, &st};
   __syncthreads();
   const unsigned long long* __restrict__ exptab = s_exp2f;   // this kernel serves consts.exp_libm = 1 only (strict_kernel_version, ndt_align.hip)
   const unsigned long long* __restrict__ exptab_d = kGlibcExpTab;
@@ -975,6 +1082,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
     for (int sub = 0; sub < subs; sub++) {
       const int i = first + sub * stride + lane;
       const int slot = sub * 64 + lane;
+      const StrictHeader<kLdsHeader> hdr = hdr_wg.per_use();
       unsigned mask = 0;
       int vids[NB];
       if (i < n) {
@@ -987,7 +1095,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
         if (mask) {
           if (WITH_HD && kind == 2) {
             double xj[8], xh[15];
-            strict_point_tables_hd(x, st, xj, xh);
+            strict_point_tables_hd(x, hdr, xj, xh);
 #pragma unroll
             for (int f = 0; f < 8; f++) td[f * TL::PTS_HD + slot] = xj[f];
 #pragma unroll
@@ -996,8 +1104,8 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
             for (int f = 0; f < 3; f++) tdx[f * TL::PTS_HD + slot] = xt[f];
           } else {
             float xj[8], xh[15];
-            if (kind == 1) strict_point_tables<true>(x, st, xj, xh);
-            else strict_point_tables<false>(x, st, xj, xh);
+            if (kind == 1) strict_point_tables<true>(x, hdr, xj, xh);
+            else strict_point_tables<false>(x, hdr, xj, xh);
 #pragma unroll
             for (int f = 0; f < 3; f++) tf[f * TL::PTS + slot] = xt[f];
 #pragma unroll

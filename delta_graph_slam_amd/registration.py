@@ -586,6 +586,14 @@ class Registration:
         self._check(self._lib.dgs_ndt_hessian_double(self._h, p.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p)))
         return H
 
+    def ndt_score_gradient(self, p):
+        """The score + gradient evaluation of a More-Thuente trial at pose p (dgs_ndt_score_gradient; upstream evaluation orders only)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        s = C.c_double(0)
+        g = np.zeros(6)
+        self._check(self._lib.dgs_ndt_score_gradient(self._h, p.ctypes.data_as(C.c_void_p), C.byref(s), g.ctypes.data_as(C.c_void_p)))
+        return s.value, g
+
     def gicp_covariances(self, which: str = "source", n: int | None = None):
         c = self.counts()   # the library writes one 3x3 per point of the cloud it holds: size the buffer from ITS count
         n = int(c["source_points"] if which == "source" else c["target_points"])

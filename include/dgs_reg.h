@@ -408,6 +408,13 @@ int dgs_ndt_derivatives(dgs_handle* h, const double* p6, const float* T16, doubl
 /* NDT computeHessian in PCL's double-precision form at pose p (the pass computeStepLengthMT ends with when a line search took extra
  * trials; dgs_params.ndt_hessian_recompute_double).  Upstream evaluation orders only (DGS_ERR_UNSUPPORTED otherwise). */
 int dgs_ndt_hessian_double(dgs_handle* h, const double* p6, double* hess36);
+/* The score + gradient evaluation of a More-Thuente trial at pose p, through the kernels of the upstream evaluation orders (which skip the
+ * Hessian code for it).  Upstream evaluation orders only (DGS_ERR_UNSUPPORTED otherwise). */
+int dgs_ndt_score_gradient(dgs_handle* h, const double* p6, double* score, double* grad6);
+/* How a launch of `grid` workgroups is dealt to the pairs of a batch whose active[pair] != 0 (n_pairs host ints; grid >= n_pairs), at most
+ * cap_blocks workgroups per pair: out receives 4 ints per wave, 4 waves per workgroup (16 * grid host ints): pair, slice, workgroups per
+ * pair -- all -1 for a workgroup without work -- and the number of active pairs, as every wave derives them on the device. */
+int dgs_deal_probe(dgs_handle* h, const int32_t* active, int32_t n_pairs, int32_t cap_blocks, int32_t grid, int32_t* out);
 /* DGS_METHOD_PCL_NDT handles are served by dgs_ndt_derivatives (its evaluation with the Hessian; hess36 == NULL asks for the score +
  * gradient evaluation of a More-Thuente trial), dgs_ndt_hessian_double, dgs_ndt_get_trajectory and dgs_ndt_get_voxels as well.
  * Test hook of such a handle: the neighbourhood of `m` query points (x y z pad, taken as they are: no transform) in the current
