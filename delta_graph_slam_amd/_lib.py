@@ -113,7 +113,7 @@ class LineAlignParams(C.Structure):
                 # appended for align_local
                 ("l_avg_distance_weight", C.c_double), ("l_coverage_weight", C.c_double), ("l_transform_weight", C.c_double),
                 ("l_max_score_distance", C.c_double), ("l_max_score_translation", C.c_double), ("l_max_distance", C.c_double),
-                ("l_max_angle", C.c_double), ("refine_three_nearest", C.c_int32), ("reserved2", C.c_int32)]
+                ("l_max_angle", C.c_double), ("refine_three_nearest", C.c_int32), ("edges_on_device", C.c_int32)]   # the former reserved2
 
 
 class LineAlignment(C.Structure):
@@ -160,6 +160,7 @@ class LineAlignHypothesis(C.Structure):
 LA_STATUS = {0: "ALIGNED", 1: "NO_HYPOTHESES", 2: "ALL_GATED", 3: "NONE_BETTER", 4: "LINE_ALIGNED"}
 LA_GATE = {0: "PASS", 1: "DISTANCE", 2: "IDENTITY", 3: "ANGLE", 4: "LINE_DIRECTION", 5: "LINE_DISTANCE", 6: "RANK", 7: "OVERLAP"}
 BO_MAX_BUILDINGS = 1 << 14
+LA_MAX_ITEMS, LA_MAX_LINES_TARGET, LA_MAX_EDGE_PAIRS = 4096, 512, 1 << 24
 LE_STATUS = {0: "DONE", 1: "RANSAC_FAILED", 2: "STALL", 3: "MAX_ROUNDS", 4: "RNG_EXHAUSTED"}
 FD_STATUS = {0: "DETECTED", 1: "TOO_FEW_POINTS", 2: "TOO_FEW_INLIERS", 3: "NOT_VERTICAL", 4: "RNG_EXHAUSTED"}
 SAC_METHODS = ["SAC_RANSAC", "SAC_LMEDS", "SAC_MSAC", "SAC_RRANSAC", "SAC_RMSAC", "SAC_MLESAC", "SAC_PROSAC"]
@@ -198,6 +199,7 @@ SYMBOLS = [
     "dgs_line_align_local_batch", "dgs_line_align_local", "dgs_line_edges_angular", "dgs_line_align_local_get_hypotheses",
     "dgs_building_overlap_pairs", "dgs_line_align_overlapped_batch", "dgs_line_align_overlapped", "dgs_line_align_overlapped_get_hypotheses",
     "dgs_building_overlap_get_counts",
+    "dgs_line_edge_extraction_batch", "dgs_line_edge_extraction", "dgs_line_edges_get_counts",
     "dgs_floor_detection_params_init", "dgs_floor_detection", "dgs_floor_detection_get_filtered", "dgs_floor_detection_get_inliers",
     "dgs_floor_detection_get_trace", "dgs_floor_detection_get_clipped", "dgs_floor_detection_draws", "dgs_floor_detection_walk",
     "dgs_calc_fitness_score_batch_clouds", "dgs_cloud_build_indices", "dgs_fitness_batch_get_counts",
@@ -346,6 +348,10 @@ def load(path=None):
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dgs_line_align_overlapped.argtypes = [C.c_void_p, P(LineAlignParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_void_p, P(LineOverlapAlignment)]
+    lib.dgs_line_edge_extraction_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                   C.c_void_p, P(C.c_int64)]
+    lib.dgs_line_edge_extraction.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_line_edges_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     lib.dgs_line_align_overlapped_get_hypotheses.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
     lib.dgs_building_overlap_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     lib.dgs_floor_detection_params_init.argtypes = [P(FloorDetectionParams)]

@@ -266,6 +266,7 @@ __global__ __launch_bounds__(kBlock) void deal_probe_kernel(const int* __restric
 }  // namespace dgs
 
 static thread_local std::string g_create_error;  // dgs_last_error(NULL): why the last dgs_create on this thread failed
+void dgs::set_handleless_error(const char* why) { g_create_error = why; }
 
 extern "C" {
 
@@ -497,6 +498,7 @@ void dgs_destroy(dgs_handle* h) {
   line_extraction_release(h);
   line_align_release(h);
   line_align_local_release(h);
+  line_edges_release(h);
   building_overlap_release(h);
   floor_detection_release(h);
   fitness_batch_release(h);

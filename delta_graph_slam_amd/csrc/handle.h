@@ -189,6 +189,7 @@ struct LaScratch {
 struct LalHyp;    // line_align_local.hip
 struct LalScratch {
   DevBuf<unsigned char> in;            // one upload: item table, workgroup tables, source lines, target tables, both edge lists
+  DevBuf<unsigned char> tab;           // edges_on_device: the item and workgroup tables (`in` then holds source lines, target lines, target tables)
   DevBuf<LalHyp> hyps;                 // per hypothesis of both phases, at the item's offsets
   DevBuf<double> fit;                  // 5 doubles per hypothesis
   DevBuf<double> keys;                 // line pairs: nn_key(real_distance) per (snapshot line, target line)
@@ -196,6 +197,20 @@ struct LalScratch {
   DevBuf<unsigned char> out;           // one download: a record per item, then the aligned lines
   std::vector<int64_t> off1, off2;     // of the last call: first hypothesis per item and phase (n_items + 1 entries; phase 1 after all of phase 0)
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+// edge_extraction, batched (line_edges.hip): scratch of its own; the two aligners read `edges` when their edges_on_device is set.
+struct LeSeg;     // line_edges.hip
+struct LeScratch {
+  DevBuf<double> lines;                // the public entry points' upload: 6 doubles per line (the aligners pass their own)
+  DevBuf<LeSeg> segs;                  // n_seg + 1 records
+  DevBuf<unsigned char> cnt;           // edges (0..4) per pair p = the segment's first pair + i * n + j; 0 for j <= i
+  DevBuf<int> blk;                     // edges per workgroup of pairs, scanned in place; [workgroups] = all edges
+  DevBuf<int> eoff;                    // first edge per segment, n_seg + 1 entries
+  DevBuf<double> edges;                // 9 doubles per edge, all segments back to back
+  void* stage = nullptr;               // pinned: the segment table's upload, behind it the edge offsets' download
+  size_t stage_bytes = 0;
+  std::vector<int> eoff_host;          // of the last extraction
+  int64_t counts4[4] = {0, 0, 0, 0};   // launches, host waits, pairs i < j, edges
 };
 // are_buildings_overlapped over all pairs and align_overlapped_buildings, batched (building_overlap.hip): scratch of its own.
 struct BoHyp;     // building_overlap.hip
@@ -463,6 +478,7 @@ struct dgs_handle {
   dgs::LnScratch ln;
   dgs::LaScratch la;
   dgs::LalScratch lal;
+  dgs::LeScratch le;
   dgs::BoScratch bo;
 
   // ---- floor detection (floor_detection.hip): own buffers; everything above is left untouched
@@ -562,6 +578,12 @@ void line_extraction_release(dgs_handle* h);
 void line_align_release(dgs_handle* h);
 // line_align_local.hip
 void line_align_local_release(dgs_handle* h);
+// line_edges.hip: edge_extraction of n_seg segments of the packed lines at d_lines (device, 6 doubles per line) -> h->le.edges and
+// h->le.eoff_host (n_seg + 1).  `emit` false stops after the counts.  The caller has checked the limits (line_edges_bad_segments).
+int line_edges_run(dgs_handle* h, const double* d_lines, const std::vector<LeSeg>& segs, bool emit);
+void line_edges_release(dgs_handle* h);
+// dgs_api.hip: the message dgs_last_error(NULL) returns, for an entry point that refuses its arguments before it looks at the handle
+void set_handleless_error(const char* why);
 // building_overlap.hip
 void building_overlap_release(dgs_handle* h);
 // floor_detection.hip

@@ -3,8 +3,9 @@
 //   * host and device: the scalar functions.  The kernels, the host-side merge / edge extraction, the refinement pass and la::align_local
 //     all call them, so a value computed on either side has the same bits but for the trigonometric functions.
 //   * device only: the one wave scorer (fitness_wave<LOCAL>, calc_fitness_score on a wavefront) and the wave arg-max both aligners use.
-//   * host only: merge / edge extraction, calc_fitness<LOCAL>, la::align_local, and what both drivers need around the C ABI (feature to
-//     Line, the checks, the packing of the upload).
+//   * host only: merge / edge extraction (the pair function itself, la::edge_pair, is in the first section: line_edges.hip runs it on the
+//     device), calc_fitness<LOCAL>, la::align_local, and what both drivers need around the C ABI (feature to Line, the checks, the packing
+//     of the upload, the segment table of a device edge extraction).
 // Everything is double and must not be contracted (the including file is built with -ffp-contract=off); the float steps are
 // LineFeature::lenght() and the angle gate's transform3Dto2D chain.  Eigen details recalled from memory are tagged [UPSTREAM-RECALL];
 // DESIGN.md 6f lists them.
@@ -62,6 +63,7 @@ LA_HD Edge load_edge(const double* p) { Edge e; e.e = load3(p); e.a = load3(p + 
 LA_HD void store_fit(double* o, const Fitness f, const double score) {
   o[0] = f.real_avg_distance; o[1] = f.avg_distance; o[2] = f.coverage; o[3] = f.coverage_percentage; o[4] = score;
 }
+LA_HD V3 pick(const bool c, const V3 a, const V3 b) { return v3(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z); }   // c ? a : b by component: stays in registers on the device
 LA_HD V3 sub(const V3 a, const V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
 LA_HD V3 add(const V3 a, const V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 LA_HD V3 scale(const V3 a, const double s) { return v3(a.x * s, a.y * s, a.z * s); }
@@ -370,6 +372,67 @@ LA_HD bool takes_over(const double sb, const int hb, const double sa, const int 
   return sb > sa || (sb == sa && (unsigned)hb < (unsigned)ha);
 }
 
+// get_edges (:501-682) of one pair of lines, for the host and for the device (line_edges.hip): up to four edges in the order of the four
+// cases; returns how many.  EMIT = false only counts (`out` is not touched); EMIT = true writes at most `cap` edges (the device's emit
+// pass hands in the count it stored for the pair, so a write can never pass the pair's own room).  only_angular_edges drops an edge whose lines end further
+// than max_dist_angular_edge from the corner (cases 1, 2 and 3; case 4 has no such check upstream).  Only + - * /, sqrt, comparisons and
+// fmin / fmax of ordered values: without contraction both sides produce the same bits.
+template <bool EMIT>
+LA_HD int edge_pair(const Line l1, const Line l2, const bool only_angular_edges, const double max_dist_angular_edge, Edge* out, const int cap) {
+  const double cosine = dot(normalized(sub(l1.a, l1.b)), normalized(sub(l2.a, l2.b)));
+  if (fabs(cosine) > 0.5) return 0;
+  const double min_side = 1.0;
+  const V3 ep = lines_intersection(l1.a, l1.b, l2.a, l2.b);
+  const V3 s1a = sub(l1.a, ep), s1b = sub(l1.b, ep), s2a = sub(l2.a, ep), s2b = sub(l2.b, ep);
+  const double n1a = norm(s1a), n1b = norm(s1b), n2a = norm(s2a), n2b = norm(s2b);
+  const bool same1 = n1a < 0.01 || n1b < 0.01 || norm(sub(normalized(s1a), normalized(s1b))) < 1.;
+  const bool same2 = n2a < 0.01 || n2b < 0.01 || norm(sub(normalized(s2a), normalized(s2b))) < 1.;
+  int n = 0;
+  Edge e;
+  e.e = ep;
+#define LA_EMIT_EDGE()        \
+  do {                        \
+    if (EMIT && n < cap) {    \
+      out[n].e = e.e;         \
+      out[n].a = e.a;         \
+      out[n].b = e.b;         \
+    }                         \
+    n++;                      \
+  } while (0)
+  if (same1 && same2) {
+    if (fmax(n1a, n1b) < min_side || fmax(n2a, n2b) < min_side) return 0;
+    if (only_angular_edges && (fmin(n1a, n1b) > max_dist_angular_edge || fmin(n2a, n2b) > max_dist_angular_edge)) return 0;
+    e.a = pick(n1a > n1b, l1.a, l1.b);
+    e.b = pick(n2a > n2b, l2.a, l2.b);
+    LA_EMIT_EDGE();
+  } else if (same1 && !same2) {
+    if (fmax(n1a, n1b) < min_side) return 0;
+    if (only_angular_edges && fmin(n1a, n1b) > max_dist_angular_edge) return 0;
+    e.a = pick(n1a > n1b, l1.a, l1.b);
+    if (n2a > min_side) { e.b = l2.a; LA_EMIT_EDGE(); }
+    if (n2b > min_side) { e.b = l2.b; LA_EMIT_EDGE(); }
+  } else if (!same1 && same2) {
+    if (fmax(n2a, n2b) < min_side) return 0;
+    if (only_angular_edges && fmin(n2a, n2b) > max_dist_angular_edge) return 0;
+    e.a = pick(n1a > n1b, l2.a, l2.b);   // upstream compares side1A with side1B here and takes the point from line2
+    if (n1a > min_side) { e.b = l1.a; LA_EMIT_EDGE(); }
+    if (n1b > min_side) { e.b = l1.b; LA_EMIT_EDGE(); }
+  } else {
+    if (n1a > min_side) {
+      e.a = l1.a;
+      if (n2a > min_side) { e.b = l2.a; LA_EMIT_EDGE(); }
+      if (n2b > min_side) { e.b = l2.b; LA_EMIT_EDGE(); }
+    }
+    if (n1b > min_side) {
+      e.a = l1.b;
+      if (n2a > min_side) { e.b = l2.a; LA_EMIT_EDGE(); }
+      if (n2b > min_side) { e.b = l2.b; LA_EMIT_EDGE(); }
+    }
+  }
+#undef LA_EMIT_EDGE
+  return n;
+}
+
 #if defined(__HIPCC__)
 // ---- device only ---------------------------------------------------------------------------------------------------------------
 // calc_fitness_score (:905-955) of `Ls` lines, moved by `t` or as they are, against the `Lt` rows of the target table in LDS, by one
@@ -482,50 +545,12 @@ inline void merge_lines(std::vector<Line>& lines, std::vector<int>& origin) {
     }
   }
 }
-// get_edges (:501-682).  only_angular_edges drops an edge whose lines end further than max_dist_angular_edge from the corner (cases 1, 2
-// and 3; case 4 has no such check upstream).  The defaults are align_global's call.
+// get_edges on the host: edge_pair's edges appended to `out`.  The defaults are align_global's call.
 inline void get_edges(const Line l1, const Line l2, std::vector<Edge>& out, const bool only_angular_edges = false,
                       const double max_dist_angular_edge = 7.0) {
-  const double cosine = dot(normalized(sub(l1.a, l1.b)), normalized(sub(l2.a, l2.b)));
-  if (fabs(cosine) > 0.5) return;
-  const double min_side = 1.0;
-  const V3 ep = lines_intersection(l1.a, l1.b, l2.a, l2.b);
-  const V3 s1a = sub(l1.a, ep), s1b = sub(l1.b, ep), s2a = sub(l2.a, ep), s2b = sub(l2.b, ep);
-  const double n1a = norm(s1a), n1b = norm(s1b), n2a = norm(s2a), n2b = norm(s2b);
-  const bool same1 = n1a < 0.01 || n1b < 0.01 || norm(sub(normalized(s1a), normalized(s1b))) < 1.;
-  const bool same2 = n2a < 0.01 || n2b < 0.01 || norm(sub(normalized(s2a), normalized(s2b))) < 1.;
-  Edge e;
-  e.e = ep;
-  if (same1 && same2) {
-    if (fmax(n1a, n1b) < min_side || fmax(n2a, n2b) < min_side) return;
-    if (only_angular_edges && (fmin(n1a, n1b) > max_dist_angular_edge || fmin(n2a, n2b) > max_dist_angular_edge)) return;
-    e.a = n1a > n1b ? l1.a : l1.b;
-    e.b = n2a > n2b ? l2.a : l2.b;
-    out.push_back(e);
-  } else if (same1 && !same2) {
-    if (fmax(n1a, n1b) < min_side) return;
-    if (only_angular_edges && fmin(n1a, n1b) > max_dist_angular_edge) return;
-    e.a = n1a > n1b ? l1.a : l1.b;
-    if (n2a > min_side) { e.b = l2.a; out.push_back(e); }
-    if (n2b > min_side) { e.b = l2.b; out.push_back(e); }
-  } else if (!same1 && same2) {
-    if (fmax(n2a, n2b) < min_side) return;
-    if (only_angular_edges && fmin(n2a, n2b) > max_dist_angular_edge) return;
-    e.a = n1a > n1b ? l2.a : l2.b;   // upstream compares side1A with side1B here and takes the point from line2
-    if (n1a > min_side) { e.b = l1.a; out.push_back(e); }
-    if (n1b > min_side) { e.b = l1.b; out.push_back(e); }
-  } else {
-    if (n1a > min_side) {
-      e.a = l1.a;
-      if (n2a > min_side) { e.b = l2.a; out.push_back(e); }
-      if (n2b > min_side) { e.b = l2.b; out.push_back(e); }
-    }
-    if (n1b > min_side) {
-      e.a = l1.b;
-      if (n2a > min_side) { e.b = l2.a; out.push_back(e); }
-      if (n2b > min_side) { e.b = l2.b; out.push_back(e); }
-    }
-  }
+  Edge e[4];
+  const int n = edge_pair<true>(l1, l2, only_angular_edges, max_dist_angular_edge, e, 4);
+  out.insert(out.end(), e, e + n);
 }
 // edge_extraction (:459-471); fewer than two lines give no edges (upstream's unsigned `size() - 1` reads out of bounds there)
 inline void edge_extraction(const std::vector<Line>& lines, std::vector<Edge>& out, const bool only_angular_edges = false,
@@ -591,6 +616,9 @@ inline bool all_finite(const dgs_line_feature* l, const int64_t n) {
       if (!std::isfinite(l[i].point_a[a]) || !std::isfinite(l[i].point_b[a])) return false;
   return true;
 }
+// edges_on_device of a struct that has the member (it took the place of `reserved2`, which dgs_line_align_params_init zeroes); the
+// short struct is the host path
+inline bool edges_on_device(const dgs_line_align_params* p) { return p->struct_size >= sizeof(dgs_line_align_params) && p->edges_on_device != 0; }
 // what is wrong with the struct itself (nullptr: nothing): it ends before align_local's members were appended, or it is the whole of it
 inline const char* params_guard(const dgs_line_align_params* p) {
   if (!p) return "line align: params is NULL";
@@ -616,6 +644,24 @@ inline void matrix(const Tf t, double* T) {
   const double m[16] = {t.r00, t.r01, 0.0, t.tx, t.r10, t.r11, 0.0, t.ty, 0.0, 0.0, 1.0, t.tz, 0.0, 0.0, 0.0, 1.0};
   std::memcpy(T, m, sizeof(m));
 }
+
+// ---- the batched device edge extraction (line_edges.hip): what its callers hand it
+}  // namespace la
+// One segment: `n` lines from line `line_off` of the packed lines on.  Its pairs are indexed p = pair_off + i * n + j over the full square
+// (j <= i yields nothing), so a segment takes n * n pair slots.
+struct LeSeg {
+  long long pair_off;
+  int line_off, n, only_angular, pad;
+  double max_dist;
+};
+namespace la {
+inline void add_segment(std::vector<LeSeg>* segs, const int line_off, const int n, const bool only_angular, const double max_dist) {
+  LeSeg g;
+  g.pair_off = segs->empty() ? 0 : segs->back().pair_off + (long long)segs->back().n * segs->back().n;
+  g.line_off = line_off; g.n = n; g.only_angular = only_angular ? 1 : 0; g.pad = 0; g.max_dist = max_dist;
+  segs->push_back(g);
+}
+inline long long pair_slots(const std::vector<LeSeg>& segs) { return segs.empty() ? 0 : segs.back().pair_off + (long long)segs.back().n * segs.back().n; }
 
 // ---- align_local (:205-297) on the host: the restatement the device path of line_align_local.hip is tested against, and the CPU side of
 // scripts/bench_line_align_local.py.  The semantics are DESIGN.md 6g's.

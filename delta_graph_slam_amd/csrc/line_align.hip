@@ -1,11 +1,16 @@
 // LineBasedScanmatcher::align_global (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp:109-203) on the device: every
 // (source edge, target edge) pair is a hypothesis h = es * Et + et; align_edges, the three gates, calc_fitness_score of the
-// transformed source lines against the merged target lines and the strict arg-max run there.  merge_lines, edge_extraction and the
-// refinement pass are sequential and small and run on the host from the same functions (line_align.h).  The scorer
+// transformed source lines against the merged target lines and the strict arg-max run there.  merge_lines and the refinement pass are
+// sequential and run on the host from the same functions (line_align.h); edge_extraction runs there too, or with
+// params->edges_on_device on the device (line_edges.hip: the same pair function, the same bits), after the merge and the one upload of
+// lines.  The device extraction costs one more host wait: the two edge counts are read back to size the hypothesis space and to check
+// DGS_LA_MAX_HYPOTHESES, while the edges themselves stay in HBM for la_hypothesis_kernel.  The counters show it (counts4[1] == 2, and
+// the extraction's launches in counts4[0]).  The scorer
 // (la::fitness_wave), the wave arg-max and the host's checks and packing are line_align.h's, shared with line_align_local.hip.
 //
 // MI355X design
-//   * One upload: source lines, the target table (A, B, (B - A).normalized() per merged line) and both edge lists.
+//   * One upload: source lines, the target table (A, B, (B - A).normalized() per merged line) and both edge lists (edges_on_device: the
+//     merged target lines in place of the edge lists).
 //   * la_hypothesis_kernel: one lane per h; transform, gate code, survivor flag.  Survivors are compacted in h order with the
 //     prefilter's stable compaction (pf_count_kernel, pf_scan_kernel) and la_scatter_kernel.
 //   * la_score_kernel: one wavefront per survivor (item 0 is the identity, the baseline) runs la::fitness_wave<false> against the
@@ -178,16 +183,51 @@ struct LaOut {
   double score;
 };
 
-// phase 1 on the device: -> the winner (or the baseline) with one host wait
-int la_search(dgs_handle* h, const LaArgs& a, const std::vector<la::Line>& src, const std::vector<la::Line>& trg, const std::vector<la::V3>& dir,
-              const std::vector<la::Edge>& es, const std::vector<la::Edge>& et, LaResult* out) {
+// phase 1 on the device: -> the winner (or the baseline) with one host wait.  dev_edges: es / et are empty, the edges are extracted on
+// the device from the uploaded lines (a second wait, for the two counts) and a.Es / a.Et are set here.
+int la_search(dgs_handle* h, LaArgs& a, const std::vector<la::Line>& src, const std::vector<la::Line>& trg, const std::vector<la::V3>& dir,
+              const std::vector<la::Edge>& es, const std::vector<la::Edge>& et, const bool dev_edges, LaResult* out) {
   LaScratch& s = h->la;
+  const size_t n_src = (size_t)a.Ls * 6, n_tbl = (size_t)a.Lt * la::kTableDoubles;
+  // the upload: source lines, [dev_edges: target lines,] target table, [host edges: source edges, target edges]
+  const size_t n_trg6 = dev_edges ? (size_t)a.Lt * 6 : 0, n_up_es = es.size() * 9, n_up_et = et.size() * 9;
+  const size_t n_in = n_src + n_trg6 + n_tbl + n_up_es + n_up_et;
+  DGS_HIP_TRY(h, s.in.reserve(std::max<size_t>(n_in, 1)));
+  if (ensure_pinned(h, 4096 + n_in * sizeof(double)) != DGS_OK) return DGS_ERR_HIP;
+  static_assert(sizeof(LaResult) <= 4096, "the read-back block must fit in front of the upload");
+  {
+    double* up = reinterpret_cast<double*>(static_cast<char*>(h->pinned) + 4096);
+    double* o = la::pack_lines(src, up);
+    if (dev_edges) o = la::pack_lines(trg, o);
+    o = la::pack_target_table(trg, dir, o);
+    o = la::pack_edges(es, o);
+    la::pack_edges(et, o);
+    if (n_in) DGS_HIP_TRY(h, hipMemcpyAsync(s.in.ptr, up, n_in * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  const double* d_src = s.in.ptr;
+  const double* d_tbl = d_src + n_src + n_trg6;
+  const double* d_es = d_tbl + n_tbl;
+  const double* d_et = d_es + n_up_es;
+  if (dev_edges) {
+    std::vector<LeSeg> segs;
+    la::add_segment(&segs, 0, a.Ls, false, 7.0);        // get_edges' defaults: align_global's call
+    la::add_segment(&segs, a.Ls, a.Lt, false, 7.0);
+    const int rc = line_edges_run(h, d_src, segs, true);   // Ls <= 256, Lt <= 512: far below DGS_LA_MAX_EDGE_PAIRS
+    s.counts4[0] += h->le.counts4[0];
+    s.counts4[1] += h->le.counts4[1];
+    if (rc != DGS_OK) return rc;
+    a.Es = h->le.eoff_host[1];
+    a.Et = h->le.eoff_host[2] - h->le.eoff_host[1];
+    if ((int64_t)a.Es * a.Et > DGS_LA_MAX_HYPOTHESES) {
+      h->err = "line align: more than DGS_LA_MAX_HYPOTHESES edge-pair hypotheses";
+      return DGS_ERR_INVALID_ARGUMENT;
+    }
+    d_es = h->le.edges.ptr;                             // not read when there is no hypothesis
+    d_et = d_es + 9 * (size_t)a.Es;
+  }
   const int64_t H = (int64_t)a.Es * a.Et;
-  const size_t n_src = (size_t)a.Ls * 6, n_tbl = (size_t)a.Lt * la::kTableDoubles, n_es = (size_t)a.Es * 9, n_et = (size_t)a.Et * 9;
-  const size_t n_in = n_src + n_tbl + n_es + n_et;
   const size_t hh = (size_t)std::max<int64_t>(H, 1);
   const unsigned nb = (unsigned)((hh + kBlock - 1) / kBlock);
-  DGS_HIP_TRY(h, s.in.reserve(std::max<size_t>(n_in, 1)));
   DGS_HIP_TRY(h, s.hyps.reserve(hh));
   DGS_HIP_TRY(h, s.keep.reserve(hh));
   DGS_HIP_TRY(h, s.gate.reserve(hh));
@@ -197,18 +237,6 @@ int la_search(dgs_handle* h, const LaArgs& a, const std::vector<la::Line>& src, 
   DGS_HIP_TRY(h, s.slot.reserve(hh));
   DGS_HIP_TRY(h, s.fit.reserve(hh * 5));
   DGS_HIP_TRY(h, s.result.reserve(1));
-  if (ensure_pinned(h, 4096 + n_in * sizeof(double)) != DGS_OK) return DGS_ERR_HIP;
-  static_assert(sizeof(LaResult) <= 4096, "the read-back block must fit in front of the upload");
-  double* up = reinterpret_cast<double*>(static_cast<char*>(h->pinned) + 4096);
-  double* o = la::pack_lines(src, up);
-  o = la::pack_target_table(trg, dir, o);
-  o = la::pack_edges(es, o);
-  la::pack_edges(et, o);
-  if (n_in) DGS_HIP_TRY(h, hipMemcpyAsync(s.in.ptr, up, n_in * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  const double* d_src = s.in.ptr;
-  const double* d_tbl = d_src + n_src;
-  const double* d_es = d_tbl + n_tbl;
-  const double* d_et = d_es + n_es;
   if (H > 0) {
     hipLaunchKernelGGL(la_hypothesis_kernel, dim3(nb), dim3(kBlock), 0, h->stream, d_es, d_et, a, s.hyps.ptr, s.keep.ptr, s.gate.ptr, s.fit.ptr);
     hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, s.keep.ptr, (int)H, s.blk.ptr);
@@ -302,6 +330,7 @@ int dgs_line_align_params_init(dgs_line_align_params* p) {
   p->l_max_distance = 2.5;
   p->l_max_angle = M_PI / 9.0;
   p->refine_three_nearest = 0;
+  p->edges_on_device = 0;
   return DGS_OK;
 }
 
@@ -328,10 +357,12 @@ int dgs_line_edges(const dgs_line_feature* lines, int64_t n, dgs_edge_feature* e
 int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, const dgs_line_feature* src_lines, int64_t n_src,
                           const dgs_line_feature* trg_lines, int64_t n_trg, int32_t constrain_angle, double max_range,
                           dgs_line_feature* aligned_lines, dgs_line_alignment* alignment) {
-  if (const char* why = la_bad_params(params)) {   // before anything touches a device
+  if (const char* why = la_bad_params(params)) {   // before anything touches a device; without a handle the message is dgs_last_error(NULL)'s
     if (h) h->err = why;
+    else set_handleless_error(why);
     return DGS_ERR_INVALID_ARGUMENT;
   }
+  if (!h) set_handleless_error("line align: the handle is NULL");
   if (!h || !alignment || n_src < 0 || n_trg < 0 || (n_src > 0 && !src_lines) || (n_trg > 0 && !trg_lines)) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   std::memset(alignment, 0, sizeof(*alignment));
@@ -353,13 +384,15 @@ int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, co
     return DGS_ERR_INVALID_ARGUMENT;
   }
   const std::vector<la::V3> dir = la::directions(trg);
+  const bool dev_edges = la::edges_on_device(params);
   std::vector<la::Edge> es, et;
-  la::edge_extraction(src, es);
-  la::edge_extraction(trg, et);
-  const int64_t H = (int64_t)es.size() * (int64_t)et.size();
-  if (H > DGS_LA_MAX_HYPOTHESES) {
-    h->err = "line align: more than DGS_LA_MAX_HYPOTHESES edge-pair hypotheses";
-    return DGS_ERR_INVALID_ARGUMENT;
+  if (!dev_edges) {
+    la::edge_extraction(src, es);
+    la::edge_extraction(trg, et);
+    if ((int64_t)es.size() * (int64_t)et.size() > DGS_LA_MAX_HYPOTHESES) {
+      h->err = "line align: more than DGS_LA_MAX_HYPOTHESES edge-pair hypotheses";
+      return DGS_ERR_INVALID_ARGUMENT;
+    }
   }
   LaArgs a{};
   a.Ls = (int)src.size(); a.Lt = (int)trg.size(); a.Es = (int)es.size(); a.Et = (int)et.size();
@@ -377,11 +410,12 @@ int dgs_line_align_global(dgs_handle* h, const dgs_line_align_params* params, co
   for (int k = 0; k < 4; k++) h->la.counts4[k] = 0;
   DGS_HIP_TRY(h, hipSetDevice(h->device));
   LaResult res{};
-  const int rc = la_search(h, a, src, trg, dir, es, et, &res);
+  const int rc = la_search(h, a, src, trg, dir, es, et, dev_edges, &res);
   if (rc != DGS_OK) {
     (void)hipStreamSynchronize(h->stream);
     return rc;
   }
+  const int64_t H = (int64_t)a.Es * a.Et;
   LaOut r;
   r.t = res.hyp.t;
   r.fit.real_avg_distance = res.fit[0]; r.fit.avg_distance = res.fit[1]; r.fit.coverage = res.fit[2]; r.fit.coverage_percentage = res.fit[3];

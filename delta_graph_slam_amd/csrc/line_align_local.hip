@@ -1,7 +1,10 @@
 // LineBasedScanmatcher::align_local (upstream src/hdl_graph_slam/line_based_scanmatcher.cpp:205-297) on the device, for a batch of
 // independent items (a keyframe's near buildings): per item the baseline, the edge-pair hypotheses h = es * Et + et with their two
 // gates, the strict arg-max, then the line-pair hypotheses k = i * Lt + r over the snapshot of the first phase's result and the second
-// arg-max.  Edge extraction is sequential and small and runs on the host from the same functions (line_align.h).  The scorer
+// arg-max.  Edge extraction runs on the host from the same functions (line_align.h), or with params->edges_on_device on the device
+// (line_edges.hip): one batched extraction over all items' sources and targets, 2 * n_items segments, no per-item host loop.  That
+// costs one more host wait (the edge offsets come back to build the item and workgroup tables, counts8[1] == 2), a second upload (those
+// tables) and the extraction's launches, whose number does not depend on n_items either.  The scorer
 // (la::fitness_wave), the wave arg-max and the host's checks and packing are line_align.h's, shared with line_align.hip.
 //
 // MI355X design
@@ -285,7 +288,7 @@ const char* lal_bad_params(const dgs_line_align_params* p) {
 
 void line_align_local_release(dgs_handle* h) {
   LalScratch& s = h->lal;
-  s.in.release(); s.hyps.release(); s.fit.release(); s.keys.release(); s.base.release(); s.out.release();
+  s.in.release(); s.tab.release(); s.hyps.release(); s.fit.release(); s.keys.release(); s.base.release(); s.out.release();
   s.off1.clear();
   s.off2.clear();
 }
@@ -314,10 +317,12 @@ int dgs_line_edges_angular(const dgs_line_feature* lines, int64_t n, int32_t onl
 int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* params, int64_t n_items, const dgs_line_feature* src_lines,
                                const int64_t* src_offsets, const dgs_line_feature* trg_lines, const int64_t* trg_offsets, double max_range,
                                dgs_line_feature* aligned_lines, dgs_line_local_alignment* alignments) {
-  if (const char* why = lal_bad_params(params)) {   // before anything touches a device
+  if (const char* why = lal_bad_params(params)) {   // before anything touches a device; without a handle the message is dgs_last_error(NULL)'s
     if (h) h->err = why;
+    else set_handleless_error(why);
     return DGS_ERR_INVALID_ARGUMENT;
   }
+  if (!h) set_handleless_error("line align: the handle is NULL");
   if (!h || n_items < 0 || (n_items > 0 && (!alignments || !src_offsets || !trg_offsets))) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   LalScratch& s = h->lal;
@@ -344,12 +349,42 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
   }
   const dgs_line_align_params prm = lal_params(params);
 
-  // ---- the host's share: edges, offsets, the workgroup tables
+  // ---- the host's share: edges (or, with edges_on_device, their offsets read back from the device), offsets, the workgroup tables
   const std::vector<la::Line> src = la::lines_of(src_lines, n_src), trg = la::lines_of(trg_lines, n_trg);
   const auto part = [](const std::vector<la::Line>& v, int first, int n) { return std::vector<la::Line>(v.begin() + first, v.begin() + first + n); };
+  const bool dev_edges = la::edges_on_device(params);
+  const size_t n_srcd = (size_t)n_src * 6, n_tbl = (size_t)n_trg * la::kTableDoubles, n_trg6 = dev_edges ? (size_t)n_trg * 6 : 0;
+  const size_t b_lines = (n_srcd + n_trg6 + n_tbl) * sizeof(double);
   std::vector<LalItem> items((size_t)n_items);
   std::vector<la::Edge> es, et;
   std::vector<int2> wg1, wg2;
+  const int* eoff = nullptr;
+  if (dev_edges) {
+    // segments 0 .. n_items - 1: the sources; n_items .. 2 n_items - 1: the targets, whose packed lines follow the sources'
+    std::vector<LeSeg> segs;
+    for (int64_t b = 0; b < n_items; b++) la::add_segment(&segs, (int)src_offsets[b], (int)(src_offsets[b + 1] - src_offsets[b]), true, 0.01);
+    for (int64_t b = 0; b < n_items; b++) la::add_segment(&segs, (int)(n_src + trg_offsets[b]), (int)(trg_offsets[b + 1] - trg_offsets[b]), true, 7.0);
+    if (la::pair_slots(segs) > DGS_LA_MAX_EDGE_PAIRS) {
+      h->err = "line align: edges_on_device: more than DGS_LA_MAX_EDGE_PAIRS pairs (the squares of the items' line counts, summed)";
+      return DGS_ERR_INVALID_ARGUMENT;
+    }
+    // the first upload: source lines, target lines, target tables
+    DGS_HIP_TRY(h, hipSetDevice(h->device));
+    DGS_HIP_TRY(h, s.in.reserve(std::max<size_t>(b_lines, 8)));
+    if (ensure_pinned(h, b_lines) != DGS_OK) return DGS_ERR_HIP;
+    double* o = la::pack_lines(src, static_cast<double*>(h->pinned));
+    o = la::pack_lines(trg, o);
+    la::pack_target_table(trg, la::directions(trg), o);
+    if (b_lines) DGS_HIP_TRY(h, hipMemcpyAsync(s.in.ptr, h->pinned, b_lines, hipMemcpyHostToDevice, h->stream));
+    const int rc = line_edges_run(h, reinterpret_cast<const double*>(s.in.ptr), segs, true);
+    s.counts8[0] += h->le.counts4[0];
+    s.counts8[1] += h->le.counts4[1];
+    if (rc != DGS_OK) {
+      (void)hipStreamSynchronize(h->stream);
+      return rc;
+    }
+    eoff = h->le.eoff_host.data();                                     // 2 * n_items + 1 entries; this call's copies have completed
+  }
   long long H1 = 0, H2 = 0;
   for (int64_t b = 0; b < n_items; b++) {
     LalItem& it = items[(size_t)b];
@@ -357,12 +392,19 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
     it.Lt = (int)(trg_offsets[b + 1] - trg_offsets[b]);
     it.src_off = (int)src_offsets[b];
     it.trg_off = (int)trg_offsets[b];
-    it.es_off = (int)es.size();
-    it.et_off = (int)et.size();
-    la::edge_extraction(part(src, it.src_off, it.Ls), es, true, 0.01);
-    la::edge_extraction(part(trg, it.trg_off, it.Lt), et, true);
-    it.Es = (int)es.size() - it.es_off;
-    it.Et = (int)et.size() - it.et_off;
+    if (dev_edges) {
+      it.es_off = eoff[b];
+      it.et_off = eoff[n_items + b] - eoff[n_items];
+      it.Es = eoff[b + 1] - eoff[b];
+      it.Et = eoff[n_items + b + 1] - eoff[n_items + b];
+    } else {
+      it.es_off = (int)es.size();
+      it.et_off = (int)et.size();
+      la::edge_extraction(part(src, it.src_off, it.Ls), es, true, 0.01);
+      la::edge_extraction(part(trg, it.trg_off, it.Lt), et, true);
+      it.Es = (int)es.size() - it.es_off;
+      it.Et = (int)et.size() - it.et_off;
+    }
     it.h1_off = H1;
     it.h2_off = H2;                                                    // made absolute below
     H1 += (long long)it.Es * it.Et;
@@ -386,14 +428,15 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
   s.off1.push_back(H1);
   s.off2.push_back(H1 + H2);
 
-  // ---- one upload
+  // ---- one upload (edges_on_device: the second, of the tables alone; the lines are on the device already)
   const size_t b_items = lal_align8(items.size() * sizeof(LalItem)), b_wg1 = lal_align8(wg1.size() * sizeof(int2)), b_wg2 = lal_align8(wg2.size() * sizeof(int2));
-  const size_t n_srcd = (size_t)n_src * 6, n_tbl = (size_t)n_trg * la::kTableDoubles, n_es = es.size() * 9, n_et = et.size() * 9;
-  const size_t b_in = b_items + b_wg1 + b_wg2 + (n_srcd + n_tbl + n_es + n_et) * sizeof(double);
+  const size_t n_es = es.size() * 9, n_et = et.size() * 9;
+  const size_t b_tab = b_items + b_wg1 + b_wg2;
+  const size_t b_in = dev_edges ? b_tab : b_tab + (n_srcd + n_tbl + n_es + n_et) * sizeof(double);
   const size_t b_rec = (size_t)n_items * sizeof(LalRecord), b_out = b_rec + n_srcd * sizeof(double);
   const size_t HH = (size_t)std::max<long long>(H1 + H2, 1);
   DGS_HIP_TRY(h, hipSetDevice(h->device));
-  DGS_HIP_TRY(h, s.in.reserve(b_in));
+  DGS_HIP_TRY(h, (dev_edges ? s.tab : s.in).reserve(b_in));
   DGS_HIP_TRY(h, s.hyps.reserve(HH));
   DGS_HIP_TRY(h, s.fit.reserve(HH * 5));
   DGS_HIP_TRY(h, s.keys.reserve((size_t)std::max<long long>(H2, 1)));
@@ -405,19 +448,23 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
   std::memcpy(up, items.data(), items.size() * sizeof(LalItem));
   if (!wg1.empty()) std::memcpy(up + b_items, wg1.data(), wg1.size() * sizeof(int2));
   if (!wg2.empty()) std::memcpy(up + b_items + b_wg1, wg2.data(), wg2.size() * sizeof(int2));
-  double* o = reinterpret_cast<double*>(up + b_items + b_wg1 + b_wg2);
-  o = la::pack_lines(src, o);
-  o = la::pack_target_table(trg, la::directions(trg), o);
-  o = la::pack_edges(es, o);
-  la::pack_edges(et, o);
-  DGS_HIP_TRY(h, hipMemcpyAsync(s.in.ptr, up, b_in, hipMemcpyHostToDevice, h->stream));
-  const LalItem* d_items = reinterpret_cast<const LalItem*>(s.in.ptr);
-  const int2* d_wg1 = reinterpret_cast<const int2*>(s.in.ptr + b_items);
-  const int2* d_wg2 = reinterpret_cast<const int2*>(s.in.ptr + b_items + b_wg1);
-  const double* d_src = reinterpret_cast<const double*>(s.in.ptr + b_items + b_wg1 + b_wg2);
-  const double* d_tbl = d_src + n_srcd;
-  const double* d_es = d_tbl + n_tbl;
-  const double* d_et = d_es + n_es;
+  if (!dev_edges) {
+    double* o = reinterpret_cast<double*>(up + b_tab);
+    o = la::pack_lines(src, o);
+    o = la::pack_target_table(trg, la::directions(trg), o);
+    o = la::pack_edges(es, o);
+    la::pack_edges(et, o);
+  }
+  unsigned char* d_tab = dev_edges ? s.tab.ptr : s.in.ptr;
+  DGS_HIP_TRY(h, hipMemcpyAsync(d_tab, up, b_in, hipMemcpyHostToDevice, h->stream));
+  const LalItem* d_items = reinterpret_cast<const LalItem*>(d_tab);
+  const int2* d_wg1 = reinterpret_cast<const int2*>(d_tab + b_items);
+  const int2* d_wg2 = reinterpret_cast<const int2*>(d_tab + b_items + b_wg1);
+  const double* d_src = reinterpret_cast<const double*>(dev_edges ? s.in.ptr : s.in.ptr + b_tab);
+  const double* d_tbl = d_src + n_srcd + n_trg6;
+  // edges_on_device: the extraction's buffer, the sources' edges in front of the targets' (not read when the batch has no edge pair)
+  const double* d_es = dev_edges ? h->le.edges.ptr : d_tbl + n_tbl;
+  const double* d_et = dev_edges ? d_es + 9 * (size_t)eoff[n_items] : d_es + n_es;
   LalRecord* d_rec = reinterpret_cast<LalRecord*>(s.out.ptr);
   double* d_aligned = reinterpret_cast<double*>(s.out.ptr + b_rec);
 
@@ -459,7 +506,7 @@ int dgs_line_align_local_batch(dgs_handle* h, const dgs_line_align_params* param
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(down, s.out.ptr, b_out, hipMemcpyDeviceToHost, h->stream);
   const hipError_t e2 = hipStreamSynchronize(h->stream);               // the one host wait, also on the error path
-  s.counts8[1] = 1;
+  s.counts8[1] += 1;
   DGS_HIP_TRY(h, e);
   DGS_HIP_TRY(h, e2);
 

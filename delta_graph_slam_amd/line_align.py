@@ -8,6 +8,11 @@ flat cloud (float32 [N,4], numpy or device tensor), which goes through a `LineEx
 yields no lines falls through as upstream does (the identity with the empty score).  `merge_lines` and `edge_extraction` are the
 host-only pieces and need no GPU.
 
+`LineScanMatcher.edge_extraction(lines, only_angular_edges, max_dist_angular_edge)` and `edge_extraction_batch(items)` are the same
+edge extraction on the device (dgs_line_edge_extraction_batch): the same `EdgeFeature` objects, bit for bit.  The
+parameter `edges_on_device=1` makes align_global and align_local / align_local_batch take their edges from those kernels instead of the
+host (the default, 0); the results are identical, the call pays one more host wait.
+
 `align_local(lines_source, lines_target, max_range)` and `align_local_batch(items, max_range)` are LineBasedScanmatcher::align_local
 (:205-297; dgs_line_align_local_batch): a batch of independent (source lines, target lines) items -- a keyframe's near
 buildings -- goes to the device in one call.  The matcher's `l_*` members and the nodelet's `delta_local_*` names set weight_local,
@@ -45,7 +50,8 @@ _NAMES = {   # member name -> the nodelet's parameter name
     "l_transform_weight": "delta_local_transform_weight", "l_max_score_distance": "delta_local_max_score_distance",
     "l_max_score_translation": "delta_local_max_score_translation",
 }
-_EXTRA = ("max_distance", "max_angle", "l_max_distance", "l_max_angle", "angle_gate_float_chain", "nn_tie_highest_index", "refine_three_nearest")
+_EXTRA = ("max_distance", "max_angle", "l_max_distance", "l_max_angle", "angle_gate_float_chain", "nn_tie_highest_index", "refine_three_nearest",
+          "edges_on_device")
 
 
 @dataclass
@@ -271,7 +277,43 @@ class LineScanMatcher:
                         not_overlapped=al[b].n_not_overlapped, edges_source=al[b].n_edges_source, edges_target=al[b].n_edges_target))
             for b, it in enumerate(items)]
 
+    def edge_extraction(self, lines: List[LineFeature], only_angular_edges: bool = False, max_dist_angular_edge: float = 7.0) -> List[EdgeFeature]:
+        """edge_extraction (:459-471) of one list of lines on the device: a batch of one segment.  The defaults are align_global's call."""
+        return self.edge_extraction_batch([(lines, only_angular_edges, max_dist_angular_edge)])[0]
+
+    def edge_extraction_batch(self, items) -> List[List[EdgeFeature]]:
+        """`items`: a sequence of (lines, only_angular_edges, max_dist_angular_edge), e.g. (source lines, True, 0.01) and (target lines, True,
+        7.0) for align_local.  One list of `EdgeFeature` per item, each what the module-level `edge_extraction` returns for it."""
+        arr, off = self._edge_batch_raw(items)
+        return [[EdgeFeature(np.array(e[0]), np.array(e[1]), np.array(e[2])) for e in arr[off[b]:off[b + 1]]] for b in range(len(off) - 1)]
+
+    def _edge_batch_raw(self, items):
+        """-> (float64 [n_edges, 3, 3]: edgePoint, pointA, pointB; int64 [n_items + 1] edge offsets)."""
+        items = [(list(l), bool(o), float(d)) for l, o, d in items]
+        n = len(items)
+        lo = (C.c_int64 * (n + 1))()
+        for b, (l, _, _) in enumerate(items):
+            lo[b + 1] = lo[b] + len(l)
+        lines = _to_c([f for l, _, _ in items for f in l])
+        only = (C.c_int32 * max(n, 1))(*[1 if o else 0 for _, o, _ in items])
+        dist = (C.c_double * max(n, 1))(*[d for _, _, d in items])
+        eo = (C.c_int64 * (n + 1))()
+        ne = C.c_int64(0)
+        args = (self._h, C.cast(lines, C.c_void_p), C.cast(lo, C.c_void_p), n, C.cast(only, C.c_void_p), C.cast(dist, C.c_void_p))
+        rc = self._lib.dgs_line_edge_extraction_batch(*args, None, 0, C.cast(eo, C.c_void_p), C.byref(ne))   # the count
+        if rc and ne.value == 0:
+            self.registration._check(rc)
+        out = np.zeros((max(ne.value, 1), 3, 3), np.float64)
+        self.registration._check(self._lib.dgs_line_edge_extraction_batch(*args, out.ctypes.data, ne.value, C.cast(eo, C.c_void_p), C.byref(ne)))
+        return out[:ne.value], np.array(eo[:], np.int64)
+
     # -- test hooks ----------------------------------------------------------------------------------------------------------
+    def edge_counts(self):
+        """-> dict(launches, host_waits, pairs, edges) of the last device edge extraction on this handle."""
+        c = (C.c_int64 * 4)()
+        self.registration._check(self._lib.dgs_line_edges_get_counts(self._h, C.cast(c, C.c_void_p)))
+        return dict(launches=c[0], host_waits=c[1], pairs=c[2], edges=c[3])
+
     def hypotheses(self, first: int = 0, count: Optional[int] = None):
         """Per-hypothesis records of the last call as arrays: gate, slot, rotation [n,4], translation [n,3], fitness [n,4], score."""
         if count is None:

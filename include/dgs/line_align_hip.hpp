@@ -12,6 +12,10 @@
 // upstream's setter of that name writes the global member, so l_avg_distance_weight keeps the constructor's 0.6.
 // alignOverlappedBatch() is LineBasedScanmatcher::align_overlapped_buildings (:29-107; dgs_line_align_overlapped_batch) from
 // the building-frame lines on, one call for all overlapped pairs of a round; the caller keeps the frame transforms.
+// edgeExtraction() / edgeExtractionBatch() are LineBasedScanmatcher::edge_extraction (:459-471) on the device
+// (dgs_line_edge_extraction_batch): EdgeFeatureT is any struct with upstream's edgePoint, pointA and pointB (indexable by
+// 0..2 and assignable from double).  params().edges_on_device = 1 makes alignGlobal() and alignLocalBatch() take their edges from the same
+// kernels instead of the host's loop over line pairs: identical results, one more host wait per call; the default is 0.
 #pragma once
 
 #include <cstddef>
@@ -179,6 +183,58 @@ class HipLineAligner {
     return true;
   }
   dgs_handle* handle() { return ensure_handle() ? h_ : nullptr; }   // for the test hooks
+
+  struct EdgeItem {   // one edge_extraction(lines, only_angular_edges, max_dist_angular_edge) call
+    const std::vector<LinePtr>* lines;
+    bool only_angular_edges;
+    double max_dist_angular_edge;
+  };
+  // One device call for all items; (*edges)[b] is what edge_extraction returns for item b.  false: *edges is untouched.
+  template <typename EdgeFeatureT>
+  bool edgeExtractionBatch(const std::vector<EdgeItem>& items, std::vector<std::vector<std::shared_ptr<EdgeFeatureT>>>* edges) {
+    if (!edges || !ensure_handle()) return false;
+    src_.clear();
+    so_.assign(1, 0);
+    std::vector<int32_t> only;
+    std::vector<double> dist;
+    for (const EdgeItem& it : items) {
+      append(*it.lines, &src_);
+      so_.push_back((int64_t)src_.size());
+      only.push_back(it.only_angular_edges ? 1 : 0);
+      dist.push_back(it.max_dist_angular_edge);
+    }
+    if (items.empty()) {   // the arrays of an empty batch may not be NULL-checked by every caller: give them one element
+      only.push_back(0);
+      dist.push_back(0.0);
+    }
+    to_.assign(items.size() + 1, 0);
+    int64_t n = 0;
+    const int rc = dgs_line_edge_extraction_batch(h_, src_.data(), so_.data(), (int64_t)items.size(), only.data(), dist.data(), nullptr, 0, to_.data(), &n);
+    if (rc != DGS_OK && n == 0) return false;   // with edges to fetch the count-only call reports the missing room
+    std::vector<dgs_edge_feature> e((size_t)(n ? n : 1));
+    if (n && dgs_line_edge_extraction_batch(h_, src_.data(), so_.data(), (int64_t)items.size(), only.data(), dist.data(), e.data(), n, to_.data(), &n) != DGS_OK)
+      return false;
+    edges->assign(items.size(), std::vector<std::shared_ptr<EdgeFeatureT>>());
+    for (size_t b = 0; b < items.size(); b++)
+      for (int64_t k = to_[b]; k < to_[b + 1]; k++) {
+        auto f = std::make_shared<EdgeFeatureT>();
+        for (int a = 0; a < 3; a++) {
+          f->edgePoint[a] = e[(size_t)k].edge_point[a];
+          f->pointA[a] = e[(size_t)k].point_a[a];
+          f->pointB[a] = e[(size_t)k].point_b[a];
+        }
+        (*edges)[b].push_back(f);
+      }
+    return true;
+  }
+  template <typename EdgeFeatureT>
+  bool edgeExtraction(const std::vector<LinePtr>& lines, bool only_angular_edges, double max_dist_angular_edge,
+                      std::vector<std::shared_ptr<EdgeFeatureT>>* edges) {
+    std::vector<std::vector<std::shared_ptr<EdgeFeatureT>>> r;
+    if (!edges || !edgeExtractionBatch<EdgeFeatureT>({EdgeItem{&lines, only_angular_edges, max_dist_angular_edge}}, &r)) return false;
+    *edges = r[0];
+    return true;
+  }
 
   bool alignLocal(const std::vector<LinePtr>& linesSource, const std::vector<LinePtr>& linesTarget, double max_range, BestFitAlignmentT* result) {
     std::vector<BestFitAlignmentT> r;

@@ -666,7 +666,8 @@ int dgs_line_extraction_get_rounds(dgs_handle* h, dgs_line_extraction_round* rou
                                    int32_t* inlier_idx, int32_t* cluster_idx, int64_t* counts4);
 
 /* ---- LineBasedScanmatcher::align_global on the device (src/hdl_graph_slam/line_based_scanmatcher.cpp:109-203) ------------------
- * The target lines are merged, the edges of both sides are extracted (host, order-dependent), every (source edge, target edge)
+ * The target lines are merged (host, order-dependent), the edges of both sides are extracted (on the host, or with
+ * params->edges_on_device on the device: one more host wait, which reads the two edge counts back), every (source edge, target edge)
  * hypothesis h = es * Et + et is aligned, gated and scored on the device, the strict arg-max over h is taken there, and the
  * refinement pass over the aligned lines runs on the host.  Semantics, the Eigen details recalled from upstream and the limits:
  * DESIGN.md 6f.  The aligner works in buffers of its own: registration, prefilter, map and line-extraction state are untouched.
@@ -717,7 +718,10 @@ typedef struct dgs_line_align_params {
   double l_max_angle;
   int32_t refine_three_nearest;    /* 0: the line-pair phase visits every neighbour rank (what upstream's `i<3 || i<size` does for three or
                                       more); 1: ranks 0..2 only, what its comment intends */
-  int32_t reserved2;
+  int32_t edges_on_device;         /* the member that was `reserved2` (dgs_line_align_params_init has always zeroed it, and the struct keeps
+                                      its size): 0: align_global and align_local extract their edges on the host, as before; 1: on the
+                                      device (dgs_line_edge_extraction_batch's kernels): the same edges bit for bit, one
+                                      more host wait per call.  A caller whose struct_size ends at `reserved` gets 0. */
 } dgs_line_align_params;
 int dgs_line_align_params_init(dgs_line_align_params* params);
 /* upstream's BestFitAlignment without the two line vectors, and what the search saw */
@@ -773,8 +777,10 @@ int dgs_line_align_get_hypotheses(dgs_handle* h, int64_t first, int64_t count, d
  * (calc_fitness_score with is_local, weight_local), the edge pairs h = es * Et + et of edge_extraction(src, true, 0.01) x
  * edge_extraction(trg, true) gated by distance then angle, the strict arg-max, then the line pairs k = i * Lt + r over the snapshot
  * of the first phase's result (i: line of the snapshot, r: rank of a target line by (real_distance, index)), and the second
- * arg-max.  Edges are extracted on the host; everything else runs on the device with one upload, one download, one host wait and a
- * number of kernel launches that does not depend on n_items.  Nothing is merged: the target lines are used as given.  Semantics,
+ * arg-max.  Edges are extracted on the host, or with params->edges_on_device on the device in one batched extraction over all items'
+ * sources and targets (one more host wait, which reads the edge offsets back; the summed squares of the line counts are then limited by
+ * DGS_LA_MAX_EDGE_PAIRS); everything else runs on the device with one upload, one download, one host wait and a number of kernel
+ * launches that does not depend on n_items.  Nothing is merged: the target lines are used as given.  Semantics,
  * the deliberate differences from upstream and the limits: DESIGN.md 6g.  Additions only: DGS_ABI_VERSION is unchanged. */
 #define DGS_LA_MAX_ITEMS 4096             /* items per batch call; the summed hypotheses of both phases: DGS_LA_MAX_HYPOTHESES */
 typedef struct dgs_line_local_alignment {
@@ -828,6 +834,30 @@ typedef struct dgs_line_align_local_hypothesis {
 int dgs_line_align_local_get_hypotheses(dgs_handle* h, int64_t item, int32_t phase, int64_t first, int64_t count,
                                         dgs_line_align_local_hypothesis* records, int64_t* counts8);
 
+/* ---- edge_extraction on the device, batched (src/hdl_graph_slam/line_based_scanmatcher.cpp:459-471, get_edges :501-682) -----------
+ * The lines of n_items segments back to back with n_items + 1 ascending offsets; per segment only_angular[b] and max_dist[b]
+ * (align_local: 1 and 0.01 for the source, 1 and 7.0 for the target; align_global: 0 and 7.0).  The edges of all segments come back to
+ * back, a segment's in edge_extraction's order (pairs i < j ascending in (i, j), a pair's edges in case order), bit for bit what
+ * dgs_line_edges_angular gives for that segment; edge_offsets (nullable): n_items + 1 offsets into them.  A segment of fewer than two
+ * lines gives no edges.  *n_edges is always the full count, DGS_ERR_INVALID_ARGUMENT when it exceeds `capacity` (capacity 0 with a NULL
+ * array asks for the count and the offsets alone; nothing is emitted then).  More than DGS_LA_MAX_ITEMS segments, more than
+ * DGS_LA_MAX_LINES_TARGET lines in a segment, more than DGS_LA_MAX_EDGE_PAIRS pairs (the squares of the segments' line counts summed: the
+ * kernels index a segment's pairs as i * n + j), offsets that do not ascend from 0, a NaN max_dist or a coordinate that is not finite is
+ * DGS_ERR_INVALID_ARGUMENT with a message, checked before anything is launched and before the handle is looked at (with a NULL handle
+ * the message is dgs_last_error(NULL)'s): nothing is truncated.  Three launches for the counts, one host wait, one launch for the edges,
+ * a second wait for their download.  Own buffers on the handle.  Semantics and kernels: DESIGN.md 6l.  Additions only: DGS_ABI_VERSION
+ * is unchanged. */
+#define DGS_LA_MAX_EDGE_PAIRS (1 << 24)
+int dgs_line_edge_extraction_batch(dgs_handle* h, const dgs_line_feature* lines, const int64_t* offsets, int64_t n_items,
+                                   const int32_t* only_angular, const double* max_dist, dgs_edge_feature* edges, int64_t capacity,
+                                   int64_t* edge_offsets, int64_t* n_edges);
+/* a batch of one segment */
+int dgs_line_edge_extraction(dgs_handle* h, const dgs_line_feature* lines, int64_t n, int32_t only_angular_edges, double max_dist_angular_edge,
+                             dgs_edge_feature* edges, int64_t capacity, int64_t* n_edges);
+/* Test hook.  counts4: kernel launches, host waits, pairs i < j and edges of the last device edge extraction on this handle (a
+ * dgs_line_edge_extraction* call, or an aligner call with edges_on_device). */
+int dgs_line_edges_get_counts(dgs_handle* h, int64_t* counts4);
+
 /* ---- are_buildings_overlapped and LineBasedScanmatcher::align_overlapped_buildings on the device ---------------------------------
  * (include/hdl_graph_slam/check_overlapping.hpp; src/hdl_graph_slam/line_based_scanmatcher.cpp:29-107; the loop of
  * apps/delta_graph_slam_nodelet.cpp:846-900).  Semantics, the deliberate non-differences from the geometric predicate, the limits
@@ -860,8 +890,8 @@ typedef struct dgs_line_overlap_alignment {
 /* align_overlapped_buildings from the building-frame lines on, for n_items independent (source, target) pairs: the caller keeps the
  * frame transforms around it.  Layout of lines, offsets and aligned_lines as in dgs_line_align_local_batch;
  * centers_source / centers_target: double[n_items][3] (upstream: zero, and B's centre in A's frame).  Of `params` only
- * angle_gate_float_chain is read; the angle is DGS_LA_OVERLAP_MAX_ANGLE.  Edges come from edge_extraction with its defaults on the
- * host; one upload, one download, one host wait, three launches.  DGS_LA_MAX_ITEMS, DGS_LA_MAX_LINES_SOURCE / _TARGET per item and
+ * angle_gate_float_chain is read (edges_on_device is not: the items are pairs of single buildings with a handful of lines); the angle
+ * is DGS_LA_OVERLAP_MAX_ANGLE.  Edges come from edge_extraction with its defaults on the host; one upload, one download, one host wait, three launches.  DGS_LA_MAX_ITEMS, DGS_LA_MAX_LINES_SOURCE / _TARGET per item and
  * DGS_LA_MAX_HYPOTHESES summed over the batch as for align_local; 72 bytes of device memory per hypothesis. */
 int dgs_line_align_overlapped_batch(dgs_handle* h, const dgs_line_align_params* params, int64_t n_items, const dgs_line_feature* src_lines,
                                     const int64_t* src_offsets, const dgs_line_feature* trg_lines, const int64_t* trg_offsets,
