@@ -121,6 +121,11 @@ struct NdtPair {
   //             BESIDE the first kernel of round r + 1 (its own stream): an exact match, so a value written while that launch runs
   //             (r + 2) is read as "not this round" before and after the store alike.
   // The item-compacted kernel (one launch per round) uses serve[0] alone.
+  //   serve[3]: the KIND of the evaluation that round r serves, in bits 2 * (r & 1) and above (two 2-bit fields, one per round parity): what
+  //             the cost-ordered dealing of the item-compacted kernel ranks the pairs by (deal_workgroup_by_cost).  need_hessian cannot serve:
+  //             the pair's closing overwrites it for the NEXT evaluation while workgroups of other pairs in the same launch are still being
+  //             dealt.  The closing of round r stores the field of round r + 1 (strict_note_kind) and leaves the field of round r as it is,
+  //             so every workgroup of round r reads the same kinds whenever it starts.
   int serve[4];
   // Speculated Newton steps of the upstream order (ndt_strict.h "deferred exact solve"): the closing publishes the next evaluation from the
   // 2-us Gauss-Jordan direction (spec_pending = 1); one wave of the pair's first workgroup in the NEXT launch runs the exact Jacobi-SVD step
@@ -211,6 +216,9 @@ struct NdtInit {  // host -> device per pair, per align
 // their own, or the choice in a helper function, the compiler laid the fixed-slices kernels' row flush out in front of their tile loop, and
 // tests/test_isa_handoff.py reads the hand-off sequence in program text order.)  Test hook: dgs_deal_probe.
 constexpr int kDealKept = 4;
+// The upstream order's evaluation kinds (NdtPair::need_hessian) from the heaviest workgroup to the lightest, as MEASURED per workgroup on the
+// bench step (profiles/r08): what the item-compacted NDT kernel ranks the pairs of a launch by (deal_workgroup_by_cost).
+constexpr int kNdtCostKind0 = 2, kNdtCostKind1 = 1, kNdtCostKind2 = 0;   // medians 64.7 / 54.7 / 30.9 us per workgroup
 #ifdef __HIPCC__
 template <class Pred>
 __device__ inline bool deal_workgroup(const int n_pairs, const int cap_blocks, Pred pred, int& pair, int& slice, int& blocks_per_pair, int* n_active_out = nullptr,
@@ -244,6 +252,71 @@ __device__ inline bool deal_workgroup(const int n_pairs, const int cap_blocks, P
     } else {
       const int pi = c0 + lane_id;
       m = __ballot((pi < n_pairs) && pred(pi));
+    }
+    const int cnt = __popcll(m);
+    if (rank < seen + cnt) {
+      for (int k = rank - seen; k > 0; k--) m &= m - 1ull;  // drop the (rank - seen) lowest set bits
+      found = c0 + __ffsll((long long)m) - 1;
+    }
+    seen += cnt;
+  }
+  pair = __builtin_amdgcn_readfirstlane(found);
+  return true;
+}
+
+// deal_workgroup with the pairs ranked by (cost class of the evaluation they wait for, then pair index) instead of by pair index alone: the
+// workgroups of the heaviest class come first in blockIdx order, which is the order the dispatcher hands workgroups out in, so a launch of
+// more workgroups than the chip holds ends on its light workgroups and not on heavy ones that started last.  n_active, blocks_per_pair and the
+// set of (pair, slice) served are deal_workgroup's: only which workgroup serves which changes (tests/test_deal_by_cost_gpu.py).
+// kind_of(pair index) gives the pair's evaluation kind 0..2, or a negative value for a pair that is not served; H0, H1, H2 are the kinds from
+// the heaviest to the lightest.  It must give every workgroup of the launch the same answer WHENEVER it is asked: it may read only words
+// that nothing stores to while the launch runs.  Same counting pass: one strided load + three ballots per 64 pairs, the first kDealKept
+// chunks' ballots kept in scalar registers for the choosing pass.  With all kinds equal the mapping is deal_workgroup's.  Test hook:
+// dgs_deal_probe_cost.
+template <int H0, int H1, int H2, class Kind>
+__device__ inline bool deal_workgroup_by_cost(const int n_pairs, const int cap_blocks, Kind kind_of, int& pair, int& slice, int& blocks_per_pair, int* n_active_out = nullptr,
+                                              const int block_id_in = -1, const int grid_in = -1) {
+  static_assert(H0 != H1 && H1 != H2 && H0 != H2 && H0 + H1 + H2 == 3 && H0 >= 0 && H1 >= 0 && H2 >= 0, "a permutation of the kinds 0, 1, 2");
+  const int block_id = block_id_in >= 0 ? block_id_in : (int)blockIdx.x, grid = grid_in >= 0 ? grid_in : (int)gridDim.x;
+  const int lane_id = threadIdx.x & 63;
+  int n0 = 0, n1 = 0, n2 = 0;   // pairs per class, heaviest first
+  unsigned long long kept0[kDealKept], kept1[kDealKept], kept2[kDealKept];
+#pragma unroll
+  for (int j = 0; j < kDealKept; j++) kept0[j] = kept1[j] = kept2[j] = 0ull;
+  for (int c0 = 0; c0 < n_pairs; c0 += 64) {
+    const int pi = c0 + lane_id;
+    const int k = (pi < n_pairs) ? kind_of(pi) : -1;
+    const unsigned long long m0 = __ballot(k == H0), m1 = __ballot(k == H1), m2 = __ballot(k == H2);
+#pragma unroll
+    for (int j = 0; j < kDealKept; j++) {
+      kept0[j] = (c0 == j * 64) ? m0 : kept0[j];
+      kept1[j] = (c0 == j * 64) ? m1 : kept1[j];
+      kept2[j] = (c0 == j * 64) ? m2 : kept2[j];
+    }
+    n0 += __popcll(m0);
+    n1 += __popcll(m1);
+    n2 += __popcll(m2);
+  }
+  const int n_active = n0 + n1 + n2;
+  if (n_active_out) *n_active_out = n_active;
+  if (n_active == 0) return false;
+  blocks_per_pair = max(1, min(grid / n_active, cap_blocks));
+  int rank = block_id / blocks_per_pair;
+  slice = block_id % blocks_per_pair;
+  if (rank >= n_active) return false;
+  // the class the rank falls into, and the rank inside it (wave-uniform: the counts come from ballots)
+  const int cls = rank < n0 ? 0 : (rank < n0 + n1 ? 1 : 2);
+  rank -= cls == 0 ? 0 : (cls == 1 ? n0 : n0 + n1);
+  const int want = cls == 0 ? H0 : (cls == 1 ? H1 : H2);
+  int found = -1, seen = 0;
+  for (int c0 = 0; c0 < n_pairs && found < 0; c0 += 64) {
+    unsigned long long m = 0ull;
+    if (c0 < kDealKept * 64) {
+#pragma unroll
+      for (int j = 0; j < kDealKept; j++) m = (c0 == j * 64) ? (cls == 0 ? kept0[j] : (cls == 1 ? kept1[j] : kept2[j])) : m;
+    } else {
+      const int pi = c0 + lane_id;
+      m = __ballot(((pi < n_pairs) ? kind_of(pi) : -1) == want);
     }
     const int cnt = __popcll(m);
     if (rank < seen + cnt) {

@@ -263,6 +263,14 @@ __global__ __launch_bounds__(kBlock) void deal_probe_kernel(const int* __restric
   const bool ok = deal_workgroup(n_pairs, cap_blocks, [&](int pi) { return active[pi] != 0; }, pair, slice, blocks_per_pair, &n_active);
   if ((threadIdx.x & 63) == 0) out[blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)] = ok ? make_int4(pair, slice, blocks_per_pair, n_active) : make_int4(-1, -1, -1, n_active);
 }
+// dgs_deal_probe_cost: the same for deal_workgroup_by_cost, with a kind per pair as data; H0 / H1 / H2 as the NDT kernel instantiates it
+__global__ __launch_bounds__(kBlock) void deal_probe_cost_kernel(const int* __restrict__ active, const int* __restrict__ kinds, const int n_pairs, const int cap_blocks,
+                                                                 int4* __restrict__ out) {
+  int pair = -1, slice = -1, blocks_per_pair = -1, n_active = -1;
+  const bool ok = deal_workgroup_by_cost<kNdtCostKind0, kNdtCostKind1, kNdtCostKind2>(
+      n_pairs, cap_blocks, [&](int pi) { return active[pi] != 0 ? kinds[pi] : -1; }, pair, slice, blocks_per_pair, &n_active);
+  if ((threadIdx.x & 63) == 0) out[blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)] = ok ? make_int4(pair, slice, blocks_per_pair, n_active) : make_int4(-1, -1, -1, n_active);
+}
 }  // namespace dgs
 
 static thread_local std::string g_create_error;  // dgs_last_error(NULL): why the last dgs_create on this thread failed
@@ -440,6 +448,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (const char* e = std::getenv("DGS_NDT_SOLVE_MIN_ACTIVE")) h->solve_min_active = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("DGS_NDT_SPECULATE")) h->ndt_speculate = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_FIXED_SLICES")) h->ndt_fixed_slices = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DGS_NDT_DEAL_BY_COST")) h->ndt_deal_by_cost = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_QUEUE")) h->ndt_queue_mode = std::atoi(e);
   if (const char* e = std::getenv("DGS_NDT_SCHEDULE")) h->ndt_schedule = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_QUEUE_MIN_PAIRS")) h->ndt_queue_min_pairs = std::max(1, std::atoi(e));
@@ -1050,6 +1059,35 @@ int dgs_deal_probe(dgs_handle* h, const int32_t* active, int32_t n_pairs, int32_
   d_out.release();
   if (e != hipSuccess) {
     h->err = std::string("dgs_deal_probe: ") + hipGetErrorString(e);
+    return DGS_ERR_HIP;
+  }
+  return DGS_OK;
+}
+
+int dgs_deal_probe_cost(dgs_handle* h, const int32_t* active, const int32_t* kinds, int32_t n_pairs, int32_t cap_blocks, int32_t grid, int32_t* out, int32_t* order3) {
+  if (!h || !active || !kinds || !out || n_pairs < 1 || cap_blocks < 1 || grid < n_pairs || grid > (1 << 20)) return DGS_ERR_INVALID_ARGUMENT;
+  for (int32_t i = 0; i < n_pairs; i++)
+    if (kinds[i] < 0 || kinds[i] > 2) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  if (order3) { order3[0] = kNdtCostKind0; order3[1] = kNdtCostKind1; order3[2] = kNdtCostKind2; }
+  DevBuf<int> d_in;   // the mask, then the kinds
+  DevBuf<int4> d_out;
+  const size_t n_out = (size_t)grid * (kBlock / kWave);
+  hipError_t e = d_in.reserve(2 * (size_t)n_pairs);
+  if (e == hipSuccess) e = d_out.reserve(n_out);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in.ptr, active, sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in.ptr + n_pairs, kinds, sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(deal_probe_cost_kernel, dim3(grid), dim3(kBlock), 0, h->stream, d_in.ptr, d_in.ptr + n_pairs, n_pairs, cap_blocks, d_out.ptr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.ptr, sizeof(int4) * n_out, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  d_in.release();
+  d_out.release();
+  if (e != hipSuccess) {
+    h->err = std::string("dgs_deal_probe_cost: ") + hipGetErrorString(e);
     return DGS_ERR_HIP;
   }
   return DGS_OK;

@@ -298,6 +298,12 @@ struct dgs_handle {
   bool ndt_speculate = true;          // DGS_NDT_SPECULATE=0: upstream order, item-compacted kernel: the Newton step's Jacobi SVD in the closing workgroup instead of speculated
   bool ndt_fixed_slices = false;     // DGS_NDT_FIXED_SLICES=1: upstream order, item-compacted kernel: a pair's slices are a function of its own size (ndt_strict.h strict_slices_of)
                                       // from the Gauss-Jordan direction and verified beside the next launch (NdtPair::spec_s)
+  bool ndt_deal_by_cost = true;       // DGS_NDT_DEAL_BY_COST=0: upstream order, item-compacted kernel: a launch's workgroups dealt to the pairs in index order (deal_workgroup)
+                                      // instead of heaviest evaluation kind first (deal_workgroup_by_cost); the same (pair, slice) set and the same bits either way
+#ifdef DGS_DEAL_STAMPS
+  unsigned long long* deal_stamps = nullptr;   // stamp build (make stamps): the workgroup stamps of the recorded launches
+  long long deal_stamp_seq = 0;                // item-kernel launches issued by this handle
+#endif
   int solve_min_active = 0;           // DGS_NDT_SOLVE_MIN_ACTIVE (default 0 = the Newton step stays in the closing workgroup): item-compacted upstream-order kernel:
                                       // with at least this many pairs in a launch the Newton steps go to ndt_strict_solve_kernel on the third stream.  Measured on the
                                       // bench step: 6.58-6.65 ms with 2 / 4 / 8 / 16 against 6.24 ms in line -- a pair sits out a round per iteration, and the closings'

@@ -116,7 +116,7 @@ __global__ void ndt_init_kernel(NdtPair* __restrict__ pairs, const NdtInit* __re
   st->serve[0] = 0;    // upstream order, fused: the first evaluation (kind 1) is served by round 0's first kernel
   st->serve[1] = -1;
   st->serve[2] = -1;
-  st->serve[3] = 0;
+  st->serve[3] = st->need_hessian & 3;   // round 0's kind (NdtPair::serve)
   st->spec_pending = 0;
   st->spec_result = 0;
   if (queue) {   // queue kernel: the record slot of round 0
@@ -377,13 +377,49 @@ static void launch_strict_rows(dgs_handle* h, const NdtLaunch& L, const dim3 gri
 // accumulators, 47 ms per step.)
 // (It carries ONE exponential -- glibc's, the default: with both compiled in it went from 4 to 27 spilled registers; ndt_exp_glibc = 0,
 //  the rounds 1-3 polynomial, is served by the lane-per-point kernels.)
+#ifdef DGS_DEAL_STAMPS
+// Stamp build (make stamps): the item-kernel launches number DGS_DEAL_STAMPS_AT .. + kStampLaunches - 1 of this handle are recorded; the
+// launch after them waits for the stream and writes the records to DGS_DEAL_STAMPS_FILE (raw, kStampLaunches x kStampGrid x kStampWords
+// 64-bit words).  Returns 1 + the slot of the launch about to be issued, or 0.
+static int deal_stamp_slot(dgs_handle* h, hipStream_t st) {
+  static const char* file = std::getenv("DGS_DEAL_STAMPS_FILE");
+  static const long long at = std::getenv("DGS_DEAL_STAMPS_AT") ? std::atoll(std::getenv("DGS_DEAL_STAMPS_AT")) : 2200;
+  if (!file) return 0;
+  const size_t words = (size_t)kStampLaunches * kStampGrid * kStampWords;
+  const long long seq = h->deal_stamp_seq++;
+  if (seq == at) {
+    if (hipMalloc(reinterpret_cast<void**>(&h->deal_stamps), words * 8) != hipSuccess) { h->deal_stamps = nullptr; return 0; }
+    (void)hipMemsetAsync(h->deal_stamps, 0, words * 8, st);
+    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_deal_stamps), &h->deal_stamps, sizeof(h->deal_stamps), 0, hipMemcpyHostToDevice, st);
+    (void)hipStreamSynchronize(st);
+  }
+  if (!h->deal_stamps || seq < at) return 0;
+  if (seq < at + kStampLaunches) return (int)(seq - at) + 1;
+  if (seq == at + kStampLaunches) {
+    (void)hipStreamSynchronize(st);
+    std::vector<unsigned long long> host(words);
+    if (hipMemcpy(host.data(), h->deal_stamps, words * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+      if (FILE* f = std::fopen(file, "wb")) {
+        std::fwrite(host.data(), 8, words, f);
+        std::fclose(f);
+      }
+    }
+  }
+  return 0;
+}
+#endif
+
 template <int SEARCH, bool FUSED, bool FIXED>
 static void launch_strict_items(dgs_handle* h, const NdtPlan& P, const NdtLaunch& L, const dim3 grid, const int leaf_pow2, const int launch, hipStream_t st) {
   const int spec = (FUSED && P.speculate) ? 1 : 0;
   const dim3 grid_s(grid.x + (spec ? L.n_pairs : 0));   // + one solver workgroup per pair, in front (ndt_strict.h)
+  int flags = (spec ? kStrictSpeculate : 0) | (h->ndt_deal_by_cost ? kStrictDealByCost : 0);
+#ifdef DGS_DEAL_STAMPS
+  flags |= deal_stamp_slot(h, st) << kStrictStampShift;
+#endif
   hipLaunchKernelGGL((ndt_strict3_kernel<SEARCH, FUSED, true, FIXED>), grid_s, dim3(kBlock), 0, st, h->src_ptrs.ptr, h->src_sizes.ptr, h->pairs.ptr, h->grid, h->vox_strict.ptr,
                      h->vox_dbg.ptr, h->consts.gauss_d1, h->consts.gauss_d2, leaf_pow2, h->partials.ptr, L.n_pairs, L.cap_blocks, h->pair_blocks.ptr, h->consts,
-                     FUSED ? h->done_flags : h->done_counter.ptr, launch, (FUSED && P.solve_beside) ? h->solve_min_active : 0, spec);
+                     FUSED ? h->done_flags : h->done_counter.ptr, launch, (FUSED && P.solve_beside) ? h->solve_min_active : 0, flags);
 }
 
 // The lane-per-point kernels, two launches per round.  HD: the instantiation for the pairs waiting for the double-precision

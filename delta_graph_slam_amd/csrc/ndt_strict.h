@@ -563,6 +563,14 @@ __device__ __forceinline__ void strict_rows_flush(const double (*cols)[kBlock / 
 // launch, rows read with the hand-off's coherent loads, the pair leaves through last_launch + its host flag).
 // HD / ONE_KERNEL: which kernel of the round runs this closing -- see NdtPair::serve.  ONE_KERNEL (ndt_strict3_kernel): every evaluation
 // kind is served by the round's only launch.
+// The kind of the evaluation just queued for round `round`, where the dealing of that round finds it: NdtPair::serve[3].  By the one lane that
+// wrote the evaluation's header (it reads its own store of need_hessian); the other round parity's field keeps its bits.
+__device__ __forceinline__ void strict_note_kind(NdtPair* st, const int round) {
+  const int sh = (round & 1) * 2;
+  st->serve[3] = (st->serve[3] & ~(3 << sh)) | ((st->need_hessian & 3) << sh);
+}
+__device__ __forceinline__ int strict_kind_of_round(const int serve3, const int round) { return (serve3 >> ((round & 1) * 2)) & 3; }
+
 #ifdef DGS_CLOSE_STAMPS   // diagnostic build (make dbg): 100 MHz wall-clock stamps of the closing phases while the pair is in its second iteration
 #define STRICT_STAMP(k) if (threadIdx.x == 0 && st->s.nr_iterations == 1) st->traj[kTrajCap - 1][k] = (double)wall_clock64();
 #else
@@ -663,8 +671,10 @@ __device__ __forceinline__ void ndt_close_strict(NdtPair* st, const double* rows
     } else if (launch >= 0) {
       // which kernel of which round serves the evaluation just queued (NdtPair::serve); `launch` is the round number
       if (s.phase == PH_SOLVE_PENDING) st->serve[1] = launch;   // ndt_strict_solve_kernel of this round (its own stream) takes the Newton step
-      else if (ONE_KERNEL) st->serve[0] = launch + 1;
-      else if (st->need_hessian == 2) st->serve[1] = HD ? launch + hd_lag : launch;   // the double computeHessian kernel of this round follows this launch
+      else if (ONE_KERNEL) {
+        st->serve[0] = launch + 1;
+        strict_note_kind(st, launch + 1);
+      } else if (st->need_hessian == 2) st->serve[1] = HD ? launch + hd_lag : launch;   // the double computeHessian kernel of this round follows this launch
       else if (HD) st->serve[2] = launch + hd_lag;   // see NdtPair::serve
       else st->serve[0] = launch + 1;
     }
@@ -915,6 +925,39 @@ __device__ __forceinline__ void strict_items_hd(const double* __restrict__ td, c
   }
 }
 
+// ---- ndt_strict3_kernel's `flags` argument
+constexpr int kStrictSpeculate = 1;    // NdtPlan::speculate
+constexpr int kStrictDealByCost = 2;   // dgs_handle::ndt_deal_by_cost (DGS_NDT_DEAL_BY_COST)
+constexpr int kStrictStampShift = 8;   // stamp build: 1 + the launch's slot in the stamp buffer, 0 = not recorded
+#ifndef DGS_STRICT_DEAL_BY_COST   // `make ab AB=-DDGS_STRICT_DEAL_BY_COST=0`: the kernel without the cost-ordered dealing
+#define DGS_STRICT_DEAL_BY_COST 1
+#endif
+
+// `make stamps` (-DDGS_DEAL_STAMPS): every workgroup of a recorded launch leaves its start, the end of its derivative work and the end of
+// its closing (100 MHz wall clock) with its blockIdx, pair, slice, kind and the launch's n_active in a 64-byte record: plain vector stores by
+// thread 0.  The host names the launches to record and writes the buffer to a file (ndt_align.hip, DGS_DEAL_STAMPS_FILE).
+#ifdef DGS_DEAL_STAMPS
+constexpr int kStampLaunches = 256, kStampGrid = 2048, kStampWords = 8;
+static __device__ unsigned long long* g_deal_stamps;
+#define STRICT_DEAL_STAMP_BEGIN                                                                                                        \
+  const unsigned long long stamp_t0 = wall_clock64();                                                                                  \
+  unsigned long long* const stamp_rec = ((flags >> kStrictStampShift) > 0 && threadIdx.x == 0 && blockIdx.x < kStampGrid && g_deal_stamps) \
+      ? g_deal_stamps + ((size_t)((flags >> kStrictStampShift) - 1) * kStampGrid + blockIdx.x) * kStampWords : nullptr;
+#define STRICT_DEAL_STAMP_WORK(pair, slice, kind, n_active)                                                                            \
+  if (stamp_rec) {                                                                                                                     \
+    stamp_rec[0] = stamp_t0;                                                                                                           \
+    stamp_rec[1] = wall_clock64();                                                                                                     \
+    stamp_rec[3] = (unsigned long long)blockIdx.x | ((unsigned long long)(unsigned)(pair) << 32);                                      \
+    stamp_rec[4] = (unsigned long long)(unsigned)((slice) + 1) | ((unsigned long long)(unsigned)(kind) << 32);                         \
+    stamp_rec[5] = (unsigned long long)(unsigned)(n_active) | ((unsigned long long)gridDim.x << 32);                                   \
+  }
+#define STRICT_DEAL_STAMP_CLOSED if (stamp_rec) stamp_rec[2] = wall_clock64();
+#else
+#define STRICT_DEAL_STAMP_BEGIN
+#define STRICT_DEAL_STAMP_WORK(pair, slice, kind, n_active)
+#define STRICT_DEAL_STAMP_CLOSED
+#endif
+
 template <int SEARCH, bool WITH_HD, bool RING>
 struct StrictTile {
   static constexpr int NB = Offsets<SEARCH>::N;
@@ -954,8 +997,12 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
                                                                const VoxelGrid g, const VoxelStrictRec* __restrict__ vs, const double* __restrict__ vtab,
                                                                const double gauss_d1, const double gauss_d2, const int leaf_pow2, double* __restrict__ partials,
                                                                const int n_pairs, const int cap_blocks, int* __restrict__ pair_blocks, const NdtConsts consts,
-                                                               int* __restrict__ done_flags, const int launch, const int solve_min_active, const int speculate) {
+                                                               int* __restrict__ done_flags, const int launch, const int solve_min_active, const int flags) {
   using TL = StrictTile<SEARCH, WITH_HD, !FIXED>;
+  // flags: kStrictSpeculate, kStrictDealByCost (and, in the stamp build, the launch's slot in the stamp buffer): one word, because one more
+  // kernel argument cost this kernel's sibling registers
+  const int speculate = flags & kStrictSpeculate;
+  STRICT_DEAL_STAMP_BEGIN
   constexpr int NB = TL::NB;
   int pair, slice, blocks_per_pair;
   int n_active = 0;
@@ -982,7 +1029,31 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
     for (int c0 = 0; c0 < n_pairs; c0 += 64) n_active += __popcll(__ballot(c0 + lane_id < n_pairs && in_round(c0 + lane_id)));
     blocks_per_pair = max(1, min(((int)gridDim.x - n_solvers) / n_active, cap_blocks));   // as deal_workgroup derives it
   } else {
-    if (!deal_workgroup(n_pairs, cap_blocks, in_round, pair, slice, blocks_per_pair, &n_active, (int)blockIdx.x - n_solvers, (int)gridDim.x - n_solvers)) return;
+    // DGS_NDT_DEAL_BY_COST (default on): the pairs of the heaviest evaluation kind first -- same n_active, blocks_per_pair and (pair, slice) set
+    bool dealt;
+    if (DGS_STRICT_DEAL_BY_COST != 0 && (flags & kStrictDealByCost)) {
+      // the pair's kind in this round from a word that no closing of this round changes (NdtPair::serve[3]), requested with the serve words
+      auto kind_in_round = [&](int pi) -> int {
+        bool a;
+        int k;
+        if (FUSED) {
+          const int s0 = pairs[pi].serve[0], s2 = pairs[pi].serve[2], s3 = pairs[pi].serve[3];
+          a = (launch <= s0) | (launch == s2);
+          k = strict_kind_of_round(s3, launch);
+        } else {
+          const int active = pairs[pi].active, nh = pairs[pi].need_hessian;
+          a = (active != 0) & (WITH_HD || nh != 2);
+          k = nh;
+        }
+        if (!WITH_HD) k = k != 0 ? 1 : 0;
+        return a ? k : -1;
+      };
+      dealt = deal_workgroup_by_cost<kNdtCostKind0, kNdtCostKind1, kNdtCostKind2>(n_pairs, cap_blocks, kind_in_round, pair, slice, blocks_per_pair, &n_active,
+                                                                              (int)blockIdx.x - n_solvers, (int)gridDim.x - n_solvers);
+    } else {
+      dealt = deal_workgroup(n_pairs, cap_blocks, in_round, pair, slice, blocks_per_pair, &n_active, (int)blockIdx.x - n_solvers, (int)gridDim.x - n_solvers);
+    }
+    if (!dealt) return;
   }
   const NdtPair& st = pairs[pair];
   const float4* __restrict__ src = src_ptrs[pair];
@@ -1183,6 +1254,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   if (threadIdx.x < kStrictPad) handoff_drain_stores();   // (solver: the exact state's write-through stores)
   __syncthreads();
   // tickets of the pair in this launch: its slices, and its solver workgroup when a speculated step is pending (read before anybody can close)
+  STRICT_DEAL_STAMP_WORK(pair, slice, kind, n_active)
   const int n_tickets = blocks_per_pair + ((speculate && st.spec_pending) ? 1 : 0);
   if (threadIdx.x == 0) s_last = handoff_take_ticket(&pairs[pair].ticket, n_tickets) ? 1 : 0;
   __syncthreads();
@@ -1193,6 +1265,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   // with enough other pairs to keep the chip busy the Newton step (a ~40 us dependent chain on one wave) leaves the launch: solve_min_active > 0
   ndt_close_strict<false, WITH_HD>(pairs + pair, partials + (size_t)pair * cap_blocks * kStrictPad, n_slices, consts, done_flags + pair, launch, 1,
                                    solve_min_active > 0 && n_active >= solve_min_active, speculate != 0);
+  STRICT_DEAL_STAMP_CLOSED
 }
 
 // The Newton steps that the closings of round `launch` left behind (NdtPair::serve[1] == launch, phase PH_SOLVE_PENDING): one wave per pair,
@@ -1223,6 +1296,7 @@ __global__ __launch_bounds__(kWave) void ndt_strict_solve_kernel(NdtPair* __rest
       __hip_atomic_store(done_flags + pair, launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     } else {
       st->serve[2] = launch + lag;
+      strict_note_kind(st, launch + lag);
     }
   }
 }

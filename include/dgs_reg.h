@@ -415,6 +415,10 @@ int dgs_ndt_score_gradient(dgs_handle* h, const double* p6, double* score, doubl
  * cap_blocks workgroups per pair: out receives 4 ints per wave, 4 waves per workgroup (16 * grid host ints): pair, slice, workgroups per
  * pair -- all -1 for a workgroup without work -- and the number of active pairs, as every wave derives them on the device. */
 int dgs_deal_probe(dgs_handle* h, const int32_t* active, int32_t n_pairs, int32_t cap_blocks, int32_t grid, int32_t* out);
+/* The same for the cost-ordered dealing of the item-compacted NDT kernel: kinds[pair] in 0..2 is the evaluation kind the pair waits for.  The
+ * active pairs are ranked by (cost class, heaviest first; pair index) and workgroup b serves slice b % per of the pair of rank b / per.
+ * order3 (may be NULL) receives the kinds from the heaviest class to the lightest, as the library was built. */
+int dgs_deal_probe_cost(dgs_handle* h, const int32_t* active, const int32_t* kinds, int32_t n_pairs, int32_t cap_blocks, int32_t grid, int32_t* out, int32_t* order3);
 /* DGS_METHOD_PCL_NDT handles are served by dgs_ndt_derivatives (its evaluation with the Hessian; hess36 == NULL asks for the score +
  * gradient evaluation of a More-Thuente trial), dgs_ndt_hessian_double, dgs_ndt_get_trajectory and dgs_ndt_get_voxels as well.
  * Test hook of such a handle: the neighbourhood of `m` query points (x y z pad, taken as they are: no transform) in the current
