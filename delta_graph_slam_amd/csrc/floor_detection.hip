@@ -4,18 +4,15 @@
 //
 // MI355X design
 //   * fd_tilt_clip_kernel transforms a point and takes both clip decisions in one pass; the kept points are compacted in order by the
-//     prefilter's stable compaction (pf_count_kernel, pf_scan_kernel, pf_scatter_kernel).
+//     shared stable compaction (compact.h: pf_count_kernel, pf_scan_kernel, pf_scatter_kernel).
 //   * The normal pass is the prefilter's: an index of the detector's own over the clipped cloud, gicp.hip's exact k-NN lists and
 //     pf_normal_kernel, unchanged.  fd_normal_flag_kernel applies the floor rule to the normals it wrote.
-//   * The draw stream does not depend on any count, so the host builds the draw list from n alone and uploads it.  fd_prepare_kernel (one
-//     workgroup) tests every draw, compacts the good ones in order into hypotheses (four plane coefficients) and finds the draw that
-//     completes max_sample_checks bad ones in a row, if any.
-//   * fd_score_kernel scores a chunk of hypotheses against every point: a workgroup holds a tile of 1024 points in registers and walks
-//     64 hypotheses, whose four floats sit at wave-uniform addresses; an inlier count is one ballot and popcount per wave, gathered per
-//     workgroup in LDS and added to the hypothesis' global count with one vector atomic.
-//   * RandomSampleConsensus::computeModel's walk runs on the host over the counts that come back (upstream's own libm for pow and log).
-//     With a floor in view it ends after a handful of hypotheses, so the first launch scores hyp_chunk_first of them and further chunks
-//     of hyp_chunk are launched only while the walk is open: one host wait per chunk, one in the common case.
+//   * The RANSAC is sac.h's, shared with the line extraction, over FdModel (the plane's sample test, four coefficients and inlier test).
+//     The draw stream does not depend on any count, so the host builds the draw list from n alone and uploads it;
+//     sac_prepare_kernel<FdModel> turns it into hypotheses and sac_score_kernel<FdModel, 64> scores a chunk of them against every point.
+//   * RandomSampleConsensus::computeModel's walk (SacWalk) runs on the host over the counts that come back (upstream's own libm for pow
+//     and log).  With a floor in view it ends after a handful of hypotheses, so the first launch scores hyp_chunk_first of them and
+//     further chunks of hyp_chunk are launched only while the walk is open: one host wait per chunk, one in the common case.
 //   * The filtered cloud comes back with the first chunk; the winner's inlier list and the checks are host work.
 // Semantics and the PCL 1.10 details recalled from upstream: DESIGN.md §6j.
 #include <algorithm>
@@ -23,27 +20,19 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <random>
-
+#include "compact.h"
 #include "handle.h"
 #include "nn_group.h"
+#include "sac.h"
 
 namespace dgs {
 
-// the prefilter's stable compaction and its normal pass (prefilter.hip)
-__global__ void pf_count_kernel(const unsigned char* __restrict__ flags, const int n, int* __restrict__ blk);
-__global__ void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restrict__ total);
-__global__ void pf_scatter_kernel(const float4* __restrict__ in, const unsigned char* __restrict__ flags, const int n, const int* __restrict__ blk,
-                                  float4* __restrict__ out, const int flatten);
+// the prefilter's normal pass (prefilter.hip)
 __global__ void pf_normal_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int* __restrict__ nbr, const float vx,
                                  const float vy, const float vz, unsigned char* __restrict__ flags, float4* __restrict__ normals, float* __restrict__ cov9);
 
-constexpr int kFdTilePoints = 4;         // points per lane of fd_score_kernel
-constexpr int kFdTile = kFdTilePoints * kBlock;
-constexpr int kFdHypSub = 64;            // hypotheses per workgroup of fd_score_kernel (blockIdx.y)
-constexpr int kFdOneBlock = 1024;
+constexpr int kFdHypSub = 64;            // hypotheses per workgroup of sac_score_kernel (blockIdx.y)
 constexpr int kFdNormalK = 10;           // ne.setKSearch(10) (:219)
-constexpr int kFdDrawSlack = 64;         // draws beyond max_iterations + 1 in the first list
 
 struct FdHyp {
   float c[4];
@@ -118,194 +107,53 @@ __global__ __launch_bounds__(kBlock) void fd_transform_kernel(const float4* __re
 }
 
 // ================================================================================================ hypotheses
-// One workgroup over the D draws in chunks of 1024, in order: good flag, rank among the good ones, distance to the last good one
-// (ln_prepare_kernel's scheme).  SampleConsensusModelPlane::isSampleGood and computeModelCoefficients.
-__global__ __launch_bounds__(kFdOneBlock) void fd_prepare_kernel(const float4* __restrict__ pts, const int n, const int* __restrict__ draws, const int D,
-                                                                 const int bad_run, const int order, const int max_hyp, FdHyp* __restrict__ hyps,
-                                                                 int* __restrict__ counts, int* __restrict__ meta) {
+// pcl::SampleConsensusModelPlane for sac.h's kernels: isSampleGood, computeModelCoefficients and the countWithinDistance predicate
+struct FdModel {
+  static constexpr int kSample = 3;
+  using Hyp = FdHyp;
+  struct Params {
+    int order, bad_run;   // plane_dot_order, max_sample_checks
+    double thr;           // distance_threshold
+  };
+  struct Coef {
+    float a, b, c, d;
+  };
+  static __device__ __forceinline__ int bad_run(const Params& prm) { return prm.bad_run; }
+  // computeModel's w^3 for SacWalk::step, which runs on the host: upstream's own libm
+  static double ratio_power(double w) { return std::pow(w, 3.0); }
+  // dy1dy2 = (p1 - p0) / (p2 - p0), component-wise; good iff its x, y, z are not all equal (NaN compares unequal)
+  static __device__ __forceinline__ bool good(const Params&, const float4 (&p)[3]) {
 #pragma clang fp contract(off)
-  __shared__ int s_w[kFdOneBlock / kWave], s_l[kFdOneBlock / kWave];
-  __shared__ int s_rank, s_last, s_fail;
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  if (threadIdx.x == 0) { s_rank = 0; s_last = -1; s_fail = INT_MAX; }
-  for (int j = threadIdx.x; j < max_hyp; j += kFdOneBlock) counts[j] = 0;
-  __syncthreads();
-  for (int base = 0; base < D; base += kFdOneBlock) {
-    const int d = base + threadIdx.x;
-    bool good = false;
-    int i0 = 0, i1 = 0, i2 = 0;
-    float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0;
-    if (d < D) {
-      i0 = draws[3 * d];
-      i1 = draws[3 * d + 1];
-      i2 = draws[3 * d + 2];
-      if (i0 >= 0 && i0 < n && i1 >= 0 && i1 < n && i2 >= 0 && i2 < n) {
-        p0 = pts[i0];
-        p1 = pts[i1];
-        p2 = pts[i2];
-        // dy1dy2 = (p1 - p0) / (p2 - p0), component-wise; good iff its x, y, z are not all equal (NaN compares unequal)
-        const float rx = (p1.x - p0.x) / (p2.x - p0.x), ry = (p1.y - p0.y) / (p2.y - p0.y), rz = (p1.z - p0.z) / (p2.z - p0.z);
-        good = rx != ry || rz != ry;
-      }
-    }
-    // rank among the good draws, and the last good draw at or before this one (inclusive max scan)
-    const unsigned long long m = __ballot(good);
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    int last = good ? d : -1;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int y = __shfl_up(last, o, kWave);
-      if (lane >= o) last = max(last, y);
-    }
-    if (lane == kWave - 1) { s_w[wv] = __popcll(m); s_l[wv] = last; }
-    __syncthreads();
-    int rank = s_rank + below, prev = s_last;
-    for (int w = 0; w < wv; w++) { rank += s_w[w]; prev = max(prev, s_l[w]); }
-    last = max(last, prev);
-    if (d < D && !good && d - last == bad_run) atomicMin(&s_fail, d);
-    if (good && rank < max_hyp) {
-      const float ux = p1.x - p0.x, uy = p1.y - p0.y, uz = p1.z - p0.z;
-      const float vx = p2.x - p0.x, vy = p2.y - p0.y, vz = p2.z - p0.z;
-      float a = uy * vz - uz * vy;
-      float b = uz * vx - ux * vz;
-      float c = ux * vy - uy * vx;
-      // model_coefficients.normalize(): divided by sqrt(squaredNorm) when that is > 0
-      const float s2 = fd_dot4(a, b, c, 0.f, a, b, c, 0.f, order);
-      if (s2 > 0.f) {
-        const float s = sqrtf(s2);
-        a = a / s; b = b / s; c = c / s;
-      }
-      FdHyp hy;
-      hy.c[0] = a; hy.c[1] = b; hy.c[2] = c;
-      hy.c[3] = -1.0f * fd_dot4(a, b, c, 0.f, p0.x, p0.y, p0.z, p0.w, order);
-      hy.draw = d; hy.i0 = i0; hy.i1 = i1; hy.i2 = i2;
-      hyps[rank] = hy;   // rank < max_hyp: `hyps` holds max_hyp records
-    }
-    __syncthreads();
-    if (threadIdx.x == kFdOneBlock - 1) {
-      s_rank = rank + (good ? 1 : 0);
-      s_last = last;
-    }
-    __syncthreads();
+    const float rx = (p[1].x - p[0].x) / (p[2].x - p[0].x), ry = (p[1].y - p[0].y) / (p[2].y - p[0].y), rz = (p[1].z - p[0].z) / (p[2].z - p[0].z);
+    return rx != ry || rz != ry;
   }
-  if (threadIdx.x == 0) {
-    meta[0] = s_rank;
-    meta[1] = s_fail;
-  }
-}
-
-// grid (tiles of 1024 points, groups of 64 hypotheses of the chunk [h_first, h_end))
-__global__ __launch_bounds__(kBlock) void fd_score_kernel(const float4* __restrict__ pts, const int n, const FdHyp* __restrict__ hyps,
-                                                          const int* __restrict__ meta, const int max_hyp, const int h_first, const int h_end,
-                                                          const int order, const double thr, int* __restrict__ counts) {
-  __shared__ int s_cnt[kFdHypSub];
-  const int H = min(min(meta[0], max_hyp), h_end);
-  const int h0 = h_first + blockIdx.y * kFdHypSub;
-  if (h0 >= H) return;   // uniform per workgroup
-  const int h1 = min(h0 + kFdHypSub, H);
-  if (threadIdx.x < kFdHypSub) s_cnt[threadIdx.x] = 0;
-  float4 p[kFdTilePoints];
-  bool ok[kFdTilePoints];
-#pragma unroll
-  for (int k = 0; k < kFdTilePoints; k++) {
-    const long long i = (long long)blockIdx.x * kFdTile + k * kBlock + threadIdx.x;
-    ok[k] = i < n;
-    p[k] = ok[k] ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kWave - 1);
-  for (int hh = h0; hh < h1; hh++) {
-    const FdHyp* hy = hyps + hh;   // the same address in every lane
-    const float a = hy->c[0], b = hy->c[1], c = hy->c[2], d = hy->c[3];
-    int cnt = 0;
-#pragma unroll
-    for (int k = 0; k < kFdTilePoints; k++) cnt += __popcll(__ballot(ok[k] && fd_is_inlier(p[k], a, b, c, d, order, thr)));
-    if (lane == 0 && cnt) atomicAdd(&s_cnt[hh - h0], cnt);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < h1 - h0 && s_cnt[threadIdx.x]) atomicAdd(&counts[h0 + threadIdx.x], s_cnt[threadIdx.x]);   // h0 + threadIdx.x < h1 <= max_hyp
-}
-
-// ================================================================================================ host side
-namespace {
-
-inline unsigned fd_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-// the sample stream: SampleConsensusModel::drawIndexSample on an identity permutation `s` of at least n entries that carries over
-// between draws, D times; `s` is the identity again on return
-void fd_draws(std::vector<int>& s, const uint32_t* raw, int64_t n, int64_t D, int* out) {
-  std::vector<int> touched;
-  touched.reserve((size_t)D * 3);
-  for (int64_t d = 0; d < D; d++) {
-    for (int i = 0; i < 3; i++) {
-      const int j = i + (int)(raw[3 * d + i] % (uint32_t)(n - i));
-      std::swap(s[(size_t)i], s[(size_t)j]);
-      touched.push_back(j);
+  static __device__ __forceinline__ FdHyp make(const Params& prm, const float4 (&p)[3], const int d, const int (&idx)[3]) {
+#pragma clang fp contract(off)
+    const float ux = p[1].x - p[0].x, uy = p[1].y - p[0].y, uz = p[1].z - p[0].z;
+    const float vx = p[2].x - p[0].x, vy = p[2].y - p[0].y, vz = p[2].z - p[0].z;
+    float a = uy * vz - uz * vy;
+    float b = uz * vx - ux * vz;
+    float c = ux * vy - uy * vx;
+    // model_coefficients.normalize(): divided by sqrt(squaredNorm) when that is > 0
+    const float s2 = fd_dot4(a, b, c, 0.f, a, b, c, 0.f, prm.order);
+    if (s2 > 0.f) {
+      const float s = sqrtf(s2);
+      a = a / s; b = b / s; c = c / s;
     }
-    out[3 * d] = s[0];
-    out[3 * d + 1] = s[1];
-    out[3 * d + 2] = s[2];
+    FdHyp hy;
+    hy.c[0] = a; hy.c[1] = b; hy.c[2] = c;
+    hy.c[3] = -1.0f * fd_dot4(a, b, c, 0.f, p[0].x, p[0].y, p[0].z, p[0].w, prm.order);
+    hy.draw = d; hy.i0 = idx[0]; hy.i1 = idx[1]; hy.i2 = idx[2];
+    return hy;
   }
-  s[0] = 0; s[1] = 1; s[2] = 2;
-  for (int t : touched) s[(size_t)t] = t;
-}
-
-void fd_grow_perm(std::vector<int>& s, int64_t n) {
-  if ((int64_t)s.size() >= n) return;
-  const size_t old = s.size();
-  s.resize((size_t)n);
-  for (size_t i = old; i < (size_t)n; i++) s[i] = (int)i;
-}
-
-void fd_grow_mt(std::vector<uint32_t>& v, int64_t count) {   // boost::mt19937(12345)() >> 1 from the seed on
-  if ((int64_t)v.size() >= count) return;
-  std::mt19937 gen(12345u);
-  v.resize((size_t)count);
-  for (uint32_t& x : v) x = (uint32_t)gen() >> 1;
-}
-
-// RandomSampleConsensus::computeModel's walk: k = 1, best = -INT_MAX, while it < k; a strictly greater count takes over and resets k;
-// after ++it the loop stops once it > max_iterations.  step() consumes one hypothesis.
-struct FdWalk {
-  int it = 0, best = -INT_MAX, win = -1;
-  double k = 1.0;
-  bool open() const { return (double)it < k; }
-  // -> false when the loop broke at it > max_iterations
-  bool step(int count, int64_t n, int max_iterations, double log_one_minus_p) {
-    if (count > best) {
-      best = count;
-      win = it;
-      const double w = (double)count / (double)n;
-      double p_no_outliers = 1.0 - std::pow(w, 3.0);
-      p_no_outliers = std::max(DBL_EPSILON, p_no_outliers);
-      p_no_outliers = std::min(1.0 - DBL_EPSILON, p_no_outliers);
-      k = log_one_minus_p / std::log(p_no_outliers);
-    }
-    ++it;
-    return !(it > max_iterations);
+  static __device__ __forceinline__ Coef coef(const FdHyp* hy) { return {hy->c[0], hy->c[1], hy->c[2], hy->c[3]}; }
+  static __device__ __forceinline__ bool inlier(const Params& prm, const float4 p, const Coef& c) {
+    return fd_is_inlier(p, c.a, c.b, c.c, c.d, prm.order, prm.thr);
   }
 };
 
-// count + scan + scatter of fd.flags over n points of `in` into `out`; *m = kept points (read back: the host waits here)
-int fd_compact(dgs_handle* h, const float4* in, int64_t n, DevBuf<float4>& out, int64_t* m) {
-  FdScratch& fd = h->fd;
-  *m = 0;
-  if (n == 0) return DGS_OK;
-  const unsigned nb = fd_blocks(n);
-  DGS_HIP_TRY(h, out.reserve((size_t)n));
-  DGS_HIP_TRY(h, fd.blk.reserve(nb));
-  DGS_HIP_TRY(h, fd.cnt.reserve(4));
-  hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, fd.flags.ptr, (int)n, fd.blk.ptr);
-  hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kFdOneBlock), 0, h->stream, fd.blk.ptr, (int)nb, fd.cnt.ptr);
-  hipLaunchKernelGGL(pf_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, in, fd.flags.ptr, (int)n, fd.blk.ptr, out.ptr, 0);
-  DGS_HIP_TRY(h, hipGetLastError());
-  if (ensure_pinned(h, 4096) != DGS_OK) return DGS_ERR_HIP;
-  int* hc = reinterpret_cast<int*>(h->pinned);
-  DGS_HIP_TRY(h, hipMemcpyAsync(hc, fd.cnt.ptr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  *m = hc[0];
-  return DGS_OK;
-}
+// ================================================================================================ host side
+namespace {
 
 FdMat fd_mat(const float* col16) {
   FdMat M;
@@ -324,10 +172,10 @@ int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   DGS_HIP_TRY(h, fd.flags.reserve((size_t)n));
   DGS_HIP_TRY(h, fd.tilted.reserve((size_t)n));
   const float hi = (float)(p.sensor_height + p.height_clip_range), lo = (float)(p.sensor_height - p.height_clip_range);
-  hipLaunchKernelGGL(fd_tilt_clip_kernel, dim3(fd_blocks(n)), dim3(kBlock), 0, h->stream, in, (int)n, fd_mat(tilt16), p.transform_order, hi, lo,
+  hipLaunchKernelGGL(fd_tilt_clip_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, in, (int)n, fd_mat(tilt16), p.transform_order, hi, lo,
                      fd.tilted.ptr, fd.flags.ptr);
   int64_t nc = 0;
-  if (int rc = fd_compact(h, fd.tilted.ptr, n, fd.clipped, &nc)) return rc;
+  if (int rc = compact_points(h, fd.tilted.ptr, fd.flags.ptr, n, fd.blk, fd.cnt, fd.clipped, false, &nc)) return rc;
   fd.n_clipped = nc;
   const float4* kept = fd.clipped.ptr;
   int64_t nk = nc;
@@ -343,17 +191,17 @@ int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
     const int k = (int)std::min<int64_t>(kFdNormalK, nc);   // FLANN returns min(k, n) neighbours
     if (int rc = knn_lists(h, c, k, &fd.nbr)) return rc;
     // ne.setViewPoint(0.0f, 0.0f, sensor_height) (:220)
-    hipLaunchKernelGGL(pf_normal_kernel, dim3(fd_blocks(nc)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)nc, k, fd.nbr.ptr, 0.0f,
+    hipLaunchKernelGGL(pf_normal_kernel, dim3(compact_blocks(nc)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)nc, k, fd.nbr.ptr, 0.0f,
                        0.0f, (float)p.sensor_height, fd.nflags.ptr, fd.normals.ptr, fd.cov9.ptr);
-    hipLaunchKernelGGL(fd_normal_flag_kernel, dim3(fd_blocks(nc)), dim3(kBlock), 0, h->stream, fd.normals.ptr, (int)nc,
+    hipLaunchKernelGGL(fd_normal_flag_kernel, dim3(compact_blocks(nc)), dim3(kBlock), 0, h->stream, fd.normals.ptr, (int)nc,
                        std::cos(p.normal_filter_thresh * M_PI / 180.0), fd.flags.ptr);
     fd.have_normals = true;
-    if (int rc = fd_compact(h, fd.clipped.ptr, nc, fd.kept, &nk)) return rc;
+    if (int rc = compact_points(h, fd.clipped.ptr, fd.flags.ptr, nc, fd.blk, fd.cnt, fd.kept, false, &nk)) return rc;
     kept = fd.kept.ptr;
   }
   if (nk > 0) {
     DGS_HIP_TRY(h, fd.filtered.reserve((size_t)nk));
-    hipLaunchKernelGGL(fd_transform_kernel, dim3(fd_blocks(nk)), dim3(kBlock), 0, h->stream, kept, (int)nk, fd_mat(tilt_inv16), p.transform_order,
+    hipLaunchKernelGGL(fd_transform_kernel, dim3(compact_blocks(nk)), dim3(kBlock), 0, h->stream, kept, (int)nk, fd_mat(tilt_inv16), p.transform_order,
                        fd.filtered.ptr);
     DGS_HIP_TRY(h, hipGetLastError());
   }
@@ -362,12 +210,11 @@ int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   return DGS_OK;
 }
 
-enum { FD_WALK_DONE = 0, FD_WALK_NEED_DRAWS = 1 };
-
 // steps 5-8 over fd.filtered (n >= 3 points) with a draw list of D draws: the walk's end state in fd.trace, the winner's coefficients in
-// coeffs, the filtered cloud in fd.host_filtered.  *outcome = FD_WALK_NEED_DRAWS when the walk ran past the list.
-int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, const uint32_t* raw, int64_t D, int* outcome, float* coeffs) {
+// coeffs, the filtered cloud in fd.host_filtered.  *need_draws when the walk ran past the list.
+int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, const uint32_t* raw, int64_t D, bool* need_draws, float* coeffs) {
   FdScratch& fd = h->fd;
+  SacScratch& sac = fd.sac;
   dgs_floor_detection_trace& tr = fd.trace;
   const int max_hyp = p.max_iterations + 1;
   // pinned block: meta | hypotheses | counts | filtered cloud | draw list
@@ -379,35 +226,35 @@ int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, con
   FdHyp* h_hyp = reinterpret_cast<FdHyp*>(pin + off_hyp);
   int* h_cnt = reinterpret_cast<int*>(pin + off_cnt);
   int* h_draws = reinterpret_cast<int*>(pin + off_draws);
-  DGS_HIP_TRY(h, fd.draws.reserve((size_t)D * 3));
+  DGS_HIP_TRY(h, sac.draws.reserve((size_t)D * 3));
   DGS_HIP_TRY(h, fd.hyps.reserve((size_t)max_hyp));
-  DGS_HIP_TRY(h, fd.counts.reserve((size_t)max_hyp));
-  DGS_HIP_TRY(h, fd.meta.reserve(4));
-  fd_grow_perm(fd.perm, n);
-  fd_draws(fd.perm, raw, n, D, h_draws);
-  DGS_HIP_TRY(h, hipMemcpyAsync(fd.draws.ptr, h_draws, (size_t)D * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(fd_prepare_kernel, dim3(1), dim3(kFdOneBlock), 0, h->stream, fd.filtered.ptr, (int)n, fd.draws.ptr, (int)D, p.max_sample_checks,
-                     p.plane_dot_order, max_hyp, fd.hyps.ptr, fd.counts.ptr, fd.meta.ptr);
+  DGS_HIP_TRY(h, sac.counts.reserve((size_t)max_hyp));
+  DGS_HIP_TRY(h, sac.meta.reserve(4));
+  sac_grow_perm(sac.perm, n);
+  sac_draws<3>(sac.perm, raw, n, D, h_draws);
+  DGS_HIP_TRY(h, hipMemcpyAsync(sac.draws.ptr, h_draws, (size_t)D * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const FdModel::Params prm{p.plane_dot_order, p.max_sample_checks, p.distance_threshold};
+  hipLaunchKernelGGL(sac_prepare_kernel<FdModel>, dim3(1), dim3(kSacPrepareBlock), 0, h->stream, fd.filtered.ptr, (int)n, sac.draws.ptr, (int)D, prm,
+                     max_hyp, fd.hyps.ptr, sac.counts.ptr, sac.meta.ptr);
   DGS_HIP_TRY(h, hipMemcpyAsync(pin + off_cloud, fd.filtered.ptr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
 
-  FdWalk wk;
+  SacWalk wk;
   const double log_one_minus_p = std::log(1.0 - p.probability);
-  int scored = 0, chunks = 0, H = 0, fail_at = INT_MAX, draws = 0;
-  bool failed = false, need = false;
+  int scored = 0, chunks = 0, H = 0, fail_at = INT_MAX;
   while (wk.open()) {
     if (wk.it >= scored) {
-      if (chunks > 0 && scored >= H) {   // no further good draw in the list: a run of bad ones completed, or the list is too short
-        if (fail_at < D) { failed = true; draws = fail_at + 1; } else { need = true; draws = (int)D; }
+      if (chunks > 0 && scored >= H) {
+        wk.end_of_list(fail_at, (int)D);
         break;
       }
       const int h_end = (int)std::min<int64_t>(max_hyp, (int64_t)scored + (chunks == 0 ? p.hyp_chunk_first : p.hyp_chunk));
-      hipLaunchKernelGGL(fd_score_kernel, dim3((unsigned)((n + kFdTile - 1) / kFdTile), (unsigned)((h_end - scored + kFdHypSub - 1) / kFdHypSub)), dim3(kBlock),
-                         0, h->stream, fd.filtered.ptr, (int)n, fd.hyps.ptr, fd.meta.ptr, max_hyp, scored, h_end, p.plane_dot_order, p.distance_threshold,
-                         fd.counts.ptr);
+      hipLaunchKernelGGL((sac_score_kernel<FdModel, kFdHypSub>),
+                         dim3((unsigned)((n + kSacTile - 1) / kSacTile), (unsigned)((h_end - scored + kFdHypSub - 1) / kFdHypSub)), dim3(kBlock), 0,
+                         h->stream, fd.filtered.ptr, (int)n, fd.hyps.ptr, sac.meta.ptr, max_hyp, scored, h_end, prm, sac.counts.ptr);
       DGS_HIP_TRY(h, hipGetLastError());
-      DGS_HIP_TRY(h, hipMemcpyAsync(h_meta, fd.meta.ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      DGS_HIP_TRY(h, hipMemcpyAsync(h_meta, sac.meta.ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
       DGS_HIP_TRY(h, hipMemcpyAsync(h_hyp + scored, fd.hyps.ptr + scored, (size_t)(h_end - scored) * sizeof(FdHyp), hipMemcpyDeviceToHost, h->stream));
-      DGS_HIP_TRY(h, hipMemcpyAsync(h_cnt + scored, fd.counts.ptr + scored, (size_t)(h_end - scored) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      DGS_HIP_TRY(h, hipMemcpyAsync(h_cnt + scored, sac.counts.ptr + scored, (size_t)(h_end - scored) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
       DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
       chunks++;
       H = std::min(h_meta[0], max_hyp);
@@ -415,21 +262,16 @@ int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, con
       scored = std::min(h_end, H);
       continue;
     }
-    if (h_hyp[wk.it].draw > fail_at) {   // getSamples returned an empty selection before this hypothesis' draw: the loop breaks
-      failed = true;
-      draws = fail_at + 1;
-      break;
-    }
-    draws = h_hyp[wk.it].draw + 1;
-    if (!wk.step(h_cnt[wk.it], n, p.max_iterations, log_one_minus_p)) break;
+    if (!wk.next(h_hyp[wk.it].draw, fail_at)) break;
+    if (!wk.step(h_cnt[wk.it], n, p.max_iterations, log_one_minus_p, FdModel::ratio_power)) break;
   }
-  tr.draws = draws;
+  tr.draws = wk.draws;
   tr.hypotheses_scored = scored;
   tr.iterations = wk.it;
   tr.chunks_launched = chunks;
-  tr.ransac_failed = failed ? 1 : 0;
-  *outcome = need ? FD_WALK_NEED_DRAWS : FD_WALK_DONE;
-  if (need) return DGS_OK;
+  tr.ransac_failed = wk.status == SAC_FAILED ? 1 : 0;
+  *need_draws = wk.status == SAC_NEED_DRAWS;
+  if (*need_draws) return DGS_OK;
   fd.host_filtered.resize((size_t)n);
   std::memcpy(fd.host_filtered.data(), pin + off_cloud, (size_t)n * sizeof(float4));
   if (wk.win >= 0) {
@@ -489,21 +331,18 @@ int fd_detect(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
       DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
   } else {
-    const int max_hyp = p.max_iterations + 1;
-    const int64_t avail = rng_raw ? rng_len / 3 : INT32_MAX / 4;
-    int64_t D = std::min<int64_t>(avail, (int64_t)max_hyp + kFdDrawSlack);
+    SacDrawPlan plan(rng_raw ? rng_len / 3 : INT32_MAX / 4, p.max_iterations + 1, p.max_sample_checks);
     for (;;) {
-      if (D < 1) { *status_out = DGS_FD_RNG_EXHAUSTED; return DGS_OK; }
+      if (plan.empty()) { *status_out = DGS_FD_RNG_EXHAUSTED; return DGS_OK; }
       const uint32_t* raw = rng_raw;
       if (!rng_raw) {
-        fd_grow_mt(fd.mt_raw, 3 * D);
-        raw = fd.mt_raw.data();
+        sac_grow_mt(fd.sac.mt_raw, 3 * plan.D);
+        raw = fd.sac.mt_raw.data();
       }
-      int outcome = FD_WALK_DONE;
-      if (int rc = fd_ransac(h, p, nf, raw, D, &outcome, coeffs)) return rc;
-      if (outcome == FD_WALK_DONE) break;
-      if (D >= avail) { *status_out = DGS_FD_RNG_EXHAUSTED; return DGS_OK; }
-      D = std::min<int64_t>(avail, std::min<int64_t>(D * 4, (int64_t)max_hyp * p.max_sample_checks + p.max_sample_checks));
+      bool need_draws = false;
+      if (int rc = fd_ransac(h, p, nf, raw, plan.D, &need_draws, coeffs)) return rc;
+      if (!need_draws) break;
+      if (!plan.grow()) { *status_out = DGS_FD_RNG_EXHAUSTED; return DGS_OK; }
     }
   }
   // selectWithinDistance of the winner, in index order; no model: empty inliers
@@ -536,8 +375,8 @@ int fd_detect(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
 void floor_detection_release(dgs_handle* h) {
   FdScratch& fd = h->fd;
   for (DevBuf<float4>* b : {&fd.in, &fd.tilted, &fd.clipped, &fd.kept, &fd.filtered, &fd.normals}) b->release();
-  fd.flags.release(); fd.nflags.release(); fd.blk.release(); fd.cnt.release(); fd.nbr.release(); fd.cov9.release(); fd.draws.release();
-  fd.hyps.release(); fd.counts.release(); fd.meta.release();
+  fd.flags.release(); fd.nflags.release(); fd.blk.release(); fd.cnt.release(); fd.nbr.release(); fd.cov9.release(); fd.hyps.release();
+  fd.sac.release();
   fd.cloud.release();
   fd.host_filtered.clear(); fd.inliers.clear();
   fd.n_clipped = fd.n_filtered = 0;
@@ -639,13 +478,13 @@ int dgs_floor_detection_get_clipped(dgs_handle* h, float* clipped_xyz16, float* 
 int dgs_floor_detection_draws(int64_t n, const uint32_t* rng_raw, int64_t n_draws, int32_t* triples_out) {
   if (n < 3 || n > INT32_MAX || n_draws < 0 || n_draws > (1 << 24) || (n_draws > 0 && !triples_out)) return DGS_ERR_INVALID_ARGUMENT;
   std::vector<int> perm;
-  fd_grow_perm(perm, n);
+  sac_grow_perm(perm, n);
   std::vector<uint32_t> mt;
   if (!rng_raw) {
-    fd_grow_mt(mt, 3 * n_draws);
+    sac_grow_mt(mt, 3 * n_draws);
     rng_raw = mt.data();
   }
-  fd_draws(perm, rng_raw, n, n_draws, triples_out);
+  sac_draws<3>(perm, rng_raw, n, n_draws, triples_out);
   return DGS_OK;
 }
 
@@ -654,11 +493,11 @@ int dgs_floor_detection_walk(int64_t n, int32_t max_iterations, double probabili
   if (n < 1 || max_iterations < 0 || !(probability > 0.0 && probability < 1.0) || n_counts < 0 || (n_counts > 0 && !counts) || !winner_out ||
       !iterations_out || !open_out)
     return DGS_ERR_INVALID_ARGUMENT;
-  FdWalk wk;
+  SacWalk wk;
   const double log_one_minus_p = std::log(1.0 - probability);
   bool broke = false;
   while (wk.open() && wk.it < n_counts) {
-    if (!wk.step(counts[wk.it], n, max_iterations, log_one_minus_p)) { broke = true; break; }
+    if (!wk.step(counts[wk.it], n, max_iterations, log_one_minus_p, FdModel::ratio_power)) { broke = true; break; }
   }
   *winner_out = wk.win;
   *iterations_out = wk.it;

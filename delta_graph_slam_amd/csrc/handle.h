@@ -1,6 +1,7 @@
 // dgs_handle: per-registration-object state (one per pcl::Registration instance on the reference side).
 #pragma once
 #include "common.h"
+#include "sac.h"
 
 namespace dgs {
 
@@ -145,8 +146,8 @@ struct McScratch {
   int used_sort = 0;                   // the last map took the sort path
 };
 
-// LineBasedScanmatcher::line_extraction (line_extraction.hip): the two round clouds, the draw list and hypotheses of a round, the
-// inlier / cluster lists, the clustering's sort and union-find arrays, and what the test hook reads back.  Separate from everything
+// LineBasedScanmatcher::line_extraction (line_extraction.hip): the two round clouds, the hypotheses of a round and what sac.h's kernels
+// need around them (SacScratch), the inlier / cluster lists, the clustering's sort and union-find arrays, and what the test hook reads back.  Separate from everything
 // a registration, the prefilter or the map cloud uses.
 struct LnHyp;     // line_extraction.hip
 struct LnRound;
@@ -155,9 +156,8 @@ struct LnScratch {
   DevBuf<float4> inl, clu, sorted;     // inliers / cluster members (w = position in the round's cloud); inliers in projection order
   DevBuf<unsigned char> flags, cflags; // inlier / keep flag per point; cluster flag per point
   DevBuf<int> blk, cnt;                // compaction offsets; [0] inliers, [1] cluster members, [2] points kept
-  DevBuf<int> draws;                   // two point indices per draw
+  SacScratch sac;                      // two point indices per draw; the permutation is the identity between rounds
   DevBuf<LnHyp> hyps;                  // the good draws in order, at most max_iterations + 1
-  DevBuf<int> counts, meta;            // inliers per hypothesis; [0] good draws, [1] draw that completes 1000 bad ones in a row
   DevBuf<LnRound> round;
   DevBuf<uint32_t> keys, keys_alt, vals, vals_alt;
   DevBuf<float> sproj;                 // projection on the line per sorted inlier
@@ -165,8 +165,6 @@ struct LnScratch {
   DevBuf<unsigned char> temp;          // sort temporary storage
   std::vector<dgs_line_extraction_round> rounds;        // the last extraction
   std::vector<std::vector<int32_t>> inlier_lists, cluster_lists;   // with record_lists
-  std::vector<uint32_t> mt_raw;        // mt19937(12345)() >> 1, extended on demand
-  std::vector<int> perm;               // identity between rounds: shuffled_indices_
   int64_t counts4[4] = {0, 0, 0, 0};
 };
 
@@ -239,13 +237,10 @@ struct FdScratch {
   DevBuf<int> nbr;                     // its k-NN lists
   DevBuf<float4> normals;
   DevBuf<float> cov9;
-  DevBuf<int> draws;                   // three point indices per draw
+  SacScratch sac;                      // three point indices per draw; the permutation is the identity between detects
   DevBuf<FdHyp> hyps;                  // the good draws in order, at most max_iterations + 1
-  DevBuf<int> counts, meta;            // inliers per hypothesis; [0] good draws, [1] draw that completes max_sample_checks bad ones in a row
   std::vector<float4> host_filtered;   // the filtered cloud on the host: final inlier flags and checks run there
   std::vector<int32_t> inliers;
-  std::vector<uint32_t> mt_raw;        // mt19937(12345)() >> 1, extended on demand
-  std::vector<int> perm;               // identity between detects: shuffled_indices_
   int64_t n_clipped = 0, n_filtered = 0;
   bool have_normals = false;
   dgs_floor_detection_trace trace{};

@@ -12,7 +12,7 @@
 //   * One upload: source lines, the target table (A, B, (B - A).normalized() per merged line) and both edge lists (edges_on_device: the
 //     merged target lines in place of the edge lists).
 //   * la_hypothesis_kernel: one lane per h; transform, gate code, survivor flag.  Survivors are compacted in h order with the
-//     prefilter's stable compaction (pf_count_kernel, pf_scan_kernel) and la_scatter_kernel.
+//     shared stable compaction (compact.h: pf_count_kernel, pf_scan_kernel) and la_scatter_kernel.
 //   * la_score_kernel: one wavefront per survivor (item 0 is the identity, the baseline) runs la::fitness_wave<false> against the
 //     target table in LDS (72 bytes per line, 36 KiB at the limit of 512 lines).  FP64 throughout: the loop is bound by the FP64
 //     divide and square-root sequences of line_to_line_distance, not by memory.
@@ -27,16 +27,12 @@
 #include <cstring>
 #include <vector>
 
+#include "compact.h"
 #include "handle.h"
 #include "line_align.h"
 
 namespace dgs {
 
-// the prefilter's stable compaction (prefilter.hip)
-__global__ void pf_count_kernel(const unsigned char* __restrict__ flags, const int n, int* __restrict__ blk);
-__global__ void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restrict__ total);
-
-constexpr int kLaScanBlock = 1024;      // pf_scan_kernel's workgroup
 constexpr int kLaArgmaxBlock = 1024;
 constexpr int kLaScoreBlocks = 2048;    // la_score_kernel's fixed grid: 8192 waves, 8 per SIMD of 256 CUs
 constexpr int kLaWavesPerBlock = kBlock / kWave;
@@ -82,18 +78,12 @@ __global__ __launch_bounds__(kBlock) void la_hypothesis_kernel(const double* __r
 // the survivors' h in order, and every h's position in that list
 __global__ __launch_bounds__(kBlock) void la_scatter_kernel(const unsigned char* __restrict__ keep, const int n, const int* __restrict__ blk,
                                                             int* __restrict__ surv, int* __restrict__ slot) {
-  __shared__ int s_w[kLaWavesPerBlock];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  const bool f = i < n && keep[i] != 0;
-  const unsigned long long m = __ballot(f);
-  if (lane == 0) s_w[wv] = __popcll(m);
-  __syncthreads();
-  if (i < n && !f) slot[i] = -1;
-  if (!f) return;
-  int off = blk[blockIdx.x];
-  for (int w = 0; w < wv; w++) off += s_w[w];
-  off += __popcll(m & ((1ull << lane) - 1ull));
+  int off;
+  if (!compact_slot(keep, i, n, blk, &off)) {
+    if (i < n) slot[i] = -1;
+    return;
+  }
   surv[off] = i;   // off < number of survivors <= n: `surv` holds n entries
   slot[i] = off;
 }
@@ -239,8 +229,7 @@ int la_search(dgs_handle* h, LaArgs& a, const std::vector<la::Line>& src, const 
   DGS_HIP_TRY(h, s.result.reserve(1));
   if (H > 0) {
     hipLaunchKernelGGL(la_hypothesis_kernel, dim3(nb), dim3(kBlock), 0, h->stream, d_es, d_et, a, s.hyps.ptr, s.keep.ptr, s.gate.ptr, s.fit.ptr);
-    hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, s.keep.ptr, (int)H, s.blk.ptr);
-    hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kLaScanBlock), 0, h->stream, s.blk.ptr, (int)nb, s.cnt.ptr);
+    compact_offsets(h->stream, s.keep.ptr, H, s.blk.ptr, s.cnt.ptr);
     hipLaunchKernelGGL(la_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, s.keep.ptr, (int)H, s.blk.ptr, s.surv.ptr, s.slot.ptr);
     s.counts4[0] += 4;
   } else {

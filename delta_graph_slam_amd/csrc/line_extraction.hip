@@ -3,16 +3,14 @@
 // clustering of the inliers, the statistics of the biggest cluster and its removal.
 //
 // MI355X design, one round over the n remaining points
-//   * The draw stream does not depend on any count, so the host builds the round's draw list from n alone (the generator restarts every
-//     round) and uploads it.  ln_prepare_kernel (one workgroup) tests every draw, compacts the good ones in order into hypotheses
-//     (point, unit direction) and finds the draw that completes 1000 bad ones in a row, if any.
-//   * ln_score_kernel scores every hypothesis against every point in one launch: a workgroup holds a tile of 1024 points in registers
-//     and walks the hypotheses, whose six floats sit at wave-uniform addresses; an inlier count is one ballot and popcount per wave,
-//     gathered per workgroup in LDS and added to the hypothesis' global count with one vector atomic.
-//   * ln_walk_kernel replays RandomSampleConsensus::computeModel's sequential walk over the (count, draw) records: the winner is the
-//     sequential loop's winner.
-//   * Inliers, cluster members and the removal are keep flags and the prefilter's stable compaction (pf_count_kernel, pf_scan_kernel,
-//     pf_scatter_kernel); ln_scatter_index_kernel is the scatter that also writes a point's position.
+//   * The RANSAC is sac.h's, shared with the floor detection, over LnModel (the line's sample test, point and unit direction, inlier
+//     test).  The draw stream does not depend on any count, so the host builds the round's draw list from n alone (the generator
+//     restarts every round) and uploads it; sac_prepare_kernel<LnModel> turns it into hypotheses and sac_score_kernel<LnModel, 512>
+//     scores every hypothesis against every point in one launch.
+//   * ln_walk_kernel replays RandomSampleConsensus::computeModel's sequential walk (SacWalk) over the (count, draw) records: the winner
+//     is the sequential loop's winner.
+//   * Inliers, cluster members and the removal are keep flags and the shared stable compaction (compact.h: pf_count_kernel,
+//     pf_scan_kernel, pf_scatter_kernel); ln_scatter_index_kernel is the scatter that also writes a point's position.
 //   * The refit and the statistics keep upstream's sequential sums: a workgroup stages 256 terms at a time in LDS, one lane adds them
 //     in order.  Everything that is order-independent (minimum, maximum, first extreme projection) is a reduction.
 //   * Clustering: the inliers lie within the threshold of a line, so they are sorted by their projection on it and every inlier tests
@@ -26,30 +24,20 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <random>
 
 #include <hipcub/hipcub.hpp>
 
+#include "compact.h"
 #include "eigen33.h"
 #include "handle.h"
 #include "nn_group.h"
+#include "sac.h"
 
 namespace dgs {
 
-// the prefilter's stable compaction (prefilter.hip)
-__global__ void pf_count_kernel(const unsigned char* __restrict__ flags, const int n, int* __restrict__ blk);
-__global__ void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restrict__ total);
-__global__ void pf_scatter_kernel(const float4* __restrict__ in, const unsigned char* __restrict__ flags, const int n, const int* __restrict__ blk,
-                                  float4* __restrict__ out, const int flatten);
-
-constexpr int kLnTilePoints = 4;         // points per lane of ln_score_kernel
-constexpr int kLnTile = kLnTilePoints * kBlock;
-constexpr int kLnHypChunk = 512;         // hypotheses per workgroup of ln_score_kernel (blockIdx.y)
+constexpr int kLnHypChunk = 512;         // hypotheses per workgroup of sac_score_kernel (blockIdx.y)
 constexpr int kLnBadRun = 1000;          // SampleConsensusModel::max_sample_checks_
-constexpr int kLnOneBlock = 1024;
-constexpr int kLnDrawSlack = 64;         // draws beyond max_iterations + 1 in a round's first list
-
-enum { LN_OK = 0, LN_FAILED = 1, LN_NEED_DRAWS = 2 };
+constexpr int kLnPickBlock = 1024;       // ln_pick_kernel: one workgroup
 
 struct LnHyp {
   float p0[3];
@@ -81,151 +69,75 @@ __device__ __forceinline__ bool ln_is_inlier(const float4 p, const float p0x, co
 }
 
 // ================================================================================================ hypotheses
-// One workgroup over the D draws in chunks of 1024, in order: good flag, rank among the good ones, distance to the last good one.
-__global__ __launch_bounds__(kLnOneBlock) void ln_prepare_kernel(const float4* __restrict__ pts, const int n, const int* __restrict__ draws, const int D,
-                                                                 const int any_axis, const int max_hyp, LnHyp* __restrict__ hyps,
-                                                                 int* __restrict__ counts, int* __restrict__ meta) {
-  __shared__ int s_w[kLnOneBlock / kWave], s_l[kLnOneBlock / kWave];
-  __shared__ int s_rank, s_last, s_fail;
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-  if (threadIdx.x == 0) { s_rank = 0; s_last = -1; s_fail = INT_MAX; }
-  for (int j = threadIdx.x; j < max_hyp; j += kLnOneBlock) counts[j] = 0;
-  __syncthreads();
-  for (int base = 0; base < D; base += kLnOneBlock) {
-    const int d = base + threadIdx.x;
-    bool good = false;
-    int i0 = 0, i1 = 0;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    if (d < D) {
-      i0 = draws[2 * d];
-      i1 = draws[2 * d + 1];
-      if (i0 >= 0 && i0 < n && i1 >= 0 && i1 < n) {
-        a = pts[i0];
-        b = pts[i1];
-        good = any_axis ? (a.x != b.x || a.y != b.y || a.z != b.z) : (a.x != b.x && a.y != b.y && a.z != b.z);
-      }
-    }
-    // rank among the good draws, and the last good draw at or before this one (inclusive max scan)
-    const unsigned long long m = __ballot(good);
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    int last = good ? d : -1;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int y = __shfl_up(last, o, kWave);
-      if (lane >= o) last = max(last, y);
-    }
-    if (lane == kWave - 1) { s_w[wv] = __popcll(m); s_l[wv] = last; }
-    __syncthreads();
-    int rank = s_rank + below, prev = s_last;
-    for (int w = 0; w < wv; w++) { rank += s_w[w]; prev = max(prev, s_l[w]); }
-    last = max(last, prev);
-    if (d < D && !good && d - last == kLnBadRun) atomicMin(&s_fail, d);
-    if (good && rank < max_hyp) {
-      LnHyp hy;
-      hy.p0[0] = a.x; hy.p0[1] = a.y; hy.p0[2] = a.z;
-      // model_coefficients.tail<3>() = p1 - p0, normalize(): divided by sqrt(squaredNorm) when that is > 0
-      float ux = sub_rn(b.x, a.x), uy = sub_rn(b.y, a.y), uz = sub_rn(b.z, a.z);
-      const float n2 = add_rn(add_rn(mul_rn(ux, ux), mul_rn(uy, uy)), mul_rn(uz, uz));
-      if (n2 > 0.f) {
-        const float s = sqrtf(n2);
-        ux = ux / s; uy = uy / s; uz = uz / s;
-      }
-      hy.dir[0] = ux; hy.dir[1] = uy; hy.dir[2] = uz;
-      hy.draw = d; hy.i0 = i0; hy.i1 = i1;
-      hy.pad[0] = hy.pad[1] = hy.pad[2] = 0;
-      hyps[rank] = hy;   // rank < max_hyp: `hyps` holds max_hyp records
-    }
-    __syncthreads();
-    if (threadIdx.x == kLnOneBlock - 1) {
-      s_rank = rank + (good ? 1 : 0);
-      s_last = last;
-    }
-    __syncthreads();
+// pcl::SampleConsensusModelLine for sac.h's kernels: isSampleGood, computeModelCoefficients and the countWithinDistance predicate
+struct LnModel {
+  static constexpr int kSample = 2;
+  using Hyp = LnHyp;
+  struct Params {
+    int any_axis, order;   // sample_good_any_axis, sqnorm_order
+    double thr2;           // sac_distance_threshold squared
+  };
+  struct Coef {
+    float p0x, p0y, p0z, dx, dy, dz;
+  };
+  static __device__ __forceinline__ int bad_run(const Params&) { return kLnBadRun; }
+  static __device__ __forceinline__ bool good(const Params& prm, const float4 (&p)[2]) {
+    const float4 a = p[0], b = p[1];
+    return prm.any_axis ? (a.x != b.x || a.y != b.y || a.z != b.z) : (a.x != b.x && a.y != b.y && a.z != b.z);
   }
-  if (threadIdx.x == 0) {
-    meta[0] = s_rank;
-    meta[1] = s_fail;
+  static __device__ __forceinline__ LnHyp make(const Params&, const float4 (&p)[2], const int d, const int (&idx)[2]) {
+    const float4 a = p[0], b = p[1];
+    LnHyp hy;
+    hy.p0[0] = a.x; hy.p0[1] = a.y; hy.p0[2] = a.z;
+    // model_coefficients.tail<3>() = p1 - p0, normalize(): divided by sqrt(squaredNorm) when that is > 0
+    float ux = sub_rn(b.x, a.x), uy = sub_rn(b.y, a.y), uz = sub_rn(b.z, a.z);
+    const float n2 = add_rn(add_rn(mul_rn(ux, ux), mul_rn(uy, uy)), mul_rn(uz, uz));
+    if (n2 > 0.f) {
+      const float s = sqrtf(n2);
+      ux = ux / s; uy = uy / s; uz = uz / s;
+    }
+    hy.dir[0] = ux; hy.dir[1] = uy; hy.dir[2] = uz;
+    hy.draw = d; hy.i0 = idx[0]; hy.i1 = idx[1];
+    hy.pad[0] = hy.pad[1] = hy.pad[2] = 0;
+    return hy;
   }
-}
+  static __device__ __forceinline__ Coef coef(const LnHyp* hy) { return {hy->p0[0], hy->p0[1], hy->p0[2], hy->dir[0], hy->dir[1], hy->dir[2]}; }
+  static __device__ __forceinline__ bool inlier(const Params& prm, const float4 p, const Coef& c) {
+    return ln_is_inlier(p, c.p0x, c.p0y, c.p0z, c.dx, c.dy, c.dz, prm.order, prm.thr2);
+  }
+  // computeModel's w^2 for SacWalk::step, which runs on the device
+  static __device__ __forceinline__ double ratio_power(const double w) {
+#pragma clang fp contract(off)
+    return w * w;
+  }
+};
 
-// grid (tiles of 1024 points, chunks of 512 hypotheses)
-__global__ __launch_bounds__(kBlock) void ln_score_kernel(const float4* __restrict__ pts, const int n, const LnHyp* __restrict__ hyps,
-                                                          const int* __restrict__ meta, const int max_hyp, const int order, const double thr2,
-                                                          int* __restrict__ counts) {
-  __shared__ int s_cnt[kLnHypChunk];
-  const int H = min(meta[0], max_hyp);
-  const int h0 = blockIdx.y * kLnHypChunk;
-  if (h0 >= H) return;   // uniform per workgroup
-  const int h1 = min(h0 + kLnHypChunk, H);
-  for (int j = threadIdx.x; j < kLnHypChunk; j += kBlock) s_cnt[j] = 0;
-  float4 p[kLnTilePoints];
-  bool ok[kLnTilePoints];
-#pragma unroll
-  for (int k = 0; k < kLnTilePoints; k++) {
-    const long long i = (long long)blockIdx.x * kLnTile + k * kBlock + threadIdx.x;
-    ok[k] = i < n;
-    p[k] = ok[k] ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kWave - 1);
-  for (int hh = h0; hh < h1; hh++) {
-    const LnHyp* hy = hyps + hh;   // the same address in every lane
-    const float p0x = hy->p0[0], p0y = hy->p0[1], p0z = hy->p0[2], dx = hy->dir[0], dy = hy->dir[1], dz = hy->dir[2];
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < kLnTilePoints; k++) c += __popcll(__ballot(ok[k] && ln_is_inlier(p[k], p0x, p0y, p0z, dx, dy, dz, order, thr2)));
-    if (lane == 0 && c) atomicAdd(&s_cnt[hh - h0], c);
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < h1 - h0; j += kBlock)
-    if (s_cnt[j]) atomicAdd(&counts[h0 + j], s_cnt[j]);
-}
-
-// RandomSampleConsensus::computeModel's walk over the counts (one lane): k = 1, best = -INT_MAX, while it < k; a strictly greater count
-// takes over and resets k; after ++it the loop stops once it > max_iterations.
+// RandomSampleConsensus::computeModel's walk over the counts (one lane)
 __global__ void ln_walk_kernel(const LnHyp* __restrict__ hyps, const int* __restrict__ counts, const int* __restrict__ meta, const int n, const int D,
                                const int max_hyp, const int max_iterations, const double log_one_minus_p, LnRound* __restrict__ R) {
-#pragma clang fp contract(off)
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const int H = min(meta[0], max_hyp), fail_at = meta[1];
-  int it = 0, best = -INT_MAX, win = -1, status = LN_OK, draws = 0;
-  double k = 1.0;
-  while ((double)it < k) {
-    if (it >= H) {   // no further good draw in the list: a run of bad ones completed, or the list is too short
-      status = fail_at < D ? LN_FAILED : LN_NEED_DRAWS;
-      draws = fail_at < D ? fail_at + 1 : D;
+  SacWalk wk;
+  while (wk.open()) {
+    if (wk.it >= H) {
+      wk.end_of_list(fail_at, D);
       break;
     }
-    if (hyps[it].draw > fail_at) {
-      status = LN_FAILED;
-      draws = fail_at + 1;
-      break;
-    }
-    draws = hyps[it].draw + 1;
-    const int c = counts[it];
-    if (c > best) {
-      best = c;
-      win = it;
-      const double w = (double)c / (double)n;
-      double p_no_outliers = 1.0 - w * w;
-      p_no_outliers = fmax(DBL_EPSILON, p_no_outliers);
-      p_no_outliers = fmin(1.0 - DBL_EPSILON, p_no_outliers);
-      k = log_one_minus_p / log(p_no_outliers);
-    }
-    ++it;
-    if (it > max_iterations) break;
+    if (!wk.next(hyps[wk.it].draw, fail_at)) break;
+    if (!wk.step(counts[wk.it], n, max_iterations, log_one_minus_p, LnModel::ratio_power)) break;
   }
-  if (status == LN_OK && win < 0) status = LN_FAILED;
+  const int win = wk.win;
+  const int status = (wk.status == SAC_OK && win < 0) ? SAC_FAILED : wk.status;
   R->status = status;
-  R->draws = draws;
-  R->iterations = it;
+  R->draws = wk.draws;
+  R->iterations = wk.it;
   R->i0 = R->i1 = -1;
   R->n_inliers = R->n_cluster = R->emitted = 0;
   R->chosen = -1;
   for (int a = 0; a < 3; a++) { R->p0[a] = 0.f; R->dir[a] = 0.f; R->A[a] = 0.0; R->B[a] = 0.0; }
   R->line[0] = R->line[1] = R->d[0] = R->d[1] = 0.0;
   R->mean = R->sigma = R->maxe = R->mine = 0.0;
-  if (status == LN_OK) {
+  if (status == SAC_OK) {
     R->i0 = hyps[win].i0;
     R->i1 = hyps[win].i1;
     for (int a = 0; a < 3; a++) { R->p0[a] = hyps[win].p0[a]; R->dir[a] = hyps[win].dir[a]; }
@@ -237,23 +149,15 @@ __global__ __launch_bounds__(kBlock) void ln_flag_kernel(const float4* __restric
                                                          const double thr2, unsigned char* __restrict__ flags) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  flags[i] = (R->status == LN_OK && ln_is_inlier(pts[i], R->p0[0], R->p0[1], R->p0[2], R->dir[0], R->dir[1], R->dir[2], order, thr2)) ? 1 : 0;
+  flags[i] = (R->status == SAC_OK && ln_is_inlier(pts[i], R->p0[0], R->p0[1], R->p0[2], R->dir[0], R->dir[1], R->dir[2], order, thr2)) ? 1 : 0;
 }
 
 // pf_scatter_kernel that writes the point's position into the fourth float
 __global__ __launch_bounds__(kBlock) void ln_scatter_index_kernel(const float4* __restrict__ in, const unsigned char* __restrict__ flags, const int n,
                                                                   const int* __restrict__ blk, float4* __restrict__ out) {
-  __shared__ int s_w[kBlock / kWave];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  const bool f = i < n && flags[i] != 0;
-  const unsigned long long m = __ballot(f);
-  if (lane == 0) s_w[wv] = __popcll(m);
-  __syncthreads();
-  if (!f) return;
-  int off = blk[blockIdx.x];
-  for (int w = 0; w < wv; w++) off += s_w[w];
-  off += __popcll(m & ((1ull << lane) - 1ull));
+  int off;
+  if (!compact_slot(flags, i, n, blk, &off)) return;
   float4 p = in[i];
   p.w = __int_as_float(i);
   out[off] = p;   // off < number of flagged points <= n: `out` holds n points
@@ -269,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void ln_refit_kernel(const float4* __restri
   __shared__ float s_c[3];
   const int m = cnt[0];
   float px = R->p0[0], py = R->p0[1], vx = R->dir[0], vy = R->dir[1];
-  if (m > 2 && R->status == LN_OK) {
+  if (m > 2 && R->status == SAC_OK) {
     float cx = 0.f, cy = 0.f, cz = 0.f;
     for (int base = 0; base < m; base += kBlock) {
       const int j = base + threadIdx.x;
@@ -422,14 +326,14 @@ __global__ __launch_bounds__(kBlock) void ln_component_kernel(const float4* __re
 }
 
 // the biggest component of at most max_cluster members; ties to the one that holds the lowest position (one workgroup)
-__global__ __launch_bounds__(kLnOneBlock) void ln_pick_kernel(const int* __restrict__ label, const int* __restrict__ csize, const int* __restrict__ cminpos,
+__global__ __launch_bounds__(kLnPickBlock) void ln_pick_kernel(const int* __restrict__ label, const int* __restrict__ csize, const int* __restrict__ cminpos,
                                                               const int* __restrict__ cnt, const int max_cluster, LnRound* __restrict__ R) {
   __shared__ unsigned long long s_best;
   if (threadIdx.x == 0) s_best = 0ull;
   __syncthreads();
   const int m = cnt[0];
   unsigned long long best = 0ull;
-  for (int q = threadIdx.x; q < m; q += kLnOneBlock) {
+  for (int q = threadIdx.x; q < m; q += kLnPickBlock) {
     if (label[q] != q) continue;
     const int sz = csize[q];
     if (sz < 1 || sz > max_cluster) continue;
@@ -441,7 +345,7 @@ __global__ __launch_bounds__(kLnOneBlock) void ln_pick_kernel(const int* __restr
   const unsigned long long top = s_best;
   if (threadIdx.x == 0 && top == 0ull) R->chosen = -1;
   if (top == 0ull) return;
-  for (int q = threadIdx.x; q < m; q += kLnOneBlock) {
+  for (int q = threadIdx.x; q < m; q += kLnPickBlock) {
     if (label[q] != q) continue;
     const int sz = csize[q];
     if (sz < 1 || sz > max_cluster) continue;
@@ -564,8 +468,6 @@ __global__ __launch_bounds__(kBlock) void ln_keep_kernel(const unsigned char* __
 // ================================================================================================ host side
 namespace {
 
-inline unsigned ln_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 struct LnBack {   // what comes back once per round
   LnRound r;
   int cnt[4];
@@ -577,31 +479,9 @@ static_assert(sizeof(LnBack) <= kLnDrawOffset, "the read-back block must fit in 
 template <class Scatter>
 void ln_compact(dgs_handle* h, int64_t n, const unsigned char* flags, int slot, Scatter scatter) {
   LnScratch& ln = h->ln;
-  const unsigned nb = ln_blocks(n);
-  hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, flags, (int)n, ln.blk.ptr);
-  hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kLnOneBlock), 0, h->stream, ln.blk.ptr, (int)nb, ln.cnt.ptr + slot);
-  scatter(nb);
+  compact_offsets(h->stream, flags, n, ln.blk.ptr, ln.cnt.ptr + slot);
+  scatter(compact_blocks(n));
   ln.counts4[0] += 3;
-}
-
-// the round's draw list: drawIndexSample on a fresh identity permutation of n entries, D times; -> pairs in `out`
-void ln_draws(LnScratch& ln, const uint32_t* raw, int64_t n, int D, int* out) {
-  std::vector<int>& s = ln.perm;
-  std::vector<int> touched;
-  touched.reserve((size_t)D * 2 + 2);
-  for (int d = 0; d < D; d++) {
-    const int a = (int)(raw[2 * d] % (uint32_t)n);
-    const int b = 1 + (int)(raw[2 * d + 1] % (uint32_t)(n - 1));
-    std::swap(s[0], s[a]);
-    std::swap(s[1], s[b]);
-    touched.push_back(a);
-    touched.push_back(b);
-    out[2 * d] = s[0];
-    out[2 * d + 1] = s[1];
-  }
-  s[0] = 0;
-  s[1] = 1;
-  for (int t : touched) s[t] = t;
 }
 
 int ln_reserve(dgs_handle* h, int64_t n, int max_hyp) {
@@ -610,11 +490,11 @@ int ln_reserve(dgs_handle* h, int64_t n, int max_hyp) {
   for (DevBuf<float4>* b : {&ln.a, &ln.b, &ln.inl, &ln.clu, &ln.sorted}) DGS_HIP_TRY(h, b->reserve(m));
   DGS_HIP_TRY(h, ln.flags.reserve(m));
   DGS_HIP_TRY(h, ln.cflags.reserve(m));
-  DGS_HIP_TRY(h, ln.blk.reserve(ln_blocks(m)));
+  DGS_HIP_TRY(h, ln.blk.reserve(compact_blocks(m)));
   DGS_HIP_TRY(h, ln.cnt.reserve(4));
   DGS_HIP_TRY(h, ln.hyps.reserve((size_t)max_hyp));
-  DGS_HIP_TRY(h, ln.counts.reserve((size_t)max_hyp));
-  DGS_HIP_TRY(h, ln.meta.reserve(4));
+  DGS_HIP_TRY(h, ln.sac.counts.reserve((size_t)max_hyp));
+  DGS_HIP_TRY(h, ln.sac.meta.reserve(4));
   DGS_HIP_TRY(h, ln.round.reserve(1));
   for (DevBuf<uint32_t>* b : {&ln.keys, &ln.keys_alt, &ln.vals, &ln.vals_alt}) DGS_HIP_TRY(h, b->reserve(m));
   DGS_HIP_TRY(h, ln.sproj.reserve(m));
@@ -627,19 +507,22 @@ int ln_reserve(dgs_handle* h, int64_t n, int max_hyp) {
 int ln_round(dgs_handle* h, const dgs_line_extraction_params& p, const float4* cur, float4* next, int64_t n, const uint32_t* raw, int D, int max_hyp,
              LnBack* back) {
   LnScratch& ln = h->ln;
-  const unsigned nb = ln_blocks(n);
+  SacScratch& sac = ln.sac;
+  const unsigned nb = compact_blocks(n);
   const double thr2 = (double)p.sac_distance_threshold * (double)p.sac_distance_threshold;
   const double tol2 = (double)p.cluster_tolerance * (double)p.cluster_tolerance;
-  DGS_HIP_TRY(h, ln.draws.reserve((size_t)D * 2));
+  DGS_HIP_TRY(h, sac.draws.reserve((size_t)D * 2));
   if (ensure_pinned(h, kLnDrawOffset + (size_t)D * 2 * sizeof(int)) != DGS_OK) return DGS_ERR_HIP;
   int* hd = reinterpret_cast<int*>(static_cast<char*>(h->pinned) + kLnDrawOffset);
-  ln_draws(ln, raw, n, D, hd);
-  DGS_HIP_TRY(h, hipMemcpyAsync(ln.draws.ptr, hd, (size_t)D * 2 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(ln_prepare_kernel, dim3(1), dim3(kLnOneBlock), 0, h->stream, cur, (int)n, ln.draws.ptr, D, p.sample_good_any_axis ? 1 : 0, max_hyp,
-                     ln.hyps.ptr, ln.counts.ptr, ln.meta.ptr);
-  hipLaunchKernelGGL(ln_score_kernel, dim3((unsigned)((n + kLnTile - 1) / kLnTile), (unsigned)((max_hyp + kLnHypChunk - 1) / kLnHypChunk)), dim3(kBlock), 0,
-                     h->stream, cur, (int)n, ln.hyps.ptr, ln.meta.ptr, max_hyp, p.sqnorm_order, thr2, ln.counts.ptr);
-  hipLaunchKernelGGL(ln_walk_kernel, dim3(1), dim3(kWave), 0, h->stream, ln.hyps.ptr, ln.counts.ptr, ln.meta.ptr, (int)n, D, max_hyp, p.max_iterations,
+  sac_draws<2>(sac.perm, raw, n, D, hd);
+  DGS_HIP_TRY(h, hipMemcpyAsync(sac.draws.ptr, hd, (size_t)D * 2 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const LnModel::Params prm{p.sample_good_any_axis ? 1 : 0, p.sqnorm_order, thr2};
+  hipLaunchKernelGGL(sac_prepare_kernel<LnModel>, dim3(1), dim3(kSacPrepareBlock), 0, h->stream, cur, (int)n, sac.draws.ptr, D, prm, max_hyp,
+                     ln.hyps.ptr, sac.counts.ptr, sac.meta.ptr);
+  hipLaunchKernelGGL((sac_score_kernel<LnModel, kLnHypChunk>),
+                     dim3((unsigned)((n + kSacTile - 1) / kSacTile), (unsigned)((max_hyp + kLnHypChunk - 1) / kLnHypChunk)), dim3(kBlock), 0, h->stream, cur,
+                     (int)n, ln.hyps.ptr, sac.meta.ptr, max_hyp, 0, max_hyp, prm, sac.counts.ptr);
+  hipLaunchKernelGGL(ln_walk_kernel, dim3(1), dim3(kWave), 0, h->stream, ln.hyps.ptr, sac.counts.ptr, sac.meta.ptr, (int)n, D, max_hyp, p.max_iterations,
                      std::log(1.0 - 0.99), ln.round.ptr);
   hipLaunchKernelGGL(ln_flag_kernel, dim3(nb), dim3(kBlock), 0, h->stream, cur, (int)n, ln.round.ptr, p.sqnorm_order, thr2, ln.flags.ptr);
   ln.counts4[0] += 4;
@@ -661,7 +544,7 @@ int ln_round(dgs_handle* h, const dgs_line_extraction_params& p, const float4* c
                      p.cluster_inclusive ? 1 : 0, ln.parent.ptr);
   hipLaunchKernelGGL(ln_component_kernel, dim3(nb), dim3(kBlock), 0, h->stream, ln.sorted.ptr, ln.cnt.ptr, ln.parent.ptr, label, ln.csize.ptr,
                      ln.cminpos.ptr);
-  hipLaunchKernelGGL(ln_pick_kernel, dim3(1), dim3(kLnOneBlock), 0, h->stream, label, ln.csize.ptr, ln.cminpos.ptr, ln.cnt.ptr, p.max_cluster_size,
+  hipLaunchKernelGGL(ln_pick_kernel, dim3(1), dim3(kLnPickBlock), 0, h->stream, label, ln.csize.ptr, ln.cminpos.ptr, ln.cnt.ptr, p.max_cluster_size,
                      ln.round.ptr);
   hipLaunchKernelGGL(ln_cluster_flag_kernel, dim3(nb), dim3(kBlock), 0, h->stream, ln.sorted.ptr, label, ln.cnt.ptr, (int)n, ln.round.ptr, ln.cflags.ptr);
   ln.counts4[0] += 7;
@@ -726,11 +609,7 @@ int ln_extract(dgs_handle* h, const dgs_line_extraction_params& p, const float* 
       DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
       ln.counts4[1] += 1;
     }
-    if ((int64_t)ln.perm.size() < n) {
-      const size_t old = ln.perm.size();
-      ln.perm.resize((size_t)n);
-      for (size_t i = old; i < (size_t)n; i++) ln.perm[i] = (int)i;
-    }
+    sac_grow_perm(ln.sac.perm, n);
   }
   float4* cur = ln.a.ptr;
   float4* next = ln.b.ptr;
@@ -745,35 +624,30 @@ int ln_extract(dgs_handle* h, const dgs_line_extraction_params& p, const float* 
       ln.rounds.push_back(rec);
       break;
     }
-    int64_t D = std::min<int64_t>(avail_draws, (int64_t)max_hyp + kLnDrawSlack);
+    SacDrawPlan plan(avail_draws, max_hyp, kLnBadRun);
     LnBack back{};
     bool exhausted = false;
     for (;;) {
+      if (plan.empty()) { exhausted = true; break; }
       const uint32_t* raw = rng_raw;
-      if (!rng_raw) {
-        if ((int64_t)ln.mt_raw.size() < 2 * D) {   // boost::mt19937(12345)() >> 1 from the seed on: every round restarts there
-          std::mt19937 gen(12345u);
-          ln.mt_raw.resize((size_t)(2 * D));
-          for (uint32_t& v : ln.mt_raw) v = (uint32_t)gen() >> 1;
-        }
-        raw = ln.mt_raw.data();
+      if (!rng_raw) {   // every round restarts the generator at the seed
+        sac_grow_mt(ln.sac.mt_raw, 2 * plan.D);
+        raw = ln.sac.mt_raw.data();
       }
-      if (D < 1) { exhausted = true; break; }
-      if (int rc = ln_round(h, p, cur, next, n, raw, (int)D, max_hyp, &back)) return rc;
-      if (back.r.status != LN_NEED_DRAWS) break;
-      if (D >= avail_draws) { exhausted = true; break; }
-      D = std::min<int64_t>(avail_draws, std::min<int64_t>(D * 4, (int64_t)max_hyp * kLnBadRun + kLnBadRun));
+      if (int rc = ln_round(h, p, cur, next, n, raw, (int)plan.D, max_hyp, &back)) return rc;
+      if (back.r.status != SAC_NEED_DRAWS) break;
+      if (!plan.grow()) { exhausted = true; break; }
     }
     if (exhausted) {
       status = DGS_LE_RNG_EXHAUSTED;
-      rec.draws = (int32_t)std::max<int64_t>(D, 0);
+      rec.draws = (int32_t)std::max<int64_t>(plan.D, 0);
       rec.iterations = back.r.iterations;
       ln.rounds.push_back(rec);
       break;
     }
     rec.draws = back.r.draws;
     rec.iterations = back.r.iterations;
-    if (back.r.status == LN_FAILED) {
+    if (back.r.status == SAC_FAILED) {
       status = DGS_LE_RANSAC_FAILED;
       ln.rounds.push_back(rec);
       break;
@@ -816,8 +690,8 @@ int ln_extract(dgs_handle* h, const dgs_line_extraction_params& p, const float* 
 void line_extraction_release(dgs_handle* h) {
   LnScratch& ln = h->ln;
   for (DevBuf<float4>* b : {&ln.a, &ln.b, &ln.inl, &ln.clu, &ln.sorted}) b->release();
-  ln.flags.release(); ln.cflags.release(); ln.blk.release(); ln.cnt.release(); ln.draws.release(); ln.hyps.release(); ln.counts.release();
-  ln.meta.release(); ln.round.release(); ln.keys.release(); ln.keys_alt.release(); ln.vals.release(); ln.vals_alt.release(); ln.sproj.release();
+  ln.flags.release(); ln.cflags.release(); ln.blk.release(); ln.cnt.release(); ln.sac.release(); ln.hyps.release();
+  ln.round.release(); ln.keys.release(); ln.keys_alt.release(); ln.vals.release(); ln.vals_alt.release(); ln.sproj.release();
   ln.parent.release(); ln.csize.release(); ln.cminpos.release(); ln.temp.release();
   ln.rounds.clear(); ln.inlier_lists.clear(); ln.cluster_lists.clear();
 }

@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "compact.h"
 #include "eigen33.h"
 #include "handle.h"
 #include "nn_group.h"
@@ -34,7 +35,7 @@ namespace dgs {
 
 constexpr int kPfNormalK = 10;             // normal_filtering: ne.setKSearch(10) (:227)
 constexpr float kPfNormalThresh = 0.2f;    // normal_filter_thresh (:235)
-constexpr int kPfScanBlock = 1024;
+constexpr int kPfStatsBlock = 1024;        // pf_sor_stats_kernel: one workgroup
 
 // ================================================================================================ stable compaction
 __global__ __launch_bounds__(kBlock) void pf_count_kernel(const unsigned char* __restrict__ flags, const int n, int* __restrict__ blk) {
@@ -54,13 +55,13 @@ __global__ __launch_bounds__(kBlock) void pf_count_kernel(const unsigned char* _
 
 // One workgroup: exclusive scan of the nb workgroup counts in place, total -> *total.  Chunks of 1024 in order, so the result is the
 // same whatever the hardware schedule.
-__global__ __launch_bounds__(kPfScanBlock) void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restrict__ total) {
-  __shared__ int s_w[kPfScanBlock / kWave];
+__global__ __launch_bounds__(kCompactScanBlock) void pf_scan_kernel(int* __restrict__ blk, const int nb, int* __restrict__ total) {
+  __shared__ int s_w[kCompactScanBlock / kWave];
   __shared__ int s_carry;
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   if (threadIdx.x == 0) s_carry = 0;
   __syncthreads();
-  for (int base = 0; base < nb; base += kPfScanBlock) {
+  for (int base = 0; base < nb; base += kCompactScanBlock) {
     const int i = base + threadIdx.x;
     const int v = i < nb ? blk[i] : 0;
     int x = v;
@@ -72,20 +73,20 @@ __global__ __launch_bounds__(kPfScanBlock) void pf_scan_kernel(int* __restrict__
     if (lane == kWave - 1) s_w[wv] = x;
     __syncthreads();
     if (wv == 0) {
-      int w = lane < kPfScanBlock / kWave ? s_w[lane] : 0;
+      int w = lane < kCompactScanBlock / kWave ? s_w[lane] : 0;
 #pragma unroll
-      for (int o = 1; o < kPfScanBlock / kWave; o <<= 1) {
+      for (int o = 1; o < kCompactScanBlock / kWave; o <<= 1) {
         const int y = __shfl_up(w, o, kWave);
         if (lane >= o) w += y;
       }
-      if (lane < kPfScanBlock / kWave) s_w[lane] = w;
+      if (lane < kCompactScanBlock / kWave) s_w[lane] = w;
     }
     __syncthreads();
     const int carry = s_carry;
     const int before = carry + (wv ? s_w[wv - 1] : 0) + x - v;
     if (i < nb) blk[i] = before;
     __syncthreads();
-    if (threadIdx.x == kPfScanBlock - 1) s_carry = before + v;
+    if (threadIdx.x == kCompactScanBlock - 1) s_carry = before + v;
     __syncthreads();
   }
   if (threadIdx.x == 0) *total = s_carry;
@@ -93,17 +94,9 @@ __global__ __launch_bounds__(kPfScanBlock) void pf_scan_kernel(int* __restrict__
 
 __global__ __launch_bounds__(kBlock) void pf_scatter_kernel(const float4* __restrict__ in, const unsigned char* __restrict__ flags, const int n,
                                                             const int* __restrict__ blk, float4* __restrict__ out, const int flatten) {
-  __shared__ int s_w[kBlock / kWave];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  const bool f = i < n && flags[i] != 0;
-  const unsigned long long m = __ballot(f);
-  if (lane == 0) s_w[wv] = __popcll(m);
-  __syncthreads();
-  if (!f) return;
-  int off = blk[blockIdx.x];
-  for (int w = 0; w < wv; w++) off += s_w[w];
-  off += __popcll(m & ((1ull << lane) - 1ull));
+  int off;
+  if (!compact_slot(flags, i, n, blk, &off)) return;
   float4 p = in[i];
   if (flatten) p.z = 0.f;   // flatten (:181): point.z = 0
   out[off] = p;             // off < number of kept points <= n: `out` holds n points
@@ -202,17 +195,9 @@ __global__ __launch_bounds__(kBlock) void pf_head_flag_kernel(const float4* __re
 // pf_scatter_kernel over the raw cloud: the kept point is recomputed from the raw one and written at its compacted place
 __global__ __launch_bounds__(kBlock) void pf_head_scatter_kernel(const float4* __restrict__ in, const unsigned char* __restrict__ flags, const long long n,
                                                                  const PfHead hd, const int* __restrict__ blk, float4* __restrict__ out) {
-  __shared__ int s_w[kBlock / kWave];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-  const bool f = i < n && flags[i] != 0;
-  const unsigned long long m = __ballot(f);
-  if (lane == 0) s_w[wv] = __popcll(m);
-  __syncthreads();
-  if (!f) return;
-  int off = blk[blockIdx.x];
-  for (int w = 0; w < wv; w++) off += s_w[w];
-  off += __popcll(m & ((1ull << lane) - 1ull));
+  int off;
+  if (!compact_slot(flags, i, n, blk, &off)) return;
   out[off] = pf_head_point(in[i], i, n, hd);   // off < number of kept points <= n: `out` holds n points
 }
 
@@ -309,12 +294,12 @@ __global__ __launch_bounds__(kBlock) void pf_sor_distance_kernel(const BvhView b
 
 // mean / stddev / threshold: sum and sq_sum as double sums (sq_sum adds the float product d*d), reduced in a fixed order in one
 // workgroup; variance = (sq_sum - sum*sum/n) / (n-1), threshold = mean + mul * sqrt(variance).
-__global__ __launch_bounds__(kPfScanBlock) void pf_sor_stats_kernel(const float* __restrict__ mean_d, const int n, const double mul,
+__global__ __launch_bounds__(kPfStatsBlock) void pf_sor_stats_kernel(const float* __restrict__ mean_d, const int n, const double mul,
                                                                     double* __restrict__ stats) {
 #pragma clang fp contract(off)
-  __shared__ double s_s[kPfScanBlock], s_q[kPfScanBlock];
+  __shared__ double s_s[kPfStatsBlock], s_q[kPfStatsBlock];
   double s = 0.0, q = 0.0;
-  for (int i = threadIdx.x; i < n; i += kPfScanBlock) {
+  for (int i = threadIdx.x; i < n; i += kPfStatsBlock) {
     const float d = mean_d[i];
     s += (double)d;
     q += (double)mul_rn(d, d);
@@ -322,7 +307,7 @@ __global__ __launch_bounds__(kPfScanBlock) void pf_sor_stats_kernel(const float*
   s_s[threadIdx.x] = s;
   s_q[threadIdx.x] = q;
   __syncthreads();
-  for (int h = kPfScanBlock / 2; h > 0; h >>= 1) {
+  for (int h = kPfStatsBlock / 2; h > 0; h >>= 1) {
     if ((int)threadIdx.x < h) {
       s_s[threadIdx.x] += s_s[threadIdx.x + h];
       s_q[threadIdx.x] += s_q[threadIdx.x + h];
@@ -431,31 +416,14 @@ __global__ __launch_bounds__(kBlock) void pf_normal_kernel(const BvhView b, cons
 // ================================================================================================ host side
 namespace {
 
-inline unsigned pf_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 // compact `in` (n points) by pf.flags into `out` (reserved for n points); *m = kept points (read back: the host waits here).
 // With a head, `in` is the raw cloud and the scatter writes the deskewed, transformed point.
 int pf_compact(dgs_handle* h, const float4* in, int64_t n, DevBuf<float4>& out, bool flatten, int64_t* m, const PfHead* head = nullptr) {
   PfScratch& pf = h->pf;
-  *m = 0;
-  if (n == 0) return DGS_OK;
-  const unsigned nb = pf_blocks(n);
-  DGS_HIP_TRY(h, out.reserve((size_t)n));
-  DGS_HIP_TRY(h, pf.blk.reserve(nb));
-  DGS_HIP_TRY(h, pf.cnt.reserve(4));
-  hipLaunchKernelGGL(pf_count_kernel, dim3(nb), dim3(kBlock), 0, h->stream, pf.flags.ptr, (int)n, pf.blk.ptr);
-  hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kPfScanBlock), 0, h->stream, pf.blk.ptr, (int)nb, pf.cnt.ptr);
-  if (head)
+  if (!head) return compact_points(h, in, pf.flags.ptr, n, pf.blk, pf.cnt, out, flatten, m);
+  return compact_scatter(h, pf.flags.ptr, n, pf.blk, pf.cnt, out, m, [&](unsigned nb) {
     hipLaunchKernelGGL(pf_head_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, in, pf.flags.ptr, (long long)n, *head, pf.blk.ptr, out.ptr);
-  else
-    hipLaunchKernelGGL(pf_scatter_kernel, dim3(nb), dim3(kBlock), 0, h->stream, in, pf.flags.ptr, (int)n, pf.blk.ptr, out.ptr, flatten ? 1 : 0);
-  DGS_HIP_TRY(h, hipGetLastError());
-  if (ensure_pinned(h, 4096) != DGS_OK) return DGS_ERR_HIP;
-  int* hc = reinterpret_cast<int*>(h->pinned);
-  DGS_HIP_TRY(h, hipMemcpyAsync(hc, pf.cnt.ptr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  *m = hc[0];
-  return DGS_OK;
+  });
 }
 
 int pf_reserve_flags(dgs_handle* h, int64_t n) {
@@ -477,7 +445,7 @@ int pf_distance(dgs_handle* h, const float4* in, int64_t n, double near_t, doubl
   *m = 0;
   if (n == 0) return DGS_OK;
   if (int rc = pf_reserve_flags(h, n)) return rc;
-  hipLaunchKernelGGL(pf_distance_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, in, (int)n, near_t, far_t, h->pf.flags.ptr);
+  hipLaunchKernelGGL(pf_distance_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, in, (int)n, near_t, far_t, h->pf.flags.ptr);
   return pf_compact(h, in, n, out, false, m);
 }
 
@@ -486,7 +454,7 @@ int pf_head_distance(dgs_handle* h, const float4* in, int64_t n, const PfHead& h
   *m = 0;
   if (n == 0) return DGS_OK;
   if (int rc = pf_reserve_flags(h, n)) return rc;
-  hipLaunchKernelGGL(pf_head_flag_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, in, (long long)n, head, near_t, far_t, h->pf.flags.ptr);
+  hipLaunchKernelGGL(pf_head_flag_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, in, (long long)n, head, near_t, far_t, h->pf.flags.ptr);
   return pf_compact(h, in, n, out, false, m, &head);
 }
 
@@ -502,7 +470,7 @@ int pf_radius(dgs_handle* h, const float4* in, int64_t n, double radius, int min
   if (int rc = pf_reserve_flags(h, n)) return rc;
   if (int rc = pf_knn(h, in, n, k)) return rc;
   const CloudState& c = h->pf.cloud;
-  hipLaunchKernelGGL(pf_radius_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, h->pf.nbr.ptr,
+  hipLaunchKernelGGL(pf_radius_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, h->pf.nbr.ptr,
                      radius * radius, inclusive, h->pf.flags.ptr);
   return pf_compact(h, in, n, out, false, m);
 }
@@ -526,10 +494,10 @@ int pf_statistical(dgs_handle* h, const float4* in, int64_t n, int mean_k, doubl
   const int k = mean_k + 1;
   if (int rc = pf_knn(h, in, n, k)) return rc;
   const CloudState& c = pf.cloud;
-  hipLaunchKernelGGL(pf_sor_distance_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, pf.nbr.ptr,
+  hipLaunchKernelGGL(pf_sor_distance_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, pf.nbr.ptr,
                      sqrt_float, pf.mean_d.ptr);
-  hipLaunchKernelGGL(pf_sor_stats_kernel, dim3(1), dim3(kPfScanBlock), 0, h->stream, pf.mean_d.ptr, (int)n, mul, pf.stats.ptr);
-  hipLaunchKernelGGL(pf_sor_flag_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, pf.mean_d.ptr, (int)n, pf.stats.ptr, pf.flags.ptr);
+  hipLaunchKernelGGL(pf_sor_stats_kernel, dim3(1), dim3(kPfStatsBlock), 0, h->stream, pf.mean_d.ptr, (int)n, mul, pf.stats.ptr);
+  hipLaunchKernelGGL(pf_sor_flag_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, pf.mean_d.ptr, (int)n, pf.stats.ptr, pf.flags.ptr);
   pf.stat_n = n;
   return pf_compact(h, in, n, out, false, m);
 }
@@ -546,7 +514,7 @@ int pf_normal(dgs_handle* h, const float4* in, int64_t n, const double* lidar, D
   if (int rc = pf_knn(h, in, n, k)) return rc;
   const CloudState& c = pf.cloud;
   // ne.setViewPoint(float, float, float)
-  hipLaunchKernelGGL(pf_normal_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, pf.nbr.ptr,
+  hipLaunchKernelGGL(pf_normal_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, make_bvh_view(c.bvh), c.pts.ptr, (int)n, k, pf.nbr.ptr,
                      (float)lidar[0], (float)lidar[1], (float)lidar[2], pf.flags.ptr, pf.normals.ptr, pf.cov9.ptr);
   pf.normal_n = n;
   return pf_compact(h, in, n, out, flatten, m);
@@ -660,7 +628,7 @@ int pf_chain(dgs_handle* h, const dgs_prefilter_params* p, const PfHead* head, c
   int64_t n4 = 0, n5 = 0;
   if (rc == DGS_OK && n3 > 0) {
     if ((rc = pf_reserve_flags(h, n3)) == DGS_OK) {
-      hipLaunchKernelGGL(pf_height_kernel, dim3(pf_blocks(n3)), dim3(kBlock), 0, h->stream, s3, (int)n3, lidar[2], pf.flags.ptr);
+      hipLaunchKernelGGL(pf_height_kernel, dim3(compact_blocks(n3)), dim3(kBlock), 0, h->stream, s3, (int)n3, lidar[2], pf.flags.ptr);
       rc = pf_compact(h, s3, n3, pf.d, false, &n4);
     }
   }
@@ -747,7 +715,7 @@ int dgs_prefilter_deskew(dgs_handle* h, const dgs_prefilter_scan_params* sp, con
   int rc = pf_input(h, in_xyz16, n, in_on_device, &in);
   if (rc == DGS_OK && h->pf.a.reserve((size_t)n) != hipSuccess) { h->err = "hipMalloc failed"; rc = DGS_ERR_HIP; }
   if (rc == DGS_OK) {
-    hipLaunchKernelGGL(pf_head_apply_kernel, dim3(pf_blocks(n)), dim3(kBlock), 0, h->stream, in, (long long)n, head, h->pf.a.ptr);
+    hipLaunchKernelGGL(pf_head_apply_kernel, dim3(compact_blocks(n)), dim3(kBlock), 0, h->stream, in, (long long)n, head, h->pf.a.ptr);
     *n_out = n;
     rc = pf_output(h, h->pf.a.ptr, n, out_xyz16, cap, out_on_device);
   }

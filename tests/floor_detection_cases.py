@@ -7,8 +7,8 @@ import floor_detection_reference as R
 from delta_graph_slam_amd import synth
 
 F = np.float32
-TILE = 1024                 # points per workgroup of fd_score_kernel
-PREPARE_CHUNK = 1024        # draws per pass of fd_prepare_kernel
+TILE = 1024                 # points per workgroup of sac_score_kernel (kSacTile)
+PREPARE_CHUNK = 1024        # draws per pass of sac_prepare_kernel (kSacPrepareBlock)
 CHUNK_FIRST, CHUNK = 64, 512
 SENSOR_Z = 1.73             # synth.street_scan's sensor height over the street
 

@@ -1,5 +1,5 @@
 """Scenes that put the line extraction (delta_graph_slam_amd/csrc/line_extraction.hip) at the edges of its kernels: the hypothesis chunks
-and point tiles of ln_score_kernel, the carry of ln_prepare_kernel across its 1024-draw chunks, the regrowth of the draw list, the
+and point tiles of sac_score_kernel<LnModel, 512>, the carry of sac_prepare_kernel<LnModel> across its 1024-draw chunks, the regrowth of the draw list, the
 windowed union-find clustering at its tolerance, ln_pick_kernel's choice, the 256-term staging of the refit and the statistics, the
 strict emission thresholds and the host loop at its smallest inputs.
 
@@ -17,7 +17,7 @@ import numpy as np
 import line_extraction_reference as R
 
 F = np.float32
-TILE, CHUNK, PREPARE, BLOCK = 1024, 512, 1024, 256     # kLnTile, kLnHypChunk, kLnOneBlock, kBlock of line_extraction.hip
+TILE, CHUNK, PREPARE, BLOCK = 1024, 512, 1024, 256     # kSacTile, kLnHypChunk, kSacPrepareBlock, kBlock of sac.h / line_extraction.hip
 BAD_RUN, SLACK = 1000, 64                              # kLnBadRun, kLnDrawSlack
 
 
@@ -87,7 +87,7 @@ def on_line(t, origin=(0.0, 0.0), direction=(1.0, 0.0)):
 DIAG = (0.8, 0.6)
 DEG30 = (float(np.cos(np.pi / 6)), 0.5)
 
-# ==================================================================================================== chunks and tiles of ln_score_kernel
+# ==================================================================================================== chunks and tiles of sac_score_kernel
 # Sparse clutter, uniform in +-40 m: with the threshold 0.1 a clutter hypothesis counts a handful of points, so k stays in the thousands
 # and the walk runs to max_iterations + 1.  Two planted lines hold every other count: the runner-up, 30 points on y = 10, at a low
 # rank, and the winner, 31 points on x = 15, at the rank the case names.  No clutter point lies within 0.5 of either (infinite) line, so
@@ -132,18 +132,18 @@ def _winner_case(n, seed, win_rank, run_rank, max_iterations, late, aims):
 
 def _chunk_rank(rank):
     return _winner_case(700, 1000 + rank, rank, 3, 600 if rank < 600 else 1200, 0,
-                        f"ln_score_kernel: the winner's count is s_cnt[{rank} - h0] of hypothesis chunk blockIdx.y = {rank // CHUNK}, and the walk reads "
+                        f"ln_round's sac_score_kernel<LnModel, 512>: the winner's count is s_cnt[{rank} - h0] of hypothesis chunk blockIdx.y = {rank // CHUNK}, and the walk reads "
                         f"counts[] up to max_iterations.")
 
 
 def _tile_tail(n):
     late = 1 if n > TILE else 2
     return _winner_case(n, 2000 + n, 5, 2, 40, late,
-                        f"ln_score_kernel: the winner leads the runner-up only through the last {late} point(s) of the cloud, which sit in the "
+                        f"ln_round's sac_score_kernel<LnModel, 512>: the winner leads the runner-up only through the last {late} point(s) of the cloud, which sit in the "
                         f"{'partial ' if n % TILE else ''}last tile (blockIdx.x = {(n - 1) // TILE}, ok[k] = i < n).")
 
 
-# ==================================================================================================== draw list: ln_prepare_kernel, regrowth
+# ==================================================================================================== draw list: sac_prepare_kernel, regrowth
 # One point repeated 30 times, eight points in general position and three collinear ones: a draw is bad exactly when both of its
 # indices are copies of the repeated point.  A pair of general points counts 2, the collinear pair 3.
 def _dup_scene(seed):
@@ -172,7 +172,7 @@ def _draw_case(seed, kinds, line_at, params, aims, plan):
 
 def _bad_run(length):
     kinds = [True] * 501 + [False] * length + [True] * (1600 - 501 - length)
-    aims = ("ln_prepare_kernel: a bad run that starts after 501 good draws and straddles draw 1024 -- s_last carries the last good draw "
+    aims = ("ln_round's sac_prepare_kernel<LnModel>: a bad run that starts after 501 good draws and straddles draw 1024 -- s_last carries the last good draw "
             f"across the chunk edge, and d - last == {BAD_RUN} ")
     if length == BAD_RUN - 1:
         return _draw_case(31, kinds, 1505, dict(max_iterations=520), aims + "is never true: the round goes on and the winner is drawn behind the run.",
@@ -354,7 +354,7 @@ def _host(name):
                     dict(status="RANSAC_FAILED", rounds=1, sample=(-1, -1), draws=0, iterations=0, launched=0))
     if name == "n2_min2":
         return Case(cloud_of([[1.0, 2.0], [1.5, 2.0]]), dict(min_cluster_size=2, line_length_threshold=0.25, max_iterations=20), None,
-                    "ln_draws: n = 2, `1 + raw % (n - 1)` has one choice; ln_refit_kernel keeps the sample's model.",
+                    "sac_draws<2>: n = 2, `1 + raw % (n - 1)` has one choice; ln_refit_kernel keeps the sample's model.",
                     dict(status="DONE", rounds=1, inliers=2, cluster=2, emitted=1, relaunches=0))
     xy = np.concatenate([on_line(0.2 * np.arange(25), (1.0, -3.0), DIAG), [[30.0, -20.0], [-25.0, 18.0], [12.0, 33.0], [-31.0, -7.0], [2.0, -29.0]]])
     return _pinned(xy, 95, 0, 24, dict(max_iterations=20, max_rounds=2), "ln_stats_kernel: `c < min_cluster` with c == min_cluster_size == 25.",
@@ -367,7 +367,7 @@ for _r in (511, 512, 513, 1023, 1024, 1100):
 for _n in (1023, 1024, 1025, 2049):
     _BUILDERS[f"tile_tail_{_n}"] = (_tile_tail, _n)
 _BUILDERS["chunk_and_tile"] = (lambda _: _winner_case(2049, 3000, 600, 3, 700, 1,
-                                                      "ln_score_kernel: grid (3, 2) -- the winner at rank 600 (blockIdx.y = 1) leads through index 2048 "
+                                                      "ln_round's sac_score_kernel<LnModel, 512>: grid (3, 2) -- the winner at rank 600 (blockIdx.y = 1) leads through index 2048 "
                                                       "(blockIdx.x = 2)."), None)
 _BUILDERS["bad_run_999_over_1024"] = (_bad_run, BAD_RUN - 1)
 _BUILDERS["bad_run_1000_over_1024"] = (_bad_run, BAD_RUN)

@@ -15,7 +15,7 @@ import numpy as np
 import prefilter_reference as R
 
 F = np.float32
-WAVE, BLOCK, CHUNK = 64, 256, 1024            # kWave, kBlock, kPfScanBlock of prefilter.hip
+WAVE, BLOCK, CHUNK = 64, 256, 1024            # kWave, kBlock of common.h, kCompactScanBlock of compact.h
 EDGE = CHUNK * BLOCK                          # 262,144 points: the first point of the scan's second chunk
 
 

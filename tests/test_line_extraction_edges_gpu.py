@@ -66,7 +66,7 @@ def test_a_used_handle_gives_the_bits_of_a_fresh_one(monkeypatch):
             ("n4099_it100", lib_cloud, lib_prm, None), ("chunk_and_tile again", big.cloud, big.params, big.raw)]
     used = Registration("NDT_OMP", device=0)
     for what, cloud, prm, raw in jobs:
-        ex = LineExtractor(dict(prm, record_lists=1), registration=used)      # ln.perm, mt_raw and every buffer are the handle's
+        ex = LineExtractor(dict(prm, record_lists=1), registration=used)      # ln.sac.perm, mt_raw and every buffer are the handle's
         got = _result(ex, ex.extract(cloud, rng_raw=raw))
         fresh, lines = G._extract(Registration("NDT_OMP", device=0), cloud, prm, raw)
         assert _same_result(got, _result(fresh, lines)), what
