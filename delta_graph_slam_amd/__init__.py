@@ -1,6 +1,6 @@
 """delta_graph_slam_amd -- MI355X-native scan registration (NDT / GICP) hot path."""
 
-__all__ = ["MapCloudGenerator", "LineExtractor", "LineScanMatcher", "BuildingOverlap", "FloorDetector"]
+__all__ = ["MapCloudGenerator", "LineExtractor", "LineScanMatcher", "BuildingOverlap", "FloorDetector", "BuildingClouds"]
 
 
 def __getattr__(name):   # resolved on first use: importing the package alone loads neither torch nor the HIP library
@@ -19,4 +19,7 @@ def __getattr__(name):   # resolved on first use: importing the package alone lo
     if name == "FloorDetector":
         from .floor_detection import FloorDetector
         return FloorDetector
+    if name == "BuildingClouds":
+        from .building_cloud import BuildingClouds
+        return BuildingClouds
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

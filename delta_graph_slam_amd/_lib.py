@@ -98,6 +98,11 @@ class FloorDetectionParams(C.Structure):
                 ("plane_dot_order", C.c_int32), ("hyp_chunk_first", C.c_int32), ("hyp_chunk", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BuildingCloudParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sample_step", C.c_float), ("sqnorm_order", C.c_int32), ("normalized_guard", C.c_int32),
+                ("transform_order", C.c_int32), ("max_points_per_line", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FloorDetectionTrace(C.Structure):
     _fields_ = [("n_clipped", C.c_int32), ("n_filtered", C.c_int32), ("draws", C.c_int32), ("hypotheses_scored", C.c_int32),
                 ("iterations", C.c_int32), ("chunks_launched", C.c_int32), ("winner_rank", C.c_int32), ("sample", C.c_int32 * 3),
@@ -203,6 +208,7 @@ SYMBOLS = [
     "dgs_floor_detection_params_init", "dgs_floor_detection", "dgs_floor_detection_get_filtered", "dgs_floor_detection_get_inliers",
     "dgs_floor_detection_get_trace", "dgs_floor_detection_get_clipped", "dgs_floor_detection_draws", "dgs_floor_detection_walk",
     "dgs_calc_fitness_score_batch_clouds", "dgs_cloud_build_indices", "dgs_fitness_batch_get_counts",
+    "dgs_building_cloud_params_init", "dgs_building_cloud_generate", "dgs_building_cloud_get", "dgs_building_cloud_get_counts",
 ]
 
 _libs = {}
@@ -364,5 +370,10 @@ def load(path=None):
     lib.dgs_floor_detection_get_clipped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
     lib.dgs_floor_detection_draws.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.dgs_floor_detection_walk.argtypes = [C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32)]
+    lib.dgs_building_cloud_params_init.argtypes = [P(BuildingCloudParams)]
+    lib.dgs_building_cloud_generate.argtypes = [C.c_void_p, P(BuildingCloudParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                P(C.c_int64)]
+    lib.dgs_building_cloud_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, P(C.c_int64), P(C.c_void_p)]
+    lib.dgs_building_cloud_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     _libs[path] = lib
     return lib

@@ -511,6 +511,7 @@ void dgs_destroy(dgs_handle* h) {
   building_overlap_release(h);
   floor_detection_release(h);
   fitness_batch_release(h);
+  building_cloud_release(h);
   h->gitems.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
   h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();

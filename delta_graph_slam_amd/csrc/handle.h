@@ -1,5 +1,6 @@
 // dgs_handle: per-registration-object state (one per pcl::Registration instance on the reference side).
 #pragma once
+#include "building_cloud.h"
 #include "common.h"
 #include "sac.h"
 
@@ -266,6 +267,21 @@ struct FbScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launches, host waits, edges, indices built, partial rows
 };
 
+// interpolate / buildPointCloud / getCloud over many lines (building_cloud.hip): the table of sample positions, kept across calls, and
+// scratch of its own; everything above is left untouched.
+struct BcScratch {
+  bc::StepTable steps;                 // the table on the host: the master copy, grown on demand
+  int64_t table_on_device = 0;         // entries of it that `table` holds
+  DevBuf<float> table;
+  DevBuf<unsigned char> in;            // one upload: header {error line, total}, first line per item, matrix per line, matrices, end points
+  DevBuf<float4> rec;                  // per line: a.x, a.y, dn.x, dn.y
+  DevBuf<int> cnt;                     // per line: points, scanned in place to the line's first point
+  DevBuf<int> item_off;                // first point per item, n_items + 1 entries
+  DevBuf<float4> out;                  // the last result
+  int64_t n_out = 0, n_items = -1;     // n_items < 0: no result to read
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -488,6 +504,9 @@ struct dgs_handle {
   // ---- batched calc_fitness_score between resident clouds (fitness_batch.hip): own buffers; everything above is left untouched
   dgs::FbScratch fb;
 
+  // ---- building clouds (building_cloud.hip): own buffers and the table of sample positions; everything above is left untouched
+  dgs::BcScratch bcl;
+
   dgs::Profiler prof;
 };
 
@@ -594,6 +613,8 @@ int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, 
 int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_range,
                          double* scores, int64_t* used);
 void fitness_batch_release(dgs_handle* h);
+// building_cloud.hip
+void building_cloud_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -994,6 +994,51 @@ int dgs_floor_detection_draws(int64_t n, const uint32_t* rng_raw, int64_t n_draw
 int dgs_floor_detection_walk(int64_t n, int32_t max_iterations, double probability, const int32_t* counts, int64_t n_counts,
                              int32_t* winner_out, int32_t* iterations_out, int32_t* open_out);
 
+/* ---- interpolate, BuildingTools::buildPointCloud and Building::getCloud on the device --------------------------------------------
+ * (src/hdl_graph_slam/ros_utils.cpp:146-165, building_tools.cpp:166-196, building.cpp:7-22; the call sites of
+ * apps/delta_graph_slam_nodelet.cpp:266-288, :327-336, :689-711, :751-757, :1184-1198).  Every line of every item is sampled into
+ * points a + i_k * normalized(b - a) with i_0 = 0, i_{k+1} = fl(i_k + sample_step), one point per i_k <= norm(b - a), z = 0, the fourth
+ * float 1; an item's points may then go through pcl::transformPointCloud(Matrix4f).  All float32, no FMA; semantics, kernels and the
+ * Eigen / PCL details recalled from upstream ([UPSTREAM-RECALL]): DESIGN.md 6m.  Each recalled detail is a field:
+ *   sqnorm_order:     dgs_prefilter_norm_order of squaredNorm's terms x², y², z² (the w term is 0, so orders 0 and 2 give the same bits).
+ *   normalized_guard: 1 = Eigen 3.3's normalized(): d / sqrt(n2) when n2 > 0, else d.  0 = the older form, which divides
+ *                     unconditionally: a zero-length line then gives one NaN point instead of one point at a.
+ *   transform_order:  dgs_floor_detection_params::transform_order, the same restatement of pcl::transformPointCloud.
+ * sample_step is upstream's 0.02f.  max_points_per_line ends the table of i_k (it also ends where i_{k+1} <= i_k); a line whose norm is
+ * +inf or exceeds the table's last entry is DGS_ERR_INVALID_ARGUMENT (upstream would not terminate, or would exhaust memory).
+ * Own buffers on the handle: registration, prefilter, map, line, overlap and floor state are untouched.  Additions only:
+ * DGS_ABI_VERSION is unchanged. */
+#define DGS_BC_TILE 1024                  /* output points per workgroup of the fill kernel */
+typedef struct dgs_building_cloud_params {
+  uint32_t struct_size;          /* sizeof(dgs_building_cloud_params), set by dgs_building_cloud_params_init */
+  float sample_step;             /* > 0 and finite */
+  int32_t sqnorm_order;          /* dgs_prefilter_norm_order */
+  int32_t normalized_guard;
+  int32_t transform_order;       /* 0 or 1 */
+  int32_t max_points_per_line;   /* >= 1 */
+  int32_t reserved;
+} dgs_building_cloud_params;
+/* Defaults: 0.02f, DGS_PF_NORM_PAIRS_XY_ZW, 1, 0, 1 << 20. */
+int dgs_building_cloud_params_init(dgs_building_cloud_params* params);
+/* lines: the lines of all n_items items back to back (point_a and point_b are read); line_offsets: n_items + 1 ascending offsets from
+ * 0.  transforms16 (nullable): 4 x 4 float matrices, COLUMN-major (Eigen's data()), 16 floats each; transform_index (nullable): per
+ * item the matrix its points go through, -1 for none.  With transforms16 and no transform_index every item takes matrix 0; without
+ * transforms16 no item is transformed and transform_index is not read.  The points come in item order, line order within an item and
+ * k ascending; *n_points is their number.  They stay on the handle until the next call: read them with dgs_building_cloud_get.
+ * n_items == 0 and items without lines are not errors.  A NaN norm gives no point.  On DGS_ERR_INVALID_ARGUMENT the message names
+ * the item and the line, nothing is produced and the handle stays usable.  Three launches whatever the sizes, one host wait. */
+int dgs_building_cloud_generate(dgs_handle* h, const dgs_building_cloud_params* params, const dgs_line_feature* lines,
+                                const int64_t* line_offsets, int64_t n_items, const float* transforms16, const int32_t* transform_index,
+                                int64_t* n_points);
+/* Copies the last result out: the points (host array, or device pointer with out_on_device; nullable with capacity 0) and the
+ * n_items + 1 point offsets of the items (a host array, nullable).  *n is always the full count; DGS_ERR_INVALID_ARGUMENT when it
+ * exceeds `capacity`.  device_ptr_out (nullable): the stage's own buffer on the device, valid until the next generate call. */
+int dgs_building_cloud_get(dgs_handle* h, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* point_offsets, int64_t* n,
+                           const float** device_ptr_out);
+/* Test hook.  counts8 of the last generate call: kernel launches, host waits, lines, points, entries of the step table, entries the
+ * call added to it, DGS_BC_TILE, items. */
+int dgs_building_cloud_get_counts(dgs_handle* h, int64_t* counts8);
+
 #ifdef __cplusplus
 }
 #endif
