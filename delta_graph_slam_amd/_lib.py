@@ -17,6 +17,7 @@ VGICP_SEARCH = {"DIRECT1": 0, "DIRECT7": 1, "DIRECT27": 2}
 NDT_SEARCH = {"KDTREE": 0, "DIRECT26": 1, "DIRECT7": 2, "DIRECT1": 3}
 NDT_ORDER = {"FAST": 0, "UPSTREAM": 1, "UPSTREAM_SEQUENTIAL": 2}
 GICP_REG = {"NONE": 0, "MIN_EIG": 1, "NORMALIZED_MIN_EIG": 2, "PLANE": 3, "FROBENIUS": 4}
+GICP_COV = {"SYM_EIG": 0, "JACOBI_SVD": 1, "UPSTREAM_ORDER": 2}   # dgs_gicp_cov_mode: dgs_params.gicp_cov_jacobi_svd
 K_NDT_DERIVATIVES, K_NDT_SOLVE, K_NDT_VOXEL_BUILD, K_NN_SEARCH, K_GICP_LINEARIZE, K_GICP_COVARIANCE, K_TRANSFORM = range(7)
 
 

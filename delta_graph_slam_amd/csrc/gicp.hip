@@ -1161,8 +1161,11 @@ static int ensure_covariance(dgs_handle* h, CloudState& c) {
   int rc = knn_lists(h, c, h->gconsts.k);
   if (rc) return rc;
   constexpr int kCovPerBlock = kCovPerWave * (kBlock / kWave);
-  hipLaunchKernelGGL(gicp_cov_from_knn_kernel, dim3((unsigned)(((int64_t)c.n + kCovPerBlock - 1) / kCovPerBlock)), dim3(kBlock), 0, h->stream, v, c.pts.ptr, (int)c.n,
-                     h->gconsts.k, h->gconsts.regularization | (h->prm.gicp_cov_jacobi_svd ? 0x100 : 0), h->knn_nbr.ptr, c.cov.ptr);
+  if (h->prm.gicp_cov_jacobi_svd == DGS_GICP_COV_UPSTREAM_ORDER)   // ordered lists, sequential sums, JacobiSVD: gicp_cov_ordered.hip
+    gicp_cov_upstream_order(h, v, c, h->gconsts.k, h->gconsts.regularization, h->knn_nbr.ptr);
+  else
+    hipLaunchKernelGGL(gicp_cov_from_knn_kernel, dim3((unsigned)(((int64_t)c.n + kCovPerBlock - 1) / kCovPerBlock)), dim3(kBlock), 0, h->stream, v, c.pts.ptr, (int)c.n,
+                       h->gconsts.k, h->gconsts.regularization | (h->prm.gicp_cov_jacobi_svd ? 0x100 : 0), h->knn_nbr.ptr, c.cov.ptr);
   prof_end(h, DGS_K_GICP_COVARIANCE, slot);
   DGS_HIP_TRY(h, hipGetLastError());
 #ifdef DGS_KNN_STATS

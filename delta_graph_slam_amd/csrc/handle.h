@@ -581,6 +581,9 @@ int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float*
 const float* gicp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int gicp_covariances(dgs_handle* h, int which, double* host_out6, int64_t n);
 int gicp_probe(dgs_handle* h, const double* T16_rowmajor, int error_only, double* err, double* H36, double* b6);
+// gicp_cov_ordered.hip: covariances in upstream's operation order (dgs_params.gicp_cov_jacobi_svd = DGS_GICP_COV_UPSTREAM_ORDER) from knn_lists' sets
+struct BvhView;
+int gicp_cov_upstream_order(dgs_handle* h, const BvhView& v, CloudState& c, int k, int regularization, const int* nbr);
 // icp.hip
 int icp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -195,7 +195,7 @@ __device__ inline void eigen_selfadjoint3_d(const double* Ain, double* ev, doubl
 // Eigen::JacobiSVD<Matrix3d>(A, ComputeFullU | ComputeFullV) as Eigen 3.3 executes it for a square real matrix (two-sided Jacobi on A / max|A|, sweeps
 // over (p, q), q < p, real_2x2_jacobi_svd + makeJacobi, signs, descending order): what fast_gicp's calculate_covariances calls on every
 // neighbourhood covariance.  The same sequence of IEEE operations as the CPU checker's generic restatement (the 6 x 6 Newton solve uses it too, laid
-// out across a wave in solve6.h), contraction off.  U, V row-major, sv descending.  dgs_params.gicp_cov_jacobi_svd = 1 (default).
+// out across a wave in solve6.h), contraction off.  U, V row-major, sv descending.  dgs_params.gicp_cov_jacobi_svd = 1 or 2 (the default is 0).
 __device__ inline void jacobi_svd3_d(const double* A, double* U, double* V, double* sv) {
 #pragma clang fp contract(off)
   constexpr int N = 3;

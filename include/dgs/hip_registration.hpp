@@ -88,6 +88,9 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     else { params_.gicp_rotation_epsilon = e; dirty_ = true; }
   }
   void setRegularizationMethod(int m) { params_.gicp_regularization = m; dirty_ = true; }
+  // dgs_gicp_cov_mode (dgs_reg.h): 0 tree sums + symmetric eigen-decomposition (default), 1 tree sums + JacobiSVD, 2 upstream order (ordered neighbours,
+  // sequential sums, JacobiSVD: the covariances of calculate_covariances bit for bit).  FAST_GICP / FAST_VGICP; takes effect at the next handle.
+  void setCovarianceMode(int mode) { params_.gicp_cov_jacobi_svd = mode; dirty_ = true; }
   void setDevice(int ordinal) { params_.device = ordinal; dirty_ = true; }
   // pcl::IterativeClosestPoint (DGS_METHOD_ICP): registrations.cpp:63, and the criteria settings dgs_params has no field for
   // (applied to a live handle in place: its target stays uploaded and indexed)

@@ -40,6 +40,8 @@ typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration(const st
     gicp->setMaximumIterations(pnh.template param<int>("reg_maximum_iterations", 64));                    // :32
     gicp->setMaxCorrespondenceDistance(pnh.template param<double>("reg_max_correspondence_distance", 2.5));  // :33
     gicp->setCorrespondenceRandomness(pnh.template param<int>("reg_correspondence_randomness", 20));      // :34
+    // not a parameter of the reference: covariances in upstream's operation order (dgs_reg.h, DGS_GICP_COV_UPSTREAM_ORDER); off by default
+    if (param_bool(pnh, "reg_covariance_upstream_order", false, 0)) gicp->setCovarianceMode(DGS_GICP_COV_UPSTREAM_ORDER);
     return base;
   }
   if (registration_method == "FAST_VGICP_HIP") {
@@ -51,6 +53,7 @@ typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration(const st
     vgicp->setTransformationEpsilon(pnh.template param<double>("reg_transformation_epsilon", 0.01));      // :53
     vgicp->setMaximumIterations(pnh.template param<int>("reg_maximum_iterations", 64));                   // :54
     vgicp->setCorrespondenceRandomness(pnh.template param<int>("reg_correspondence_randomness", 20));     // :55
+    if (param_bool(pnh, "reg_covariance_upstream_order", false, 0)) vgicp->setCovarianceMode(DGS_GICP_COV_UPSTREAM_ORDER);   // as FAST_GICP_HIP
     return base;
   }
   if (registration_method == "ICP_HIP") {   // registrations.cpp:59-64 on the GPU (the reference's own "ICP" string keeps its branch)

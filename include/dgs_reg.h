@@ -101,6 +101,12 @@ enum dgs_gicp_regularization {
   DGS_GICP_REG_PLANE = 3, DGS_GICP_REG_FROBENIUS = 4
 };
 enum dgs_gicp_optimizer { DGS_GICP_OPT_GAUSS_NEWTON = 0, DGS_GICP_OPT_LEVENBERG_MARQUARDT = 1 };
+/* dgs_params.gicp_cov_jacobi_svd: how FAST_GICP / FAST_VGICP form and regularise the k-NN covariances */
+enum dgs_gicp_cov_mode {
+  DGS_GICP_COV_SYM_EIG = 0,        /* tree sums over the neighbours, symmetric eigen-decomposition (default) */
+  DGS_GICP_COV_JACOBI_SVD = 1,     /* tree sums, Eigen::JacobiSVD<Matrix3d> restated */
+  DGS_GICP_COV_UPSTREAM_ORDER = 2  /* neighbours in ascending (distance, index) order, summed one after another, JacobiSVD: upstream's operation order */
+};
 
 typedef struct dgs_params {
   uint32_t struct_size; /* sizeof(dgs_params), set by dgs_params_init */
@@ -159,7 +165,11 @@ typedef struct dgs_params {
                                            Jacobi; the routine fast_gicp calls), 0 (default) = the symmetric eigen-decomposition of ABI <= 4 -- the same factors up to
                                            rounding on regular neighbourhoods.  Not the default because JacobiSVD skips rotations below 2 eps maxDiag: on a rank-deficient
                                            neighbourhood (duplicated points, points on a line) the basis of the null space -- and with it U diag(1, 1, 1e-3) V^T -- then
-                                           jumps with the last bit of the input covariance, which the device and a CPU sum in different orders.  (Was reserved1.) */
+                                           jumps with the last bit of the input covariance, which the device (8-lane tree sums) and a CPU sum in different orders.
+                                           2 (DGS_GICP_COV_UPSTREAM_ORDER) = JacobiSVD fed upstream's bits: each point's neighbours put in ascending (float squared
+                                           distance, index) order, mean and covariance summed over them one after another in double, every operation individually
+                                           rounded -- the six stored entries are the CPU restatement's (oracle, cov_svd = 1) bit for bit, rank-deficient
+                                           neighbourhoods included; slower (one lane per point).  dgs_gicp_cov_mode; fixed at dgs_create.  (Was reserved1.) */
 } dgs_params;
 
 /* What the callers read back after align(): hasConverged(), getFinalTransformation(), and the
