@@ -87,9 +87,10 @@ struct NdtSolver {
   // [eps / 2, step_size], so a search often evaluates the SAME pose again -- on the CPU that gives the same doubles and updateIntervalMT's
   // `f_t > f_l` is decided by equality; here the sums of two launches of different composition differ in their last bits (~1e-14), which
   // flipped that test on 3 of ~700 pairs at transformation_epsilon = 0.1 (soak, profiles/r04).  A pose that was evaluated before in this line
-  // search takes its earlier value (ndt_advance); reset by begin_iteration.
+  // search takes its earlier value (ndt_advance); reset by begin_iteration.  A trial whose pose is in the cache when it is QUEUED is
+  // consumed in the same call, without a launch (NdtConsts::reuse_trials); trial_hits counts the cached poses met, in both switch positions.
   static constexpr int kTrialCache = 3;
-  int trial_n, trial_next;
+  int trial_n, trial_next, trial_hits, trial_pad;
   double trial_x[kTrialCache][6];
   double trial_score[kTrialCache];
   double trial_grad[kTrialCache][6];
@@ -200,7 +201,9 @@ struct NdtConsts {
   int newton_solver;     // upstream orders: 1 = Eigen's two-sided JacobiSVD sequence (solve6.h jsvd_solve6_wave), 0 = one-sided Hestenes Jacobi
   int hessian_double;    // upstream orders: computeStepLengthMT's closing computeHessian in PCL's double form (evaluation kind 2)
   int exp_libm;          // upstream orders: updateDerivatives' std::exp(float) as glibc computes it (glibc_expf_dev), 0 = det_expf (rounds 1-3)
+  int reuse_trials;      // upstream orders: a repeated More-Thuente trial pose is answered from NdtSolver::trial_x without a launch (DGS_NDT_REUSE_TRIALS)
 };
+static_assert(sizeof(NdtConsts) == 72, "reuse_trials sits in what was padding: the kernels' argument blocks keep their size");
 
 struct NdtInit {  // host -> device per pair, per align
   float guess[16];  // column-major

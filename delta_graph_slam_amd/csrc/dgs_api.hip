@@ -449,6 +449,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (const char* e = std::getenv("DGS_NDT_SPECULATE")) h->ndt_speculate = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_FIXED_SLICES")) h->ndt_fixed_slices = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_DEAL_BY_COST")) h->ndt_deal_by_cost = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DGS_NDT_REUSE_TRIALS")) h->ndt_reuse_trials = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_QUEUE")) h->ndt_queue_mode = std::atoi(e);
   if (const char* e = std::getenv("DGS_NDT_SCHEDULE")) h->ndt_schedule = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_QUEUE_MIN_PAIRS")) h->ndt_queue_min_pairs = std::max(1, std::atoi(e));
@@ -992,6 +993,7 @@ int dgs_get_counts(dgs_handle* h, int64_t out[8]) {
     out[4] = h->grid_cells;
   }
   out[5] = h->last_evaluations;
+  out[6] = h->last_reused;
   return DGS_OK;
 }
 

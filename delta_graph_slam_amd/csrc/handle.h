@@ -310,6 +310,7 @@ struct dgs_handle {
   bool ndt_fixed_slices = false;     // DGS_NDT_FIXED_SLICES=1: upstream order, item-compacted kernel: a pair's slices are a function of its own size (ndt_strict.h strict_slices_of)
                                       // from the Gauss-Jordan direction and verified beside the next launch (NdtPair::spec_s)
   bool ndt_deal_by_cost = true;       // DGS_NDT_DEAL_BY_COST=0: upstream order, item-compacted kernel: a launch's workgroups dealt to the pairs in index order (deal_workgroup)
+  bool ndt_reuse_trials = true;       // DGS_NDT_REUSE_TRIALS=0: upstream orders: a repeated More-Thuente trial pose is evaluated again and its result replaced by the cached one
                                       // instead of heaviest evaluation kind first (deal_workgroup_by_cost); the same (pair, slice) set and the same bits either way
 #ifdef DGS_DEAL_STAMPS
   unsigned long long* deal_stamps = nullptr;   // stamp build (make stamps): the workgroup stamps of the recorded launches
@@ -373,6 +374,7 @@ struct dgs_handle {
   dgs::DevBuf<int> src_sizes;
   dgs::NdtConsts consts{};
   int64_t last_evaluations = 0;
+  int64_t last_reused = 0;            // NDT, upstream orders: trial poses of the last align / batch found in the line search's cache (dgs_get_counts slot 6)
   dgs::DevBuf<int> knn_nbr;           // k-NN sets of the cloud whose covariances are being made: [position in Hilbert order * 32 + slot]
   dgs::DevBuf<int> knn_stats;         // debug build (-DDGS_KNN_STATS): waves, waves on the cooperative path, candidate leaves
   bool nn_kd = true;                  // DGS_NN_KD=0: Hilbert order also for the loop batch's target index

@@ -90,6 +90,8 @@ __global__ void ndt_init_kernel(NdtPair* __restrict__ pairs, const NdtInit* __re
   s.nr_iterations = 0;
   s.trial_n = 0;
   s.trial_next = 0;
+  s.trial_hits = 0;
+  s.trial_pad = 0;
   s.evaluations = 0;
   s.converged = 0;
   s.step_iterations = 0;
@@ -128,7 +130,7 @@ __global__ void ndt_init_kernel(NdtPair* __restrict__ pairs, const NdtInit* __re
 
 struct NdtOut {
   float T[16];
-  int converged, iterations, evaluations, pad;
+  int converged, iterations, evaluations, reused;   // evaluations: upstream's count; reused: those of them answered from the trial cache (NdtSolver::trial_hits)
   double score;
 };
 
@@ -141,7 +143,7 @@ __global__ void ndt_export_kernel(const NdtPair* __restrict__ pairs, int n_pairs
   o.converged = (st.s.phase == PH_DONE) ? st.s.converged : 0;
   o.iterations = st.s.nr_iterations;
   o.evaluations = st.s.evaluations;
-  o.pad = 0;
+  o.reused = st.s.trial_hits;
   o.score = st.s.score;
   out[i] = o;
 }
@@ -300,6 +302,7 @@ static void fill_consts(dgs_handle* h) {
   c.newton_solver = p.ndt_newton_solver;
   c.hessian_double = (p.ndt_strict_order != DGS_NDT_ORDER_FAST && p.ndt_hessian_recompute_double) ? 1 : 0;
   c.exp_libm = p.ndt_exp_glibc ? 1 : 0;
+  c.reuse_trials = (DGS_NDT_REUSE_TRIALS != 0 && h->ndt_reuse_trials && p.ndt_strict_order != DGS_NDT_ORDER_FAST) ? 1 : 0;
 }
 
 struct NdtLaunch {
@@ -808,7 +811,7 @@ static int ndt_export(dgs_handle* h, int n_pairs, dgs_result* results) {
   DGS_HIP_TRY(h, hipMemcpyAsync(hout, dout, sizeof(NdtOut) * n_pairs, hipMemcpyDeviceToHost, st));
   DGS_HIP_TRY(h, hipStreamSynchronize(st));
   DGS_HIP_TRY(h, hipGetLastError());
-  int64_t evals = 0;
+  int64_t evals = 0, reused = 0;
   for (int i = 0; i < n_pairs; i++) {
     std::memcpy(results[i].final_transformation, hout[i].T, sizeof(float) * 16);
     results[i].converged = hout[i].converged;
@@ -818,8 +821,11 @@ static int ndt_export(dgs_handle* h, int n_pairs, dgs_result* results) {
     results[i].score = hout[i].score;
     results[i].fitness = NAN;
     evals += hout[i].evaluations;
+    reused += hout[i].reused;
   }
-  h->last_evaluations = evals;
+  // what ran on the device: with the reuse on, a cached trial pose is counted by upstream and the records, and launches nothing
+  h->last_evaluations = evals - (h->consts.reuse_trials ? reused : 0);
+  h->last_reused = reused;
   return DGS_OK;
 }
 

@@ -311,22 +311,36 @@ __device__ __forceinline__ void queue_trial(NdtPair* st, NdtPair* hdr, NdtSolver
 // with that phase -- from ndt_strict_solve_kernel -- continues there.
 // speculate (upstream order, fused item-compacted kernel): take the next iteration's Newton step from the fast solver and tell the caller
 // (*speculated) -- see NdtPair::spec_s.
+// `make ab AB=-DDGS_NDT_REUSE_TRIALS=0`: ndt_advance without the reuse of cached trial poses (as DGS_NDT_REUSE_TRIALS=0 chooses at run time)
+#ifndef DGS_NDT_REUSE_TRIALS
+#define DGS_NDT_REUSE_TRIALS 1
+#endif
+// the entry of this line search's trial cache that holds pose s.x_t (all six doubles equal), or -1
+__device__ __forceinline__ int trial_cached(const NdtSolver& s) {
+  int hit = -1;
+  for (int k = 0; k < s.trial_n; k++) {
+    bool eq = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) eq = eq && (s.trial_x[k][j] == s.x_t[j]);
+    if (eq && hit < 0) hit = k;
+  }
+  return hit;
+}
+
 template <bool SVD_REGS = false, bool COH = false, bool STRICT = false>
 __device__ __forceinline__ void ndt_advance(NdtPair* st, NdtPair* hdr, NdtSolver& s, const NdtConsts& c, bool writer, bool defer_solve = false, bool speculate = false,
                                             bool* speculated = nullptr) {
   bool iteration_open = false;  // true: an iteration's line search has accepted its step, close it
   const bool resume = STRICT && s.phase == PH_SOLVE_PENDING;
   if (!resume) s.evaluations++;
+  // One pass per trial consumed.  The upstream orders go round again when the trial just queued is a pose this line search has evaluated
+  // before (NdtConsts::reuse_trials): its value is in the cache, so it is consumed here and now instead of costing the pair a launch.
+  for (;;) {
   if (STRICT && (s.phase == PH_MT_FIRST || s.phase == PH_MT_TRIAL)) {
     // a trial point this line search has evaluated before takes the value it had then (NdtSolver::trial_x): same pose, same doubles, as on the CPU
-    int hit = -1;
-    for (int k = 0; k < s.trial_n; k++) {
-      bool eq = true;
-#pragma unroll
-      for (int j = 0; j < 6; j++) eq = eq && (s.trial_x[k][j] == s.x_t[j]);
-      if (eq && hit < 0) hit = k;
-    }
+    const int hit = trial_cached(s);
     if (hit >= 0) {
+      s.trial_hits++;
       s.score = s.trial_score[hit];
 #pragma unroll
       for (int j = 0; j < 6; j++) s.grad[j] = s.trial_grad[hit][j];
@@ -368,7 +382,13 @@ __device__ __forceinline__ void ndt_advance(NdtPair* st, NdtPair* hdr, NdtSolver
       if (mt_keep_going(s, c, psi_t, d_phi_t)) {
         const double a_n = s.open_interval ? mt_trial_value(s.a_l, s.f_l, s.g_l, s.a_u, s.f_u, s.g_u, s.a_t, psi_t, d_psi_t)
                                            : mt_trial_value(s.a_l, s.f_l, s.g_l, s.a_u, s.f_u, s.g_u, s.a_t, phi_t, d_phi_t);
+        // (queued in full on a hit too: the pair's record holds the transform and the angle tables of the pose in flight, which the
+        //  computeHessian pass behind an accepted trial and final_T read)
         queue_trial<COH>(st, hdr, s, c, a_n, writer);
+        if (STRICT && DGS_NDT_REUSE_TRIALS != 0 && c.reuse_trials && trial_cached(s) >= 0) {
+          s.evaluations++;   // upstream's count: the CPU evaluates this pose again
+          continue;          // mt_keep_going bounds the chain: every pass is a loop trial, step_iterations < mt_max_step_iterations
+        }
         return;
       }
       if (s.step_iterations) {  // computeHessian at the accepted point
@@ -386,6 +406,8 @@ __device__ __forceinline__ void ndt_advance(NdtPair* st, NdtPair* hdr, NdtSolver
       break;
     default:
       return;
+  }
+  break;
   }
   for (int guard = 0; guard < 4096; guard++) {
     if (iteration_open) {

@@ -544,7 +544,7 @@ class Registration:
         out = (C.c_int64 * 8)()
         self._check(self._lib.dgs_get_counts(self._h, out))
         return dict(target_points=out[0], source_points=out[1], valid_voxels=out[2], occupied_voxels=out[3],
-                    grid_cells=out[4], evaluations=out[5])
+                    grid_cells=out[4], evaluations=out[5], evaluations_reused=out[6])
 
     def vgicp_voxels(self):
         """FAST_VGICP target voxel map -> (coords [V,3], counts [V], means [V,3], covs [V,3,3]) in ascending (z, y, x) order"""

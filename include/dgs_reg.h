@@ -178,7 +178,7 @@ typedef struct dgs_result {
   float final_transformation[16]; /* getFinalTransformation(), column-major */
   int32_t converged;              /* hasConverged() */
   int32_t iterations;             /* nr_iterations_ */
-  int32_t evaluations;            /* derivative / linearisation passes executed */
+  int32_t evaluations;            /* derivative / linearisation passes as upstream counts them (NDT, upstream orders: repeated More-Thuente trial poses answered from the line search's cache included) */
   int32_t status;                 /* dgs_status of this registration (batch entries fail independently) */
   double score;                   /* NDT: score (trans_probability * Ns); GICP: final sum of Mahalanobis errors */
   double fitness;                 /* getFitnessScore(max_range) when requested, else NaN */
@@ -409,7 +409,9 @@ int dgs_profile_get(dgs_handle* h, int32_t kernel_id, double* total_ms, int64_t*
 int dgs_profile_reset(dgs_handle* h);
 /* Counts describing the current problem, for algorithmic-byte accounting:
  * out[0] = target points, out[1] = source points, out[2] = valid voxels V, out[3] = occupied voxels,
- * out[4] = voxel grid cells, out[5] = derivative evaluations of the last align / batch (sum over pairs; ICP: correspondence passes). */
+ * out[4] = voxel grid cells, out[5] = derivative evaluations of the last align / batch that ran on the device (sum over pairs; ICP: correspondence
+ * passes; NDT, upstream orders: the sum of dgs_result.evaluations minus out[6] unless DGS_NDT_REUSE_TRIALS=0), out[6] = NDT, upstream orders:
+ * More-Thuente trial poses of the last align / batch that their line search had evaluated before (answered from its cache). */
 int dgs_get_counts(dgs_handle* h, int64_t out[8]);
 
 /* Test hooks: single evaluations on the device, so tests can compare kernels with the oracle directly. */
