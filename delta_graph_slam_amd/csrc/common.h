@@ -183,7 +183,8 @@ struct GicpItem {  // one registration of a batch: its source cloud (with index 
   int* corr;                 // per source point: index of its target correspondence or -1
   float* corr_sq;
   double* mahal;             // 6 doubles per source point
-  int n, pad;
+  int n;
+  int tgt;                   // per-pair targets (gicp_align_pairs): the pair's entry of the launch's target table; 0 on the single-target paths
 };
 
 struct GicpConsts {

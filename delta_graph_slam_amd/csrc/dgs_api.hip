@@ -513,7 +513,7 @@ void dgs_destroy(dgs_handle* h) {
   floor_detection_release(h);
   fitness_batch_release(h);
   building_cloud_release(h);
-  h->gitems.release(); h->vvox.release(); h->vcell2vox.release();
+  h->gitems.release(); h->gtargets.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
   h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();
   h->run_counts.release(); h->run_offsets.release(); h->dev_scalars.release(); h->vg_run_keys.release(); h->vg_scalars.release(); h->minmax_partial.release(); h->cub_temp.release();
@@ -945,6 +945,51 @@ int dgs_align_batch_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* sources, 
   std::vector<CloudState*> cs(n);
   for (int i = 0; i < n; i++) cs[i] = &sources[i]->st;
   return gicp_batch(h, n, cs.data(), guesses16, compute_fitness, fitness_max_range, results);
+}
+
+static const char* method_name(int32_t m) {
+  static const char* const names[] = {"NDT_OMP", "FAST_GICP", "FAST_VGICP", "ICP_HIP", "GICP_HIP", "PCL_NDT_HIP"};
+  return valid_method(m) ? names[m] : "unknown";
+}
+
+// n registrations that each name their own target (a tick of the loop detector: every new keyframe is a target with a short candidate
+// list of its own): one batched index build, one chain of round launches for all pairs, one fitness launch over all edges
+int dgs_align_pairs_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* targets, dgs_cloud* const* sources, const float* guesses16, int32_t compute_fitness,
+                           double fitness_max_range, dgs_result* results) {
+  if (!h || n < 0 || (n > 0 && (!targets || !sources || !results))) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (h->prm.method != DGS_METHOD_GICP) {
+    h->err = std::string("dgs_align_pairs_clouds serves FAST_GICP only; this handle's method is ") + method_name(h->prm.method) +
+             " (its target model lives on the handle, not on the cloud)";
+    return DGS_ERR_UNSUPPORTED;
+  }
+  if (set_device(h)) return DGS_ERR_HIP;
+  if (n == 0) return DGS_OK;
+  for (int i = 0; i < n; i++)
+    if (!targets[i] || !sources[i] || targets[i]->device != h->device || sources[i]->device != h->device) {
+      h->err = "dgs_align_pairs_clouds: a NULL cloud or a cloud of another device";
+      return DGS_ERR_INVALID_ARGUMENT;
+    }
+  for (int i = 0; i < n; i++) fail_result(&results[i], guesses16 ? guesses16 + 16 * i : nullptr, DGS_OK);
+  int rc = gicp_align_pairs(h, n, targets, sources, guesses16, results);
+  if (rc == DGS_OK && compute_fitness) {
+    // getFitnessScore of source i under its final transform against target i: the edge (target i, source i, T_i) of the batched scorer
+    std::vector<float> T((size_t)n * 16);
+    std::vector<double> scores((size_t)n);
+    for (int i = 0; i < n; i++) std::memcpy(&T[(size_t)i * 16], results[i].final_transformation, sizeof(float) * 16);
+    rc = fitness_batch_clouds(h, n, targets, sources, T.data(), fitness_max_range, scores.data(), nullptr);
+    if (rc == DGS_OK)
+      for (int i = 0; i < n; i++) results[i].fitness = scores[i];
+  }
+  if (rc != DGS_OK) {
+    for (int i = 0; i < n; i++) fail_result(&results[i], guesses16 ? guesses16 + 16 * i : nullptr, rc);
+    return rc;
+  }
+  for (int i = 0; i < n; i++) {   // what dgs_align reports for the pair alone: a missing target first, then a missing source
+    const int st = targets[i]->st.n <= 0 ? DGS_ERR_NO_TARGET : sources[i]->st.n <= 0 ? DGS_ERR_NO_SOURCE : DGS_OK;
+    if (st != DGS_OK) fail_result(&results[i], guesses16 ? guesses16 + 16 * i : nullptr, st);
+  }
+  return DGS_OK;
 }
 
 int dgs_profile_enable(dgs_handle* h, int32_t enable) {

@@ -966,6 +966,113 @@ __global__ __launch_bounds__(kBlock, FUSED ? 4 : 1) void gicp_linearize_kernel(c
   if (FUSED) gicp_close_round(pairs, pair, nblocks, partials + (size_t)pair * cap_blocks * kAccumPad, consts, done_counter, launch);
 }
 
+// ================================================================================================ per-pair targets
+// gicp_align_pairs: pair i registers ITS source against ITS target (the loop detector's tick: every new keyframe is a target with a short
+// candidate list of its own).  The two round kernels above with one difference: the target's index view, points and covariances are not
+// kernel arguments but an entry of a device table, chosen by GicpItem::tgt.  deal_workgroup makes the pair index workgroup-uniform, so
+// the entry's address is uniform too: the 64 bytes come in through scalar loads, once per wave, and live in SGPRs exactly where the
+// single-target kernels keep their arguments (load16_at's base, the walk's depth and first leaf).  Everything else -- the walk in the
+// source's own order, the warm bound, the threshold, the Mahalanobis matrices, the sums, the closing workgroup -- is the code above,
+// operation for operation; the bodies are restated rather than shared so that the single-target instantiations stay what they were.
+struct GicpTarget {
+  BvhView b;           // exact-NN index of the target cloud
+  const float4* pts;   // its points in the caller's order
+  const double* cov;   // its covariances, 6 doubles per point
+  int n, pad;
+};
+static_assert(sizeof(GicpTarget) == 64, "one target is one 64-byte scalar load");
+
+__global__ __launch_bounds__(kBlock) void gicp_correspond_pairs_kernel(const GicpTarget* __restrict__ targets, const GicpItem* __restrict__ items,
+                                                                       const GicpPair* __restrict__ pairs, const int n_pairs, const int cap_blocks,
+                                                                       const float max_sq) {
+  int pair, slice, bpp;
+  if (!deal_workgroup(n_pairs, cap_blocks, [&](int pi) { return pairs[pi].active != 0 && pairs[pi].eval_kind == 0; }, pair, slice, bpp)) return;
+  const GicpPair& st = pairs[pair];
+  const GicpItem it = items[pair];
+  const BvhView b = targets[it.tgt].b;   // uniform address: scalar loads
+  const int n = it.n;
+  float T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = (float)st.Teval[k];
+  const int sub = threadIdx.x & 7;
+  constexpr int QPB = kBlock / 8;
+  const int run = (n + bpp * QPB - 1) / (bpp * QPB);
+  const int first = (slice * (kBlock / kWave) + (threadIdx.x >> 6)) * (8 * run) + ((threadIdx.x & 63) >> 3);
+  float px = 0.f, py = 0.f, pz = 0.f, prev_best = INFINITY;
+  bool prev_found = false;
+  for (int r = 0; r < run; r++) {
+    const int pos = first + r * 8;
+    const float4 p = (pos < n) ? it.src_sorted[pos] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int i = (pos < n) ? (int)__float_as_uint(p.w) : -1;
+    const bool alive = pos < n && i >= 0 && i < n;
+    const float x = affine_row_rn(T[0], T[1], T[2], T[3], p.x, p.y, p.z);
+    const float y = affine_row_rn(T[4], T[5], T[6], T[7], p.x, p.y, p.z);
+    const float z = affine_row_rn(T[8], T[9], T[10], T[11], p.x, p.y, p.z);
+    float best;
+    int bi;
+    const float bound = fminf(max_sq, nn_warm_bound_round(prev_best, prev_found, x, y, z, px, py, pz));
+    nn_query_group(b, x, y, z, alive, bound, best, bi);
+    prev_found = alive && bi != 0x7FFFFFFF;
+    prev_best = best;
+    px = x; py = y; pz = z;
+    if (alive && sub == 0) {
+      const bool ok = (bi != 0x7FFFFFFF) && (best < max_sq);
+      it.corr[i] = ok ? bi : -1;
+      it.corr_sq[i] = (bi != 0x7FFFFFFF) ? best : max_sq;
+    }
+  }
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(kBlock, FUSED ? 4 : 1) void gicp_linearize_pairs_kernel(const GicpTarget* __restrict__ targets, const GicpItem* __restrict__ items,
+                                                                      GicpPair* __restrict__ pairs, double* __restrict__ partials, const int n_pairs,
+                                                                      const int cap_blocks, int* __restrict__ pair_blocks, const GicpConsts consts,
+                                                                      int* __restrict__ done_counter, const int launch) {
+  int pair, slice, nblocks;
+  if (!deal_workgroup(n_pairs, cap_blocks, [&](int pi) { return FUSED ? (launch <= pairs[pi].last_launch) : (pairs[pi].active != 0); }, pair, slice, nblocks)) return;
+  if (slice == 0 && threadIdx.x == 0) pair_blocks[pair] = nblocks;
+  const GicpPair& st = pairs[pair];
+  const GicpItem it = items[pair];
+  const int n = it.n;
+  const float4* __restrict__ src = it.src;
+  const double* __restrict__ cov_s = it.cov_s;
+  const int* __restrict__ corr = it.corr;
+  double* __restrict__ mahal = it.mahal;
+  const float4* __restrict__ tgt = targets[it.tgt].pts;   // uniform address: scalar loads
+  const double* __restrict__ cov_t = targets[it.tgt].cov;
+  const bool full = st.eval_kind == 0;
+  double T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = st.Teval[k];
+  double acc[kAccum];
+#pragma unroll
+  for (int k = 0; k < kAccum; k++) acc[k] = 0.0;
+
+  for (int i = slice * kBlock + threadIdx.x; i < n; i += nblocks * kBlock) {
+    const int j = corr[i];
+    if (j < 0) continue;
+    const float4 pa = src[i], pb = tgt[j];
+    double M[6];
+    if (full) {
+      gicp_mahalanobis(T, cov_s + (size_t)i * 6, cov_t + (size_t)j * 6, M);
+      double* mo = mahal + (size_t)i * 6;
+#pragma unroll
+      for (int k = 0; k < 6; k++) mo[k] = M[k];
+    } else {
+      const double* mo = mahal + (size_t)i * 6;
+#pragma unroll
+      for (int k = 0; k < 6; k++) M[k] = mo[k];
+    }
+    const double ax = pa.x, ay = pa.y, az = pa.z;
+    const double t0 = T[0] * ax + T[1] * ay + T[2] * az + T[3];
+    const double t1 = T[4] * ax + T[5] * ay + T[6] * az + T[7];
+    const double t2 = T[8] * ax + T[9] * ay + T[10] * az + T[11];
+    gicp_accumulate<false>(acc, M, (double)pb.x - t0, (double)pb.y - t1, (double)pb.z - t2, t0, t1, t2, 1.0, full);
+  }
+  gicp_block_reduce<FUSED>(acc, partials + ((size_t)pair * cap_blocks + slice) * kAccumPad);
+  if (FUSED) gicp_close_round(pairs, pair, nblocks, partials + (size_t)pair * cap_blocks * kAccumPad, consts, done_counter, launch);
+}
+
 // ================================================================================================ FAST_VGICP linearize / error
 // FastVGICP::update_correspondences + linearize (eval_kind 0) or compute_error (eval_kind 1) in one pass: the voxel of T p
 // (double) and its DIRECT1 / 7 / 27 neighbours are looked up in the dense cell table -- no tree, no distance gate --, every hit is
@@ -1239,12 +1346,15 @@ static void gicp_launch_round(dgs_handle* h, const GicpLaunch& L, const int laun
 using GicpStaging = BatchStaging<GicpInit, GicpItem, GicpPair>;
 
 // Covariances and indices of every cloud, work arrays, per-pair state: everything a batch needs before its first round.
-static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const double* x0_rows, int probe_kind, GicpLaunch* L_out, int* n_live) {
+// tgt_of (gicp_align_pairs): pair i's entry of the target table, < 0 for a pair without a target (it never becomes active); the caller has
+// seen to the targets' covariances.  nullptr: every pair registers against the handle's target.
+static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const double* x0_rows, int probe_kind, GicpLaunch* L_out, int* n_live,
+                      const int* tgt_of = nullptr) {
   hipStream_t st = h->stream;
   fill_gconsts(h);
-  int rc = ensure_covariance(h, *h->tgt);
+  int rc = tgt_of ? DGS_OK : ensure_covariance(h, *h->tgt);
   if (rc) return rc;
-  const bool vgicp = h->prm.method == DGS_METHOD_VGICP;
+  const bool vgicp = !tgt_of && h->prm.method == DGS_METHOD_VGICP;
   if (vgicp && !h->vmap_valid) {
     rc = vgicp_build_map(h);
     if (rc) return rc;
@@ -1253,7 +1363,7 @@ static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const doubl
   int64_t total = 0, max_n = 1;
   *n_live = 0;
   for (int i = 0; i < n; i++) {
-    if (srcs[i]->n <= 0) continue;
+    if (srcs[i]->n <= 0 || (tgt_of && tgt_of[i] < 0)) continue;
     rc = ensure_covariance(h, *srcs[i]);
     if (rc) return rc;
     total += srcs[i]->n;
@@ -1281,16 +1391,18 @@ static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const doubl
     const CloudState& c = *srcs[i];
     for (int k = 0; k < 12; k++) hin[i].x0[k] = x0_rows[12 * i + k];
     hin[i].probe_kind = probe_kind;
-    hin[i].n = (int)c.n;
+    // a pair without a target is dead: the sizing loop above left its source out of `total`, so it gets a zero-length slot here
+    const int64_t live_n = (tgt_of && tgt_of[i] < 0) ? 0 : c.n;
+    hin[i].n = (int)live_n;
     hit[i].src = c.pts.ptr;
     hit[i].src_sorted = c.bvh.sorted.ptr;
     hit[i].cov_s = c.cov.ptr;
     hit[i].corr = h->corr.ptr + off * per_point;
     hit[i].corr_sq = h->corr_sq.ptr + off;
     hit[i].mahal = h->mahal.ptr + off * per_point * 6;
-    hit[i].n = (int)c.n;
-    hit[i].pad = 0;
-    off += c.n;
+    hit[i].n = (int)live_n;
+    hit[i].tgt = tgt_of ? std::max(tgt_of[i], 0) : 0;
+    off += live_n;
   }
   DGS_HIP_TRY(h, hipMemcpyAsync(h->inits.ptr, hin, (size_t)n * sizeof(GicpInit), hipMemcpyHostToDevice, st));
   DGS_HIP_TRY(h, hipMemcpyAsync(h->gitems.ptr, hit, (size_t)n * sizeof(GicpItem), hipMemcpyHostToDevice, st));
@@ -1302,27 +1414,40 @@ static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const doubl
 
 // FastGICP::align for every source of a batch against the handle's target; the LM loops of all pairs advance together,
 // one (correspond, linearize, solve) launch triple per round, and pairs that finish hand their workgroups to the rest.
-int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out) {
+static std::vector<double> gicp_guess_rows(int n, const float* guesses16) {
   std::vector<double> x0((size_t)n * 12);
   for (int i = 0; i < n; i++) {
     const float* G = guesses16 ? guesses16 + 16 * i : kIdentity16;
     for (int r = 0; r < 3; r++)
       for (int c = 0; c < 4; c++) x0[(size_t)i * 12 + r * 4 + c] = (double)G[c * 4 + r];  // Eigen::Isometry3d(guess.cast<double>())
   }
+  return x0;
+}
+
+// whole chunks of 4 rounds: the bound rounded up
+static long gicp_max_rounds(const dgs_handle* h) { return ((long)h->prm.maximum_iterations * (h->prm.gicp_lm_max_iterations + 1) + 4 + 3) / 4 * 4; }
+
+static int gicp_read_results(dgs_handle* h, int n, CloudState* const* srcs, dgs_result* out);
+
+int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out) {
+  const std::vector<double> x0 = gicp_guess_rows(n, guesses16);
   GicpLaunch L;
   int n_live = 0;
   int rc = gicp_start(h, n, srcs, x0.data(), -1, &L, &n_live);
   if (rc) return rc;
 
   if (n_live > 0) {
-    // whole chunks of 4 rounds: the bound rounded up
-    const long max_rounds = ((long)h->prm.maximum_iterations * (h->prm.gicp_lm_max_iterations + 1) + 4 + 3) / 4 * 4;
     int launch_no = 0;
-    rc = run_rounds_polled(h, n_live, max_rounds, 4, [&] { gicp_launch_round(h, L, launch_no++); });
+    rc = run_rounds_polled(h, n_live, gicp_max_rounds(h), 4, [&] { gicp_launch_round(h, L, launch_no++); });
     if (rc != DGS_OK) return rc;
   }
+  return gicp_read_results(h, n, srcs, out);
+}
+
+// the pair states of the batch that has just run -> results
+static int gicp_read_results(dgs_handle* h, int n, CloudState* const* srcs, dgs_result* out) {
   const GicpStaging stg(h, n);
-  rc = stg.read_back(h->gpairs, n, "GICP optimiser state");
+  int rc = stg.read_back(h->gpairs, n, "GICP optimiser state");
   if (rc) return rc;
   const GicpPair* hp = stg.pairs();
   long evals = 0;
@@ -1339,6 +1464,77 @@ int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float*
   }
   h->last_evaluations = evals;
   return DGS_OK;
+}
+
+// ---- per-pair targets: pair i = (tgts[i], srcs[i], guess i), all LM loops advancing together in the same rounds (the kernels: "per-pair
+// targets" above).  The handle's own target, source and last result are not touched.  A pair whose target or source is empty never
+// becomes active: its status is the caller's business (dgs_align_pairs_clouds).
+static void gicp_launch_pairs_round(dgs_handle* h, const GicpLaunch& L, const int launch) {
+  const bool fused = h->gicp_fused;
+  int slot = prof_begin(h, DGS_K_NN_SEARCH);
+  hipLaunchKernelGGL(gicp_correspond_pairs_kernel, dim3(L.grid_c), dim3(kBlock), 0, h->stream, h->gtargets.ptr, h->gitems.ptr, h->gpairs.ptr, L.n_pairs, L.cap_c,
+                     h->gconsts.max_corr_sq);
+  prof_end(h, DGS_K_NN_SEARCH, slot);
+  slot = prof_begin(h, DGS_K_GICP_LINEARIZE);
+  if (fused)
+    hipLaunchKernelGGL(gicp_linearize_pairs_kernel<true>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gtargets.ptr, h->gitems.ptr, h->gpairs.ptr, h->partials.ptr,
+                       L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+  else
+    hipLaunchKernelGGL(gicp_linearize_pairs_kernel<false>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gtargets.ptr, h->gitems.ptr, h->gpairs.ptr, h->partials.ptr,
+                       L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+  prof_end(h, DGS_K_GICP_LINEARIZE, slot);
+  if (!fused)
+    hipLaunchKernelGGL(gicp_solve_kernel, dim3(L.n_pairs), dim3(kBlock), 0, h->stream, h->gpairs.ptr, h->partials.ptr, h->pair_blocks.ptr, L.cap_l,
+                       h->gconsts, h->done_counter.ptr);
+}
+
+int gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* const* srcs, const float* guesses16, dgs_result* out) {
+  fill_gconsts(h);
+  // the distinct non-empty targets, by pointer, in order of first appearance; tgt_of[i] < 0: pair i has no target
+  std::vector<dgs_cloud*> uniq;
+  std::vector<int> tgt_of((size_t)n);
+  for (int i = 0; i < n; i++) {
+    tgt_of[i] = -1;
+    if (tgts[i]->st.n <= 0) continue;
+    const auto at = std::find(uniq.begin(), uniq.end(), tgts[i]);
+    tgt_of[i] = (int)(at - uniq.begin());
+    if (at == uniq.end()) uniq.push_back(tgts[i]);
+  }
+  // every index that is missing, of targets and sources alike, in ONE batched build (the bits of a single build: fitness_batch.hip)
+  std::vector<dgs_cloud*> all(tgts, tgts + n);
+  all.insert(all.end(), srcs, srcs + n);
+  int rc = fitness_batch_build_indices(h, 2 * n, all.data());
+  if (rc) return rc;
+  for (dgs_cloud* c : uniq) {   // cached on the cloud under (k, regularisation): shared with every other path that uses the cloud
+    rc = ensure_covariance(h, c->st);
+    if (rc) return rc;
+  }
+  std::vector<CloudState*> cs((size_t)n);
+  for (int i = 0; i < n; i++) cs[i] = &srcs[i]->st;
+  const std::vector<double> x0 = gicp_guess_rows(n, guesses16);
+  // the target table travels from the pinned block, behind the batch's own staging (gicp_start sizes the block for that alone)
+  const size_t tab_off = (GicpStaging(h, n).bytes + 63) & ~(size_t)63, tab_bytes = std::max<size_t>(uniq.size(), 1) * sizeof(GicpTarget);
+  if (ensure_pinned(h, tab_off + tab_bytes) != DGS_OK) return DGS_ERR_HIP;
+  GicpLaunch L;
+  int n_live = 0;
+  rc = gicp_start(h, n, cs.data(), x0.data(), -1, &L, &n_live, tgt_of.data());
+  if (rc) return rc;
+  if (n_live > 0) {
+    DGS_HIP_TRY(h, h->gtargets.reserve(uniq.size()));
+    GicpTarget* tab = reinterpret_cast<GicpTarget*>(reinterpret_cast<char*>(h->pinned) + tab_off);
+    for (size_t t = 0; t < uniq.size(); t++) {
+      const CloudState& c = uniq[t]->st;
+      tab[t] = GicpTarget{make_bvh_view(c.bvh), c.pts.ptr, c.cov.ptr, (int)c.n, 0};
+    }
+    DGS_HIP_TRY(h, hipMemcpyAsync(h->gtargets.ptr, tab, uniq.size() * sizeof(GicpTarget), hipMemcpyHostToDevice, h->stream));
+    int launch_no = 0;
+    rc = run_rounds_polled(h, n_live, gicp_max_rounds(h), 4, [&] { gicp_launch_pairs_round(h, L, launch_no++); });
+    if (rc != DGS_OK) return rc;
+  }
+  const int64_t own_evaluations = h->last_evaluations;   // dgs_get_counts keeps reporting the handle's own last align / batch
+  rc = gicp_read_results(h, n, cs.data(), out);
+  h->last_evaluations = own_evaluations;
+  return rc;
 }
 
 int gicp_align(dgs_handle* h, const float* guess16, dgs_result* out) {

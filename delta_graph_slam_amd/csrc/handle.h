@@ -24,6 +24,7 @@ struct IcpItem;
 struct PgPair;    // pcl_gicp.hip
 struct PgItem;
 struct PgInit;
+struct GicpTarget;   // gicp.hip
 
 // Exact-NN index over a point cloud (nn_bvh.hip): Hilbert-sorted points, implicit complete 8-ary tree of AABBs.
 struct Bvh {
@@ -444,6 +445,7 @@ struct dgs_handle {
   dgs::DevBuf<double> mahal;                   // 6 doubles per source point
   dgs::DevBuf<dgs::GicpPair> gpairs;
   dgs::DevBuf<dgs::GicpItem> gitems;
+  dgs::DevBuf<dgs::GicpTarget> gtargets;       // gicp_align_pairs: one entry per distinct target cloud of the call
   // FAST_VGICP target model
   dgs::VgicpMap vmap{};
   dgs::DevBuf<dgs::VgicpVoxel> vvox;
@@ -580,6 +582,7 @@ int vgicp_voxels(dgs_handle* h, int64_t capacity, int32_t* coord3, int32_t* coun
 int gicp_ensure_target_covariance(dgs_handle* h);
 int gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);
+int gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* const* srcs, const float* guesses16, dgs_result* out);   // pair i against tgts[i]
 const float* gicp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int gicp_covariances(dgs_handle* h, int which, double* host_out6, int64_t n);
 int gicp_probe(dgs_handle* h, const double* T16_rowmajor, int error_only, double* err, double* H36, double* b6);

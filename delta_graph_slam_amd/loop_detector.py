@@ -62,7 +62,8 @@ class Loop:
 
 class LoopDetector:
     def __init__(self, params: Optional[dict] = None, registration=None, group=None, device: Optional[int] = None,
-                 cache_clouds: bool = False, filter_on_device: bool = False, cache_capacity: Optional[int] = None, local_only: bool = False):
+                 cache_clouds: bool = False, filter_on_device: bool = False, cache_capacity: Optional[int] = None, local_only: bool = False,
+                 batch_new_keyframes: bool = False):
         pr = dict(params or {})
         self.distance_thresh = float(pr.get("distance_thresh", 5.0))
         self.accum_distance_thresh = float(pr.get("accum_distance_thresh", 8.0))
@@ -79,6 +80,9 @@ class LoopDetector:
         # exists (side measurements of one rank of a multi-rank job: bench.py's other-order / parity legs)
         self.local_only = bool(local_only)
         self.last_records = None
+        # True: a tick's new keyframes are registered against their candidates in ONE Registration.align_pairs call (detect_batched) instead
+        # of one setInputTarget + align_batch per new keyframe.  OFF by default; only on one local FAST_GICP registration (_can_batch_tick)
+        self.batch_new_keyframes = bool(batch_new_keyframes)
         # keyframe id -> DeviceCloud: a keyframe that is a candidate tick after tick (delta_graph_slam_nodelet.cpp:816 calls
         # detect() every graph_update_interval) is uploaded and indexed once; needs KeyFrame.id to be unique
         self.cache_clouds = bool(cache_clouds)
@@ -130,12 +134,67 @@ class LoopDetector:
 
     # ---------------------------------------------------------------------------------------------- reference logic
     def detect(self, keyframes: Sequence[KeyFrame], new_keyframes: Sequence[KeyFrame]) -> List[Loop]:
+        if self.batch_new_keyframes and self._can_batch_tick():
+            return self.detect_batched(keyframes, new_keyframes)
         loops = []
         for nk in new_keyframes:
             cands = self.find_candidates(keyframes, nk)
             loop = self.matching(cands, nk)
             if loop is not None:
                 loops.append(loop)
+        return loops
+
+    def _can_batch_tick(self) -> bool:
+        """One local FAST_GICP registration that offers align_pairs_records: no group of devices, no second rank, no forced exchange."""
+        reg = self.registration
+        return (hasattr(reg, "align_pairs_records") and not hasattr(reg, "devices") and getattr(reg, "method", None) in ("FAST_GICP", "FAST_GICP_HIP")
+                and self._world()[1] == 1 and not self.force_exchange)
+
+    def detect_batched(self, keyframes: Sequence[KeyFrame], new_keyframes: Sequence[KeyFrame]) -> List[Loop]:
+        """detect() with all of the tick's registrations in one device call: every (new keyframe = target, candidate = source, guess_for)
+        pair of the tick goes to ONE align_pairs_records, then upstream's sequential loop is replayed on the host over the records.
+
+        The candidate sets do not depend on what is accepted earlier in the tick -- only the last-edge gate does, and
+        last_edge_accum_distance only grows during a tick, so a keyframe that fails the gate with the pre-tick value fails it later too.
+        The replay re-tests the gate against the running value in keyframe order, so the loops (and the final last_edge_accum_distance)
+        are the sequential detector's.  The price: the pairs of a keyframe that the replay gates out, because an earlier keyframe of the
+        same tick was accepted, have been registered for nothing and are discarded.
+
+        With cache_clouds, such a keyframe and its candidates have also been made resident, and _after_tick runs for it as for the
+        others (after the device call, so nothing in use is evicted): the sequential detector does neither for a keyframe it gates
+        out, so with a cache_capacity set the two may evict in a different order.  The loops do not depend on that."""
+        per_keyframe = []   # (new keyframe, its candidates, first record)
+        targets, sources, guesses = [], [], []
+        for nk in new_keyframes:
+            cands = self.find_candidates(keyframes, nk)   # the gate with the pre-tick last_edge_accum_distance: nothing below moves it before the replay
+            per_keyframe.append((nk, cands, len(targets)))
+            if not cands:
+                continue
+            t = self.resident(nk, as_target=True)
+            targets += [t] * len(cands)
+            sources += [self.resident(c) for c in cands]
+            guesses.append(self.guesses_for(nk, cands))
+        if not targets:
+            return []
+        records = self.registration.align_pairs_records(targets, sources, np.concatenate(guesses), compute_fitness=True,
+                                                        fitness_max_range=self.fitness_score_max_range)
+        if self.cache_clouds:
+            for nk, cands, _ in per_keyframe:
+                if cands:
+                    self._after_tick(nk, [nk.id] + [c.id for c in cands])
+        loops = []
+        for nk, cands, first in per_keyframe:
+            if not cands or nk.accum_distance - self.last_edge_accum_distance < self.distance_from_last_edge_thresh:
+                continue   # no candidates, or gated out by a loop accepted earlier in this tick: its records are discarded
+            rec = records[first:first + len(cands)].copy()
+            rec[:, 0] = np.arange(len(cands))
+            self.last_records = rec
+            best, best_score = self.select_best(rec)
+            if best < 0 or best_score > self.fitness_score_thresh:
+                continue
+            rel = rec[best, 4:20].reshape(4, 4).astype(np.float32)
+            self.last_edge_accum_distance = nk.accum_distance
+            loops.append(Loop(nk, cands[best], rel, transform3Dto2D(rel), best_score))
         return loops
 
     def find_candidates(self, keyframes: Sequence[KeyFrame], new_keyframe: KeyFrame) -> List[KeyFrame]:

@@ -446,6 +446,57 @@ class Registration:
         out[:, 4:20] = a["T"].reshape(n, 4, 4).transpose(0, 2, 1).reshape(n, 16)   # column-major -> row-major
         return out
 
+    # -- pairs that each name their own target (a tick of the loop detector: every new keyframe is a target) ---------------
+    def _align_pairs_raw(self, targets, sources, guesses, compute_fitness, fitness_max_range):
+        """-> ctypes array of dgs_result, one per pair (dgs_align_pairs_clouds); arrays and tensors are resident for the call only"""
+        targets, sources = list(targets), list(sources)
+        n = len(targets)
+        if len(sources) != n:
+            raise ValueError("targets and sources differ in length")
+        if n == 0:   # nothing to register, whatever shape an empty `guesses` has
+            return (L.Result * 1)()
+        gp = None
+        if guesses is not None:
+            if len(guesses) != n:
+                raise ValueError("guesses and the clouds differ in length")
+            ga = np.asarray(guesses, dtype=np.float32)
+            g = np.ascontiguousarray(ga.transpose(0, 2, 1).reshape(n, 16)) if ga.ndim == 3 else np.ascontiguousarray(np.stack([_col16(G) for G in guesses]))
+            gp = g.ctypes.data_as(C.c_void_p)
+        arr, objs, temps = self._cloud_array(targets + sources)
+        at = (C.c_void_p * max(n, 1))(*arr[:n])
+        as_ = (C.c_void_p * max(n, 1))(*arr[n:2 * n])
+        res = (L.Result * max(n, 1))()
+        try:
+            self._check(self._lib.dgs_align_pairs_clouds(self._h, n, C.cast(at, C.c_void_p), C.cast(as_, C.c_void_p), gp, 1 if compute_fitness else 0,
+                                                         float(fitness_max_range), res))
+        finally:
+            for c in temps:
+                c.close()
+        return res
+
+    def align_pairs(self, targets, sources, guesses=None, compute_fitness: bool = True, fitness_max_range: float = 1.7976931348623157e308):
+        """Pair i registers sources[i] against targets[i] from guesses[i]; all pairs advance together in one chain of launches
+        (dgs_align_pairs_clouds, FAST_GICP).  -> one dict per pair, as align_batch gives.  The registration's own target, source,
+        last result and counts() are untouched.  DeviceClouds are used as they are (and keep the index and covariances made here)."""
+        n = len(targets)
+        res = self._align_pairs_raw(targets, sources, guesses, compute_fitness, fitness_max_range)
+        return [dict(T=_from_col16(r.final_transformation), converged=bool(r.converged), iterations=r.iterations,
+                     evaluations=r.evaluations, status=r.status, score=r.score, fitness=r.fitness) for r in res[:n]]
+
+    def align_pairs_records(self, targets, sources, guesses=None, compute_fitness: bool = True, fitness_max_range: float = 1.7976931348623157e308):
+        """align_pairs as the loop detector's exchange records: float64 [n, 20], laid out as align_batch_records'."""
+        n = len(targets)
+        out = np.full((n, 20), -1.0, dtype=np.float64)
+        res = self._align_pairs_raw(targets, sources, guesses, compute_fitness, fitness_max_range)
+        if n == 0:
+            return out
+        a = np.frombuffer(res, dtype=_RESULT_DTYPE, count=n)
+        out[:, 1] = a["converged"] != 0
+        out[:, 2] = a["fitness"]
+        out[:, 3] = a["status"]
+        out[:, 4:20] = a["T"].reshape(n, 4, 4).transpose(0, 2, 1).reshape(n, 16)   # column-major -> row-major
+        return out
+
     # -- pcl::IterativeClosestPoint setters (ICP_HIP) ----------------------------------------------------------
     def _set_icp(self, field, value):
         if self.method != "ICP_HIP":
@@ -860,6 +911,12 @@ class RegistrationGroup:
         out[:, 3] = a["status"]
         out[:, 4:20] = a["T"].reshape(n, 4, 4).transpose(0, 2, 1).reshape(n, 16)
         return out
+
+
+    def align_pairs(self, *args, **kwargs):
+        raise NotImplementedError("align_pairs (per-pair targets) is served by a single-device Registration; the multi-GPU forms are not built")
+
+    align_pairs_records = align_pairs
 
 
 def select_registration_method(params: dict | None = None, device: int | None = None) -> Registration:

@@ -24,7 +24,10 @@
 
 #include <cfloat>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <unordered_map>
+#include <vector>
 
 #include <pcl/registration/registration.h>
 
@@ -58,6 +61,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     this->corr_dist_threshold_ = params_.gicp_max_correspondence_distance;
   }
   ~HipRegistration() override {
+    forgetPairClouds();
     if (handle_) dgs_destroy(handle_);
   }
   HipRegistration(const HipRegistration&) = delete;
@@ -145,6 +149,48 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     if (!handle_ || dgs_get_inlier_fraction(handle_, max_sq_dist, &f) != DGS_OK) return 0.0;
     return f;
   }
+  // n registrations that each name their own target in ONE device call (dgs_align_pairs_clouds; FAST_GICP): pair i is
+  // (targets[i], sources[i], guesses[i]) -- a tick of loop_detector.hpp:59-80, where every new keyframe is a target with a short candidate
+  // list of its own.  (*results)[i] is what setInputTarget(targets[i]) + setInputSource(sources[i]) + align(guesses[i]) would leave, with
+  // fitness = getFitnessScore(max_range) when compute_fitness.  The clouds are uploaded once per pcl::PointCloud object and kept with their
+  // index and covariances (an entry holds its cloud's shared pointer; forgetPairCloud(ptr) releases one, a new handle releases all).
+  // REQUIREMENT: a cloud passed here is immutable while it is resident, as KeyFrame::cloud is (keyframe.hpp:51).  The entry is keyed by
+  // the cloud object's address and its point count, so points edited in place at the same size are NOT seen: call forgetPairCloud(ptr)
+  // before using such a cloud again.  Entries (host cloud kept alive + device copy) live until forgetPairCloud / forgetPairClouds, a new
+  // handle or the destructor: call forgetPairCloud when a keyframe leaves the graph, or memory grows with every cloud ever passed.
+  // This object's own target, source and last result are untouched.  false: nothing was registered (lastError() says why) and *results
+  // is untouched; statuses of single pairs (empty source or target) are in the records.
+  bool alignPairs(const std::vector<PointCloudTargetConstPtr>& targets, const std::vector<PointCloudSourceConstPtr>& sources,
+                  const std::vector<Matrix4>& guesses, bool compute_fitness, double max_range, std::vector<dgs_result>* results) {
+    const size_t n = targets.size();
+    if (!results || sources.size() != n || (!guesses.empty() && guesses.size() != n) || !ensure_handle()) return false;
+    std::vector<dgs_cloud*> t(n, nullptr), s(n, nullptr);
+    std::vector<float> g(guesses.empty() ? 0 : n * 16);
+    for (size_t i = 0; i < n; i++) {
+      if (!targets[i] || !sources[i]) return false;
+      t[i] = resident(targets[i]);
+      s[i] = resident(sources[i]);
+      if (!t[i] || !s[i]) return false;
+      if (!guesses.empty()) std::memcpy(&g[i * 16], guesses[i].data(), sizeof(float) * 16);   // Eigen's column-major, as the ABI wants
+    }
+    std::vector<dgs_result> out(n);
+    if (dgs_align_pairs_clouds(handle_, (int32_t)n, t.data(), s.data(), guesses.empty() ? nullptr : g.data(), compute_fitness ? 1 : 0, max_range,
+                               out.data()) != DGS_OK)
+      return false;
+    results->swap(out);
+    return true;
+  }
+  void forgetPairCloud(const void* cloud) {
+    auto it = pair_clouds_.find(cloud);
+    if (it == pair_clouds_.end()) return;
+    dgs_cloud_destroy(it->second.cloud);
+    pair_clouds_.erase(it);
+  }
+  void forgetPairClouds() {
+    for (auto& kv : pair_clouds_) dgs_cloud_destroy(kv.second.cloud);
+    pair_clouds_.clear();
+  }
+
   const dgs_result& lastResult() const { return last_; }
   std::string lastError() const { return handle_ ? dgs_last_error(handle_) : dgs_last_error(nullptr); }
   dgs_handle* handle() { return handle_; }
@@ -164,6 +210,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
         params_.maximum_iterations == applied_.maximum_iterations &&
         params_.gicp_max_correspondence_distance == applied_.gicp_max_correspondence_distance)
       return true;
+    forgetPairClouds();   // their covariances were made under the old parameters
     if (handle_) dgs_destroy(handle_);
     handle_ = nullptr;
     if (dgs_create(&params_, &handle_) != DGS_OK) return false;
@@ -207,6 +254,26 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     }
     if (this->tree_) this->tree_->setInputCloud(sentinel_);
   }
+
+  // alignPairs: the device copy of a host cloud, keyed by the cloud object's address; `owner` keeps that address from passing to another cloud
+  struct PairCloud {
+    dgs_cloud* cloud;
+    size_t n;
+    std::shared_ptr<void> owner;   // a copy of the caller's smart pointer, whatever its kind (boost:: before PCL 1.11, std:: from it on)
+  };
+  template <class CloudPtr>
+  dgs_cloud* resident(const CloudPtr& cloud) {
+    const void* key = cloud.get();
+    const size_t n = cloud->points.size();
+    auto it = pair_clouds_.find(key);
+    if (it != pair_clouds_.end() && it->second.n == n) return it->second.cloud;
+    if (it != pair_clouds_.end()) forgetPairCloud(key);
+    dgs_cloud* c = nullptr;
+    if (dgs_cloud_create(handle_, reinterpret_cast<const float*>(cloud->points.data()), (int64_t)n, 0, &c) != DGS_OK) return nullptr;
+    pair_clouds_[key] = PairCloud{c, n, std::make_shared<CloudPtr>(cloud)};
+    return c;
+  }
+  std::unordered_map<const void*, PairCloud> pair_clouds_;
 
   typename pcl::PointCloud<PointTarget>::ConstPtr sentinel_;
   dgs_params params_{};

@@ -285,6 +285,20 @@ int dgs_set_input_source_cloud(dgs_handle* h, dgs_cloud* cloud);
 /* dgs_align_batch over resident clouds (loop_detector.hpp:137-156 with cached candidates) */
 int dgs_align_batch_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* sources, const float* guesses16, int32_t compute_fitness,
                            double fitness_max_range, dgs_result* results);
+/* n registrations that each name their own target: pair i = (targets[i], sources[i], guess i), all pairs advancing together in the same
+ * round launches (a tick of the loop detector: every new keyframe is a target with a short candidate list of its own).
+ * results[i] is what dgs_set_input_target_cloud(targets[i]) followed by dgs_align_batch_clouds over sources[i] alone would report (the
+ * sums of a pair are formed by as many workgroups as the batch leaves it, so poses agree to rounding, as between any two batches);
+ * fitness is getFitnessScore(fitness_max_range) of source i under its final transform against target i, from one
+ * dgs_calc_fitness_score_batch_clouds-style launch over all n edges (bit-identical in any batch).  FAST_GICP handles only: any other
+ * method is DGS_ERR_UNSUPPORTED with the method named in dgs_last_error (their target models live on the handle, not on the cloud).
+ * n == 0: DGS_OK without a launch.  A NULL cloud or a cloud of another device: DGS_ERR_INVALID_ARGUMENT.  An empty source: status
+ * DGS_ERR_NO_SOURCE for that pair, transform = guess; an empty target: DGS_ERR_NO_TARGET for that pair; the other pairs run.  A cloud may be
+ * the target of any number of pairs, the source of others, and both sides of one pair.  Missing indices of all clouds are built in one
+ * batched build and kept, covariances are made once per cloud and kept (dgs_params.gicp_cov_jacobi_svd is honoured).  The handle's own
+ * registration target / source / last result and what dgs_get_counts reports are untouched.  Additions only: DGS_ABI_VERSION is unchanged. */
+int dgs_align_pairs_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* targets, dgs_cloud* const* sources, const float* guesses16,
+                           int32_t compute_fitness, double fitness_max_range, dgs_result* results);
 
 /* LoopDetector::find_candidates (/root/reference/include/hdl_graph_slam/loop_detector.hpp:83-111) over n keyframes on the device
  * (second half): keyframe i is a candidate iff
