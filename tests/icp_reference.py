@@ -53,7 +53,10 @@ def f32_matmul4(A, B):
 
 
 def icp_align(orc, tgt, src, guess=None, max_corr=2.5, transformation_epsilon=0.01, maximum_iterations=64, reciprocal=False,
-              euclidean_fitness_epsilon=-DBL_MAX, rotation_epsilon=0.0):
+              euclidean_fitness_epsilon=-DBL_MAX, rotation_epsilon=0.0, trace=None, nudge=0):
+    """trace: a list that receives, per correspondence pass, dict(d2, keep, j, W) (tests/test_icp_gicp_edge_cases_cpu.py reads the
+    margins of every decision there).  nudge = +1 / -1: every entry of T_k's three rows moved one float ulp up / down before it is used,
+    the stability probe of the same file."""
     tgt = np.asarray(tgt, np.float32)[:, :3]
     src = np.asarray(src, np.float32)[:, :3]
     final = np.eye(4, dtype=np.float32) if guess is None else np.asarray(guess, np.float32).copy()
@@ -75,10 +78,14 @@ def icp_align(orc, tgt, src, guess=None, max_corr=2.5, transformation_epsilon=0.
             ok = (i2 == kept) & (d2r.astype(np.float64) <= max_sq)
             keep[kept[~ok]] = False
         n = int(keep.sum())
+        if trace is not None:
+            trace.append(dict(d2=d2.copy(), keep=keep.copy(), j=j.copy(), W=W.copy(), o=o.copy()))
         if n < 3:
             converged = False
             break
         Tk = kabsch(W[keep], tgt[j[keep]], o).astype(np.float32)
+        if nudge:
+            Tk[:3] = np.nextafter(Tk[:3], np.float32(np.inf if nudge > 0 else -np.inf))
         mse = float(d2[keep].astype(np.float64).sum() / n)
         W = f32_transform(Tk, W)
         final = f32_matmul4(Tk, final)

@@ -374,9 +374,11 @@ class Bfgs:
         return SUCCESS
 
 
-def estimate_bfgs(x0, P, Q, M, max_inner):
-    """estimateRigidTransformationBFGS from state x0 -> (x, f, inner iterations, evaluation passes, the optimiser)."""
-    opt = Bfgs(lambda x: evaluate(x, P, Q, M), x0)
+def estimate_bfgs(x0, P, Q, M, max_inner, perturb=None):
+    """estimateRigidTransformationBFGS from state x0 -> (x, f, inner iterations, evaluation passes, the optimiser).  perturb: maps every
+    (f, g) the functor returns to another one (a stand-in for another summation order, tests/test_icp_gicp_edge_cases_cpu.py)."""
+    fdf = (lambda x: evaluate(x, P, Q, M)) if perturb is None else (lambda x: perturb(*evaluate(x, P, Q, M)))
+    opt = Bfgs(fdf, x0)
     inner = 0
     while True:
         inner += 1
@@ -417,8 +419,8 @@ def _nn_finite(orc, tgt, fin_t, queries):
     return j, d2
 
 
-def correspondences(orc, tgt, output, T, guess, Cs, Ct, max_corr):
-    """One correspondence pass: (kept source indices, their target indices, M of each)."""
+def correspondences(orc, tgt, output, T, guess, Cs, Ct, max_corr, trace=None):
+    """One correspondence pass: (kept source indices, their target indices, M of each).  trace: a list that receives dict(d2, keep, j)."""
     tgt = np.asarray(tgt, np.float32)[:, :3]
     output = np.asarray(output, np.float32)[:, :3]
     fin_t = np.nonzero(np.isfinite(tgt).all(axis=1))[0]
@@ -426,6 +428,8 @@ def correspondences(orc, tgt, output, T, guess, Cs, Ct, max_corr):
     query = f32_transform(T, output)
     j, d2 = _nn_finite(orc, tgt, fin_t, query)
     keep = (j >= 0) & (d2.astype(np.float64) < float(max_corr) * float(max_corr))
+    if trace is not None:
+        trace.append(dict(d2=d2.copy(), keep=keep.copy(), j=j.copy()))
     src_i = np.nonzero(keep)[0]
     tgt_j = j[keep]
     RC = R[None] @ Cs[src_i]
@@ -434,7 +438,7 @@ def correspondences(orc, tgt, output, T, guess, Cs, Ct, max_corr):
 
 
 def gicp_align(orc, tgt, src, guess=None, max_corr=2.5, transformation_epsilon=0.01, maximum_iterations=64, k=20,
-               max_optimizer_iterations=20, rotation_epsilon=2e-3, gicp_epsilon=1e-3, Ct=None, Cs=None):
+               max_optimizer_iterations=20, rotation_epsilon=2e-3, gicp_epsilon=1e-3, Ct=None, Cs=None, trace=None, perturb=None):
     tgt = np.asarray(tgt, np.float32)[:, :3]
     src = np.asarray(src, np.float32)[:, :3]
     guess = np.eye(4, dtype=np.float32) if guess is None else np.asarray(guess, np.float32).copy()
@@ -448,10 +452,10 @@ def gicp_align(orc, tgt, src, guess=None, max_corr=2.5, transformation_epsilon=0
     traj, searches = [], []
     while not converged:
         evaluations += 1
-        si, tj, Mi = correspondences(orc, tgt, output, T, guess, Cs, Ct, max_corr)
+        si, tj, Mi = correspondences(orc, tgt, output, T, guess, Cs, Ct, max_corr, trace)
         if si.size < 4:
             break
-        x, f, inner, passes, opt = estimate_bfgs(state_of(T), output[si], tgt[tj], Mi, max_optimizer_iterations)
+        x, f, inner, passes, opt = estimate_bfgs(state_of(T), output[si], tgt[tj], Mi, max_optimizer_iterations, perturb)
         evaluations += passes
         searches += opt.searches
         # a line search that ended in roundoff (NoProgress, or its step budget spent) turns on comparisons of f values a few ulps
@@ -468,7 +472,7 @@ def gicp_align(orc, tgt, src, guess=None, max_corr=2.5, transformation_epsilon=0
                     delta = cd
         iterations += 1
         score = f
-        traj.append(dict(T=T.copy(), n=int(si.size), inner=inner, passes=passes, f=f, roundoff=roundoff))
+        traj.append(dict(T=T.copy(), n=int(si.size), inner=inner, passes=passes, f=f, roundoff=roundoff, delta=delta))
         if iterations >= maximum_iterations or delta < 1:
             converged = True
     final = f32_matmul4(T, guess)
