@@ -79,11 +79,16 @@ struct SliceTable {
   std::vector<int> slice0, n_slices, blk;   // blk: pageable, read by upload()'s copy -- the caller syncs the stream before this object goes
   int total_slices = 0;
   SliceTable(int n, CloudState* const* srcs, int points_per_slice) : slice0(n), n_slices(n) {
-    for (int i = 0; i < n; i++) {
-      slice0[i] = total_slices;
-      n_slices[i] = (int)((srcs[i]->n + points_per_slice - 1) / points_per_slice);
-      total_slices += n_slices[i];
-    }
+    for (int i = 0; i < n; i++) add(i, srcs[i]->n, points_per_slice);
+  }
+  // live sizes: 0 for a pair that never becomes active, so that it owns no slice (and no workgroup) whatever its cloud holds
+  SliceTable(const std::vector<int64_t>& live_n, int points_per_slice) : slice0(live_n.size()), n_slices(live_n.size()) {
+    for (size_t i = 0; i < live_n.size(); i++) add((int)i, live_n[i], points_per_slice);
+  }
+  void add(int i, int64_t points, int points_per_slice) {
+    slice0[i] = total_slices;
+    n_slices[i] = (int)((points + points_per_slice - 1) / points_per_slice);
+    total_slices += n_slices[i];
   }
   int upload(dgs_handle* h, int row_stride) {
     DGS_HIP_TRY(h, h->slice_blk_pair.reserve((size_t)std::max(total_slices, 1)));

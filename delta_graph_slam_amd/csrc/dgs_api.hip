@@ -958,8 +958,9 @@ int dgs_align_pairs_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* targets, 
                            double fitness_max_range, dgs_result* results) {
   if (!h || n < 0 || (n > 0 && (!targets || !sources || !results))) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
-  if (h->prm.method != DGS_METHOD_GICP) {
-    h->err = std::string("dgs_align_pairs_clouds serves FAST_GICP only; this handle's method is ") + method_name(h->prm.method) +
+  const bool pcl_gicp = h->prm.method == DGS_METHOD_PCL_GICP;
+  if (h->prm.method != DGS_METHOD_GICP && !pcl_gicp) {
+    h->err = std::string("dgs_align_pairs_clouds serves FAST_GICP and GICP_HIP; this handle's method is ") + method_name(h->prm.method) +
              " (its target model lives on the handle, not on the cloud)";
     return DGS_ERR_UNSUPPORTED;
   }
@@ -971,7 +972,9 @@ int dgs_align_pairs_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* targets, 
       return DGS_ERR_INVALID_ARGUMENT;
     }
   for (int i = 0; i < n; i++) fail_result(&results[i], guesses16 ? guesses16 + 16 * i : nullptr, DGS_OK);
-  int rc = gicp_align_pairs(h, n, targets, sources, guesses16, results);
+  int rc = pcl_gicp ? pcl_gicp_align_pairs(h, n, targets, sources, guesses16, results) : gicp_align_pairs(h, n, targets, sources, guesses16, results);
+  std::vector<int> status((size_t)n);   // GICP_HIP: a cloud of fewer than k points fails the pairs that name it
+  for (int i = 0; i < n; i++) status[i] = results[i].status;
   if (rc == DGS_OK && compute_fitness) {
     // getFitnessScore of source i under its final transform against target i: the edge (target i, source i, T_i) of the batched scorer
     std::vector<float> T((size_t)n * 16);
@@ -986,7 +989,7 @@ int dgs_align_pairs_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* targets, 
     return rc;
   }
   for (int i = 0; i < n; i++) {   // what dgs_align reports for the pair alone: a missing target first, then a missing source
-    const int st = targets[i]->st.n <= 0 ? DGS_ERR_NO_TARGET : sources[i]->st.n <= 0 ? DGS_ERR_NO_SOURCE : DGS_OK;
+    const int st = targets[i]->st.n <= 0 ? DGS_ERR_NO_TARGET : sources[i]->st.n <= 0 ? DGS_ERR_NO_SOURCE : status[i];
     if (st != DGS_OK) fail_result(&results[i], guesses16 ? guesses16 + 16 * i : nullptr, st);
   }
   return DGS_OK;

@@ -24,6 +24,7 @@ struct IcpItem;
 struct PgPair;    // pcl_gicp.hip
 struct PgItem;
 struct PgInit;
+struct PgTarget;
 struct GicpTarget;   // gicp.hip
 
 // Exact-NN index over a point cloud (nn_bvh.hip): Hilbert-sorted points, implicit complete 8-ary tree of AABBs.
@@ -478,6 +479,7 @@ struct dgs_handle {
   dgs::DevBuf<dgs::PgPair> pgpairs;
   dgs::DevBuf<dgs::PgItem> pgitems;
   dgs::DevBuf<dgs::PgInit> pginits;
+  dgs::DevBuf<dgs::PgTarget> pgtargets;        // pcl_gicp_align_pairs: one entry per distinct target cloud of the call
   dgs::DevBuf<float4> pg_w;                    // per source slot (walk order): output = guess * source, w = original index
   dgs::DevBuf<float4> pg_q;                    // per source slot: the target point of this outer iteration's pair, w = 1 kept / 0 not
   dgs::DevBuf<double> pg_m;                    // per source slot: M_i, 9 planes of doubles (structure of arrays)
@@ -626,6 +628,7 @@ void building_cloud_release(dgs_handle* h);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);
+int pcl_gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* const* srcs, const float* guesses16, dgs_result* out);   // pair i against tgts[i]
 const float* pcl_gicp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int pcl_gicp_covariances(dgs_handle* h, int which, double* host_out9, int64_t n);
 int pcl_gicp_evaluate(dgs_handle* h, const double* x6, int32_t* m, double* f, double* g6);

@@ -15,6 +15,7 @@
 //     line-search state machine of bfgs.h up to its next evaluation request, or PCL's convergence test and the next correspondence pass.
 //   * Every pass computes f and g together: a trial step costs one pass, and a cached alpha none.
 //   * The host enqueues launches in chunks and polls a pinned done counter once per chunk: no host round trip per evaluation.
+#include <algorithm>
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -55,7 +56,8 @@ struct PgItem {
   const float4* src_sorted;  // the same points in their own Hilbert index's order, w = original index
   const double* cs;          // the source's PCL-style covariances (9 per point, caller's order)
   long long off;             // first slot of this pair in the batch-wide slot arrays
-  int n, slice0, n_slices, pad;
+  int n, slice0, n_slices;
+  int tgt;                   // per-pair targets (pcl_gicp_align_pairs): the pair's entry of the launch's target table; 0 on the single-target path
 };
 
 struct PgInit {
@@ -546,17 +548,13 @@ __global__ __launch_bounds__(kBlock) void pg_prepare_kernel(const PgItem* __rest
   W[it.off + pos] = o;
 }
 
-// One round of every active pair: its correspondence pass or its evaluation pass, then (last workgroup) the pair's closing.
-__global__ __launch_bounds__(kBlock) void pg_round_kernel(const BvhView tv, const float4* __restrict__ tgt, const double* __restrict__ tcov, const PgItem* __restrict__ items,
-                                                          PgPair* __restrict__ pairs, const int* __restrict__ blk_pair, const float4* __restrict__ W,
-                                                          float4* __restrict__ Q, double* __restrict__ Mp, double* __restrict__ rows, const PgConsts c,
-                                                          int* __restrict__ done_counter, float* __restrict__ traj_T, int* __restrict__ traj_i,
-                                                          double* __restrict__ traj_f) {
+// One round of one active pair's slice: its correspondence pass or its evaluation pass, then (last workgroup) the pair's closing.  The
+// body of both round kernels below; (tv, tgt, tcov) is the pair's target: index view, points in the caller's order, PCL-style covariances.
+__device__ __forceinline__ void pg_round_body(const BvhView tv, const float4* __restrict__ tgt, const double* __restrict__ tcov, const PgItem it, PgPair* st,
+                                              const int pair, const float4* __restrict__ W, float4* __restrict__ Q, double* __restrict__ Mp,
+                                              double* __restrict__ rows, const PgConsts c, int* __restrict__ done_counter, float* __restrict__ traj_T,
+                                              int* __restrict__ traj_i, double* __restrict__ traj_f) {
 #pragma clang fp contract(off)
-  const int pair = blk_pair[blockIdx.x];
-  PgPair* st = pairs + pair;
-  if (!st->active) return;   // uniform per pair: the closing workgroup clears it after every slice of this launch has read it
-  const PgItem it = items[pair];
   const int slice = (int)blockIdx.x - it.slice0;
   const int n = it.n;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & 7;
@@ -657,6 +655,44 @@ __global__ __launch_bounds__(kBlock) void pg_round_kernel(const BvhView tv, cons
   if (threadIdx.x == 0) pg_close(st, tot, c, done_counter, traj_T, traj_i, traj_f, pair);
 }
 
+// One round of every active pair against the handle's target.
+__global__ __launch_bounds__(kBlock) void pg_round_kernel(const BvhView tv, const float4* __restrict__ tgt, const double* __restrict__ tcov, const PgItem* __restrict__ items,
+                                                          PgPair* __restrict__ pairs, const int* __restrict__ blk_pair, const float4* __restrict__ W,
+                                                          float4* __restrict__ Q, double* __restrict__ Mp, double* __restrict__ rows, const PgConsts c,
+                                                          int* __restrict__ done_counter, float* __restrict__ traj_T, int* __restrict__ traj_i,
+                                                          double* __restrict__ traj_f) {
+  const int pair = blk_pair[blockIdx.x];
+  PgPair* st = pairs + pair;
+  if (!st->active) return;   // uniform per pair: the closing workgroup clears it after every slice of this launch has read it
+  const PgItem it = items[pair];
+  pg_round_body(tv, tgt, tcov, it, st, pair, W, Q, Mp, rows, c, done_counter, traj_T, traj_i, traj_f);
+}
+
+// Per-pair targets (pcl_gicp_align_pairs): the same round, but the target's index view, points and covariances are not kernel arguments.
+// They are an entry of a device table, chosen by PgItem::tgt.  blk_pair[blockIdx.x] is workgroup-uniform and items[pair] a scalar load, so
+// targets[it.tgt] has a uniform address: its 64 bytes come in through scalar loads, once per wave, and live in SGPRs where pg_round_kernel
+// keeps its arguments.  No lane loads a target field.
+struct PgTarget {
+  BvhView b;            // exact-NN index of the target cloud
+  const float4* pts;    // its points in the caller's order
+  const double* pcov;   // its PCL-style covariances, 9 doubles per point
+  int n, pad;
+};
+static_assert(sizeof(PgTarget) == 64, "one target is one 64-byte scalar load");
+
+__global__ __launch_bounds__(kBlock) void pg_round_pairs_kernel(const PgTarget* __restrict__ targets, const PgItem* __restrict__ items, PgPair* __restrict__ pairs,
+                                                                const int* __restrict__ blk_pair, const float4* __restrict__ W, float4* __restrict__ Q,
+                                                                double* __restrict__ Mp, double* __restrict__ rows, const PgConsts c,
+                                                                int* __restrict__ done_counter, float* __restrict__ traj_T, int* __restrict__ traj_i,
+                                                                double* __restrict__ traj_f) {
+  const int pair = blk_pair[blockIdx.x];
+  PgPair* st = pairs + pair;
+  if (!st->active) return;
+  const PgItem it = items[pair];
+  const PgTarget t = targets[it.tgt];   // uniform address: scalar loads
+  pg_round_body(t.b, t.pts, t.pcov, it, st, pair, W, Q, Mp, rows, c, done_counter, traj_T, traj_i, traj_f);
+}
+
 __global__ void pg_init_kernel(PgPair* __restrict__ pairs, const PgInit* __restrict__ inits, const int n_pairs) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= n_pairs) return;
@@ -737,35 +773,50 @@ static int ensure_pcov(dgs_handle* h, CloudState& c) {
 
 using PgStaging = BatchStaging<PgInit, PgItem, PgPair>;
 
-// computeTransformation for every source of a batch against the handle's target (probe != nullptr: one pair, the test hook's single
-// correspondence + evaluation pass).  Per-pair status in out[i].status.
+// Per-pair targets of a batch (pcl_gicp_align_pairs): the distinct target clouds, indexed and with their covariances, and pair i's entry
+// of[i] of that table; of[i] < 0: the pair has no usable target and never becomes active.
+struct PgTargets {
+  int n;
+  CloudState* const* clouds;
+  const int* of;
+};
+
+// computeTransformation for every source of a batch, against the handle's target or (tg != nullptr) each against the target it names
+// (probe != nullptr: one pair, the test hook's single correspondence + evaluation pass; single-target only).  Per-pair status in
+// out[i].status.  A pair that never becomes active -- an empty source, a source of fewer than k points, no usable target -- owns no
+// slice and no slot of the work arrays.
 static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out, const double* probe_x,
-                        PgPair* probe_out) {
+                        PgPair* probe_out, const PgTargets* tg = nullptr) {
   hipStream_t st = h->stream;
   PgConsts c = pg_consts(h);
-  int rc = ensure_target_index(h);
-  if (rc) return rc;
-  rc = ensure_pcov(h, *h->tgt);
-  if (rc) return rc;
+  int rc = DGS_OK;
+  if (!tg) {
+    rc = ensure_target_index(h);
+    if (rc) return rc;
+    rc = ensure_pcov(h, *h->tgt);
+    if (rc) return rc;
+  }
   const int k = h->prm.gicp_correspondence_randomness;
   int64_t total = 0;
   int n_live = 0;
-  SliceTable slices(n, srcs, kPgSlicePoints);
-  const int total_slices = slices.total_slices;
   std::vector<int> skip(n, 0);
   std::vector<long long> off(n);
+  std::vector<int64_t> live_n(n, 0);
   for (int i = 0; i < n; i++) {
     CloudState& s = *srcs[i];
     off[i] = total;
-    total += s.n;
     if (s.n <= 0) continue;
-    if ((int64_t)k > s.n) { skip[i] = 1; continue; }   // computeCovariances refuses the cloud: this registration fails
+    if ((int64_t)k > s.n || (tg && tg->of[i] < 0)) { skip[i] = 1; continue; }   // computeCovariances refuses the cloud: this registration fails
     rc = ensure_walk_order(h, s);
     if (rc) return rc;
     rc = ensure_pcov(h, s);
     if (rc) return rc;
+    live_n[i] = s.n;
+    total += s.n;
     n_live++;
   }
+  SliceTable slices(live_n, kPgSlicePoints);
+  const int total_slices = slices.total_slices;
   c.total = std::max<int64_t>(total, 1);
   DGS_HIP_TRY(h, h->pgpairs.reserve(n));
   DGS_HIP_TRY(h, h->pgitems.reserve(n));
@@ -778,7 +829,9 @@ static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const flo
   DGS_HIP_TRY(h, h->pg_traj_f.reserve((size_t)n * c.traj_cap));
   DGS_HIP_TRY(h, h->done_counter.reserve(16));
   const PgStaging stg(h, n);
-  if (stg.ensure() != DGS_OK) return DGS_ERR_HIP;
+  // the target table travels from the pinned block, behind the batch's own staging
+  const size_t tab_off = (stg.bytes + 63) & ~(size_t)63, tab_bytes = tg ? (size_t)std::max(tg->n, 1) * sizeof(PgTarget) : 0;
+  if (ensure_pinned(h, tab_off + tab_bytes) != DGS_OK) return DGS_ERR_HIP;
   PgInit* hin = stg.inits();
   PgItem* hit = stg.items();
   for (int i = 0; i < n; i++) {
@@ -795,27 +848,40 @@ static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const flo
     hit[i].src_sorted = walk_sorted(s);
     hit[i].cs = s.pcov.ptr;
     hit[i].off = off[i];
-    hit[i].n = (skip[i] || s.n <= 0) ? 0 : (int)s.n;   // a skipped pair has no slot to walk (its workgroups return at once anyway)
+    hit[i].n = (int)live_n[i];
     hit[i].slice0 = slices.slice0[i];
     hit[i].n_slices = slices.n_slices[i];
-    hit[i].pad = 0;
+    hit[i].tgt = tg ? std::max(tg->of[i], 0) : 0;
   }
   rc = slices.upload(h, kPgPad);
   if (rc) return rc;
   DGS_HIP_TRY(h, hipMemcpyAsync(h->pginits.ptr, hin, (size_t)n * sizeof(PgInit), hipMemcpyHostToDevice, st));
   DGS_HIP_TRY(h, hipMemcpyAsync(h->pgitems.ptr, hit, (size_t)n * sizeof(PgItem), hipMemcpyHostToDevice, st));
+  if (tg && n_live > 0) {
+    DGS_HIP_TRY(h, h->pgtargets.reserve((size_t)tg->n));
+    PgTarget* tab = reinterpret_cast<PgTarget*>(reinterpret_cast<char*>(h->pinned) + tab_off);
+    for (int t = 0; t < tg->n; t++) {
+      const CloudState& tc = *tg->clouds[t];
+      tab[t] = PgTarget{make_bvh_view(tc.bvh), tc.pts.ptr, tc.pcov.ptr, (int)tc.n, 0};
+    }
+    DGS_HIP_TRY(h, hipMemcpyAsync(h->pgtargets.ptr, tab, (size_t)tg->n * sizeof(PgTarget), hipMemcpyHostToDevice, st));
+  }
   DGS_HIP_TRY(h, hipMemsetAsync(h->done_counter.ptr, 0, 16 * sizeof(int), st));
   hipLaunchKernelGGL(pg_init_kernel, dim3((n + 63) / 64), dim3(64), 0, st, h->pgpairs.ptr, h->pginits.ptr, n);
   if (total_slices > 0)
     hipLaunchKernelGGL(pg_prepare_kernel, dim3(total_slices), dim3(kBlock), 0, st, h->pgitems.ptr, h->pgpairs.ptr, h->slice_blk_pair.ptr, h->pg_w.ptr);
   DGS_HIP_TRY(h, hipGetLastError());
   DGS_HIP_TRY(h, hipStreamSynchronize(st));   // slices.blk is pageable host memory
-  const BvhView tv = make_bvh_view(h->tgt->bvh);
+  const BvhView tv = tg ? BvhView{} : make_bvh_view(h->tgt->bvh);
   auto launch_round = [&]() {
     int slot = prof_begin(h, DGS_K_NN_SEARCH);
-    hipLaunchKernelGGL(pg_round_kernel, dim3(total_slices), dim3(kBlock), 0, st, tv, h->tgt->pts.ptr, h->tgt->pcov.ptr, h->pgitems.ptr, h->pgpairs.ptr,
-                       h->slice_blk_pair.ptr, h->pg_w.ptr, h->pg_q.ptr, h->pg_m.ptr, h->slice_rows.ptr, c, h->done_counter.ptr, h->pg_traj_T.ptr, h->pg_traj_i.ptr,
-                       h->pg_traj_f.ptr);
+    if (tg)
+      hipLaunchKernelGGL(pg_round_pairs_kernel, dim3(total_slices), dim3(kBlock), 0, st, h->pgtargets.ptr, h->pgitems.ptr, h->pgpairs.ptr, h->slice_blk_pair.ptr,
+                         h->pg_w.ptr, h->pg_q.ptr, h->pg_m.ptr, h->slice_rows.ptr, c, h->done_counter.ptr, h->pg_traj_T.ptr, h->pg_traj_i.ptr, h->pg_traj_f.ptr);
+    else
+      hipLaunchKernelGGL(pg_round_kernel, dim3(total_slices), dim3(kBlock), 0, st, tv, h->tgt->pts.ptr, h->tgt->pcov.ptr, h->pgitems.ptr, h->pgpairs.ptr,
+                         h->slice_blk_pair.ptr, h->pg_w.ptr, h->pg_q.ptr, h->pg_m.ptr, h->slice_rows.ptr, c, h->done_counter.ptr, h->pg_traj_T.ptr, h->pg_traj_i.ptr,
+                         h->pg_traj_f.ptr);
     prof_end(h, DGS_K_NN_SEARCH, slot);
   };
   if (n_live > 0) {
@@ -864,6 +930,48 @@ int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out) {
     return DGS_ERR_INVALID_ARGUMENT;
   }
   return rc;
+}
+
+// ---- per-pair targets: pair i = (tgts[i], srcs[i], guess i), every pair in its own phase of the same round launches
+// (pg_round_pairs_kernel).  The handle's own target, source, last result and counts are not touched; the trajectory arrays answer for
+// this batch afterwards.  A pair whose target is empty or has fewer than k points never becomes active: out[i].status says which (an
+// empty target first, then an empty source, then k > n of either cloud); the other pairs run.
+int pcl_gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* const* srcs, const float* guesses16, dgs_result* out) {
+  const int k = h->prm.gicp_correspondence_randomness;
+  if (k > kKnnMax) {
+    h->err = "reg_correspondence_randomness > 32 is not supported by the HIP k-NN";
+    return DGS_ERR_UNSUPPORTED;
+  }
+  // the distinct targets that can serve (not empty, at least k points), by pointer, in order of first appearance
+  std::vector<dgs_cloud*> uniq;
+  std::vector<int> tgt_of((size_t)n);
+  for (int i = 0; i < n; i++) {
+    tgt_of[i] = -1;
+    if (tgts[i]->st.n <= 0 || (int64_t)k > tgts[i]->st.n) continue;
+    const auto at = std::find(uniq.begin(), uniq.end(), tgts[i]);
+    tgt_of[i] = (int)(at - uniq.begin());
+    if (at == uniq.end()) uniq.push_back(tgts[i]);
+  }
+  // every index that is missing, of targets and sources alike, in ONE batched build (the bits of a single build: fitness_batch.hip)
+  std::vector<dgs_cloud*> all(tgts, tgts + n);
+  all.insert(all.end(), srcs, srcs + n);
+  int rc = fitness_batch_build_indices(h, 2 * n, all.data());
+  if (rc) return rc;
+  std::vector<CloudState*> tc(uniq.size()), cs((size_t)n);
+  for (size_t t = 0; t < uniq.size(); t++) {   // cached on the cloud under (k, epsilon): shared with every other path that uses the cloud
+    tc[t] = &uniq[t]->st;
+    rc = ensure_pcov(h, *tc[t]);
+    if (rc) return rc;
+  }
+  for (int i = 0; i < n; i++) cs[i] = &srcs[i]->st;
+  const PgTargets tg{(int)uniq.size(), tc.data(), tgt_of.data()};
+  const int64_t own_evaluations = h->last_evaluations;   // dgs_get_counts keeps reporting the handle's own last align / batch
+  rc = pg_run_batch(h, n, cs.data(), guesses16, out, nullptr, nullptr, &tg);
+  h->last_evaluations = own_evaluations;
+  if (rc) return rc;
+  for (int i = 0; i < n; i++)
+    if (tgts[i]->st.n <= 0) out[i].status = DGS_ERR_NO_TARGET;
+  return DGS_OK;
 }
 
 // device pointer and stride of the batch's final transforms (column-major float[16] per pair) for the fitness kernel
@@ -918,7 +1026,7 @@ int pcl_gicp_trajectory(dgs_handle* h, int pair, float* T16s, int32_t* n_corr, i
 }
 
 void pcl_gicp_release(dgs_handle* h) {
-  h->pgpairs.release(); h->pgitems.release(); h->pginits.release(); h->pg_w.release(); h->pg_q.release(); h->pg_m.release();
+  h->pgpairs.release(); h->pgitems.release(); h->pginits.release(); h->pgtargets.release(); h->pg_w.release(); h->pg_q.release(); h->pg_m.release();
   h->pg_traj_T.release(); h->pg_traj_i.release(); h->pg_traj_f.release();
 }
 

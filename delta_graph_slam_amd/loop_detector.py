@@ -81,7 +81,7 @@ class LoopDetector:
         self.local_only = bool(local_only)
         self.last_records = None
         # True: a tick's new keyframes are registered against their candidates in ONE Registration.align_pairs call (detect_batched) instead
-        # of one setInputTarget + align_batch per new keyframe.  OFF by default; only on one local FAST_GICP registration (_can_batch_tick)
+        # of one setInputTarget + align_batch per new keyframe.  OFF by default; only on one local FAST_GICP or GICP_HIP registration (_can_batch_tick)
         self.batch_new_keyframes = bool(batch_new_keyframes)
         # keyframe id -> DeviceCloud: a keyframe that is a candidate tick after tick (delta_graph_slam_nodelet.cpp:816 calls
         # detect() every graph_update_interval) is uploaded and indexed once; needs KeyFrame.id to be unique
@@ -145,9 +145,11 @@ class LoopDetector:
         return loops
 
     def _can_batch_tick(self) -> bool:
-        """One local FAST_GICP registration that offers align_pairs_records: no group of devices, no second rank, no forced exchange."""
+        """One local FAST_GICP or GICP_HIP registration that offers align_pairs_records: no group of devices, no second rank, no forced
+        exchange."""
         reg = self.registration
-        return (hasattr(reg, "align_pairs_records") and not hasattr(reg, "devices") and getattr(reg, "method", None) in ("FAST_GICP", "FAST_GICP_HIP")
+        return (hasattr(reg, "align_pairs_records") and not hasattr(reg, "devices")
+                and getattr(reg, "method", None) in ("FAST_GICP", "FAST_GICP_HIP", "GICP_HIP", "GICP_OMP_HIP")
                 and self._world()[1] == 1 and not self.force_exchange)
 
     def detect_batched(self, keyframes: Sequence[KeyFrame], new_keyframes: Sequence[KeyFrame]) -> List[Loop]:

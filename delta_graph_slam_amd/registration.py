@@ -476,8 +476,10 @@ class Registration:
 
     def align_pairs(self, targets, sources, guesses=None, compute_fitness: bool = True, fitness_max_range: float = 1.7976931348623157e308):
         """Pair i registers sources[i] against targets[i] from guesses[i]; all pairs advance together in one chain of launches
-        (dgs_align_pairs_clouds, FAST_GICP).  -> one dict per pair, as align_batch gives.  The registration's own target, source,
-        last result and counts() are untouched.  DeviceClouds are used as they are (and keep the index and covariances made here)."""
+        (dgs_align_pairs_clouds; FAST_GICP and GICP_HIP / GICP_OMP_HIP).  -> one dict per pair, as align_batch gives.  The registration's own target, source,
+        last result and counts() are untouched.  DeviceClouds are used as they are (and keep the index and covariances made here).
+        GICP_HIP: a cloud of fewer than k points fails the pairs that name it (status 1), not the call; pcl_gicp_trajectory(i) answers
+        for pair i of this call afterwards."""
         n = len(targets)
         res = self._align_pairs_raw(targets, sources, guesses, compute_fitness, fitness_max_range)
         return [dict(T=_from_col16(r.final_transformation), converged=bool(r.converged), iterations=r.iterations,

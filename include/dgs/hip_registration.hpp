@@ -149,7 +149,8 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     if (!handle_ || dgs_get_inlier_fraction(handle_, max_sq_dist, &f) != DGS_OK) return 0.0;
     return f;
   }
-  // n registrations that each name their own target in ONE device call (dgs_align_pairs_clouds; FAST_GICP): pair i is
+  // n registrations that each name their own target in ONE device call (dgs_align_pairs_clouds; no method gate here: the
+  // library serves FAST_GICP and GICP_HIP / GICP_OMP_HIP and names any other method in lastError()): pair i is
   // (targets[i], sources[i], guesses[i]) -- a tick of loop_detector.hpp:59-80, where every new keyframe is a target with a short candidate
   // list of its own.  (*results)[i] is what setInputTarget(targets[i]) + setInputSource(sources[i]) + align(guesses[i]) would leave, with
   // fitness = getFitnessScore(max_range) when compute_fitness.  The clouds are uploaded once per pcl::PointCloud object and kept with their
@@ -159,7 +160,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   // before using such a cloud again.  Entries (host cloud kept alive + device copy) live until forgetPairCloud / forgetPairClouds, a new
   // handle or the destructor: call forgetPairCloud when a keyframe leaves the graph, or memory grows with every cloud ever passed.
   // This object's own target, source and last result are untouched.  false: nothing was registered (lastError() says why) and *results
-  // is untouched; statuses of single pairs (empty source or target) are in the records.
+  // is untouched; statuses of single pairs (empty source or target; GICP_HIP: a cloud of fewer than k points) are in the records.
   bool alignPairs(const std::vector<PointCloudTargetConstPtr>& targets, const std::vector<PointCloudSourceConstPtr>& sources,
                   const std::vector<Matrix4>& guesses, bool compute_fitness, double max_range, std::vector<dgs_result>* results) {
     const size_t n = targets.size();

@@ -290,8 +290,13 @@ int dgs_align_batch_clouds(dgs_handle* h, int32_t n, dgs_cloud* const* sources, 
  * results[i] is what dgs_set_input_target_cloud(targets[i]) followed by dgs_align_batch_clouds over sources[i] alone would report (the
  * sums of a pair are formed by as many workgroups as the batch leaves it, so poses agree to rounding, as between any two batches);
  * fitness is getFitnessScore(fitness_max_range) of source i under its final transform against target i, from one
- * dgs_calc_fitness_score_batch_clouds-style launch over all n edges (bit-identical in any batch).  FAST_GICP handles only: any other
- * method is DGS_ERR_UNSUPPORTED with the method named in dgs_last_error (their target models live on the handle, not on the cloud).
+ * dgs_calc_fitness_score_batch_clouds-style launch over all n edges (bit-identical in any batch).  FAST_GICP and GICP_HIP handles: any
+ * other method is DGS_ERR_UNSUPPORTED with the method named in dgs_last_error (their target models live on the handle, not on the cloud).
+ * GICP_HIP sums over fixed slices, so its transforms, flags, counts and scores are the bits of dgs_align on the pair alone.
+ * One deliberate difference from dgs_set_input_target_cloud + dgs_align there: a target of fewer than k = gicp_correspondence_randomness
+ * points fails only the pairs that name it (status DGS_ERR_INVALID_ARGUMENT, transform = guess, as for a source of fewer than k points),
+ * the other pairs run and the call returns DGS_OK; k > 32 fails the call with DGS_ERR_UNSUPPORTED.  dgs_pcl_gicp_get_trajectory(pair)
+ * afterwards answers for the pairs of this call.
  * n == 0: DGS_OK without a launch.  A NULL cloud or a cloud of another device: DGS_ERR_INVALID_ARGUMENT.  An empty source: status
  * DGS_ERR_NO_SOURCE for that pair, transform = guess; an empty target: DGS_ERR_NO_TARGET for that pair; the other pairs run.  A cloud may be
  * the target of any number of pairs, the source of others, and both sides of one pair.  Missing indices of all clouds are built in one

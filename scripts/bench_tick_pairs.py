@@ -1,5 +1,5 @@
-"""A loop-detection tick of K new keyframes x c candidates over resident VLP-16-shaped clouds, FAST_GICP, two ways, alternating in one
-process.  Not bench.py: recorded in DESIGN.md 6n, not gated.
+"""A loop-detection tick of K new keyframes x c candidates over resident VLP-16-shaped clouds, FAST_GICP or GICP_HIP (--method), two ways,
+alternating in one process.  Not bench.py: recorded in DESIGN.md 6n (FAST_GICP) and 6o (GICP_HIP), not gated.
 
   seq    today's sequence: per new keyframe setInputTarget(cloud) + align_batch(its c candidates)   (K calls pairs, K chains of rounds)
   pairs  one align_pairs over all K x c (new keyframe, candidate, guess) pairs                       (one chain of rounds)
@@ -11,7 +11,10 @@ synchronisation (both return their results to the host).  Per (K, c): the median
 over `--runs` repetitions of that the medians in order; the kernel launches of one tick of each way from dgs_profile_get (a run of its
 own with the profiler on, after the timed ones), and the poses of the two ways compared first.  One JSON line per (K, c).
 
-    python scripts/bench_tick_pairs.py [--keyframes 1 4 10] [--candidates 1 3 8] [--repeats 50] [--warmup 5] [--runs 3]
+FAST_GICP runs with the launch files' values; GICP_HIP with the factory settings, as scripts/bench_pcl_gicp.py does.  For GICP_HIP the
+evaluations and the score of the two ways are compared too (its sums are formed over fixed slices: bit-equality is expected).
+
+    python scripts/bench_tick_pairs.py [--method FAST_GICP|GICP_HIP] [--keyframes 1 4 10] [--candidates 1 3 8] [--repeats 50] [--warmup 5] [--runs 3]
 """
 import argparse
 import json
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--method", choices=["FAST_GICP", "GICP_HIP"], default="FAST_GICP")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -44,7 +48,10 @@ def main():
     K_max, c_max = max(args.keyframes), max(args.candidates)
     n_pool = 12                                   # candidate frames, shared between the new keyframes as old keyframes are in a real graph
     frames, poses = synth.vlp16_stream(n_frames=K_max + n_pool)
-    reg = Registration("FAST_GICP", device=0, gicp_max_correspondence_distance=2.0, transformation_epsilon=0.1)   # the launch files' values
+    if args.method == "GICP_HIP":
+        reg = Registration("GICP_HIP", device=0)   # the factory settings (scripts/bench_pcl_gicp.py)
+    else:
+        reg = Registration("FAST_GICP", device=0, gicp_max_correspondence_distance=2.0, transformation_epsilon=0.1)   # the launch files' values
     resident = [reg.make_cloud(f) for f in frames]
     rng = np.random.default_rng(0)
 
@@ -77,13 +84,14 @@ def main():
         reg.profile_enable(False)
         return n
 
-    print(json.dumps(dict(points_per_cloud=[int(f.shape[0]) for f in frames[:3]], repeats=args.repeats, warmup=args.warmup, runs=args.runs)), flush=True)
+    print(json.dumps(dict(method=args.method, points_per_cloud=[int(f.shape[0]) for f in frames[:3]], repeats=args.repeats, warmup=args.warmup, runs=args.runs)), flush=True)
     for K in args.keyframes:
         for c in args.candidates:
             t = tick(K, c)
             a, b = run_seq(t), run_pairs(t)   # caches every index and covariance; and the two ways must agree
             worst = max(float(np.abs(x["T"] - y["T"]).max()) for x, y in zip(a, b))
             same_counts = all(x["converged"] == y["converged"] and x["iterations"] == y["iterations"] for x, y in zip(a, b))
+            same_bits = all(np.array_equal(x["T"], y["T"]) and x["evaluations"] == y["evaluations"] and x["score"] == y["score"] for x, y in zip(a, b))
             med = {"seq": [], "pairs": []}
             for _ in range(args.runs):
                 for _ in range(args.warmup):
@@ -100,7 +108,8 @@ def main():
             print(json.dumps(dict(K=K, c=c, pairs=K * c, seq_ms=med["seq"], pairs_ms=med["pairs"],
                                   pairs_faster_in_all_runs=all(p < s for p, s in zip(med["pairs"], med["seq"])),
                                   launches_seq=launches(run_seq, t), launches_pairs=launches(run_pairs, t),
-                                  iterations=[x["iterations"] for x in a], max_abs_T_difference=worst, same_flags_and_iterations=same_counts)), flush=True)
+                                  iterations=[x["iterations"] for x in a], evaluations=[x["evaluations"] for x in a], max_abs_T_difference=worst,
+                                  same_flags_and_iterations=same_counts, same_transform_evaluations_and_score_bits=same_bits)), flush=True)
 
 
 if __name__ == "__main__":
