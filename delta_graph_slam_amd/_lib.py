@@ -196,6 +196,7 @@ SYMBOLS = [
     "dgs_icp_options_init", "dgs_set_icp_options", "dgs_group_set_icp_options", "dgs_icp_get_trajectory",
     "dgs_pcl_gicp_options_init", "dgs_set_pcl_gicp_options", "dgs_group_set_pcl_gicp_options", "dgs_pcl_gicp_get_trajectory",
     "dgs_pcl_gicp_set_probe", "dgs_pcl_gicp_evaluate", "dgs_pcl_gicp_set_correspondence_randomness",
+    "dgs_set_batch_independent", "dgs_get_batch_independent", "dgs_group_set_batch_independent",
     "dgs_prefilter_params_init", "dgs_prefilter", "dgs_prefilter_distance", "dgs_prefilter_radius", "dgs_prefilter_statistical",
     "dgs_prefilter_normal", "dgs_prefilter_get_statistics", "dgs_prefilter_get_normals",
     "dgs_prefilter_scan_params_init", "dgs_prefilter_scan", "dgs_prefilter_deskew",
@@ -311,6 +312,9 @@ def load(path=None):
     lib.dgs_pcl_gicp_get_trajectory.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                 P(C.c_int32)]
     lib.dgs_pcl_gicp_set_correspondence_randomness.argtypes = [C.c_void_p, C.c_int32]
+    lib.dgs_set_batch_independent.argtypes = [C.c_void_p, C.c_int32]
+    lib.dgs_get_batch_independent.argtypes = [C.c_void_p, P(C.c_int32)]
+    lib.dgs_group_set_batch_independent.argtypes = [C.c_void_p, C.c_int32]
     lib.dgs_pcl_gicp_set_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dgs_pcl_gicp_evaluate.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int32), P(C.c_double), C.c_void_p]
     lib.dgs_prefilter_params_init.argtypes = [P(PrefilterParams)]

@@ -398,6 +398,35 @@ int dgs_set_icp_options(dgs_handle* h, const dgs_icp_options* o) {
   return DGS_OK;
 }
 
+// Host-side switch, no device work: see dgs_reg.h.  FAST_GICP / FAST_VGICP read it at every round launch (gicp.hip), the NDT driver reads
+// ndt_fixed_slices at every align (plan_align), every fitness entry point reads it where it chooses its scorer.
+int dgs_set_batch_independent(dgs_handle* h, int32_t on) {
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (h->prm.method == DGS_METHOD_NDT) {
+    if (h->prm.ndt_strict_order == DGS_NDT_ORDER_FAST) {
+      h->err = "dgs_set_batch_independent: NDT with ndt_strict_order 0 (the re-associated fast order) sums a pair over the slices its launch leaves it; "
+               "choose ndt_strict_order 1 or 2";
+      return DGS_ERR_UNSUPPORTED;
+    }
+    if (h->prm.ndt_strict_order == DGS_NDT_ORDER_UPSTREAM) {
+      if (h->strict_kernel == 2 || !h->prm.ndt_exp_glibc) {
+        h->err = "dgs_set_batch_independent: the lane-per-point upstream-order kernels (DGS_NDT_STRICT_KERNEL=2, ndt_exp_glibc = 0) have no fixed slices";
+        return DGS_ERR_UNSUPPORTED;
+      }
+      h->ndt_fixed_slices = on ? true : h->ndt_fixed_slices_initial;
+    }
+  }
+  h->batch_independent = on != 0;
+  return DGS_OK;
+}
+
+int dgs_get_batch_independent(const dgs_handle* h, int32_t* on) {
+  if (!h || !on) return DGS_ERR_INVALID_ARGUMENT;
+  *on = h->batch_independent ? 1 : 0;
+  return DGS_OK;
+}
+
 int dgs_icp_get_trajectory(dgs_handle* h, int32_t pair, float* T16s, double* mse, int32_t* n_corr, int32_t capacity, int32_t* len) {
   if (!h || !len || pair < 0 || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
@@ -448,6 +477,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (const char* e = std::getenv("DGS_NDT_SOLVE_MIN_ACTIVE")) h->solve_min_active = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("DGS_NDT_SPECULATE")) h->ndt_speculate = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_FIXED_SLICES")) h->ndt_fixed_slices = std::atoi(e) != 0;
+  h->ndt_fixed_slices_initial = h->ndt_fixed_slices;   // what dgs_set_batch_independent(h, 0) goes back to
   if (const char* e = std::getenv("DGS_NDT_DEAL_BY_COST")) h->ndt_deal_by_cost = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_REUSE_TRIALS")) h->ndt_reuse_trials = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_NDT_QUEUE")) h->ndt_queue_mode = std::atoi(e);
@@ -708,6 +738,10 @@ int dgs_get_fitness_score(dgs_handle* h, double max_range, double* score) {
   if (set_device(h)) return DGS_ERR_HIP;
   if (!h->have_target || h->nt == 0) return DGS_ERR_NO_TARGET;
   if (!h->have_source || h->ns == 0) return DGS_ERR_NO_SOURCE;
+  if (h->batch_independent) {   // the edge (target, source, final transform): rows that follow the source's size alone
+    const float4* src = h->src->pts.ptr;
+    return fitness_target_edges(h, 1, &src, &h->ns, h->final_T, 16, max_range, score);
+  }
   double sum = 0;
   int64_t cnt = 0, inl = 0;
   int rc = nn_fitness(h, h->src->pts.ptr, h->ns, h->final_T, max_range, 0.0, &sum, &cnt, &inl);
@@ -793,10 +827,25 @@ static int gicp_batch(dgs_handle* h, int n, CloudState* const* cs, const float* 
   // critical path here (measured per tick over resident 65,536-point keyframes, k-d / Hilbert: 4 candidates 1.38 / 1.17 ms, 8: 1.77 / 1.72,
   // 12: 2.08 / 2.16, 32: 3.30 / 4.23)
   static const int kd_min = std::getenv("DGS_GICP_KD_MIN_CANDIDATES") ? std::atoi(std::getenv("DGS_GICP_KD_MIN_CANDIDATES")) : 10;
-  h->batch_kd = h->nn_kd && n >= kd_min;
+  // batch-independent: a k-d ordered index hands the k-NN sets to the covariance sums in another order than the Hilbert one a single align builds
+  h->batch_kd = h->nn_kd && n >= kd_min && !h->batch_independent;
   const MethodOps& ops = kMethodOps[h->prm.method];
   int rc = ops.align_batch(h, n, cs, guesses16, results);
-  if (rc == DGS_OK && compute_fitness) {
+  if (rc == DGS_OK && compute_fitness && h->batch_independent) {
+    // one edge (target, source i, T_i) per candidate through the edge scorer: an edge's rows do not depend on the batch it is in
+    std::vector<const float4*> ptrs(n);
+    std::vector<int64_t> sz(n);
+    std::vector<float> T((size_t)n * 16);
+    std::vector<double> scores(n);
+    for (int i = 0; i < n; i++) {
+      ptrs[i] = cs[i]->pts.ptr;
+      sz[i] = cs[i]->n;
+      std::memcpy(&T[(size_t)i * 16], results[i].final_transformation, sizeof(float) * 16);
+    }
+    rc = fitness_target_edges(h, n, ptrs.data(), sz.data(), T.data(), 16, fitness_max_range, scores.data());
+    if (rc == DGS_OK)
+      for (int i = 0; i < n; i++) results[i].fitness = scores[i];
+  } else if (rc == DGS_OK && compute_fitness) {
     DGS_HIP_TRY(h, h->src_ptrs.reserve(n));
     DGS_HIP_TRY(h, h->src_sizes.reserve(n));
     std::vector<const float4*> ptrs(n);
@@ -877,7 +926,7 @@ int dgs_align_batch(dgs_handle* h, int32_t n, const float* const* sources, const
   struct KdScope { dgs_handle* h; ~KdScope() { h->batch_kd = false; } } kd_scope{h};
   // ... from ~6 candidates of 65,536 points on: below that the build (~0.9 ms of side-stream time) outlasts the iterations it should hide
   // behind (measured per tick, k-d / Hilbert: 1 candidate 0.74 / 0.59 ms, 4: 0.80 / 0.77, 8: 1.16 / 1.24, 32: 2.26 / 2.59)
-  h->batch_kd = h->nn_kd && compute_fitness && total >= h->nn_kd_min_queries;
+  h->batch_kd = h->nn_kd && compute_fitness && total >= h->nn_kd_min_queries && !h->batch_independent;
   // The side stream forks HERE (it depends on the target only), but its launches are enqueued by ndt_align_pairs after the first
   // chunks of iteration launches: enqueueing a dozen launches costs the host ~50 us during which the main stream would sit empty.
   if (compute_fitness && (!h->tgt->bvh.valid || (h->use_grid && !h->tgt_grid.valid)) && !h->prof.enabled) {
@@ -888,7 +937,8 @@ int dgs_align_batch(dgs_handle* h, int32_t n, const float* const* sources, const
   int max_n = 0;
   for (int i = 0; i < n; i++) max_n = std::max(max_n, sz[i]);
   // the walk of a finished candidate starts while the others still iterate (ndt_align_pairs); kernels timed one by one stay in line
-  h->early_fit.on = h->early_fitness_enabled && compute_fitness && !h->prof.enabled && !h->use_grid && n <= 65535;
+  // (batch-independent: the edge scorer below, after the batch -- the early walk's rows per pair follow the whole batch)
+  h->early_fit.on = h->early_fitness_enabled && compute_fitness && !h->prof.enabled && !h->use_grid && n <= 65535 && !h->batch_independent;
   h->early_fit.enqueued = false;
   h->early_fit.max_range = fitness_max_range;
   h->early_fit.max_n = max_n;
@@ -901,6 +951,14 @@ int dgs_align_batch(dgs_handle* h, int32_t n, const float* const* sources, const
     std::vector<int64_t> cnts(n), inl(n);
     nn_fitness_read(h, n, sums.data(), cnts.data(), inl.data());
     for (int i = 0; i < n; i++) results[i].fitness = cnts[i] > 0 ? sums[i] / (double)cnts[i] : DBL_MAX;
+  } else if (rc == DGS_OK && compute_fitness && h->batch_independent) {
+    std::vector<int64_t> sz64(sz.begin(), sz.end());
+    std::vector<float> T((size_t)n * 16);
+    std::vector<double> scores(n);
+    for (int i = 0; i < n; i++) std::memcpy(&T[(size_t)i * 16], results[i].final_transformation, sizeof(float) * 16);
+    rc = fitness_target_edges(h, n, ptrs.data(), sz64.data(), T.data(), 16, fitness_max_range, scores.data());
+    if (rc == DGS_OK)
+      for (int i = 0; i < n; i++) results[i].fitness = scores[i];
   } else if (rc == DGS_OK && compute_fitness) {
     // getFitnessScore for every candidate in one launch; transforms are read from the optimiser state in HBM
     std::vector<double> sums(n);

@@ -416,6 +416,19 @@ int dgs_group_set_icp_options(dgs_group* g, const dgs_icp_options* options) {
   return DGS_OK;
 }
 
+int dgs_group_set_batch_independent(dgs_group* g, int32_t on) {
+  if (!g) return DGS_ERR_INVALID_ARGUMENT;
+  g->err.clear();
+  for (size_t k = 0; k < g->members.size(); k++) {   // host-side switch only: no device work, no member thread needed
+    const int rc = dgs_set_batch_independent(g->members[k], on);
+    if (rc != DGS_OK) {
+      g->err = "member " + std::to_string(k) + ": " + dgs_last_error(g->members[k]);
+      return rc;
+    }
+  }
+  return DGS_OK;
+}
+
 int dgs_group_set_pcl_gicp_options(dgs_group* g, const dgs_pcl_gicp_options* options) {
   if (!g || !options) return DGS_ERR_INVALID_ARGUMENT;
   g->err.clear();

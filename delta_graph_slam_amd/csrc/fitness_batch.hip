@@ -353,9 +353,20 @@ int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, 
   FbScratch& F = h->fb;
   std::fill(F.counts8, F.counts8 + 8, 0);
   if (n_edges == 0) return DGS_OK;
-  F.counts8[2] = n_edges;
   int rc = fitness_batch_build_indices(h, n_edges, cloud1s, false);
   if (rc != DGS_OK) return rc;
+  std::vector<FbEdgeIn> in((size_t)n_edges);
+  for (int e = 0; e < n_edges; e++)
+    in[e] = FbEdgeIn{&cloud1s[e]->st.bvh, cloud2s[e]->st.pts.ptr, cloud1s[e]->st.n, cloud2s[e]->st.n, relposes16 ? relposes16 + (size_t)e * 16 : kIdentity16};
+  return fitness_batch_edges(h, n_edges, in.data(), max_range, scores, used);
+}
+
+// The walk and the closing launch over edges given as (index over cloud1, cloud2's points, pose): what fitness_batch_clouds runs once its
+// clouds' indices stand, and what a batch-independent handle scores its own target's candidates with (fitness_target_edges).
+int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double max_range, double* scores, int64_t* used) {
+  FbScratch& F = h->fb;
+  if (n_edges == 0) return DGS_OK;
+  F.counts8[2] = n_edges;
   // one pinned block: [row prefix | edge table] up, [sum, used per edge] down
   const size_t pre_bytes = (((size_t)n_edges + 1) * sizeof(int) + 127) & ~(size_t)127;
   const size_t up_bytes = pre_bytes + (size_t)n_edges * sizeof(FbEdge), down_bytes = (size_t)n_edges * 2 * sizeof(double);
@@ -365,19 +376,17 @@ int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, 
   double* down = reinterpret_cast<double*>(reinterpret_cast<char*>(F.stage) + up_bytes);
   int64_t total_rows = 0;
   for (int e = 0; e < n_edges; e++) {
-    const CloudState& c1 = cloud1s[e]->st;
-    const CloudState& c2 = cloud2s[e]->st;
     FbEdge& E = edges[e];
     std::memset(&E, 0, sizeof(E));
-    const bool empty = c1.n == 0 || c2.n == 0;   // no neighbour / no query: the "nr == 0" branch of the reference
+    const bool empty = in[e].n1 == 0 || in[e].n2 == 0;   // no neighbour / no query: the "nr == 0" branch of the reference
     if (!empty) {
-      E.b = make_bvh_view(c1.bvh);
-      E.src = c2.pts.ptr;
-      E.n = (int)c2.n;
+      E.b = make_bvh_view(*in[e].index);
+      E.src = in[e].src;
+      E.n = (int)in[e].n2;
       E.rows = fb_rows_of(E.n);
     }
     E.row0 = (int)total_rows;
-    std::memcpy(E.T, relposes16 ? relposes16 + (size_t)e * 16 : kIdentity16, sizeof(float) * 16);
+    std::memcpy(E.T, in[e].T16, sizeof(float) * 16);
     row0s[e] = (int)total_rows;
     total_rows += E.rows;
   }
@@ -408,6 +417,17 @@ int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, 
     if (used) used[e] = (int64_t)cnt;
   }
   return DGS_OK;
+}
+
+int fitness_target_edges(dgs_handle* h, int n, const float4* const* srcs, const int64_t* sizes, const float* T16s, size_t T_stride_floats, double max_range, double* scores) {
+  if (side_join(h) != DGS_OK) return DGS_ERR_HIP;   // an index being built on the side stream
+  h->use_grid = false;                               // the edge scorer walks the tree
+  int rc = ensure_target_index(h);
+  if (rc != DGS_OK) return rc;
+  std::fill(h->fb.counts8, h->fb.counts8 + 8, 0);
+  std::vector<FbEdgeIn> in((size_t)n);
+  for (int i = 0; i < n; i++) in[i] = FbEdgeIn{&h->tgt->bvh, srcs[i], h->nt, sizes[i], T16s + (size_t)i * T_stride_floats};
+  return fitness_batch_edges(h, n, in.data(), max_range, scores, nullptr);
 }
 
 void fitness_batch_release(dgs_handle* h) {

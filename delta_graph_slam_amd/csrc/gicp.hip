@@ -1146,6 +1146,214 @@ __global__ __launch_bounds__(kBlock, FUSED ? 3 : 1) void vgicp_linearize_kernel(
   if (FUSED) gicp_close_round(pairs, pair, nblocks, partials + (size_t)pair * cap_blocks * kAccumPad, consts, done_counter, launch);
 }
 
+// ================================================================================================ fixed slices (dgs_set_batch_independent)
+// The three linearize kernels above cut a pair into as many slices as the launch leaves it (deal_workgroup's blocks_per_pair), so the
+// association of its double sums follows the batch.  Here the slices follow the pair's own size: S(n) = clamp(ceil(n / kBlock), 1, 512),
+// point i in slice (i / kBlock) % S(n), one row per slice through gicp_block_reduce, the rows added by gicp_step_from_rows with
+// nblocks = S(n) -- the layout a LONE default align gets from gicp_choose_launch(1, n) and deal_workgroup, so a pair in any batch is
+// bit-equal to its own single align.  A workgroup is still dealt (pair, slice, blocks_per_pair); it takes the slices slice,
+// slice + blocks_per_pair, ... of the pair one after the other and ONE ticket after the last (a workgroup dealt no slice takes its
+// ticket all the same: the count is blocks_per_pair, as in pcl_ndt.hip); the last ticket closes over S(n) rows.  The per-point bodies
+// are restated, not shared with the kernels above, which stay what they were instruction for instruction -- and not shared between the
+// kernels below either: through a __forceinline__ helper the compiler contracted a * b + c differently and the score left the lone
+// align's by 1-4 ulp.  Keep the point loops written as gicp_linearize_kernel writes its own.
+__device__ __forceinline__ int gicp_fixed_slices_of(const int n) { return max(1, min((n + kBlock - 1) / kBlock, 512)); }
+
+// gicp_close_round with the ticket count (workgroups of the pair in this launch) apart from the row count (slices of the pair)
+__device__ __forceinline__ void gicp_close_round_fixed(GicpPair* pairs, const int pair, const int n_tickets, const int n_rows,
+                                                       const double* __restrict__ partials_of_pair, const GicpConsts& c, int* __restrict__ done_counter,
+                                                       const int launch) {
+  __shared__ int s_last;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s_last = handoff_take_ticket(&pairs[pair].ticket, n_tickets) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  gicp_step_from_rows<true>(pairs + pair, partials_of_pair, n_rows, c, done_counter, launch);
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(kBlock, FUSED ? 4 : 1) void gicp_linearize_fixed_kernel(const GicpItem* __restrict__ items, const float4* __restrict__ tgt,
+                                                                      const double* __restrict__ cov_t, GicpPair* __restrict__ pairs,
+                                                                      double* __restrict__ partials, const int n_pairs, const int cap_blocks,
+                                                                      int* __restrict__ pair_blocks, const GicpConsts consts, int* __restrict__ done_counter,
+                                                                      const int launch) {
+  int pair, slice, nblocks;
+  if (!deal_workgroup(n_pairs, cap_blocks, [&](int pi) { return FUSED ? (launch <= pairs[pi].last_launch) : (pairs[pi].active != 0); }, pair, slice, nblocks)) return;
+  const GicpPair& st = pairs[pair];
+  const GicpItem it = items[pair];
+  const int n = it.n;
+  const int n_slices = min(gicp_fixed_slices_of(n), cap_blocks);   // cap_blocks = S(largest source) >= S(n): the min only guards the rows
+  if (slice == 0 && threadIdx.x == 0) pair_blocks[pair] = n_slices;
+  const float4* __restrict__ src = it.src;
+  const double* __restrict__ cov_s = it.cov_s;
+  const int* __restrict__ corr = it.corr;
+  double* __restrict__ mahal = it.mahal;
+  const bool full = st.eval_kind == 0;
+  double T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = st.Teval[k];
+  double* __restrict__ rows_of_pair = partials + (size_t)pair * cap_blocks * kAccumPad;
+  for (int q = slice; q < n_slices; q += nblocks) {
+    double acc[kAccum];
+#pragma unroll
+    for (int k = 0; k < kAccum; k++) acc[k] = 0.0;
+
+    for (int i = q * kBlock + threadIdx.x; i < n; i += n_slices * kBlock) {
+      const int j = corr[i];
+      if (j < 0) continue;
+      const float4 pa = src[i], pb = tgt[j];
+      double M[6];
+      if (full) {
+        gicp_mahalanobis(T, cov_s + (size_t)i * 6, cov_t + (size_t)j * 6, M);
+        double* mo = mahal + (size_t)i * 6;
+#pragma unroll
+        for (int k = 0; k < 6; k++) mo[k] = M[k];
+      } else {
+        const double* mo = mahal + (size_t)i * 6;
+#pragma unroll
+        for (int k = 0; k < 6; k++) M[k] = mo[k];
+      }
+      const double ax = pa.x, ay = pa.y, az = pa.z;
+      const double t0 = T[0] * ax + T[1] * ay + T[2] * az + T[3];
+      const double t1 = T[4] * ax + T[5] * ay + T[6] * az + T[7];
+      const double t2 = T[8] * ax + T[9] * ay + T[10] * az + T[11];
+      gicp_accumulate<false>(acc, M, (double)pb.x - t0, (double)pb.y - t1, (double)pb.z - t2, t0, t1, t2, 1.0, full);
+    }
+    gicp_block_reduce<FUSED>(acc, rows_of_pair + (size_t)q * kAccumPad);
+    __syncthreads();   // the row has been read out of gicp_block_reduce's LDS before the next slice's sums land there
+  }
+  if (FUSED) gicp_close_round_fixed(pairs, pair, nblocks, n_slices, rows_of_pair, consts, done_counter, launch);
+}
+
+// the per-pair-target form: the target's points and covariances from the GicpTarget table (gicp_linearize_pairs_kernel), the rest as above
+template <bool FUSED>
+__global__ __launch_bounds__(kBlock, FUSED ? 4 : 1) void gicp_linearize_pairs_fixed_kernel(const GicpTarget* __restrict__ targets, const GicpItem* __restrict__ items,
+                                                                            GicpPair* __restrict__ pairs, double* __restrict__ partials, const int n_pairs,
+                                                                            const int cap_blocks, int* __restrict__ pair_blocks, const GicpConsts consts,
+                                                                            int* __restrict__ done_counter, const int launch) {
+  int pair, slice, nblocks;
+  if (!deal_workgroup(n_pairs, cap_blocks, [&](int pi) { return FUSED ? (launch <= pairs[pi].last_launch) : (pairs[pi].active != 0); }, pair, slice, nblocks)) return;
+  const GicpPair& st = pairs[pair];
+  const GicpItem it = items[pair];
+  const int n = it.n;
+  const int n_slices = min(gicp_fixed_slices_of(n), cap_blocks);   // cap_blocks = S(largest source) >= S(n): the min only guards the rows
+  if (slice == 0 && threadIdx.x == 0) pair_blocks[pair] = n_slices;
+  const float4* __restrict__ src = it.src;
+  const double* __restrict__ cov_s = it.cov_s;
+  const int* __restrict__ corr = it.corr;
+  double* __restrict__ mahal = it.mahal;
+  const float4* __restrict__ tgt = targets[it.tgt].pts;   // uniform address: scalar loads
+  const double* __restrict__ cov_t = targets[it.tgt].cov;
+  const bool full = st.eval_kind == 0;
+  double T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = st.Teval[k];
+  double* __restrict__ rows_of_pair = partials + (size_t)pair * cap_blocks * kAccumPad;
+  for (int q = slice; q < n_slices; q += nblocks) {
+    double acc[kAccum];
+#pragma unroll
+    for (int k = 0; k < kAccum; k++) acc[k] = 0.0;
+
+    for (int i = q * kBlock + threadIdx.x; i < n; i += n_slices * kBlock) {
+      const int j = corr[i];
+      if (j < 0) continue;
+      const float4 pa = src[i], pb = tgt[j];
+      double M[6];
+      if (full) {
+        gicp_mahalanobis(T, cov_s + (size_t)i * 6, cov_t + (size_t)j * 6, M);
+        double* mo = mahal + (size_t)i * 6;
+#pragma unroll
+        for (int k = 0; k < 6; k++) mo[k] = M[k];
+      } else {
+        const double* mo = mahal + (size_t)i * 6;
+#pragma unroll
+        for (int k = 0; k < 6; k++) M[k] = mo[k];
+      }
+      const double ax = pa.x, ay = pa.y, az = pa.z;
+      const double t0 = T[0] * ax + T[1] * ay + T[2] * az + T[3];
+      const double t1 = T[4] * ax + T[5] * ay + T[6] * az + T[7];
+      const double t2 = T[8] * ax + T[9] * ay + T[10] * az + T[11];
+      gicp_accumulate<false>(acc, M, (double)pb.x - t0, (double)pb.y - t1, (double)pb.z - t2, t0, t1, t2, 1.0, full);
+    }
+    gicp_block_reduce<FUSED>(acc, rows_of_pair + (size_t)q * kAccumPad);
+    __syncthreads();   // the row has been read out of gicp_block_reduce's LDS before the next slice's sums land there
+  }
+  if (FUSED) gicp_close_round_fixed(pairs, pair, nblocks, n_slices, rows_of_pair, consts, done_counter, launch);
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(kBlock, FUSED ? 3 : 1) void vgicp_linearize_fixed_kernel(const GicpItem* __restrict__ items, const VgicpMap m,
+                                                                       GicpPair* __restrict__ pairs, double* __restrict__ partials,
+                                                                       const int n_pairs, const int cap_blocks, int* __restrict__ pair_blocks,
+                                                                       const GicpConsts consts, int* __restrict__ done_counter, const int launch) {
+  int pair, slice, nblocks;
+  if (!deal_workgroup(n_pairs, cap_blocks, [&](int pi) { return FUSED ? (launch <= pairs[pi].last_launch) : (pairs[pi].active != 0); }, pair, slice, nblocks)) return;
+  const GicpPair& st = pairs[pair];
+  const GicpItem it = items[pair];
+  const int n = it.n, no = m.n_offsets;
+  const int n_slices = min(gicp_fixed_slices_of(n), cap_blocks);
+  if (slice == 0 && threadIdx.x == 0) pair_blocks[pair] = n_slices;
+  double* __restrict__ rows_of_pair = partials + (size_t)pair * cap_blocks * kAccumPad;
+  const bool full = st.eval_kind == 0;
+  double T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = st.Teval[k];
+  for (int q = slice; q < n_slices; q += nblocks) {
+    double acc[kAccum];
+#pragma unroll
+    for (int k = 0; k < kAccum; k++) acc[k] = 0.0;
+    for (int i = q * kBlock + threadIdx.x; i < n; i += n_slices * kBlock) {
+      const float4 pa = it.src[i];
+      const double ax = pa.x, ay = pa.y, az = pa.z;
+      const double t0 = T[0] * ax + T[1] * ay + T[2] * az + T[3];
+      const double t1 = T[4] * ax + T[5] * ay + T[6] * az + T[7];
+      const double t2 = T[8] * ax + T[9] * ay + T[10] * az + T[11];
+      // GaussianVoxelMap::voxel_coord: floor(x / resolution - 0.5), relative to the table's first cell
+      const int c0 = (int)floor(t0 / m.resolution - 0.5) - m.min_c[0];
+      const int c1 = (int)floor(t1 / m.resolution - 0.5) - m.min_c[1];
+      const int c2 = (int)floor(t2 / m.resolution - 0.5) - m.min_c[2];
+      for (int k = 0; k < no; k++) {
+        const size_t slot = (size_t)i * no + k;
+        int v;
+        if (full) {
+          int dx = 0, dy = 0, dz = 0;
+          if (m.search == DGS_VGICP_DIRECT7) {  // (0,0,0) (1,0,0) (-1,0,0) (0,1,0) (0,-1,0) (0,0,1) (0,0,-1)
+            dx = (k == 1) - (k == 2);
+            dy = (k == 3) - (k == 4);
+            dz = (k == 5) - (k == 6);
+          } else if (m.search == DGS_VGICP_DIRECT27) {
+            dx = k / 9 - 1;
+            dy = (k / 3) % 3 - 1;
+            dz = k % 3 - 1;
+          }
+          const int x = c0 + dx, y = c1 + dy, z = c2 + dz;
+          v = -1;
+          if (x >= 0 && x < m.div[0] && y >= 0 && y < m.div[1] && z >= 0 && z < m.div[2]) v = m.cell2vox[x + y * m.mul1 + z * m.mul2];
+          it.corr[slot] = v;
+        } else {
+          v = it.corr[slot];
+        }
+        if (v < 0) continue;
+        const VgicpVoxel* vx = m.vox + v;
+        double M[6];
+        if (full) {
+          gicp_mahalanobis(T, it.cov_s + (size_t)i * 6, vx->cov, M);
+#pragma unroll
+          for (int a = 0; a < 6; a++) it.mahal[slot * 6 + a] = M[a];
+        } else {
+#pragma unroll
+          for (int a = 0; a < 6; a++) M[a] = it.mahal[slot * 6 + a];
+        }
+        gicp_accumulate<true>(acc, M, vx->mean[0] - t0, vx->mean[1] - t1, vx->mean[2] - t2, t0, t1, t2, vx->w, full);
+      }
+    }
+    gicp_block_reduce<FUSED>(acc, rows_of_pair + (size_t)q * kAccumPad);
+    __syncthreads();   // the row has been read out of gicp_block_reduce's LDS before the next slice's sums land there
+  }
+  if (FUSED) gicp_close_round_fixed(pairs, pair, nblocks, n_slices, rows_of_pair, consts, done_counter, launch);
+}
 
 __global__ __launch_bounds__(kBlock) void gicp_solve_kernel(GicpPair* __restrict__ pairs, const double* __restrict__ all_partials,
                                                             const int* __restrict__ pair_blocks, const int cap_blocks, const GicpConsts c,
@@ -1311,9 +1519,16 @@ static void gicp_launch_round(dgs_handle* h, const GicpLaunch& L, const int laun
   // fused rounds (default; DGS_GICP_FUSED=0 restores the separate solve launch): the optimiser step of a pair runs in the last
   // workgroup of its linearize slice -- two dependent launches per evaluation instead of three (VGICP: one instead of two)
   const bool fused = h->gicp_fused;
+  const bool fixed = h->batch_independent;   // slices that follow the pair's own size: the fixed-slices kernels
   if (h->prm.method == DGS_METHOD_VGICP) {
     int slot = prof_begin(h, DGS_K_GICP_LINEARIZE);
-    if (fused)
+    if (fixed && fused)
+      hipLaunchKernelGGL(vgicp_linearize_fixed_kernel<true>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gitems.ptr, h->vmap, h->gpairs.ptr, h->partials.ptr,
+                         L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+    else if (fixed)
+      hipLaunchKernelGGL(vgicp_linearize_fixed_kernel<false>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gitems.ptr, h->vmap, h->gpairs.ptr, h->partials.ptr,
+                         L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+    else if (fused)
       hipLaunchKernelGGL(vgicp_linearize_kernel<true>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gitems.ptr, h->vmap, h->gpairs.ptr, h->partials.ptr,
                          L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
     else
@@ -1331,7 +1546,13 @@ static void gicp_launch_round(dgs_handle* h, const GicpLaunch& L, const int laun
                      h->gconsts.max_corr_sq);
   prof_end(h, DGS_K_NN_SEARCH, slot);
   slot = prof_begin(h, DGS_K_GICP_LINEARIZE);
-  if (fused)
+  if (fixed && fused)
+    hipLaunchKernelGGL(gicp_linearize_fixed_kernel<true>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gitems.ptr, h->tgt->pts.ptr, h->tgt->cov.ptr, h->gpairs.ptr,
+                       h->partials.ptr, L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+  else if (fixed)
+    hipLaunchKernelGGL(gicp_linearize_fixed_kernel<false>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gitems.ptr, h->tgt->pts.ptr, h->tgt->cov.ptr, h->gpairs.ptr,
+                       h->partials.ptr, L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+  else if (fused)
     hipLaunchKernelGGL(gicp_linearize_kernel<true>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gitems.ptr, h->tgt->pts.ptr, h->tgt->cov.ptr, h->gpairs.ptr,
                        h->partials.ptr, L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
   else
@@ -1476,7 +1697,13 @@ static void gicp_launch_pairs_round(dgs_handle* h, const GicpLaunch& L, const in
                      h->gconsts.max_corr_sq);
   prof_end(h, DGS_K_NN_SEARCH, slot);
   slot = prof_begin(h, DGS_K_GICP_LINEARIZE);
-  if (fused)
+  if (h->batch_independent && fused)
+    hipLaunchKernelGGL(gicp_linearize_pairs_fixed_kernel<true>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gtargets.ptr, h->gitems.ptr, h->gpairs.ptr, h->partials.ptr,
+                       L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+  else if (h->batch_independent)
+    hipLaunchKernelGGL(gicp_linearize_pairs_fixed_kernel<false>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gtargets.ptr, h->gitems.ptr, h->gpairs.ptr, h->partials.ptr,
+                       L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
+  else if (fused)
     hipLaunchKernelGGL(gicp_linearize_pairs_kernel<true>, dim3(L.grid_l), dim3(kBlock), 0, h->stream, h->gtargets.ptr, h->gitems.ptr, h->gpairs.ptr, h->partials.ptr,
                        L.n_pairs, L.cap_l, h->pair_blocks.ptr, h->gconsts, h->done_counter.ptr, launch);
   else

@@ -311,6 +311,9 @@ struct dgs_handle {
   bool ndt_speculate = true;          // DGS_NDT_SPECULATE=0: upstream order, item-compacted kernel: the Newton step's Jacobi SVD in the closing workgroup instead of speculated
   bool ndt_fixed_slices = false;     // DGS_NDT_FIXED_SLICES=1: upstream order, item-compacted kernel: a pair's slices are a function of its own size (ndt_strict.h strict_slices_of)
                                       // from the Gauss-Jordan direction and verified beside the next launch (NdtPair::spec_s)
+  bool ndt_fixed_slices_initial = false;   // ndt_fixed_slices as dgs_create left it
+  bool batch_independent = false;     // dgs_set_batch_independent: FAST_GICP / FAST_VGICP sum a pair over slices that follow its own size (gicp.hip, "fixed slices"), NDT order 1
+                                      // takes ndt_fixed_slices with it, and every fitness goes through the edge scorer (fitness_batch.hip): a pair's record does not depend on its batch
   bool ndt_deal_by_cost = true;       // DGS_NDT_DEAL_BY_COST=0: upstream order, item-compacted kernel: a launch's workgroups dealt to the pairs in index order (deal_workgroup)
   bool ndt_reuse_trials = true;       // DGS_NDT_REUSE_TRIALS=0: upstream orders: a repeated More-Thuente trial pose is evaluated again and its result replaced by the cached one
                                       // instead of heaviest evaluation kind first (deal_workgroup_by_cost); the same (pair, slice) set and the same bits either way
@@ -622,6 +625,16 @@ void floor_detection_release(dgs_handle* h);
 int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, bool reset_counts = true);
 int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_range,
                          double* scores, int64_t* used);
+// one edge of the scorer over plain device arrays: index over cloud1, cloud2's points, the relative pose (column-major, host)
+struct FbEdgeIn {
+  const Bvh* index;
+  const float4* src;
+  int64_t n1, n2;
+  const float* T16;
+};
+int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double max_range, double* scores, int64_t* used);
+// the same scorer for sources of the handle's current target (batch-independent fitness): builds the target's index when it has none
+int fitness_target_edges(dgs_handle* h, int n, const float4* const* srcs, const int64_t* sizes, const float* T16s, size_t T_stride_floats, double max_range, double* scores);
 void fitness_batch_release(dgs_handle* h);
 // building_cloud.hip
 void building_cloud_release(dgs_handle* h);

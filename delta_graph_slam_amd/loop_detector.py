@@ -81,7 +81,8 @@ class LoopDetector:
         self.local_only = bool(local_only)
         self.last_records = None
         # True: a tick's new keyframes are registered against their candidates in ONE Registration.align_pairs call (detect_batched) instead
-        # of one setInputTarget + align_batch per new keyframe.  OFF by default; only on one local FAST_GICP or GICP_HIP registration (_can_batch_tick)
+        # of one setInputTarget + align_batch per new keyframe.  OFF by default; only on one local FAST_GICP or GICP_HIP registration (_can_batch_tick).
+        # With a batch-independent FAST_GICP registration (or GICP_HIP, whose sums are fixed already) the batched tick equals the sequential one bit for bit.
         self.batch_new_keyframes = bool(batch_new_keyframes)
         # keyframe id -> DeviceCloud: a keyframe that is a candidate tick after tick (delta_graph_slam_nodelet.cpp:816 calls
         # detect() every graph_update_interval) is uploaded and indexed once; needs KeyFrame.id to be unique
@@ -164,7 +165,11 @@ class LoopDetector:
 
         With cache_clouds, such a keyframe and its candidates have also been made resident, and _after_tick runs for it as for the
         others (after the device call, so nothing in use is evicted): the sequential detector does neither for a keyframe it gates
-        out, so with a cache_capacity set the two may evict in a different order.  The loops do not depend on that."""
+        out, so with a cache_capacity set the two may evict in a different order.  The loops do not depend on that.
+
+        With a batch-independent FAST_GICP registration (Registration(..., batch_independent=True)) a pair's record does
+        not depend on the batch it is registered in, so detect_batched equals the sequential detect bit for bit: the same loops, the
+        same relative poses and scores.  The replay's price remains the registrations that the gate throws away."""
         per_keyframe = []   # (new keyframe, its candidates, first record)
         targets, sources, guesses = [], [], []
         for nk in new_keyframes:

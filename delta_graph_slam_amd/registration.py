@@ -154,6 +154,7 @@ class Registration:
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends (served: {sorted(exact)})")
         m = exact[method]
         params = dict(params)
+        batch_independent = bool(params.pop("batch_independent", False))   # a switch of the handle, not a dgs_params field
         icp_opt = _icp_options(lib, method, params)
         pg_opt = _pcl_gicp_options(lib, method, params)
         p = L.Params()
@@ -182,6 +183,29 @@ class Registration:
         self._final = np.eye(4, dtype=np.float32)
         self.last_result = None
         self._keep = {}
+        if batch_independent:
+            try:
+                self.set_batch_independent(True)
+            except DgsError:   # a method that refuses the switch: no half-made object is left behind
+                self.close()
+                raise
+
+    # -- batch-independent results (dgs_set_batch_independent) -------------------------------
+    def set_batch_independent(self, on: bool = True):
+        """While on, every field of a pair's result, and every fitness, is a function of (parameters, target, source, guess) alone:
+        align, align_batch, align_pairs and a RegistrationGroup member give the same bits for the same pair.  FAST_GICP / FAST_VGICP:
+        the bits of a single align with the switch off.  NDT_OMP in the re-associated fast order raises DgsError (status 6)."""
+        self._check(self._lib.dgs_set_batch_independent(self._h, 1 if on else 0))
+
+    @property
+    def batch_independent(self) -> bool:
+        on = C.c_int32(0)
+        self._check(self._lib.dgs_get_batch_independent(self._h, C.byref(on)))
+        return bool(on.value)
+
+    @batch_independent.setter
+    def batch_independent(self, on: bool):
+        self.set_batch_independent(on)
 
     # -- lifetime ---------------------------------------------------------------------------------------
     def close(self):
@@ -744,6 +768,7 @@ class RegistrationGroup:
         if method not in exact:
             raise NotImplementedError(f"registration_method {method!r} is not served by the HIP back-ends")
         params = dict(params)
+        batch_independent = bool(params.pop("batch_independent", False))   # a switch of the members' handles, not a dgs_params field
         icp_opt = _icp_options(lib, method, params)
         pg_opt = _pcl_gicp_options(lib, method, params)
         p = L.Params()
@@ -769,6 +794,27 @@ class RegistrationGroup:
             self._check(lib.dgs_group_set_pcl_gicp_options(self._g, C.byref(pg_opt)))
         self.best_index = -1
         self.best_score = float("inf")
+        self._batch_independent = False
+        if batch_independent:
+            try:
+                self.set_batch_independent(True)
+            except DgsError:
+                self.close()
+                raise
+
+    def set_batch_independent(self, on: bool = True):
+        """Registration.set_batch_independent on every member: a candidate's record is the same whichever member registers it,
+        and whatever the number of members."""
+        self._check(self._lib.dgs_group_set_batch_independent(self._g, 1 if on else 0))
+        self._batch_independent = bool(on)
+
+    @property
+    def batch_independent(self) -> bool:
+        return self._batch_independent
+
+    @batch_independent.setter
+    def batch_independent(self, on: bool):
+        self.set_batch_independent(on)
 
     def close(self):
         if getattr(self, "_g", None) is not None and self._g.value:
@@ -936,8 +982,20 @@ def select_registration_method(params: dict | None = None, device: int | None = 
     another algorithm -> NotImplementedError, while a name containing "OMP" ("NDT_OMP", and e.g. "FOO_OMP" after the warning) is
     pclomp::NormalDistributionsTransform (:101-120), which this library serves.  "PCL_NDT_HIP" (tested before that chain) is the HIP
     pcl::NormalDistributionsTransform of :94-100 with its three rosparams: reg_resolution, reg_transformation_epsilon, reg_maximum_iterations.
+    dgs_batch_independent (default false; not a key of the reference) turns on Registration.set_batch_independent.
     """
     pr = dict(params or {})
+    reg = _select_registration_method(pr, device)
+    if bool(pr.get("dgs_batch_independent", False)):   # this library's own key: batch-independent results (Registration.set_batch_independent)
+        try:
+            reg.set_batch_independent(True)
+        except DgsError:
+            reg.close()
+            raise
+    return reg
+
+
+def _select_registration_method(pr: dict, device) -> Registration:
     method = pr.get("registration_method", "NDT_OMP")
     common = dict(num_threads=int(pr.get("reg_num_threads", 0)),
                   transformation_epsilon=float(pr.get("reg_transformation_epsilon", 0.01)),

@@ -104,6 +104,14 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     apply_icp_options();
     apply_pg_options();
   }
+  // dgs_set_batch_independent (dgs_reg.h): every field of a pair's result, and every fitness, a function of (parameters, target,
+  // source, guess) alone -- align(), alignPairs() and any batch give the same bits for the same pair.  Applied to a live handle in place, and
+  // to every handle made later; a method that refuses the switch (NDT_HIP in the fast order) says so in lastError() at the next align().
+  void setBatchIndependent(bool on) {
+    batch_independent_ = on;
+    if (handle_ && dgs_set_batch_independent(handle_, on ? 1 : 0) != DGS_OK) dirty_ = true;   // else: at the next dgs_create
+  }
+  bool getBatchIndependent() const { return batch_independent_; }
   void setIcpOptions(const dgs_icp_options& o) { icp_options_ = o; icp_options_.struct_size = sizeof(dgs_icp_options); apply_icp_options(); }
   const dgs_icp_options& icpOptions() const { return icp_options_; }
   // pcl::GeneralizedIterativeClosestPoint (DGS_METHOD_PCL_GICP): registrations.cpp:74 and the settings dgs_params has no field for
@@ -217,6 +225,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     if (dgs_create(&params_, &handle_) != DGS_OK) return false;
     if (params_.method == DGS_METHOD_ICP && dgs_set_icp_options(handle_, &icp_options_) != DGS_OK) return false;
     if (params_.method == DGS_METHOD_PCL_GICP && dgs_set_pcl_gicp_options(handle_, &pg_options_) != DGS_OK) return false;
+    if (batch_independent_ && dgs_set_batch_independent(handle_, 1) != DGS_OK) return false;
     applied_ = params_;
     dirty_ = false;
     target_dirty_ = source_dirty_ = true;
@@ -284,6 +293,7 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
   dgs_handle* handle_ = nullptr;
   dgs_result last_{};
   bool dirty_ = true, target_dirty_ = true, source_dirty_ = true, keep_pcl_tree_ = true;
+  bool batch_independent_ = false;   // setBatchIndependent: applied to every handle this object makes
 };
 
 }  // namespace dgs

@@ -29,7 +29,19 @@ bool param_bool(Params& pnh, const std::string& name, bool def, long) {
 }
 
 template <typename PointT, typename Params>
+typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration_method(const std::string& registration_method, Params& pnh);
+
+// not a parameter of the reference: dgs_batch_independent (default false) turns on HipRegistration::setBatchIndependent for whichever HIP
+// back-end the method names -- a pair's result then does not depend on the batch, the launch shape or the entry point that registered it
+template <typename PointT, typename Params>
 typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration(const std::string& registration_method, Params& pnh) {
+  typename pcl::Registration<PointT, PointT>::Ptr base = select_hip_registration_method<PointT>(registration_method, pnh);
+  if (base && param_bool(pnh, "dgs_batch_independent", false, 0)) static_cast<HipRegistration<PointT, PointT>*>(base.get())->setBatchIndependent(true);
+  return base;
+}
+
+template <typename PointT, typename Params>
+typename pcl::Registration<PointT, PointT>::Ptr select_hip_registration_method(const std::string& registration_method, Params& pnh) {
   using Reg = HipRegistration<PointT, PointT>;
   if (registration_method == "FAST_GICP_HIP") {
     std::cout << "registration: FAST_GICP_HIP" << std::endl;

@@ -90,7 +90,8 @@ enum dgs_ndt_line_search { DGS_NDT_LS_FIXED_STEP = 0, DGS_NDT_LS_MORE_THUENTE = 
  * UPSTREAM (default since ABI 5): every float operation of upstream's per-voxel update in upstream's order, individually rounded (no FMA), a
  *   platform-independent exp, each voxel's increments added to the point's double totals, the full (not exactly symmetric)
  *   6x6 Hessian, Jacobi-SVD Newton solve; the points' totals are summed in the GPU's own fixed order, so only the order of
- *   the double summation differs from a CPU run of upstream.
+ *   the double summation differs from a CPU run of upstream.  That order follows the launch: a pair's bits are reproducible only for
+ *   an identical batch composition, unless dgs_set_batch_independent.
  * UPSTREAM_SEQUENTIAL: as UPSTREAM, and the per-point totals are written out and summed in point-index order like
  *   upstream's final loop: every evaluation is bit-identical to the CPU restatement (slow: one lane per sum). */
 enum dgs_ndt_strict_order { DGS_NDT_ORDER_FAST = 0, DGS_NDT_ORDER_UPSTREAM = 1, DGS_NDT_ORDER_UPSTREAM_SEQUENTIAL = 2 };
@@ -227,6 +228,23 @@ int dgs_set_pcl_gicp_options(dgs_handle* h, const dgs_pcl_gicp_options* options)
 /* setCorrespondenceRandomness on a live GICP_HIP handle (dgs_params.gicp_correspondence_randomness): the covariances of the target and
  * of every source are recomputed for the new k at the next align.  DGS_ERR_UNSUPPORTED on a handle of another method. */
 int dgs_pcl_gicp_set_correspondence_randomness(dgs_handle* h, int32_t k);
+
+/* Batch-independent results on request.  Off by default; while it is on, every dgs_result field of a pair, and every
+ * fitness, is a function of (method parameters, target, source, guess) alone: batch size, the pair's neighbours in the batch, the launch
+ * shape and the entry point (dgs_align, dgs_align_batch*, dgs_align_pairs_clouds, a dgs_group member) do not enter.  May be changed
+ * between calls at any time; nothing that is cached on clouds is invalidated.
+ *   behaviour changes: FAST_GICP and FAST_VGICP sum a pair over slices that follow its own size -- the layout of a lone default dgs_align,
+ *     so a pair of any batch carries the bits of its own single align with the switch OFF; NDT with ndt_strict_order 1 takes the
+ *     item-compacted kernel's fixed slices (what DGS_NDT_FIXED_SLICES=1 at dgs_create selects, which keeps giving the initial value).
+ *   fitness routing only: NDT order 2, ICP_HIP, GICP_HIP, PCL_NDT_HIP -- their sums are batch-independent already.  For every method,
+ *     dgs_get_fitness_score and the fitness of dgs_align_batch* (and of dgs_group_align_batch*) then go through the edge scorer of
+ *     dgs_calc_fitness_score_batch_clouds, whose rows follow the edge alone; the value stays within a relative 1e-9 of the default one.
+ *   refused: NDT with ndt_strict_order 0 (the re-associated fast order), and order 1 under DGS_NDT_STRICT_KERNEL=2: DGS_ERR_UNSUPPORTED,
+ *     the reason in dgs_last_error.  NULL handle or NULL `on`: DGS_ERR_INVALID_ARGUMENT.  No device work in any of the three calls.
+ * A target whose index an earlier switch-off batch of ten or more candidates built k-d ordered keeps the covariances made from that index.
+ * Additions only: DGS_ABI_VERSION is unchanged. */
+int dgs_set_batch_independent(dgs_handle* h, int32_t on);
+int dgs_get_batch_independent(const dgs_handle* h, int32_t* on);
 
 /* Run all of this handle's work on a caller-owned hipStream_t (NULL = a stream the handle owns). */
 int dgs_set_stream(dgs_handle* h, void* hip_stream);
@@ -389,6 +407,7 @@ dgs_handle* dgs_group_member(dgs_group* g, int32_t k);         /* member k's han
 int dgs_group_set_input_target(dgs_group* g, const float* xyz16, int64_t n);
 int dgs_group_set_icp_options(dgs_group* g, const dgs_icp_options* options);   /* dgs_set_icp_options on every member */
 int dgs_group_set_pcl_gicp_options(dgs_group* g, const dgs_pcl_gicp_options* options);   /* dgs_set_pcl_gicp_options on every member */
+int dgs_group_set_batch_independent(dgs_group* g, int32_t on);   /* dgs_set_batch_independent on every member: a candidate's record is the same whichever member registers it */
 int dgs_group_align_batch(dgs_group* g, int32_t n, const float* const* sources, const int64_t* sizes, const float* guesses16,
                           int32_t compute_fitness, double fitness_max_range, dgs_result* results, int32_t* best_index, double* best_score);
 
