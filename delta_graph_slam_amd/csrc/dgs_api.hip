@@ -345,6 +345,7 @@ int dgs_pcl_gicp_set_correspondence_randomness(dgs_handle* h, int32_t k) {
   if (!h || k < 1) return DGS_ERR_INVALID_ARGUMENT;
   h->err.clear();
   if (h->prm.method != DGS_METHOD_PCL_GICP) { h->err = "dgs_pcl_gicp_set_correspondence_randomness: not a GICP_HIP handle"; return DGS_ERR_UNSUPPORTED; }
+  if (k > dgs::kKnnMaxWide) { h->err = dgs::kKnnTooWide; return DGS_ERR_UNSUPPORTED; }
   h->prm.gicp_correspondence_randomness = k;   // CloudState::pcov is keyed by k: every cloud recomputes at its next use
   return DGS_OK;
 }
@@ -492,6 +493,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (const char* e = std::getenv("DGS_NN_KD_MIN_QUERIES")) h->nn_kd_min_queries = std::atoll(e);
   if (const char* e = std::getenv("DGS_KNN_PARTS")) { const int v = std::atoi(e); h->knn_parts = (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }
   if (const char* e = std::getenv("DGS_KNN_LEAF")) h->knn_leaf = std::atoi(e) != 0;
+  if (const char* e = std::getenv("DGS_KNN_LEAF_WIDE")) h->knn_leaf_wide = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_KNN_MIN_WAVES")) h->knn_min_waves = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("DGS_KNN_ROUNDS")) h->knn_rounds = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("DGS_GICP_FUSED")) h->gicp_fused = std::atoi(e) != 0;

@@ -80,7 +80,9 @@ __device__ void regularize_cov(const double* cov9, int method_and_flag, double* 
 // round: all k neighbours of q' lie within r_k(q') + |q - q'| of q (pruning only: same sets).  It writes the set of every
 // point to `nbr` (slot r * 8 + sub of the 8-lane group -> nbr[pos * 32 + slot], -1 = nothing found).  (2)
 // gicp_cov_from_knn_kernel: 8 lanes per point gather the neighbours and reduce mean and covariance in double; one lane per point regularises.
-__global__ __launch_bounds__(kBlock) void gicp_knn_kernel(const BvhView b, const int n, const int k, const int run, int* __restrict__ nbr) {
+// SLOTS = 4: k <= 32, table stride kKnnMax; SLOTS = 8: k <= 64, table stride kKnnMaxWide (the wide kernels below).
+template <int SLOTS>
+__device__ __forceinline__ void gicp_knn_body(const BvhView& b, const int n, const int k, const int run, int* __restrict__ nbr) {
   const int sub = threadIdx.x & 7;
   const int wave = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
   const int first = wave * (8 * run) + ((threadIdx.x & 63) >> 3);
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void gicp_knn_kernel(const BvhView b, const
     const int i = (pos < n) ? (int)__float_as_uint(q.w) : -1;
     const bool alive = pos < n && i >= 0 && i < n;
     const float bound = nn_warm_bound_round(prev_kth, prev_found, q.x, q.y, q.z, px, py, pz);
-    KnnList L;
+    KnnListT<SLOTS> L;
     knn_query_group(b, q.x, q.y, q.z, alive, k, L, bound);
     const unsigned long long worst = knn_largest(L);
     prev_kth = __uint_as_float((unsigned)(worst >> 32));
@@ -101,12 +103,18 @@ __global__ __launch_bounds__(kBlock) void gicp_knn_kernel(const BvhView b, const
     px = q.x; py = q.y; pz = q.z;
     if (alive) {
 #pragma unroll
-      for (int s = 0; s < kKnnSlots; s++) {
+      for (int s = 0; s < SLOTS; s++) {
         const int slot = s * 8 + sub;
-        if (slot < k) nbr[(size_t)pos * kKnnMax + slot] = (L.dist(s) < INFINITY) ? L.index(s) : -1;
+        if (slot < k) nbr[(size_t)pos * (SLOTS * 8) + slot] = (L.dist(s) < INFINITY) ? L.index(s) : -1;
       }
     }
   }
+}
+__global__ __launch_bounds__(kBlock) void gicp_knn_kernel(const BvhView b, const int n, const int k, const int run, int* __restrict__ nbr) {
+  gicp_knn_body<kKnnSlots>(b, n, k, run, nbr);
+}
+__global__ __launch_bounds__(kBlock) void gicp_knn_wide_kernel(const BvhView b, const int n, const int k, const int run, int* __restrict__ nbr) {
+  gicp_knn_body<kKnnSlotsWide>(b, n, k, run, nbr);
 }
 
 // ---- k-NN sets, one WAVE per leaf of the index (8 Hilbert-adjacent query points), in three cooperative steps:
@@ -192,7 +200,9 @@ __device__ __forceinline__ unsigned kth_smallest_upper_bound(const unsigned d, c
 // Step (a) for NQ queries j0 .. j0 + NQ - 1 of the leaf at once: per query an UPPER BOUND of the k-th smallest distance to the 64 window
 // points (the top 14 bits of the bit descent, the undecided low bits set: within 1.6 %, and it only prunes), written to lane j of Tl.
 // Returns false when a query has fewer than k finite window points (the caller takes the careful path).
-template <int NQ>
+// FULL: k may be the whole window (the wide kernel at k = 64).  Then "exactly k values below trial" holds at the first bit tried and says
+// nothing -- no (k + 1)-th value stands above it -- so the descent goes on to the bits of the largest window distance itself.
+template <int NQ, bool FULL>
 __device__ __forceinline__ bool knn_window_bounds(const float4 wp, const bool wfinite, const int w0, const int j0, const int k, float& Tl) {
   const int lane = threadIdx.x & 63;
   unsigned d[NQ], V[NQ];
@@ -216,7 +226,7 @@ __device__ __forceinline__ bool knn_window_bounds(const float4 wp, const bool wf
       const unsigned trial = V[t] | (1u << bit);
       const int cnt = __popcll(__ballot(d[t] < trial));
       if (!done[t]) {
-        if (cnt == k) { V[t] = trial; done[t] = true; }   // exactly k values below trial: the k-th smallest is below it
+        if (cnt == k && (!FULL || k < kWave)) { V[t] = trial; done[t] = true; }   // exactly k values below trial: the k-th smallest is below it
         else if (cnt < k) V[t] = trial;
       }
     }
@@ -298,7 +308,7 @@ __device__ __forceinline__ int knn_gather_leaves(const BvhView& b, const float4 
 
 // step (c) for a candidate list of exactly NCH chunks (NCH * 8 leaves, the last chunk possibly partial): per open query the k-th smallest
 // candidate distance, the selection (ties at the k-th distance to the lower index) and its neighbour list; answered queries leave `open`
-template <int NCH>
+template <int NCH, int STRIDE>
 __device__ __forceinline__ void knn_select(const BvhView& b, const float4 wp, const int w0, const int n_q, const int n_cand, const int k, const float Tl,
                                            const float scale, const int* leaves, int* __restrict__ nbr, const int l, unsigned& open) {
   const int lane = threadIdx.x & 63;
@@ -360,7 +370,7 @@ __device__ __forceinline__ void knn_select(const BvhView& b, const float4 wp, co
         }
       }
     }
-    int* __restrict__ out = nbr + (size_t)(l * kLeaf + j) * kKnnMax;
+    int* __restrict__ out = nbr + (size_t)(l * kLeaf + j) * STRIDE;
     int written = 0;
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
@@ -374,11 +384,11 @@ __device__ __forceinline__ void knn_select(const BvhView& b, const float4 wp, co
   }
 }
 
-template <int N>
+template <int N, int STRIDE>
 __device__ __forceinline__ void knn_select_dispatch(const int chunks, const BvhView& b, const float4 wp, const int w0, const int n_q, const int n_cand, const int k,
                                                     const float Tl, const float scale, const int* leaves, int* __restrict__ nbr, const int l, unsigned& open) {
-  if (chunks <= N || N == kLeafChunks) knn_select<N>(b, wp, w0, n_q, n_cand, k, Tl, scale, leaves, nbr, l, open);
-  else if constexpr (N < kLeafChunks) knn_select_dispatch<N + 1>(chunks, b, wp, w0, n_q, n_cand, k, Tl, scale, leaves, nbr, l, open);
+  if (chunks <= N || N == kLeafChunks) knn_select<N, STRIDE>(b, wp, w0, n_q, n_cand, k, Tl, scale, leaves, nbr, l, open);
+  else if constexpr (N < kLeafChunks) knn_select_dispatch<N + 1, STRIDE>(chunks, b, wp, w0, n_q, n_cand, k, Tl, scale, leaves, nbr, l, open);
 }
 
 // `parts` (1, 2, 4 or 8) waves share a leaf, each answering 8 / parts of its queries: a small cloud has too few leaves to fill the
@@ -388,7 +398,8 @@ __device__ __forceinline__ void knn_select_dispatch(const int chunks, const BvhV
 #ifndef DGS_KNN_WAVES
 #define DGS_KNN_WAVES 4
 #endif
-__global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void gicp_knn_leaf_kernel(const BvhView b, const int n, const int k, const int parts, int* __restrict__ nbr, int* __restrict__ stats) {
+template <int SLOTS>
+__device__ __forceinline__ void gicp_knn_leaf_body(const BvhView& b, const int n, const int k, const int parts, int* __restrict__ nbr, int* __restrict__ stats) {
   __shared__ int s_front[kBlock / kWave][2][kFrontCap];
   __shared__ int s_leaves[kBlock / kWave][kLeafCap];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -417,11 +428,11 @@ __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void gicp_knn_leaf_kernel(co
     // the bounds of this wave's queries, their descents interleaved (one descent is a chain of dependent ballot -> count -> branch
     // rounds; 2 / 4 / 8 of them side by side hide each other's latency)
     switch (j_hi - j_lo) {
-      case 8: fast = knn_window_bounds<8>(wp, wfinite, w0, j_lo, k, Tl); break;
-      case 4: fast = knn_window_bounds<4>(wp, wfinite, w0, j_lo, k, Tl); break;
-      case 2: fast = knn_window_bounds<2>(wp, wfinite, w0, j_lo, k, Tl); break;
+      case 8: fast = knn_window_bounds<8, (SLOTS > kKnnSlots)>(wp, wfinite, w0, j_lo, k, Tl); break;
+      case 4: fast = knn_window_bounds<4, (SLOTS > kKnnSlots)>(wp, wfinite, w0, j_lo, k, Tl); break;
+      case 2: fast = knn_window_bounds<2, (SLOTS > kKnnSlots)>(wp, wfinite, w0, j_lo, k, Tl); break;
       default:
-        for (int j = j_lo; j < j_hi && fast; j++) fast = knn_window_bounds<1>(wp, wfinite, w0, j, k, Tl);
+        for (int j = j_lo; j < j_hi && fast; j++) fast = knn_window_bounds<1, (SLOTS > kKnnSlots)>(wp, wfinite, w0, j, k, Tl);
         break;
     }
   }
@@ -452,7 +463,7 @@ __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void gicp_knn_leaf_kernel(co
       // instructions per wave, `profiles/r03/knn_*`), not by anything it computes.
       const int chunks = (n_cand + 7) >> 3;
       const unsigned was_open = open;
-      knn_select_dispatch<1>(chunks, b, wp, w0, n_q, n_cand, k, Tl, scale, s_leaves[wv], nbr, l, open);
+      knn_select_dispatch<1, SLOTS * 8>(chunks, b, wp, w0, n_q, n_cand, k, Tl, scale, s_leaves[wv], nbr, l, open);
 #ifdef DGS_KNN_STATS
       acc_c += wall_clock64() - tb1;
 #endif
@@ -477,16 +488,28 @@ __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void gicp_knn_leaf_kernel(co
     const float4 q = (mine && pos < n) ? b.sorted[pos] : make_float4(0.f, 0.f, 0.f, 0.f);
     const int i = (mine && pos < n) ? (int)__float_as_uint(q.w) : -1;
     const bool alive = mine && pos < n && i >= 0 && i < n;
-    KnnList L;
+    KnnListT<SLOTS> L;
     knn_query_group(b, q.x, q.y, q.z, alive, k, L);
     if (alive) {
 #pragma unroll
-      for (int s = 0; s < kKnnSlots; s++) {
+      for (int s = 0; s < SLOTS; s++) {
         const int slot = s * 8 + sub;
-        if (slot < k) nbr[(size_t)pos * kKnnMax + slot] = (L.dist(s) < INFINITY) ? L.index(s) : -1;
+        if (slot < k) nbr[(size_t)pos * (SLOTS * 8) + slot] = (L.dist(s) < INFINITY) ? L.index(s) : -1;
       }
     }
   }
+}
+__global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void gicp_knn_leaf_kernel(const BvhView b, const int n, const int k, const int parts, int* __restrict__ nbr, int* __restrict__ stats) {
+  gicp_knn_leaf_body<kKnnSlots>(b, n, k, parts, nbr, stats);
+}
+// 32 < k <= 64.  The window of step (a) stays 8 leaves = 64 points, one per lane: it bounds the k-th distance of a query by its k-th
+// smallest distance to those 64 points, which for k near 64 is the far edge of the window -- a loose bound, more gathered leaves, more
+// retries with a scaled bound (the sets do not depend on it).  Whether this or the per-query walk serves wide k: knn_lists.
+// The narrow kernel's occupancy bound on purpose: under 4 waves per SIMD (128 registers) this form spills 24 registers (100 bytes of scratch
+// per lane), under 3 waves it needs 151 registers and spills nothing -- and is 9 to 16 % slower at every k measured (33 .. 60, both bench
+// clouds: 0.136 against 0.118 ms per 65,536-point cloud at k = 33, 0.178 against 0.154 ms at k = 60).
+__global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void gicp_knn_leaf_wide_kernel(const BvhView b, const int n, const int k, const int parts, int* __restrict__ nbr, int* __restrict__ stats) {
+  gicp_knn_leaf_body<kKnnSlotsWide>(b, n, k, parts, nbr, stats);
 }
 
 // One wave per 64 points, two phases.  (1) eight rounds of 8 points, 8 lanes per point: gather the neighbours, mean and covariance in
@@ -500,8 +523,9 @@ __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void gicp_knn_leaf_kernel(co
 // 8 rounds fill every lane of the second phase but leave a 65,536-point cloud with one wave per SIMD and nothing to hide its gathers
 // behind; measured 8 / 4 / 2 rounds: 23.6 / 20.8 / 25.4 us per 65,536-point cloud, 21.5 / 14.6 / 15.2 us per 26,668 points.
 constexpr int kCovRounds = DGS_COV_ROUNDS, kCovPerWave = kCovRounds * 8;
-__global__ __launch_bounds__(kBlock) void gicp_cov_from_knn_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int method,
-                                                                   const int* __restrict__ nbr, double* __restrict__ cov6) {
+template <int SLOTS>
+__device__ __forceinline__ void gicp_cov_from_knn_body(const BvhView& b, const float4* __restrict__ pts, const int n, const int k, const int method,
+                                                       const int* __restrict__ nbr, double* __restrict__ cov6) {
   __shared__ double s_c[kBlock / kWave][kCovPerWave][6];
   __shared__ int s_i[kBlock / kWave][kCovPerWave];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, sub = lane & 7, grp = lane >> 3;
@@ -515,13 +539,13 @@ __global__ __launch_bounds__(kBlock) void gicp_cov_from_knn_kernel(const BvhView
     if (pos < n) i = (int)__float_as_uint(b.sorted[pos].w);
     const bool live = i >= 0 && i < n;
     // neighbours of this lane (slots q * 8 + sub < k); slots that found nothing are zero columns, as upstream's matrix
-    double px[kKnnSlots], py[kKnnSlots], pz[kKnnSlots];
-    bool use[kKnnSlots];
+    double px[SLOTS], py[SLOTS], pz[SLOTS];
+    bool use[SLOTS];
     double sx = 0, sy = 0, sz = 0;
 #pragma unroll
-    for (int q = 0; q < kKnnSlots; q++) {
+    for (int q = 0; q < SLOTS; q++) {
       use[q] = (q * 8 + sub) < k;
-      const int j = (live && use[q]) ? nbr[(size_t)pos * kKnnMax + q * 8 + sub] : -1;
+      const int j = (live && use[q]) ? nbr[(size_t)pos * (SLOTS * 8) + q * 8 + sub] : -1;
       const float4 p = (j >= 0) ? pts[j] : make_float4(0.f, 0.f, 0.f, 0.f);
       px[q] = p.x; py[q] = p.y; pz[q] = p.z;
       if (use[q]) { sx += px[q]; sy += py[q]; sz += pz[q]; }
@@ -529,7 +553,7 @@ __global__ __launch_bounds__(kBlock) void gicp_cov_from_knn_kernel(const BvhView
     const double mx = group8_sum_f64(sx) / kk, my = group8_sum_f64(sy) / kk, mz = group8_sum_f64(sz) / kk;
     double c[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int q = 0; q < kKnnSlots; q++) {
+    for (int q = 0; q < SLOTS; q++) {
       if (use[q]) {
         const double dx = px[q] - mx, dy = py[q] - my, dz = pz[q] - mz;
         c[0] += dx * dx; c[1] += dx * dy; c[2] += dx * dz; c[3] += dy * dy; c[4] += dy * dz; c[5] += dz * dz;
@@ -554,6 +578,15 @@ __global__ __launch_bounds__(kBlock) void gicp_cov_from_knn_kernel(const BvhView
   regularize_cov(cov9, method, out6);
 #pragma unroll
   for (int a = 0; a < 6; a++) cov6[(size_t)i * 6 + a] = out6[a];
+}
+__global__ __launch_bounds__(kBlock) void gicp_cov_from_knn_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int method,
+                                                                   const int* __restrict__ nbr, double* __restrict__ cov6) {
+  gicp_cov_from_knn_body<kKnnSlots>(b, pts, n, k, method, nbr, cov6);
+}
+// 32 < k <= 64: 8 slots per lane, table stride kKnnMaxWide; the same sums in the same order per lane (slot q * 8 + sub, q ascending), then the same tree
+__global__ __launch_bounds__(kBlock) void gicp_cov_from_knn_wide_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int method,
+                                                                        const int* __restrict__ nbr, double* __restrict__ cov6) {
+  gicp_cov_from_knn_body<kKnnSlotsWide>(b, pts, n, k, method, nbr, cov6);
 }
 
 // ================================================================================================ K5 correspondences
@@ -1422,26 +1455,38 @@ int gicp_ensure_target_covariance(dgs_handle* h) {
   return ensure_covariance(h, *h->tgt);
 }
 
-// Exact k-NN of every point of `c` in `c` itself (the point included) -> h->knn_nbr (nbr[pos * kKnnMax + slot], pos in c.bvh's order).
-// Shared by FAST_GICP's covariances, GICP_HIP's (pcl_gicp.hip) and the prefilter (prefilter.hip, which passes a buffer of its own).
-int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out) {
+// Exact k-NN of every point of `c` in `c` itself (the point included) -> h->knn_nbr (nbr[pos * stride + slot], pos in c.bvh's order).
+// Shared by FAST_GICP's covariances, GICP_HIP's (pcl_gicp.hip), the prefilter (prefilter.hip) and floor detection (floor_detection.hip),
+// the last two with a buffer of their own.
+// Two widths.  A caller that passes `stride` reads the table at the stride it gets back: kKnnMax (32) for k <= 32 -- the kernels every
+// earlier release ran, unchanged -- and kKnnMaxWide (64) for 32 < k <= 64, the wide kernels.  Only the GICP family's covariance passes do
+// (ensure_covariance here, ensure_pcov in pcl_gicp.hip).  A caller that does not -- the prefilter's pf_radius / pf_statistical / normals and
+// floor detection -- keeps k <= 32 and stride 32: their limits, messages and kernels are as they were.
+// Which search makes the lists: the wave-per-leaf search at either width (measured 10 to 13 times faster than the per-query walk with
+// warm bounds at every k in 33 .. 64 on both bench clouds); DGS_KNN_LEAF=0 selects the walk for every k,
+// DGS_KNN_LEAF_WIDE=0 for wide k only.
+static bool knn_uses_leaf_search(const dgs_handle* h, const int k) { return h->knn_leaf && (k <= kKnnMax || h->knn_leaf_wide); }
+int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out, int* stride) {
   DevBuf<int>& nbr = out ? *out : h->knn_nbr;
-  if (k > kKnnMax) {
-    h->err = "reg_correspondence_randomness > 32 is not supported by the HIP k-NN";
+  if (k > (stride ? kKnnMaxWide : kKnnMax)) {
+    h->err = stride ? kKnnTooWide : "reg_correspondence_randomness > 32 is not supported by the HIP k-NN";
     return DGS_ERR_UNSUPPORTED;
   }
+  const bool wide = k > kKnnMax;
+  const int width = wide ? kKnnMaxWide : kKnnMax;
+  if (stride) *stride = width;
   if (!c.bvh.valid) {
     // the target of a batch is searched by every candidate at every linearisation: worth the slower k-d ordered build (nn_bvh.hip)
     int rc = bvh_build(h, c.bvh, c.pts.ptr, c.n, nullptr, h->batch_kd && &c == h->tgt);
     if (rc) return rc;
   }
   const BvhView v = make_bvh_view(c.bvh);
-  DGS_HIP_TRY(h, nbr.reserve((size_t)c.n * kKnnMax));
+  DGS_HIP_TRY(h, nbr.reserve((size_t)c.n * width));
   DGS_HIP_TRY(h, h->knn_stats.reserve(8));
   // rounds per wave: enough waves to fill the chip several times over, and stretches long enough for the warm bounds to pay
   const int run = (int)std::max<int64_t>(1, std::min<int64_t>(h->knn_rounds, (c.n + 8 * (int64_t)h->knn_min_waves - 1) / (8 * (int64_t)h->knn_min_waves)));
   const int64_t waves = (c.n + 8 * (int64_t)run - 1) / (8 * (int64_t)run);
-  if (h->knn_leaf) {
+  if (knn_uses_leaf_search(h, k)) {
     const int64_t n_leaves = (c.n + kLeaf - 1) / kLeaf;
     // waves per leaf (each answers 8 / parts of the leaf's queries after its own walk, whose loops run over ITS queries only): measured
     // 1 / 2 / 4 / 8 waves per leaf: 0.168 / 0.148 / 0.143 / 0.160 ms per 65,536-point cloud, 0.099 / 0.076 / 0.065 / 0.069 ms per 26,668 points
@@ -1451,19 +1496,25 @@ int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out) {
 #ifdef DGS_KNN_STATS
     (void)hipMemsetAsync(h->knn_stats.ptr, 0, 8 * sizeof(int), h->stream);
 #endif
-    hipLaunchKernelGGL(gicp_knn_leaf_kernel, dim3((unsigned)((n_leaves * parts + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, h->stream, v, (int)c.n,
-                       k, parts, nbr.ptr, h->knn_stats.ptr);
+    const dim3 grid((unsigned)((n_leaves * parts + kBlock / kWave - 1) / (kBlock / kWave)));
+    if (wide)
+      hipLaunchKernelGGL(gicp_knn_leaf_wide_kernel, grid, dim3(kBlock), 0, h->stream, v, (int)c.n, k, parts, nbr.ptr, h->knn_stats.ptr);
+    else
+      hipLaunchKernelGGL(gicp_knn_leaf_kernel, grid, dim3(kBlock), 0, h->stream, v, (int)c.n, k, parts, nbr.ptr, h->knn_stats.ptr);
   } else {
-    hipLaunchKernelGGL(gicp_knn_kernel, dim3((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, h->stream, v, (int)c.n, k, run,
-                       nbr.ptr);
+    const dim3 grid((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave)));
+    if (wide)
+      hipLaunchKernelGGL(gicp_knn_wide_kernel, grid, dim3(kBlock), 0, h->stream, v, (int)c.n, k, run, nbr.ptr);
+    else
+      hipLaunchKernelGGL(gicp_knn_kernel, grid, dim3(kBlock), 0, h->stream, v, (int)c.n, k, run, nbr.ptr);
   }
   return DGS_OK;
 }
 
 static int ensure_covariance(dgs_handle* h, CloudState& c) {
   if (c.cov_valid && c.cov_k == h->gconsts.k && c.cov_reg == h->gconsts.regularization) return DGS_OK;
-  if (h->gconsts.k > kKnnMax) {
-    h->err = "reg_correspondence_randomness > 32 is not supported by the HIP k-NN";
+  if (h->gconsts.k > kKnnMaxWide) {
+    h->err = kKnnTooWide;
     return DGS_ERR_UNSUPPORTED;
   }
   if (!c.bvh.valid) {
@@ -1473,18 +1524,22 @@ static int ensure_covariance(dgs_handle* h, CloudState& c) {
   DGS_HIP_TRY(h, c.cov.reserve((size_t)c.n * 6));
   const BvhView v = make_bvh_view(c.bvh);
   int slot = prof_begin(h, DGS_K_GICP_COVARIANCE);
-  int rc = knn_lists(h, c, h->gconsts.k);
+  int stride = 0;
+  int rc = knn_lists(h, c, h->gconsts.k, nullptr, &stride);
   if (rc) return rc;
   constexpr int kCovPerBlock = kCovPerWave * (kBlock / kWave);
+  const dim3 cov_grid((unsigned)(((int64_t)c.n + kCovPerBlock - 1) / kCovPerBlock));
+  const int cov_method = h->gconsts.regularization | (h->prm.gicp_cov_jacobi_svd ? 0x100 : 0);
   if (h->prm.gicp_cov_jacobi_svd == DGS_GICP_COV_UPSTREAM_ORDER)   // ordered lists, sequential sums, JacobiSVD: gicp_cov_ordered.hip
-    gicp_cov_upstream_order(h, v, c, h->gconsts.k, h->gconsts.regularization, h->knn_nbr.ptr);
+    gicp_cov_upstream_order(h, v, c, h->gconsts.k, h->gconsts.regularization, h->knn_nbr.ptr, stride);
+  else if (stride == kKnnMaxWide)
+    hipLaunchKernelGGL(gicp_cov_from_knn_wide_kernel, cov_grid, dim3(kBlock), 0, h->stream, v, c.pts.ptr, (int)c.n, h->gconsts.k, cov_method, h->knn_nbr.ptr, c.cov.ptr);
   else
-    hipLaunchKernelGGL(gicp_cov_from_knn_kernel, dim3((unsigned)(((int64_t)c.n + kCovPerBlock - 1) / kCovPerBlock)), dim3(kBlock), 0, h->stream, v, c.pts.ptr, (int)c.n,
-                       h->gconsts.k, h->gconsts.regularization | (h->prm.gicp_cov_jacobi_svd ? 0x100 : 0), h->knn_nbr.ptr, c.cov.ptr);
+    hipLaunchKernelGGL(gicp_cov_from_knn_kernel, cov_grid, dim3(kBlock), 0, h->stream, v, c.pts.ptr, (int)c.n, h->gconsts.k, cov_method, h->knn_nbr.ptr, c.cov.ptr);
   prof_end(h, DGS_K_GICP_COVARIANCE, slot);
   DGS_HIP_TRY(h, hipGetLastError());
 #ifdef DGS_KNN_STATS
-  if (h->knn_leaf) {
+  if (knn_uses_leaf_search(h, h->gconsts.k)) {
     int st[8];
     (void)hipMemcpyAsync(st, h->knn_stats.ptr, sizeof(st), hipMemcpyDeviceToHost, h->stream);
     (void)hipStreamSynchronize(h->stream);

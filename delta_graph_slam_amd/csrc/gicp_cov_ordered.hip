@@ -64,29 +64,35 @@ __device__ static void regularize_cov_upstream(const double* cov9, const int met
 #endif
 constexpr int kOrdRounds = DGS_COV_ORDERED_ROUNDS, kOrdPerWave = kOrdRounds * 8, kOrdPerBlock = kOrdPerWave * (kBlock / kWave);
 static_assert(kOrdPerWave <= kWave, "phase 2 takes one lane per point");
+// The wide form (32 < k <= 64: 8 slots per lane, table stride kKnnMaxWide) takes 2 rounds = 16 points per wave: 3 * 64 * 16 * 4 = 12 KiB of
+// LDS per wave at k = 64, the 48 KiB per workgroup of the narrow form at k = 32 (4 rounds would ask for 96 KiB).
+constexpr int kOrdRoundsWide = 2, kOrdPerWaveWide = kOrdRoundsWide * 8, kOrdPerBlockWide = kOrdPerWaveWide * (kBlock / kWave);
 
-__global__ __launch_bounds__(kBlock) void gicp_cov_ordered_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int method,
-                                                                  const int* __restrict__ nbr, double* __restrict__ cov6) {
+// SLOTS slots per lane (table stride SLOTS * 8), ROUNDS rounds of 8 points per wave
+template <int SLOTS, int ROUNDS>
+__device__ __forceinline__ void gicp_cov_ordered_body(const BvhView& b, const float4* __restrict__ pts, const int n, const int k, const int method,
+                                                      const int* __restrict__ nbr, double* __restrict__ cov6) {
+  constexpr int kPerWave = ROUNDS * 8;                // points of a wave in this instantiation
   extern __shared__ float s_xyz[];                    // [wave][coordinate][rank < k][point of the wave]
-  __shared__ int s_i[kBlock / kWave][kOrdPerWave];
+  __shared__ int s_i[kBlock / kWave][kPerWave];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, sub = lane & 7, grp = lane >> 3;
-  const int wave_base = (blockIdx.x * (kBlock / kWave) + wv) * kOrdPerWave;   // first point (position in index order) of this wave
+  const int wave_base = (blockIdx.x * (kBlock / kWave) + wv) * kPerWave;   // first point (position in index order) of this wave
   if (wave_base >= n) return;   // wave-uniform; the kernel has no workgroup barrier
-  float* __restrict__ sw = s_xyz + (size_t)wv * 3 * k * kOrdPerWave;
-  float* __restrict__ sx = sw, * __restrict__ sy = sw + k * kOrdPerWave, * __restrict__ sz = sw + 2 * k * kOrdPerWave;
+  float* __restrict__ sw = s_xyz + (size_t)wv * 3 * k * kPerWave;
+  float* __restrict__ sx = sw, * __restrict__ sy = sw + k * kPerWave, * __restrict__ sz = sw + 2 * k * kPerWave;
 #pragma unroll 1
-  for (int r = 0; r < kOrdRounds; r++) {
+  for (int r = 0; r < ROUNDS; r++) {
     const int pt = r * 8 + grp, pos = wave_base + pt;
     const float4 q = (pos < n) ? b.sorted[pos] : make_float4(0.f, 0.f, 0.f, 0.f);
     const int i = (pos < n) ? (int)__float_as_uint(q.w) : -1;
     const bool live = i >= 0 && i < n;
-    unsigned long long key[kKnnSlots];
-    float cx[kKnnSlots], cy[kKnnSlots], cz[kKnnSlots];
+    unsigned long long key[SLOTS];
+    float cx[SLOTS], cy[SLOTS], cz[SLOTS];
 #pragma unroll
-    for (int s = 0; s < kKnnSlots; s++) {
+    for (int s = 0; s < SLOTS; s++) {
       const int slot = s * 8 + sub;
       const bool used = slot < k;
-      int j = (live && used) ? nbr[(size_t)pos * kKnnMax + slot] : -1;
+      int j = (live && used) ? nbr[(size_t)pos * (SLOTS * 8) + slot] : -1;
       if ((unsigned)j >= (unsigned)n) j = -1;
       const float4 p = (j >= 0) ? pts[j] : make_float4(0.f, 0.f, 0.f, 0.f);
       cx[s] = p.x; cy[s] = p.y; cz[s] = p.z;
@@ -95,41 +101,43 @@ __global__ __launch_bounds__(kBlock) void gicp_cov_ordered_kernel(const BvhView 
       // unused slots: the largest key, below nothing; slots that found nothing: after every distance, in slot order
       key[s] = !used ? ~0ull : ((unsigned long long)((j >= 0) ? __float_as_uint(d) : 0xFFFFFFFFu) << 32) | (unsigned)((j >= 0) ? j : slot);
     }
-    int rank[kKnnSlots] = {0, 0, 0, 0};
+    int rank[SLOTS];
+#pragma unroll
+    for (int s = 0; s < SLOTS; s++) rank[s] = 0;
 #pragma unroll
     for (int l = 0; l < 8; l++)
 #pragma unroll
-      for (int t = 0; t < kKnnSlots; t++) {
+      for (int t = 0; t < SLOTS; t++) {
         const unsigned long long o = __shfl(key[t], l, 8);
 #pragma unroll
-        for (int s = 0; s < kKnnSlots; s++) rank[s] += (o < key[s]) ? 1 : 0;
+        for (int s = 0; s < SLOTS; s++) rank[s] += (o < key[s]) ? 1 : 0;
       }
 #pragma unroll
-    for (int s = 0; s < kKnnSlots; s++)
+    for (int s = 0; s < SLOTS; s++)
       if (s * 8 + sub < k && rank[s] < k) {   // rank < k always (k distinct keys below every unused one); the test keeps a store inside the wave's LDS whatever nbr holds
-        const int at = rank[s] * kOrdPerWave + pt;
+        const int at = rank[s] * kPerWave + pt;
         sx[at] = cx[s]; sy[at] = cy[s]; sz[at] = cz[s];
       }
     if (sub == 0) s_i[wv][pt] = live ? i : -1;
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS stores have landed
-  if (lane >= kOrdPerWave) return;
+  if (lane >= kPerWave) return;
   const int i = s_i[wv][lane];
   if (i < 0) return;
   const double kk = (double)k;
   double m0 = 0, m1 = 0, m2 = 0;
 #pragma unroll 4
   for (int j = 0; j < k; j++) {   // columns that found nothing add +0: the same bits as leaving them out
-    m0 += (double)sx[j * kOrdPerWave + lane];
-    m1 += (double)sy[j * kOrdPerWave + lane];
-    m2 += (double)sz[j * kOrdPerWave + lane];
+    m0 += (double)sx[j * kPerWave + lane];
+    m1 += (double)sy[j * kPerWave + lane];
+    m2 += (double)sz[j * kPerWave + lane];
   }
   m0 /= kk; m1 /= kk; m2 /= kk;
   double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 4
   for (int j = 0; j < k; j++) {
-    const double d[3] = {(double)sx[j * kOrdPerWave + lane] - m0, (double)sy[j * kOrdPerWave + lane] - m1, (double)sz[j * kOrdPerWave + lane] - m2};
+    const double d[3] = {(double)sx[j * kPerWave + lane] - m0, (double)sy[j * kPerWave + lane] - m1, (double)sz[j * kPerWave + lane] - m2};
 #pragma unroll
     for (int a = 0; a < 3; a++)
 #pragma unroll
@@ -142,9 +150,23 @@ __global__ __launch_bounds__(kBlock) void gicp_cov_ordered_kernel(const BvhView 
 #pragma unroll
   for (int a = 0; a < 6; a++) cov6[(size_t)i * 6 + a] = out6[a];
 }
+__global__ __launch_bounds__(kBlock) void gicp_cov_ordered_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int method,
+                                                                  const int* __restrict__ nbr, double* __restrict__ cov6) {
+  gicp_cov_ordered_body<kKnnSlots, kOrdRounds>(b, pts, n, k, method, nbr, cov6);
+}
+__global__ __launch_bounds__(kBlock) void gicp_cov_ordered_wide_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int method,
+                                                                       const int* __restrict__ nbr, double* __restrict__ cov6) {
+  gicp_cov_ordered_body<kKnnSlotsWide, kOrdRoundsWide>(b, pts, n, k, method, nbr, cov6);
+}
 
-// c.cov of every point of `c` from the k-NN lists in `nbr` (knn_lists), in upstream's operation order.
-int gicp_cov_upstream_order(dgs_handle* h, const BvhView& v, CloudState& c, int k, int regularization, const int* nbr) {
+// c.cov of every point of `c` from the k-NN lists in `nbr` (knn_lists, a table of stride `stride`), in upstream's operation order.
+int gicp_cov_upstream_order(dgs_handle* h, const BvhView& v, CloudState& c, int k, int regularization, const int* nbr, int stride) {
+  if (stride == kKnnMaxWide) {
+    const size_t lds = (size_t)(kBlock / kWave) * 3 * (size_t)k * kOrdPerWaveWide * sizeof(float);
+    hipLaunchKernelGGL(gicp_cov_ordered_wide_kernel, dim3((unsigned)(((int64_t)c.n + kOrdPerBlockWide - 1) / kOrdPerBlockWide)), dim3(kBlock), lds, h->stream, v, c.pts.ptr,
+                       (int)c.n, k, regularization, nbr, c.cov.ptr);
+    return DGS_OK;
+  }
   const size_t lds = (size_t)(kBlock / kWave) * 3 * (size_t)k * kOrdPerWave * sizeof(float);
   hipLaunchKernelGGL(gicp_cov_ordered_kernel, dim3((unsigned)(((int64_t)c.n + kOrdPerBlock - 1) / kOrdPerBlock)), dim3(kBlock), lds, h->stream, v, c.pts.ptr, (int)c.n, k,
                      regularization, nbr, c.cov.ptr);

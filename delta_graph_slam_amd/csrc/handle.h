@@ -380,7 +380,7 @@ struct dgs_handle {
   dgs::NdtConsts consts{};
   int64_t last_evaluations = 0;
   int64_t last_reused = 0;            // NDT, upstream orders: trial poses of the last align / batch found in the line search's cache (dgs_get_counts slot 6)
-  dgs::DevBuf<int> knn_nbr;           // k-NN sets of the cloud whose covariances are being made: [position in Hilbert order * 32 + slot]
+  dgs::DevBuf<int> knn_nbr;           // k-NN sets of the cloud whose covariances are being made: [position in Hilbert order * stride + slot], stride 32 (k <= 32) or 64
   dgs::DevBuf<int> knn_stats;         // debug build (-DDGS_KNN_STATS): waves, waves on the cooperative path, candidate leaves
   bool nn_kd = true;                  // DGS_NN_KD=0: Hilbert order also for the loop batch's target index
   int64_t nn_kd_min_queries = 6 * 65536;   // DGS_NN_KD_MIN_QUERIES: source points of a batch from which its target index is built k-d ordered
@@ -388,6 +388,7 @@ struct dgs_handle {
   bool batch_kd = false;              // set by dgs_align_batch* around its work: the target index it builds is k-d ordered
   int knn_parts = 0;                  // DGS_KNN_PARTS: waves per leaf in gicp_knn_leaf_kernel (0 = by cloud size)
   bool knn_leaf = true;               // DGS_KNN_LEAF=0: the per-query k-NN walk (gicp_knn_kernel) instead of the wave-per-leaf search
+  bool knn_leaf_wide = true;          // DGS_KNN_LEAF_WIDE=0: the per-query walk (gicp_knn_wide_kernel) for 32 < k <= 64 instead of the wave-per-leaf search
   int knn_min_waves = 4096;           // DGS_KNN_MIN_WAVES: ... but never fewer waves than this (4 per SIMD)
   int knn_rounds = 8;                 // DGS_KNN_ROUNDS: rounds of 8 adjacent queries per wave in gicp_knn_kernel (1 = no warm bounds)
   bool gicp_fused = true;             // DGS_GICP_FUSED=0: the optimiser step of FAST_GICP / FAST_VGICP as its own launch (gicp_solve_kernel)
@@ -593,7 +594,7 @@ int gicp_covariances(dgs_handle* h, int which, double* host_out6, int64_t n);
 int gicp_probe(dgs_handle* h, const double* T16_rowmajor, int error_only, double* err, double* H36, double* b6);
 // gicp_cov_ordered.hip: covariances in upstream's operation order (dgs_params.gicp_cov_jacobi_svd = DGS_GICP_COV_UPSTREAM_ORDER) from knn_lists' sets
 struct BvhView;
-int gicp_cov_upstream_order(dgs_handle* h, const BvhView& v, CloudState& c, int k, int regularization, const int* nbr);
+int gicp_cov_upstream_order(dgs_handle* h, const BvhView& v, CloudState& c, int k, int regularization, const int* nbr, int stride);
 // icp.hip
 int icp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);
@@ -601,7 +602,13 @@ const float* icp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int icp_trajectory(dgs_handle* h, int pair, float* T16s, double* mse, int32_t* n_corr, int capacity, int* len);
 void icp_release(dgs_handle* h);
 // gicp.hip: exact k-NN lists of a cloud in itself -> h->knn_nbr
-int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out = nullptr);   // out: default h->knn_nbr
+// out: default h->knn_nbr; stride: where the table's stride goes (kKnnMax or, k > 32, kKnnMaxWide) -- without it k <= 32 and the stride is kKnnMax
+int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out = nullptr, int* stride = nullptr);
+// the two widths of the k-NN lists (nn_group.h): slots per lane of the 8-lane group; the table's stride, which is the largest k of that width
+constexpr int kKnnSlots = 4, kKnnMax = kKnnSlots * 8;               // k <= 32: every consumer of the lists
+constexpr int kKnnSlotsWide = 8, kKnnMaxWide = kKnnSlotsWide * 8;   // 32 < k <= 64: the GICP family's covariances
+constexpr const char* kKnnTooWide = "reg_correspondence_randomness > 64 is not supported by the HIP k-NN";
+static_assert(kKnnMaxWide == 64, "kKnnTooWide names the limit");
 // prefilter.hip
 void prefilter_release(dgs_handle* h);
 // map_cloud.hip

@@ -238,18 +238,21 @@ __device__ __forceinline__ void nn_query_group(const BvhView& b, float x, float 
     nn_query_group_t<unsigned long long, WANT_INDEX>(b, x, y, z, alive, bound, best, best_idx);
 }
 
-// ---- exact k-NN for the 8-lane group (k <= 32): the k best (distance, index) pairs live in registers, 4 slots per lane, as an
+// ---- exact k-NN for the 8-lane group: the k best (distance, index) pairs live in registers, SLOTS slots per lane, as an
 // UNSORTED set of 64-bit keys (distance bits << 32 | index): squared distances are non-negative floats, so unsigned key order is
 // the lexicographic (distance, index) order and the set is deterministic.  The set tracks its largest key (the k-th best);
 // a better candidate replaces it.  Every cross-lane step is a DPP min / max inside the group: no LDS traffic, no sorted
 // insertion (measured: the sorted list with bpermute shuffles spent more time inserting than traversing).
-constexpr int kKnnSlots = 4;
-constexpr int kKnnMax = kKnnSlots * 8;
-struct KnnList {
-  unsigned long long key[kKnnSlots];  // slot r * 8 + sub; slots >= k hold 0 (never the largest), empty slots hold (inf, ~slot)
+// Two widths: 4 slots per lane (k <= 32: every consumer of the lists, neighbour tables of stride kKnnMax) and 8 slots per lane
+// (32 < k <= 64: the GICP family's covariances only, tables of stride kKnnMaxWide).
+// (kKnnSlots / kKnnMax and kKnnSlotsWide / kKnnMaxWide: handle.h, beside knn_lists.)
+template <int SLOTS>
+struct KnnListT {
+  unsigned long long key[SLOTS];  // slot r * 8 + sub; slots >= k hold 0 (never the largest), empty slots hold (inf, ~slot)
   __device__ __forceinline__ float dist(int r) const { return __uint_as_float((unsigned)(key[r] >> 32)); }
   __device__ __forceinline__ int index(int r) const { return (int)(unsigned)key[r]; }
 };
+using KnnList = KnnListT<kKnnSlots>;
 constexpr unsigned long long kKnnInvalid = ~0ull;
 
 __device__ __forceinline__ double group8_sum_f64(double v) {
@@ -291,20 +294,26 @@ __device__ __forceinline__ unsigned long long group8_max_u64(unsigned long long 
 }
 
 // largest key of the set = the current k-th best (group-uniform)
-__device__ __forceinline__ unsigned long long knn_largest(const KnnList& L) {
-  return group8_max_u64(max(max(L.key[0], L.key[1]), max(L.key[2], L.key[3])));
+template <int LO, int N>
+__device__ __forceinline__ unsigned long long knn_max_tree(const unsigned long long* key) {   // balanced: max(max(k0, k1), max(k2, k3)) for N = 4
+  if constexpr (N == 1) return key[LO];
+  else return max(knn_max_tree<LO, N / 2>(key), knn_max_tree<LO + N / 2, N - N / 2>(key));
+}
+template <int SLOTS>
+__device__ __forceinline__ unsigned long long knn_largest(const KnnListT<SLOTS>& L) {
+  return group8_max_u64(knn_max_tree<0, SLOTS>(L.key));
 }
 
 // All 8 lanes of the group end with the same distributed set.  `alive` = false lanes follow the control flow only.
 // Same instruction-lean loop as nn_query_group_t (32-bit pending word for trees of up to 5 levels, FLT_MAX instead of +inf as
 // the open bound so that one compare rejects the inverted boxes of empty slots).
 // `bound`: an upper bound on the squared distance of the k-th neighbour (INFINITY when nothing is known) -- pruning only.
-template <class PT>
-__device__ __forceinline__ void knn_query_group_t(const BvhView& b, float x, float y, float z, bool alive, int k, float bound, KnnList& L) {
+template <class PT, int SLOTS>
+__device__ __forceinline__ void knn_query_group_t(const BvhView& b, float x, float y, float z, bool alive, int k, float bound, KnnListT<SLOTS>& L) {
   const int lane = threadIdx.x & 63;
   const unsigned sub = lane & 7, gshift = lane & ~7, bit = 1u << sub;
 #pragma unroll
-  for (int r = 0; r < kKnnSlots; r++) {
+  for (int r = 0; r < SLOTS; r++) {
     const int slot = r * 8 + (int)sub;
     L.key[r] = (slot < k) ? (((unsigned long long)__float_as_uint(INFINITY) << 32) | (unsigned)(0x7FFFFFFF - slot)) : 0ull;
   }
@@ -341,7 +350,7 @@ __device__ __forceinline__ void knn_query_group_t(const BvhView& b, float x, flo
           while ((unsigned)(__ballot(cand != kKnnInvalid) >> gshift) & 0xFFu) {
             const unsigned long long best = group8_min_u64(cand);
 #pragma unroll
-            for (int r = 0; r < kKnnSlots; r++)
+            for (int r = 0; r < SLOTS; r++)
               if (L.key[r] == worst) L.key[r] = best;  // keys are unique: exactly one slot of one lane holds the largest
             worst = knn_largest(L);
             if (cand == best || !(cand < worst)) cand = kKnnInvalid;
@@ -366,11 +375,12 @@ __device__ __forceinline__ void knn_query_group_t(const BvhView& b, float x, flo
   }
 }
 
-__device__ __forceinline__ void knn_query_group(const BvhView& b, float x, float y, float z, bool alive, int k, KnnList& L, float bound = INFINITY) {
+template <int SLOTS>
+__device__ __forceinline__ void knn_query_group(const BvhView& b, float x, float y, float z, bool alive, int k, KnnListT<SLOTS>& L, float bound = INFINITY) {
   if (b.depth <= 5)
-    knn_query_group_t<unsigned>(b, x, y, z, alive, k, bound, L);
+    knn_query_group_t<unsigned, SLOTS>(b, x, y, z, alive, k, bound, L);
   else
-    knn_query_group_t<unsigned long long>(b, x, y, z, alive, k, bound, L);
+    knn_query_group_t<unsigned long long, SLOTS>(b, x, y, z, alive, k, bound, L);
 }
 
 // host: device view of a built index (nn_bvh.hip)

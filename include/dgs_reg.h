@@ -136,7 +136,9 @@ typedef struct dgs_params {
                                               setMaxCorrespondenceDistance (DGS_METHOD_ICP, registrations.cpp:62) */
   double gicp_rotation_epsilon;            /* upstream default 2e-3 */
   double gicp_lm_init_lambda_factor;       /* upstream default 1e-9 */
-  int32_t gicp_correspondence_randomness;  /* setCorrespondenceRandomness (k), default 20 (registrations.cpp:34) */
+  int32_t gicp_correspondence_randomness;  /* setCorrespondenceRandomness (k), default 20 (registrations.cpp:34).  Range 1..64 for FAST_GICP,
+                                            * FAST_VGICP and GICP_HIP / GICP_OMP_HIP: k <= 32 runs the kernels of every earlier release, 33..64
+                                            * their wide forms; k > 64 is DGS_ERR_UNSUPPORTED at the first covariance pass */
   int32_t gicp_regularization;             /* default DGS_GICP_REG_PLANE */
   int32_t gicp_optimizer;                  /* default DGS_GICP_OPT_LEVENBERG_MARQUARDT */
   int32_t gicp_lm_max_iterations;          /* default 10 */
@@ -226,7 +228,8 @@ int dgs_set_icp_options(dgs_handle* h, const dgs_icp_options* options);
 /* Settings of a GICP_HIP handle, taking effect at the next align; DGS_ERR_UNSUPPORTED on a handle of another method. */
 int dgs_set_pcl_gicp_options(dgs_handle* h, const dgs_pcl_gicp_options* options);
 /* setCorrespondenceRandomness on a live GICP_HIP handle (dgs_params.gicp_correspondence_randomness): the covariances of the target and
- * of every source are recomputed for the new k at the next align.  DGS_ERR_UNSUPPORTED on a handle of another method. */
+ * of every source are recomputed for the new k at the next align.  DGS_ERR_UNSUPPORTED on a handle of another method, and for k > 64
+ * (the handle keeps its k). */
 int dgs_pcl_gicp_set_correspondence_randomness(dgs_handle* h, int32_t k);
 
 /* Batch-independent results on request.  Off by default; while it is on, every dgs_result field of a pair, and every
