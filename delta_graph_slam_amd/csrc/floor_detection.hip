@@ -5,7 +5,7 @@
 // MI355X design
 //   * fd_tilt_clip_kernel transforms a point and takes both clip decisions in one pass; the kept points are compacted in order by the
 //     shared stable compaction (compact.h: pf_count_kernel, pf_scan_kernel, pf_scatter_kernel).
-//   * The normal pass is the prefilter's: an index of the detector's own over the clipped cloud, gicp.hip's exact k-NN lists and
+//   * The normal pass is the prefilter's: an index of the detector's own over the clipped cloud, knn_lists.hip's exact k-NN lists and
 //     pf_normal_kernel, unchanged.  fd_normal_flag_kernel applies the floor rule to the normals it wrote.
 //   * The RANSAC is sac.h's, shared with the line extraction, over FdModel (the plane's sample test, four coefficients and inlier test).
 //     The draw stream does not depend on any count, so the host builds the draw list from n alone and uploads it;

@@ -3,7 +3,7 @@
 // fast_gicp::FastGICP::calculate_covariances sums a point's k neighbours one after another, in the order its kd-tree returns them
 // (ascending squared distance), and hands the 3 x 3 result to Eigen::JacobiSVD.  On a rank-deficient neighbourhood (duplicated points,
 // points on a line) JacobiSVD's 2 eps maxDiag rotation threshold turns the last bit of that matrix into another basis of the null
-// space, so the regularised covariance is upstream's only if the sums are upstream's bit for bit.  gicp_cov_from_knn_kernel (gicp.hip)
+// space, so the regularised covariance is upstream's only if the sums are upstream's bit for bit.  gicp_cov_from_knn_kernel (gicp_cov.hip)
 // reduces over 8 lanes in a tree; this kernel restates the sequence of the CPU restatement of calculate_covariances (the test suite's
 // checker) operation for operation, every one individually rounded: the whole file is compiled without contraction (Makefile).
 //

@@ -312,7 +312,7 @@ struct dgs_handle {
   bool ndt_fixed_slices = false;     // DGS_NDT_FIXED_SLICES=1: upstream order, item-compacted kernel: a pair's slices are a function of its own size (ndt_strict.h strict_slices_of)
                                       // from the Gauss-Jordan direction and verified beside the next launch (NdtPair::spec_s)
   bool ndt_fixed_slices_initial = false;   // ndt_fixed_slices as dgs_create left it
-  bool batch_independent = false;     // dgs_set_batch_independent: FAST_GICP / FAST_VGICP sum a pair over slices that follow its own size (gicp.hip, "fixed slices"), NDT order 1
+  bool batch_independent = false;     // dgs_set_batch_independent: FAST_GICP / FAST_VGICP sum a pair over slices that follow its own size (gicp.hip, the FIXED round kernels), NDT order 1
                                       // takes ndt_fixed_slices with it, and every fitness goes through the edge scorer (fitness_batch.hip): a pair's record does not depend on its batch
   bool ndt_deal_by_cost = true;       // DGS_NDT_DEAL_BY_COST=0: upstream order, item-compacted kernel: a launch's workgroups dealt to the pairs in index order (deal_workgroup)
   bool ndt_reuse_trials = true;       // DGS_NDT_REUSE_TRIALS=0: upstream orders: a repeated More-Thuente trial pose is evaluated again and its result replaced by the cached one
@@ -585,13 +585,14 @@ inline int nn_grid_search(dgs_handle*, NnGrid&, const Bvh&, const float4*, int64
 // gicp.hip
 int vgicp_build_map(dgs_handle* h);  // vgicp_voxel.hip: needs the target covariances
 int vgicp_voxels(dgs_handle* h, int64_t capacity, int32_t* coord3, int32_t* counts, double* mean3, double* cov9, int64_t* n_voxels);
-int gicp_ensure_target_covariance(dgs_handle* h);
 int gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);
 int gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* const* srcs, const float* guesses16, dgs_result* out);   // pair i against tgts[i]
 const float* gicp_final_transforms(dgs_handle* h, size_t* stride_bytes);
-int gicp_covariances(dgs_handle* h, int which, double* host_out6, int64_t n);
 int gicp_probe(dgs_handle* h, const double* T16_rowmajor, int error_only, double* err, double* H36, double* b6);
+// gicp_cov.hip: FAST_GICP / FAST_VGICP covariances of a cloud under the handle's (k, regularisation), cached on the cloud
+int ensure_covariance(dgs_handle* h, CloudState& c);
+int gicp_covariances(dgs_handle* h, int which, double* host_out6, int64_t n);
 // gicp_cov_ordered.hip: covariances in upstream's operation order (dgs_params.gicp_cov_jacobi_svd = DGS_GICP_COV_UPSTREAM_ORDER) from knn_lists' sets
 struct BvhView;
 int gicp_cov_upstream_order(dgs_handle* h, const BvhView& v, CloudState& c, int k, int regularization, const int* nbr, int stride);
@@ -601,9 +602,10 @@ int icp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* 
 const float* icp_final_transforms(dgs_handle* h, size_t* stride_bytes);
 int icp_trajectory(dgs_handle* h, int pair, float* T16s, double* mse, int32_t* n_corr, int capacity, int* len);
 void icp_release(dgs_handle* h);
-// gicp.hip: exact k-NN lists of a cloud in itself -> h->knn_nbr
+// knn_lists.hip: exact k-NN lists of a cloud in itself -> h->knn_nbr
 // out: default h->knn_nbr; stride: where the table's stride goes (kKnnMax or, k > 32, kKnnMaxWide) -- without it k <= 32 and the stride is kKnnMax
 int knn_lists(dgs_handle* h, CloudState& c, int k, DevBuf<int>* out = nullptr, int* stride = nullptr);
+bool knn_uses_leaf_search(const dgs_handle* h, int k);   // whether knn_lists serves k with the wave-per-leaf search (the DGS_KNN_STATS printout asks)
 // the two widths of the k-NN lists (nn_group.h): slots per lane of the 8-lane group; the table's stride, which is the largest k of that width
 constexpr int kKnnSlots = 4, kKnnMax = kKnnSlots * 8;               // k <= 32: every consumer of the lists
 constexpr int kKnnSlotsWide = 8, kKnnMaxWide = kKnnSlotsWide * 8;   // 32 < k <= 64: the GICP family's covariances

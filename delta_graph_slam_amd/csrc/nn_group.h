@@ -1,4 +1,4 @@
-// Cooperative exact nearest-neighbour traversal shared by nn_bvh.hip (fitness / nearestKSearch) and gicp.hip
+// Cooperative exact nearest-neighbour traversal shared by nn_bvh.hip (fitness / nearestKSearch), gicp.hip and knn_lists.hip
 // (correspondences, k-NN covariances).  See nn_bvh.hip for the data structure.
 #pragma once
 #include <cfloat>

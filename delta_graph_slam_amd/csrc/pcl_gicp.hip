@@ -3,7 +3,7 @@
 // test-side restatement tests/pcl_gicp_reference.py is the specification this file reproduces.
 //
 // MI355X design
-//   * Covariances (computeCovariances): gicp.hip's k-NN lists (knn_lists), then pg_cov_kernel, one lane per point: the list sorted by
+//   * Covariances (computeCovariances): knn_lists.hip's k-NN lists (knn_lists), then pg_cov_kernel, one lane per point: the list sorted by
 //     index (a register sorting network: the sums do not depend on which index ordered the search), raw moments in double from float
 //     products, JacobiSVD (jacobi_svd3_d) and U diag(1, 1, eps) U^T.  Kept per cloud in CloudState::pcov, keyed by (k, eps).
 //   * One launch per round for the whole batch (pg_round_kernel), every pair in its own phase.  A pair owns a FIXED number of

@@ -10,7 +10,7 @@
 //     workgroup), one workgroup scanning the counts, and a scatter pass (ballot prefix inside the wave, the wave totals of the
 //     workgroup, the scanned workgroup offset).  The whole 16-byte point is copied, pad lane included.
 //   * Down-sampling is dgs_voxel_grid_filter's / dgs_approx_voxel_grid_filter's code path, unchanged (ndt_voxel.hip).
-//   * The outlier passes and the normal pass run on gicp.hip's exact k-NN lists (knn_lists, k <= 32) over an index of the
+//   * The outlier passes and the normal pass run on knn_lists.hip's exact k-NN lists (knn_lists, k <= 32) over an index of the
 //     prefilter's own (PfScratch::cloud).  A list is the k smallest (float FLANN distance, index) keys, ties to the lower index; each
 //     lane sorts its list (bitonic network in registers) before any order-dependent sum.
 //   * StatisticalOutlierRemoval's mean and standard deviation are a fixed-order reduction in one workgroup; the threshold is

@@ -83,7 +83,7 @@ int vgicp_build_map(dgs_handle* h) {
   h->vmap_valid = false;
   h->vmap_voxels = 0;
   if (n == 0) return DGS_OK;
-  int rc = gicp_ensure_target_covariance(h);
+  int rc = ensure_covariance(h, *h->tgt);
   if (rc) return rc;
   int slot = prof_begin(h, DGS_K_NDT_VOXEL_BUILD);
   float hmm[6];

@@ -10,7 +10,7 @@ POSE_TOL = (1e-6, 1e-7)   # metres, radians: the project's batch-against-single 
 FIT_RTOL = 1e-9
 
 # nn_group.h / nn_bvh.hip: an index leaf holds kLeaf = 8 points and a node has kFan = 8 children, so the tree gains a level past 64, 512 and
-# 4,096 points.  gicp.hip, correspond kernels: a wave walks 8 adjacent source points per round (8 lanes a point), a workgroup
+# 4,096 points.  gicp.hip, gicp_correspond_kernel: a wave walks 8 adjacent source points per round (8 lanes a point), a workgroup
 # kBlock / 8 = 32, and a wave's stretch is 8 x run points with run = ceil(n / (32 x workgroups of the pair)).
 K_LEAF, K_FAN, ROUND_POINTS, BLOCK_QUERIES = 8, 8, 8, 32
 
