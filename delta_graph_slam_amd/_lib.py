@@ -211,6 +211,7 @@ SYMBOLS = [
     "dgs_floor_detection_get_trace", "dgs_floor_detection_get_clipped", "dgs_floor_detection_draws", "dgs_floor_detection_walk",
     "dgs_calc_fitness_score_batch_clouds", "dgs_cloud_build_indices", "dgs_fitness_batch_get_counts",
     "dgs_building_cloud_params_init", "dgs_building_cloud_generate", "dgs_building_cloud_get", "dgs_building_cloud_get_counts",
+    "dgs_cloud_assign_batch", "dgs_cloud_assign_get_counts", "dgs_cloud_read", "dgs_calc_inlier_fraction_batch_clouds",
 ]
 
 _libs = {}
@@ -250,6 +251,10 @@ def load(path=None):
                                              C.c_int64, P(C.c_int64)]
     lib.dgs_calc_fitness_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_double, P(C.c_double)]
     lib.dgs_calc_fitness_score_batch_clouds.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    lib.dgs_calc_inlier_fraction_batch_clouds.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    lib.dgs_cloud_assign_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+    lib.dgs_cloud_assign_get_counts.argtypes = [C.c_void_p, C.c_void_p]
+    lib.dgs_cloud_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_cloud_build_indices.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.dgs_fitness_batch_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     lib.dgs_voxel_grid_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]

@@ -7,6 +7,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
+#include <vector>
 
 #include "handle.h"
 
@@ -272,6 +274,14 @@ __global__ __launch_bounds__(kBlock) void deal_probe_cost_kernel(const int* __re
   if ((threadIdx.x & 63) == 0) out[blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)] = ok ? make_int4(pair, slice, blocks_per_pair, n_active) : make_int4(-1, -1, -1, n_active);
 }
 }  // namespace dgs
+
+void dgs::cloud_detach_users(dgs_cloud* c) {
+  for (dgs_handle* h : c->users) {  // handles still pointing here fall back to "no input set"
+    if (h->tgt_cloud == c) { h->tgt_cloud = nullptr; h->tgt = &h->own_target; h->nt = 0; h->have_target = false; h->tgt_grid.valid = false; }
+    if (h->src_cloud == c) { h->src_cloud = nullptr; h->src = &h->own_source; h->ns = 0; h->have_source = false; }
+  }
+  c->users.clear();
+}
 
 static thread_local std::string g_create_error;  // dgs_last_error(NULL): why the last dgs_create on this thread failed
 void dgs::set_handleless_error(const char* why) { g_create_error = why; }
@@ -545,6 +555,7 @@ void dgs_destroy(dgs_handle* h) {
   floor_detection_release(h);
   fitness_batch_release(h);
   building_cloud_release(h);
+  voxel_batch_release(h);
   h->gitems.release(); h->gtargets.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
   h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();
@@ -648,10 +659,7 @@ int dgs_cloud_create(dgs_handle* h, const float* xyz16, int64_t n, int32_t on_de
 
 void dgs_cloud_destroy(dgs_cloud* c) {
   if (!c) return;
-  for (dgs_handle* h : c->users) {  // handles still pointing here fall back to "no input set"
-    if (h->tgt_cloud == c) { h->tgt_cloud = nullptr; h->tgt = &h->own_target; h->nt = 0; h->have_target = false; h->tgt_grid.valid = false; }
-    if (h->src_cloud == c) { h->src_cloud = nullptr; h->src = &h->own_source; h->ns = 0; h->have_source = false; }
-  }
+  cloud_detach_users(c);
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   c->st.release();
@@ -1308,6 +1316,67 @@ int dgs_cloud_build_indices(dgs_handle* h, int32_t n, dgs_cloud* const* clouds) 
   if (rc != DGS_OK) return rc;
   if (set_device(h)) return DGS_ERR_HIP;
   return fitness_batch_build_indices(h, n, clouds);
+}
+
+int dgs_calc_inlier_fraction_batch_clouds(dgs_handle* h, int32_t n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16,
+                                          double max_sq_dist, double* fractions, int64_t* inliers) {
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (n_edges < 0 || (n_edges > 0 && (!cloud1s || !cloud2s || (!fractions && !inliers))) || std::isnan(max_sq_dist)) {
+    h->err = "dgs_calc_inlier_fraction_batch_clouds: bad arguments";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  int rc = check_clouds(h, n_edges, cloud1s, "cloud1s");
+  if (rc == DGS_OK) rc = check_clouds(h, n_edges, cloud2s, "cloud2s");
+  if (rc != DGS_OK) return rc;
+  if (set_device(h)) return DGS_ERR_HIP;
+  return inlier_batch_clouds(h, n_edges, cloud1s, cloud2s, relposes16, max_sq_dist, fractions, inliers);
+}
+
+// ---- resident clouds refilled in place, a batch at a time (voxel_batch.hip) ------------------------------------------------------
+int dgs_cloud_assign_batch(dgs_handle* h, int32_t n, const float* const* inputs_xyz16, const int64_t* sizes, int32_t on_device, int32_t filter, float leaf_size,
+                           dgs_cloud* const* clouds, int64_t* out_sizes) {
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (n < 0 || (n > 0 && (!inputs_xyz16 || !sizes || !clouds || !out_sizes)) || filter < 0 || filter > 2 || (filter != 0 && !(leaf_size > 0))) {
+    h->err = "dgs_cloud_assign_batch: bad arguments";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  for (int32_t i = 0; i < n; i++)
+    if (sizes[i] < 0 || sizes[i] > INT32_MAX || (sizes[i] > 0 && !inputs_xyz16[i])) {
+      h->err = "dgs_cloud_assign_batch: bad size or NULL input at " + std::to_string(i);
+      return DGS_ERR_INVALID_ARGUMENT;
+    }
+  const int rc = check_clouds(h, n, clouds, "clouds");
+  if (rc != DGS_OK) return rc;
+  std::vector<dgs_cloud*> sorted(clouds, clouds + n);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+    h->err = "dgs_cloud_assign_batch: the same cloud is listed twice";
+    return DGS_ERR_INVALID_ARGUMENT;
+  }
+  std::fill(h->vb.counts8, h->vb.counts8 + 8, 0);
+  if (n == 0) return DGS_OK;
+  if (set_device(h)) return DGS_ERR_HIP;
+  return cloud_assign_batch(h, n, inputs_xyz16, sizes, on_device, filter, leaf_size, clouds, out_sizes);
+}
+
+int dgs_cloud_assign_get_counts(dgs_handle* h, int64_t* counts8) {
+  if (!h || !counts8) return DGS_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 8; k++) counts8[k] = h->vb.counts8[k];
+  return DGS_OK;
+}
+
+int dgs_cloud_read(dgs_handle* h, const dgs_cloud* c, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n_out) {
+  if (!h || !c || !n_out || capacity < 0 || (capacity > 0 && !out_xyz16) || c->device != h->device) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  *n_out = c->st.n;
+  if (c->st.n > capacity) { h->err = "output buffer too small for the cloud"; return DGS_ERR_INVALID_ARGUMENT; }
+  if (c->st.n == 0) return DGS_OK;
+  if (set_device(h)) return DGS_ERR_HIP;
+  DGS_HIP_TRY(h, hipMemcpyAsync(out_xyz16, c->st.pts.ptr, (size_t)c->st.n * sizeof(float4), out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return DGS_OK;
 }
 
 int dgs_fitness_batch_get_counts(dgs_handle* h, int64_t* counts8) {

@@ -108,6 +108,58 @@ __global__ __launch_bounds__(kBlock) void fb_walk_kernel(const int* __restrict__
   if (threadIdx.x < 2) rows[(size_t)blockIdx.x * 2 + threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
 }
 
+// The same walk counting, per row, the points of cloud2 whose squared NN distance is strictly below `inlier_sq` (the nearestKSearch loop
+// of publish_scan_matching_status; nn_fitness_kernel's `best < inlier_sq`).  A kernel of its own: fb_walk_kernel compiles to what it did.
+// Rows hold {inliers, 0}: counts are integers, so any order of the sums gives the same total.
+__global__ __launch_bounds__(kBlock) void fb_inlier_kernel(const int* __restrict__ row0s, const FbEdge* __restrict__ edges, const int n_edges,
+                                                           const float inlier_sq, double* __restrict__ rows) {
+  int lo = 0, hi = n_edges;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (row0s[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+  }
+  const FbEdge* __restrict__ E = edges + __builtin_amdgcn_readfirstlane(lo);
+  const BvhView b = E->b;
+  const float4* __restrict__ src = E->src;
+  const int n = E->n, n_rows = E->rows, slice = (int)blockIdx.x - E->row0;
+  const float t00 = E->T[0], t10 = E->T[1], t20 = E->T[2], t01 = E->T[4], t11 = E->T[5], t21 = E->T[6], t02 = E->T[8], t12 = E->T[9], t22 = E->T[10],
+              t03 = E->T[12], t13 = E->T[13], t23 = E->T[14];
+  double inl = 0.0;
+  constexpr int QPB = kBlock / 8;
+  const int sub = threadIdx.x & 7;
+  const int run = (n + n_rows * QPB - 1) / (n_rows * QPB);
+  const int first = (slice * (kBlock / kWave) + (threadIdx.x >> 6)) * (8 * run) + ((threadIdx.x & 63) >> 3);
+  float px = 0.f, py = 0.f, pz = 0.f, prev_best = INFINITY;
+  bool prev_found = false;
+  for (int r = 0; r < run; r++) {
+    const int i = first + r * 8;
+    const bool alive = i < n;
+    const float4 p = alive ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float x = affine_row_rn(t00, t01, t02, t03, p.x, p.y, p.z);
+    const float y = affine_row_rn(t10, t11, t12, t13, p.x, p.y, p.z);
+    const float z = affine_row_rn(t20, t21, t22, t23, p.x, p.y, p.z);
+    float best;
+    int bi;
+    nn_query_group<false>(b, x, y, z, alive, nn_warm_bound_round(prev_best, prev_found, x, y, z, px, py, pz), best, bi);
+    prev_found = alive && bi != 0x7FFFFFFF;
+    prev_best = best;
+    px = x; py = y; pz = z;
+    if (alive && sub == 0) {
+      if (bi == 0x7FFFFFFF) best = INFINITY;  // nothing found (non-finite query)
+      if (best < inlier_sq) inl += 1.0;
+    }
+  }
+  __shared__ double sm[kBlock / kWave];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  inl = wave_sum(inl);
+  if (lane == 0) sm[wave] = inl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    rows[(size_t)blockIdx.x * 2] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+    rows[(size_t)blockIdx.x * 2 + 1] = 0.0;
+  }
+}
+
 // one wave per edge: lane l sums the edge's rows l, l + 64, ... in order, then the lanes are summed in a fixed order
 __global__ __launch_bounds__(kWave) void fb_close_kernel(const int* __restrict__ row0s, const double* __restrict__ rows, const int n_edges,
                                                          double* __restrict__ out) {
@@ -363,9 +415,10 @@ int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, 
 
 // The walk and the closing launch over edges given as (index over cloud1, cloud2's points, pose): what fitness_batch_clouds runs once its
 // clouds' indices stand, and what a batch-independent handle scores its own target's candidates with (fitness_target_edges).
-int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double max_range, double* scores, int64_t* used) {
+// inlier false: fb_walk_kernel under max_range = `bound`, totals {sum, used}; true: fb_inlier_kernel under the strict threshold `bound`,
+// totals {inliers, 0}.  *totals: 2 doubles per edge in the pinned block (zeros for an edge without rows), valid until the next call.
+static int fb_run_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, bool inlier, double bound, const double** totals) {
   FbScratch& F = h->fb;
-  if (n_edges == 0) return DGS_OK;
   F.counts8[2] = n_edges;
   // one pinned block: [row prefix | edge table] up, [sum, used per edge] down
   const size_t pre_bytes = (((size_t)n_edges + 1) * sizeof(int) + 127) & ~(size_t)127;
@@ -400,9 +453,10 @@ int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double m
     DGS_HIP_TRY(h, hipMemcpyAsync(F.tab.ptr, F.stage, up_bytes, hipMemcpyHostToDevice, st));
     const int* d_row0s = reinterpret_cast<const int*>(F.tab.ptr);
     const FbEdge* d_edges = reinterpret_cast<const FbEdge*>(F.tab.ptr + pre_bytes);
-    // PCL's comparison is float(sq_dist) <= double(max_range); clamp so DBL_MAX keeps every finite distance
-    const float mr = (max_range >= (double)FLT_MAX) ? FLT_MAX : (float)max_range;
-    hipLaunchKernelGGL(fb_walk_kernel, dim3((unsigned)total_rows), dim3(kBlock), 0, st, d_row0s, d_edges, n_edges, mr, F.rows.ptr);
+    // PCL's comparison is float(sq_dist) <= double(max_range); clamp so DBL_MAX keeps every finite distance (nn_fitness_enqueue clamps the
+    // inlier threshold the same way)
+    const float mr = (bound >= (double)FLT_MAX) ? FLT_MAX : (float)bound;
+    hipLaunchKernelGGL(inlier ? fb_inlier_kernel : fb_walk_kernel, dim3((unsigned)total_rows), dim3(kBlock), 0, st, d_row0s, d_edges, n_edges, mr, F.rows.ptr);
     hipLaunchKernelGGL(fb_close_kernel, dim3(n_edges), dim3(kWave), 0, st, d_row0s, F.rows.ptr, n_edges, d_out);
     F.counts8[0] += 2;
     DGS_HIP_TRY(h, hipMemcpyAsync(down, d_out, down_bytes, hipMemcpyDeviceToHost, st));
@@ -411,10 +465,43 @@ int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double m
     F.bstage_pending = false;   // the build's upload went first on the same stream
     DGS_HIP_TRY(h, hipGetLastError());
   }
+  for (int e = 0; e < n_edges; e++)
+    if (!edges[e].rows) down[e * 2] = down[e * 2 + 1] = 0.0;
+  *totals = down;
+  return DGS_OK;
+}
+
+int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double max_range, double* scores, int64_t* used) {
+  if (n_edges == 0) return DGS_OK;
+  const double* down = nullptr;
+  const int rc = fb_run_edges(h, n_edges, in, false, max_range, &down);
+  if (rc != DGS_OK) return rc;
   for (int e = 0; e < n_edges; e++) {
-    const double sum = edges[e].rows ? down[e * 2] : 0.0, cnt = edges[e].rows ? down[e * 2 + 1] : 0.0;
+    const double sum = down[e * 2], cnt = down[e * 2 + 1];
     scores[e] = cnt > 0.0 ? sum / cnt : DBL_MAX;
     if (used) used[e] = (int64_t)cnt;
+  }
+  return DGS_OK;
+}
+
+// dgs_calc_inlier_fraction_batch_clouds: missing indices by the batched build, one walk launch over all edges, one closing launch, one wait
+int inlier_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_sq_dist,
+                        double* fractions, int64_t* inliers) {
+  FbScratch& F = h->fb;
+  std::fill(F.counts8, F.counts8 + 8, 0);
+  if (n_edges == 0) return DGS_OK;
+  int rc = fitness_batch_build_indices(h, n_edges, cloud1s, false);
+  if (rc != DGS_OK) return rc;
+  std::vector<FbEdgeIn> in((size_t)n_edges);
+  for (int e = 0; e < n_edges; e++)
+    in[e] = FbEdgeIn{&cloud1s[e]->st.bvh, cloud2s[e]->st.pts.ptr, cloud1s[e]->st.n, cloud2s[e]->st.n, relposes16 ? relposes16 + (size_t)e * 16 : kIdentity16};
+  const double* down = nullptr;
+  rc = fb_run_edges(h, n_edges, in.data(), true, max_sq_dist, &down);
+  if (rc != DGS_OK) return rc;
+  for (int e = 0; e < n_edges; e++) {
+    const bool empty = in[e].n1 == 0 || in[e].n2 == 0;
+    if (inliers) inliers[e] = empty ? 0 : (int64_t)down[e * 2];
+    if (fractions) fractions[e] = empty ? (double)NAN : down[e * 2] / (double)in[e].n2;   // dgs_get_inlier_fraction's division
   }
   return DGS_OK;
 }

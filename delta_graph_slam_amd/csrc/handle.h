@@ -269,6 +269,19 @@ struct FbScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launches, host waits, edges, indices built, partial rows
 };
 
+// dgs_cloud_assign_batch (voxel_batch.hip): the staged inputs, one record per cloud, the keys, values and runs of all clouds back to
+// back; everything above is left untouched.
+struct VbSeg;     // voxel_batch.hip
+struct VbScratch {
+  DevBuf<float4> in;                   // host inputs, all clouds back to back
+  DevBuf<VbSeg> segs;
+  DevBuf<float> mm;                    // per cloud 64 partial boxes, then the boxes
+  DevBuf<unsigned long long> keys, keys_alt, run_keys;   // (cloud number << 32) | cell index
+  DevBuf<uint32_t> vals, vals_alt;     // index of the point in its own cloud
+  DevBuf<int> run_counts, run_offsets, scalars, bounds;  // scalars[0] = runs; bounds: first run and end of the emitted runs per cloud
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // of the last call: launches, host waits, clouds
+};
+
 // interpolate / buildPointCloud / getCloud over many lines (building_cloud.hip): the table of sample positions, kept across calls, and
 // scratch of its own; everything above is left untouched.
 struct BcScratch {
@@ -517,6 +530,9 @@ struct dgs_handle {
   // ---- building clouds (building_cloud.hip): own buffers and the table of sample positions; everything above is left untouched
   dgs::BcScratch bcl;
 
+  // ---- batched down-sampling into resident clouds (voxel_batch.hip): own buffers; everything above is left untouched
+  dgs::VbScratch vb;
+
   dgs::Profiler prof;
 };
 
@@ -643,10 +659,19 @@ struct FbEdgeIn {
 };
 int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double max_range, double* scores, int64_t* used);
 // the same scorer for sources of the handle's current target (batch-independent fitness): builds the target's index when it has none
+// dgs_calc_inlier_fraction_batch_clouds: per edge the points of relpose * cloud2 whose exact 1-NN squared distance in cloud1 is < max_sq_dist
+int inlier_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_sq_dist,
+                        double* fractions, int64_t* inliers);
 int fitness_target_edges(dgs_handle* h, int n, const float4* const* srcs, const int64_t* sizes, const float* T16s, size_t T_stride_floats, double max_range, double* scores);
 void fitness_batch_release(dgs_handle* h);
 // building_cloud.hip
 void building_cloud_release(dgs_handle* h);
+// voxel_batch.hip: inputs filtered (0 NONE, 1 VOXELGRID, 2 APPROX_VOXELGRID) into resident clouds; the caller has checked the arguments
+int cloud_assign_batch(dgs_handle* h, int n, const float* const* inputs, const int64_t* sizes, int on_device, int filter, float leaf, dgs_cloud* const* clouds,
+                       int64_t* out_sizes);
+void voxel_batch_release(dgs_handle* h);
+// dgs_api.hip: the handles that borrow `c` as target or source fall back to "no input set" (what dgs_cloud_destroy does first)
+void cloud_detach_users(dgs_cloud* c);
 // pcl_gicp.hip
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);

@@ -124,6 +124,13 @@ class DeviceCloud:
     def __len__(self):
         return self.n
 
+    def read(self, registration: "Registration") -> np.ndarray:
+        """The cloud's points as it holds them now ([n, 4] float32, dgs_cloud_read)."""
+        out = np.empty((max(self.n, 1), 4), dtype=np.float32)
+        m = C.c_int64(0)
+        registration._check(self._lib.dgs_cloud_read(registration._h, self._c, out.ctypes.data_as(C.c_void_p), self.n, 0, C.byref(m)))
+        return out[:m.value].copy()
+
     def close(self):
         if getattr(self, "_c", None) is not None and self._c.value:
             self._lib.dgs_cloud_destroy(self._c)
@@ -377,6 +384,80 @@ class Registration:
             for c in temps:
                 c.close()
         return (scores, used) if return_used else scores
+
+    def calc_inlier_fraction_batch(self, cloud1s, cloud2s, relposes=None, max_sq_dist: float = 0.25, return_counts: bool = False):
+        """getInlierFraction for every edge (cloud1s[e] indexed, cloud2s[e] moved by relposes[e]) in one call
+        (dgs_calc_inlier_fraction_batch_clouds): the count of an edge is getInlierFraction's of the same pair exactly.  -> float64 [E]
+        (NaN where a cloud is empty), and int64 [E] with return_counts."""
+        cloud1s, cloud2s = list(cloud1s), list(cloud2s)
+        n = len(cloud1s)
+        if len(cloud2s) != n:
+            raise ValueError("cloud1s and cloud2s differ in length")
+        arr, objs, temps = self._cloud_array(cloud1s + cloud2s)
+        a1 = (C.c_void_p * max(n, 1))(*arr[:n])
+        a2 = (C.c_void_p * max(n, 1))(*arr[n:2 * n])
+        t = None
+        if relposes is not None:
+            if len(relposes) != n:
+                raise ValueError("relposes and the clouds differ in length")
+            t = np.ascontiguousarray(np.stack([_col16(r) for r in relposes]) if n else np.zeros((0, 16), np.float32), dtype=np.float32)
+        fractions = np.empty(n, dtype=np.float64)
+        counts = np.zeros(n, dtype=np.int64)
+        try:
+            self._check(self._lib.dgs_calc_inlier_fraction_batch_clouds(self._h, n, C.cast(a1, C.c_void_p), C.cast(a2, C.c_void_p),
+                                                                        None if t is None else t.ctypes.data_as(C.c_void_p), float(max_sq_dist),
+                                                                        fractions.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+        finally:
+            for c in temps:
+                c.close()
+        return (fractions, counts) if return_counts else fractions
+
+    _FILTERS = {"NONE": 0, "VOXELGRID": 1, "APPROX_VOXELGRID": 2}
+
+    def assign_batch(self, clouds, inputs, downsample_method: str = "NONE", leaf_size: float = 0.1) -> np.ndarray:
+        """dgs_cloud_assign_batch: DeviceCloud clouds[i] is refilled with inputs[i] (numpy arrays, or device tensors) passed through
+        downsample_method -- one chain of launches and two host waits for the whole batch under VOXELGRID, each cloud receiving the
+        bits of voxel_grid_filter(inputs[i], leaf_size).  Index and covariances of the clouds are dropped, registrations that borrowed
+        one lose it.  -> the new sizes, int64 [n]."""
+        clouds, inputs = list(clouds), list(inputs)
+        n = len(clouds)
+        if len(inputs) != n:
+            raise ValueError("clouds and inputs differ in length")
+        if not all(isinstance(c, DeviceCloud) for c in clouds):
+            raise TypeError("assign_batch refills DeviceClouds")
+        if downsample_method not in self._FILTERS:
+            raise ValueError(f"downsample_method {downsample_method!r} is none of {sorted(self._FILTERS)}")
+        ptrs = (C.c_void_p * max(n, 1))()
+        sizes = (C.c_int64 * max(n, 1))()
+        keep, devs, cuda_devs = [], set(), set()
+        for i, a in enumerate(inputs):
+            ptr, m, dev, k = _cloud_ptr(a, sync=False)
+            ptrs[i] = ptr.value if ptr.value else 0
+            sizes[i] = m
+            keep.append(k)
+            if m:
+                devs.add(dev)
+            if dev:
+                cuda_devs.add(k.device)
+        if len(devs) > 1:
+            raise ValueError("inputs must be all host arrays or all device tensors")
+        for d in cuda_devs:   # one ordering point for the whole batch (the device-pointer contract of include/dgs_reg.h)
+            torch.cuda.current_stream(d).synchronize()
+        arr = (C.c_void_p * max(n, 1))(*[c._c.value for c in clouds])
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        rc = self._lib.dgs_cloud_assign_batch(self._h, n, C.cast(ptrs, C.c_void_p), C.cast(sizes, C.c_void_p), devs.pop() if devs else 0,
+                                              self._FILTERS[downsample_method], float(leaf_size), C.cast(arr, C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        if rc != 5:   # DGS_ERR_GRID_TOO_LARGE leaves every cloud as it was; anything else that ran has resized them
+            for c, m in zip(clouds, out):
+                c.n = int(self._lib.dgs_cloud_size(c._c))
+        self._check(rc)
+        return out[:n].copy()
+
+    def cloud_assign_counts(self) -> dict:
+        """Of the last assign_batch: kernel launches, host waits, clouds."""
+        c = (C.c_int64 * 8)()
+        self._check(self._lib.dgs_cloud_assign_get_counts(self._h, C.cast(c, C.c_void_p)))
+        return {"launches": c[0], "host_waits": c[1], "clouds": c[2]}
 
     def build_indices(self, clouds):
         """dgs_cloud_build_indices: the Hilbert-ordered NN index of every listed DeviceCloud that has none, in one batched build."""

@@ -367,6 +367,40 @@ int dgs_cloud_build_indices(dgs_handle* h, int32_t n, dgs_cloud* const* clouds);
  * builds this handle made by any other path (registration targets, the prefilter, dgs_calc_fitness_score ...); the rest 0. */
 int dgs_fitness_batch_get_counts(dgs_handle* h, int64_t* counts8);
 
+/* The inlier count of publish_scan_matching_status (apps/scan_matching_odometry_nodelet.cpp:321-332) over a batch of edges between
+ * device-resident clouds, with dgs_calc_fitness_score_batch_clouds' arguments: cloud1 carries the index, cloud2 is moved by the edge's
+ * relative pose.  inliers[e] (nullable) = the points of relpose e * cloud2s[e] whose exact 1-NN squared distance in cloud1s[e] is
+ * < max_sq_dist (strict, compared in float as dgs_get_inlier_fraction compares it); fractions[e] (nullable) = inliers[e] / size of
+ * cloud2s[e].  The count equals dgs_get_inlier_fraction's for the same pair exactly.  An edge with an empty cloud1 or cloud2: fraction
+ * NaN, count 0, the other edges run.  Missing indices by the batched build, one walk launch over all edges, one closing launch, one
+ * download, one host wait; dgs_fitness_batch_get_counts answers for this call too.  n_edges == 0: DGS_OK without a launch.  A NULL cloud,
+ * a cloud of another device or a NaN threshold: DGS_ERR_INVALID_ARGUMENT.  Additions only: DGS_ABI_VERSION is unchanged. */
+int dgs_calc_inlier_fraction_batch_clouds(dgs_handle* h, int32_t n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s,
+                                          const float* relposes16, double max_sq_dist, double* fractions, int64_t* inliers);
+
+/* Refills n resident clouds in one call: clouds[i] (it exists, possibly empty) afterwards holds input i (sizes[i] points; host arrays, or
+ * device arrays with on_device) passed through `filter`: 0 NONE (a copy), 1 VOXELGRID, 2 APPROX_VOXELGRID, both with leaf_size;
+ * out_sizes[i] receives its new size.  The cloud's index, walk index and both covariance caches are invalidated; its buffer is kept when
+ * it holds sizes[i] points (it is grown to the INPUT size, so a stream of similar scans stops allocating after its first frames); handles
+ * that use the cloud as target or source are detached first, as dgs_cloud_destroy detaches them.  An input may not be a listed cloud's
+ * own buffer.
+ * VOXELGRID: cloud i receives, bit for bit and in the same order, what dgs_voxel_grid_filter(input i, leaf_size) returns -- a grid from
+ * the cloud's own bounding box, float sums in point-index order inside a cell, cells in ascending index, non-finite points dropped --
+ * from ONE chain of launches over all clouds (boxes, keys, one sort of (cloud, cell) keys, run lengths, centroids) and two host waits
+ * whatever n is: the boxes come back to size the grids, then the n sizes.  PCL's overflow test is kept per cloud: if any cloud fails it
+ * the call returns DGS_ERR_GRID_TOO_LARGE, dgs_last_error names the cloud's position in the batch, and no cloud has been modified.
+ * APPROX_VOXELGRID runs dgs_approx_voxel_grid_filter's routine once per cloud inside the call: identical results, n host waits.
+ * The same cloud listed twice, a NULL cloud, a cloud of another device, a negative size, a NULL input of positive size, an unknown filter
+ * or a leaf_size that is not positive: DGS_ERR_INVALID_ARGUMENT, nothing modified.  n == 0: DGS_OK without a launch.  Any handle of the
+ * clouds' device may make the call; its registration state is untouched.  Additions only: DGS_ABI_VERSION is unchanged. */
+int dgs_cloud_assign_batch(dgs_handle* h, int32_t n, const float* const* inputs_xyz16, const int64_t* sizes, int32_t on_device,
+                           int32_t filter /* 0 NONE, 1 VOXELGRID, 2 APPROX_VOXELGRID */, float leaf_size, dgs_cloud* const* clouds, int64_t* out_sizes);
+/* counts8: of the last dgs_cloud_assign_batch call kernel launches (a sort, a run-length pass and a scan count as one each), host waits,
+ * clouds; the rest 0. */
+int dgs_cloud_assign_get_counts(dgs_handle* h, int64_t* counts8);
+/* The points of a resident cloud, in its order: *n_out is always its size, DGS_ERR_INVALID_ARGUMENT when it exceeds `capacity`. */
+int dgs_cloud_read(dgs_handle* h, const dgs_cloud* cloud, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n_out);
+
 /* pcl::VoxelGrid<PointXYZ> centroid down-sampling, the step right before the path
  * (/root/reference/apps/scan_matching_odometry_nodelet.cpp:83-89,155-165; apps/prefiltering_nodelet.cpp:59-63):
  * cell = floor(p / leaf) as PCL indexes it, output = centroid of every occupied cell in cell-index order, pad lane = 1.
