@@ -212,6 +212,7 @@ SYMBOLS = [
     "dgs_calc_fitness_score_batch_clouds", "dgs_cloud_build_indices", "dgs_fitness_batch_get_counts",
     "dgs_building_cloud_params_init", "dgs_building_cloud_generate", "dgs_building_cloud_get", "dgs_building_cloud_get_counts",
     "dgs_cloud_assign_batch", "dgs_cloud_assign_get_counts", "dgs_cloud_read", "dgs_calc_inlier_fraction_batch_clouds",
+    "dgs_cloud_build_covariances", "dgs_cloud_covariances_get_counts",
 ]
 
 _libs = {}
@@ -257,6 +258,8 @@ def load(path=None):
     lib.dgs_cloud_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_cloud_build_indices.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.dgs_fitness_batch_get_counts.argtypes = [C.c_void_p, C.c_void_p]
+    lib.dgs_cloud_build_covariances.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.dgs_cloud_covariances_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     lib.dgs_voxel_grid_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_approx_voxel_grid_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
     lib.dgs_cloud_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(C.c_void_p)]

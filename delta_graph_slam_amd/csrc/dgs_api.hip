@@ -112,6 +112,8 @@ int prof_begin(dgs_handle* h, int kernel_id, hipStream_t st) {
     p.pool.push_back(ep);
   }
   const int slot = (int)p.next_free++;
+  p.weight.resize(p.pool.size(), 1);
+  p.weight[slot] = 1;
   (void)hipEventRecord(p.pool[slot].start, st ? st : h->stream);
   (void)kernel_id;
   return slot;
@@ -124,6 +126,12 @@ void prof_end(dgs_handle* h, int kernel_id, int slot, hipStream_t st) {
   p.pending[kernel_id].push_back(slot);
 }
 
+void prof_end_counted(dgs_handle* h, int kernel_id, int slot, int count) {
+  if (slot < 0) return;
+  h->prof.weight[slot] = count;
+  prof_end(h, kernel_id, slot);
+}
+
 static void prof_collect(dgs_handle* h) {
   Profiler& p = h->prof;
   (void)hipStreamSynchronize(h->stream);
@@ -133,7 +141,7 @@ static void prof_collect(dgs_handle* h) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, p.pool[slot].start, p.pool[slot].stop) == hipSuccess) {
         p.total_ms[k] += ms;
-        p.launches[k] += 1;
+        p.launches[k] += p.weight[slot];
       }
     }
     p.pending[k].clear();
@@ -506,6 +514,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (const char* e = std::getenv("DGS_KNN_LEAF_WIDE")) h->knn_leaf_wide = std::atoi(e) != 0;
   if (const char* e = std::getenv("DGS_KNN_MIN_WAVES")) h->knn_min_waves = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("DGS_KNN_ROUNDS")) h->knn_rounds = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("DGS_COV_BATCH_POINTS")) h->cb.points_budget = std::min<int64_t>(std::max<int64_t>(0, std::atoll(e)), (int64_t)32 << 20);
   if (const char* e = std::getenv("DGS_GICP_FUSED")) h->gicp_fused = std::atoi(e) != 0;
   if (kExperiments)
     if (const char* e = std::getenv("DGS_NDT_PACK2")) h->ndt_pack2 = std::atoi(e) != 0;
@@ -556,6 +565,7 @@ void dgs_destroy(dgs_handle* h) {
   fitness_batch_release(h);
   building_cloud_release(h);
   voxel_batch_release(h);
+  cov_batch_release(h);
   h->gitems.release(); h->gtargets.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
   h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();
@@ -1316,6 +1326,28 @@ int dgs_cloud_build_indices(dgs_handle* h, int32_t n, dgs_cloud* const* clouds) 
   if (rc != DGS_OK) return rc;
   if (set_device(h)) return DGS_ERR_HIP;
   return fitness_batch_build_indices(h, n, clouds);
+}
+
+// ---- the k-NN covariances of many resident clouds in one pass (cov_batch.hip) ------------------------------------------------------
+int dgs_cloud_build_covariances(dgs_handle* h, int32_t n, dgs_cloud* const* clouds) {
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (n < 0 || (n > 0 && !clouds)) { h->err = "dgs_cloud_build_covariances: bad arguments"; return DGS_ERR_INVALID_ARGUMENT; }
+  const int rc = check_clouds(h, n, clouds, "clouds");
+  if (rc != DGS_OK) return rc;
+  const int32_t m = h->prm.method;
+  if (m != DGS_METHOD_GICP && m != DGS_METHOD_VGICP && m != DGS_METHOD_PCL_GICP) {
+    h->err = std::string("dgs_cloud_build_covariances: ") + method_name(m) + " keeps no k-NN covariances (FAST_GICP, FAST_VGICP and GICP_HIP do)";
+    return DGS_ERR_UNSUPPORTED;
+  }
+  if (set_device(h)) return DGS_ERR_HIP;
+  return cloud_build_covariances(h, n, clouds);
+}
+
+int dgs_cloud_covariances_get_counts(dgs_handle* h, int64_t* counts8) {
+  if (!h || !counts8) return DGS_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < 8; k++) counts8[k] = h->cb.counts8[k];
+  return DGS_OK;
 }
 
 int dgs_calc_inlier_fraction_batch_clouds(dgs_handle* h, int32_t n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16,

@@ -712,13 +712,18 @@ static int gicp_start(dgs_handle* h, int n, CloudState* const* srcs, const doubl
   const int64_t per_point = vgicp ? h->vmap.n_offsets : 1;  // correspondences per source point
   int64_t total = 0, max_n = 1;
   *n_live = 0;
+  std::vector<CloudState*> live;
   for (int i = 0; i < n; i++) {
     if (srcs[i]->n <= 0 || (tgt_of && tgt_of[i] < 0)) continue;
-    rc = ensure_covariance(h, *srcs[i]);
-    if (rc) return rc;
+    live.push_back(srcs[i]);
     total += srcs[i]->n;
     max_n = std::max<int64_t>(max_n, srcs[i]->n);
     (*n_live)++;
+  }
+  // the sources' covariances: one batched pass (cov_batch.hip), a lone source on the single pass; gicp_align_pairs has made them with its targets'
+  if (!tgt_of) {
+    rc = live.size() == 1 ? ensure_covariance(h, *live[0]) : ensure_covariances(h, (int)live.size(), live.data(), covplan::kFast);
+    if (rc) return rc;
   }
   const GicpLaunch L = gicp_choose_launch(n, max_n);
   *L_out = L;
@@ -835,12 +840,18 @@ int gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* co
   all.insert(all.end(), srcs, srcs + n);
   int rc = fitness_batch_build_indices(h, 2 * n, all.data());
   if (rc) return rc;
-  for (dgs_cloud* c : uniq) {   // cached on the cloud under (k, regularisation): shared with every other path that uses the cloud
-    rc = ensure_covariance(h, c->st);
-    if (rc) return rc;
+  // the covariances of the distinct targets and of the live pairs' sources in ONE batched pass (cov_batch.hip), cached on the cloud under
+  // (k, regularisation): shared with every other path that uses the cloud
+  const int64_t indices_built = h->fb.counts8[3];
+  std::vector<CloudState*> cs((size_t)n), need;
+  for (dgs_cloud* c : uniq) need.push_back(&c->st);
+  for (int i = 0; i < n; i++) {
+    cs[i] = &srcs[i]->st;
+    if (tgt_of[i] >= 0 && cs[i]->n > 0) need.push_back(cs[i]);
   }
-  std::vector<CloudState*> cs((size_t)n);
-  for (int i = 0; i < n; i++) cs[i] = &srcs[i]->st;
+  rc = ensure_covariances(h, (int)need.size(), need.data(), covplan::kFast);
+  h->cb.counts8[7] = indices_built;
+  if (rc) return rc;
   const std::vector<double> x0 = gicp_guess_rows(n, guesses16);
   // the target table travels from the pinned block, behind the batch's own staging (gicp_start sizes the block for that alone)
   const size_t tab_off = (GicpStaging(h, n).bytes + 63) & ~(size_t)63, tab_bytes = std::max<size_t>(uniq.size(), 1) * sizeof(GicpTarget);

@@ -2,6 +2,7 @@
 #pragma once
 #include "building_cloud.h"
 #include "common.h"
+#include "cov_batch_plan.h"
 #include "sac.h"
 
 namespace dgs {
@@ -14,6 +15,7 @@ struct Profiler {
   bool enabled = false;
   std::vector<EventPair> pool;                 // all events ever created
   std::vector<int> pending[DGS_K_COUNT];       // indices into pool, recorded but not yet read
+  std::vector<int> weight;                     // per pool slot: by how much its bracket advances `launches` (1; a batched covariance pass: its clouds)
   size_t next_free = 0;
   double total_ms[DGS_K_COUNT] = {0};
   int64_t launches[DGS_K_COUNT] = {0};
@@ -297,6 +299,19 @@ struct BcScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// Batched k-NN covariances of resident clouds (cov_batch.hip): the device tables of a pass's chunks, the pinned block they travel from
+// (its own, with an event: the handle's pinned block is rewritten by the batch that follows while this upload may still be in flight),
+// and the counts of the last pass.
+struct CbScratch {
+  DevBuf<unsigned char> tables;        // per chunk: entries | first search workgroup per cloud | first covariance workgroup per cloud
+  void* stage = nullptr;               // pinned: the tables' upload; not written again before ev_stage has passed
+  size_t stage_bytes = 0;
+  hipEvent_t ev_stage = nullptr;
+  bool stage_pending = false;
+  int64_t points_budget = 0;           // DGS_COV_BATCH_POINTS (0: covplan::kCovBatchPoints)
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -533,6 +548,9 @@ struct dgs_handle {
   // ---- batched down-sampling into resident clouds (voxel_batch.hip): own buffers; everything above is left untouched
   dgs::VbScratch vb;
 
+  // ---- batched k-NN covariances (cov_batch.hip): the chunk tables and their staging; the neighbour table is knn_nbr
+  dgs::CbScratch cb;
+
   dgs::Profiler prof;
 };
 
@@ -541,6 +559,7 @@ namespace dgs {
 // profiling wrappers (dgs_api.hip)
 int prof_begin(dgs_handle* h, int kernel_id, hipStream_t st = nullptr);   // st: default the handle's stream
 void prof_end(dgs_handle* h, int kernel_id, int slot, hipStream_t st = nullptr);
+void prof_end_counted(dgs_handle* h, int kernel_id, int slot, int count);   // one bracket that stands for `count` passes: its time once, the count advanced by `count`
 int ensure_pinned(dgs_handle* h, size_t bytes);
 int ensure_poll_events(dgs_handle* h);
 int side_fork(dgs_handle* h);   // side_stream continues from what the main stream has enqueued so far
@@ -609,6 +628,11 @@ int gicp_probe(dgs_handle* h, const double* T16_rowmajor, int error_only, double
 // gicp_cov.hip: FAST_GICP / FAST_VGICP covariances of a cloud under the handle's (k, regularisation), cached on the cloud
 int ensure_covariance(dgs_handle* h, CloudState& c);
 int gicp_covariances(dgs_handle* h, int which, double* host_out6, int64_t n);
+// cov_batch.hip: the covariances of many clouds (indices built) under the handle's key, in one search and one covariance launch per chunk.
+// kind: covplan::kFast (CloudState::cov, what ensure_covariance makes) or covplan::kPcl (CloudState::pcov, what ensure_pcov makes) -- the same bits.
+int ensure_covariances(dgs_handle* h, int n, CloudState* const* clouds, int kind);
+int cloud_build_covariances(dgs_handle* h, int n, dgs_cloud* const* clouds);   // dgs_cloud_build_covariances behind its argument checks
+void cov_batch_release(dgs_handle* h);
 // gicp_cov_ordered.hip: covariances in upstream's operation order (dgs_params.gicp_cov_jacobi_svd = DGS_GICP_COV_UPSTREAM_ORDER) from knn_lists' sets
 struct BvhView;
 int gicp_cov_upstream_order(dgs_handle* h, const BvhView& v, CloudState& c, int k, int regularization, const int* nbr, int stride);
@@ -673,6 +697,7 @@ void voxel_batch_release(dgs_handle* h);
 // dgs_api.hip: the handles that borrow `c` as target or source fall back to "no input set" (what dgs_cloud_destroy does first)
 void cloud_detach_users(dgs_cloud* c);
 // pcl_gicp.hip
+int ensure_pcov(dgs_handle* h, CloudState& c);   // the PCL-style covariances of a cloud, cached under (k, epsilon)
 int pcl_gicp_align(dgs_handle* h, const float* guess16, dgs_result* out);
 int pcl_gicp_align_batch(dgs_handle* h, int n, CloudState* const* srcs, const float* guesses16, dgs_result* out);
 int pcl_gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* const* srcs, const float* guesses16, dgs_result* out);   // pair i against tgts[i]

@@ -26,6 +26,7 @@
 #include "batch_rounds.h"
 #include "handle.h"
 #include "nn_group.h"
+#include "pg_cov.h"
 #include "slice_rows.h"
 #include "small_linalg.h"
 
@@ -82,115 +83,14 @@ constexpr int kPgLsIters = 100;                          // bracket_iters = sect
 constexpr double kPgRho = 0.01, kPgSigma = 0.01, kPgTau1 = 9.0, kPgTau2 = 0.05, kPgTau3 = 0.5, kPgGradEps = 1e-2;
 
 // ================================================================================================ covariances
-// Sorting network (odd-even transposition) over kKnnMax register slots; compile-time indices only.
-__device__ __forceinline__ void pg_sort32(int* v) {
-#pragma unroll
-  for (int r = 0; r < kKnnMax; r++) {
-#pragma unroll
-    for (int i = (r & 1); i + 1 < kKnnMax; i += 2) {
-      const int lo = min(v[i], v[i + 1]), hi = max(v[i], v[i + 1]);
-      v[i] = lo;
-      v[i + 1] = hi;
-    }
-  }
-}
-
-// The neighbours' sums, one point after another in ascending index order, and what computeCovariances makes of them.
-struct PgCovSums {
-  double mx = 0, my = 0, mz = 0, sxx = 0, syx = 0, syy = 0, szx = 0, szy = 0, szz = 0;
-  __device__ __forceinline__ void add(const float4 p) {
-#pragma clang fp contract(off)
-    mx += (double)p.x; my += (double)p.y; mz += (double)p.z;
-    sxx += (double)(p.x * p.x);
-    syx += (double)(p.y * p.x); syy += (double)(p.y * p.y);
-    szx += (double)(p.z * p.x); szy += (double)(p.z * p.y); szz += (double)(p.z * p.z);
-  }
-  __device__ __forceinline__ void finish(const int k, const double eps, double* out) {
-#pragma clang fp contract(off)
-    const double kk = (double)k;
-    mx /= kk; my /= kk; mz /= kk;
-    double C[9];
-    C[0] = sxx / kk - mx * mx;
-    C[3] = syx / kk - my * mx; C[4] = syy / kk - my * my;
-    C[6] = szx / kk - mz * mx; C[7] = szy / kk - mz * my; C[8] = szz / kk - mz * mz;
-    C[1] = C[3]; C[2] = C[6]; C[5] = C[7];
-    double U[9], V[9], sv[3];
-    jacobi_svd3_d(C, U, V, sv);
-    const double val[3] = {1.0, 1.0, eps};
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++)
-        out[r * 3 + c] = ((val[0] * U[r * 3 + 0]) * U[c * 3 + 0] + (val[1] * U[r * 3 + 1]) * U[c * 3 + 1]) + (val[2] * U[r * 3 + 2]) * U[c * 3 + 2];
-  }
-};
-
-// computeCovariances for one point per lane.  nbr: slot lists in index order (pos), -1 = nothing found (a zero column, as upstream's
-// matrix); out: 9 doubles per point in the caller's order.  Non-finite points get NaN (they never pair, never are a neighbour).
+// computeCovariances over one cloud: the bodies are pg_cov.h's (the batched pass of cov_batch.hip runs the same ones over many clouds).
 __global__ __launch_bounds__(kBlock) void pg_cov_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const double eps,
                                                         const int* __restrict__ nbr, double* __restrict__ cov9) {
-#pragma clang fp contract(off)
-  const int pos = blockIdx.x * kBlock + threadIdx.x;
-  if (pos >= n) return;
-  const int i = (int)__float_as_uint(b.sorted[pos].w);
-  if (i < 0 || i >= n) return;
-  const float4 q = pts[i];
-  double* out = cov9 + (size_t)i * 9;
-  if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.z))) {
-    for (int a = 0; a < 9; a++) out[a] = NAN;
-    return;
-  }
-  int v[kKnnMax];
-#pragma unroll
-  for (int s = 0; s < kKnnMax; s++) {
-    const int j = (s < k) ? nbr[(size_t)pos * kKnnMax + s] : -1;
-    v[s] = (j >= 0 && j < n) ? j : INT_MAX;
-  }
-  pg_sort32(v);
-  PgCovSums sums;
-#pragma unroll
-  for (int s = 0; s < kKnnMax; s++) {
-    if (v[s] != INT_MAX) sums.add(pts[v[s]]);
-  }
-  sums.finish(k, eps, out);
+  pg_cov_body(b, pts, n, k, eps, nbr, cov9, (int)blockIdx.x);
 }
-
-// 32 < k <= 64, table stride kKnnMaxWide.  A 64-slot sorting network in registers is 2,016 compare-exchanges of straight-line code per
-// lane (the compiler did not finish it); the list is sorted in LDS instead: lane t owns column t of s_v (consecutive lanes, consecutive
-// banks: no conflict) and inserts its neighbours one by one.  Same sums in the same (ascending index) order as the narrow kernel.
-// 128 lanes per workgroup: 32 KiB of LDS.
-constexpr int kPgWideBlock = 128;
 __global__ __launch_bounds__(kPgWideBlock) void pg_cov_wide_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const double eps,
                                                                    const int* __restrict__ nbr, double* __restrict__ cov9) {
-#pragma clang fp contract(off)
-  __shared__ int s_v[kKnnMaxWide][kPgWideBlock];
-  const int tid = threadIdx.x;
-  const int pos = blockIdx.x * kPgWideBlock + tid;
-  if (pos >= n) return;   // no barrier below: every lane works on its own column
-  const int i = (int)__float_as_uint(b.sorted[pos].w);
-  if (i < 0 || i >= n) return;
-  const float4 q = pts[i];
-  double* out = cov9 + (size_t)i * 9;
-  if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.z))) {
-    for (int a = 0; a < 9; a++) out[a] = NAN;
-    return;
-  }
-  const int kc = min(k, kKnnMaxWide);
-  int m = 0;   // neighbours found so far, s_v[0 .. m)[tid] ascending
-#pragma unroll 1
-  for (int s = 0; s < kc; s++) {
-    const int j = nbr[(size_t)pos * kKnnMaxWide + s];
-    if (j < 0 || j >= n) continue;
-    int t = m;
-#pragma unroll 1
-    for (; t > 0 && s_v[t - 1][tid] > j; t--) s_v[t][tid] = s_v[t - 1][tid];
-    s_v[t][tid] = j;
-    m++;
-  }
-  PgCovSums sums;
-#pragma unroll 1
-  for (int s = 0; s < m; s++) sums.add(pts[s_v[s][tid]]);
-  sums.finish(k, eps, out);
+  pg_cov_wide_body(b, pts, n, k, eps, nbr, cov9, (int)blockIdx.x);
 }
 
 // ================================================================================================ device helpers
@@ -792,7 +692,7 @@ static PgConsts pg_consts(const dgs_handle* h) {
 }
 
 // the PCL-style covariances of a cloud, computed once per (k, epsilon)
-static int ensure_pcov(dgs_handle* h, CloudState& c) {
+int ensure_pcov(dgs_handle* h, CloudState& c) {
   const int k = h->prm.gicp_correspondence_randomness;
   const double eps = h->pg_opt.gicp_epsilon;
   if (c.pcov_valid && c.pcov_k == k && c.pcov_eps == eps) return DGS_OK;
@@ -853,6 +753,7 @@ static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const flo
   std::vector<int> skip(n, 0);
   std::vector<long long> off(n);
   std::vector<int64_t> live_n(n, 0);
+  std::vector<CloudState*> live;
   for (int i = 0; i < n; i++) {
     CloudState& s = *srcs[i];
     off[i] = total;
@@ -860,11 +761,15 @@ static int pg_run_batch(dgs_handle* h, int n, CloudState* const* srcs, const flo
     if ((int64_t)k > s.n || (tg && tg->of[i] < 0)) { skip[i] = 1; continue; }   // computeCovariances refuses the cloud: this registration fails
     rc = ensure_walk_order(h, s);
     if (rc) return rc;
-    rc = ensure_pcov(h, s);
-    if (rc) return rc;
+    live.push_back(&s);
     live_n[i] = s.n;
     total += s.n;
     n_live++;
+  }
+  // the sources' covariances: one batched pass (cov_batch.hip), a lone source on the single pass; pcl_gicp_align_pairs has made them with its targets'
+  if (!tg) {
+    rc = live.size() == 1 ? ensure_pcov(h, *live[0]) : ensure_covariances(h, (int)live.size(), live.data(), covplan::kPcl);
+    if (rc) return rc;
   }
   SliceTable slices(live_n, kPgSlicePoints);
   const int total_slices = slices.total_slices;
@@ -1008,13 +913,21 @@ int pcl_gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud
   all.insert(all.end(), srcs, srcs + n);
   int rc = fitness_batch_build_indices(h, 2 * n, all.data());
   if (rc) return rc;
-  std::vector<CloudState*> tc(uniq.size()), cs((size_t)n);
-  for (size_t t = 0; t < uniq.size(); t++) {   // cached on the cloud under (k, epsilon): shared with every other path that uses the cloud
+  // the covariances of the distinct targets and of the live pairs' sources in ONE batched pass (cov_batch.hip), cached on the cloud under
+  // (k, epsilon): shared with every other path that uses the cloud
+  const int64_t indices_built = h->fb.counts8[3];
+  std::vector<CloudState*> tc(uniq.size()), cs((size_t)n), need;
+  for (size_t t = 0; t < uniq.size(); t++) {
     tc[t] = &uniq[t]->st;
-    rc = ensure_pcov(h, *tc[t]);
-    if (rc) return rc;
+    need.push_back(tc[t]);
   }
-  for (int i = 0; i < n; i++) cs[i] = &srcs[i]->st;
+  for (int i = 0; i < n; i++) {
+    cs[i] = &srcs[i]->st;
+    if (tgt_of[i] >= 0 && cs[i]->n >= (int64_t)k) need.push_back(cs[i]);
+  }
+  rc = ensure_covariances(h, (int)need.size(), need.data(), covplan::kPcl);
+  h->cb.counts8[7] = indices_built;
+  if (rc) return rc;
   const PgTargets tg{(int)uniq.size(), tc.data(), tgt_of.data()};
   const int64_t own_evaluations = h->last_evaluations;   // dgs_get_counts keeps reporting the handle's own last align / batch
   rc = pg_run_batch(h, n, cs.data(), guesses16, out, nullptr, nullptr, &tg);

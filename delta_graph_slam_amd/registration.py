@@ -474,6 +474,24 @@ class Registration:
         self._check(self._lib.dgs_fitness_batch_get_counts(self._h, C.cast(c, C.c_void_p)))
         return {"launches": c[0], "host_waits": c[1], "edges": c[2], "indices_built": c[3], "rows": c[4], "single_builds": c[5]}
 
+    def build_covariances(self, clouds):
+        """dgs_cloud_build_covariances: the missing NN indices, then the k-NN covariances this handle's method and parameters would make
+        of every listed DeviceCloud on first use, for all of them in one search and one covariance launch per chunk.  Kept on the clouds;
+        bit for bit what setInputSource(cloud) + align would have made.  FAST_GICP, FAST_VGICP, GICP_HIP / GICP_OMP_HIP."""
+        clouds = list(clouds)
+        if not all(isinstance(c, DeviceCloud) for c in clouds):
+            raise TypeError("build_covariances takes DeviceClouds")
+        arr = (C.c_void_p * max(len(clouds), 1))(*[c._c.value for c in clouds])
+        self._check(self._lib.dgs_cloud_build_covariances(self._h, len(clouds), C.cast(arr, C.c_void_p)))
+
+    def covariance_batch_counts(self) -> dict:
+        """Of the last batched covariance pass (build_covariances, align_pairs, an align_batch of two or more sources): kernel launches,
+        host waits, clouds listed / covered / already cached, chunks, clouds served one at a time by a fallback, indices built."""
+        c = (C.c_int64 * 8)()
+        self._check(self._lib.dgs_cloud_covariances_get_counts(self._h, C.cast(c, C.c_void_p)))
+        return {"launches": c[0], "host_waits": c[1], "listed": c[2], "covered": c[3], "cached": c[4], "chunks": c[5], "fallback": c[6],
+                "indices_built": c[7]}
+
     def voxel_grid_filter(self, cloud, leaf_size: float, approximate: bool = False):
         """pcl::VoxelGrid centroid filter (scan_matching_odometry_nodelet.cpp:83-89,155-165) -- or, with approximate=True,
         pcl::ApproximateVoxelGrid (:90-96) -- on the device.

@@ -189,6 +189,21 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
     results->swap(out);
     return true;
   }
+  // What alignPairs would do to these clouds before its first round, ahead of time and for all of them together
+  // (dgs_cloud_build_covariances): upload (once per pcl::PointCloud object, alignPairs' residency and its REQUIREMENT), the exact-NN
+  // indices in one batched build, the k-NN covariances in one search and one covariance launch per chunk of clouds.  FAST_GICP,
+  // FAST_VGICP, GICP_HIP / GICP_OMP_HIP; any other method is named in lastError().  false: nothing was built.
+  template <class CloudPtr>
+  bool buildCovariances(const std::vector<CloudPtr>& clouds) {
+    if (!ensure_handle()) return false;
+    std::vector<dgs_cloud*> c(clouds.size(), nullptr);
+    for (size_t i = 0; i < clouds.size(); i++) {
+      if (!clouds[i]) return false;
+      c[i] = resident(clouds[i]);
+      if (!c[i]) return false;
+    }
+    return dgs_cloud_build_covariances(handle_, (int32_t)c.size(), c.data()) == DGS_OK;
+  }
   void forgetPairCloud(const void* cloud) {
     auto it = pair_clouds_.find(cloud);
     if (it == pair_clouds_.end()) return;

@@ -366,6 +366,23 @@ int dgs_cloud_build_indices(dgs_handle* h, int32_t n, dgs_cloud* const* clouds);
  * counts as one), host waits, edges, indices built, partial rows; then, not of that call but since dgs_create, the single-cloud index
  * builds this handle made by any other path (registration targets, the prefilter, dgs_calc_fitness_score ...); the rest 0. */
 int dgs_fitness_batch_get_counts(dgs_handle* h, int64_t* counts8);
+/* The second half of what a resident cloud needs before it can be registered: the k-NN covariances this handle's method and parameters
+ * would make of each listed cloud on first use -- FAST_GICP / FAST_VGICP: 6 doubles per point under (reg_correspondence_randomness,
+ * regularisation); GICP_HIP / GICP_OMP_HIP: 9 doubles per point under (k, epsilon) -- for all listed clouds together: the missing
+ * indices in dgs_cloud_build_indices' batched build, then per chunk of clouds (4 Mi points; DGS_COV_BATCH_POINTS in the environment of
+ * dgs_create) one table upload, one search launch and one covariance launch, whatever n.  Enqueued on the handle's stream, no host
+ * wait.  The covariances are kept on the cloud for every later user and are, bit for bit, what a lone dgs_set_input_source_cloud +
+ * dgs_align would have made.  Dropped from the work: a cloud listed before, an empty cloud, a cloud whose covariances already answer
+ * the handle's key, and (GICP_HIP) a cloud of fewer than k points, which stays without covariances.  gicp_cov_jacobi_svd = 2 and the
+ * per-query k-NN walk (DGS_KNN_LEAF=0, DGS_KNN_LEAF_WIDE=0) are served one cloud at a time inside the call, results unchanged.
+ * Any other method: DGS_ERR_UNSUPPORTED with the method named; reg_correspondence_randomness > 64: DGS_ERR_UNSUPPORTED; a NULL cloud or
+ * a cloud of another device: DGS_ERR_INVALID_ARGUMENT, nothing modified; n == 0: DGS_OK without a launch. */
+int dgs_cloud_build_covariances(dgs_handle* h, int32_t n, dgs_cloud* const* clouds);
+/* counts8: of the last batched covariance pass, explicit (dgs_cloud_build_covariances) or internal (dgs_align_pairs_clouds, a
+ * dgs_align_batch* of two or more sources): kernel launches of the pass (index builds are dgs_fitness_batch_get_counts'), host waits
+ * (0, unless the previous pass's table upload was still in flight), clouds listed, clouds covered, clouds that had a valid cache,
+ * chunks, clouds served by a per-cloud fallback, indices built. */
+int dgs_cloud_covariances_get_counts(dgs_handle* h, int64_t* counts8);
 
 /* The inlier count of publish_scan_matching_status (apps/scan_matching_odometry_nodelet.cpp:321-332) over a batch of edges between
  * device-resident clouds, with dgs_calc_fitness_score_batch_clouds' arguments: cloud1 carries the index, cloud2 is moved by the edge's
@@ -479,7 +496,9 @@ enum dgs_kernel_id {
 };
 /* When enabled, every launch of a tracked kernel is bracketed by hipEvents on the launch stream. */
 int dgs_profile_enable(dgs_handle* h, int32_t enable);
-/* Sum of event-measured durations and number of launches since the last dgs_profile_reset (synchronises). */
+/* Sum of event-measured durations and number of launches since the last dgs_profile_reset (synchronises).
+ * DGS_K_GICP_COVARIANCE counts covariance passes, one per cloud: a batched pass (dgs_cloud_build_covariances and the paths that use it)
+ * advances the count by the number of clouds it covers and the time by the pass's own; its launches: dgs_cloud_covariances_get_counts. */
 int dgs_profile_get(dgs_handle* h, int32_t kernel_id, double* total_ms, int64_t* launches);
 int dgs_profile_reset(dgs_handle* h);
 /* Counts describing the current problem, for algorithmic-byte accounting:

@@ -95,10 +95,13 @@ def main():
                 reg.profile_enable(True)
                 reg.profile_reset()
                 fleet.step([0.1 * args.frames] * B, [clouds[args.frames // 2]] * B)
-                assign, fb = reg.cloud_assign_counts(), reg.fitness_batch_counts()
+                assign, fb, cb = reg.cloud_assign_counts(), reg.fitness_batch_counts(), reg.covariance_batch_counts()
                 slots = {name: reg.profile_get(k)[1] for name, k in (("correspondence", L.K_NN_SEARCH), ("linearize", L.K_GICP_LINEARIZE), ("covariance", L.K_GICP_COVARIANCE))}
                 counts = {"downsample_launches": assign["launches"], "downsample_host_waits": assign["host_waits"], "index_build_launches": fb["launches"],
-                          "index_build_host_waits": fb["host_waits"], "round_launch_slots": slots}
+                          "index_build_host_waits": fb["host_waits"], "round_launch_slots": slots,
+                          # beside the "covariance" slot count (passes, one per cloud): what the batched pass launched for them
+                          "covariance_launches": cb["launches"], "covariance_chunks": cb["chunks"], "covariance_clouds": cb["covered"],
+                          "covariance_host_waits": cb["host_waits"], "covariance_fallback": cb["fallback"]}
                 reg.profile_enable(False)
             reg.close()
         row = {"streams": B, "frames": args.frames, "solo_fps": [round(v, 1) for v in solo_fps], "fleet_fps": [round(v, 1) for v in fleet_fps],

@@ -15,6 +15,10 @@ FAST_GICP runs with the launch files' values; GICP_HIP with the factory settings
 evaluations and the score of the two ways are compared too (its sums are formed over fixed slices: bit-equality is expected).
 
     python scripts/bench_tick_pairs.py [--method FAST_GICP|GICP_HIP] [--keyframes 1 4 10] [--candidates 1 3 8] [--repeats 50] [--warmup 5] [--runs 3]
+
+--fresh measures the first-use tick instead: per (K, c) one align_pairs over K + K c clouds that nothing has seen before, so
+that their indices and covariances are made inside the timed call; per run the median tick and, from profiled ticks, the device time and
+the passes of the covariance stage alone (--keyframes 3 --candidates 10: 33 clouds).
 """
 import argparse
 import json
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--method", choices=["FAST_GICP", "GICP_HIP"], default="FAST_GICP")
+    ap.add_argument("--fresh", action="store_true", help="the first-use tick instead: every cloud of every timed align_pairs is a new DeviceCloud (DESIGN.md 6s)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -52,8 +57,46 @@ def main():
         reg = Registration("GICP_HIP", device=0)   # the factory settings (scripts/bench_pcl_gicp.py)
     else:
         reg = Registration("FAST_GICP", device=0, gicp_max_correspondence_distance=2.0, transformation_epsilon=0.1)   # the launch files' values
-    resident = [reg.make_cloud(f) for f in frames]
     rng = np.random.default_rng(0)
+    if args.fresh:
+        # The first-use tick: K new keyframes x c candidates, K + K c clouds that nothing has seen before -- their indices and covariances
+        # are made inside the timed align_pairs.  Per repeat the clouds are uploaded anew (not timed).  Per run the median tick and, from a
+        # profiled tick, the device time and the passes of the covariance stage alone.
+        for K in args.keyframes:
+            for c in args.candidates:
+                fr, ps = synth.vlp16_stream(n_frames=K + K * c)
+                tgt = [i for i in range(K) for _ in range(c)]
+                src = [K + i * c + j for i in range(K) for j in range(c)]
+                g = [(np.linalg.inv(ps[t]) @ ps[s]).astype(np.float32) for t, s in zip(tgt, src)]
+
+                def one(profile=False):
+                    clouds = [reg.make_cloud(f) for f in fr]
+                    reg.synchronize()
+                    if profile:
+                        reg.profile_enable(True)
+                        reg.profile_reset()
+                    t0 = time.perf_counter()
+                    reg.align_pairs([clouds[t] for t in tgt], [clouds[s] for s in src], g, compute_fitness=True)
+                    ms = (time.perf_counter() - t0) * 1e3
+                    cov = reg.profile_get(L.K_GICP_COVARIANCE) if profile else None
+                    if profile:
+                        reg.profile_enable(False)
+                    for cl in clouds:
+                        cl.close()
+                    return ms, cov
+
+                med, cov_ms, cov_n = [], [], 0
+                for _ in range(args.runs):
+                    for _ in range(args.warmup):
+                        one()
+                    med.append(round(statistics.median(one()[0] for _ in range(args.repeats)), 4))
+                    cov = [one(profile=True)[1] for _ in range(5)]
+                    cov_ms.append(round(statistics.median(x[0] for x in cov), 4))
+                    cov_n = cov[0][1]
+                print(json.dumps(dict(fresh=True, method=args.method, K=K, c=c, clouds=K + K * c, points_per_cloud=int(fr[0].shape[0]), tick_ms=med,
+                                      covariance_stage_ms=cov_ms, covariance_passes=cov_n)), flush=True)
+        return
+    resident = [reg.make_cloud(f) for f in frames]
 
     def tick(K, c):
         """-> per new keyframe (target index, [source indices], [guesses])"""
