@@ -213,6 +213,7 @@ SYMBOLS = [
     "dgs_building_cloud_params_init", "dgs_building_cloud_generate", "dgs_building_cloud_get", "dgs_building_cloud_get_counts",
     "dgs_cloud_assign_batch", "dgs_cloud_assign_get_counts", "dgs_cloud_read", "dgs_calc_inlier_fraction_batch_clouds",
     "dgs_cloud_build_covariances", "dgs_cloud_covariances_get_counts",
+    "dgs_prefilter_scan_batch", "dgs_prefilter_batch_get_counts", "dgs_prefilter_batch_get_statistics",
 ]
 
 _libs = {}
@@ -340,6 +341,10 @@ def load(path=None):
     lib.dgs_prefilter_scan_params_init.argtypes = [P(PrefilterScanParams)]
     lib.dgs_prefilter_scan.argtypes = [C.c_void_p, P(PrefilterParams), P(PrefilterScanParams), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64), P(C.c_int64), C.c_void_p]
+    lib.dgs_prefilter_scan_batch.argtypes = [C.c_void_p, P(PrefilterParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dgs_prefilter_batch_get_counts.argtypes = [C.c_void_p, C.c_void_p]
+    lib.dgs_prefilter_batch_get_statistics.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
     lib.dgs_prefilter_deskew.argtypes = [C.c_void_p, P(PrefilterScanParams), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                          P(C.c_int64)]
     lib.dgs_map_cloud_params_init.argtypes = [P(MapCloudParams)]

@@ -33,6 +33,42 @@ __device__ __forceinline__ bool compact_slot(const unsigned char* __restrict__ f
   return true;
 }
 
+// ---- the same compaction over many segments in one chain (prefilter_batch.hip).  Every segment owns whole workgroups of the count and
+// scatter launches, and its flags stand at its first workgroup * kBlock of the shared flag array.  The count pass writes every
+// workgroup's count to blk[global workgroup] (and a 0 behind the last one), pf_scan_kernel scans all of them plus that one, so
+// blk[first workgroup of segment s + 1] - blk[first workgroup of segment s] is the segment's total and blk[w] - blk[first workgroup of
+// w's segment] is workgroup w's first slot inside its segment's output: what compact_offsets gives the segment alone (integer sums).
+// `flags`: the segment's own flags, i its local element, n its size.  -> the workgroup's count in lane 0 of wave 0 (every lane calls it).
+template <class Index>
+__device__ __forceinline__ int compact_count_seg(const unsigned char* __restrict__ flags, const Index i, const Index n) {
+  __shared__ int s_w[kBlock / kWave];
+  const bool f = i < n && flags[i] != 0;
+  const unsigned long long m = __ballot(f);
+  if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = __popcll(m);
+  __syncthreads();
+  int t = 0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; w++) t += s_w[w];
+  }
+  return t;
+}
+// compact_slot for a workgroup whose first slot inside its segment's output is `base`
+template <class Index>
+__device__ __forceinline__ bool compact_slot_seg(const unsigned char* __restrict__ flags, const Index i, const Index n, const int base, int* off) {
+  __shared__ int s_w[kBlock / kWave];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const bool f = i < n && flags[i] != 0;
+  const unsigned long long m = __ballot(f);
+  if (lane == 0) s_w[wv] = __popcll(m);
+  __syncthreads();
+  if (!f) return false;
+  int o = base;
+  for (int w = 0; w < wv; w++) o += s_w[w];
+  *off = o + __popcll(m & ((1ull << lane) - 1ull));
+  return true;
+}
+
 inline unsigned compact_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 // count + scan of `flags` over n elements: blk (compact_blocks(n) ints) becomes every workgroup's first output slot, *total the number

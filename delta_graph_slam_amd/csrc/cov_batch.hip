@@ -43,17 +43,7 @@ struct CovBatchEntry {
 };
 static_assert(sizeof(CovBatchEntry) == 96, "one entry is six 16-byte scalar loads");
 
-// The cloud whose workgroups hold `blk`: the largest c with first[c] <= blk (first[0] = 0, ascending, every cloud owns at least one
-// workgroup; blk < first[m]).  Uniform: scalar loads.
-__device__ __forceinline__ int cov_batch_find(const int* __restrict__ first, const int m, const int blk) {
-  int lo = 0, hi = m;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= blk) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
+// (cov_batch_find, the bisection of the array of first workgroups: knn_leaf.h, shared with prefilter_batch.hip)
 // ---- the search: gicp_knn_leaf_kernel / gicp_knn_leaf_wide_kernel over the chunk, their launch bounds
 __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void cov_knn_batch_kernel(const CovBatchEntry* __restrict__ tab, const int* __restrict__ first, const int m, const int k,
                                                                               int* __restrict__ stats) {

@@ -309,13 +309,20 @@ static int fb_host_reserve(dgs_handle* h, void*& p, size_t& cap, size_t bytes) {
 }
 
 int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, bool reset_counts) {
+  std::vector<CloudState*> states((size_t)n);
+  for (int i = 0; i < n; i++) states[i] = &clouds[i]->st;
+  return fitness_batch_build_state_indices(h, n, states.data(), reset_counts);
+}
+
+// The build over cloud states, whoever owns them: dgs_cloud objects (above) or a handle's own stage clouds (prefilter_batch.hip).
+int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* clouds, bool reset_counts) {
   FbScratch& F = h->fb;
   if (reset_counts) std::fill(F.counts8, F.counts8 + 8, 0);
   if (side_join(h) != DGS_OK) return DGS_ERR_HIP;   // an index being built on the side stream
-  std::vector<dgs_cloud*> todo;
+  std::vector<CloudState*> todo;
   for (int i = 0; i < n; i++) {
-    dgs_cloud* c = clouds[i];
-    if (c->st.n > 0 && !c->st.bvh.valid && std::find(todo.begin(), todo.end(), c) == todo.end()) todo.push_back(c);
+    CloudState* c = clouds[i];
+    if (c->n > 0 && !c->bvh.valid && std::find(todo.begin(), todo.end(), c) == todo.end()) todo.push_back(c);
   }
   const int M = (int)todo.size();
   if (M == 0) return DGS_OK;
@@ -326,7 +333,7 @@ int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, 
   int64_t total = 0;
   int max_n = 0, max_pad = 0, max_depth = 0;
   for (int s = 0; s < M; s++) {
-    const int cn = (int)todo[s]->st.n, n_leaves = (cn + kLeaf - 1) / kLeaf;
+    const int cn = (int)todo[s]->n, n_leaves = (cn + kLeaf - 1) / kLeaf;
     int depth = 1;
     int64_t slots = kFan;
     while (slots < n_leaves) { slots *= kFan; depth++; }
@@ -341,7 +348,7 @@ int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, 
   std::vector<FbSeg> segs((size_t)M);
   int off = 0;
   for (int s = 0; s < M; s++) {
-    CloudState& C = todo[s]->st;
+    CloudState& C = *todo[s];
     Bvh& B = C.bvh;
     const Shape& S = shapes[s];
     B.valid = false;
@@ -392,9 +399,9 @@ int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, 
     F.counts8[0]++;
   }
   DGS_HIP_TRY(h, hipGetLastError());
-  for (dgs_cloud* c : todo) {
-    c->st.bvh.kd = false;
-    c->st.bvh.valid = true;
+  for (CloudState* c : todo) {
+    c->bvh.kd = false;
+    c->bvh.valid = true;
   }
   F.counts8[3] += M;
   return DGS_OK;

@@ -312,6 +312,29 @@ struct CbScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// The prefilter chain over many scans (prefilter_batch.hip): a pool of stage clouds per scan of a chunk, the shared flag / count /
+// neighbour arrays of all scans back to back, the stage tables and the pinned block they travel through.  Separate from PfScratch: the
+// single call's buffers and hooks are not touched, except that its hooks report n = 0 afterwards.
+struct PfbScratch {
+  std::vector<CloudState> a, b, c, d, e;   // per scan: distance / down-sampling / outlier / height / flatten outputs (a, b, d carry the indices)
+  DevBuf<float4> in;                   // staged host inputs, all scans of a chunk back to back
+  DevBuf<unsigned char> flags;         // keep flags, every scan padded to whole workgroups
+  DevBuf<int> blk;                     // per-workgroup kept counts of all scans (+ 1), scanned in place
+  DevBuf<int> cnt;                     // [0] kept points of all scans
+  DevBuf<int> totals;                  // kept points per scan of the stage
+  DevBuf<int> nbr;                     // k-NN lists of all scans of a stage: [(points before the scan + position in index order) * 32 + slot]
+  DevBuf<float> mean_d;                // statistical pass: per point, all scans back to back
+  DevBuf<double> stats;                // statistical pass: mean, stddev, threshold, variance per scan
+  DevBuf<float4> normals;              // normal pass (the body writes them)
+  DevBuf<float> cov9;
+  DevBuf<unsigned char> tables;        // the stage's table: entries | heads | first workgroups | first search workgroups
+  void* stage = nullptr;               // pinned: the table's upload and the totals' download; every stage ends with a host wait
+  size_t stage_bytes = 0;
+  std::vector<double> stats_host;      // of the last call: {mean, stddev, threshold, points} per scan
+  int64_t points_budget = 0;           // DGS_PREFILTER_BATCH_POINTS (0: pfbplan::kBatchPoints)
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -551,6 +574,9 @@ struct dgs_handle {
   // ---- batched k-NN covariances (cov_batch.hip): the chunk tables and their staging; the neighbour table is knn_nbr
   dgs::CbScratch cb;
 
+  // ---- the prefilter over many scans (prefilter_batch.hip): own buffers and indices; PfScratch and everything above is left untouched
+  dgs::PfbScratch pfb;
+
   dgs::Profiler prof;
 };
 
@@ -672,6 +698,7 @@ void building_overlap_release(dgs_handle* h);
 void floor_detection_release(dgs_handle* h);
 // fitness_batch.hip
 int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, bool reset_counts = true);
+int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* clouds, bool reset_counts = true);   // the same build over cloud states
 int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_range,
                          double* scores, int64_t* used);
 // one edge of the scorer over plain device arrays: index over cloud1, cloud2's points, the relative pose (column-major, host)
@@ -693,7 +720,13 @@ void building_cloud_release(dgs_handle* h);
 // voxel_batch.hip: inputs filtered (0 NONE, 1 VOXELGRID, 2 APPROX_VOXELGRID) into resident clouds; the caller has checked the arguments
 int cloud_assign_batch(dgs_handle* h, int n, const float* const* inputs, const int64_t* sizes, int on_device, int filter, float leaf, dgs_cloud* const* clouds,
                        int64_t* out_sizes);
+// VOXELGRID of n device inputs into n cloud states by one chain, two host waits (adds to VbScratch::counts8[0..1]); `owners` (nullable):
+// the dgs_cloud objects the states belong to, whose users are detached.  On DGS_ERR_GRID_TOO_LARGE no state has been touched.
+int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64_t* sizes, float leaf, CloudState* const* states, dgs_cloud* const* owners,
+                    int64_t* out_sizes);
 void voxel_batch_release(dgs_handle* h);
+// prefilter_batch.hip
+void prefilter_batch_release(dgs_handle* h);
 // dgs_api.hip: the handles that borrow `c` as target or source fall back to "no input set" (what dgs_cloud_destroy does first)
 void cloud_detach_users(dgs_cloud* c);
 // pcl_gicp.hip

@@ -134,7 +134,9 @@ __global__ __launch_bounds__(kBlock) void vb_centroid_kernel(const VbSeg* __rest
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 // inputs: device pointers (host inputs have been staged by the caller).  On DGS_ERR_GRID_TOO_LARGE no cloud has been touched.
-static int assign_voxelgrid(dgs_handle* h, int n, const float4* const* d_in, const int64_t* sizes, float leaf, dgs_cloud* const* clouds, int64_t* out_sizes) {
+// The outputs are cloud states: those of dgs_cloud objects (`owners`, dgs_cloud_assign_batch) or a handle's own (prefilter_batch.hip).
+int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64_t* sizes, float leaf, CloudState* const* states, dgs_cloud* const* owners,
+                    int64_t* out_sizes) {
   VbScratch& V = h->vb;
   hipStream_t st = h->stream;
   int64_t total = 0;
@@ -147,9 +149,9 @@ static int assign_voxelgrid(dgs_handle* h, int n, const float4* const* d_in, con
   for (int i = 0; i < n; i++) out_sizes[i] = 0;
   if (total == 0) {   // nothing to launch: every cloud becomes empty
     for (int i = 0; i < n; i++) {
-      cloud_detach_users(clouds[i]);
-      clouds[i]->st.invalidate();
-      clouds[i]->st.n = 0;
+      if (owners) cloud_detach_users(owners[i]);
+      states[i]->invalidate();
+      states[i]->n = 0;
     }
     return DGS_OK;
   }
@@ -220,11 +222,11 @@ static int assign_voxelgrid(dgs_handle* h, int n, const float4* const* d_in, con
   }
   // from here on the clouds change: whoever borrowed one loses it, buffers grow to the input size (the steady state allocates nothing)
   for (int i = 0; i < n; i++) {
-    cloud_detach_users(clouds[i]);
-    clouds[i]->st.invalidate();
-    clouds[i]->st.n = 0;
-    if (sizes[i] > 0) DGS_HIP_TRY(h, clouds[i]->st.pts.reserve((size_t)sizes[i]));
-    segs[i].out = clouds[i]->st.pts.ptr;
+    if (owners) cloud_detach_users(owners[i]);
+    states[i]->invalidate();
+    states[i]->n = 0;
+    if (sizes[i] > 0) DGS_HIP_TRY(h, states[i]->pts.reserve((size_t)sizes[i]));
+    segs[i].out = states[i]->pts.ptr;
   }
 
   // 2. - 5.
@@ -248,9 +250,15 @@ static int assign_voxelgrid(dgs_handle* h, int n, const float4* const* d_in, con
   V.counts8[1]++;
   for (int i = 0; i < n; i++) {
     out_sizes[i] = bounds_h[2 * i + 1] - bounds_h[2 * i];
-    clouds[i]->st.n = out_sizes[i];
+    states[i]->n = out_sizes[i];
   }
   return DGS_OK;
+}
+
+static int assign_voxelgrid(dgs_handle* h, int n, const float4* const* d_in, const int64_t* sizes, float leaf, dgs_cloud* const* clouds, int64_t* out_sizes) {
+  std::vector<CloudState*> states((size_t)n);
+  for (int i = 0; i < n; i++) states[i] = &clouds[i]->st;
+  return voxelgrid_batch(h, n, d_in, sizes, leaf, states.data(), clouds, out_sizes);
 }
 
 int cloud_assign_batch(dgs_handle* h, int n, const float* const* inputs, const int64_t* sizes, int on_device, int filter, float leaf, dgs_cloud* const* clouds,

@@ -149,6 +149,59 @@ class Prefilter:
                                                  C.byref(m3), C.byref(m2), lidar.ctypes.data_as(C.c_void_p)))
         return self._take(o3, m3.value), self._take(o2, m2.value), lidar
 
+    def filter_scan_batch(self, clouds, angular_velocities=None, base_link_transforms=None, scan_period=0.1):
+        """filter_scan over many scans in one device call (dgs_prefilter_scan_batch): the frames of several streams.
+        -> ([(filtered3d, filtered2d, lidar_position)] per scan, statuses int32 [n]).  Scan i receives the bits filter_scan gives it
+        alone; statuses[i] is what that single call would have returned (0 = ok; otherwise the scan's outputs are empty and the other
+        scans are unaffected).  angular_velocities / base_link_transforms: one entry per scan (None entries allowed), or None for all.
+        clouds: all numpy (numpy out) or all device tensors (device tensors out, views of two slabs)."""
+        n = len(clouds)
+        avs = list(angular_velocities) if angular_velocities is not None else [None] * n
+        tfs = list(base_link_transforms) if base_link_transforms is not None else [None] * n
+        if len(avs) != n or len(tfs) != n:
+            raise ValueError("angular_velocities and base_link_transforms need one entry per scan")
+        statuses = np.zeros(n, np.int32)
+        if n == 0:
+            self._check(self._lib.dgs_prefilter_scan_batch(self._h, C.byref(self.params), 0, None, None, None, 0, None, None, None, None, 0, None, None, None, None))
+            return [], statuses
+        dev = _is_device(clouds[0])
+        if any(_is_device(c) != dev for c in clouds):
+            raise ValueError("filter_scan_batch takes all numpy arrays or all device tensors")
+        ptrs = [_cloud_ptr(c, sync=False) for c in clouds]
+        if dev:
+            torch.cuda.current_stream(clouds[0].device).synchronize()   # once for the whole batch
+        sizes = np.array([q[1] for q in ptrs], np.int64)
+        offs = np.concatenate([[0], np.cumsum(np.maximum(sizes, 1))]).astype(np.int64)
+        slab3, slab2 = self._new(clouds[0], int(offs[-1])), self._new(clouds[0], int(offs[-1]))
+        o3 = [slab3[offs[i]:offs[i + 1]] for i in range(n)]
+        o2 = [slab2[offs[i]:offs[i + 1]] for i in range(n)]
+        sps = (L.PrefilterScanParams * n)(*[self._scan_params(avs[i], tfs[i], scan_period) for i in range(n)])
+        in_p = (C.c_void_p * n)(*[q[0] for q in ptrs])
+        o3_p = (C.c_void_p * n)(*[self._ptr(o) for o in o3])
+        o2_p = (C.c_void_p * n)(*[self._ptr(o) for o in o2])
+        m3, m2 = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        lidar = np.zeros((n, 3), np.float64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.dgs_prefilter_scan_batch(self._h, C.byref(self.params), n, sps, in_p, vp(sizes), 1 if dev else 0, o3_p, vp(sizes), o2_p, vp(sizes),
+                                                       1 if dev else 0, vp(m3), vp(m2), vp(lidar), vp(statuses)))
+        return [(self._take(o3[i], int(m3[i])), self._take(o2[i], int(m2[i])), lidar[i].copy()) for i in range(n)], statuses
+
+    def batch_counts(self) -> np.ndarray:
+        """counts8 of the last filter_scan_batch: [0] kernel launches, [1] host waits, [2] scans listed, [3] scans that reached the
+        normal filter, [4] scans served by a per-scan fallback, [5] chunks, [6] indices built."""
+        c = np.zeros(8, np.int64)
+        self._check(self._lib.dgs_prefilter_batch_get_counts(self._h, c.ctypes.data_as(C.c_void_p)))
+        return c
+
+    def batch_statistics(self) -> np.ndarray:
+        """float64 [n, 4]: {mean, stddev, threshold, points} of every scan's statistical pass in the last filter_scan_batch; zeros
+        where that pass did not run."""
+        n = C.c_int64(0)
+        self._check(self._lib.dgs_prefilter_batch_get_statistics(self._h, None, 0, C.byref(n)))
+        s = np.zeros((n.value, 4), np.float64)
+        self._check(self._lib.dgs_prefilter_batch_get_statistics(self._h, s.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return s
+
     def deskew(self, cloud, angular_velocity=None, base_link_transform=None, scan_period=0.1):
         """Deskewing and the base_link transform alone (dgs_prefilter_deskew): every point at its own place, non-finite ones included."""
         ptr, n, dev, keep = _cloud_ptr(cloud)

@@ -111,6 +111,64 @@ class HipPrefilter {
     return true;
   }
 
+  // filterScan over many scans in one device call (dgs_prefilter_scan_batch): the frames of several streams.  srcs / filtered3d /
+  // filtered2d: one cloud per scan; angular_velocities / base_link_matrices16: one pointer per scan (a null entry: none for that scan)
+  // or null for all; lidar_positions_out (3 doubles per scan, nullable); statuses_out (nullable): what filterScan's device call would
+  // have returned for each scan.  Scan i receives the bits filterScan gives it alone.  false: the call itself failed, every output empty;
+  // a scan whose status is not DGS_OK has empty outputs and does not fail the call.
+  bool filterScanBatch(const std::vector<const pcl::PointCloud<PointT>*>& srcs, const double* const* angular_velocities,
+                       const double* const* base_link_matrices16, std::vector<pcl::PointCloud<PointT>>& filtered3d,
+                       std::vector<pcl::PointCloud<PointT>>& filtered2d, double* lidar_positions_out, std::vector<int>* statuses_out) {
+    const size_t n = srcs.size();
+    filtered3d.assign(n, pcl::PointCloud<PointT>());
+    filtered2d.assign(n, pcl::PointCloud<PointT>());
+    if (statuses_out) statuses_out->assign(n, DGS_OK);
+    if (!ensure_handle()) return false;
+    if (n == 0) return true;
+    std::vector<std::vector<float>> in(n), o3(n), o2(n);
+    std::vector<const float*> in_p(n);
+    std::vector<float*> o3_p(n), o2_p(n);
+    std::vector<int64_t> sizes(n), n3(n, 0), n2(n, 0);
+    std::vector<int32_t> status(n, 0);
+    std::vector<dgs_prefilter_scan_params> sps(n, sp_);
+    const double period = scan_period_();
+    for (size_t s = 0; s < n; s++) {
+      const pcl::PointCloud<PointT>& src = *srcs[s];
+      const size_t m = src.points.size();
+      in[s].resize(4 * (m ? m : 1));
+      for (size_t i = 0; i < m; i++) {
+        std::memcpy(&in[s][4 * i], &src.points[i], 3 * sizeof(float));
+        in[s][4 * i + 3] = 1.f;
+      }
+      o3[s].resize(4 * (m ? m : 1));
+      o2[s].resize(4 * (m ? m : 1));
+      in_p[s] = in[s].data();
+      o3_p[s] = o3[s].data();
+      o2_p[s] = o2[s].data();
+      sizes[s] = (int64_t)m;
+      const double* av = angular_velocities ? angular_velocities[s] : nullptr;
+      const double* m16 = base_link_matrices16 ? base_link_matrices16[s] : nullptr;
+      dgs_prefilter_scan_params& sp = sps[s];
+      sp.has_angular_velocity = av ? 1 : 0;
+      for (int a = 0; a < 3; a++) sp.angular_velocity[a] = av ? av[a] : 0.0;
+      sp.scan_period = period;
+      sp.has_transform = m16 ? 1 : 0;
+      for (int a = 0; a < 16; a++) sp.transform[a] = m16 ? m16[a] : (a % 5 == 0 ? 1.0 : 0.0);
+      sp.transform[3] = 0.0;   // lidar scans should be centered in base_link
+      sp.transform[7] = 0.0;
+    }
+    if (dgs_prefilter_scan_batch(h_, &p_, (int32_t)n, sps.data(), in_p.data(), sizes.data(), 0, o3_p.data(), sizes.data(), o2_p.data(), sizes.data(), 0, n3.data(),
+                                 n2.data(), lidar_positions_out, status.data()) != DGS_OK)
+      return false;
+    for (size_t s = 0; s < n; s++) {
+      if (statuses_out) (*statuses_out)[s] = status[s];
+      if (status[s] != DGS_OK) continue;
+      unpack(o3[s], n3[s], filtered3d[s]);
+      unpack(o2[s], n2[s], filtered2d[s]);
+    }
+    return true;
+  }
+
  private:
   bool ensure_handle() {
     if (h_) return true;

@@ -658,6 +658,35 @@ int dgs_prefilter_scan(dgs_handle* h, const dgs_prefilter_params* chain_params, 
 int dgs_prefilter_deskew(dgs_handle* h, const dgs_prefilter_scan_params* scan_params, const float* in_xyz16, int64_t n, int32_t in_on_device,
                          float* out_xyz16, int64_t out_capacity, int32_t out_on_device, int64_t* n_out);
 
+/* ---- dgs_prefilter_scan over many scans in one device call: the frames of several streams ------------------------
+ * Scan i receives, bit for bit and in the same order, what dgs_prefilter_scan(h, chain_params, &scan_params[i], in_xyz16[i], sizes[i],
+ * ...) writes: out3d_xyz16[i] / out2d_xyz16[i] (capacities cap3d[i] / cap2d[i]), n3d_out[i] / n2d_out[i] and lidar_xyz_out[3 i ..]
+ * (nullable); with scan_params == NULL, what dgs_prefilter with a zero lidar_xyz writes.  One chain parameter set serves all scans,
+ * the head is per scan.  A scan's result depends on neither its place in the batch nor the other scans.  The launches and host waits
+ * of a call follow the parameter set, the deepest index among the scans and the number of chunks, not n_scans.
+ * status_out[i] (one per scan) is what the single call would have returned for scan i; a per-scan condition does not fail the call
+ * and the other scans run: STATISTICAL with 0 < points <= statistical_mean_k (DGS_ERR_INVALID_ARGUMENT, counts 0) and an output
+ * capacity too small (DGS_ERR_INVALID_ARGUMENT, the full counts are reported).  An empty scan, and a scan that a stage empties, end
+ * with counts 0 and DGS_OK.
+ * DGS_ERR_INVALID_ARGUMENT with nothing written: a wrong struct_size of the chain parameters or of any head, a deskew_norm_order out
+ * of range, k-NN sizes above 32, a NULL array, a negative size, a NULL input of positive size, more than 2^31 points in total.
+ * n_scans == 0 is DGS_OK without a launch.  A grid too large for VOXELGRID in any scan fails the call (DGS_ERR_GRID_TOO_LARGE).
+ * Own buffers on the handle: registration state and the single call's scratch are untouched; afterwards dgs_prefilter_get_statistics
+ * and dgs_prefilter_get_normals report n = 0.  Additions only: DGS_ABI_VERSION is unchanged. */
+int dgs_prefilter_scan_batch(dgs_handle* h, const dgs_prefilter_params* chain_params, int32_t n_scans,
+                             const dgs_prefilter_scan_params* scan_params /* n_scans entries; NULL: no head, lidar position zero */,
+                             const float* const* in_xyz16, const int64_t* sizes, int32_t in_on_device, float* const* out3d_xyz16, const int64_t* cap3d,
+                             float* const* out2d_xyz16, const int64_t* cap2d, int32_t out_on_device, int64_t* n3d_out, int64_t* n2d_out,
+                             double* lidar_xyz_out /* 3 per scan, nullable */, int32_t* status_out /* one per scan */);
+/* counts8 of the last batch call: [0] kernel launches (a library sort, run-length pass or scan counts as one each), [1] host waits,
+ * [2] scans listed, [3] scans that ran the whole chain (reached the normal filter), [4] scans served by a per-scan fallback
+ * (APPROX_VOXELGRID, DGS_KNN_LEAF=0: every scan of the chunk), [5] chunks (DGS_PREFILTER_BATCH_POINTS raw points each, default
+ * 4 Mi), [6] indices built, [7] reserved. */
+int dgs_prefilter_batch_get_counts(dgs_handle* h, int64_t* counts8);
+/* {mean, stddev, threshold, points} of every scan's statistical pass in the last batch call, zeros where that pass did not run.
+ * *n_scans is always set; the array (nullable) is filled when capacity_scans suffices. */
+int dgs_prefilter_batch_get_statistics(dgs_handle* h, double* stats4_per_scan, int64_t capacity_scans, int64_t* n_scans);
+
 /* ---- MapCloudGenerator::generate on the device (src/hdl_graph_slam/map_cloud_generator.cpp:13-50) ------------
  * Every keyframe cloud transformed by its pose (pose.matrix().cast<float>(), w = 1, no FMA), concatenated in keyframe and point
  * order, inserted into a pcl::octree::OctreePointCloud of `resolution` and replaced by the centres of the occupied voxels in the
