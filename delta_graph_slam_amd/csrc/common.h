@@ -400,6 +400,47 @@ struct DevBuf {
   }
 };
 
+// Pinned host memory that a call's tables go up from and its results come down into, grown like a DevBuf (a quarter plus 4 KiB).
+// A block whose upload nobody waits for is mark()ed behind the copy; its next writer calls wait_if_in_flight() first.
+struct PinnedBlock {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;   // behind the last marked copy (created by the first mark)
+  bool pending = false;      // that copy may still be reading the block
+  char* at(size_t off) const { return static_cast<char*>(ptr) + off; }
+  hipError_t reserve(size_t n) {
+    if (n <= bytes) return hipSuccess;
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr;
+    bytes = 0;
+    const size_t want = n + n / 4 + 4096;
+    hipError_t e = hipHostMalloc(&ptr, want, hipHostMallocDefault);
+    if (e == hipSuccess) bytes = want;
+    return e;
+  }
+  // *waited: the host had to wait for the marked copy (a host wait the caller counts)
+  hipError_t wait_if_in_flight(bool* waited) {
+    *waited = pending && hipEventQuery(ev) != hipSuccess;
+    pending = false;
+    return *waited ? hipEventSynchronize(ev) : hipSuccess;
+  }
+  hipError_t mark(hipStream_t st) {
+    hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(ev, st);
+    pending = e == hipSuccess;
+    return e;
+  }
+  void settled() { pending = false; }   // the caller has waited for the stream the marked copy went on
+  void release() {
+    if (ptr) (void)hipHostFree(ptr);
+    if (ev) (void)hipEventDestroy(ev);
+    ptr = nullptr;
+    bytes = 0;
+    ev = nullptr;
+    pending = false;
+  }
+};
+
 // ---- device helpers --------------------------------------------------------------------------------------
 // Individually rounded float ops.  hipcc contracts a*b+c into FMA by default (-ffp-contract=fast-honor-pragmas) and
 // HIP's __fmul_rn/__fadd_rn are plain operators, so the pragma is what keeps these two roundings apart.

@@ -6,13 +6,13 @@
 // The table.  One CovBatchEntry per cloud of the chunk: the cloud's index, points, slice of the chunk's neighbour table, output, size, the
 // `parts` knn_lists would give it alone (cov_batch_plan.h: the slot order of a neighbour list depends on it, and the 6-double sums follow
 // slot order) and its first workgroup in either launch.  Every cloud owns whole workgroups.  A workgroup finds its cloud by bisecting the
-// launch's array of first workgroups with its blockIdx.x; the address is workgroup-uniform, so the bisection and the entry are scalar
+// launch's array of first workgroups with its blockIdx.x (seg_find, seg_device.h); the address is workgroup-uniform, so the bisection and the entry are scalar
 // loads and the entry lives in SGPRs, like PgTarget (pcl_gicp.hip).  From there on the workgroup is a workgroup of the single-cloud
 // launch: same body, same local index, same arguments.
 //
 // Chunks.  A chunk's neighbour table is h->knn_nbr (points * 32 or * 64 ints), reused by the next chunk in stream order; the plan
-// (cov_batch_plan.h) fills chunks up to a point budget.  Nothing in here waits for the device: the tables travel from a pinned block of
-// their own, and only a call that finds the previous pass's upload still in flight waits for it (counted).
+// (cov_batch_plan.h) fills chunks up to a point budget.  Nothing in here waits for the device: the tables, laid out by seg_table.h, travel
+// from a PinnedBlock of their own, and only a call that finds the previous pass's upload still in flight waits for it (counted).
 //
 // Served one cloud at a time inside the call, results unchanged, and counted as such: gicp_cov_jacobi_svd = 2 (upstream order,
 // gicp_cov_ordered.hip) and the per-query walk (DGS_KNN_LEAF=0, DGS_KNN_LEAF_WIDE=0 for wide k).
@@ -27,6 +27,8 @@
 #include "knn_leaf.h"
 #include "nn_group.h"
 #include "pg_cov.h"
+#include "seg_device.h"
+#include "seg_table.h"
 
 namespace dgs {
 
@@ -43,38 +45,38 @@ struct CovBatchEntry {
 };
 static_assert(sizeof(CovBatchEntry) == 96, "one entry is six 16-byte scalar loads");
 
-// (cov_batch_find, the bisection of the array of first workgroups: knn_leaf.h, shared with prefilter_batch.hip)
+// (seg_find, the bisection of the array of first workgroups: seg_device.h)
 // ---- the search: gicp_knn_leaf_kernel / gicp_knn_leaf_wide_kernel over the chunk, their launch bounds
 __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void cov_knn_batch_kernel(const CovBatchEntry* __restrict__ tab, const int* __restrict__ first, const int m, const int k,
                                                                               int* __restrict__ stats) {
-  const CovBatchEntry e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const CovBatchEntry e = tab[seg_find(first, m, (int)blockIdx.x)];
   gicp_knn_leaf_body<kKnnSlots>(e.b, e.n, k, e.parts, e.nbr, stats, (int)blockIdx.x - e.knn_blk0);
 }
 __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void cov_knn_batch_wide_kernel(const CovBatchEntry* __restrict__ tab, const int* __restrict__ first, const int m,
                                                                                    const int k, int* __restrict__ stats) {
-  const CovBatchEntry e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const CovBatchEntry e = tab[seg_find(first, m, (int)blockIdx.x)];
   gicp_knn_leaf_body<kKnnSlotsWide>(e.b, e.n, k, e.parts, e.nbr, stats, (int)blockIdx.x - e.knn_blk0);
 }
 
 // ---- FAST_GICP / FAST_VGICP: gicp_cov_from_knn_kernel / gicp_cov_from_knn_wide_kernel over the chunk
 __global__ __launch_bounds__(kBlock) void cov_fast_batch_kernel(const CovBatchEntry* __restrict__ tab, const int* __restrict__ first, const int m, const int k, const int method) {
-  const CovBatchEntry e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const CovBatchEntry e = tab[seg_find(first, m, (int)blockIdx.x)];
   gicp_cov_from_knn_body<kKnnSlots>(e.b, e.pts, e.n, k, method, e.nbr, e.out, (int)blockIdx.x - e.cov_blk0);
 }
 __global__ __launch_bounds__(kBlock) void cov_fast_batch_wide_kernel(const CovBatchEntry* __restrict__ tab, const int* __restrict__ first, const int m, const int k,
                                                                      const int method) {
-  const CovBatchEntry e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const CovBatchEntry e = tab[seg_find(first, m, (int)blockIdx.x)];
   gicp_cov_from_knn_body<kKnnSlotsWide>(e.b, e.pts, e.n, k, method, e.nbr, e.out, (int)blockIdx.x - e.cov_blk0);
 }
 
 // ---- GICP_HIP: pg_cov_kernel / pg_cov_wide_kernel over the chunk
 __global__ __launch_bounds__(kBlock) void cov_pcl_batch_kernel(const CovBatchEntry* __restrict__ tab, const int* __restrict__ first, const int m, const int k, const double eps) {
-  const CovBatchEntry e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const CovBatchEntry e = tab[seg_find(first, m, (int)blockIdx.x)];
   pg_cov_body(e.b, e.pts, e.n, k, eps, e.nbr, e.out, (int)blockIdx.x - e.cov_blk0);
 }
 __global__ __launch_bounds__(kPgWideBlock) void cov_pcl_batch_wide_kernel(const CovBatchEntry* __restrict__ tab, const int* __restrict__ first, const int m, const int k,
                                                                           const double eps) {
-  const CovBatchEntry e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const CovBatchEntry e = tab[seg_find(first, m, (int)blockIdx.x)];
   pg_cov_wide_body(e.b, e.pts, e.n, k, eps, e.nbr, e.out, (int)blockIdx.x - e.cov_blk0);
 }
 
@@ -82,8 +84,6 @@ __global__ __launch_bounds__(kPgWideBlock) void cov_pcl_batch_wide_kernel(const 
 // counts8 of the last pass: [0] kernel launches of the pass, [1] host waits, [2] clouds listed, [3] clouds covered, [4] clouds whose cache
 // was valid, [5] chunks, [6] clouds served by a per-cloud fallback, [7] indices built (by the caller that builds them: cloud_build_covariances,
 // the align_pairs paths).
-static size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
-
 int ensure_covariances(dgs_handle* h, int n, CloudState* const* clouds, int kind) {
   CbScratch& S = h->cb;
   std::fill(S.counts8, S.counts8 + 8, 0);
@@ -135,38 +135,24 @@ int ensure_covariances(dgs_handle* h, int n, CloudState* const* clouds, int kind
   DGS_HIP_TRY(h, h->knn_nbr.reserve((size_t)P.max_chunk_points * width));
   DGS_HIP_TRY(h, h->knn_stats.reserve(8));
   // the tables of all chunks, back to back: entries | first search workgroups (count + 1) | first covariance workgroups (count + 1)
-  struct Section { size_t entries, knn_first, cov_first, end; };
-  std::vector<Section> sec(P.chunks.size());
-  size_t bytes = 0;
-  for (size_t c = 0; c < P.chunks.size(); c++) {
-    const size_t cnt = (size_t)P.chunks[c].count;
-    sec[c].entries = bytes;
-    sec[c].knn_first = sec[c].entries + cnt * sizeof(CovBatchEntry);
-    sec[c].cov_first = sec[c].knn_first + (cnt + 1) * sizeof(int);
-    sec[c].end = sec[c].cov_first + (cnt + 1) * sizeof(int);
-    bytes = align64(sec[c].end);
-  }
+  std::vector<segtab::ChunkTable> sec(P.chunks.size());
+  segtab::Layout L;
+  for (size_t c = 0; c < P.chunks.size(); c++) sec[c] = segtab::chunk_table(L, (size_t)P.chunks[c].count, sizeof(CovBatchEntry));
+  const size_t bytes = L.end;
   DGS_HIP_TRY(h, S.tables.reserve(bytes));
-  if (!S.ev_stage) DGS_HIP_TRY(h, hipEventCreateWithFlags(&S.ev_stage, hipEventDisableTiming));
-  if (S.stage_pending && hipEventQuery(S.ev_stage) != hipSuccess) {
-    DGS_HIP_TRY(h, hipEventSynchronize(S.ev_stage));
-    S.counts8[1]++;
-  }
-  S.stage_pending = false;
-  if (bytes > S.stage_bytes) {
-    if (S.stage) (void)hipHostFree(S.stage);
-    S.stage = nullptr;
-    S.stage_bytes = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    DGS_HIP_TRY(h, hipHostMalloc(&S.stage, want, hipHostMallocDefault));
-    S.stage_bytes = want;
-  }
-  char* stage = static_cast<char*>(S.stage);
+  bool waited = false;
+  DGS_HIP_TRY(h, S.stage.wait_if_in_flight(&waited));
+  if (waited) S.counts8[1]++;
+  DGS_HIP_TRY(h, S.stage.reserve(bytes));
+  char* stage = S.stage.at(0);
   for (size_t c = 0; c < P.chunks.size(); c++) {
     const covplan::Chunk& ch = P.chunks[c];
+    const covplan::Item* items = P.items.data() + ch.first;
     CovBatchEntry* tab = reinterpret_cast<CovBatchEntry*>(stage + sec[c].entries);
-    int* knn_first = reinterpret_cast<int*>(stage + sec[c].knn_first);
-    int* cov_first = reinterpret_cast<int*>(stage + sec[c].cov_first);
+    const std::vector<int> knn_first = segtab::first_array(items, (size_t)ch.count, &covplan::Item::knn_blk0, ch.knn_blocks);
+    const std::vector<int> cov_first = segtab::first_array(items, (size_t)ch.count, &covplan::Item::cov_blk0, ch.cov_blocks);
+    std::memcpy(stage + sec[c].knn_first, knn_first.data(), knn_first.size() * sizeof(int));
+    std::memcpy(stage + sec[c].cov_first, cov_first.data(), cov_first.size() * sizeof(int));
     for (int j = 0; j < ch.count; j++) {
       const covplan::Item& it = P.items[(size_t)ch.first + j];
       CloudState& cs = *clouds[it.input];
@@ -179,11 +165,7 @@ int ensure_covariances(dgs_handle* h, int n, CloudState* const* clouds, int kind
       tab[j].parts = it.parts;
       tab[j].knn_blk0 = it.knn_blk0;
       tab[j].cov_blk0 = it.cov_blk0;
-      knn_first[j] = it.knn_blk0;
-      cov_first[j] = it.cov_blk0;
     }
-    knn_first[ch.count] = ch.knn_blocks;
-    cov_first[ch.count] = ch.cov_blocks;
   }
   const int cov_method = h->prm.gicp_regularization | (h->prm.gicp_cov_jacobi_svd ? 0x100 : 0);
   const double eps = h->pg_opt.gicp_epsilon;
@@ -192,10 +174,7 @@ int ensure_covariances(dgs_handle* h, int n, CloudState* const* clouds, int kind
     const covplan::Chunk& ch = P.chunks[c];
     unsigned char* dev = S.tables.ptr + sec[c].entries;
     DGS_HIP_TRY(h, hipMemcpyAsync(dev, stage + sec[c].entries, sec[c].end - sec[c].entries, hipMemcpyHostToDevice, st));
-    if (c + 1 == P.chunks.size()) {
-      DGS_HIP_TRY(h, hipEventRecord(S.ev_stage, st));
-      S.stage_pending = true;
-    }
+    if (c + 1 == P.chunks.size()) DGS_HIP_TRY(h, S.stage.mark(st));
     const CovBatchEntry* tab = reinterpret_cast<const CovBatchEntry*>(dev);
     const int* knn_first = reinterpret_cast<const int*>(S.tables.ptr + sec[c].knn_first);
     const int* cov_first = reinterpret_cast<const int*>(S.tables.ptr + sec[c].cov_first);
@@ -241,25 +220,19 @@ int cloud_build_covariances(dgs_handle* h, int n, dgs_cloud* const* clouds) {
     return DGS_ERR_UNSUPPORTED;
   }
   if (n == 0) return DGS_OK;
-  int rc = fitness_batch_build_indices(h, n, clouds);
+  StageCounts build;
+  int rc = fitness_batch_build_indices(h, n, clouds, &build);
   if (rc) return rc;
-  const int64_t built = h->fb.counts8[3];
   std::vector<CloudState*> cs((size_t)n);
   for (int i = 0; i < n; i++) cs[i] = &clouds[i]->st;
   rc = ensure_covariances(h, n, cs.data(), h->prm.method == DGS_METHOD_PCL_GICP ? covplan::kPcl : covplan::kFast);
-  S.counts8[7] = built;
+  S.counts8[7] = build.built;
   return rc;
 }
 
 void cov_batch_release(dgs_handle* h) {
-  CbScratch& S = h->cb;
-  S.tables.release();
-  if (S.stage) (void)hipHostFree(S.stage);
-  S.stage = nullptr;
-  S.stage_bytes = 0;
-  if (S.ev_stage) (void)hipEventDestroy(S.ev_stage);
-  S.ev_stage = nullptr;
-  S.stage_pending = false;
+  h->cb.tables.release();
+  h->cb.stage.release();
 }
 
 }  // namespace dgs

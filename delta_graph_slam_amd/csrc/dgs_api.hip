@@ -31,6 +31,18 @@ int ensure_pinned(dgs_handle* h, size_t bytes) {
   return DGS_OK;
 }
 
+int stage_host_inputs(dgs_handle* h, DevBuf<float4>& slab, int n, const float* const* inputs, const int64_t* sizes, const float4** d_in) {
+  int64_t total = 0, off = 0;
+  for (int i = 0; i < n; i++) total += sizes[i];
+  if (total > 0) DGS_HIP_TRY(h, slab.reserve((size_t)total));
+  for (int i = 0; i < n; i++) {   // an empty input stands where its successor does and is never read
+    d_in[i] = slab.ptr + off;
+    if (sizes[i] > 0) DGS_HIP_TRY(h, hipMemcpyAsync(slab.ptr + off, inputs[i], (size_t)sizes[i] * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    off += sizes[i];
+  }
+  return DGS_OK;
+}
+
 int ensure_poll_events(dgs_handle* h) {
   for (int k = 0; k < 2; k++)
     if (!h->ev_poll[k]) DGS_HIP_TRY(h, hipEventCreateWithFlags(&h->ev_poll[k], hipEventDisableTiming));
@@ -922,7 +934,6 @@ int dgs_align_batch(dgs_handle* h, int32_t n, const float* const* sources, const
   // stage sources on the device when they come from the host (one contiguous slab, kept by the handle between calls)
   std::vector<const float4*> ptrs(n);
   std::vector<int> sz(n);
-  DevBuf<float4>& slab = h->batch_slab;
   int64_t total = 0;
   for (int i = 0; i < n; i++) {
     if (sizes[i] < 0 || sizes[i] > INT32_MAX || (sizes[i] > 0 && !sources[i])) return DGS_ERR_INVALID_ARGUMENT;
@@ -930,13 +941,7 @@ int dgs_align_batch(dgs_handle* h, int32_t n, const float* const* sources, const
     total += sizes[i];
   }
   if (!on_device) {
-    DGS_HIP_TRY(h, slab.reserve((size_t)std::max<int64_t>(total, 1)));
-    int64_t off = 0;
-    for (int i = 0; i < n; i++) {
-      ptrs[i] = slab.ptr + off;
-      if (sz[i]) DGS_HIP_TRY(h, hipMemcpyAsync(slab.ptr + off, sources[i], (size_t)sz[i] * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-      off += sz[i];
-    }
+    if (int rc = stage_host_inputs(h, h->batch_slab, n, sources, sizes, ptrs.data())) return rc;
   } else {
     for (int i = 0; i < n; i++) ptrs[i] = reinterpret_cast<const float4*>(sources[i]);
   }

@@ -9,7 +9,7 @@
 // walks' a moment later), and a tick costs one batched index build for the clouds that have none, ONE walk launch over all edges, one
 // closing launch, one download and one host wait.
 //
-// Walk.  A workgroup is one slice of one edge: it finds its edge in a prefix table of rows (wave-uniform, scalar loads), reads the
+// Walk.  A workgroup is one slice of one edge: it finds its edge in a prefix table of rows (seg_find: wave-uniform, scalar loads), reads the
 // edge's BvhView, source, size and transform from the edge table and then does exactly what nn_fitness_kernel does -- the same
 // nn_query_group<false> / nn_warm_bound_round calls (nn_group.h), so a distance is the very float the single call produces.  Index
 // depths differ between edges, never inside a workgroup.  FIXED SLICES: the rows of an edge and the stretch each wave walks are a
@@ -30,12 +30,13 @@
 
 #include "handle.h"
 #include "nn_group.h"
+#include "seg_device.h"
+#include "seg_table.h"
 
 namespace dgs {
 
 constexpr int kFbRowQueries = 128;   // cloud2 points per partial row: 4 waves x 4 rounds of 8 adjacent queries (warm bounds from round 2 on)
 constexpr int kFbMaxRows = 512;      // ... up to this many rows; beyond 65,536 points the stretches grow instead
-constexpr int kFbMmBlocks = 64;      // partial boxes per cloud = lanes of the wave that folds them
 
 inline int fb_rows_of(const int n) { return n <= 0 ? 0 : std::max(1, std::min(kFbMaxRows, (n + kFbRowQueries - 1) / kFbRowQueries)); }
 
@@ -56,15 +57,15 @@ struct FbSeg {
 };
 
 // ---- walk --------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void fb_walk_kernel(const int* __restrict__ row0s, const FbEdge* __restrict__ edges, const int n_edges,
-                                                         const float max_range, double* __restrict__ rows) {
-  // the edge of this workgroup: row0s[e] <= blockIdx.x < row0s[e + 1] (edges without rows have no workgroup)
-  int lo = 0, hi = n_edges;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (row0s[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-  }
-  const FbEdge* __restrict__ E = edges + __builtin_amdgcn_readfirstlane(lo);
+// INLIER false: the sum and the number of the squared NN distances <= bound (PCL compares the SQUARED distance with max_range), rows
+// {sum, used}.  INLIER true: the points of cloud2 whose squared NN distance is strictly below `bound` (the nearestKSearch loop of
+// publish_scan_matching_status; nn_fitness_kernel's `best < inlier_sq`), rows {inliers, 0}: counts are integers, so any order of the
+// sums gives the same total.
+template <bool INLIER>
+__device__ __forceinline__ void fb_walk_body(const int* __restrict__ row0s, const FbEdge* __restrict__ edges, const int n_edges, const float bound,
+                                             double* __restrict__ rows) {
+  // the edge of this workgroup: row0s[e] <= blockIdx.x < row0s[e + 1] (edges without rows have no workgroup: seg_find passes them by)
+  const FbEdge* __restrict__ E = edges + __builtin_amdgcn_readfirstlane(seg_find(row0s, n_edges, (int)blockIdx.x));
   const BvhView b = E->b;
   const float4* __restrict__ src = E->src;
   const int n = E->n, n_rows = E->rows, slice = (int)blockIdx.x - E->row0;
@@ -94,70 +95,39 @@ __global__ __launch_bounds__(kBlock) void fb_walk_kernel(const int* __restrict__
     px = x; py = y; pz = z;
     if (alive && sub == 0) {
       if (bi == 0x7FFFFFFF) best = INFINITY;  // nothing found (non-finite query): as the unbounded search reports it
-      if (best <= max_range) {  // PCL compares the SQUARED distance with max_range
+      if constexpr (INLIER) {
+        if (best < bound) s += 1.0;
+      } else if (best <= bound) {
         s += (double)best;
         c += 1.0;
       }
     }
   }
-  __shared__ double sm[kBlock / kWave][2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  s = wave_sum(s); c = wave_sum(c);
-  if (lane == 0) { sm[wave][0] = s; sm[wave][1] = c; }
-  __syncthreads();
-  if (threadIdx.x < 2) rows[(size_t)blockIdx.x * 2 + threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+  if constexpr (INLIER) {
+    __shared__ double sm[kBlock / kWave];
+    s = wave_sum(s);
+    if (lane == 0) sm[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      rows[(size_t)blockIdx.x * 2] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+      rows[(size_t)blockIdx.x * 2 + 1] = 0.0;
+    }
+  } else {
+    __shared__ double sm[kBlock / kWave][2];
+    s = wave_sum(s); c = wave_sum(c);
+    if (lane == 0) { sm[wave][0] = s; sm[wave][1] = c; }
+    __syncthreads();
+    if (threadIdx.x < 2) rows[(size_t)blockIdx.x * 2 + threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+  }
 }
-
-// The same walk counting, per row, the points of cloud2 whose squared NN distance is strictly below `inlier_sq` (the nearestKSearch loop
-// of publish_scan_matching_status; nn_fitness_kernel's `best < inlier_sq`).  A kernel of its own: fb_walk_kernel compiles to what it did.
-// Rows hold {inliers, 0}: counts are integers, so any order of the sums gives the same total.
+__global__ __launch_bounds__(kBlock) void fb_walk_kernel(const int* __restrict__ row0s, const FbEdge* __restrict__ edges, const int n_edges,
+                                                         const float max_range, double* __restrict__ rows) {
+  fb_walk_body<false>(row0s, edges, n_edges, max_range, rows);
+}
 __global__ __launch_bounds__(kBlock) void fb_inlier_kernel(const int* __restrict__ row0s, const FbEdge* __restrict__ edges, const int n_edges,
                                                            const float inlier_sq, double* __restrict__ rows) {
-  int lo = 0, hi = n_edges;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (row0s[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-  }
-  const FbEdge* __restrict__ E = edges + __builtin_amdgcn_readfirstlane(lo);
-  const BvhView b = E->b;
-  const float4* __restrict__ src = E->src;
-  const int n = E->n, n_rows = E->rows, slice = (int)blockIdx.x - E->row0;
-  const float t00 = E->T[0], t10 = E->T[1], t20 = E->T[2], t01 = E->T[4], t11 = E->T[5], t21 = E->T[6], t02 = E->T[8], t12 = E->T[9], t22 = E->T[10],
-              t03 = E->T[12], t13 = E->T[13], t23 = E->T[14];
-  double inl = 0.0;
-  constexpr int QPB = kBlock / 8;
-  const int sub = threadIdx.x & 7;
-  const int run = (n + n_rows * QPB - 1) / (n_rows * QPB);
-  const int first = (slice * (kBlock / kWave) + (threadIdx.x >> 6)) * (8 * run) + ((threadIdx.x & 63) >> 3);
-  float px = 0.f, py = 0.f, pz = 0.f, prev_best = INFINITY;
-  bool prev_found = false;
-  for (int r = 0; r < run; r++) {
-    const int i = first + r * 8;
-    const bool alive = i < n;
-    const float4 p = alive ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float x = affine_row_rn(t00, t01, t02, t03, p.x, p.y, p.z);
-    const float y = affine_row_rn(t10, t11, t12, t13, p.x, p.y, p.z);
-    const float z = affine_row_rn(t20, t21, t22, t23, p.x, p.y, p.z);
-    float best;
-    int bi;
-    nn_query_group<false>(b, x, y, z, alive, nn_warm_bound_round(prev_best, prev_found, x, y, z, px, py, pz), best, bi);
-    prev_found = alive && bi != 0x7FFFFFFF;
-    prev_best = best;
-    px = x; py = y; pz = z;
-    if (alive && sub == 0) {
-      if (bi == 0x7FFFFFFF) best = INFINITY;  // nothing found (non-finite query)
-      if (best < inlier_sq) inl += 1.0;
-    }
-  }
-  __shared__ double sm[kBlock / kWave];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  inl = wave_sum(inl);
-  if (lane == 0) sm[wave] = inl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    rows[(size_t)blockIdx.x * 2] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-    rows[(size_t)blockIdx.x * 2 + 1] = 0.0;
-  }
+  fb_walk_body<true>(row0s, edges, n_edges, inlier_sq, rows);
 }
 
 // one wave per edge: lane l sums the edge's rows l, l + 64, ... in order, then the lanes are summed in a fixed order
@@ -179,55 +149,12 @@ __global__ __launch_bounds__(kWave) void fb_close_kernel(const int* __restrict__
 }
 
 // ---- batched Hilbert index build ---------------------------------------------------------------------------------------------
-// blockIdx.y = cloud.  Boxes of the finite points (minmax_kernel / minmax_final_kernel of ndt_voxel.hip per segment; min and max
-// are exact, so the order of the folds does not show in the result).
+// blockIdx.y = cloud.  Boxes of the finite points: the per-segment bodies of seg_device.h over this file's records.
 __global__ __launch_bounds__(kBlock) void fb_minmax_kernel(const FbSeg* __restrict__ segs, float* __restrict__ partial) {
   const FbSeg& S = segs[blockIdx.y];
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < S.n; i += kFbMmBlocks * kBlock) {
-    const float4 p = S.pts[i];
-    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-      mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-      mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-    }
-  }
-  __shared__ float sm[kBlock / kWave][6];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_down(mn[a], off, 64));
-      mx[a] = fmaxf(mx[a], __shfl_down(mx[a], off, 64));
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    for (int a = 0; a < 3; a++) { sm[wave][a] = mn[a]; sm[wave][3 + a] = mx[a]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float v = sm[0][threadIdx.x];
-    for (int w = 1; w < kBlock / kWave; w++) v = (threadIdx.x < 3) ? fminf(v, sm[w][threadIdx.x]) : fmaxf(v, sm[w][threadIdx.x]);
-    partial[((size_t)blockIdx.y * kFbMmBlocks + blockIdx.x) * 6 + threadIdx.x] = v;
-  }
+  seg_box_partial_body(S.pts, S.n, partial);
 }
-
-__global__ __launch_bounds__(kWave) void fb_minmax_final_kernel(const float* __restrict__ partial, float* __restrict__ boxes) {
-  static_assert(kFbMmBlocks == kWave, "one partial box per lane");
-  const float* p = partial + ((size_t)blockIdx.x * kFbMmBlocks + threadIdx.x) * 6;
-  float v[6];
-#pragma unroll
-  for (int a = 0; a < 6; a++) v[a] = p[a];
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float o = __shfl_down(v[a], off, 64);
-      v[a] = (a < 3) ? fminf(v[a], o) : fmaxf(v[a], o);
-    }
-  }
-  if (threadIdx.x == 0)
-    for (int a = 0; a < 6; a++) boxes[(size_t)blockIdx.x * 6 + a] = v[a];
-}
+__global__ __launch_bounds__(kWave) void fb_minmax_final_kernel(const float* __restrict__ partial, float* __restrict__ boxes) { seg_box_final_body(partial, boxes); }
 
 // hilbert_key_kernel (nn_bvh.hip) per segment, the cloud's number above the 30 key bits
 __global__ __launch_bounds__(kBlock) void fb_key_kernel(const FbSeg* __restrict__ segs, const float* __restrict__ boxes, unsigned long long* __restrict__ keys,
@@ -297,27 +224,27 @@ __global__ __launch_bounds__(kBlock) void fb_boxes_kernel(const FbSeg* __restric
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-static int fb_host_reserve(dgs_handle* h, void*& p, size_t& cap, size_t bytes) {
-  if (bytes <= cap) return DGS_OK;
-  if (p) (void)hipHostFree(p);
-  p = nullptr;
-  cap = 0;
-  const size_t want = bytes + bytes / 4 + 4096;
-  DGS_HIP_TRY(h, hipHostMalloc(&p, want, hipHostMallocDefault));
-  cap = want;
-  return DGS_OK;
-}
-
-int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, bool reset_counts) {
+// the build of dgs_cloud objects' indices inside a call that reports in FbScratch::counts8 (zeroed by the caller)
+static int fb_build_counted(dgs_handle* h, int n, dgs_cloud* const* clouds, StageCounts* did) {
   std::vector<CloudState*> states((size_t)n);
   for (int i = 0; i < n; i++) states[i] = &clouds[i]->st;
-  return fitness_batch_build_state_indices(h, n, states.data(), reset_counts);
+  StageCounts sc;
+  const int rc = fitness_batch_build_state_indices(h, n, states.data(), &sc);
+  h->fb.counts8[0] += sc.launches;
+  h->fb.counts8[1] += sc.waits;
+  h->fb.counts8[3] += sc.built;
+  if (did) *did = sc;
+  return rc;
+}
+
+int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, StageCounts* did) {
+  std::fill(h->fb.counts8, h->fb.counts8 + 8, 0);
+  return fb_build_counted(h, n, clouds, did);
 }
 
 // The build over cloud states, whoever owns them: dgs_cloud objects (above) or a handle's own stage clouds (prefilter_batch.hip).
-int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* clouds, bool reset_counts) {
+int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* clouds, StageCounts* sink) {
   FbScratch& F = h->fb;
-  if (reset_counts) std::fill(F.counts8, F.counts8 + 8, 0);
   if (side_join(h) != DGS_OK) return DGS_ERR_HIP;   // an index being built on the side stream
   std::vector<CloudState*> todo;
   for (int i = 0; i < n; i++) {
@@ -362,7 +289,7 @@ int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* c
     off += (int)C.n;
   }
   DGS_HIP_TRY(h, F.segs.reserve((size_t)M));
-  DGS_HIP_TRY(h, F.mm.reserve((size_t)M * (kFbMmBlocks + 1) * 6));
+  DGS_HIP_TRY(h, F.mm.reserve((size_t)M * (kSegBoxBlocks + 1) * 6));
   DGS_HIP_TRY(h, F.keys.reserve((size_t)total));
   DGS_HIP_TRY(h, F.keys_alt.reserve((size_t)total));
   DGS_HIP_TRY(h, F.vals.reserve((size_t)total));
@@ -373,46 +300,41 @@ int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* c
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, F.keys.ptr, F.keys_alt.ptr, F.vals.ptr, F.vals_alt.ptr, (int)total, 0, 30 + seg_bits, st);
   DGS_HIP_TRY(h, h->cub_temp.reserve(tb + 256));
   // the table travels from a pinned block of its own, which the previous build's copy may still be reading
-  if (!F.ev_bstage) DGS_HIP_TRY(h, hipEventCreateWithFlags(&F.ev_bstage, hipEventDisableTiming));
-  if (F.bstage_pending && hipEventQuery(F.ev_bstage) != hipSuccess) {
-    DGS_HIP_TRY(h, hipEventSynchronize(F.ev_bstage));
-    F.counts8[1]++;
-  }
-  F.bstage_pending = false;
-  if (fb_host_reserve(h, F.bstage, F.bstage_bytes, sizeof(FbSeg) * (size_t)M) != DGS_OK) return DGS_ERR_HIP;
-  std::memcpy(F.bstage, segs.data(), sizeof(FbSeg) * (size_t)M);
-  DGS_HIP_TRY(h, hipMemcpyAsync(F.segs.ptr, F.bstage, sizeof(FbSeg) * (size_t)M, hipMemcpyHostToDevice, st));
-  DGS_HIP_TRY(h, hipEventRecord(F.ev_bstage, st));
-  F.bstage_pending = true;
-  float* boxes = F.mm.ptr + (size_t)M * kFbMmBlocks * 6;
-  hipLaunchKernelGGL(fb_minmax_kernel, dim3(kFbMmBlocks, M), dim3(kBlock), 0, st, F.segs.ptr, F.mm.ptr);
+  bool waited = false;
+  DGS_HIP_TRY(h, F.bstage.wait_if_in_flight(&waited));
+  if (waited) sink->waits++;
+  DGS_HIP_TRY(h, F.bstage.reserve(sizeof(FbSeg) * (size_t)M));
+  std::memcpy(F.bstage.ptr, segs.data(), sizeof(FbSeg) * (size_t)M);
+  DGS_HIP_TRY(h, hipMemcpyAsync(F.segs.ptr, F.bstage.ptr, sizeof(FbSeg) * (size_t)M, hipMemcpyHostToDevice, st));
+  DGS_HIP_TRY(h, F.bstage.mark(st));
+  float* boxes = F.mm.ptr + (size_t)M * kSegBoxBlocks * 6;
+  hipLaunchKernelGGL(fb_minmax_kernel, dim3(kSegBoxBlocks, M), dim3(kBlock), 0, st, F.segs.ptr, F.mm.ptr);
   hipLaunchKernelGGL(fb_minmax_final_kernel, dim3(M), dim3(kWave), 0, st, F.mm.ptr, boxes);
   hipLaunchKernelGGL(fb_key_kernel, dim3((max_n + kBlock - 1) / kBlock, M), dim3(kBlock), 0, st, F.segs.ptr, boxes, F.keys.ptr, F.vals.ptr);
   tb = h->cub_temp.cap;
   DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, F.keys.ptr, F.keys_alt.ptr, F.vals.ptr, F.vals_alt.ptr, (int)total, 0, 30 + seg_bits, st));
   hipLaunchKernelGGL(fb_gather_kernel, dim3((max_pad + kBlock - 1) / kBlock, M), dim3(kBlock), 0, st, F.segs.ptr, F.vals_alt.ptr);
-  F.counts8[0] += 5;
+  sink->launches += 5;
   // leaf slots first, then every internal level bottom-up (the root's own box is never needed)
   for (int step = 0; step < max_depth; step++) {
     const int64_t count = (int64_t)1 << (3 * (max_depth - step));
     hipLaunchKernelGGL(fb_boxes_kernel, dim3((unsigned)((count + kBlock - 1) / kBlock), M), dim3(kBlock), 0, st, F.segs.ptr, step);
-    F.counts8[0]++;
+    sink->launches++;
   }
   DGS_HIP_TRY(h, hipGetLastError());
   for (CloudState* c : todo) {
     c->bvh.kd = false;
     c->bvh.valid = true;
   }
-  F.counts8[3] += M;
+  sink->built += M;
   return DGS_OK;
 }
 
 int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_range,
                          double* scores, int64_t* used) {
-  FbScratch& F = h->fb;
-  std::fill(F.counts8, F.counts8 + 8, 0);
+  std::fill(h->fb.counts8, h->fb.counts8 + 8, 0);
   if (n_edges == 0) return DGS_OK;
-  int rc = fitness_batch_build_indices(h, n_edges, cloud1s, false);
+  int rc = fb_build_counted(h, n_edges, cloud1s, nullptr);
   if (rc != DGS_OK) return rc;
   std::vector<FbEdgeIn> in((size_t)n_edges);
   for (int e = 0; e < n_edges; e++)
@@ -428,12 +350,14 @@ static int fb_run_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, bool inl
   FbScratch& F = h->fb;
   F.counts8[2] = n_edges;
   // one pinned block: [row prefix | edge table] up, [sum, used per edge] down
-  const size_t pre_bytes = (((size_t)n_edges + 1) * sizeof(int) + 127) & ~(size_t)127;
-  const size_t up_bytes = pre_bytes + (size_t)n_edges * sizeof(FbEdge), down_bytes = (size_t)n_edges * 2 * sizeof(double);
-  if (fb_host_reserve(h, F.stage, F.stage_bytes, up_bytes + down_bytes) != DGS_OK) return DGS_ERR_HIP;
-  int* row0s = reinterpret_cast<int*>(F.stage);
-  FbEdge* edges = reinterpret_cast<FbEdge*>(reinterpret_cast<char*>(F.stage) + pre_bytes);
-  double* down = reinterpret_cast<double*>(reinterpret_cast<char*>(F.stage) + up_bytes);
+  segtab::Layout L;
+  L.take(((size_t)n_edges + 1) * sizeof(int), 128);
+  const size_t pre_bytes = L.take((size_t)n_edges * sizeof(FbEdge), 128), up_bytes = L.end, down_bytes = (size_t)n_edges * 2 * sizeof(double);
+  L.take(down_bytes, alignof(double));   // at up_bytes: a multiple of 128
+  DGS_HIP_TRY(h, F.stage.reserve(L.end));
+  int* row0s = reinterpret_cast<int*>(F.stage.ptr);
+  FbEdge* edges = reinterpret_cast<FbEdge*>(F.stage.at(pre_bytes));
+  double* down = reinterpret_cast<double*>(F.stage.at(up_bytes));
   int64_t total_rows = 0;
   for (int e = 0; e < n_edges; e++) {
     FbEdge& E = edges[e];
@@ -457,7 +381,7 @@ static int fb_run_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, bool inl
     DGS_HIP_TRY(h, F.tab.reserve(up_bytes));
     DGS_HIP_TRY(h, F.rows.reserve((size_t)total_rows * 2 + (size_t)n_edges * 2));
     double* d_out = F.rows.ptr + (size_t)total_rows * 2;
-    DGS_HIP_TRY(h, hipMemcpyAsync(F.tab.ptr, F.stage, up_bytes, hipMemcpyHostToDevice, st));
+    DGS_HIP_TRY(h, hipMemcpyAsync(F.tab.ptr, F.stage.ptr, up_bytes, hipMemcpyHostToDevice, st));
     const int* d_row0s = reinterpret_cast<const int*>(F.tab.ptr);
     const FbEdge* d_edges = reinterpret_cast<const FbEdge*>(F.tab.ptr + pre_bytes);
     // PCL's comparison is float(sq_dist) <= double(max_range); clamp so DBL_MAX keeps every finite distance (nn_fitness_enqueue clamps the
@@ -469,7 +393,7 @@ static int fb_run_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, bool inl
     DGS_HIP_TRY(h, hipMemcpyAsync(down, d_out, down_bytes, hipMemcpyDeviceToHost, st));
     DGS_HIP_TRY(h, hipStreamSynchronize(st));
     F.counts8[1]++;
-    F.bstage_pending = false;   // the build's upload went first on the same stream
+    F.bstage.settled();   // the build's upload went first on the same stream
     DGS_HIP_TRY(h, hipGetLastError());
   }
   for (int e = 0; e < n_edges; e++)
@@ -494,10 +418,9 @@ int fitness_batch_edges(dgs_handle* h, int n_edges, const FbEdgeIn* in, double m
 // dgs_calc_inlier_fraction_batch_clouds: missing indices by the batched build, one walk launch over all edges, one closing launch, one wait
 int inlier_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_sq_dist,
                         double* fractions, int64_t* inliers) {
-  FbScratch& F = h->fb;
-  std::fill(F.counts8, F.counts8 + 8, 0);
+  std::fill(h->fb.counts8, h->fb.counts8 + 8, 0);
   if (n_edges == 0) return DGS_OK;
-  int rc = fitness_batch_build_indices(h, n_edges, cloud1s, false);
+  int rc = fb_build_counted(h, n_edges, cloud1s, nullptr);
   if (rc != DGS_OK) return rc;
   std::vector<FbEdgeIn> in((size_t)n_edges);
   for (int e = 0; e < n_edges; e++)
@@ -527,12 +450,7 @@ int fitness_target_edges(dgs_handle* h, int n, const float4* const* srcs, const 
 void fitness_batch_release(dgs_handle* h) {
   FbScratch& F = h->fb;
   F.tab.release(); F.rows.release(); F.segs.release(); F.mm.release(); F.keys.release(); F.keys_alt.release(); F.vals.release(); F.vals_alt.release();
-  if (F.stage) (void)hipHostFree(F.stage);
-  if (F.bstage) (void)hipHostFree(F.bstage);
-  if (F.ev_bstage) (void)hipEventDestroy(F.ev_bstage);
-  F.stage = F.bstage = nullptr;
-  F.stage_bytes = F.bstage_bytes = 0;
-  F.ev_bstage = nullptr;
+  F.stage.release(); F.bstage.release();
 }
 
 }  // namespace dgs

@@ -838,11 +838,11 @@ int gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* co
   // every index that is missing, of targets and sources alike, in ONE batched build (the bits of a single build: fitness_batch.hip)
   std::vector<dgs_cloud*> all(tgts, tgts + n);
   all.insert(all.end(), srcs, srcs + n);
-  int rc = fitness_batch_build_indices(h, 2 * n, all.data());
+  StageCounts build;
+  int rc = fitness_batch_build_indices(h, 2 * n, all.data(), &build);
   if (rc) return rc;
   // the covariances of the distinct targets and of the live pairs' sources in ONE batched pass (cov_batch.hip), cached on the cloud under
   // (k, regularisation): shared with every other path that uses the cloud
-  const int64_t indices_built = h->fb.counts8[3];
   std::vector<CloudState*> cs((size_t)n), need;
   for (dgs_cloud* c : uniq) need.push_back(&c->st);
   for (int i = 0; i < n; i++) {
@@ -850,7 +850,7 @@ int gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud* co
     if (tgt_of[i] >= 0 && cs[i]->n > 0) need.push_back(cs[i]);
   }
   rc = ensure_covariances(h, (int)need.size(), need.data(), covplan::kFast);
-  h->cb.counts8[7] = indices_built;
+  h->cb.counts8[7] = build.built;
   if (rc) return rc;
   const std::vector<double> x0 = gicp_guess_rows(n, guesses16);
   // the target table travels from the pinned block, behind the batch's own staging (gicp_start sizes the block for that alone)

@@ -210,8 +210,7 @@ struct LeScratch {
   DevBuf<int> blk;                     // edges per workgroup of pairs, scanned in place; [workgroups] = all edges
   DevBuf<int> eoff;                    // first edge per segment, n_seg + 1 entries
   DevBuf<double> edges;                // 9 doubles per edge, all segments back to back
-  void* stage = nullptr;               // pinned: the segment table's upload, behind it the edge offsets' download
-  size_t stage_bytes = 0;
+  PinnedBlock stage;                   // the segment table's upload, behind it the edge offsets' download
   std::vector<int> eoff_host;          // of the last extraction
   int64_t counts4[4] = {0, 0, 0, 0};   // launches, host waits, pairs i < j, edges
 };
@@ -258,16 +257,12 @@ struct FbSeg;
 struct FbScratch {
   DevBuf<unsigned char> tab;           // walk, one upload: the row prefix (n_edges + 1 ints), then the edge table
   DevBuf<double> rows;                 // one partial row {sum, used} per (edge, slice); then {sum, used} per edge
-  void* stage = nullptr;               // pinned: the walk's upload, and behind it the download
-  size_t stage_bytes = 0;
+  PinnedBlock stage;                   // the walk's upload, and behind it the download
   DevBuf<FbSeg> segs;                  // build: per cloud to be indexed, its points, its index arrays and its offsets in the shared arrays
-  DevBuf<float> mm;                    // build: per cloud kFbMmBlocks partial boxes, then the boxes
+  DevBuf<float> mm;                    // build: per cloud kSegBoxBlocks partial boxes, then the boxes
   DevBuf<unsigned long long> keys, keys_alt;   // build: (cloud number << 30) | hilbert30, all clouds back to back
   DevBuf<uint32_t> vals, vals_alt;     // build: index of the point in its own cloud
-  void* bstage = nullptr;              // pinned: the build's upload; not written again before ev_bstage has passed
-  size_t bstage_bytes = 0;
-  hipEvent_t ev_bstage = nullptr;
-  bool bstage_pending = false;
+  PinnedBlock bstage;                  // the build's upload: marked, nobody waits for it
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launches, host waits, edges, indices built, partial rows
 };
 
@@ -300,14 +295,11 @@ struct BcScratch {
 };
 
 // Batched k-NN covariances of resident clouds (cov_batch.hip): the device tables of a pass's chunks, the pinned block they travel from
-// (its own, with an event: the handle's pinned block is rewritten by the batch that follows while this upload may still be in flight),
+// (its own, marked: the handle's pinned block is rewritten by the batch that follows while this upload may still be in flight),
 // and the counts of the last pass.
 struct CbScratch {
   DevBuf<unsigned char> tables;        // per chunk: entries | first search workgroup per cloud | first covariance workgroup per cloud
-  void* stage = nullptr;               // pinned: the tables' upload; not written again before ev_stage has passed
-  size_t stage_bytes = 0;
-  hipEvent_t ev_stage = nullptr;
-  bool stage_pending = false;
+  PinnedBlock stage;                   // the tables' upload: marked, nobody waits for it
   int64_t points_budget = 0;           // DGS_COV_BATCH_POINTS (0: covplan::kCovBatchPoints)
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
@@ -328,8 +320,7 @@ struct PfbScratch {
   DevBuf<float4> normals;              // normal pass (the body writes them)
   DevBuf<float> cov9;
   DevBuf<unsigned char> tables;        // the stage's table: entries | heads | first workgroups | first search workgroups
-  void* stage = nullptr;               // pinned: the table's upload and the totals' download; every stage ends with a host wait
-  size_t stage_bytes = 0;
+  PinnedBlock stage;                   // the table's upload and the totals' download; every stage ends with a host wait
   std::vector<double> stats_host;      // of the last call: {mean, stddev, threshold, points} per scan
   int64_t points_budget = 0;           // DGS_PREFILTER_BATCH_POINTS (0: pfbplan::kBatchPoints)
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -587,6 +578,9 @@ int prof_begin(dgs_handle* h, int kernel_id, hipStream_t st = nullptr);   // st:
 void prof_end(dgs_handle* h, int kernel_id, int slot, hipStream_t st = nullptr);
 void prof_end_counted(dgs_handle* h, int kernel_id, int slot, int count);   // one bracket that stands for `count` passes: its time once, the count advanced by `count`
 int ensure_pinned(dgs_handle* h, size_t bytes);
+// dgs_api.hip: n host inputs (float4 points) into `slab` back to back, on the handle's stream, in order; d_in[i]: where input i stands.
+// Pageable memory: each copy has left the caller's array when it returns.
+int stage_host_inputs(dgs_handle* h, DevBuf<float4>& slab, int n, const float* const* inputs, const int64_t* sizes, const float4** d_in);
 int ensure_poll_events(dgs_handle* h);
 int side_fork(dgs_handle* h);   // side_stream continues from what the main stream has enqueued so far
 int side_join(dgs_handle* h);   // the main stream waits for what side_fork()'s work (no-op when nothing is pending)
@@ -696,9 +690,15 @@ void set_handleless_error(const char* why);
 void building_overlap_release(dgs_handle* h);
 // floor_detection.hip
 void floor_detection_release(dgs_handle* h);
+// What a batched stage that runs inside another call did: the stage adds to the sink its caller hands it, the caller folds the sink
+// into the counts8 of its own call.
+struct StageCounts {
+  int64_t launches = 0, waits = 0, built = 0;   // kernel launches, host waits, indices built
+};
 // fitness_batch.hip
-int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, bool reset_counts = true);
-int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* clouds, bool reset_counts = true);   // the same build over cloud states
+// the batched index build as a call of its own: FbScratch::counts8 reports it (and nothing else); `did` (nullable) receives the same
+int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, StageCounts* did = nullptr);
+int fitness_batch_build_state_indices(dgs_handle* h, int n, CloudState* const* clouds, StageCounts* sink);   // the build over cloud states, inside another call
 int fitness_batch_clouds(dgs_handle* h, int n_edges, dgs_cloud* const* cloud1s, dgs_cloud* const* cloud2s, const float* relposes16, double max_range,
                          double* scores, int64_t* used);
 // one edge of the scorer over plain device arrays: index over cloud1, cloud2's points, the relative pose (column-major, host)
@@ -720,10 +720,10 @@ void building_cloud_release(dgs_handle* h);
 // voxel_batch.hip: inputs filtered (0 NONE, 1 VOXELGRID, 2 APPROX_VOXELGRID) into resident clouds; the caller has checked the arguments
 int cloud_assign_batch(dgs_handle* h, int n, const float* const* inputs, const int64_t* sizes, int on_device, int filter, float leaf, dgs_cloud* const* clouds,
                        int64_t* out_sizes);
-// VOXELGRID of n device inputs into n cloud states by one chain, two host waits (adds to VbScratch::counts8[0..1]); `owners` (nullable):
+// VOXELGRID of n device inputs into n cloud states by one chain, two host waits (added to `sink`); `owners` (nullable):
 // the dgs_cloud objects the states belong to, whose users are detached.  On DGS_ERR_GRID_TOO_LARGE no state has been touched.
 int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64_t* sizes, float leaf, CloudState* const* states, dgs_cloud* const* owners,
-                    int64_t* out_sizes);
+                    int64_t* out_sizes, StageCounts* sink);
 void voxel_batch_release(dgs_handle* h);
 // prefilter_batch.hip
 void prefilter_batch_release(dgs_handle* h);

@@ -10,18 +10,6 @@
 
 namespace dgs {
 
-// A launch over a table of clouds in which every cloud owns whole workgroups (cov_batch.hip, prefilter_batch.hip): the cloud whose
-// workgroups hold `blk` is the largest c with first[c] <= blk (first[0] = 0, ascending, every cloud owns at least one workgroup;
-// blk < first[m]).  Uniform: scalar loads.
-__device__ __forceinline__ int cov_batch_find(const int* __restrict__ first, const int m, const int blk) {
-  int lo = 0, hi = m;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= blk) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // a group's list -> the table: slot s * 8 + sub of the 8-lane group -> nbr[pos * (SLOTS * 8) + slot], -1 = nothing found
 template <int SLOTS>
 __device__ __forceinline__ void knn_write_list(const KnnListT<SLOTS>& L, const int pos, const int sub, const int k, int* __restrict__ nbr) {

@@ -25,6 +25,7 @@
 
 #include "handle.h"
 #include "line_align.h"
+#include "seg_table.h"
 
 namespace dgs {
 
@@ -156,19 +157,17 @@ static_assert(sizeof(la::Edge) == 9 * sizeof(double) && sizeof(dgs_edge_feature)
 // ================================================================================================ host side
 namespace {
 
-inline size_t le_align8(size_t b) { return (b + 7) & ~(size_t)7; }
-inline size_t le_table_bytes(size_t n_seg) { return le_align8(n_seg * sizeof(LeSeg)) + le_align8((n_seg + 1) * sizeof(int)); }
-
-int le_ensure_stage(dgs_handle* h, size_t bytes) {
-  LeScratch& s = h->le;
-  if (bytes <= s.stage_bytes) return DGS_OK;
-  if (s.stage) (void)hipHostFree(s.stage);
-  s.stage = nullptr;
-  s.stage_bytes = 0;
-  const size_t want = bytes + bytes / 4 + 4096;
-  DGS_HIP_TRY(h, hipHostMalloc(&s.stage, want, hipHostMallocDefault));
-  s.stage_bytes = want;
-  return DGS_OK;
+// the pinned block: the segment table | the edge offsets' download (n_seg + 1 ints), both from a multiple of 8 on; L.end is one as well
+struct LeTable {
+  segtab::Layout L;
+  size_t down;
+};
+inline LeTable le_table(size_t n_seg) {
+  LeTable T;
+  T.L.take(n_seg * sizeof(LeSeg), 8);
+  T.down = T.L.take((n_seg + 1) * sizeof(int), 8);
+  T.L.take(0, 8);
+  return T;
 }
 
 }  // namespace
@@ -188,9 +187,10 @@ int line_edges_run(dgs_handle* h, const double* d_lines, const std::vector<LeSeg
   DGS_HIP_TRY(h, s.cnt.reserve((size_t)P));
   DGS_HIP_TRY(h, s.blk.reserve((size_t)nb + 1));
   DGS_HIP_TRY(h, s.eoff.reserve(n_seg + 1));
-  if (le_ensure_stage(h, le_table_bytes(n_seg)) != DGS_OK) return DGS_ERR_HIP;
-  char* up = static_cast<char*>(s.stage);
-  int* down = reinterpret_cast<int*>(up + le_align8(n_seg * sizeof(LeSeg)));
+  const LeTable T = le_table(n_seg);
+  DGS_HIP_TRY(h, s.stage.reserve(T.L.end));
+  char* up = s.stage.at(0);
+  int* down = reinterpret_cast<int*>(s.stage.at(T.down));
   std::memcpy(up, segs.data(), n_seg * sizeof(LeSeg));
   DGS_HIP_TRY(h, hipMemcpyAsync(s.segs.ptr, up, n_seg * sizeof(LeSeg), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(le_count_kernel, dim3((unsigned)nb), dim3(kBlock), 0, h->stream, s.segs.ptr, (int)n_seg, d_lines, P, s.cnt.ptr, s.blk.ptr);
@@ -217,10 +217,7 @@ int line_edges_run(dgs_handle* h, const double* d_lines, const std::vector<LeSeg
 
 void line_edges_release(dgs_handle* h) {
   LeScratch& s = h->le;
-  s.lines.release(); s.segs.release(); s.cnt.release(); s.blk.release(); s.eoff.release(); s.edges.release();
-  if (s.stage) (void)hipHostFree(s.stage);
-  s.stage = nullptr;
-  s.stage_bytes = 0;
+  s.lines.release(); s.segs.release(); s.cnt.release(); s.blk.release(); s.eoff.release(); s.edges.release(); s.stage.release();
   s.eoff_host.clear();
 }
 
@@ -262,11 +259,12 @@ int dgs_line_edge_extraction_batch(dgs_handle* h, const dgs_line_feature* lines,
   LeScratch& s = h->le;
   DGS_HIP_TRY(h, hipSetDevice(h->device));
   // one pinned block: the segment table and the offsets' download (line_edges_run), behind them the packed lines
-  const size_t b_tab = le_table_bytes(segs.size()), b_lines = (size_t)n_lines * 6 * sizeof(double);
-  if (le_ensure_stage(h, b_tab + b_lines) != DGS_OK) return DGS_ERR_HIP;
+  segtab::Layout L = le_table(segs.size()).L;
+  const size_t b_lines = (size_t)n_lines * 6 * sizeof(double), b_tab = L.take(b_lines, alignof(double));
+  DGS_HIP_TRY(h, s.stage.reserve(L.end));
   DGS_HIP_TRY(h, s.lines.reserve(std::max<size_t>((size_t)n_lines * 6, 1)));
   if (n_lines) {
-    double* up = reinterpret_cast<double*>(static_cast<char*>(s.stage) + b_tab);
+    double* up = reinterpret_cast<double*>(s.stage.at(b_tab));
     la::pack_lines(la::lines_of(lines, n_lines), up);
     DGS_HIP_TRY(h, hipMemcpyAsync(s.lines.ptr, up, b_lines, hipMemcpyHostToDevice, h->stream));
   }

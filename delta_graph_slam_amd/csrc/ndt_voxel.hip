@@ -14,38 +14,16 @@
 #include <cmath>
 
 #include "handle.h"
+#include "seg_device.h"
 #include "small_linalg.h"
 
 namespace dgs {
 
-// ---- AABB of the finite points ---------------------------------------------------------------------------
+// ---- AABB of the finite points (the folds: seg_device.h) -------------------------------------------------
 __global__ __launch_bounds__(kBlock) void minmax_kernel(const float4* __restrict__ pts, int64_t n, float* __restrict__ partial) {
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 p = pts[i];
-    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-      mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-      mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-    }
-  }
-  __shared__ float sm[kBlock / kWave][6];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_down(mn[a], off, 64));
-      mx[a] = fmaxf(mx[a], __shfl_down(mx[a], off, 64));
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    for (int a = 0; a < 3; a++) { sm[wave][a] = mn[a]; sm[wave][3 + a] = mx[a]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float v = sm[0][threadIdx.x];
-    for (int w = 1; w < kBlock / kWave; w++) v = (threadIdx.x < 3) ? fminf(v, sm[w][threadIdx.x]) : fmaxf(v, sm[w][threadIdx.x]);
-    partial[blockIdx.x * 6 + threadIdx.x] = v;
-  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) box_add_finite(pts[i], mn, mx);
+  box_fold_block(mn, mx, partial, blockIdx.x * 6);
 }
 
 __global__ void minmax_final_kernel(const float* __restrict__ partial, int nblocks, float* __restrict__ out6) {
@@ -54,14 +32,7 @@ __global__ void minmax_final_kernel(const float* __restrict__ partial, int nbloc
   float v[6] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
   for (int b = lane; b < nblocks; b += 64)
     for (int a = 0; a < 6; a++) v[a] = (a < 3) ? fminf(v[a], partial[b * 6 + a]) : fmaxf(v[a], partial[b * 6 + a]);
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float o = __shfl_down(v[a], off, 64);
-      v[a] = (a < 3) ? fminf(v[a], o) : fmaxf(v[a], o);
-    }
-  }
+  box_fold_wave(v);
   if (lane == 0)
     for (int a = 0; a < 6; a++) out6[a] = v[a];
 }

@@ -911,11 +911,11 @@ int pcl_gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud
   // every index that is missing, of targets and sources alike, in ONE batched build (the bits of a single build: fitness_batch.hip)
   std::vector<dgs_cloud*> all(tgts, tgts + n);
   all.insert(all.end(), srcs, srcs + n);
-  int rc = fitness_batch_build_indices(h, 2 * n, all.data());
+  StageCounts build;
+  int rc = fitness_batch_build_indices(h, 2 * n, all.data(), &build);
   if (rc) return rc;
   // the covariances of the distinct targets and of the live pairs' sources in ONE batched pass (cov_batch.hip), cached on the cloud under
   // (k, epsilon): shared with every other path that uses the cloud
-  const int64_t indices_built = h->fb.counts8[3];
   std::vector<CloudState*> tc(uniq.size()), cs((size_t)n), need;
   for (size_t t = 0; t < uniq.size(); t++) {
     tc[t] = &uniq[t]->st;
@@ -926,7 +926,7 @@ int pcl_gicp_align_pairs(dgs_handle* h, int n, dgs_cloud* const* tgts, dgs_cloud
     if (tgt_of[i] >= 0 && cs[i]->n >= (int64_t)k) need.push_back(cs[i]);
   }
   rc = ensure_covariances(h, (int)need.size(), need.data(), covplan::kPcl);
-  h->cb.counts8[7] = indices_built;
+  h->cb.counts8[7] = build.built;
   if (rc) return rc;
   const PgTargets tg{(int)uniq.size(), tc.data(), tgt_of.data()};
   const int64_t own_evaluations = h->last_evaluations;   // dgs_get_counts keeps reporting the handle's own last align / batch

@@ -4,7 +4,7 @@
 //
 // The table.  Every stage uploads one PfbSeg per scan that is still live: where its points, flags, neighbour lists and outputs are, its
 // size and index, and its first workgroup in the stage's launches.  Every scan owns whole workgroups.  A workgroup finds its scan by
-// bisecting the launch's array of first workgroups with its blockIdx.x (cov_batch_find); the address is workgroup-uniform, so the
+// bisecting the launch's array of first workgroups with its blockIdx.x (seg_find, seg_device.h); the address is workgroup-uniform, so the
 // bisection and the entry are scalar loads and the entry lives in SGPRs.  From there on the workgroup is a workgroup of the single
 // launch: the bodies of prefilter_body.h with the scan's own arguments and the workgroup's number inside the scan.
 //
@@ -31,6 +31,8 @@
 #include "nn_group.h"
 #include "prefilter_batch_plan.h"
 #include "prefilter_body.h"
+#include "seg_device.h"
+#include "seg_table.h"
 
 namespace dgs {
 
@@ -57,24 +59,24 @@ static_assert(sizeof(PfbSeg) == 144, "one entry is nine 16-byte scalar loads");
 // ---- flags -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void pfb_distance_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m, const double near_t,
                                                               const double far_t) {
-  const PfbSeg& e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   pf_distance_body(e.in, e.n, near_t, far_t, e.flags, (int)blockIdx.x - e.blk0);
 }
 __global__ __launch_bounds__(kBlock) void pfb_head_flag_kernel(const PfbSeg* __restrict__ tab, const PfHead* __restrict__ heads, const int* __restrict__ first,
                                                                const int m, const double near_t, const double far_t) {
-  const int c = cov_batch_find(first, m, (int)blockIdx.x);
+  const int c = seg_find(first, m, (int)blockIdx.x);
   const PfbSeg& e = tab[c];
   pf_head_flag_body(e.in, (long long)e.n, heads[c], near_t, far_t, e.flags, (int)blockIdx.x - e.blk0);
 }
 __global__ __launch_bounds__(kBlock) void pfb_height_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m) {
-  const PfbSeg& e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   pf_height_body(e.in, e.n, e.lz, e.flags, (int)blockIdx.x - e.blk0);
 }
 
 // ---- segmented stable compaction (compact.h) ------------------------------------------------------------------------------------
 // blk: one count per workgroup of the launch and one more behind them, which workgroup 0 zeroes: pf_scan_kernel runs over gridDim.x + 1
 __global__ __launch_bounds__(kBlock) void pfb_count_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m, int* __restrict__ blk) {
-  const PfbSeg& e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   const int i = ((int)blockIdx.x - e.blk0) * kBlock + threadIdx.x;
   const int t = compact_count_seg(e.flags, i, e.n);
   if (threadIdx.x == 0) {
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void pfb_count_kernel(const PfbSeg* __restr
 }
 __global__ __launch_bounds__(kBlock) void pfb_scatter_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m, const int* __restrict__ blk,
                                                              int* __restrict__ totals, const int flatten) {
-  const int c = cov_batch_find(first, m, (int)blockIdx.x);
+  const int c = seg_find(first, m, (int)blockIdx.x);
   const PfbSeg& e = tab[c];
   const int lb = (int)blockIdx.x - e.blk0, seg0 = blk[e.blk0];
   if (lb == 0 && threadIdx.x == 0) totals[c] = blk[first[c + 1]] - seg0;
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void pfb_scatter_kernel(const PfbSeg* __res
 }
 __global__ __launch_bounds__(kBlock) void pfb_head_scatter_kernel(const PfbSeg* __restrict__ tab, const PfHead* __restrict__ heads, const int* __restrict__ first,
                                                                   const int m, const int* __restrict__ blk, int* __restrict__ totals) {
-  const int c = cov_batch_find(first, m, (int)blockIdx.x);
+  const int c = seg_find(first, m, (int)blockIdx.x);
   const PfbSeg& e = tab[c];
   const int lb = (int)blockIdx.x - e.blk0, seg0 = blk[e.blk0];
   if (lb == 0 && threadIdx.x == 0) totals[c] = blk[first[c + 1]] - seg0;
@@ -111,16 +113,16 @@ __global__ __launch_bounds__(kBlock) void pfb_head_scatter_kernel(const PfbSeg* 
 // gicp_knn_leaf_kernel (knn_lists.hip) over the stage's scans, its launch bounds
 __global__ __launch_bounds__(kBlock, DGS_KNN_WAVES) void pfb_knn_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ knn_first, const int m,
                                                                         int* __restrict__ stats) {
-  const PfbSeg& e = tab[cov_batch_find(knn_first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(knn_first, m, (int)blockIdx.x)];
   gicp_knn_leaf_body<kKnnSlots>(e.b, e.n, e.k, e.parts, e.nbr, stats, (int)blockIdx.x - e.knn_blk0);
 }
 __global__ __launch_bounds__(kBlock) void pfb_radius_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m, const double r2,
                                                             const int inclusive) {
-  const PfbSeg& e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   pf_radius_body(e.b, e.in, e.n, e.k, e.nbr, r2, inclusive, e.flags, (int)blockIdx.x - e.blk0);
 }
 __global__ __launch_bounds__(kBlock) void pfb_sor_distance_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m, const int sqrt_float) {
-  const PfbSeg& e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   pf_sor_distance_body(e.b, e.in, e.n, e.k, e.nbr, sqrt_float, e.mean_d, (int)blockIdx.x - e.blk0);
 }
 // one workgroup per scan: pf_sor_stats_kernel's fixed reduction order
@@ -129,18 +131,16 @@ __global__ __launch_bounds__(kPfStatsBlock) void pfb_sor_stats_kernel(const PfbS
   pf_sor_stats_body(e.mean_d, e.n, mul, e.stats);
 }
 __global__ __launch_bounds__(kBlock) void pfb_sor_flag_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m) {
-  const PfbSeg& e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   pf_sor_flag_body(e.mean_d, e.n, e.stats, e.flags, (int)blockIdx.x - e.blk0);
 }
 __global__ __launch_bounds__(kBlock) void pfb_normal_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m) {
-  const PfbSeg& e = tab[cov_batch_find(first, m, (int)blockIdx.x)];
+  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   pf_normal_body(e.b, e.in, e.n, e.k, e.nbr, e.vx, e.vy, e.vz, e.flags, e.normals, e.cov9, (int)blockIdx.x - e.blk0);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 namespace {
-
-size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 // the device addresses of an uploaded stage table
 struct PfbDev {
@@ -157,33 +157,24 @@ struct PfbDev {
 int pfb_upload(dgs_handle* h, const pfbplan::Stage& St, const std::vector<PfbSeg>& segs, const PfHead* heads, PfbDev* dev) {
   PfbScratch& S = h->pfb;
   const size_t m = St.items.size();
-  const size_t o_heads = align64(m * sizeof(PfbSeg)), o_first = align64(o_heads + (heads ? m * sizeof(PfHead) : 0));
-  const size_t o_knn = align64(o_first + (m + 1) * sizeof(int)), up = align64(o_knn + (m + 1) * sizeof(int));
-  const size_t o_tot = up, o_stats = align64(o_tot + m * sizeof(int)), all = o_stats + m * 4 * sizeof(double);
-  if (all > S.stage_bytes) {
-    if (S.stage) (void)hipHostFree(S.stage);
-    S.stage = nullptr;
-    S.stage_bytes = 0;
-    const size_t want = all + all / 4 + 4096;
-    DGS_HIP_TRY(h, hipHostMalloc(&S.stage, want, hipHostMallocDefault));
-    S.stage_bytes = want;
-  }
-  DGS_HIP_TRY(h, S.tables.reserve(up));
+  const segtab::StageTable T = segtab::stage_table(m, sizeof(PfbSeg), heads ? sizeof(PfHead) : 0);
+  DGS_HIP_TRY(h, S.stage.reserve(T.all));
+  DGS_HIP_TRY(h, S.tables.reserve(T.up));
   DGS_HIP_TRY(h, S.totals.reserve(m));
-  char* st = static_cast<char*>(S.stage);
-  std::memcpy(st, segs.data(), m * sizeof(PfbSeg));
+  char* st = S.stage.at(0);
+  std::memcpy(st + T.entries, segs.data(), m * sizeof(PfbSeg));
   if (heads)
-    for (size_t j = 0; j < m; j++) std::memcpy(st + o_heads + j * sizeof(PfHead), &heads[St.items[j].scan], sizeof(PfHead));
+    for (size_t j = 0; j < m; j++) std::memcpy(st + T.heads + j * sizeof(PfHead), &heads[St.items[j].scan], sizeof(PfHead));
   const std::vector<int> first = St.first(), knn_first = St.knn_first();
-  std::memcpy(st + o_first, first.data(), (m + 1) * sizeof(int));
-  std::memcpy(st + o_knn, knn_first.data(), (m + 1) * sizeof(int));
-  DGS_HIP_TRY(h, hipMemcpyAsync(S.tables.ptr, st, up, hipMemcpyHostToDevice, h->stream));
-  dev->tab = reinterpret_cast<const PfbSeg*>(S.tables.ptr);
-  dev->heads = reinterpret_cast<const PfHead*>(S.tables.ptr + o_heads);
-  dev->first = reinterpret_cast<const int*>(S.tables.ptr + o_first);
-  dev->knn_first = reinterpret_cast<const int*>(S.tables.ptr + o_knn);
-  dev->totals_h = reinterpret_cast<int*>(st + o_tot);
-  dev->stats_h = reinterpret_cast<double*>(st + o_stats);
+  std::memcpy(st + T.first, first.data(), (m + 1) * sizeof(int));
+  std::memcpy(st + T.knn_first, knn_first.data(), (m + 1) * sizeof(int));
+  DGS_HIP_TRY(h, hipMemcpyAsync(S.tables.ptr, st, T.up, hipMemcpyHostToDevice, h->stream));
+  dev->tab = reinterpret_cast<const PfbSeg*>(S.tables.ptr + T.entries);
+  dev->heads = reinterpret_cast<const PfHead*>(S.tables.ptr + T.heads);
+  dev->first = reinterpret_cast<const int*>(S.tables.ptr + T.first);
+  dev->knn_first = reinterpret_cast<const int*>(S.tables.ptr + T.knn_first);
+  dev->totals_h = reinterpret_cast<int*>(st + T.totals);
+  dev->stats_h = reinterpret_cast<double*>(st + T.stats);
   return DGS_OK;
 }
 
@@ -230,11 +221,12 @@ int pfb_knn(dgs_handle* h, const pfbplan::Stage& St, std::vector<CloudState>& po
   const int m = (int)St.items.size();
   std::vector<CloudState*> cs((size_t)m);
   for (int j = 0; j < m; j++) cs[j] = &pool[St.items[j].scan];
-  const int64_t l0 = h->fb.counts8[0], w0 = h->fb.counts8[1], b0 = h->fb.counts8[3];
-  if (int rc = fitness_batch_build_state_indices(h, m, cs.data(), false)) return rc;
-  S.counts8[0] += h->fb.counts8[0] - l0;
-  S.counts8[1] += h->fb.counts8[1] - w0;
-  S.counts8[6] += h->fb.counts8[3] - b0;
+  StageCounts build;
+  const int rc = fitness_batch_build_state_indices(h, m, cs.data(), &build);
+  S.counts8[0] += build.launches;
+  S.counts8[1] += build.waits;
+  S.counts8[6] += build.built;
+  if (rc) return rc;
   DGS_HIP_TRY(h, S.nbr.reserve((size_t)St.points * kKnnMax));
   DGS_HIP_TRY(h, h->knn_stats.reserve(8));
   for (int j = 0; j < m; j++) {
@@ -316,13 +308,10 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
         if (cur[s] > 0) { vin.push_back(S.a[s].pts.ptr); vn.push_back(cur[s]); vst.push_back(&S.b[s]); who.push_back(s); }
       if (!who.empty()) {
         vout.assign(who.size(), 0);
-        int64_t saved[8];
-        std::copy(h->vb.counts8, h->vb.counts8 + 8, saved);   // dgs_cloud_assign_get_counts keeps reporting the last assign call
-        h->vb.counts8[0] = h->vb.counts8[1] = 0;
-        const int rc = voxelgrid_batch(h, (int)who.size(), vin.data(), vn.data(), leaf, vst.data(), nullptr, vout.data());
-        S.counts8[0] += h->vb.counts8[0];
-        S.counts8[1] += h->vb.counts8[1];
-        std::copy(saved, saved + 8, h->vb.counts8);
+        StageCounts down;   // dgs_cloud_assign_get_counts keeps reporting the last assign call
+        const int rc = voxelgrid_batch(h, (int)who.size(), vin.data(), vn.data(), leaf, vst.data(), nullptr, vout.data(), &down);
+        S.counts8[0] += down.launches;
+        S.counts8[1] += down.waits;
         if (rc) return rc;
         for (size_t j = 0; j < who.size(); j++) cur[who[j]] = vout[j];
       }
@@ -493,10 +482,7 @@ void prefilter_batch_release(dgs_handle* h) {
     pool->clear();
   }
   S.in.release(); S.flags.release(); S.blk.release(); S.cnt.release(); S.totals.release(); S.nbr.release(); S.mean_d.release(); S.stats.release();
-  S.normals.release(); S.cov9.release(); S.tables.release();
-  if (S.stage) (void)hipHostFree(S.stage);
-  S.stage = nullptr;
-  S.stage_bytes = 0;
+  S.normals.release(); S.cov9.release(); S.tables.release(); S.stage.release();
   S.stats_host.clear();
 }
 
@@ -564,17 +550,12 @@ int dgs_prefilter_scan_batch(dgs_handle* h, const dgs_prefilter_params* p, int32
   const std::vector<pfbplan::Chunk> chunks = pfbplan::make_chunks(n_scans, sizes, budget);
   std::vector<const float4*> d_in((size_t)n_scans);
   for (const pfbplan::Chunk& ch : chunks) {
-    // host inputs travel into one slab, back to back (pageable memory: each copy has left the caller's array when it returns)
-    if (!in_on_device && ch.points > 0) DGS_HIP_TRY(h, S.in.reserve((size_t)ch.points));
-    int64_t off = 0;
-    for (int s = ch.first; s < ch.first + ch.count; s++) {
-      d_in[s] = reinterpret_cast<const float4*>(in_xyz16[s]);
-      if (in_on_device || sizes[s] == 0) continue;
-      DGS_HIP_TRY(h, hipMemcpyAsync(S.in.ptr + off, in_xyz16[s], (size_t)sizes[s] * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-      d_in[s] = S.in.ptr + off;
-      off += sizes[s];
-    }
     const int f = ch.first;
+    if (in_on_device) {
+      for (int s = f; s < f + ch.count; s++) d_in[s] = reinterpret_cast<const float4*>(in_xyz16[s]);
+    } else if (int rc = stage_host_inputs(h, S.in, ch.count, in_xyz16 + f, sizes + f, d_in.data() + f)) {
+      return rc;
+    }
     const int rc = pfb_chain(h, p, ch.count, heads.empty() ? nullptr : heads.data() + f, lidar.data() + (size_t)f * 3, d_in.data() + f, sizes + f, out3d_xyz16 + f,
                              cap3d + f, out2d_xyz16 + f, cap2d + f, out_on_device, n3d_out + f, n2d_out + f, status_out + f, S.stats_host.data() + (size_t)f * 4);
     if (rc != DGS_OK) {

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "cov_batch_plan.h"
+#include "seg_table.h"
 
 namespace dgs {
 namespace pfbplan {
@@ -48,18 +49,8 @@ struct Stage {
   int blocks = 0, knn_blocks = 0;   // workgroups of the per-point launches / of the search launch
   int64_t points = 0;
   // first workgroup per item and, behind the last, the number of workgroups: what the launch bisects
-  std::vector<int> first() const {
-    std::vector<int> f;
-    for (const Item& it : items) f.push_back(it.blk0);
-    f.push_back(blocks);
-    return f;
-  }
-  std::vector<int> knn_first() const {
-    std::vector<int> f;
-    for (const Item& it : items) f.push_back(it.knn_blk0);
-    f.push_back(knn_blocks);
-    return f;
-  }
+  std::vector<int> first() const { return segtab::first_array(items.data(), items.size(), &Item::blk0, blocks); }
+  std::vector<int> knn_first() const { return segtab::first_array(items.data(), items.size(), &Item::knn_blk0, knn_blocks); }
 };
 inline Stage make_stage(const int n_scans, const int64_t* sizes, const bool knn, const int override_parts) {
   Stage S;

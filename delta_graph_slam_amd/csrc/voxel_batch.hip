@@ -22,10 +22,9 @@
 #include <vector>
 
 #include "handle.h"
+#include "seg_device.h"
 
 namespace dgs {
-
-constexpr int kVbMmBlocks = 64;   // partial boxes per cloud = lanes of the wave that folds them
 
 struct VbSeg {
   const float4* in;    // the input points (the caller's device array, or its place in the staged slab)
@@ -38,54 +37,12 @@ struct VbSeg {
 };
 static_assert(sizeof(VbSeg) == 64, "one cloud is one 64-byte scalar load");
 
-// ---- 1. boxes (minmax_kernel / minmax_final_kernel of ndt_voxel.hip per segment) ------------------------------------------------
+// ---- 1. boxes: the per-segment bodies of seg_device.h over this file's records ----------------------------------------------------
 __global__ __launch_bounds__(kBlock) void vb_minmax_kernel(const VbSeg* __restrict__ segs, float* __restrict__ partial) {
   const VbSeg& S = segs[blockIdx.y];
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < S.n; i += kVbMmBlocks * kBlock) {
-    const float4 p = S.in[i];
-    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-      mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-      mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-    }
-  }
-  __shared__ float sm[kBlock / kWave][6];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_down(mn[a], off, 64));
-      mx[a] = fmaxf(mx[a], __shfl_down(mx[a], off, 64));
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    for (int a = 0; a < 3; a++) { sm[wave][a] = mn[a]; sm[wave][3 + a] = mx[a]; }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float v = sm[0][threadIdx.x];
-    for (int w = 1; w < kBlock / kWave; w++) v = (threadIdx.x < 3) ? fminf(v, sm[w][threadIdx.x]) : fmaxf(v, sm[w][threadIdx.x]);
-    partial[((size_t)blockIdx.y * kVbMmBlocks + blockIdx.x) * 6 + threadIdx.x] = v;
-  }
+  seg_box_partial_body(S.in, S.n, partial);
 }
-
-__global__ __launch_bounds__(kWave) void vb_minmax_final_kernel(const float* __restrict__ partial, float* __restrict__ boxes) {
-  static_assert(kVbMmBlocks == kWave, "one partial box per lane");
-  const float* p = partial + ((size_t)blockIdx.x * kVbMmBlocks + threadIdx.x) * 6;
-  float v[6];
-#pragma unroll
-  for (int a = 0; a < 6; a++) v[a] = p[a];
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float o = __shfl_down(v[a], off, 64);
-      v[a] = (a < 3) ? fminf(v[a], o) : fmaxf(v[a], o);
-    }
-  }
-  if (threadIdx.x == 0)
-    for (int a = 0; a < 6; a++) boxes[(size_t)blockIdx.x * 6 + a] = v[a];
-}
+__global__ __launch_bounds__(kWave) void vb_minmax_final_kernel(const float* __restrict__ partial, float* __restrict__ boxes) { seg_box_final_body(partial, boxes); }
 
 // ---- 2. keys (voxel_key_kernel per segment, the cloud's number above the 32 bits of the cell) ------------------------------------
 __global__ __launch_bounds__(kBlock) void vb_key_kernel(const VbSeg* __restrict__ segs, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
@@ -136,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void vb_centroid_kernel(const VbSeg* __rest
 // inputs: device pointers (host inputs have been staged by the caller).  On DGS_ERR_GRID_TOO_LARGE no cloud has been touched.
 // The outputs are cloud states: those of dgs_cloud objects (`owners`, dgs_cloud_assign_batch) or a handle's own (prefilter_batch.hip).
 int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64_t* sizes, float leaf, CloudState* const* states, dgs_cloud* const* owners,
-                    int64_t* out_sizes) {
+                    int64_t* out_sizes, StageCounts* sink) {
   VbScratch& V = h->vb;
   hipStream_t st = h->stream;
   int64_t total = 0;
@@ -162,7 +119,7 @@ int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64
   float* boxes_h = reinterpret_cast<float*>(reinterpret_cast<char*>(h->pinned) + seg_bytes);
   int* bounds_h = reinterpret_cast<int*>(reinterpret_cast<char*>(h->pinned) + seg_bytes + box_bytes);
   DGS_HIP_TRY(h, V.segs.reserve((size_t)n));
-  DGS_HIP_TRY(h, V.mm.reserve((size_t)n * (kVbMmBlocks + 1) * 6));
+  DGS_HIP_TRY(h, V.mm.reserve((size_t)n * (kSegBoxBlocks + 1) * 6));
   DGS_HIP_TRY(h, V.keys.reserve((size_t)total));
   DGS_HIP_TRY(h, V.keys_alt.reserve((size_t)total));
   DGS_HIP_TRY(h, V.run_keys.reserve((size_t)total));
@@ -190,14 +147,14 @@ int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64
     off += (int)sizes[i];
   }
   const int slot = prof_begin(h, DGS_K_NDT_VOXEL_BUILD);
-  float* boxes_d = V.mm.ptr + (size_t)n * kVbMmBlocks * 6;
+  float* boxes_d = V.mm.ptr + (size_t)n * kSegBoxBlocks * 6;
   DGS_HIP_TRY(h, hipMemcpyAsync(V.segs.ptr, segs, seg_bytes, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(vb_minmax_kernel, dim3(kVbMmBlocks, n), dim3(kBlock), 0, st, V.segs.ptr, V.mm.ptr);
+  hipLaunchKernelGGL(vb_minmax_kernel, dim3(kSegBoxBlocks, n), dim3(kBlock), 0, st, V.segs.ptr, V.mm.ptr);
   hipLaunchKernelGGL(vb_minmax_final_kernel, dim3(n), dim3(kWave), 0, st, V.mm.ptr, boxes_d);
   DGS_HIP_TRY(h, hipMemcpyAsync(boxes_h, boxes_d, box_bytes, hipMemcpyDeviceToHost, st));
   DGS_HIP_TRY(h, hipStreamSynchronize(st));
-  V.counts8[0] += 2;
-  V.counts8[1]++;
+  sink->launches += 2;
+  sink->waits++;
 
   // grids (voxel_grid_filter's arithmetic) and PCL's overflow test, per cloud, before anything is written
   const float inv_leaf = 1.0f / leaf;
@@ -246,8 +203,8 @@ int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64
   prof_end(h, DGS_K_NDT_VOXEL_BUILD, slot);
   DGS_HIP_TRY(h, hipStreamSynchronize(st));
   DGS_HIP_TRY(h, hipGetLastError());
-  V.counts8[0] += 6;   // keys, sort, run lengths, scan, bounds, centroids
-  V.counts8[1]++;
+  sink->launches += 6;   // keys, sort, run lengths, scan, bounds, centroids
+  sink->waits++;
   for (int i = 0; i < n; i++) {
     out_sizes[i] = bounds_h[2 * i + 1] - bounds_h[2 * i];
     states[i]->n = out_sizes[i];
@@ -258,7 +215,11 @@ int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64
 static int assign_voxelgrid(dgs_handle* h, int n, const float4* const* d_in, const int64_t* sizes, float leaf, dgs_cloud* const* clouds, int64_t* out_sizes) {
   std::vector<CloudState*> states((size_t)n);
   for (int i = 0; i < n; i++) states[i] = &clouds[i]->st;
-  return voxelgrid_batch(h, n, d_in, sizes, leaf, states.data(), clouds, out_sizes);
+  StageCounts sc;
+  const int rc = voxelgrid_batch(h, n, d_in, sizes, leaf, states.data(), clouds, out_sizes, &sc);
+  h->vb.counts8[0] += sc.launches;
+  h->vb.counts8[1] += sc.waits;
+  return rc;
 }
 
 int cloud_assign_batch(dgs_handle* h, int n, const float* const* inputs, const int64_t* sizes, int on_device, int filter, float leaf, dgs_cloud* const* clouds,
@@ -267,18 +228,9 @@ int cloud_assign_batch(dgs_handle* h, int n, const float* const* inputs, const i
   std::fill(V.counts8, V.counts8 + 8, 0);
   V.counts8[2] = n;
   hipStream_t st = h->stream;
-  // host inputs travel into one slab, back to back (pageable memory: each copy has left the caller's array when it returns)
   std::vector<const float4*> d_in((size_t)n);
-  int64_t total = 0;
-  for (int i = 0; i < n; i++) total += sizes[i];
-  if (!on_device && filter != 0 && total > 0) {
-    DGS_HIP_TRY(h, V.in.reserve((size_t)total));
-    int64_t off = 0;
-    for (int i = 0; i < n; i++) {
-      d_in[i] = V.in.ptr + off;
-      if (sizes[i] > 0) DGS_HIP_TRY(h, hipMemcpyAsync(V.in.ptr + off, inputs[i], (size_t)sizes[i] * sizeof(float4), hipMemcpyHostToDevice, st));
-      off += sizes[i];
-    }
+  if (!on_device && filter != 0) {
+    if (int rc = stage_host_inputs(h, V.in, n, inputs, sizes, d_in.data())) return rc;
   } else {
     for (int i = 0; i < n; i++) d_in[i] = reinterpret_cast<const float4*>(inputs[i]);
   }

@@ -223,6 +223,21 @@ def test_cache_keys_duplicates_and_refills(method):
     reg.close()
 
 
+@pytest.mark.parametrize("method", FAMILIES)
+def test_a_table_that_outgrows_its_pinned_block_between_calls(method):
+    """1 cloud, then 64 clouds of at most 64 points -- 64 entries of 96 bytes, more than the bytes + bytes / 4 + 4 KiB the first call
+    left the pinned block with -- then 1 cloud again, all on one handle: every call gives the single path's bits and the counts a fresh
+    handle reports"""
+    sizes = (20, 33, 64, 47)
+    one, many = [_cloud(300, 77)], [_cloud(sizes[i % 4], 200 + sizes[i % 4]) for i in range(64)]   # 64 device clouds of four arrays
+    reg = _reg(method)
+    for clouds, keys in ((one, [("grow", 300)]), (many, [("grow", sizes[i % 4]) for i in range(64)]), (one, [("grow", 300)])):
+        n = len(clouds)
+        _, _, counts = _check_batch(method, clouds, keys, reg=reg)
+        assert counts == {"launches": 2, "host_waits": 0, "listed": n, "covered": n, "cached": 0, "chunks": 1, "fallback": 0, "indices_built": n}, counts
+    reg.close()
+
+
 # ------------------------------------------------------------------------------------------------------ refusals
 @pytest.mark.parametrize("method,name", [("NDT_OMP", "NDT_OMP"), ("ICP_HIP", "ICP_HIP"), ("PCL_NDT_HIP", "PCL_NDT_HIP")])
 def test_other_methods_are_refused_with_the_method_named(method, name):

@@ -133,6 +133,30 @@ def test_three_hundred_edges_over_the_tiny_clouds(reg, warm):
     assert len(seen) > 100
 
 
+def test_a_table_that_outgrows_its_pinned_block_between_calls():
+    """One edge, then 64 edges between clouds of at most 64 points -- 64 entries of 128 bytes, more than the bytes + bytes / 4 + 4 KiB
+    the first call left the pinned block with -- then the one edge again, all on one handle: scores, used counts and the call's counts
+    are those of a fresh handle"""
+    from delta_graph_slam_amd.registration import Registration
+    clouds, _ = R.scene()
+    T = R.relpose(0, 1)
+
+    def call(r, pairs):
+        c1 = [r.make_cloud(clouds["k0"][:a]) for a, _ in pairs]   # cold clouds: the call builds their indices
+        c2 = [r.make_cloud(clouds["k1"][:b]) for _, b in pairs]
+        return r.calc_fitness_score_batch(c1, c2, [T] * len(pairs), DBL_MAX, return_used=True), r.fitness_batch_counts()
+
+    one, many = [(300, 200)], [(1 + (5 * i) % 64, 1 + (11 * i) % 64) for i in range(64)]
+    used = Registration("FAST_GICP")
+    for pairs in (one, many, one):
+        fresh = Registration("FAST_GICP")
+        (a, ca), (b, cb) = call(used, pairs), call(fresh, pairs)
+        assert same_bits(a, b) and ca == cb, (len(pairs), ca, cb)
+        assert ca["edges"] == len(pairs) and ca["indices_built"] == len(pairs) and ca["host_waits"] == 1 and a[1].sum() > 0
+        fresh.close()
+    used.close()
+
+
 # ---------------------------------------------------------------------------------------------- cold equals warm
 def test_cold_equals_warm(reg):
     edges = list(R.main_edges()) + list(R.size_edges())

@@ -90,6 +90,26 @@ def test_batch_order(reg):
             assert _same(got[off[pos]:off[pos + 1]], _host(names[k], mode)[0]), (order, pos)
 
 
+def test_a_table_that_outgrows_its_pinned_block_between_calls():
+    """One segment, then 64 segments of at most 64 lines -- their table and packed lines are more than the bytes + bytes / 4 + 4 KiB the
+    first call left the pinned block with -- then the one segment again, all on one handle: edges, offsets and counts of a fresh handle"""
+    from delta_graph_slam_amd.registration import Registration
+    names = ("tri23", "n0", "star", "case3_other_end", "n1", "wg_exact", "gate60", "n3")
+    mode = S.MODES[0]
+    one, many = [S.scenes()["tri23"][0]], [S.scenes()[names[i % 8]][0] for i in range(64)]
+    block = lambda segs: 32 * len(segs) + 8 * ((len(segs) + 2) // 2) + 48 * sum(len(s) for s in segs)   # segment table | offsets | lines
+    assert max(len(s) for s in many) <= 64 and block(many) > block(one) + block(one) // 4 + 4096
+    used = Registration("NDT_OMP", device=0)
+    for segments in (one, many, one):
+        fresh = Registration("NDT_OMP", device=0)
+        a, b = _device(used, segments, [mode] * len(segments)), _device(fresh, segments, [mode] * len(segments))
+        assert a[0] == b[0] == 0 and a[3] == b[3] and _same(a[1], b[1]) and _same(a[2], b[2])
+        assert _matcher(used).edge_counts() == _matcher(fresh).edge_counts() and _matcher(used).edge_counts()["edges"] == a[3]
+        assert len(segments) == 1 or a[3] > 64
+        fresh.close()
+    used.close()
+
+
 def test_capacity_rule_is_dgs_line_edges_s(reg):
     from delta_graph_slam_amd import _lib as L
     segments = S.scenes()["mixed_sizes"]

@@ -66,6 +66,17 @@ def test_the_host_plan_against_hand_written_expectations(tmp_path):
     assert p.returncode == 0 and p.stdout.strip().splitlines()[-1] == "ok", p.stdout + p.stderr
 
 
+def test_the_table_layouts_against_hand_written_offsets(tmp_path):
+    """seg_table.h has no HIP in it either: the offsets of the stage block (entries | heads | firsts | search firsts | totals | statistics)
+    and of the covariance pass's chunk sections for 0, 1 and 3 entries, and the first-workgroup array around an empty item, against values
+    written out by hand; built with the host sanitizers and run directly"""
+    exe = str(tmp_path / "seg_table_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "delta_graph_slam_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "seg_table_check.cpp"), "-o", exe])
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.strip().splitlines()[-1] == "ok", p.stdout + p.stderr
+
+
 def test_cpp_driver_compiles_and_links_against_the_stubs(tmp_path):
     exe = str(tmp_path / "prefilter_batch_driver")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "stub_pcl"), "-I", os.path.join(ROOT, "include"),

@@ -404,6 +404,22 @@ def test_a_handle_that_ran_a_large_batch_gives_a_small_batch_the_bits_of_a_fresh
     assert a[-2][0].shape[0] > 500
 
 
+def test_a_table_that_outgrows_its_pinned_block_between_calls():
+    """1 scan, then 64 scans of at most 64 points -- 64 entries of 144 bytes, more than the bytes + bytes / 4 + 4 KiB the first call left
+    the pinned block with -- then the 1 scan again, all on one handle: every call gives the bits, statuses and counts of a fresh handle"""
+    one = ([small_vlp16(seed=9, azimuths=100)], [HEADS[3]])
+    many = ([tiny(1 + (7 * i) % 64) for i in range(64)], [HEADS[i % 4] for i in range(64)])
+    used = _pf(R.LAUNCH)
+    for scans, heads in (one, many, one):
+        fresh = _pf(R.LAUNCH)
+        a, sa = run_batch(used, scans, heads)
+        b, sb = run_batch(fresh, scans, heads)
+        assert np.array_equal(sa, sb) and np.array_equal(used.batch_counts(), fresh.batch_counts()), (used.batch_counts(), fresh.batch_counts())
+        for x, y in zip(a, b):
+            assert np.array_equal(_bits(x[0]), _bits(y[0])) and np.array_equal(_bits(x[1]), _bits(y[1])) and np.array_equal(x[2], y[2])
+        assert sum(o[0].shape[0] for o in a) > 0
+
+
 # ---- 7. fleet hand-over ----------------------------------------------------------------------------------------------------------
 def test_batch_outputs_feed_the_odometry_fleet_as_the_single_calls_do():
     from delta_graph_slam_amd.odometry import ScanMatchingOdometryFleet
