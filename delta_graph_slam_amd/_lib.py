@@ -214,6 +214,8 @@ SYMBOLS = [
     "dgs_cloud_assign_batch", "dgs_cloud_assign_get_counts", "dgs_cloud_read", "dgs_calc_inlier_fraction_batch_clouds",
     "dgs_cloud_build_covariances", "dgs_cloud_covariances_get_counts",
     "dgs_prefilter_scan_batch", "dgs_prefilter_batch_get_counts", "dgs_prefilter_batch_get_statistics",
+    "dgs_floor_detection_batch", "dgs_floor_detection_batch_get_filtered", "dgs_floor_detection_batch_get_inliers",
+    "dgs_floor_detection_batch_get_trace", "dgs_floor_detection_batch_get_clipped", "dgs_floor_detection_batch_get_counts",
 ]
 
 _libs = {}
@@ -389,6 +391,13 @@ def load(path=None):
     lib.dgs_floor_detection_get_clipped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
     lib.dgs_floor_detection_draws.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.dgs_floor_detection_walk.argtypes = [C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32)]
+    lib.dgs_floor_detection_batch.argtypes = [C.c_void_p, P(FloorDetectionParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dgs_floor_detection_batch_get_filtered.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, P(C.c_int64)]
+    lib.dgs_floor_detection_batch_get_inliers.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_floor_detection_batch_get_trace.argtypes = [C.c_void_p, C.c_int32, P(FloorDetectionTrace)]
+    lib.dgs_floor_detection_batch_get_clipped.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64)]
+    lib.dgs_floor_detection_batch_get_counts.argtypes = [C.c_void_p, C.c_void_p]
     lib.dgs_building_cloud_params_init.argtypes = [P(BuildingCloudParams)]
     lib.dgs_building_cloud_generate.argtypes = [C.c_void_p, P(BuildingCloudParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                 P(C.c_int64)]

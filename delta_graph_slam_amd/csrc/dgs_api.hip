@@ -528,6 +528,7 @@ int dgs_create(const dgs_params* params, dgs_handle** out) {
   if (const char* e = std::getenv("DGS_KNN_ROUNDS")) h->knn_rounds = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("DGS_COV_BATCH_POINTS")) h->cb.points_budget = std::min<int64_t>(std::max<int64_t>(0, std::atoll(e)), (int64_t)32 << 20);
   if (const char* e = std::getenv("DGS_PREFILTER_BATCH_POINTS")) h->pfb.points_budget = std::max<int64_t>(0, std::atoll(e));
+  if (const char* e = std::getenv("DGS_FLOOR_BATCH_POINTS")) h->fdb.points_budget = std::max<int64_t>(0, std::atoll(e));
   if (const char* e = std::getenv("DGS_GICP_FUSED")) h->gicp_fused = std::atoi(e) != 0;
   if (kExperiments)
     if (const char* e = std::getenv("DGS_NDT_PACK2")) h->ndt_pack2 = std::atoi(e) != 0;
@@ -576,6 +577,7 @@ void dgs_destroy(dgs_handle* h) {
   line_edges_release(h);
   building_overlap_release(h);
   floor_detection_release(h);
+  floor_detection_batch_release(h);
   fitness_batch_release(h);
   building_cloud_release(h);
   voxel_batch_release(h);

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstring>
 #include "compact.h"
+#include "floor_detection_body.h"
 #include "handle.h"
 #include "nn_group.h"
 #include "sac.h"
@@ -31,136 +32,26 @@ namespace dgs {
 __global__ void pf_normal_kernel(const BvhView b, const float4* __restrict__ pts, const int n, const int k, const int* __restrict__ nbr, const float vx,
                                  const float vy, const float vz, unsigned char* __restrict__ flags, float4* __restrict__ normals, float* __restrict__ cov9);
 
-constexpr int kFdHypSub = 64;            // hypotheses per workgroup of sac_score_kernel (blockIdx.y)
-constexpr int kFdNormalK = 10;           // ne.setKSearch(10) (:219)
-
-struct FdHyp {
-  float c[4];
-  int draw, i0, i1, i2;
-};
-
-struct FdMat {
-  float m[16];   // row-major
-};
-
-// a four-term float dot product, the terms associated as plane_dot_order says
-__host__ __device__ __forceinline__ float fd_dot4(const float a0, const float a1, const float a2, const float a3, const float b0, const float b1,
-                                                  const float b2, const float b3, const int order) {
-#pragma clang fp contract(off)
-  const float x = a0 * b0, y = a1 * b1, z = a2 * b2, w = a3 * b3;
-  return order == 0 ? (x + y) + (z + w) : order == 1 ? (x + z) + (y + w) : ((x + y) + z) + w;
-}
-
-// countWithinDistance / selectWithinDistance: |dot4(coefficients, (x, y, z, 1))| < threshold, compared in double
-__host__ __device__ __forceinline__ bool fd_is_inlier(const float4 p, const float a, const float b, const float c, const float d, const int order,
-                                                      const double thr) {
-  return (double)fabsf(fd_dot4(a, b, c, d, p.x, p.y, p.z, 1.0f, order)) < thr;
-}
-
-// pcl::transformPointCloud(Matrix4f): a non-finite point goes through the arithmetic, the fourth float becomes 1
-__device__ __forceinline__ float4 fd_transform(const float4 p, const FdMat& M, const int order) {
-#pragma clang fp contract(off)
-  float4 q;
-  const float* m = M.m;
-  if (order == 0) {
-    q.x = p.x * m[0] + (p.y * m[1] + (p.z * m[2] + m[3]));
-    q.y = p.x * m[4] + (p.y * m[5] + (p.z * m[6] + m[7]));
-    q.z = p.x * m[8] + (p.y * m[9] + (p.z * m[10] + m[11]));
-  } else {
-    q.x = ((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3];
-    q.y = ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7];
-    q.z = ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11];
-  }
-  q.w = 1.0f;
-  return q;
-}
-
 // ================================================================================================ filter stage
-// tilt, then plane_clip twice (:117-119): PlaneClipper3D keeps a point whose float distance ((0*x + 0*y) + 1*z) + d is >= 0; the second
-// clip is negated
+// the bodies, the transform and the plane model: floor_detection_body.h, shared with floor_detection_batch.hip
 __global__ __launch_bounds__(kBlock) void fd_tilt_clip_kernel(const float4* __restrict__ in, const int n, const FdMat M, const int order, const float hi,
                                                               const float lo, float4* __restrict__ out, unsigned char* __restrict__ flags) {
-#pragma clang fp contract(off)
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const float4 q = fd_transform(in[i], M, order);
-  const float base = (0.0f * q.x + 0.0f * q.y) + 1.0f * q.z;
-  const float dhi = base + hi, dlo = base + lo;
-  out[i] = q;
-  flags[i] = (dhi >= 0.0f && !(dlo >= 0.0f)) ? 1 : 0;
+  fd_tilt_clip_body(in, n, M, order, hi, lo, out, flags, (int)blockIdx.x);
 }
 
-// normal_filtering's rule (:227-228) over the normals pf_normal_kernel wrote: kept iff |n.z| > cos(normal_filter_thresh) in double; a NaN
-// normal fails the comparison
 __global__ __launch_bounds__(kBlock) void fd_normal_flag_kernel(const float4* __restrict__ normals, const int n, const double cos_thr,
                                                                 unsigned char* __restrict__ flags) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = ((double)fabsf(normals[i].z) > cos_thr) ? 1 : 0;
+  fd_normal_flag_body(normals, n, cos_thr, flags, (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(kBlock) void fd_transform_kernel(const float4* __restrict__ in, const int n, const FdMat M, const int order,
                                                               float4* __restrict__ out) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  out[i] = fd_transform(in[i], M, order);
+  fd_transform_body(in, n, M, order, out, (int)blockIdx.x);
 }
 
-// ================================================================================================ hypotheses
-// pcl::SampleConsensusModelPlane for sac.h's kernels: isSampleGood, computeModelCoefficients and the countWithinDistance predicate
-struct FdModel {
-  static constexpr int kSample = 3;
-  using Hyp = FdHyp;
-  struct Params {
-    int order, bad_run;   // plane_dot_order, max_sample_checks
-    double thr;           // distance_threshold
-  };
-  struct Coef {
-    float a, b, c, d;
-  };
-  static __device__ __forceinline__ int bad_run(const Params& prm) { return prm.bad_run; }
-  // computeModel's w^3 for SacWalk::step, which runs on the host: upstream's own libm
-  static double ratio_power(double w) { return std::pow(w, 3.0); }
-  // dy1dy2 = (p1 - p0) / (p2 - p0), component-wise; good iff its x, y, z are not all equal (NaN compares unequal)
-  static __device__ __forceinline__ bool good(const Params&, const float4 (&p)[3]) {
-#pragma clang fp contract(off)
-    const float rx = (p[1].x - p[0].x) / (p[2].x - p[0].x), ry = (p[1].y - p[0].y) / (p[2].y - p[0].y), rz = (p[1].z - p[0].z) / (p[2].z - p[0].z);
-    return rx != ry || rz != ry;
-  }
-  static __device__ __forceinline__ FdHyp make(const Params& prm, const float4 (&p)[3], const int d, const int (&idx)[3]) {
-#pragma clang fp contract(off)
-    const float ux = p[1].x - p[0].x, uy = p[1].y - p[0].y, uz = p[1].z - p[0].z;
-    const float vx = p[2].x - p[0].x, vy = p[2].y - p[0].y, vz = p[2].z - p[0].z;
-    float a = uy * vz - uz * vy;
-    float b = uz * vx - ux * vz;
-    float c = ux * vy - uy * vx;
-    // model_coefficients.normalize(): divided by sqrt(squaredNorm) when that is > 0
-    const float s2 = fd_dot4(a, b, c, 0.f, a, b, c, 0.f, prm.order);
-    if (s2 > 0.f) {
-      const float s = sqrtf(s2);
-      a = a / s; b = b / s; c = c / s;
-    }
-    FdHyp hy;
-    hy.c[0] = a; hy.c[1] = b; hy.c[2] = c;
-    hy.c[3] = -1.0f * fd_dot4(a, b, c, 0.f, p[0].x, p[0].y, p[0].z, p[0].w, prm.order);
-    hy.draw = d; hy.i0 = idx[0]; hy.i1 = idx[1]; hy.i2 = idx[2];
-    return hy;
-  }
-  static __device__ __forceinline__ Coef coef(const FdHyp* hy) { return {hy->c[0], hy->c[1], hy->c[2], hy->c[3]}; }
-  static __device__ __forceinline__ bool inlier(const Params& prm, const float4 p, const Coef& c) {
-    return fd_is_inlier(p, c.a, c.b, c.c, c.d, prm.order, prm.thr);
-  }
-};
 
 // ================================================================================================ host side
 namespace {
-
-FdMat fd_mat(const float* col16) {
-  FdMat M;
-  for (int r = 0; r < 4; r++)
-    for (int c = 0; c < 4; c++) M.m[4 * r + c] = col16[4 * c + r];
-  return M;
-}
 
 // steps 1-4: -> the filtered cloud in fd.filtered, its size in *nf
 int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* tilt16, const float* tilt_inv16, const float4* in, int64_t n, int64_t* nf) {
@@ -210,12 +101,13 @@ int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   return DGS_OK;
 }
 
-// steps 5-8 over fd.filtered (n >= 3 points) with a draw list of D draws: the walk's end state in fd.trace, the winner's coefficients in
-// coeffs, the filtered cloud in fd.host_filtered.  *need_draws when the walk ran past the list.
-int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, const uint32_t* raw, int64_t D, bool* need_draws, float* coeffs) {
-  FdScratch& fd = h->fd;
-  SacScratch& sac = fd.sac;
-  dgs_floor_detection_trace& tr = fd.trace;
+}  // namespace
+
+// steps 5-8 over `pts` (n >= 3 points) with a draw list of D draws, in the buffers handed in (the single call's FdScratch, or the batch's
+// for a scan it finishes alone): the walk's end state in tr, the winner's coefficients in coeffs, the filtered cloud in *host_cloud.
+// *need_draws when the walk ran past the list.
+int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float4* pts, int64_t n, const uint32_t* raw, int64_t D, SacScratch& sac,
+              DevBuf<FdHyp>& hyps, dgs_floor_detection_trace& tr, std::vector<float4>* host_cloud, bool* need_draws, float* coeffs) {
   const int max_hyp = p.max_iterations + 1;
   // pinned block: meta | hypotheses | counts | filtered cloud | draw list
   const size_t off_hyp = 64, off_cnt = off_hyp + (size_t)max_hyp * sizeof(FdHyp), off_cloud = (off_cnt + (size_t)max_hyp * sizeof(int) + 63) / 64 * 64;
@@ -227,16 +119,16 @@ int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, con
   int* h_cnt = reinterpret_cast<int*>(pin + off_cnt);
   int* h_draws = reinterpret_cast<int*>(pin + off_draws);
   DGS_HIP_TRY(h, sac.draws.reserve((size_t)D * 3));
-  DGS_HIP_TRY(h, fd.hyps.reserve((size_t)max_hyp));
+  DGS_HIP_TRY(h, hyps.reserve((size_t)max_hyp));
   DGS_HIP_TRY(h, sac.counts.reserve((size_t)max_hyp));
   DGS_HIP_TRY(h, sac.meta.reserve(4));
   sac_grow_perm(sac.perm, n);
   sac_draws<3>(sac.perm, raw, n, D, h_draws);
   DGS_HIP_TRY(h, hipMemcpyAsync(sac.draws.ptr, h_draws, (size_t)D * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
   const FdModel::Params prm{p.plane_dot_order, p.max_sample_checks, p.distance_threshold};
-  hipLaunchKernelGGL(sac_prepare_kernel<FdModel>, dim3(1), dim3(kSacPrepareBlock), 0, h->stream, fd.filtered.ptr, (int)n, sac.draws.ptr, (int)D, prm,
-                     max_hyp, fd.hyps.ptr, sac.counts.ptr, sac.meta.ptr);
-  DGS_HIP_TRY(h, hipMemcpyAsync(pin + off_cloud, fd.filtered.ptr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+  hipLaunchKernelGGL(sac_prepare_kernel<FdModel>, dim3(1), dim3(kSacPrepareBlock), 0, h->stream, pts, (int)n, sac.draws.ptr, (int)D, prm,
+                     max_hyp, hyps.ptr, sac.counts.ptr, sac.meta.ptr);
+  DGS_HIP_TRY(h, hipMemcpyAsync(pin + off_cloud, pts, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
 
   SacWalk wk;
   const double log_one_minus_p = std::log(1.0 - p.probability);
@@ -250,10 +142,10 @@ int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, con
       const int h_end = (int)std::min<int64_t>(max_hyp, (int64_t)scored + (chunks == 0 ? p.hyp_chunk_first : p.hyp_chunk));
       hipLaunchKernelGGL((sac_score_kernel<FdModel, kFdHypSub>),
                          dim3((unsigned)((n + kSacTile - 1) / kSacTile), (unsigned)((h_end - scored + kFdHypSub - 1) / kFdHypSub)), dim3(kBlock), 0,
-                         h->stream, fd.filtered.ptr, (int)n, fd.hyps.ptr, sac.meta.ptr, max_hyp, scored, h_end, prm, sac.counts.ptr);
+                         h->stream, pts, (int)n, hyps.ptr, sac.meta.ptr, max_hyp, scored, h_end, prm, sac.counts.ptr);
       DGS_HIP_TRY(h, hipGetLastError());
       DGS_HIP_TRY(h, hipMemcpyAsync(h_meta, sac.meta.ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      DGS_HIP_TRY(h, hipMemcpyAsync(h_hyp + scored, fd.hyps.ptr + scored, (size_t)(h_end - scored) * sizeof(FdHyp), hipMemcpyDeviceToHost, h->stream));
+      DGS_HIP_TRY(h, hipMemcpyAsync(h_hyp + scored, hyps.ptr + scored, (size_t)(h_end - scored) * sizeof(FdHyp), hipMemcpyDeviceToHost, h->stream));
       DGS_HIP_TRY(h, hipMemcpyAsync(h_cnt + scored, sac.counts.ptr + scored, (size_t)(h_end - scored) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
       DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
       chunks++;
@@ -272,8 +164,8 @@ int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, int64_t n, con
   tr.ransac_failed = wk.status == SAC_FAILED ? 1 : 0;
   *need_draws = wk.status == SAC_NEED_DRAWS;
   if (*need_draws) return DGS_OK;
-  fd.host_filtered.resize((size_t)n);
-  std::memcpy(fd.host_filtered.data(), pin + off_cloud, (size_t)n * sizeof(float4));
+  host_cloud->resize((size_t)n);
+  std::memcpy(host_cloud->data(), pin + off_cloud, (size_t)n * sizeof(float4));
   if (wk.win >= 0) {
     const FdHyp& w = h_hyp[wk.win];
     tr.winner_rank = wk.win;
@@ -296,6 +188,8 @@ const char* fd_bad_params(const dgs_floor_detection_params* p) {
   if (!(p->probability > 0.0 && p->probability < 1.0)) return "floor detection: probability must lie in (0, 1)";
   return nullptr;
 }
+
+namespace {
 
 int fd_detect(dgs_handle* h, const dgs_floor_detection_params& p, const float* tilt16, const float* tilt_inv16, const float* in_xyz16, int64_t n,
               int32_t in_on_device, const uint32_t* rng_raw, int64_t rng_len, float* coeffs4_out, int32_t* status_out) {
@@ -340,7 +234,7 @@ int fd_detect(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
         raw = fd.sac.mt_raw.data();
       }
       bool need_draws = false;
-      if (int rc = fd_ransac(h, p, nf, raw, plan.D, &need_draws, coeffs)) return rc;
+      if (int rc = fd_ransac(h, p, fd.filtered.ptr, nf, raw, plan.D, fd.sac, fd.hyps, tr, &fd.host_filtered, &need_draws, coeffs)) return rc;
       if (!need_draws) break;
       if (!plan.grow()) { *status_out = DGS_FD_RNG_EXHAUSTED; return DGS_OK; }
     }

@@ -326,6 +326,40 @@ struct PfbScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// dgs_floor_detection_batch (floor_detection_batch.hip): detect() over many scans in one chain.  Per scan the clipped cloud with its
+// index, its normals and its filtered cloud stay on the device until the next batch; the getters read them by scan number.  The normal
+// stage runs in a PfbScratch of the batch's own (prefilter_batch_normal_stage).  Separate from FdScratch: the single call's buffers and
+// getters are not touched.
+struct FdbScan {
+  int64_t n = 0, n_clipped = 0, n_filtered = 0;
+  bool have_normals = false, have_host = false, have_inliers = false;
+  int32_t status = 1;                  // DGS_FD_TOO_FEW_POINTS
+  float coeffs[4] = {0.f, 0.f, 0.f, 0.f};
+  dgs_floor_detection_trace trace{};
+  std::vector<float4> host_filtered;   // fetched when a getter asks for the inliers
+  std::vector<int32_t> inliers;
+};
+struct FdbScratch {
+  std::vector<CloudState> clip;        // per scan: the clipped cloud and (normal filter) its index
+  std::vector<DevBuf<float4>> normals, filtered;   // per scan
+  std::vector<FdbScan> scans;          // of the last batch
+  PfbScratch nrm;                      // the normal stage's index build, lists, tables and pinned block
+  DevBuf<float4> in, tilted, kept;     // staged host inputs; after the tilt; after the normal filter: all scans of a chunk back to back
+  DevBuf<unsigned char> flags;         // keep flags, every scan padded to whole workgroups
+  DevBuf<int> blk, cnt, totals;        // the segmented compaction's counts, total and per-scan totals
+  DevBuf<unsigned char> tables;        // the stage's table: entries | first workgroups
+  PinnedBlock stage;                   // a filter stage's table goes up from it, the totals come down into it
+  DevBuf<unsigned char> sac_tables;    // the RANSAC's table: entries | first tiles
+  PinnedBlock sac_stage;               // its upload, the draw lists behind it, and where meta, counts and hypotheses come down
+  DevBuf<int> draws, counts, meta;     // per live scan: its draw list; max_hyp counts; 4 ints of meta
+  DevBuf<FdHyp> hyps;                  // per live scan max_hyp records
+  SacScratch sac;                      // mt19937 values and the identity permutation; the device buffers of a scan finished alone
+  DevBuf<FdHyp> hyps_single;           // that scan's hypotheses
+  dgs_floor_detection_params params{}; // of the last batch: the getters' inlier rule
+  int64_t points_budget = 0;           // DGS_FLOOR_BATCH_POINTS (0: fdbplan::kBatchPoints)
+  int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 }  // namespace dgs
 
 struct dgs_handle;
@@ -567,6 +601,7 @@ struct dgs_handle {
 
   // ---- the prefilter over many scans (prefilter_batch.hip): own buffers and indices; PfScratch and everything above is left untouched
   dgs::PfbScratch pfb;
+  dgs::FdbScratch fdb;
 
   dgs::Profiler prof;
 };
@@ -690,6 +725,13 @@ void set_handleless_error(const char* why);
 void building_overlap_release(dgs_handle* h);
 // floor_detection.hip
 void floor_detection_release(dgs_handle* h);
+const char* fd_bad_params(const dgs_floor_detection_params* p);   // why the parameters are refused, or nullptr
+// steps 5-8 of detect() over `pts` (n >= 3 points on the device) with a draw list of D draws, in the buffers handed in: the walk's end
+// state in `tr`, the winner's coefficients in `coeffs`, the cloud in *host_cloud.  *need_draws when the walk ran past the list.
+int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float4* pts, int64_t n, const uint32_t* raw, int64_t D, SacScratch& sac,
+              DevBuf<FdHyp>& hyps, dgs_floor_detection_trace& tr, std::vector<float4>* host_cloud, bool* need_draws, float* coeffs);
+// floor_detection_batch.hip
+void floor_detection_batch_release(dgs_handle* h);
 // What a batched stage that runs inside another call did: the stage adds to the sink its caller hands it, the caller folds the sink
 // into the counts8 of its own call.
 struct StageCounts {
@@ -727,6 +769,13 @@ int voxelgrid_batch(dgs_handle* h, int n, const float4* const* d_in, const int64
 void voxel_batch_release(dgs_handle* h);
 // prefilter_batch.hip
 void prefilter_batch_release(dgs_handle* h);
+void prefilter_batch_release(PfbScratch& S);
+// The normal stage of the batched chain for another call (floor_detection_batch.hip), in the scratch S it hands in: the batched index
+// build over pool[s] for every scan s < n with sizes[s] > 0, the k = min(10, size) lists and pf_normal_body with one view point,
+// normals of scan s -> normals[s].  Launches only: nobody waits.  Launches, waits and builds are added to S.counts8; *fell_back: the
+// lists came from the per-query walk scan by scan (DGS_KNN_LEAF=0).
+int prefilter_batch_normal_stage(dgs_handle* h, PfbScratch& S, int n, CloudState* pool, const int64_t* sizes, float vx, float vy, float vz,
+                                 float4* const* normals, bool* fell_back);
 // dgs_api.hip: the handles that borrow `c` as target or source fall back to "no input set" (what dgs_cloud_destroy does first)
 void cloud_detach_users(dgs_cloud* c);
 // pcl_gicp.hip

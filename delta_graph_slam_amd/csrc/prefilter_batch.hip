@@ -154,8 +154,7 @@ struct PfbDev {
 
 // entries | heads | first workgroups | first search workgroups -> S.tables in one copy from the pinned block.  The stream is idle here
 // (every stage ended with a host wait), so the block may be rewritten and regrown.
-int pfb_upload(dgs_handle* h, const pfbplan::Stage& St, const std::vector<PfbSeg>& segs, const PfHead* heads, PfbDev* dev) {
-  PfbScratch& S = h->pfb;
+int pfb_upload(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, const std::vector<PfbSeg>& segs, const PfHead* heads, PfbDev* dev) {
   const size_t m = St.items.size();
   const segtab::StageTable T = segtab::stage_table(m, sizeof(PfbSeg), heads ? sizeof(PfHead) : 0);
   DGS_HIP_TRY(h, S.stage.reserve(T.all));
@@ -179,8 +178,7 @@ int pfb_upload(dgs_handle* h, const pfbplan::Stage& St, const std::vector<PfbSeg
 }
 
 // the flag array of a stage and every entry's place in it
-int pfb_flags(dgs_handle* h, const pfbplan::Stage& St, std::vector<PfbSeg>& segs) {
-  PfbScratch& S = h->pfb;
+int pfb_flags(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, std::vector<PfbSeg>& segs) {
   DGS_HIP_TRY(h, S.flags.reserve((size_t)St.blocks * kBlock));
   for (size_t j = 0; j < segs.size(); j++) {
     const pfbplan::Item& it = St.items[j];
@@ -194,8 +192,7 @@ int pfb_flags(dgs_handle* h, const pfbplan::Stage& St, std::vector<PfbSeg>& segs
 }
 
 // count, scan, scatter over all scans of the stage; kept[j] = kept points of item j (read back: the host waits here)
-int pfb_compact(dgs_handle* h, const pfbplan::Stage& St, const PfbDev& dev, bool head, bool flatten, std::vector<int64_t>& kept) {
-  PfbScratch& S = h->pfb;
+int pfb_compact(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, const PfbDev& dev, bool head, bool flatten, std::vector<int64_t>& kept) {
   const int m = (int)St.items.size();
   DGS_HIP_TRY(h, S.blk.reserve((size_t)St.blocks + 1));
   DGS_HIP_TRY(h, S.cnt.reserve(4));
@@ -216,8 +213,7 @@ int pfb_compact(dgs_handle* h, const pfbplan::Stage& St, const PfbDev& dev, bool
 }
 
 // indices of the stage's input clouds by the batched build, their k-NN lists into S.nbr; the entries get views and slices
-int pfb_knn(dgs_handle* h, const pfbplan::Stage& St, std::vector<CloudState>& pool, std::vector<PfbSeg>& segs) {
-  PfbScratch& S = h->pfb;
+int pfb_knn(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, CloudState* pool, std::vector<PfbSeg>& segs) {
   const int m = (int)St.items.size();
   std::vector<CloudState*> cs((size_t)m);
   for (int j = 0; j < m; j++) cs[j] = &pool[St.items[j].scan];
@@ -237,8 +233,7 @@ int pfb_knn(dgs_handle* h, const pfbplan::Stage& St, std::vector<CloudState>& po
   return DGS_OK;
 }
 // the search launch over the uploaded table, or (DGS_KNN_LEAF=0) the per-query walk scan by scan into the same slices
-int pfb_knn_search(dgs_handle* h, const pfbplan::Stage& St, std::vector<CloudState>& pool, const std::vector<PfbSeg>& segs, const PfbDev& dev, bool leaf) {
-  PfbScratch& S = h->pfb;
+int pfb_knn_search(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, CloudState* pool, const std::vector<PfbSeg>& segs, const PfbDev& dev, bool leaf) {
   const int m = (int)St.items.size();
   if (leaf) {
     hipLaunchKernelGGL(pfb_knn_kernel, dim3((unsigned)St.knn_blocks), dim3(kBlock), 0, h->stream, dev.tab, dev.knn_first, m, h->knn_stats.ptr);
@@ -277,20 +272,20 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
     for (int s = 0; s < n; s++) { cur[s] = 0; src[s] = &S.a[s]; S.a[s].n = 0; S.a[s].invalidate(); }
     if (m > 0) {
       segs.assign((size_t)m, PfbSeg{});
-      if (int rc = pfb_flags(h, St, segs)) return rc;
+      if (int rc = pfb_flags(h, S, St, segs)) return rc;
       for (int j = 0; j < m; j++) {
         const int s = St.items[j].scan;
         DGS_HIP_TRY(h, S.a[s].pts.reserve((size_t)sizes[s]));
         segs[j].in = d_in[s];
         segs[j].out = S.a[s].pts.ptr;
       }
-      if (int rc = pfb_upload(h, St, segs, heads, &dev)) return rc;
+      if (int rc = pfb_upload(h, S, St, segs, heads, &dev)) return rc;
       if (heads)
         hipLaunchKernelGGL(pfb_head_flag_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.heads, dev.first, m, p->distance_near_thresh, p->distance_far_thresh);
       else
         hipLaunchKernelGGL(pfb_distance_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.first, m, p->distance_near_thresh, p->distance_far_thresh);
       S.counts8[0]++;
-      if (int rc = pfb_compact(h, St, dev, heads != nullptr, false, kept)) return rc;
+      if (int rc = pfb_compact(h, S, St, dev, heads != nullptr, false, kept)) return rc;
       for (int j = 0; j < m; j++) { cur[St.items[j].scan] = kept[j]; S.a[St.items[j].scan].n = kept[j]; }
     }
   }
@@ -351,10 +346,10 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
     const int m = (int)St.items.size();
     if (m > 0) {
       segs.assign((size_t)m, PfbSeg{});
-      if (int rc = pfb_flags(h, St, segs)) return rc;
+      if (int rc = pfb_flags(h, S, St, segs)) return rc;
       // the stage's input clouds are a or b, whichever every scan's points stand in
       std::vector<CloudState>& pool = p->downsample_method != DGS_PF_DOWNSAMPLE_NONE ? S.b : S.a;
-      if (int rc = pfb_knn(h, St, pool, segs)) return rc;
+      if (int rc = pfb_knn(h, S, St, pool.data(), segs)) return rc;
       if (stat) {
         DGS_HIP_TRY(h, S.mean_d.reserve((size_t)St.points));
         DGS_HIP_TRY(h, S.stats.reserve((size_t)n * 4));
@@ -369,8 +364,8 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
           segs[j].stats = S.stats.ptr + (size_t)j * 4;
         }
       }
-      if (int rc = pfb_upload(h, St, segs, nullptr, &dev)) return rc;
-      if (int rc = pfb_knn_search(h, St, pool, segs, dev, !fallback_knn)) return rc;
+      if (int rc = pfb_upload(h, S, St, segs, nullptr, &dev)) return rc;
+      if (int rc = pfb_knn_search(h, S, St, pool.data(), segs, dev, !fallback_knn)) return rc;
       fell_back = fell_back || fallback_knn;
       if (stat) {
         hipLaunchKernelGGL(pfb_sor_distance_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.first, m, p->statistical_sqrt_float);
@@ -383,7 +378,7 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
         hipLaunchKernelGGL(pfb_radius_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.first, m, p->radius_radius * p->radius_radius, p->radius_inclusive);
         S.counts8[0]++;
       }
-      if (int rc = pfb_compact(h, St, dev, false, false, kept)) return rc;
+      if (int rc = pfb_compact(h, S, St, dev, false, false, kept)) return rc;
       for (int j = 0; j < m; j++) {
         const int s = St.items[j].scan;
         cur[s] = kept[j];
@@ -407,7 +402,7 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
     for (int s = 0; s < n; s++) cur[s] = 0;
     if (m > 0) {
       segs.assign((size_t)m, PfbSeg{});
-      if (int rc = pfb_flags(h, St, segs)) return rc;
+      if (int rc = pfb_flags(h, S, St, segs)) return rc;
       for (int j = 0; j < m; j++) {
         const int s = St.items[j].scan;
         DGS_HIP_TRY(h, S.d[s].pts.reserve((size_t)St.items[j].n));
@@ -415,10 +410,10 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
         segs[j].out = S.d[s].pts.ptr;
         segs[j].lz = lidar3[(size_t)s * 3 + 2];
       }
-      if (int rc = pfb_upload(h, St, segs, nullptr, &dev)) return rc;
+      if (int rc = pfb_upload(h, S, St, segs, nullptr, &dev)) return rc;
       hipLaunchKernelGGL(pfb_height_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.first, m);
       S.counts8[0]++;
-      if (int rc = pfb_compact(h, St, dev, false, false, kept)) return rc;
+      if (int rc = pfb_compact(h, S, St, dev, false, false, kept)) return rc;
       for (int j = 0; j < m; j++) { cur[St.items[j].scan] = kept[j]; S.d[St.items[j].scan].n = kept[j]; }
     }
   }
@@ -430,8 +425,8 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
     for (int s = 0; s < n; s++) cur[s] = 0;
     if (m > 0) {
       segs.assign((size_t)m, PfbSeg{});
-      if (int rc = pfb_flags(h, St, segs)) return rc;
-      if (int rc = pfb_knn(h, St, S.d, segs)) return rc;
+      if (int rc = pfb_flags(h, S, St, segs)) return rc;
+      if (int rc = pfb_knn(h, S, St, S.d.data(), segs)) return rc;
       DGS_HIP_TRY(h, S.normals.reserve((size_t)St.points));
       DGS_HIP_TRY(h, S.cov9.reserve((size_t)St.points * 9));
       for (int j = 0; j < m; j++) {
@@ -445,12 +440,12 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
         segs[j].vy = (float)lidar3[(size_t)s * 3 + 1];
         segs[j].vz = (float)lidar3[(size_t)s * 3 + 2];
       }
-      if (int rc = pfb_upload(h, St, segs, nullptr, &dev)) return rc;
-      if (int rc = pfb_knn_search(h, St, S.d, segs, dev, !fallback_knn)) return rc;
+      if (int rc = pfb_upload(h, S, St, segs, nullptr, &dev)) return rc;
+      if (int rc = pfb_knn_search(h, S, St, S.d.data(), segs, dev, !fallback_knn)) return rc;
       fell_back = fell_back || fallback_knn;
       hipLaunchKernelGGL(pfb_normal_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.first, m);
       S.counts8[0]++;
-      if (int rc = pfb_compact(h, St, dev, false, true, kept)) return rc;
+      if (int rc = pfb_compact(h, S, St, dev, false, true, kept)) return rc;
       for (int j = 0; j < m; j++) { cur[St.items[j].scan] = kept[j]; S.e[St.items[j].scan].n = kept[j]; S.counts8[3]++; }
     }
   }
@@ -475,8 +470,38 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
 
 }  // namespace
 
-void prefilter_batch_release(dgs_handle* h) {
-  PfbScratch& S = h->pfb;
+// stage 5 of pfb_chain without its compaction, for a caller with a rule of its own over the normals
+int prefilter_batch_normal_stage(dgs_handle* h, PfbScratch& S, int n, CloudState* pool, const int64_t* sizes, float vx, float vy, float vz,
+                                 float4* const* normals, bool* fell_back) {
+  const pfbplan::Stage St = pfbplan::make_stage(n, sizes, true, h->knn_parts);
+  const int m = (int)St.items.size();
+  *fell_back = false;
+  if (m == 0) return DGS_OK;
+  const bool fallback_knn = !knn_uses_leaf_search(h, kKnnMax);
+  std::vector<PfbSeg> segs((size_t)m, PfbSeg{});
+  PfbDev dev{};
+  if (int rc = pfb_flags(h, S, St, segs)) return rc;   // the prefilter rule's flags: written by the body, read by nobody
+  if (int rc = pfb_knn(h, S, St, pool, segs)) return rc;
+  DGS_HIP_TRY(h, S.cov9.reserve((size_t)St.points * 9));
+  for (int j = 0; j < m; j++) {
+    segs[j].k = (int)std::min<int64_t>(kPfNormalK, St.items[j].n);   // FLANN returns min(k, n) neighbours
+    segs[j].normals = normals[St.items[j].scan];
+    segs[j].cov9 = S.cov9.ptr + (size_t)St.items[j].point0 * 9;
+    segs[j].vx = vx;
+    segs[j].vy = vy;
+    segs[j].vz = vz;
+  }
+  if (int rc = pfb_upload(h, S, St, segs, nullptr, &dev)) return rc;
+  if (int rc = pfb_knn_search(h, S, St, pool, segs, dev, !fallback_knn)) return rc;
+  hipLaunchKernelGGL(pfb_normal_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, h->stream, dev.tab, dev.first, m);
+  S.counts8[0]++;
+  DGS_HIP_TRY(h, hipGetLastError());
+  *fell_back = fallback_knn;
+  return DGS_OK;
+}
+
+void prefilter_batch_release(dgs_handle* h) { prefilter_batch_release(h->pfb); }
+void prefilter_batch_release(PfbScratch& S) {
   for (std::vector<CloudState>* pool : {&S.a, &S.b, &S.c, &S.d, &S.e}) {
     for (CloudState& c : *pool) c.release();
     pool->clear();

@@ -148,11 +148,11 @@ constexpr int kSacTile = kSacTilePoints * kBlock;
 // One workgroup over the D draws in chunks of 1024, in order: good flag, rank among the good ones, distance to the last good one.  The
 // good draws become hyps[0 .. min(good draws, max_hyp)) in order; counts[0 .. max_hyp) = 0; meta[0] = good draws, meta[1] = the first draw
 // that completes bad_run bad ones in a row (INT_MAX: none).
+// The body: the whole workgroup of a launch over one list, or of a launch with one workgroup per list (floor_detection_batch.hip).
 template <class Model>
-__global__ __launch_bounds__(kSacPrepareBlock) void sac_prepare_kernel(const float4* __restrict__ pts, const int n, const int* __restrict__ draws,
-                                                                      const int D, const typename Model::Params prm, const int max_hyp,
-                                                                      typename Model::Hyp* __restrict__ hyps, int* __restrict__ counts,
-                                                                      int* __restrict__ meta) {
+__device__ __forceinline__ void sac_prepare_body(const float4* __restrict__ pts, const int n, const int* __restrict__ draws, const int D,
+                                                 const typename Model::Params& prm, const int max_hyp, typename Model::Hyp* __restrict__ hyps,
+                                                 int* __restrict__ counts, int* __restrict__ meta) {
   constexpr int K = Model::kSample;
   __shared__ int s_w[kSacPrepareBlock / kWave], s_l[kSacPrepareBlock / kWave];
   __shared__ int s_rank, s_last, s_fail;
@@ -208,17 +208,26 @@ __global__ __launch_bounds__(kSacPrepareBlock) void sac_prepare_kernel(const flo
     meta[1] = s_fail;
   }
 }
+template <class Model>
+__global__ __launch_bounds__(kSacPrepareBlock) void sac_prepare_kernel(const float4* __restrict__ pts, const int n, const int* __restrict__ draws,
+                                                                      const int D, const typename Model::Params prm, const int max_hyp,
+                                                                      typename Model::Hyp* __restrict__ hyps, int* __restrict__ counts,
+                                                                      int* __restrict__ meta) {
+  sac_prepare_body<Model>(pts, n, draws, D, prm, max_hyp, hyps, counts, meta);
+}
 
 // grid (tiles of 1024 points, groups of kHypPerGroup hypotheses of the chunk [h_first, h_end)).  A workgroup holds its tile in registers
 // and walks its hypotheses, whose coefficients sit at wave-uniform addresses; an inlier count is one ballot and popcount per wave,
 // gathered per workgroup in LDS and added to the hypothesis' global count with one atomic.
+// The body takes the workgroup's tile inside its own cloud and its group of hypotheses inside its own chunk: blockIdx.x and blockIdx.y
+// of the launch over one cloud, or what a launch over the tiles of many clouds finds for the workgroup (floor_detection_batch.hip).
 template <class Model, int kHypPerGroup>
-__global__ __launch_bounds__(kBlock) void sac_score_kernel(const float4* __restrict__ pts, const int n, const typename Model::Hyp* __restrict__ hyps,
-                                                           const int* __restrict__ meta, const int max_hyp, const int h_first, const int h_end,
-                                                           const typename Model::Params prm, int* __restrict__ counts) {
+__device__ __forceinline__ void sac_score_body(const float4* __restrict__ pts, const int n, const typename Model::Hyp* __restrict__ hyps,
+                                               const int* __restrict__ meta, const int max_hyp, const int h_first, const int h_end,
+                                               const typename Model::Params& prm, int* __restrict__ counts, const int tile, const int group) {
   __shared__ int s_cnt[kHypPerGroup];
   const int H = min(min(meta[0], max_hyp), h_end);
-  const int h0 = h_first + blockIdx.y * kHypPerGroup;
+  const int h0 = h_first + group * kHypPerGroup;
   if (h0 >= H) return;   // uniform per workgroup
   const int h1 = min(h0 + kHypPerGroup, H);
   for (int j = threadIdx.x; j < kHypPerGroup; j += kBlock) s_cnt[j] = 0;
@@ -226,7 +235,7 @@ __global__ __launch_bounds__(kBlock) void sac_score_kernel(const float4* __restr
   bool ok[kSacTilePoints];
 #pragma unroll
   for (int k = 0; k < kSacTilePoints; k++) {
-    const long long i = (long long)blockIdx.x * kSacTile + k * kBlock + threadIdx.x;
+    const long long i = (long long)tile * kSacTile + k * kBlock + threadIdx.x;
     ok[k] = i < n;
     p[k] = ok[k] ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
   }
@@ -242,6 +251,12 @@ __global__ __launch_bounds__(kBlock) void sac_score_kernel(const float4* __restr
   __syncthreads();
   for (int j = threadIdx.x; j < h1 - h0; j += kBlock)
     if (s_cnt[j]) atomicAdd(&counts[h0 + j], s_cnt[j]);   // h0 + j < h1 <= max_hyp
+}
+template <class Model, int kHypPerGroup>
+__global__ __launch_bounds__(kBlock) void sac_score_kernel(const float4* __restrict__ pts, const int n, const typename Model::Hyp* __restrict__ hyps,
+                                                           const int* __restrict__ meta, const int max_hyp, const int h_first, const int h_end,
+                                                           const typename Model::Params prm, int* __restrict__ counts) {
+  sac_score_body<Model, kHypPerGroup>(pts, n, hyps, meta, max_hyp, h_first, h_end, prm, counts, (int)blockIdx.x, (int)blockIdx.y);
 }
 #endif  // __HIPCC__
 

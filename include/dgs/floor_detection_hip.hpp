@@ -69,6 +69,65 @@ class HipFloorDetector {
     return Eigen::Vector4f(coeffs[0], coeffs[1], coeffs[2], coeffs[3]);
   }
 
+  // detect() over many clouds -- the frames of several streams -- in one device call (dgs_floor_detection_batch): floors[i] is what
+  // detect(*clouds[i]) returns, statuses (nullable) receives every scan's dgs_floor_detection_status.  -> false when the call itself
+  // failed (last_error() says why); floors then holds boost::none for every scan.
+  bool detectBatch(const std::vector<const pcl::PointCloud<PointT>*>& clouds, std::vector<boost::optional<Eigen::Vector4f>>& floors,
+                   std::vector<int>* statuses = nullptr) {
+    const size_t n = clouds.size();
+    floors.assign(n, boost::none);
+    if (statuses) statuses->assign(n, DGS_FD_TOO_FEW_POINTS);
+    if (!ensure_handle()) return false;
+    Eigen::Matrix4f tilt = Eigen::Matrix4f::Identity();
+    tilt.topLeftCorner(3, 3) = Eigen::AngleAxisf(p_.tilt_deg * M_PI / 180.0f, Eigen::Vector3f::UnitY()).toRotationMatrix();
+    const Eigen::Matrix4f tilt_inv = static_cast<Eigen::Matrix4f>(tilt.inverse());
+    std::vector<int64_t> sizes(n);
+    size_t total = 0;
+    for (size_t s = 0; s < n; s++) {
+      if (!clouds[s]) return false;
+      sizes[s] = (int64_t)clouds[s]->points.size();
+      total += clouds[s]->points.size();
+    }
+    in_.resize(4 * total + 4);
+    std::vector<const float*> ptrs(n);
+    size_t off = 0;
+    for (size_t s = 0; s < n; s++) {
+      ptrs[s] = in_.data() + 4 * off;
+      for (const auto& q : clouds[s]->points) {
+        std::memcpy(&in_[4 * off], &q, 3 * sizeof(float));
+        in_[4 * off + 3] = 1.f;
+        off++;
+      }
+    }
+    std::vector<float> coeffs(4 * n + 4, 0.f);
+    std::vector<int32_t> st(n + 1, DGS_FD_TOO_FEW_POINTS);
+    if (dgs_floor_detection_batch(h_, &p_, tilt.data(), tilt_inv.data(), (int32_t)n, ptrs.data(), sizes.data(), 0, nullptr, nullptr, coeffs.data(), st.data()) !=
+        DGS_OK)
+      return false;
+    for (size_t s = 0; s < n; s++) {
+      if (statuses) (*statuses)[s] = st[s];
+      if (st[s] == DGS_FD_DETECTED) floors[s] = Eigen::Vector4f(coeffs[4 * s], coeffs[4 * s + 1], coeffs[4 * s + 2], coeffs[4 * s + 3]);
+    }
+    return true;
+  }
+  // /floor_detection/floor_filtered_points and /floor_detection/floor_points of scan `i` of the last detectBatch
+  template <typename CloudT>
+  void batchFiltered(int i, CloudT& out) {
+    int64_t m = 0;
+    if (!h_ || dgs_floor_detection_batch_get_filtered(h_, i, nullptr, 0, 0, &m) != DGS_OK) m = 0;
+    buf_.resize(4 * (size_t)m);
+    if (m > 0 && dgs_floor_detection_batch_get_filtered(h_, i, buf_.data(), m, 0, &m) != DGS_OK) m = 0;
+    fill(out, m);
+  }
+  template <typename CloudT>
+  void batchFloorPoints(int i, CloudT& out) {
+    int64_t m = 0;
+    if (!h_ || dgs_floor_detection_batch_get_inliers(h_, i, nullptr, nullptr, 0, &m) != DGS_OK) m = 0;
+    buf_.resize(4 * (size_t)m);
+    if (m > 0 && dgs_floor_detection_batch_get_inliers(h_, i, nullptr, buf_.data(), m, &m) != DGS_OK) m = 0;
+    fill(out, m);
+  }
+
   // /floor_detection/floor_filtered_points and /floor_detection/floor_points of the last detect: x, y, z of every point
   template <typename CloudT>
   void filtered(CloudT& out) {

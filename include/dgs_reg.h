@@ -1128,6 +1128,31 @@ int dgs_floor_detection_get_clipped(dgs_handle* h, float* clipped_xyz16, float* 
 int dgs_floor_detection_draws(int64_t n, const uint32_t* rng_raw, int64_t n_draws, int32_t* triples_out);
 int dgs_floor_detection_walk(int64_t n, int32_t max_iterations, double probability, const int32_t* counts, int64_t n_counts,
                              int32_t* winner_out, int32_t* iterations_out, int32_t* open_out);
+/* detect() over n_scans scans in one call, e.g. the frames of several streams: one chain of launches and three host waits whatever
+ * their number.  One parameter set and one tilt / tilt_inv pair for all scans.  in_xyz16[i]: sizes[i] xyz16 points
+ * (all host arrays, or all device pointers with in_on_device), not modified.  rng_raw (nullable array) and rng_len (nullable when
+ * rng_raw is): per scan what dgs_floor_detection takes; rng_raw[i] NULL or rng_len[i] 0: mt19937(12345).  Scan i receives in
+ * coeffs4_out[4 * i ..] and status_out[i], bit for bit, what dgs_floor_detection gives it alone, wherever it stands in the batch.
+ * Per-scan conditions (TOO_FEW_POINTS, an empty scan included, TOO_FEW_INLIERS, NOT_VERTICAL, RNG_EXHAUSTED) are statuses with
+ * zero coefficients; the other scans run.  Refused with DGS_ERR_INVALID_ARGUMENT before anything is written: what
+ * dgs_floor_detection refuses in the parameters, a NULL array, a negative size or rng_len, a NULL input of positive size, a size
+ * above INT32_MAX, more than 2^31 points in total.  n_scans == 0 is DGS_OK without a launch.  The batch works in buffers of its
+ * own: the getters of the single call keep reporting the last dgs_floor_detection. */
+int dgs_floor_detection_batch(dgs_handle* h, const dgs_floor_detection_params* params, const float* tilt16, const float* tilt_inv16,
+                              int32_t n_scans, const float* const* in_xyz16, const int64_t* sizes, int32_t in_on_device,
+                              const uint32_t* const* rng_raw, const int64_t* rng_len, float* coeffs4_out, int32_t* status_out);
+/* The getters of the single call by scan number of the last batch (0 <= scan < n_scans, else DGS_ERR_INVALID_ARGUMENT).  The
+ * filtered cloud and the inlier list of a scan are fetched and computed when asked for.  In the trace, hypotheses_scored and
+ * chunks_launched say how far that scan's own scoring went inside the batch's rounds: a scan's first chunk may be scored in a round
+ * in which other scans score a later one, so they are not the single call's launch counts. */
+int dgs_floor_detection_batch_get_filtered(dgs_handle* h, int32_t scan, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n);
+int dgs_floor_detection_batch_get_inliers(dgs_handle* h, int32_t scan, int32_t* indices, float* points_xyz16, int64_t capacity, int64_t* n);
+int dgs_floor_detection_batch_get_trace(dgs_handle* h, int32_t scan, dgs_floor_detection_trace* trace);
+int dgs_floor_detection_batch_get_clipped(dgs_handle* h, int32_t scan, float* clipped_xyz16, float* normals4, int64_t capacity, int64_t* n);
+/* Of the last batch: [0] kernel launches, [1] host waits, [2] scans listed, [3] scans that reached the RANSAC, [4] scans served by a
+ * per-scan fallback (a draw list that had to grow; every scan of a chunk under DGS_KNN_LEAF=0), [5] chunks of scans
+ * (DGS_FLOOR_BATCH_POINTS raw points each, default 4 Mi), [6] indices built, [7] RANSAC rounds (score launches) of the call. */
+int dgs_floor_detection_batch_get_counts(dgs_handle* h, int64_t* counts8);
 
 /* ---- interpolate, BuildingTools::buildPointCloud and Building::getCloud on the device --------------------------------------------
  * (src/hdl_graph_slam/ros_utils.cpp:146-165, building_tools.cpp:166-196, building.cpp:7-22; the call sites of
