@@ -22,6 +22,7 @@
 #include <cstring>
 #include "compact.h"
 #include "floor_detection_body.h"
+#include "floor_detection_plan.h"
 #include "handle.h"
 #include "nn_group.h"
 #include "sac.h"
@@ -57,8 +58,8 @@ namespace {
 int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* tilt16, const float* tilt_inv16, const float4* in, int64_t n, int64_t* nf) {
   FdScratch& fd = h->fd;
   *nf = 0;
-  fd.n_clipped = fd.n_filtered = 0;
-  fd.have_normals = false;
+  fd.scan.n_clipped = fd.scan.n_filtered = 0;
+  fd.scan.have_normals = false;
   if (n == 0) return DGS_OK;
   DGS_HIP_TRY(h, fd.flags.reserve((size_t)n));
   DGS_HIP_TRY(h, fd.tilted.reserve((size_t)n));
@@ -67,7 +68,7 @@ int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
                      fd.tilted.ptr, fd.flags.ptr);
   int64_t nc = 0;
   if (int rc = compact_points(h, fd.tilted.ptr, fd.flags.ptr, n, fd.blk, fd.cnt, fd.clipped, false, &nc)) return rc;
-  fd.n_clipped = nc;
+  fd.scan.n_clipped = nc;
   const float4* kept = fd.clipped.ptr;
   int64_t nk = nc;
   if (p.use_normal_filtering && nc > 0) {
@@ -86,7 +87,7 @@ int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
                        0.0f, (float)p.sensor_height, fd.nflags.ptr, fd.normals.ptr, fd.cov9.ptr);
     hipLaunchKernelGGL(fd_normal_flag_kernel, dim3(compact_blocks(nc)), dim3(kBlock), 0, h->stream, fd.normals.ptr, (int)nc,
                        std::cos(p.normal_filter_thresh * M_PI / 180.0), fd.flags.ptr);
-    fd.have_normals = true;
+    fd.scan.have_normals = true;
     if (int rc = compact_points(h, fd.clipped.ptr, fd.flags.ptr, nc, fd.blk, fd.cnt, fd.kept, false, &nk)) return rc;
     kept = fd.kept.ptr;
   }
@@ -96,16 +97,36 @@ int fd_filter(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
                        fd.filtered.ptr);
     DGS_HIP_TRY(h, hipGetLastError());
   }
-  fd.n_filtered = nk;
+  fd.scan.n_filtered = nk;
   *nf = nk;
   return DGS_OK;
 }
 
 }  // namespace
 
-// steps 5-8 over `pts` (n >= 3 points) with a draw list of D draws, in the buffers handed in (the single call's FdScratch, or the batch's
-// for a scan it finishes alone): the walk's end state in tr, the winner's coefficients in coeffs, the filtered cloud in *host_cloud.
-// *need_draws when the walk ran past the list.
+bool fd_walk_to_trace(const fdplan::ScanWalk& w, const FdHyp* hyps, dgs_floor_detection_trace& tr, float* coeffs) {
+  const SacWalk& wk = w.wk;
+  tr.draws = wk.draws;
+  tr.hypotheses_scored = w.scored;
+  tr.iterations = wk.it;
+  tr.chunks_launched = w.chunks;
+  tr.ransac_failed = wk.status == SAC_FAILED ? 1 : 0;
+  if (wk.status == SAC_NEED_DRAWS) return false;
+  if (wk.win >= 0) {
+    const FdHyp& win = hyps[wk.win];
+    tr.winner_rank = wk.win;
+    tr.sample[0] = win.i0; tr.sample[1] = win.i1; tr.sample[2] = win.i2;
+    tr.count = wk.best;
+    for (int a = 0; a < 4; a++) coeffs[a] = win.c[a];
+  }
+  return true;
+}
+
+namespace {
+
+// steps 5-8 over `pts` (n >= 3 points) with a draw list of D draws: one score launch and one host wait per chunk of hypotheses the walk
+// asks for.  -> the walk's end state in tr, the winner's coefficients in coeffs, the filtered cloud in *host_cloud; *need_draws when
+// the walk ran past the list.
 int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float4* pts, int64_t n, const uint32_t* raw, int64_t D, SacScratch& sac,
               DevBuf<FdHyp>& hyps, dgs_floor_detection_trace& tr, std::vector<float4>* host_cloud, bool* need_draws, float* coeffs) {
   const int max_hyp = p.max_iterations + 1;
@@ -130,50 +151,65 @@ int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float4* 
                      max_hyp, hyps.ptr, sac.counts.ptr, sac.meta.ptr);
   DGS_HIP_TRY(h, hipMemcpyAsync(pin + off_cloud, pts, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
 
-  SacWalk wk;
+  fdplan::ScanWalk w;
+  w.n = n;
+  w.D = D;
   const double log_one_minus_p = std::log(1.0 - p.probability);
-  int scored = 0, chunks = 0, H = 0, fail_at = INT_MAX;
-  while (wk.open()) {
-    if (wk.it >= scored) {
-      if (chunks > 0 && scored >= H) {
-        wk.end_of_list(fail_at, (int)D);
-        break;
-      }
-      const int h_end = (int)std::min<int64_t>(max_hyp, (int64_t)scored + (chunks == 0 ? p.hyp_chunk_first : p.hyp_chunk));
-      hipLaunchKernelGGL((sac_score_kernel<FdModel, kFdHypSub>),
-                         dim3((unsigned)((n + kSacTile - 1) / kSacTile), (unsigned)((h_end - scored + kFdHypSub - 1) / kFdHypSub)), dim3(kBlock), 0,
-                         h->stream, pts, (int)n, hyps.ptr, sac.meta.ptr, max_hyp, scored, h_end, prm, sac.counts.ptr);
-      DGS_HIP_TRY(h, hipGetLastError());
-      DGS_HIP_TRY(h, hipMemcpyAsync(h_meta, sac.meta.ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      DGS_HIP_TRY(h, hipMemcpyAsync(h_hyp + scored, hyps.ptr + scored, (size_t)(h_end - scored) * sizeof(FdHyp), hipMemcpyDeviceToHost, h->stream));
-      DGS_HIP_TRY(h, hipMemcpyAsync(h_cnt + scored, sac.counts.ptr + scored, (size_t)(h_end - scored) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-      chunks++;
-      H = std::min(h_meta[0], max_hyp);
-      fail_at = h_meta[1];
-      scored = std::min(h_end, H);
-      continue;
-    }
-    if (!wk.next(h_hyp[wk.it].draw, fail_at)) break;
-    if (!wk.step(h_cnt[wk.it], n, p.max_iterations, log_one_minus_p, FdModel::ratio_power)) break;
+  while (w.advance(h_hyp, h_cnt, p.max_iterations, p.hyp_chunk_first, p.hyp_chunk, log_one_minus_p, FdModel::ratio_power)) {
+    const int h0 = w.h_first, hc = w.h_end - w.h_first;   // h0 = the hypotheses scored so far: only the new chunk comes down
+    hipLaunchKernelGGL((sac_score_kernel<FdModel, kFdHypSub>), dim3((unsigned)((n + kSacTile - 1) / kSacTile), (unsigned)((hc + kFdHypSub - 1) / kFdHypSub)),
+                       dim3(kBlock), 0, h->stream, pts, (int)n, hyps.ptr, sac.meta.ptr, max_hyp, h0, w.h_end, prm, sac.counts.ptr);
+    DGS_HIP_TRY(h, hipGetLastError());
+    DGS_HIP_TRY(h, hipMemcpyAsync(h_meta, sac.meta.ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    DGS_HIP_TRY(h, hipMemcpyAsync(h_hyp + h0, hyps.ptr + h0, (size_t)hc * sizeof(FdHyp), hipMemcpyDeviceToHost, h->stream));
+    DGS_HIP_TRY(h, hipMemcpyAsync(h_cnt + h0, sac.counts.ptr + h0, (size_t)hc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+    w.scored_round(h_meta[0], h_meta[1], max_hyp);
   }
-  tr.draws = wk.draws;
-  tr.hypotheses_scored = scored;
-  tr.iterations = wk.it;
-  tr.chunks_launched = chunks;
-  tr.ransac_failed = wk.status == SAC_FAILED ? 1 : 0;
-  *need_draws = wk.status == SAC_NEED_DRAWS;
+  *need_draws = !fd_walk_to_trace(w, h_hyp, tr, coeffs);
   if (*need_draws) return DGS_OK;
   host_cloud->resize((size_t)n);
   std::memcpy(host_cloud->data(), pin + off_cloud, (size_t)n * sizeof(float4));
-  if (wk.win >= 0) {
-    const FdHyp& w = h_hyp[wk.win];
-    tr.winner_rank = wk.win;
-    tr.sample[0] = w.i0; tr.sample[1] = w.i1; tr.sample[2] = w.i2;
-    tr.count = wk.best;
-    for (int a = 0; a < 4; a++) coeffs[a] = w.c[a];
-  }
   return DGS_OK;
+}
+
+}  // namespace
+
+int fd_ransac_lists(dgs_handle* h, const dgs_floor_detection_params& p, const float4* pts, int64_t n, const uint32_t* rng_raw, SacDrawPlan& plan,
+                    SacScratch& sac, DevBuf<FdHyp>& hyps, FdScan& sc, float* coeffs, bool* exhausted, StageCounts* did) {
+  for (*exhausted = false;;) {
+    const uint32_t* raw = rng_raw;
+    if (!raw) {
+      sac_grow_mt(sac.mt_raw, 3 * plan.D);
+      raw = sac.mt_raw.data();
+    }
+    bool need_draws = false;
+    if (int rc = fd_ransac(h, p, pts, n, raw, plan.D, sac, hyps, sc.trace, &sc.host_filtered, &need_draws, coeffs)) return rc;
+    did->launches += 1 + sc.trace.chunks_launched;   // the prepare launch and one score launch per chunk
+    did->waits += sc.trace.chunks_launched;
+    if (!need_draws) return DGS_OK;
+    if (!plan.grow()) {
+      *exhausted = true;
+      return DGS_OK;
+    }
+  }
+}
+
+void fd_select_inliers(FdScan& sc, const dgs_floor_detection_params& p, const float* c) {
+  // read once: the compiler cannot tell that push_back leaves them alone, and the single call runs this loop inside its timed path
+  const float4* pts = sc.host_filtered.data();
+  const int64_t n = (int64_t)sc.host_filtered.size();
+  const float a = c[0], b = c[1], cz = c[2], d = c[3];
+  const int order = p.plane_dot_order;
+  const double thr = p.distance_threshold;
+  for (int64_t i = 0; i < n; i++)
+    if (fd_is_inlier(pts[i], a, b, cz, d, order, thr)) sc.inliers.push_back((int32_t)i);
+}
+
+void fd_verdict(FdScan& sc, const dgs_floor_detection_params& p, const float* tilt_inv16, const float* coeffs, int64_t inliers) {
+  dgs_floor_detection_trace& tr = sc.trace;
+  sc.status = fdplan::verdict(tr.winner_rank >= 0 ? coeffs : nullptr, inliers, tilt_inv16, p.floor_pts_thresh, p.floor_normal_thresh, tr.raw_coeffs, &tr.dot,
+                              sc.coeffs);
 }
 
 const char* fd_bad_params(const dgs_floor_detection_params* p) {
@@ -191,18 +227,14 @@ const char* fd_bad_params(const dgs_floor_detection_params* p) {
 
 namespace {
 
+// -> fd.scan: its status, coefficients, trace, host cloud and inliers
 int fd_detect(dgs_handle* h, const dgs_floor_detection_params& p, const float* tilt16, const float* tilt_inv16, const float* in_xyz16, int64_t n,
-              int32_t in_on_device, const uint32_t* rng_raw, int64_t rng_len, float* coeffs4_out, int32_t* status_out) {
+              int32_t in_on_device, const uint32_t* rng_raw, int64_t rng_len) {
   FdScratch& fd = h->fd;
-  dgs_floor_detection_trace& tr = fd.trace;
-  std::memset(&tr, 0, sizeof(tr));
-  tr.winner_rank = -1;
-  tr.sample[0] = tr.sample[1] = tr.sample[2] = -1;
-  fd.inliers.clear();
-  fd.host_filtered.clear();
-  fd.n_clipped = fd.n_filtered = 0;
-  fd.have_normals = false;
-  *status_out = DGS_FD_TOO_FEW_POINTS;
+  FdScan& sc = fd.scan;
+  dgs_floor_detection_trace& tr = sc.trace;
+  sc.reset();   // DGS_FD_TOO_FEW_POINTS
+  sc.n = n;
   if (n == 0) return DGS_OK;   // cloud_callback returns on an empty cloud (:76-78)
   const float4* in = reinterpret_cast<const float4*>(in_xyz16);
   if (!in_on_device) {
@@ -212,55 +244,32 @@ int fd_detect(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   }
   int64_t nf = 0;
   if (int rc = fd_filter(h, p, tilt16, tilt_inv16, in, n, &nf)) return rc;
-  tr.n_clipped = (int32_t)fd.n_clipped;
+  tr.n_clipped = (int32_t)sc.n_clipped;
   tr.n_filtered = (int32_t)nf;
-  if (nf < (int64_t)p.floor_pts_thresh) return DGS_OK;   // too few points for RANSAC (:133)
+  if (!fdplan::reaches_ransac(n, nf, p.floor_pts_thresh)) return DGS_OK;   // too few points for RANSAC (:133)
 
   float coeffs[4] = {0.f, 0.f, 0.f, 0.f};
   if (nf < 3) {   // getSamples: fewer points than the sample size, the selection is empty and the loop breaks at once
     tr.ransac_failed = 1;
-    fd.host_filtered.resize((size_t)nf);
+    sc.host_filtered.resize((size_t)nf);
     if (nf > 0) {
-      DGS_HIP_TRY(h, hipMemcpyAsync(fd.host_filtered.data(), fd.filtered.ptr, (size_t)nf * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+      DGS_HIP_TRY(h, hipMemcpyAsync(sc.host_filtered.data(), fd.filtered.ptr, (size_t)nf * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
       DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
   } else {
     SacDrawPlan plan(rng_raw ? rng_len / 3 : INT32_MAX / 4, p.max_iterations + 1, p.max_sample_checks);
-    for (;;) {
-      if (plan.empty()) { *status_out = DGS_FD_RNG_EXHAUSTED; return DGS_OK; }
-      const uint32_t* raw = rng_raw;
-      if (!rng_raw) {
-        sac_grow_mt(fd.sac.mt_raw, 3 * plan.D);
-        raw = fd.sac.mt_raw.data();
-      }
-      bool need_draws = false;
-      if (int rc = fd_ransac(h, p, fd.filtered.ptr, nf, raw, plan.D, fd.sac, fd.hyps, tr, &fd.host_filtered, &need_draws, coeffs)) return rc;
-      if (!need_draws) break;
-      if (!plan.grow()) { *status_out = DGS_FD_RNG_EXHAUSTED; return DGS_OK; }
+    bool exhausted = plan.empty();
+    StageCounts did;   // the single call reports no counts
+    if (!exhausted)
+      if (int rc = fd_ransac_lists(h, p, fd.filtered.ptr, nf, rng_raw, plan, fd.sac, fd.hyps, sc, coeffs, &exhausted, &did)) return rc;
+    if (exhausted) {
+      sc.status = DGS_FD_RNG_EXHAUSTED;
+      return DGS_OK;
     }
   }
   // selectWithinDistance of the winner, in index order; no model: empty inliers
-  if (tr.winner_rank >= 0) {
-    for (int64_t i = 0; i < nf; i++)
-      if (fd_is_inlier(fd.host_filtered[(size_t)i], coeffs[0], coeffs[1], coeffs[2], coeffs[3], p.plane_dot_order, p.distance_threshold))
-        fd.inliers.push_back((int32_t)i);
-  }
-  for (int a = 0; a < 4; a++) tr.raw_coeffs[a] = coeffs[a];
-  if ((int64_t)fd.inliers.size() < (int64_t)p.floor_pts_thresh) { *status_out = DGS_FD_TOO_FEW_INLIERS; return DGS_OK; }   // :147
-  {
-#pragma clang fp contract(off)
-    // reference = tilt_matrix.inverse() * UnitZ: the third column (:152); the dot product in float, compared in double (:157-158)
-    const float rx = tilt_inv16[8], ry = tilt_inv16[9], rz = tilt_inv16[10];
-    const float dot = (coeffs[0] * rx + coeffs[1] * ry) + coeffs[2] * rz;
-    tr.dot = dot;
-    if (std::abs((double)dot) < std::cos(p.floor_normal_thresh * M_PI / 180.0)) { *status_out = DGS_FD_NOT_VERTICAL; return DGS_OK; }
-    // make the normal upward (:164-166)
-    const float up = (0.0f * coeffs[0] + 0.0f * coeffs[1]) + 1.0f * coeffs[2];
-    if (up < 0.0f)
-      for (int a = 0; a < 4; a++) coeffs[a] = coeffs[a] * -1.0f;
-  }
-  for (int a = 0; a < 4; a++) coeffs4_out[a] = coeffs[a];
-  *status_out = DGS_FD_DETECTED;
+  if (tr.winner_rank >= 0) fd_select_inliers(sc, p, coeffs);
+  fd_verdict(sc, p, tilt_inv16, coeffs, (int64_t)sc.inliers.size());
   return DGS_OK;
 }
 
@@ -272,8 +281,50 @@ void floor_detection_release(dgs_handle* h) {
   fd.flags.release(); fd.nflags.release(); fd.blk.release(); fd.cnt.release(); fd.nbr.release(); fd.cov9.release(); fd.hyps.release();
   fd.sac.release();
   fd.cloud.release();
-  fd.host_filtered.clear(); fd.inliers.clear();
-  fd.n_clipped = fd.n_filtered = 0;
+  fd.scan.host_filtered.clear(); fd.scan.inliers.clear();
+  fd.scan.n_clipped = fd.scan.n_filtered = 0;
+}
+
+// ---- the getters of the single call and the batch: sc = the scan's record, or nullptr when there is no such scan
+int fd_get_filtered(dgs_handle* h, const FdScan* sc, const float4* d_filtered, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n) {
+  if (!sc || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
+  const int64_t m = sc->n_filtered;
+  *n = m;
+  if (m == 0 || !out_xyz16 || capacity < m) return DGS_OK;
+  DGS_HIP_TRY(h, hipSetDevice(h->device));
+  DGS_HIP_TRY(h, hipMemcpyAsync(out_xyz16, d_filtered, (size_t)m * sizeof(float4), out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return DGS_OK;
+}
+
+int fd_get_inliers(const FdScan* sc, int32_t* indices, float* points_xyz16, int64_t capacity, int64_t* n) {
+  if (!sc || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
+  const int64_t m = (int64_t)sc->inliers.size();
+  *n = m;
+  if (m == 0 || capacity < m) return DGS_OK;
+  if (indices) std::memcpy(indices, sc->inliers.data(), (size_t)m * sizeof(int32_t));
+  if (points_xyz16)
+    for (int64_t j = 0; j < m; j++) std::memcpy(points_xyz16 + 4 * j, &sc->host_filtered[(size_t)sc->inliers[(size_t)j]], sizeof(float4));
+  return DGS_OK;
+}
+
+int fd_get_trace(const FdScan* sc, dgs_floor_detection_trace* trace) {
+  if (!sc || !trace) return DGS_ERR_INVALID_ARGUMENT;
+  *trace = sc->trace;
+  return DGS_OK;
+}
+
+int fd_get_clipped(dgs_handle* h, const FdScan* sc, const float4* d_clipped, const float4* d_normals, float* clipped_xyz16, float* normals4, int64_t capacity,
+                   int64_t* n) {
+  if (!sc || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
+  const int64_t m = sc->n_clipped;
+  *n = m;
+  if (m == 0 || capacity < m) return DGS_OK;
+  DGS_HIP_TRY(h, hipSetDevice(h->device));
+  if (clipped_xyz16) DGS_HIP_TRY(h, hipMemcpyAsync(clipped_xyz16, d_clipped, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+  if (normals4 && sc->have_normals) DGS_HIP_TRY(h, hipMemcpyAsync(normals4, d_normals, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return DGS_OK;
 }
 
 }  // namespace dgs
@@ -316,57 +367,33 @@ int dgs_floor_detection(dgs_handle* h, const dgs_floor_detection_params* params,
   for (int a = 0; a < 4; a++) coeffs4_out[a] = 0.f;
   h->err.clear();
   DGS_HIP_TRY(h, hipSetDevice(h->device));
-  const int rc = fd_detect(h, *params, tilt16, tilt_inv16, in_xyz16, n, in_on_device, rng_len > 0 ? rng_raw : nullptr, rng_len, coeffs4_out, status_out);
+  *status_out = DGS_FD_TOO_FEW_POINTS;
+  const int rc = fd_detect(h, *params, tilt16, tilt_inv16, in_xyz16, n, in_on_device, rng_len > 0 ? rng_raw : nullptr, rng_len);
   if (rc != DGS_OK) {
     (void)hipStreamSynchronize(h->stream);
     return rc;
   }
   DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));   // a staged host input may go away after the call
+  *status_out = h->fd.scan.status;
+  for (int a = 0; a < 4; a++) coeffs4_out[a] = h->fd.scan.coeffs[a];
   return DGS_OK;
 }
 
 int dgs_floor_detection_get_filtered(dgs_handle* h, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n) {
-  if (!h || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
-  const int64_t m = h->fd.n_filtered;
-  *n = m;
-  if (m == 0 || !out_xyz16 || capacity < m) return DGS_OK;
-  DGS_HIP_TRY(h, hipSetDevice(h->device));
-  DGS_HIP_TRY(h, hipMemcpyAsync(out_xyz16, h->fd.filtered.ptr, (size_t)m * sizeof(float4), out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                                h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return DGS_OK;
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  return fd_get_filtered(h, &h->fd.scan, h->fd.filtered.ptr, out_xyz16, capacity, out_on_device, n);
 }
-
 int dgs_floor_detection_get_inliers(dgs_handle* h, int32_t* indices, float* points_xyz16, int64_t capacity, int64_t* n) {
-  if (!h || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
-  const FdScratch& fd = h->fd;
-  const int64_t m = (int64_t)fd.inliers.size();
-  *n = m;
-  if (m == 0 || capacity < m) return DGS_OK;
-  if (indices) std::memcpy(indices, fd.inliers.data(), (size_t)m * sizeof(int32_t));
-  if (points_xyz16)
-    for (int64_t j = 0; j < m; j++) std::memcpy(points_xyz16 + 4 * j, &fd.host_filtered[(size_t)fd.inliers[(size_t)j]], sizeof(float4));
-  return DGS_OK;
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  return fd_get_inliers(&h->fd.scan, indices, points_xyz16, capacity, n);
 }
-
 int dgs_floor_detection_get_trace(dgs_handle* h, dgs_floor_detection_trace* trace) {
-  if (!h || !trace) return DGS_ERR_INVALID_ARGUMENT;
-  *trace = h->fd.trace;
-  return DGS_OK;
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  return fd_get_trace(&h->fd.scan, trace);
 }
-
 int dgs_floor_detection_get_clipped(dgs_handle* h, float* clipped_xyz16, float* normals4, int64_t capacity, int64_t* n) {
-  if (!h || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
-  const FdScratch& fd = h->fd;
-  const int64_t m = fd.n_clipped;
-  *n = m;
-  if (m == 0 || capacity < m) return DGS_OK;
-  DGS_HIP_TRY(h, hipSetDevice(h->device));
-  if (clipped_xyz16) DGS_HIP_TRY(h, hipMemcpyAsync(clipped_xyz16, fd.clipped.ptr, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-  if (normals4 && fd.have_normals)
-    DGS_HIP_TRY(h, hipMemcpyAsync(normals4, fd.normals.ptr, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return DGS_OK;
+  if (!h) return DGS_ERR_INVALID_ARGUMENT;
+  return fd_get_clipped(h, &h->fd.scan, h->fd.clipped.ptr, h->fd.normals.ptr, clipped_xyz16, normals4, capacity, n);
 }
 
 int dgs_floor_detection_draws(int64_t n, const uint32_t* rng_raw, int64_t n_draws, int32_t* triples_out) {

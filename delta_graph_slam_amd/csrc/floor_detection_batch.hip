@@ -14,7 +14,7 @@
 // scans whose walk is open, y = the hypothesis groups of the round's longest chunk; the entry carries the scan's own [h_first, h_end)
 // and a workgroup beyond it leaves at once.  Counts are integer atomics: every count is the single launch's.  After a round one host
 // wait brings back meta, hypotheses and counts of all scans (three copies, the last two strided), and the host advances every walk as
-// fd_ransac does (fdbplan::ScanWalk).  A walk that runs past its draw list is finished by fd_ransac on the scan's own cloud.
+// the single call does (fdplan::ScanWalk).  A walk that runs past its draw list is finished by fd_ransac_lists on the scan's own cloud.
 //
 // Decisions.  §6j's checks need the winner's inlier count, not the list: the walk's best count is that number (the score body and the
 // host loop run fd_is_inlier, the same IEEE operations under the same flags, over the same points), so nothing is downloaded.  A
@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "compact.h"
-#include "floor_detection_batch_plan.h"
+#include "floor_detection_plan.h"
 #include "floor_detection_body.h"
 #include "handle.h"
 #include "seg_device.h"
@@ -34,11 +34,11 @@
 
 namespace dgs {
 
-static_assert(fdbplan::kTile == kSacTile && fdbplan::kHypGroup == kFdHypSub, "floor_detection_batch_plan.h restates the score launch's tile and group");
+static_assert(fdplan::kTile == kSacTile && fdplan::kHypGroup == kFdHypSub, "floor_detection_plan.h restates the score launch's tile and group");
 static_assert(pfbplan::kPlanBlock == kBlock, "prefilter_batch_plan.h restates the workgroup of the per-point passes");
-static_assert(fdbplan::kDetected == DGS_FD_DETECTED && fdbplan::kTooFewPoints == DGS_FD_TOO_FEW_POINTS && fdbplan::kTooFewInliers == DGS_FD_TOO_FEW_INLIERS &&
-                  fdbplan::kNotVertical == DGS_FD_NOT_VERTICAL && fdbplan::kRngExhausted == DGS_FD_RNG_EXHAUSTED,
-              "floor_detection_batch_plan.h restates the statuses");
+static_assert(fdplan::kDetected == DGS_FD_DETECTED && fdplan::kTooFewPoints == DGS_FD_TOO_FEW_POINTS && fdplan::kTooFewInliers == DGS_FD_TOO_FEW_INLIERS &&
+                  fdplan::kNotVertical == DGS_FD_NOT_VERTICAL && fdplan::kRngExhausted == DGS_FD_RNG_EXHAUSTED,
+              "floor_detection_plan.h restates the statuses");
 
 struct FdbSeg {
   const float4* in;        // tilt: the raw scan; floor rule: the normals; back-transform: the kept points
@@ -77,27 +77,12 @@ __global__ __launch_bounds__(kBlock) void fdb_transform_kernel(const FdbSeg* __r
   const FdbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
   fd_transform_body(e.in, e.n, M, order, e.out, (int)blockIdx.x - e.blk0);
 }
-// the segmented stable compaction (compact.h).  blk: one count per workgroup of the launch and one more behind them, which workgroup 0
-// zeroes: pf_scan_kernel runs over gridDim.x + 1
-__global__ __launch_bounds__(kBlock) void fdb_count_kernel(const FdbSeg* __restrict__ tab, const int* __restrict__ first, const int m, int* __restrict__ blk) {
-  const FdbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
-  const int i = ((int)blockIdx.x - e.blk0) * kBlock + threadIdx.x;
-  const int t = compact_count_seg(e.flags, i, e.n);
-  if (threadIdx.x == 0) {
-    blk[blockIdx.x] = t;
-    if (blockIdx.x == 0) blk[gridDim.x] = 0;
-  }
-}
+// the scatter of the segmented stable compaction (compact.h; its count launch is compact_count_seg_kernel<FdbSeg>)
 __global__ __launch_bounds__(kBlock) void fdb_scatter_kernel(const FdbSeg* __restrict__ tab, const int* __restrict__ first, const int m, const int* __restrict__ blk,
                                                              int* __restrict__ totals) {
   const int c = seg_find(first, m, (int)blockIdx.x);
   const FdbSeg& e = tab[c];
-  const int lb = (int)blockIdx.x - e.blk0, seg0 = blk[e.blk0];
-  if (lb == 0 && threadIdx.x == 0) totals[c] = blk[first[c + 1]] - seg0;
-  const int i = lb * kBlock + threadIdx.x;
-  int off;
-  if (!compact_slot_seg(e.flags, i, e.n, blk[blockIdx.x] - seg0, &off)) return;
-  e.out[off] = e.src[i];   // off < kept points of the scan <= n: `out` holds n points
+  compact_scatter_seg<int>(e, c, first, blk, totals, [&](const int i, const int off) { e.out[off] = e.src[i]; });   // `out` holds n points
 }
 
 // ---- RANSAC ----------------------------------------------------------------------------------------------------------------------
@@ -116,95 +101,22 @@ __global__ __launch_bounds__(kBlock) void fdb_score_kernel(const FdbSac* __restr
 // ---- host --------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct FdbDev {
-  const FdbSeg* tab;
-  const int* first;
-  int* totals_h;   // pinned: where the compaction's totals arrive (one per item)
-};
-
-// entries | first workgroups -> S.tables in one copy from the pinned block, which nothing in flight reads (see fdb_chain)
-int fdb_upload(dgs_handle* h, const fdbplan::Stage& St, std::vector<FdbSeg>& segs, FdbDev* dev) {
-  FdbScratch& S = h->fdb;
-  const size_t m = St.items.size();
-  const segtab::StageTable T = segtab::stage_table(m, sizeof(FdbSeg), 0);
-  DGS_HIP_TRY(h, S.stage.reserve(T.all));
-  DGS_HIP_TRY(h, S.tables.reserve(T.up));
-  DGS_HIP_TRY(h, S.totals.reserve(m));
-  for (size_t j = 0; j < m; j++) {
-    segs[j].flags = S.flags.ptr + (size_t)St.items[j].blk0 * kBlock;
-    segs[j].n = (int)St.items[j].n;
-    segs[j].blk0 = St.items[j].blk0;
-  }
-  char* st = S.stage.at(0);
-  std::memset(st, 0, T.up);
-  std::memcpy(st + T.entries, segs.data(), m * sizeof(FdbSeg));
-  const std::vector<int> first = St.first();
-  std::memcpy(st + T.first, first.data(), (m + 1) * sizeof(int));
-  DGS_HIP_TRY(h, hipMemcpyAsync(S.tables.ptr, st, T.up, hipMemcpyHostToDevice, h->stream));
-  dev->tab = reinterpret_cast<const FdbSeg*>(S.tables.ptr + T.entries);
-  dev->first = reinterpret_cast<const int*>(S.tables.ptr + T.first);
-  dev->totals_h = reinterpret_cast<int*>(st + T.totals);
-  return DGS_OK;
+// a filter stage's table: every entry's flags, size and first workgroup, then entries | first workgroups in one copy
+int fdb_upload(dgs_handle* h, const fdplan::Stage& St, std::vector<FdbSeg>& segs, SegDev<FdbSeg>* dev) {
+  if (int rc = seg_flags(h, h->fdb.seg, St, segs)) return rc;
+  return seg_upload(h, h->fdb.seg, St, segs, nullptr, 0, dev);
 }
-
 // count, scan, scatter over all scans of the stage; kept[j] = kept points of item j (read back: the host waits here)
-int fdb_compact(dgs_handle* h, const fdbplan::Stage& St, const FdbDev& dev, std::vector<int64_t>& kept) {
-  FdbScratch& S = h->fdb;
-  const int m = (int)St.items.size();
-  DGS_HIP_TRY(h, S.blk.reserve((size_t)St.blocks + 1));
-  DGS_HIP_TRY(h, S.cnt.reserve(4));
-  hipLaunchKernelGGL(fdb_count_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, h->stream, dev.tab, dev.first, m, S.blk.ptr);
-  hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kCompactScanBlock), 0, h->stream, S.blk.ptr, St.blocks + 1, S.cnt.ptr);
-  hipLaunchKernelGGL(fdb_scatter_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, h->stream, dev.tab, dev.first, m, S.blk.ptr, S.totals.ptr);
-  DGS_HIP_TRY(h, hipGetLastError());
-  DGS_HIP_TRY(h, hipMemcpyAsync(dev.totals_h, S.totals.ptr, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  S.counts8[0] += 3;
-  S.counts8[1]++;
-  kept.assign((size_t)m, 0);
-  for (int j = 0; j < m; j++) kept[j] = dev.totals_h[j];
-  return DGS_OK;
-}
-
-void fdb_reset_trace(dgs_floor_detection_trace& tr) {
-  std::memset(&tr, 0, sizeof(tr));
-  tr.winner_rank = -1;
-  tr.sample[0] = tr.sample[1] = tr.sample[2] = -1;
-}
-
-// §6j step 9 from the winner's count: fd_detect's checks behind the RANSAC, without the inlier list
-void fdb_decide(FdbScan& sc, const dgs_floor_detection_params& p, const float* tilt_inv16, const float* win_coeffs) {
-  dgs_floor_detection_trace& tr = sc.trace;
-  float coeffs[4] = {0.f, 0.f, 0.f, 0.f};
-  if (tr.winner_rank >= 0)
-    for (int a = 0; a < 4; a++) coeffs[a] = win_coeffs[a];
-  for (int a = 0; a < 4; a++) tr.raw_coeffs[a] = coeffs[a];
-  const int64_t inliers = tr.winner_rank >= 0 ? tr.count : 0;
-  const double cos_thr = std::cos(p.floor_normal_thresh * M_PI / 180.0);
-  if (fdbplan::decide(inliers, p.floor_pts_thresh, 1.0, 0.0) != fdbplan::kDetected) {   // :147, before the dot product exists
-    sc.status = DGS_FD_TOO_FEW_INLIERS;
-    return;
-  }
-  {
-#pragma clang fp contract(off)
-    // reference = tilt_matrix.inverse() * UnitZ: the third column (:152); the dot product in float, compared in double (:157-158)
-    const float rx = tilt_inv16[8], ry = tilt_inv16[9], rz = tilt_inv16[10];
-    const float dot = (coeffs[0] * rx + coeffs[1] * ry) + coeffs[2] * rz;
-    tr.dot = dot;
-    sc.status = fdbplan::decide(inliers, p.floor_pts_thresh, std::abs((double)dot), cos_thr);
-    if (sc.status != DGS_FD_DETECTED) return;
-    // make the normal upward (:164-166)
-    const float up = (0.0f * coeffs[0] + 0.0f * coeffs[1]) + 1.0f * coeffs[2];
-    if (up < 0.0f)
-      for (int a = 0; a < 4; a++) coeffs[a] = coeffs[a] * -1.0f;
-  }
-  for (int a = 0; a < 4; a++) sc.coeffs[a] = coeffs[a];
+int fdb_compact(dgs_handle* h, const fdplan::Stage& St, const SegDev<FdbSeg>& dev, std::vector<int64_t>& kept) {
+  return seg_compact(h, h->fdb.seg, St, dev, h->fdb.counts8, kept, [&](const dim3 grid, const int* blk, int* totals) {
+    hipLaunchKernelGGL(fdb_scatter_kernel, grid, dim3(kBlock), 0, h->stream, dev.tab, dev.first, (int)St.items.size(), blk, totals);
+  });
 }
 
 // a scan of the RANSAC stage
 struct FdbLive {
   int scan;                  // number inside the call
-  fdbplan::ScanWalk w;
+  fdplan::ScanWalk w;
   SacDrawPlan plan;
   const uint32_t* raw;       // the caller's stream, or nullptr: mt19937(12345)
   int64_t draw0;             // first int of its draw list in the shared array
@@ -256,11 +168,11 @@ int fdb_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float* 
   std::vector<FdbSac> segs;
   const FdbSac* d_tab = reinterpret_cast<const FdbSac*>(S.sac_tables.ptr + T.entries);
   const int* d_first = reinterpret_cast<const int*>(S.sac_tables.ptr + T.first);
-  auto upload_round = [&](const fdbplan::Round& R) -> int {
+  auto upload_round = [&](const fdplan::Round& R) -> int {
     const size_t r = R.items.size();
     segs.assign(r, FdbSac{});
     for (size_t a = 0; a < r; a++) {
-      const fdbplan::RoundItem& it = R.items[a];
+      const fdplan::RoundItem& it = R.items[a];
       const FdbLive& L = live[(size_t)it.scan];
       FdbSac& e = segs[a];
       e.pts = S.filtered[(size_t)L.scan].ptr;
@@ -274,22 +186,19 @@ int fdb_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float* 
       e.h_end = it.h_end;
       e.tile0 = it.tile0;
     }
-    std::memset(pin, 0, T.up);
-    std::memcpy(pin + T.entries, segs.data(), r * sizeof(FdbSac));
-    const std::vector<int> first = R.first();
-    std::memcpy(pin + T.first, first.data(), (r + 1) * sizeof(int));
+    segtab::place(pin, T, segs.data(), r * sizeof(FdbSac), R.first());
     DGS_HIP_TRY(h, hipMemcpyAsync(S.sac_tables.ptr, pin, T.up, hipMemcpyHostToDevice, st));
     return DGS_OK;
   };
 
   for (int round = 0;; round++) {
-    fdbplan::Round R;
+    fdplan::Round R;
     for (int j = 0; j < m; j++) {
       FdbLive& L = live[(size_t)j];
       if (!L.open) continue;
       L.open = L.w.advance(h_hyp + (size_t)j * max_hyp, h_cnt + (size_t)j * max_hyp, p.max_iterations, p.hyp_chunk_first, p.hyp_chunk, log_one_minus_p,
                            FdModel::ratio_power);
-      if (L.open) fdbplan::round_add(R, j, L.w.n, L.w.h_first, L.w.h_end);
+      if (L.open) fdplan::round_add(R, j, L.w.n, L.w.h_first, L.w.h_end);
     }
     if (R.items.empty()) break;
     if (int rc = upload_round(R)) return rc;
@@ -312,51 +221,29 @@ int fdb_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float* 
     S.counts8[0]++;
     S.counts8[1]++;
     S.counts8[7]++;
-    for (const fdbplan::RoundItem& it : R.items) live[(size_t)it.scan].w.scored_round(h_meta[(size_t)it.scan * 4], h_meta[(size_t)it.scan * 4 + 1], max_hyp);
+    for (const fdplan::RoundItem& it : R.items) live[(size_t)it.scan].w.scored_round(h_meta[(size_t)it.scan * 4], h_meta[(size_t)it.scan * 4 + 1], max_hyp);
   }
 
-  // the walks' end states; a walk that ran past its list is finished alone
+  // the walks' end states; a walk that ran past its list is finished alone, over longer ones
   for (int j = 0; j < m; j++) {
     FdbLive& L = live[(size_t)j];
-    FdbScan& sc = S.scans[(size_t)L.scan];
-    dgs_floor_detection_trace& tr = sc.trace;
-    const SacWalk& wk = L.w.wk;
-    tr.draws = wk.draws;
-    tr.hypotheses_scored = L.w.scored;
-    tr.iterations = wk.it;
-    tr.chunks_launched = L.w.chunks;
-    tr.ransac_failed = wk.status == SAC_FAILED ? 1 : 0;
+    FdScan& sc = S.scans[(size_t)L.scan];
     float coeffs[4] = {0.f, 0.f, 0.f, 0.f};
-    if (wk.status == SAC_NEED_DRAWS) {
+    if (!fd_walk_to_trace(L.w, h_hyp + (size_t)j * max_hyp, sc.trace, coeffs)) {
       S.counts8[4]++;
-      bool exhausted = false;
-      for (;;) {
-        if (!L.plan.grow()) { exhausted = true; break; }
-        const uint32_t* raw = L.raw;
-        if (!raw) {
-          sac_grow_mt(S.sac.mt_raw, 3 * L.plan.D);
-          raw = S.sac.mt_raw.data();
-        }
-        bool need_draws = false;
-        if (int rc = fd_ransac(h, p, S.filtered[(size_t)L.scan].ptr, L.w.n, raw, L.plan.D, S.sac, S.hyps_single, tr, &sc.host_filtered, &need_draws, coeffs))
-          return rc;
-        S.counts8[0] += 1 + tr.chunks_launched;
-        S.counts8[1] += tr.chunks_launched;
-        if (!need_draws) break;
-      }
+      bool exhausted = !L.plan.grow();
+      StageCounts did;
+      if (!exhausted)
+        if (int rc = fd_ransac_lists(h, p, S.filtered[(size_t)L.scan].ptr, L.w.n, L.raw, L.plan, S.sac, S.hyps_single, sc, coeffs, &exhausted, &did)) return rc;
+      S.counts8[0] += did.launches;
+      S.counts8[1] += did.waits;
       if (exhausted) {
         sc.status = DGS_FD_RNG_EXHAUSTED;
         continue;
       }
       sc.have_host = true;
-    } else if (wk.win >= 0) {
-      const FdHyp& win = h_hyp[(size_t)j * max_hyp + wk.win];
-      tr.winner_rank = wk.win;
-      tr.sample[0] = win.i0; tr.sample[1] = win.i1; tr.sample[2] = win.i2;
-      tr.count = wk.best;
-      for (int a = 0; a < 4; a++) coeffs[a] = win.c[a];
     }
-    fdb_decide(sc, p, tilt_inv16, coeffs);
+    fd_verdict(sc, p, tilt_inv16, coeffs, sc.trace.count);
   }
   return DGS_OK;
 }
@@ -368,15 +255,14 @@ int fdb_chain(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   hipStream_t st = h->stream;
   std::vector<int64_t> cur((size_t)n, 0), kept;
   std::vector<FdbSeg> segs;
-  FdbDev dev{};
+  SegDev<FdbSeg> dev{};
   bool dirty = false;   // launches are queued behind the last host wait: the pinned blocks may still be read
 
   // 1. tilt and the two clips -> the clipped clouds
   {
-    const fdbplan::Stage St = fdbplan::make_stage(n, sizes);
+    const fdplan::Stage St = fdplan::make_stage(n, sizes);
     const int m = (int)St.items.size();
     if (m > 0) {
-      DGS_HIP_TRY(h, S.flags.reserve((size_t)St.blocks * kBlock));
       DGS_HIP_TRY(h, S.tilted.reserve((size_t)St.points));
       segs.assign((size_t)m, FdbSeg{});
       for (int j = 0; j < m; j++) {
@@ -405,7 +291,7 @@ int fdb_chain(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   std::vector<const float4*> kept_ptr((size_t)n, nullptr);
   for (int s = 0; s < n; s++) kept_ptr[s] = S.clip[(size_t)(f + s)].pts.ptr;
   if (p.use_normal_filtering) {
-    const fdbplan::Stage St = fdbplan::make_stage(n, cur.data());
+    const fdplan::Stage St = fdplan::make_stage(n, cur.data());
     const int m = (int)St.items.size();
     if (m > 0) {
       std::vector<float4*> normals((size_t)n, nullptr);
@@ -424,7 +310,6 @@ int fdb_chain(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
       S.counts8[6] += S.nrm.counts8[6];
       if (rc) return rc;
       if (fell_back) S.counts8[4] += n;
-      DGS_HIP_TRY(h, S.flags.reserve((size_t)St.blocks * kBlock));
       DGS_HIP_TRY(h, S.kept.reserve((size_t)St.points));
       segs.assign((size_t)m, FdbSeg{});
       for (int j = 0; j < m; j++) {
@@ -445,7 +330,7 @@ int fdb_chain(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
 
   // 3. the back-transform -> the filtered clouds
   {
-    const fdbplan::Stage St = fdbplan::make_stage(n, cur.data());
+    const fdplan::Stage St = fdplan::make_stage(n, cur.data());
     const int m = (int)St.items.size();
     if (m > 0) {
       segs.assign((size_t)m, FdbSeg{});
@@ -466,19 +351,18 @@ int fdb_chain(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   // 4. who reaches the RANSAC
   std::vector<FdbLive> live;
   for (int s = 0; s < n; s++) {
-    FdbScan& sc = S.scans[(size_t)(f + s)];
+    FdScan& sc = S.scans[(size_t)(f + s)];
     sc.n_filtered = cur[s];
     sc.trace.n_clipped = (int32_t)sc.n_clipped;
     sc.trace.n_filtered = (int32_t)cur[s];
-    if (!fdbplan::reaches_ransac(sizes[s], cur[s], p.floor_pts_thresh)) continue;   // DGS_FD_TOO_FEW_POINTS
+    if (!fdplan::reaches_ransac(sizes[s], cur[s], p.floor_pts_thresh)) continue;   // DGS_FD_TOO_FEW_POINTS
     if (cur[s] < 3) {   // getSamples: fewer points than the sample size, the selection is empty and the loop breaks at once
       sc.trace.ransac_failed = 1;
-      const float none[4] = {0.f, 0.f, 0.f, 0.f};
-      fdb_decide(sc, p, tilt_inv16, none);
+      fd_verdict(sc, p, tilt_inv16, nullptr, 0);
       continue;
     }
     const uint32_t* raw = (rng_raw && rng_len && rng_len[s] > 0) ? rng_raw[s] : nullptr;
-    FdbLive L{f + s, fdbplan::ScanWalk{}, SacDrawPlan(raw ? rng_len[s] / 3 : INT32_MAX / 4, p.max_iterations + 1, p.max_sample_checks), raw, 0, true};
+    FdbLive L{f + s, fdplan::ScanWalk{}, SacDrawPlan(raw ? rng_len[s] / 3 : INT32_MAX / 4, p.max_iterations + 1, p.max_sample_checks), raw, 0, true};
     if (L.plan.empty()) {
       sc.status = DGS_FD_RNG_EXHAUSTED;
       continue;
@@ -496,7 +380,7 @@ int fdb_chain(dgs_handle* h, const dgs_floor_detection_params& p, const float* t
   return DGS_OK;
 }
 
-FdbScan* fdb_scan(dgs_handle* h, int32_t scan) {
+FdScan* fdb_scan(dgs_handle* h, int32_t scan) {
   if (!h || scan < 0 || (size_t)scan >= h->fdb.scans.size()) return nullptr;
   return &h->fdb.scans[(size_t)scan];
 }
@@ -510,8 +394,8 @@ void floor_detection_batch_release(dgs_handle* h) {
   for (DevBuf<float4>& b : S.filtered) b.release();
   S.clip.clear(); S.normals.clear(); S.filtered.clear(); S.scans.clear();
   prefilter_batch_release(S.nrm);
-  S.in.release(); S.tilted.release(); S.kept.release(); S.flags.release(); S.blk.release(); S.cnt.release(); S.totals.release(); S.tables.release();
-  S.stage.release(); S.sac_tables.release(); S.sac_stage.release(); S.draws.release(); S.counts.release(); S.meta.release(); S.hyps.release();
+  S.in.release(); S.tilted.release(); S.kept.release(); S.seg.release();
+  S.sac_tables.release(); S.sac_stage.release(); S.draws.release(); S.counts.release(); S.meta.release(); S.hyps.release();
   S.sac.release(); S.hyps_single.release();
 }
 
@@ -557,19 +441,19 @@ int dgs_floor_detection_batch(dgs_handle* h, const dgs_floor_detection_params* p
     S.normals.resize((size_t)n_scans);
     S.filtered.resize((size_t)n_scans);
   }
-  S.scans.assign((size_t)n_scans, FdbScan{});
+  S.scans.assign((size_t)n_scans, FdScan{});
   for (int s = 0; s < n_scans; s++) {
     for (int a = 0; a < 4; a++) coeffs4_out[4 * s + a] = 0.f;
     status_out[s] = DGS_FD_TOO_FEW_POINTS;
+    S.scans[(size_t)s].reset();
     S.scans[(size_t)s].n = sizes[s];
-    fdb_reset_trace(S.scans[(size_t)s].trace);
     S.clip[(size_t)s].n = 0;
     S.clip[(size_t)s].invalidate();
   }
-  const int64_t budget = S.points_budget > 0 ? S.points_budget : fdbplan::kBatchPoints;
-  const std::vector<fdbplan::Chunk> chunks = fdbplan::make_chunks(n_scans, sizes, budget);
+  const int64_t budget = S.points_budget > 0 ? S.points_budget : fdplan::kBatchPoints;
+  const std::vector<fdplan::Chunk> chunks = fdplan::make_chunks(n_scans, sizes, budget);
   std::vector<const float4*> d_in((size_t)n_scans);
-  for (const fdbplan::Chunk& ch : chunks) {
+  for (const fdplan::Chunk& ch : chunks) {
     const int f = ch.first;
     int rc = DGS_OK;
     if (in_on_device) {
@@ -587,7 +471,7 @@ int dgs_floor_detection_batch(dgs_handle* h, const dgs_floor_detection_params* p
     S.counts8[5]++;
   }
   for (int s = 0; s < n_scans; s++) {
-    const FdbScan& sc = S.scans[(size_t)s];
+    const FdScan& sc = S.scans[(size_t)s];
     status_out[s] = sc.status;
     for (int a = 0; a < 4; a++) coeffs4_out[4 * s + a] = sc.coeffs[a];
   }
@@ -595,67 +479,35 @@ int dgs_floor_detection_batch(dgs_handle* h, const dgs_floor_detection_params* p
 }
 
 int dgs_floor_detection_batch_get_filtered(dgs_handle* h, int32_t scan, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n) {
-  const FdbScan* sc = fdb_scan(h, scan);
-  if (!sc || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
-  const int64_t m = sc->n_filtered;
-  *n = m;
-  if (m == 0 || !out_xyz16 || capacity < m) return DGS_OK;
-  DGS_HIP_TRY(h, hipSetDevice(h->device));
-  DGS_HIP_TRY(h, hipMemcpyAsync(out_xyz16, h->fdb.filtered[(size_t)scan].ptr, (size_t)m * sizeof(float4),
-                                out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return DGS_OK;
+  const FdScan* sc = fdb_scan(h, scan);
+  return fd_get_filtered(h, sc, sc ? h->fdb.filtered[(size_t)scan].ptr : nullptr, out_xyz16, capacity, out_on_device, n);
 }
 
 int dgs_floor_detection_batch_get_inliers(dgs_handle* h, int32_t scan, int32_t* indices, float* points_xyz16, int64_t capacity, int64_t* n) {
-  FdbScan* sc = fdb_scan(h, scan);
-  if (!sc || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
-  if (!sc->have_inliers) {   // selectWithinDistance of the winner, in index order; no model: empty inliers
-    const dgs_floor_detection_params& p = h->fdb.params;
-    const int64_t nf = sc->n_filtered;
+  FdScan* sc = fdb_scan(h, scan);
+  if (sc && n && capacity >= 0 && !sc->have_inliers) {   // the list is made when somebody asks; no model: empty inliers
     if (sc->trace.winner_rank >= 0 && sc->status != DGS_FD_RNG_EXHAUSTED) {
       if (!sc->have_host) {
+        const int64_t nf = sc->n_filtered;
         DGS_HIP_TRY(h, hipSetDevice(h->device));
         sc->host_filtered.resize((size_t)nf);
         DGS_HIP_TRY(h, hipMemcpyAsync(sc->host_filtered.data(), h->fdb.filtered[(size_t)scan].ptr, (size_t)nf * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
         DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
         sc->have_host = true;
       }
-      const float* c = sc->trace.raw_coeffs;
-      for (int64_t i = 0; i < nf; i++)
-        if (fd_is_inlier(sc->host_filtered[(size_t)i], c[0], c[1], c[2], c[3], p.plane_dot_order, p.distance_threshold)) sc->inliers.push_back((int32_t)i);
+      fd_select_inliers(*sc, h->fdb.params, sc->trace.raw_coeffs);
     }
     sc->have_inliers = true;
   }
-  const int64_t m = (int64_t)sc->inliers.size();
-  *n = m;
-  if (m == 0 || capacity < m) return DGS_OK;
-  if (indices) std::memcpy(indices, sc->inliers.data(), (size_t)m * sizeof(int32_t));
-  if (points_xyz16)
-    for (int64_t j = 0; j < m; j++) std::memcpy(points_xyz16 + 4 * j, &sc->host_filtered[(size_t)sc->inliers[(size_t)j]], sizeof(float4));
-  return DGS_OK;
+  return fd_get_inliers(sc, indices, points_xyz16, capacity, n);
 }
 
-int dgs_floor_detection_batch_get_trace(dgs_handle* h, int32_t scan, dgs_floor_detection_trace* trace) {
-  const FdbScan* sc = fdb_scan(h, scan);
-  if (!sc || !trace) return DGS_ERR_INVALID_ARGUMENT;
-  *trace = sc->trace;
-  return DGS_OK;
-}
+int dgs_floor_detection_batch_get_trace(dgs_handle* h, int32_t scan, dgs_floor_detection_trace* trace) { return fd_get_trace(fdb_scan(h, scan), trace); }
 
 int dgs_floor_detection_batch_get_clipped(dgs_handle* h, int32_t scan, float* clipped_xyz16, float* normals4, int64_t capacity, int64_t* n) {
-  const FdbScan* sc = fdb_scan(h, scan);
-  if (!sc || !n || capacity < 0) return DGS_ERR_INVALID_ARGUMENT;
-  const int64_t m = sc->n_clipped;
-  *n = m;
-  if (m == 0 || capacity < m) return DGS_OK;
-  const FdbScratch& S = h->fdb;
-  DGS_HIP_TRY(h, hipSetDevice(h->device));
-  if (clipped_xyz16) DGS_HIP_TRY(h, hipMemcpyAsync(clipped_xyz16, S.clip[(size_t)scan].pts.ptr, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-  if (normals4 && sc->have_normals)
-    DGS_HIP_TRY(h, hipMemcpyAsync(normals4, S.normals[(size_t)scan].ptr, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return DGS_OK;
+  const FdScan* sc = fdb_scan(h, scan);
+  return fd_get_clipped(h, sc, sc ? h->fdb.clip[(size_t)scan].pts.ptr : nullptr, sc ? h->fdb.normals[(size_t)scan].ptr : nullptr, clipped_xyz16, normals4,
+                        capacity, n);
 }
 
 int dgs_floor_detection_batch_get_counts(dgs_handle* h, int64_t* counts8) {

@@ -229,10 +229,33 @@ struct BoScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// What detect() found in one scan, for the single call and for every scan of a batch: the getters of both read it
+// (floor_detection.hip fd_get_*).  The single call fills host_filtered and inliers while it runs, the batch when a getter asks.
+struct FdScan {
+  int64_t n = 0, n_clipped = 0, n_filtered = 0;
+  bool have_normals = false, have_host = false, have_inliers = false;
+  int32_t status = 1;                  // DGS_FD_TOO_FEW_POINTS
+  float coeffs[4] = {0.f, 0.f, 0.f, 0.f};
+  dgs_floor_detection_trace trace{};
+  std::vector<float4> host_filtered;   // the filtered cloud on the host: the inlier list is made there
+  std::vector<int32_t> inliers;
+  void reset() {                       // before a detect: nothing found; the host vectors keep their room
+    n = n_clipped = n_filtered = 0;
+    have_normals = have_host = have_inliers = false;
+    status = 1;
+    for (float& c : coeffs) c = 0.f;
+    trace = dgs_floor_detection_trace{};
+    trace.winner_rank = -1;
+    trace.sample[0] = trace.sample[1] = trace.sample[2] = -1;
+    host_filtered.clear();
+    inliers.clear();
+  }
+};
+
 // FloorDetectionNodelet::detect (floor_detection.hip): the stage clouds, the normal pass's own index and lists, the draw list and
 // hypotheses of the RANSAC, and what the getters read back.  Separate from everything a registration, the prefilter, the map cloud
 // or the line code uses.
-struct FdHyp;     // floor_detection.hip
+struct FdHyp;     // floor_detection_body.h
 struct FdScratch {
   DevBuf<float4> in, tilted, clipped, kept, filtered;   // staged host input; after the tilt; after the clips; after the normal filter; back-transformed
   DevBuf<unsigned char> flags, nflags; // keep flag per point of the pass being compacted; the prefilter rule's flags of pf_normal_kernel (unread)
@@ -243,11 +266,7 @@ struct FdScratch {
   DevBuf<float> cov9;
   SacScratch sac;                      // three point indices per draw; the permutation is the identity between detects
   DevBuf<FdHyp> hyps;                  // the good draws in order, at most max_iterations + 1
-  std::vector<float4> host_filtered;   // the filtered cloud on the host: final inlier flags and checks run there
-  std::vector<int32_t> inliers;
-  int64_t n_clipped = 0, n_filtered = 0;
-  bool have_normals = false;
-  dgs_floor_detection_trace trace{};
+  FdScan scan;                         // of the last detect
 };
 
 // calc_fitness_score over a batch of (cloud1, cloud2, relpose) edges between resident clouds, and the batched Hilbert index build in
@@ -304,23 +323,29 @@ struct CbScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// The buffers of the segmented stable compaction over the scans of a stage (compact.h seg_flags / seg_upload / seg_compact)
+struct SegCompact {
+  DevBuf<unsigned char> flags;         // keep flags, every scan padded to whole workgroups
+  DevBuf<int> blk;                     // per-workgroup kept counts of all scans (+ 1), scanned in place
+  DevBuf<int> cnt;                     // [0] kept points of all scans
+  DevBuf<int> totals;                  // kept points per scan of the stage
+  DevBuf<unsigned char> tables;        // the stage's table: entries | heads | first workgroups | first search workgroups
+  PinnedBlock stage;                   // the table's upload and the totals' download
+  void release() { flags.release(); blk.release(); cnt.release(); totals.release(); tables.release(); stage.release(); }
+};
+
 // The prefilter chain over many scans (prefilter_batch.hip): a pool of stage clouds per scan of a chunk, the shared flag / count /
 // neighbour arrays of all scans back to back, the stage tables and the pinned block they travel through.  Separate from PfScratch: the
 // single call's buffers and hooks are not touched, except that its hooks report n = 0 afterwards.
 struct PfbScratch {
   std::vector<CloudState> a, b, c, d, e;   // per scan: distance / down-sampling / outlier / height / flatten outputs (a, b, d carry the indices)
   DevBuf<float4> in;                   // staged host inputs, all scans of a chunk back to back
-  DevBuf<unsigned char> flags;         // keep flags, every scan padded to whole workgroups
-  DevBuf<int> blk;                     // per-workgroup kept counts of all scans (+ 1), scanned in place
-  DevBuf<int> cnt;                     // [0] kept points of all scans
-  DevBuf<int> totals;                  // kept points per scan of the stage
+  SegCompact seg;                      // every stage ends with its compaction's host wait
   DevBuf<int> nbr;                     // k-NN lists of all scans of a stage: [(points before the scan + position in index order) * 32 + slot]
   DevBuf<float> mean_d;                // statistical pass: per point, all scans back to back
   DevBuf<double> stats;                // statistical pass: mean, stddev, threshold, variance per scan
   DevBuf<float4> normals;              // normal pass (the body writes them)
   DevBuf<float> cov9;
-  DevBuf<unsigned char> tables;        // the stage's table: entries | heads | first workgroups | first search workgroups
-  PinnedBlock stage;                   // the table's upload and the totals' download; every stage ends with a host wait
   std::vector<double> stats_host;      // of the last call: {mean, stddev, threshold, points} per scan
   int64_t points_budget = 0;           // DGS_PREFILTER_BATCH_POINTS (0: pfbplan::kBatchPoints)
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -330,25 +355,13 @@ struct PfbScratch {
 // index, its normals and its filtered cloud stay on the device until the next batch; the getters read them by scan number.  The normal
 // stage runs in a PfbScratch of the batch's own (prefilter_batch_normal_stage).  Separate from FdScratch: the single call's buffers and
 // getters are not touched.
-struct FdbScan {
-  int64_t n = 0, n_clipped = 0, n_filtered = 0;
-  bool have_normals = false, have_host = false, have_inliers = false;
-  int32_t status = 1;                  // DGS_FD_TOO_FEW_POINTS
-  float coeffs[4] = {0.f, 0.f, 0.f, 0.f};
-  dgs_floor_detection_trace trace{};
-  std::vector<float4> host_filtered;   // fetched when a getter asks for the inliers
-  std::vector<int32_t> inliers;
-};
 struct FdbScratch {
   std::vector<CloudState> clip;        // per scan: the clipped cloud and (normal filter) its index
   std::vector<DevBuf<float4>> normals, filtered;   // per scan
-  std::vector<FdbScan> scans;          // of the last batch
+  std::vector<FdScan> scans;           // of the last batch
   PfbScratch nrm;                      // the normal stage's index build, lists, tables and pinned block
   DevBuf<float4> in, tilted, kept;     // staged host inputs; after the tilt; after the normal filter: all scans of a chunk back to back
-  DevBuf<unsigned char> flags;         // keep flags, every scan padded to whole workgroups
-  DevBuf<int> blk, cnt, totals;        // the segmented compaction's counts, total and per-scan totals
-  DevBuf<unsigned char> tables;        // the stage's table: entries | first workgroups
-  PinnedBlock stage;                   // a filter stage's table goes up from it, the totals come down into it
+  SegCompact seg;                      // the filter stages' flags, counts, tables and pinned block
   DevBuf<unsigned char> sac_tables;    // the RANSAC's table: entries | first tiles
   PinnedBlock sac_stage;               // its upload, the draw lists behind it, and where meta, counts and hypotheses come down
   DevBuf<int> draws, counts, meta;     // per live scan: its draw list; max_hyp counts; 4 ints of meta
@@ -356,7 +369,7 @@ struct FdbScratch {
   SacScratch sac;                      // mt19937 values and the identity permutation; the device buffers of a scan finished alone
   DevBuf<FdHyp> hyps_single;           // that scan's hypotheses
   dgs_floor_detection_params params{}; // of the last batch: the getters' inlier rule
-  int64_t points_budget = 0;           // DGS_FLOOR_BATCH_POINTS (0: fdbplan::kBatchPoints)
+  int64_t points_budget = 0;           // DGS_FLOOR_BATCH_POINTS (0: fdplan::kBatchPoints)
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -726,10 +739,6 @@ void building_overlap_release(dgs_handle* h);
 // floor_detection.hip
 void floor_detection_release(dgs_handle* h);
 const char* fd_bad_params(const dgs_floor_detection_params* p);   // why the parameters are refused, or nullptr
-// steps 5-8 of detect() over `pts` (n >= 3 points on the device) with a draw list of D draws, in the buffers handed in: the walk's end
-// state in `tr`, the winner's coefficients in `coeffs`, the cloud in *host_cloud.  *need_draws when the walk ran past the list.
-int fd_ransac(dgs_handle* h, const dgs_floor_detection_params& p, const float4* pts, int64_t n, const uint32_t* raw, int64_t D, SacScratch& sac,
-              DevBuf<FdHyp>& hyps, dgs_floor_detection_trace& tr, std::vector<float4>* host_cloud, bool* need_draws, float* coeffs);
 // floor_detection_batch.hip
 void floor_detection_batch_release(dgs_handle* h);
 // What a batched stage that runs inside another call did: the stage adds to the sink its caller hands it, the caller folds the sink
@@ -737,6 +746,28 @@ void floor_detection_batch_release(dgs_handle* h);
 struct StageCounts {
   int64_t launches = 0, waits = 0, built = 0;   // kernel launches, host waits, indices built
 };
+// floor_detection.hip, for the single call and the batch alike
+namespace fdplan { struct ScanWalk; }
+// a closed walk's end state -> tr; -> false: it ran past its draw list.  Else its winner, if it has one (hyps: the host's copy of the
+// scan's hypotheses), -> tr and `coeffs`.
+bool fd_walk_to_trace(const fdplan::ScanWalk& w, const FdHyp* hyps, dgs_floor_detection_trace& tr, float* coeffs);
+// steps 5-8 of detect() over `pts` (n >= 3 points on the device) in the buffers handed in (the single call's FdScratch, or the batch's
+// for a scan it finishes alone), with the draw list of `plan` and, while the walk runs past it, a longer one: the walk's end state in
+// sc.trace, the winner's coefficients in `coeffs`, the cloud in sc.host_filtered.  *exhausted: the stream (rng_raw, or nullptr:
+// mt19937(12345)) holds no further draw.  Launches and host waits are added to `did`.
+int fd_ransac_lists(dgs_handle* h, const dgs_floor_detection_params& p, const float4* pts, int64_t n, const uint32_t* rng_raw, SacDrawPlan& plan,
+                    SacScratch& sac, DevBuf<FdHyp>& hyps, FdScan& sc, float* coeffs, bool* exhausted, StageCounts* did);
+// selectWithinDistance of the plane `c` over sc.host_filtered, in index order -> sc.inliers
+void fd_select_inliers(FdScan& sc, const dgs_floor_detection_params& p, const float* c);
+// step 9, the checks behind the RANSAC (fdplan::verdict): `coeffs` the winner's when sc.trace names one, `inliers` its inlier count
+// -> sc.status, sc.coeffs, sc.trace.raw_coeffs and sc.trace.dot
+void fd_verdict(FdScan& sc, const dgs_floor_detection_params& p, const float* tilt_inv16, const float* coeffs, int64_t inliers);
+// the getters of both calls over a scan's record (nullptr: no such scan) and the device arrays of that scan
+int fd_get_filtered(dgs_handle* h, const FdScan* sc, const float4* d_filtered, float* out_xyz16, int64_t capacity, int32_t out_on_device, int64_t* n);
+int fd_get_inliers(const FdScan* sc, int32_t* indices, float* points_xyz16, int64_t capacity, int64_t* n);
+int fd_get_trace(const FdScan* sc, dgs_floor_detection_trace* trace);
+int fd_get_clipped(dgs_handle* h, const FdScan* sc, const float4* d_clipped, const float4* d_normals, float* clipped_xyz16, float* normals4, int64_t capacity,
+                   int64_t* n);
 // fitness_batch.hip
 // the batched index build as a call of its own: FbScratch::counts8 reports it (and nothing else); `did` (nullable) receives the same
 int fitness_batch_build_indices(dgs_handle* h, int n, dgs_cloud* const* clouds, StageCounts* did = nullptr);

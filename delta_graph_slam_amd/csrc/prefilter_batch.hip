@@ -73,40 +73,23 @@ __global__ __launch_bounds__(kBlock) void pfb_height_kernel(const PfbSeg* __rest
   pf_height_body(e.in, e.n, e.lz, e.flags, (int)blockIdx.x - e.blk0);
 }
 
-// ---- segmented stable compaction (compact.h) ------------------------------------------------------------------------------------
-// blk: one count per workgroup of the launch and one more behind them, which workgroup 0 zeroes: pf_scan_kernel runs over gridDim.x + 1
-__global__ __launch_bounds__(kBlock) void pfb_count_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m, int* __restrict__ blk) {
-  const PfbSeg& e = tab[seg_find(first, m, (int)blockIdx.x)];
-  const int i = ((int)blockIdx.x - e.blk0) * kBlock + threadIdx.x;
-  const int t = compact_count_seg(e.flags, i, e.n);
-  if (threadIdx.x == 0) {
-    blk[blockIdx.x] = t;
-    if (blockIdx.x == 0) blk[gridDim.x] = 0;
-  }
-}
+// ---- the scatters of the segmented stable compaction (compact.h; the count launch is compact_count_seg_kernel<PfbSeg>) ------------------
 __global__ __launch_bounds__(kBlock) void pfb_scatter_kernel(const PfbSeg* __restrict__ tab, const int* __restrict__ first, const int m, const int* __restrict__ blk,
                                                              int* __restrict__ totals, const int flatten) {
   const int c = seg_find(first, m, (int)blockIdx.x);
   const PfbSeg& e = tab[c];
-  const int lb = (int)blockIdx.x - e.blk0, seg0 = blk[e.blk0];
-  if (lb == 0 && threadIdx.x == 0) totals[c] = blk[first[c + 1]] - seg0;
-  const int i = lb * kBlock + threadIdx.x;
-  int off;
-  if (!compact_slot_seg(e.flags, i, e.n, blk[blockIdx.x] - seg0, &off)) return;
-  float4 p = e.in[i];
-  if (flatten) p.z = 0.f;   // flatten (:181): point.z = 0
-  e.out[off] = p;           // off < kept points of the scan <= n: `out` holds n points
+  compact_scatter_seg<int>(e, c, first, blk, totals, [&](const int i, const int off) {
+    float4 p = e.in[i];
+    if (flatten) p.z = 0.f;   // flatten (:181): point.z = 0
+    e.out[off] = p;           // `out` holds n points
+  });
 }
 __global__ __launch_bounds__(kBlock) void pfb_head_scatter_kernel(const PfbSeg* __restrict__ tab, const PfHead* __restrict__ heads, const int* __restrict__ first,
                                                                   const int m, const int* __restrict__ blk, int* __restrict__ totals) {
   const int c = seg_find(first, m, (int)blockIdx.x);
   const PfbSeg& e = tab[c];
-  const int lb = (int)blockIdx.x - e.blk0, seg0 = blk[e.blk0];
-  if (lb == 0 && threadIdx.x == 0) totals[c] = blk[first[c + 1]] - seg0;
-  const long long i = (long long)lb * kBlock + threadIdx.x;
-  int off;
-  if (!compact_slot_seg(e.flags, i, (long long)e.n, blk[blockIdx.x] - seg0, &off)) return;
-  pf_head_scatter_body(e.in, (long long)e.n, heads[c], i, off, e.out);
+  compact_scatter_seg<long long>(e, c, first, blk, totals,
+                                 [&](const long long i, const int off) { pf_head_scatter_body(e.in, (long long)e.n, heads[c], i, off, e.out); });
 }
 
 // ---- k-NN stages ---------------------------------------------------------------------------------------------------------------
@@ -142,74 +125,32 @@ __global__ __launch_bounds__(kBlock) void pfb_normal_kernel(const PfbSeg* __rest
 // ---- host --------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// the device addresses of an uploaded stage table
-struct PfbDev {
-  const PfbSeg* tab;
-  const PfHead* heads;
-  const int* first;
-  const int* knn_first;
-  int* totals_h;     // pinned: where the compaction's totals arrive (one per item)
-  double* stats_h;   // pinned: room for 4 doubles per item
-};
+using PfbDev = SegDev<PfbSeg>;
 
-// entries | heads | first workgroups | first search workgroups -> S.tables in one copy from the pinned block.  The stream is idle here
-// (every stage ended with a host wait), so the block may be rewritten and regrown.
-int pfb_upload(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, const std::vector<PfbSeg>& segs, const PfHead* heads, PfbDev* dev) {
-  const size_t m = St.items.size();
-  const segtab::StageTable T = segtab::stage_table(m, sizeof(PfbSeg), heads ? sizeof(PfHead) : 0);
-  DGS_HIP_TRY(h, S.stage.reserve(T.all));
-  DGS_HIP_TRY(h, S.tables.reserve(T.up));
-  DGS_HIP_TRY(h, S.totals.reserve(m));
-  char* st = S.stage.at(0);
-  std::memcpy(st + T.entries, segs.data(), m * sizeof(PfbSeg));
-  if (heads)
-    for (size_t j = 0; j < m; j++) std::memcpy(st + T.heads + j * sizeof(PfHead), &heads[St.items[j].scan], sizeof(PfHead));
-  const std::vector<int> first = St.first(), knn_first = St.knn_first();
-  std::memcpy(st + T.first, first.data(), (m + 1) * sizeof(int));
-  std::memcpy(st + T.knn_first, knn_first.data(), (m + 1) * sizeof(int));
-  DGS_HIP_TRY(h, hipMemcpyAsync(S.tables.ptr, st, T.up, hipMemcpyHostToDevice, h->stream));
-  dev->tab = reinterpret_cast<const PfbSeg*>(S.tables.ptr + T.entries);
-  dev->heads = reinterpret_cast<const PfHead*>(S.tables.ptr + T.heads);
-  dev->first = reinterpret_cast<const int*>(S.tables.ptr + T.first);
-  dev->knn_first = reinterpret_cast<const int*>(S.tables.ptr + T.knn_first);
-  dev->totals_h = reinterpret_cast<int*>(st + T.totals);
-  dev->stats_h = reinterpret_cast<double*>(st + T.stats);
-  return DGS_OK;
-}
-
-// the flag array of a stage and every entry's place in it
+// the flag array of a stage and every entry's place in it and in the search launch
 int pfb_flags(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, std::vector<PfbSeg>& segs) {
-  DGS_HIP_TRY(h, S.flags.reserve((size_t)St.blocks * kBlock));
+  if (int rc = seg_flags(h, S.seg, St, segs)) return rc;
   for (size_t j = 0; j < segs.size(); j++) {
-    const pfbplan::Item& it = St.items[j];
-    segs[j].flags = S.flags.ptr + (size_t)it.blk0 * kBlock;
-    segs[j].n = (int)it.n;
-    segs[j].blk0 = it.blk0;
-    segs[j].knn_blk0 = it.knn_blk0;
-    segs[j].parts = it.parts;
+    segs[j].knn_blk0 = St.items[j].knn_blk0;
+    segs[j].parts = St.items[j].parts;
   }
   return DGS_OK;
+}
+// entries | heads | first workgroups | first search workgroups -> S.seg.tables in one copy.  The stream is idle here: every stage ended
+// with a host wait.
+int pfb_upload(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, const std::vector<PfbSeg>& segs, const PfHead* heads, PfbDev* dev) {
+  return seg_upload(h, S.seg, St, segs, heads, sizeof(PfHead), dev);
 }
 
 // count, scan, scatter over all scans of the stage; kept[j] = kept points of item j (read back: the host waits here)
 int pfb_compact(dgs_handle* h, PfbScratch& S, const pfbplan::Stage& St, const PfbDev& dev, bool head, bool flatten, std::vector<int64_t>& kept) {
   const int m = (int)St.items.size();
-  DGS_HIP_TRY(h, S.blk.reserve((size_t)St.blocks + 1));
-  DGS_HIP_TRY(h, S.cnt.reserve(4));
-  hipLaunchKernelGGL(pfb_count_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, h->stream, dev.tab, dev.first, m, S.blk.ptr);
-  hipLaunchKernelGGL(pf_scan_kernel, dim3(1), dim3(kCompactScanBlock), 0, h->stream, S.blk.ptr, St.blocks + 1, S.cnt.ptr);
-  if (head)
-    hipLaunchKernelGGL(pfb_head_scatter_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, h->stream, dev.tab, dev.heads, dev.first, m, S.blk.ptr, S.totals.ptr);
-  else
-    hipLaunchKernelGGL(pfb_scatter_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, h->stream, dev.tab, dev.first, m, S.blk.ptr, S.totals.ptr, flatten ? 1 : 0);
-  DGS_HIP_TRY(h, hipGetLastError());
-  DGS_HIP_TRY(h, hipMemcpyAsync(dev.totals_h, S.totals.ptr, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  S.counts8[0] += 3;
-  S.counts8[1]++;
-  kept.assign((size_t)m, 0);
-  for (int j = 0; j < m; j++) kept[j] = dev.totals_h[j];
-  return DGS_OK;
+  return seg_compact(h, S.seg, St, dev, S.counts8, kept, [&](const dim3 grid, const int* blk, int* totals) {
+    if (head)
+      hipLaunchKernelGGL(pfb_head_scatter_kernel, grid, dim3(kBlock), 0, h->stream, dev.tab, static_cast<const PfHead*>(dev.heads), dev.first, m, blk, totals);
+    else
+      hipLaunchKernelGGL(pfb_scatter_kernel, grid, dim3(kBlock), 0, h->stream, dev.tab, dev.first, m, blk, totals, flatten ? 1 : 0);
+  });
 }
 
 // indices of the stage's input clouds by the batched build, their k-NN lists into S.nbr; the entries get views and slices
@@ -281,7 +222,7 @@ int pfb_chain(dgs_handle* h, const dgs_prefilter_params* p, int n, const PfHead*
       }
       if (int rc = pfb_upload(h, S, St, segs, heads, &dev)) return rc;
       if (heads)
-        hipLaunchKernelGGL(pfb_head_flag_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.heads, dev.first, m, p->distance_near_thresh, p->distance_far_thresh);
+        hipLaunchKernelGGL(pfb_head_flag_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, static_cast<const PfHead*>(dev.heads), dev.first, m, p->distance_near_thresh, p->distance_far_thresh);
       else
         hipLaunchKernelGGL(pfb_distance_kernel, dim3((unsigned)St.blocks), dim3(kBlock), 0, st, dev.tab, dev.first, m, p->distance_near_thresh, p->distance_far_thresh);
       S.counts8[0]++;
@@ -506,8 +447,7 @@ void prefilter_batch_release(PfbScratch& S) {
     for (CloudState& c : *pool) c.release();
     pool->clear();
   }
-  S.in.release(); S.flags.release(); S.blk.release(); S.cnt.release(); S.totals.release(); S.nbr.release(); S.mean_d.release(); S.stats.release();
-  S.normals.release(); S.cov9.release(); S.tables.release(); S.stage.release();
+  S.in.release(); S.seg.release(); S.nbr.release(); S.mean_d.release(); S.stats.release(); S.normals.release(); S.cov9.release();
   S.stats_host.clear();
 }
 

@@ -3,6 +3,7 @@
 // on its own (tests/cpp/seg_table_check.cpp).
 #pragma once
 #include <cstddef>
+#include <cstring>
 #include <vector>
 
 namespace dgs {
@@ -28,7 +29,7 @@ std::vector<int> first_array(const Item* items, const size_t m, int Item::*first
   return f;
 }
 
-// A stage of the prefilter over many scans (prefilter_batch.hip pfb_upload): entries | heads | first workgroups | first search
+// A stage over many scans (compact.h seg_upload; the RANSAC rounds of floor_detection_batch.hip): entries | heads | first workgroups | first search
 // workgroups go up in one copy of `up` bytes; behind them, in the pinned block only, the totals and the statistics come down.
 struct StageTable {
   size_t entries, heads, first, knn_first, up, totals, stats, all;
@@ -44,6 +45,12 @@ inline StageTable stage_table(const size_t m, const size_t entry_bytes, const si
   T.stats = L.take(m * 4 * sizeof(double), 64);
   T.all = L.end;
   return T;
+}
+// the part of `block` that goes up, zeroed, with the entries and the first workgroups (m + 1 of them) at their places
+inline void place(char* block, const StageTable& T, const void* entries, const size_t entries_bytes, const std::vector<int>& first) {
+  std::memset(block, 0, T.up);
+  std::memcpy(block + T.entries, entries, entries_bytes);
+  std::memcpy(block + T.first, first.data(), first.size() * sizeof(int));
 }
 
 // A chunk of the batched covariance pass (cov_batch.hip ensure_covariances): entries | first search workgroups | first covariance

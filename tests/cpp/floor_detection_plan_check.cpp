@@ -1,16 +1,18 @@
-// The host plan of floor detection over many scans (delta_graph_slam_amd/csrc/floor_detection_batch_plan.h) on its own, against
+// The host plan of floor detection (delta_graph_slam_amd/csrc/floor_detection_plan.h) on its own, against
 // expectations written by hand: first-workgroup tables at the sizes around a workgroup and a score tile, dead scans between live ones,
-// chunk boundaries, the walks of scans that close in different rounds with the round tables and their y extent, the status mapping.
+// chunk boundaries, the walks of scans that close in different rounds with the round tables and their y extent, the status mapping,
+// the verdict's status, dot product and coefficients at its edges.
 // No device, no library: built with g++ -fsanitize=address,undefined by tests/test_floor_detection_batch_cpu.py.  Prints "ok" and
 // exits 0, or names the first failed check.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
-#include "floor_detection_batch_plan.h"
+#include "floor_detection_plan.h"
 
-using namespace dgs::fdbplan;
+using namespace dgs::fdplan;
 
 static int failures = 0;
 #define CHECK(cond)                                                        \
@@ -25,6 +27,21 @@ struct Hyp {
   int draw;
 };
 static double cube(double w) { return std::pow(w, 3.0); }
+
+// verdict() into outputs that start at 0
+struct V {
+  int status;
+  float raw[4], dot, out[4];
+};
+static V run(const float* win, int64_t inliers, const float* tilt_inv16, int floor_pts_thresh, double floor_normal_thresh) {
+  V v{};
+  v.status = verdict(win, inliers, tilt_inv16, floor_pts_thresh, floor_normal_thresh, v.raw, &v.dot, v.out);
+  return v;
+}
+static bool same4(const float* got, float a, float b, float c, float d) {   // bit for bit: -0.0f is not 0.0f
+  const float want[4] = {a, b, c, d};
+  return std::memcmp(got, want, sizeof(want)) == 0;
+}
 
 int main() {
   // ---- first-workgroup tables of a filter stage at 0 / 1 / 256 / 257 / 1,023 / 1,024 / 1,025 points
@@ -152,6 +169,42 @@ int main() {
   CHECK(decide(0, 0, 0.0, 0.98) == kNotVertical);                       // no model, threshold 0: the zero normal fails the verticality check
   CHECK(decide(900, 512, 0.97, 0.98) == kNotVertical && decide(900, 512, 0.98, 0.98) == kDetected);
   CHECK(kDetected == 0 && kTooFewPoints == 1 && kTooFewInliers == 2 && kNotVertical == 3 && kRngExhausted == 4);
+
+  // ---- the verdict: status, dot and coefficients as both calls store them (outputs start at 0, as a reset record's do)
+  {
+    const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // column-major: the reference is (0, 0, 1)
+    const float up[4] = {0.f, 0.f, 1.f, -2.f};
+    // no model: all-zero coefficients.  floor_pts_thresh 0 lets the count pass and the zero normal fails the verticality check
+    V v = run(nullptr, 0, eye, 0, 10.0);
+    CHECK(v.status == kNotVertical && v.dot == 0.f && same4(v.raw, 0.f, 0.f, 0.f, 0.f) && same4(v.out, 0.f, 0.f, 0.f, 0.f));
+    v = run(nullptr, 0, eye, 1, 10.0);
+    CHECK(v.status == kTooFewInliers && v.dot == 0.f && same4(v.raw, 0.f, 0.f, 0.f, 0.f) && same4(v.out, 0.f, 0.f, 0.f, 0.f));
+    // one inlier below floor_pts_thresh: no dot product yet, the raw coefficients are the winner's all the same; exactly at it
+    v = run(up, 511, eye, 512, 10.0);
+    CHECK(v.status == kTooFewInliers && v.dot == 0.f && same4(v.raw, 0.f, 0.f, 1.f, -2.f) && same4(v.out, 0.f, 0.f, 0.f, 0.f));
+    v = run(up, 512, eye, 512, 10.0);
+    CHECK(v.status == kDetected && v.dot == 1.f && same4(v.raw, 0.f, 0.f, 1.f, -2.f) && same4(v.out, 0.f, 0.f, 1.f, -2.f));
+    // |dot| == cos(floor_normal_thresh) exactly (0 degrees: cos = 1): the comparison is <, so DETECTED; one float below 1: NOT_VERTICAL
+    v = run(up, 600, eye, 512, 0.0);
+    CHECK(v.status == kDetected && v.dot == 1.f && same4(v.out, 0.f, 0.f, 1.f, -2.f));
+    const float below[4] = {0.f, 0.f, 0.99999994f, -2.f};
+    v = run(below, 600, eye, 512, 0.0);
+    CHECK(v.status == kNotVertical && v.dot == 0.99999994f && same4(v.raw, 0.f, 0.f, 0.99999994f, -2.f) && same4(v.out, 0.f, 0.f, 0.f, 0.f));
+    // a downward normal: all four come back times -1, the signs of zeros included
+    const float down[4] = {0.f, 0.25f, -1.f, 0.f};
+    v = run(down, 600, eye, 512, 10.0);
+    CHECK(v.status == kDetected && v.dot == -1.f && same4(v.raw, 0.f, 0.25f, -1.f, 0.f) && same4(v.out, -0.f, -0.25f, 1.f, -0.f));
+    const float down_neg0[4] = {-0.f, 0.f, -1.f, -0.f};
+    v = run(down_neg0, 600, eye, 512, 10.0);
+    CHECK(v.status == kDetected && v.dot == -1.f && same4(v.raw, -0.f, 0.f, -1.f, -0.f) && same4(v.out, 0.f, -0.f, 1.f, 0.f));
+    // a tilted sensor: the reference is the third COLUMN (0.5, 0.25, 0.75), not the third row (9, 9, 0.75)
+    float tilt[16] = {1, 0, 9, 0, 0, 1, 9, 0, 0.5f, 0.25f, 0.75f, 0, 0, 0, 0, 1};
+    const float plane[4] = {0.5f, 0.5f, 0.75f, -2.f};   // (0.25 + 0.125) + 0.5625 = 0.9375; cos 10 deg = 0.98..., cos 25 deg = 0.90...
+    v = run(plane, 600, tilt, 512, 10.0);
+    CHECK(v.status == kNotVertical && v.dot == 0.9375f && same4(v.raw, 0.5f, 0.5f, 0.75f, -2.f) && same4(v.out, 0.f, 0.f, 0.f, 0.f));
+    v = run(plane, 600, tilt, 512, 25.0);
+    CHECK(v.status == kDetected && v.dot == 0.9375f && same4(v.out, 0.5f, 0.5f, 0.75f, -2.f));
+  }
 
   if (failures) return 1;
   std::printf("ok\n");

@@ -81,12 +81,12 @@ def test_the_python_wrapper_validates_its_lists_before_the_library_is_called():
 
 
 def test_the_host_plan_against_hand_written_expectations(tmp_path):
-    """floor_detection_batch_plan.h has no HIP in it: a plain g++ program includes it and checks the first-workgroup tables at 0 / 1 /
+    """floor_detection_plan.h has no HIP in it: a plain g++ program includes it and checks the first-workgroup tables at 0 / 1 /
     256 / 257 / 1,023 / 1,024 / 1,025 points, dead scans between live ones, chunk boundaries, round tables where scans close in different
-    rounds, the y extent of a round and the status mapping; built with the host sanitizers and run directly"""
-    exe = str(tmp_path / "floor_detection_batch_plan_check")
+    rounds, the y extent of a round, the status mapping and the verdict (status, dot product, coefficients at its edges); built with the host sanitizers and run directly"""
+    exe = str(tmp_path / "floor_detection_plan_check")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", os.path.join(ROOT, "delta_graph_slam_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "floor_detection_batch_plan_check.cpp"),
+                           "-I", os.path.join(ROOT, "delta_graph_slam_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "floor_detection_plan_check.cpp"),
                            "-o", exe])
     p = subprocess.run([exe], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.strip().splitlines()[-1] == "ok", p.stdout + p.stderr
