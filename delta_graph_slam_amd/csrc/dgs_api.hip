@@ -1231,6 +1231,13 @@ int dgs_deal_probe_cost(dgs_handle* h, const int32_t* active, const int32_t* kin
   return DGS_OK;
 }
 
+int dgs_strict_row_probe(dgs_handle* h, const double* totals, int32_t ncol, double* rows2) {
+  if (!h || !totals || !rows2 || ncol < 1 || ncol > 43) return DGS_ERR_INVALID_ARGUMENT;
+  h->err.clear();
+  if (set_device(h)) return DGS_ERR_HIP;
+  return strict_row_probe(h, totals, ncol, rows2);
+}
+
 int dgs_find_loop_candidates(dgs_handle* h, const double* accum_distance, const double* xy, int64_t n, int32_t on_device, double new_accum_distance,
                              const double* new_xy, double accum_distance_thresh, double distance_thresh, int32_t* indices, int64_t capacity, int64_t* n_out) {
   if (!h || !n_out || !new_xy || n < 0 || capacity < 0 || (n > 0 && (!accum_distance || !xy)) || (capacity > 0 && !indices) || n > INT32_MAX) return DGS_ERR_INVALID_ARGUMENT;

@@ -645,6 +645,7 @@ int ndt_align_pairs(dgs_handle* h, int n_pairs, const float4* const* d_src_ptrs_
                     const float* guesses16, dgs_result* results);
 int ndt_trajectory(dgs_handle* h, int pair, double* out, int* len);
 int ndt_probe(dgs_handle* h, const double* p6, const float* T16, double* score, double* g6, double* H36, int kind = 1);   // kind 2: the double-precision computeHessian pass
+int strict_row_probe(dgs_handle* h, const double* totals, int ncol, double* rows2);   // dgs_strict_row_probe
 // pcl_ndt.hip (DGS_METHOD_PCL_NDT): the evaluation kernel of pcl::NormalDistributionsTransform, launched by ndt_align.hip's driver in place of its own
 inline bool is_pcl_ndt(const dgs_handle* h) { return h->prm.method == DGS_METHOD_PCL_NDT; }
 inline bool is_ndt_family(const dgs_handle* h) { return h->prm.method == DGS_METHOD_NDT || h->prm.method == DGS_METHOD_PCL_NDT; }   // voxel model, NDT driver, NDT hooks

@@ -885,4 +885,35 @@ int ndt_probe(dgs_handle* h, const double* p6, const float* T16, double* score, 
   return DGS_OK;
 }
 
+// Test hook (dgs_strict_row_probe): one workgroup reduces a [kBlock][kStrictAccum] matrix of per-thread totals twice -- as the item-compacted
+// kernel's timed instantiation does, in passes as wide as its wave's table region allows, and in the stand-alone form's passes of 11 columns.
+__global__ __launch_bounds__(kBlock) void strict_row_probe_kernel(const double* __restrict__ totals, const int ncol, double* __restrict__ rows2) {
+  constexpr int kBytes = StrictTile<DGS_NDT_DIRECT7, true, true>::kTableBytes;
+  __shared__ __attribute__((aligned(16))) unsigned char s_tab[kBlock / kWave][kBytes];
+  double acc[kStrictAccum];
+#pragma unroll
+  for (int k = 0; k < kStrictAccum; k++) acc[k] = totals[(size_t)threadIdx.x * kStrictAccum + k];
+  strict_block_row<false, false, kBytes>(acc, ncol, rows2, reinterpret_cast<double*>(s_tab[threadIdx.x >> 6]));
+  __syncthreads();
+  strict_block_row<false, true>(acc, ncol, rows2 + kStrictPad);
+}
+int strict_row_probe(dgs_handle* h, const double* totals, int ncol, double* rows2) {
+  DevBuf<double> d;   // the matrix, then the two rows
+  const size_t n_in = (size_t)kBlock * kStrictAccum, n_out = 2 * (size_t)kStrictPad;
+  hipError_t e = d.reserve(n_in + n_out);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.ptr, totals, sizeof(double) * n_in, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(strict_row_probe_kernel, dim3(1), dim3(kBlock), 0, h->stream, d.ptr, ncol, d.ptr + n_in);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(rows2, d.ptr + n_in, sizeof(double) * n_out, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  d.release();
+  if (e != hipSuccess) {
+    h->err = std::string("dgs_strict_row_probe: ") + hipGetErrorString(e);
+    return DGS_ERR_HIP;
+  }
+  return DGS_OK;
+}
+
 }  // namespace dgs

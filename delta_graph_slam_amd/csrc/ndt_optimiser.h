@@ -562,20 +562,30 @@ __global__ __launch_bounds__(kBlock) void ndt_solve_kernel(NdtPair* __restrict__
   }
   if (threadIdx.x < kStrictPad) {
     if (strict_from_rows) {
-      // order 1: the workgroups' rows added in slice order (what ndt_strict_reduce_kernel did as a launch of its own), four loads in
-      // flight, the additions in the same sequence
+      // order 1: the workgroups' rows added as the fused launch's closing adds them (ndt_close_strict, ndt_strict.h) -- five partial sums, sum
+      // g over the rows g, g + 5, g + 10, ... in steps of four, (((v + r0) + r1) + r2) + r3 with 0.0 for a row the pair lacks, then the five
+      // in order -- so that the two paths give the same bits whatever the row count (tests/test_strict_closing_rows_gpu.py).  It used to add
+      // the rows one after the other in slice order: the same additions up to five rows, another association above (1-3 ulps of the score).
       const int nb = pair_blocks[pair];
       const double* base = partials + (size_t)pair * cap_blocks * kStrictPad + threadIdx.x;
-      double v = 0.0;
-      for (int b0 = 0; b0 < nb; b0 += 4) {
-        double r[4];
+      constexpr int G = kBlock / kStrictPad;
+      double t = 0.0;
+#pragma unroll 1
+      for (int grp = 0; grp < G; grp++) {
+        double v = 0.0;
+        for (int b0 = grp; b0 < nb; b0 += 4 * G) {
+          double r[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) r[k] = base[(size_t)min(b0 + k, nb - 1) * kStrictPad];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (b0 + k < nb) v += r[k];
+          for (int k = 0; k < 4; k++) {
+            const int b = b0 + k * G;
+            const double x = base[(size_t)min(b, nb - 1) * kStrictPad];
+            r[k] = (b < nb) ? x : 0.0;
+          }
+          v = (((v + r[0]) + r[1]) + r[2]) + r[3];
+        }
+        t += v;
       }
-      tot[threadIdx.x] = v;
+      tot[threadIdx.x] = t;
     } else {
       tot[threadIdx.x] = strict_totals[(size_t)pair * kStrictPad + threadIdx.x];
     }

@@ -485,13 +485,24 @@ __device__ __forceinline__ void strict_point_hd(const float4 xf, const float (&x
 // the four waves' sums are added in wave order.  Same construction as ndt_block_row, same reason: a DPP / shuffle butterfly over 43
 // doubles costs ~1,500 wave-instructions.
 constexpr int kStrictRowScratch = 11 * 65;   // doubles of per-wave transposition scratch
-template <bool COHERENT, bool OWN_SCRATCH = true>
+// A caller that hands in its own scratch (the item-compacted kernel: the wave's table region) gets passes as wide as that scratch allows: 22
+// columns x 65 doubles = 11,440 B where it holds them -- two passes instead of four for the 43 columns of a Hessian evaluation, each of them 64
+// dependent additions on the lanes that sum while the rest of the workgroup waits at the barrier behind.  A column is summed by one lane in
+// lane order whatever the width of the pass: the same additions in the same order.  The stand-alone form (OWN_SCRATCH) keeps 11.
+// `make ab AB=-DDGS_STRICT_WIDE_ROWS=0`: 11 columns per pass everywhere.
+#ifndef DGS_STRICT_WIDE_ROWS
+#define DGS_STRICT_WIDE_ROWS 1
+#endif
+constexpr int kStrictRowColsWide = 22;
+constexpr int strict_row_cols(const int scratch_bytes) { return (DGS_STRICT_WIDE_ROWS != 0 && scratch_bytes >= kStrictRowColsWide * 65 * 8) ? kStrictRowColsWide : 11; }
+template <bool COHERENT, bool OWN_SCRATCH = true, int SCRATCH_BYTES = 0>
 __device__ __forceinline__ void strict_block_row(const double (&acc)[kStrictAccum], const int ncol, double* __restrict__ row_of_slice, double* wave_scratch = nullptr) {
-  constexpr int CH = 11, RS = 65, NCH = 4;
+  constexpr int CH = OWN_SCRATCH ? 11 : strict_row_cols(SCRATCH_BYTES), RS = 65, NCH = (kStrictAccum + CH - 1) / CH;
+  static_assert(OWN_SCRATCH || CH * RS * 8 <= SCRATCH_BYTES, "a pass fits the scratch the caller hands in");
   __shared__ double tr[OWN_SCRATCH ? kBlock / kWave : 1][OWN_SCRATCH ? CH * RS : 1];
   __shared__ double sm[kBlock / kWave][kStrictPad];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double* my = OWN_SCRATCH ? tr[wave] : wave_scratch;   // !OWN_SCRATCH: this wave's own LDS region (>= kStrictRowScratch doubles), free by now
+  double* my = OWN_SCRATCH ? tr[wave] : wave_scratch;   // !OWN_SCRATCH: this wave's own LDS region (SCRATCH_BYTES of it), free by now
 #pragma unroll
   for (int h = 0; h < NCH; h++) {
     if (h * CH >= ncol) break;   // wave-uniform
@@ -523,8 +534,10 @@ __device__ __forceinline__ void strict_block_row(const double (&acc)[kStrictAccu
 // instead of 5.4, the waves waiting for the slowest of the four at every slice) leaves the wave's column sums in LDS, slot by slot; the rows of
 // up to kStrictSlots slices are then written together behind ONE barrier, each row = ((wave 0 + wave 1) + wave 2) + wave 3 as before.
 constexpr int kStrictSlots = 4;
+template <int SCRATCH_BYTES>
 __device__ __forceinline__ void strict_wave_cols(const double (&acc)[kStrictAccum], const int ncol, double* __restrict__ my, double* __restrict__ cols_of_wave) {
-  constexpr int CH = 11, RS = 65, NCH = 4;
+  constexpr int CH = strict_row_cols(SCRATCH_BYTES), RS = 65, NCH = (kStrictAccum + CH - 1) / CH;
+  static_assert(CH * RS * 8 <= SCRATCH_BYTES, "a pass fits the scratch the caller hands in");
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int h = 0; h < NCH; h++) {
@@ -602,6 +615,10 @@ __device__ __forceinline__ void ndt_close_strict(NdtPair* st, const double* rows
   constexpr int G = kBlock / kStrictPad;   // 5 groups of 48 columns; threads 240.. idle
   __shared__ double sm[G][kStrictPad];
   const int col = threadIdx.x % kStrictPad, grp = threadIdx.x / kStrictPad;
+  // (Measured and removed, see history: every row of a thread requested before its first addition, 32 rows per trip instead of four -- two
+  // dependent round trips instead of seven for the 26 rows a thread sums when a pair has the launch to itself.  The step got SLOWER, 4.26-4.41
+  // against 4.22-4.26 ms for the same build with four rows per trip, four alternations on one box: a trip of 32 clamps to the pair's last row
+  // whatever it lacks, and the launches where the time is have 32 rows per pair, seven per thread.)
   if (grp < G) {
     double v = 0.0;
     for (int b0 = grp; b0 < blocks_per_pair; b0 += 4 * G) {
@@ -937,7 +954,10 @@ constexpr int kStrictStampShift = 8;   // stamp build: 1 + the launch's slot in 
 // its closing (100 MHz wall clock) with its blockIdx, pair, slice, kind and the launch's n_active in a 64-byte record: plain vector stores by
 // thread 0.  The host names the launches to record and writes the buffer to a file (ndt_align.hip, DGS_DEAL_STAMPS_FILE).
 #ifdef DGS_DEAL_STAMPS
-constexpr int kStampLaunches = 256, kStampGrid = 2048, kStampWords = 8;
+// Words 6..11, wave 0's life around its item loops: 6 the end of the prologue barrier, 7 / 8 the ticks its tile prologues / its item loops took
+// in all (laps kept in SGPRs), 9 the start of the row reduction, 10 the row's stores issued (word 1: drained, the workgroup behind its barrier),
+// 11 the ticket taken.
+constexpr int kStampLaunches = 256, kStampGrid = 2048, kStampWords = 16;
 static __device__ unsigned long long* g_deal_stamps;
 #define STRICT_DEAL_STAMP_BEGIN                                                                                                        \
   const unsigned long long stamp_t0 = wall_clock64();                                                                                  \
@@ -952,10 +972,29 @@ static __device__ unsigned long long* g_deal_stamps;
     stamp_rec[5] = (unsigned long long)(unsigned)(n_active) | ((unsigned long long)gridDim.x << 32);                                   \
   }
 #define STRICT_DEAL_STAMP_CLOSED if (stamp_rec) stamp_rec[2] = wall_clock64();
+#define STRICT_DEAL_STAMP_MARK(word) if (stamp_rec) stamp_rec[word] = wall_clock64();
+#define STRICT_DEAL_STAMP_LAPS_DECL unsigned long long stamp_lap = 0ull, stamp_tiles = 0ull, stamp_items = 0ull;
+#define STRICT_DEAL_STAMP_LAP_BEGIN stamp_lap = wall_clock64();
+#define STRICT_DEAL_STAMP_LAP(total)                                                                                                   \
+  {                                                                                                                                    \
+    const unsigned long long stamp_now = wall_clock64();                                                                               \
+    total += stamp_now - stamp_lap;                                                                                                    \
+    stamp_lap = stamp_now;                                                                                                             \
+  }
+#define STRICT_DEAL_STAMP_LAPS_STORE                                                                                                   \
+  if (stamp_rec) {                                                                                                                     \
+    stamp_rec[7] = stamp_tiles;                                                                                                        \
+    stamp_rec[8] = stamp_items;                                                                                                        \
+  }
 #else
 #define STRICT_DEAL_STAMP_BEGIN
 #define STRICT_DEAL_STAMP_WORK(pair, slice, kind, n_active)
 #define STRICT_DEAL_STAMP_CLOSED
+#define STRICT_DEAL_STAMP_MARK(word)
+#define STRICT_DEAL_STAMP_LAPS_DECL
+#define STRICT_DEAL_STAMP_LAP_BEGIN
+#define STRICT_DEAL_STAMP_LAP(total)
+#define STRICT_DEAL_STAMP_LAPS_STORE
 #endif
 
 template <int SEARCH, bool WITH_HD, bool RING>
@@ -1084,6 +1123,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   constexpr bool kLdsHeader = DGS_STRICT_LDS_HEADER != 0 && !FIXED;
   __shared__ __attribute__((aligned(16))) StrictHeaderBlock s_hdr;
   {
+    // (Measured and removed, see history: this load requested in front of the dealing it does not depend on -- 4.22-4.25 against 4.24-4.25 ms.)
     unsigned long long e2 = 0ull;
     if (threadIdx.x < 32) e2 = kGlibcExp2fTab[threadIdx.x];
     strict_header_word_t hw = 0u;
@@ -1093,6 +1133,8 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   }
   const StrictHeader<kLdsHeader> hdr_wg{(strict_header_lds_t)&s_hdr, &st};
   __syncthreads();
+  STRICT_DEAL_STAMP_MARK(6)
+  STRICT_DEAL_STAMP_LAPS_DECL
   const unsigned long long* __restrict__ exptab = s_exp2f;   // this kernel serves consts.exp_libm = 1 only (strict_kernel_version, ndt_align.hip)
   const unsigned long long* __restrict__ exptab_d = kGlibcExpTab;
   // the wave's number as a scalar: its LDS regions' bases, its first point and the tile loop's counter then live in SGPRs, and a per-lane address
@@ -1137,6 +1179,10 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   const int subs = __builtin_amdgcn_readfirstlane(pts / 64);
   const int stride = __builtin_amdgcn_readfirstlane(n_slices * kBlock);
   static_assert(TL::kTableBytes >= kStrictRowScratch * 8, "the wave's table region doubles as its reduction scratch");
+  static_assert(DGS_STRICT_WIDE_ROWS == 0 || TL::kTableBytes < kStrictRowColsWide * 65 * 8 || strict_row_cols(TL::kTableBytes) == kStrictRowColsWide,
+                "a table region of 22 x 65 doubles or more is reduced in passes of 22 columns");
+  static_assert(DGS_STRICT_WIDE_ROWS == 0 || SEARCH != 2 || !WITH_HD || FIXED || strict_row_cols(TL::kTableBytes) == kStrictRowColsWide, "the timed instantiation: two passes");
+
   // this workgroup's slices q = slice, slice + blocks_per_pair, ...: each its own sums and its own row
   __shared__ double s_cols[FIXED ? kStrictSlots : 1][FIXED ? kBlock / kWave : 1][FIXED ? kStrictPad : 1];
   static_assert(kStrictSlots * kStrictPad <= kBlock, "one thread per entry of the rows written together");
@@ -1149,6 +1195,10 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
 #pragma unroll 1
   for (int first = q * kBlock + wave * 64; first < n; first += subs * stride) {
     int qn = 0;
+    STRICT_DEAL_STAMP_LAP_BEGIN
+    // (Measured and removed, see history: for a 128-point tile both sub-tiles' source loads, then both neighbourhoods' cell2vox look-ups, in flight
+    // together -- two dependent round trips in front of a tile's items instead of four; 256 VGPRs and no spill still.  4.22-4.25 against 4.24-4.25 ms
+    // on the step, four alternations on one box: inside the spread -- the partner wave on the SIMD hides these trips already.)
 #pragma unroll 1
     for (int sub = 0; sub < subs; sub++) {
       const int i = first + sub * stride + lane;
@@ -1199,6 +1249,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes have landed
     __builtin_amdgcn_wave_barrier();
+    STRICT_DEAL_STAMP_LAP(stamp_tiles)
     // ---- the items, 64 at a time.  The float kinds run strict_items_float, a loop specialised per kind (DGS_STRICT_ITEMS); the
     // loop below serves the double pass.  (Measured and removed, see history: that loop for all three kinds with the kind tested per round -- 7
     // spilled registers instead of 25 and 1 % SLOWER on the bench step, 5.35 against 5.27-5.30 ms, same box, two runs each.)
@@ -1235,9 +1286,11 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
       }
     }
     __builtin_amdgcn_wave_barrier();   // the next tile overwrites the tables and the queue (LDS operations of one wave stay in order)
+    STRICT_DEAL_STAMP_LAP(stamp_items)
   }
+  STRICT_DEAL_STAMP_MARK(9)
   if (FIXED) {
-    strict_wave_cols(acc, kind ? kStrictAccum : 7, td, s_cols[slot][wave]);
+    strict_wave_cols<TL::kTableBytes>(acc, kind ? kStrictAccum : 7, td, s_cols[slot][wave]);
     slot++;
     if (slot == kStrictSlots || q + blocks_per_pair >= n_slices) {   // workgroup-uniform
       strict_rows_flush<FUSED>(reinterpret_cast<const double (*)[kBlock / kWave][kStrictPad]>(&s_cols[0][0][0]), slot, kind ? kStrictAccum : 7,
@@ -1246,10 +1299,12 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
       q_first = q + blocks_per_pair;
     }
   } else {
-    strict_block_row<FUSED, false>(acc, kind ? kStrictAccum : 7, partials + ((size_t)pair * cap_blocks + slice) * kStrictPad, td);
+    strict_block_row<FUSED, false, TL::kTableBytes>(acc, kind ? kStrictAccum : 7, partials + ((size_t)pair * cap_blocks + slice) * kStrictPad, td);
   }
   }
   if (!FUSED) return;
+  STRICT_DEAL_STAMP_MARK(10)
+  STRICT_DEAL_STAMP_LAPS_STORE
   __shared__ int s_last;
   if (threadIdx.x < kStrictPad) handoff_drain_stores();   // (solver: the exact state's write-through stores)
   __syncthreads();
@@ -1258,6 +1313,7 @@ __global__ __launch_bounds__(kBlock, 2) void ndt_strict3_kernel(const float4* co
   const int n_tickets = blocks_per_pair + ((speculate && st.spec_pending) ? 1 : 0);
   if (threadIdx.x == 0) s_last = handoff_take_ticket(&pairs[pair].ticket, n_tickets) ? 1 : 0;
   __syncthreads();
+  STRICT_DEAL_STAMP_MARK(11)
   if (!s_last) return;
 #ifdef DGS_CLOSE_STAMPS
   if (threadIdx.x == 0 && pairs[pair].s.nr_iterations == 1) pairs[pair].traj[kTrajCap - 1][5] = (double)wall_clock64();

@@ -525,6 +525,11 @@ int dgs_deal_probe(dgs_handle* h, const int32_t* active, int32_t n_pairs, int32_
  * active pairs are ranked by (cost class, heaviest first; pair index) and workgroup b serves slice b % per of the pair of rank b / per.
  * order3 (may be NULL) receives the kinds from the heaviest class to the lightest, as the library was built. */
 int dgs_deal_probe_cost(dgs_handle* h, const int32_t* active, const int32_t* kinds, int32_t n_pairs, int32_t cap_blocks, int32_t grid, int32_t* out, int32_t* order3);
+/* The block reduction behind an evaluation of the upstream evaluation order: one workgroup of 256 threads reduces totals[256][43] (host doubles,
+ * a thread's 43 sums per row) to one row of `ncol` column sums (1..43), twice: rows2[0..47] through the passes of the item-compacted kernel
+ * (as wide as a wave's table region allows), rows2[48..95] through the stand-alone form's passes of 11 columns.  Entries at and behind ncol
+ * are 0.  A column is the sum of its 64 entries per wave in thread order, the four waves' sums added in wave order, in both. */
+int dgs_strict_row_probe(dgs_handle* h, const double* totals, int32_t ncol, double* rows2);
 /* DGS_METHOD_PCL_NDT handles are served by dgs_ndt_derivatives (its evaluation with the Hessian; hess36 == NULL asks for the score +
  * gradient evaluation of a More-Thuente trial), dgs_ndt_hessian_double, dgs_ndt_get_trajectory and dgs_ndt_get_voxels as well.
  * Test hook of such a handle: the neighbourhood of `m` query points (x y z pad, taken as they are: no transform) in the current

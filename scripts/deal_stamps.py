@@ -6,6 +6,9 @@ prints one JSON object:
   per_kind        median / mean workgroup duration (us, start -> end of the derivative work) per evaluation kind, in launches with >= --many
                   active pairs, and the medians relative to their workgroup-weighted mean
   dispatch_order  the share of neighbouring blockIdx whose start times are in order, and the rank correlation of start time with blockIdx
+  split_per_kind  wave 0's life per evaluation kind, medians in us over the same workgroups: start -> end of the prologue barrier (dealing,
+                  header), its tile prologues and its item loops in all, the row reduction, the drain of the row's stores + barrier, the
+                  ticket + barrier; `outside_item_loops_share` = 1 - items / (start -> ticket taken); and the closing of the workgroups that closed
   idle_share      per launch 1 - sum(workgroup durations) / (slots x launch duration), mean over the launches with >= --many active pairs and
                   over the rest (slots: the workgroups the chip holds at once, 512 for this kernel on 256 CUs)
   launch_us       mean launch duration (first start -> last end, closings included) of the two groups
@@ -16,7 +19,7 @@ import json
 
 import numpy as np
 
-LAUNCHES, GRID, WORDS = 256, 2048, 8   # kStampLaunches, kStampGrid, kStampWords (ndt_strict.h)
+LAUNCHES, GRID, WORDS = 256, 2048, 16   # kStampLaunches, kStampGrid, kStampWords (ndt_strict.h)
 TICK_US = 0.01                         # wall_clock64: 100 MHz
 
 
@@ -28,6 +31,7 @@ def main():
     a = ap.parse_args()
     raw = np.fromfile(a.file, dtype=np.uint64).reshape(LAUNCHES, GRID, WORDS)
     per_kind = {0: [], 1: [], 2: []}
+    split = {k: {p: [] for p in ("prologue", "tile_prologues", "item_loops", "row_reduction", "drain", "ticket", "whole", "closing")} for k in (0, 1, 2)}
     groups = {"many": dict(idle=[], us=[], n=0), "few": dict(idle=[], us=[], n=0)}
     in_order, neighbours, rho = 0, 0, []
     for l in range(LAUNCHES):
@@ -52,6 +56,12 @@ def main():
         if n_active >= a.many:
             for k in (0, 1, 2):
                 per_kind[k].append(((t1 - t0) * TICK_US)[work & (kind == k)])
+                w = rec[work & (kind == k)][:, :12].astype(np.int64)
+                for name, ticks in (("prologue", w[:, 6] - w[:, 0]), ("tile_prologues", w[:, 7]), ("item_loops", w[:, 8]), ("row_reduction", w[:, 10] - w[:, 9]),
+                                    ("drain", w[:, 1] - w[:, 10]), ("ticket", w[:, 11] - w[:, 1]), ("whole", w[:, 11] - w[:, 0])):
+                    split[k][name].append(ticks * TICK_US)
+                closed = w[w[:, 2] != 0]
+                split[k]["closing"].append((closed[:, 2] - closed[:, 11]) * TICK_US)
         o = np.argsort(block[work])
         s = t0[work][o]
         in_order += int((np.diff(s) >= 0).sum())
@@ -74,6 +84,14 @@ def main():
         out["per_kind_relative_to_mean"] = {str(k): med[k] / mean for k in med}
         out["mix"] = {str(k): cnt[k] / tot for k in cnt}
         out["heaviest_first"] = sorted(med, key=lambda k: -med[k])
+    out["split_per_kind"] = {}
+    for k in (0, 1, 2):
+        parts = {name: np.concatenate(v) if v else np.zeros(0) for name, v in split[k].items()}
+        if not parts["whole"].size:
+            continue
+        row = {name + "_median_us": float(np.median(v)) for name, v in parts.items() if v.size}
+        row["outside_item_loops_share"] = float(1.0 - parts["item_loops"].sum() / parts["whole"].sum())
+        out["split_per_kind"][str(k)] = row
     out["dispatch_order"] = {"neighbouring_blockIdx_started_in_order": in_order / max(1, neighbours), "mean_rank_correlation": float(np.mean(rho)) if rho else None}
     out["idle_share"] = {k: (float(np.mean(v["idle"])) if v["idle"] else None) for k, v in groups.items()}
     out["launch_us"] = {k: (float(np.mean(v["us"])) if v["us"] else None) for k, v in groups.items()}
