@@ -584,8 +584,7 @@ void dgs_destroy(dgs_handle* h) {
   cov_batch_release(h);
   h->gitems.release(); h->gtargets.release(); h->vvox.release(); h->vcell2vox.release();
   h->cell2vox.release(); h->vox.release(); h->vox_centroid.release(); h->vox_dbg.release(); h->vox_strict.release(); h->vox_count.release(); h->vox_valid.release();
-  h->key_in.release(); h->key_out.release(); h->val_in.release(); h->val_out.release(); h->run_keys.release();
-  h->run_counts.release(); h->run_offsets.release(); h->dev_scalars.release(); h->vg_run_keys.release(); h->vg_scalars.release(); h->minmax_partial.release(); h->cub_temp.release();
+  h->runs.release(); h->vg_table.release(); h->minmax_partial.release(); h->cub_temp.release();
   h->pairs.release(); h->inits.release(); h->partials.release(); h->done_counter.release(); h->ndt_queue.release(); h->ndt_ring.release(); h->pair_blocks.release(); h->src_ptrs.release(); h->src_sizes.release();
   h->nn_partials.release(); h->scratch_cloud.release(); h->strict_rows.release(); h->strict_totals.release(); h->tgt_grid.release(); h->aux_grid.release();
   h->fc_in.release(); h->fc_out.release(); h->fc_cnt.release();
@@ -1117,7 +1116,7 @@ int dgs_get_counts(dgs_handle* h, int64_t out[8]) {
   if (is_ndt_family(h) && h->have_target && h->grid_cells > 0) {
     if (h->counts_stale) {
       int sc[2] = {0, 0};
-      DGS_HIP_TRY(h, hipMemcpyAsync(sc, h->dev_scalars.ptr, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+      DGS_HIP_TRY(h, hipMemcpyAsync(sc, h->runs.table.scalars.ptr, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
       DGS_HIP_TRY(h, hipStreamSynchronize(h->stream));
       h->n_occupied = sc[0];
       h->n_valid = sc[1];
@@ -1533,7 +1532,7 @@ int dgs_ndt_get_voxels(dgs_handle* h, int64_t* n, int64_t* keys, int32_t* counts
   if (!keys || nv == 0) return DGS_OK;
   std::vector<uint32_t> k32(nv);
   std::vector<double> dbg((size_t)nv * 12);
-  DGS_HIP_TRY(h, hipMemcpy(k32.data(), h->run_keys.ptr, nv * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  DGS_HIP_TRY(h, hipMemcpy(k32.data(), h->runs.table.keys.ptr, nv * sizeof(uint32_t), hipMemcpyDeviceToHost));
   DGS_HIP_TRY(h, hipMemcpy(counts, h->vox_count.ptr, nv * sizeof(int), hipMemcpyDeviceToHost));
   DGS_HIP_TRY(h, hipMemcpy(valid, h->vox_valid.ptr, nv * sizeof(int), hipMemcpyDeviceToHost));
   DGS_HIP_TRY(h, hipMemcpy(dbg.data(), h->vox_dbg.ptr, (size_t)nv * 12 * sizeof(double), hipMemcpyDeviceToHost));

@@ -285,6 +285,33 @@ struct FbScratch {
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launches, host waits, edges, indices built, partial rows
 };
 
+// The buffers of the chain "key per point -> stable radix sort of (key, point index) -> run-length encode -> exclusive scan of the run
+// lengths" that every structure keyed by voxel cell is built with (voxel_cells.h runs it).  What a build leaves behind for later calls
+// -- the key of every run and the scalar block, scalars[0] = number of runs -- is a RunTable of its own: a chain writes the table its
+// caller names, so a call that borrows the rest (dgs_voxel_grid_filter) leaves the NDT model's table alone.
+template <class Key>
+struct RunTable {
+  DevBuf<Key> keys;
+  DevBuf<int> scalars;
+  void release() { keys.release(); scalars.release(); }
+};
+template <class Key>
+struct KeyRuns {
+  DevBuf<Key> keys, sorted_keys;
+  DevBuf<uint32_t> vals, sorted_vals;    // index of the point in its cloud; sorted: a run's points in point-index order
+  DevBuf<int> run_counts, run_offsets;   // only the first scalars[0] entries, which the run-length encoding writes, are counts
+  RunTable<Key> table;
+  // n keys, and as many runs at most, into `t` (the caller's own `table`, or another)
+  hipError_t reserve(const size_t n, RunTable<Key>& t) {
+    hipError_t e = t.scalars.reserve(8);
+    for (DevBuf<Key>* b : {&keys, &sorted_keys, &t.keys}) e = e != hipSuccess ? e : b->reserve(n);
+    for (DevBuf<uint32_t>* b : {&vals, &sorted_vals}) e = e != hipSuccess ? e : b->reserve(n);
+    for (DevBuf<int>* b : {&run_counts, &run_offsets}) e = e != hipSuccess ? e : b->reserve(n);
+    return e;
+  }
+  void release() { keys.release(); sorted_keys.release(); vals.release(); sorted_vals.release(); run_counts.release(); run_offsets.release(); table.release(); }
+};
+
 // dgs_cloud_assign_batch (voxel_batch.hip): the staged inputs, one record per cloud, the keys, values and runs of all clouds back to
 // back; everything above is left untouched.
 struct VbSeg;     // voxel_batch.hip
@@ -292,9 +319,8 @@ struct VbScratch {
   DevBuf<float4> in;                   // host inputs, all clouds back to back
   DevBuf<VbSeg> segs;
   DevBuf<float> mm;                    // per cloud 64 partial boxes, then the boxes
-  DevBuf<unsigned long long> keys, keys_alt, run_keys;   // (cloud number << 32) | cell index
-  DevBuf<uint32_t> vals, vals_alt;     // index of the point in its own cloud
-  DevBuf<int> run_counts, run_offsets, scalars, bounds;  // scalars[0] = runs; bounds: first run and end of the emitted runs per cloud
+  KeyRuns<unsigned long long> runs;    // keys: (cloud number << 32) | cell index
+  DevBuf<int> bounds;                  // first run and end of the emitted runs per cloud
   int64_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // of the last call: launches, host waits, clouds
 };
 
@@ -436,11 +462,8 @@ struct dgs_handle {
   dgs::DevBuf<dgs::VoxelStrictRec> vox_strict;   // per occupied voxel: mean, float(icov) 3 x 3 (upstream evaluation orders)
   dgs::DevBuf<int> vox_count;        // points per occupied voxel
   dgs::DevBuf<int> vox_valid;
-  dgs::DevBuf<uint32_t> key_in, key_out, val_in, val_out, run_keys;
-  dgs::DevBuf<int> run_counts, run_offsets;
-  dgs::DevBuf<int> dev_scalars;      // [0]=num_runs, [1]=n_valid
-  dgs::DevBuf<uint32_t> vg_run_keys; // dgs_voxel_grid_filter's own runs / scalars: the NDT model's (above) stay what setInputTarget made them
-  dgs::DevBuf<int> vg_scalars;
+  dgs::KeyRuns<uint32_t> runs;       // runs.table: the model's run keys and scalars, [0]=num_runs, [1]=n_valid
+  dgs::RunTable<uint32_t> vg_table;  // dgs_voxel_grid_filter's own runs / scalars: the NDT model's (above) stay what setInputTarget made them
   dgs::DevBuf<float> minmax_partial; // block partials + final 6 floats
   dgs::DevBuf<unsigned char> cub_temp;
   int64_t grid_cells = 0;

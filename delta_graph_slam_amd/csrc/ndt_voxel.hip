@@ -8,14 +8,13 @@
 // voxel key, then one lane walks each voxel's run), so the table is bit-reproducible and follows the
 // upstream accumulation order -- no float/double atomics.  The table is tiny (V ~ 10^4 x 48 B) and lives in
 // L2; the dense cell->voxel index costs 4 B per grid cell of HBM (288 GB makes that free).
-#include <hipcub/hipcub.hpp>
-
 #include <cfloat>
 #include <cmath>
 
-#include "handle.h"
 #include "seg_device.h"
 #include "small_linalg.h"
+#include "voxel_cells.h"
+#include "voxel_grid_plan.h"
 
 namespace dgs {
 
@@ -63,7 +62,7 @@ int cloud_minmax(dgs_handle* h, const float4* pts, int64_t n, float out6[6]) {
   return DGS_OK;
 }
 
-// ---- voxel key per point (VoxelGridCovariance first pass, index arithmetic in float as upstream) ---------
+// ---- voxel key per point (voxel_cells.h voxel_cell_key) ----------------------------------------------------
 // clear_cells / clear_scalars (may be null): the dense cell table is reset to -1 and the scalar block to 0 by this same launch (grid
 // stride), instead of two fill commands in front of it
 __global__ __launch_bounds__(kBlock) void voxel_key_kernel(const float4* __restrict__ pts, int64_t n, VoxelGrid g,
@@ -74,15 +73,7 @@ __global__ __launch_bounds__(kBlock) void voxel_key_kernel(const float4* __restr
     for (int64_t c = i; c < n_cells; c += (int64_t)gridDim.x * blockDim.x) clear_cells[c] = -1;
   if (clear_scalars && i < 8) clear_scalars[i] = 0;
   if (i >= n) return;
-  const float4 p = pts[i];
-  uint32_t key = 0xFFFFFFFFu;
-  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-    const int i0 = (int)(floorf(p.x * g.inv_leaf) - (float)g.min_b[0]);
-    const int i1 = (int)(floorf(p.y * g.inv_leaf) - (float)g.min_b[1]);
-    const int i2 = (int)(floorf(p.z * g.inv_leaf) - (float)g.min_b[2]);
-    key = (uint32_t)(i0 + i1 * g.mul1 + i2 * g.mul2);
-  }
-  keys[i] = key;
+  keys[i] = voxel_cell_key(pts[i], g.inv_leaf, g.min_b, g.mul1, g.mul2);
   vals[i] = (uint32_t)i;
 }
 
@@ -196,21 +187,15 @@ __global__ __launch_bounds__(kBlock) void voxel_centroid_kernel(const float4* __
                                                                 const int* __restrict__ scalars, float4* __restrict__ out, int out_capacity) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= scalars[0] || r >= out_capacity) return;
-  if (run_keys[r] == 0xFFFFFFFFu) return;  // the run of non-finite points sorts last: it is simply not emitted
-  const int off = run_offsets[r], cnt = run_counts[r];
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  for (int j = 0; j < cnt; j++) {
-    const float4 p = sorted_pts[off + j];
-    sx += p.x; sy += p.y; sz += p.z;
-  }
-  const float fn = (float)cnt;
-  out[r] = make_float4(sx / fn, sy / fn, sz / fn, 1.f);
+  if (run_keys[r] == kNonFiniteCell) return;  // the run of non-finite points sorts last: it is simply not emitted
+  const int off = run_offsets[r];
+  out[r] = run_centroid(run_counts[r], [&](const int j) { return sorted_pts[off + j]; });
 }
 
 __global__ void voxel_count_kernel(const uint32_t* __restrict__ run_keys, int* __restrict__ scalars) {
   // number of emitted cells = runs, minus the trailing run of non-finite points if there is one
   const int nr = scalars[0];
-  scalars[2] = (nr > 0 && run_keys[nr - 1] == 0xFFFFFFFFu) ? nr - 1 : nr;
+  scalars[2] = (nr > 0 && run_keys[nr - 1] == kNonFiniteCell) ? nr - 1 : nr;
 }
 
 // out receives the centroids ordered by cell index (as pcl::VoxelGrid emits them); *n_out the number of cells.
@@ -221,51 +206,29 @@ int voxel_grid_filter(dgs_handle* h, const float4* in, int64_t n, float leaf, fl
   float hmm[6];
   int rc = cloud_minmax(h, in, n, hmm);
   if (rc) return rc;
-  if (!(hmm[0] <= hmm[3])) return DGS_OK;
   VoxelGrid g{};
   g.leaf = leaf;
   g.inv_leaf = 1.0f / leaf;
-  int64_t cells = 1;
-  for (int a = 0; a < 3; a++) {
-    g.min_b[a] = (int)std::floor(hmm[a] * g.inv_leaf);
-    g.max_b[a] = (int)std::floor(hmm[3 + a] * g.inv_leaf);
-    g.div_b[a] = g.max_b[a] - g.min_b[a] + 1;
-    cells *= (int64_t)((hmm[3 + a] - hmm[a]) * g.inv_leaf) + 1;
-  }
-  if (cells > INT32_MAX || (int64_t)g.div_b[0] * g.div_b[1] * g.div_b[2] > INT32_MAX) {
-    h->err = "Leaf size is too small for the input dataset. Integer indices would overflow.";
+  const vgplan::State state = vgplan::plan(hmm, g.inv_leaf, g.min_b, g.div_b, g.mul1, g.mul2);   // max_b: no kernel of this call reads it
+  if (state == vgplan::kEmpty) return DGS_OK;
+  if (state == vgplan::kTooLarge) {
+    h->err = vgplan::kTooLargeText;
     return DGS_ERR_GRID_TOO_LARGE;
   }
-  g.mul1 = g.div_b[0];
-  g.mul2 = g.div_b[0] * g.div_b[1];
-  DGS_HIP_TRY(h, h->key_in.reserve(n));
-  DGS_HIP_TRY(h, h->key_out.reserve(n));
-  DGS_HIP_TRY(h, h->val_in.reserve(n));
-  DGS_HIP_TRY(h, h->val_out.reserve(n));
-  DGS_HIP_TRY(h, h->vg_run_keys.reserve(n));
-  DGS_HIP_TRY(h, h->run_counts.reserve(n));
-  DGS_HIP_TRY(h, h->run_offsets.reserve(n));
-  DGS_HIP_TRY(h, h->vg_scalars.reserve(8));
+  KeyRuns<uint32_t>& R = h->runs;
+  RunTable<uint32_t>& T = h->vg_table;   // not R.table: the NDT model's run keys and scalars stay what setInputTarget made them
+  DGS_HIP_TRY(h, R.reserve(n, T));
   DGS_HIP_TRY(h, h->scratch_cloud.reserve(n));
-  size_t t1 = 0, t2 = 0, t3 = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, (int)n, 0, 32, st);
-  (void)hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, h->key_out.ptr, h->vg_run_keys.ptr, h->run_counts.ptr, h->vg_scalars.ptr, (int)n, st);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t3, h->run_counts.ptr, h->run_offsets.ptr, (int)n, st);
-  DGS_HIP_TRY(h, h->cub_temp.reserve(std::max(t1, std::max(t2, t3)) + 256));
+  DGS_HIP_TRY(h, key_runs_reserve_temp(h, R, T, (int)n, 32, st));
   const int nb = (int)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(kBlock), 0, st, in, n, g, h->key_in.ptr, h->val_in.ptr, (int*)nullptr, (int64_t)0, h->vg_scalars.ptr);
-  size_t tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, (int)n, 0, 32, st));
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRunLengthEncode::Encode(h->cub_temp.ptr, tb, h->key_out.ptr, h->vg_run_keys.ptr, h->run_counts.ptr, h->vg_scalars.ptr, (int)n, st));
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(h->cub_temp.ptr, tb, h->run_counts.ptr, h->run_offsets.ptr, (int)n, st));
-  hipLaunchKernelGGL(gather_kernel, dim3(nb), dim3(kBlock), 0, st, in, h->val_out.ptr, n, h->scratch_cloud.ptr);
-  hipLaunchKernelGGL(voxel_centroid_kernel, dim3(nb), dim3(kBlock), 0, st, h->scratch_cloud.ptr, h->vg_run_keys.ptr, h->run_counts.ptr, h->run_offsets.ptr,
-                     h->vg_scalars.ptr, out, (int)std::min<int64_t>(out_capacity, INT32_MAX));
-  hipLaunchKernelGGL(voxel_count_kernel, dim3(1), dim3(1), 0, st, h->vg_run_keys.ptr, h->vg_scalars.ptr);
-  int* hs = reinterpret_cast<int*>(h->pinned);
-  DGS_HIP_TRY(h, hipMemcpyAsync(hs, h->vg_scalars.ptr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(kBlock), 0, st, in, n, g, R.keys.ptr, R.vals.ptr, (int*)nullptr, (int64_t)0, T.scalars.ptr);
+  DGS_HIP_TRY(h, key_runs_chain(h, R, T, (int)n, 32, st));
+  hipLaunchKernelGGL(gather_kernel, dim3(nb), dim3(kBlock), 0, st, in, R.sorted_vals.ptr, n, h->scratch_cloud.ptr);
+  hipLaunchKernelGGL(voxel_centroid_kernel, dim3(nb), dim3(kBlock), 0, st, h->scratch_cloud.ptr, T.keys.ptr, R.run_counts.ptr, R.run_offsets.ptr,
+                     T.scalars.ptr, out, (int)std::min<int64_t>(out_capacity, INT32_MAX));
+  hipLaunchKernelGGL(voxel_count_kernel, dim3(1), dim3(1), 0, st, T.keys.ptr, T.scalars.ptr);
+  int* hs = reinterpret_cast<int*>(h->pinned);   // cloud_minmax above has sized the pinned block (4 KiB at least)
+  DGS_HIP_TRY(h, hipMemcpyAsync(hs, T.scalars.ptr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
   DGS_HIP_TRY(h, hipStreamSynchronize(st));
   DGS_HIP_TRY(h, hipGetLastError());
   *n_out = hs[2];
@@ -353,13 +316,7 @@ __global__ __launch_bounds__(kBlock) void approx_centroid_kernel(const float4* _
   if (o >= n_runs || o >= out_capacity) return;
   const int r = (int)runs_in_output_order[o];
   const int s0 = (int)run_start[r], s1 = (r + 1 < n_runs) ? (int)run_start[r + 1] : n;
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  for (int s = s0; s < s1; s++) {
-    const float4 p = pts[order[s]];
-    sx += p.x; sy += p.y; sz += p.z;
-  }
-  const float fn = (float)(s1 - s0);
-  out[o] = make_float4(sx / fn, sy / fn, sz / fn, 1.f);
+  out[o] = run_centroid(s1 - s0, [&](const int j) { return pts[order[s0 + j]]; });
 }
 
 // out receives the centroids in upstream's output order; *n_out their number.  The input must be finite (upstream does not look).
@@ -369,40 +326,32 @@ int approx_voxel_grid_filter(dgs_handle* h, const float4* in, int64_t n64, float
   if (n64 == 0) return DGS_OK;
   const int n = (int)n64;
   const float inv_leaf = 1.0f / leaf;
-  DGS_HIP_TRY(h, h->key_in.reserve(n));
-  DGS_HIP_TRY(h, h->key_out.reserve(n));
-  DGS_HIP_TRY(h, h->val_in.reserve(n));
-  DGS_HIP_TRY(h, h->val_out.reserve(n));
-  DGS_HIP_TRY(h, h->vg_run_keys.reserve(n));
-  DGS_HIP_TRY(h, h->run_counts.reserve(n));
-  DGS_HIP_TRY(h, h->run_offsets.reserve(n));
-  DGS_HIP_TRY(h, h->vg_scalars.reserve(8));
+  // the chain's buffers: head flags in run_counts, run numbers (their inclusive scan, this routine's own) in run_offsets, run starts in T.keys
+  KeyRuns<uint32_t>& R = h->runs;
+  RunTable<uint32_t>& T = h->vg_table;
+  DGS_HIP_TRY(h, R.reserve(n, T));
   DGS_HIP_TRY(h, h->scratch_cloud.reserve(n));   // 4 n words: the second sort's outputs live here
   uint32_t* trig_sorted = reinterpret_cast<uint32_t*>(h->scratch_cloud.ptr);
   uint32_t* runs_sorted = trig_sorted + n;
-  size_t t1 = 0, t2 = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, n, 0, 32, st);
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, t2, h->run_counts.ptr, h->run_offsets.ptr, n, st);
-  DGS_HIP_TRY(h, h->cub_temp.reserve(std::max(t1, t2) + 256));
-  DGS_HIP_TRY(h, hipMemsetAsync(h->vg_scalars.ptr, 0, 8 * sizeof(int), st));
+  size_t t2 = 0;
+  (void)hipcub::DeviceScan::InclusiveSum(nullptr, t2, R.run_counts.ptr, R.run_offsets.ptr, n, st);
+  DGS_HIP_TRY(h, h->cub_temp.reserve(std::max(key_runs_sort_temp(R, n, 32, st), t2) + 256));
+  DGS_HIP_TRY(h, hipMemsetAsync(T.scalars.ptr, 0, 8 * sizeof(int), st));
   const int nb = (n + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL(approx_key_kernel, dim3(nb), dim3(kBlock), 0, st, in, n, inv_leaf, h->key_in.ptr, h->val_in.ptr);
+  hipLaunchKernelGGL(approx_key_kernel, dim3(nb), dim3(kBlock), 0, st, in, n, inv_leaf, R.keys.ptr, R.vals.ptr);
+  DGS_HIP_TRY(h, key_runs_sort(h, R, n, 9, st));
+  hipLaunchKernelGGL(approx_head_kernel, dim3(nb), dim3(kBlock), 0, st, in, R.sorted_keys.ptr, R.sorted_vals.ptr, n, inv_leaf, R.run_counts.ptr);
   size_t tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, n, 0, 9, st));
-  hipLaunchKernelGGL(approx_head_kernel, dim3(nb), dim3(kBlock), 0, st, in, h->key_out.ptr, h->val_out.ptr, n, inv_leaf, h->run_counts.ptr);
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceScan::InclusiveSum(h->cub_temp.ptr, tb, h->run_counts.ptr, h->run_offsets.ptr, n, st));
-  hipLaunchKernelGGL(approx_runs_kernel, dim3(nb), dim3(kBlock), 0, st, h->run_counts.ptr, h->run_offsets.ptr, n, h->vg_run_keys.ptr, h->vg_scalars.ptr);
-  hipLaunchKernelGGL(approx_trigger_kernel, dim3(nb), dim3(kBlock), 0, st, h->key_out.ptr, h->val_out.ptr, h->vg_run_keys.ptr, h->vg_scalars.ptr, n, h->key_in.ptr,
-                     h->val_in.ptr);
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, h->key_in.ptr, trig_sorted, h->val_in.ptr, runs_sorted, n, 0, 32, st));
-  hipLaunchKernelGGL(approx_centroid_kernel, dim3(nb), dim3(kBlock), 0, st, in, h->val_out.ptr, h->vg_run_keys.ptr, runs_sorted, h->vg_scalars.ptr, n, out,
+  DGS_HIP_TRY(h, hipcub::DeviceScan::InclusiveSum(h->cub_temp.ptr, tb, R.run_counts.ptr, R.run_offsets.ptr, n, st));
+  hipLaunchKernelGGL(approx_runs_kernel, dim3(nb), dim3(kBlock), 0, st, R.run_counts.ptr, R.run_offsets.ptr, n, T.keys.ptr, T.scalars.ptr);
+  hipLaunchKernelGGL(approx_trigger_kernel, dim3(nb), dim3(kBlock), 0, st, R.sorted_keys.ptr, R.sorted_vals.ptr, T.keys.ptr, T.scalars.ptr, n, R.keys.ptr, R.vals.ptr);
+  tb = h->cub_temp.cap;   // (trigger, run) pairs, out of R.keys / R.vals into the scratch cloud
+  DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, R.keys.ptr, trig_sorted, R.vals.ptr, runs_sorted, n, 0, 32, st));
+  hipLaunchKernelGGL(approx_centroid_kernel, dim3(nb), dim3(kBlock), 0, st, in, R.sorted_vals.ptr, T.keys.ptr, runs_sorted, T.scalars.ptr, n, out,
                      (int)std::min<int64_t>(out_capacity, INT32_MAX));
-  int* hs = reinterpret_cast<int*>(h->pinned);
   if (ensure_pinned(h, 64) != DGS_OK) return DGS_ERR_HIP;
-  hs = reinterpret_cast<int*>(h->pinned);
-  DGS_HIP_TRY(h, hipMemcpyAsync(hs, h->vg_scalars.ptr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  int* hs = reinterpret_cast<int*>(h->pinned);
+  DGS_HIP_TRY(h, hipMemcpyAsync(hs, T.scalars.ptr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
   DGS_HIP_TRY(h, hipStreamSynchronize(st));
   DGS_HIP_TRY(h, hipGetLastError());
   *n_out = hs[0];
@@ -428,42 +377,25 @@ int ndt_build_target(dgs_handle* h) {
     const int rc = cloud_minmax(h, h->tgt->pts.ptr, n, hmm);
     if (rc != DGS_OK) return rc;
   }
-  if (!(hmm[0] <= hmm[3])) {  // no finite point
-    prof_end(h, DGS_K_NDT_VOXEL_BUILD, slot);
-    return DGS_OK;
-  }
 
   // 2. grid extents (VoxelGridCovariance::applyFilter)
   VoxelGrid& g = h->grid;
-  int64_t cells = 1;
-  for (int a = 0; a < 3; a++) {
-    g.min_b[a] = (int)std::floor(hmm[a] * g.inv_leaf);
-    g.max_b[a] = (int)std::floor(hmm[3 + a] * g.inv_leaf);
-    g.div_b[a] = g.max_b[a] - g.min_b[a] + 1;
-    const int64_t dx = (int64_t)((hmm[3 + a] - hmm[a]) * g.inv_leaf) + 1;
-    cells *= dx;
-  }
-  const int64_t dense_cells = (int64_t)g.div_b[0] * g.div_b[1] * g.div_b[2];
-  if (cells > INT32_MAX || dense_cells > INT32_MAX) {
+  const vgplan::State state = vgplan::plan(hmm, g.inv_leaf, g.min_b, g.div_b, g.mul1, g.mul2);
+  if (state != vgplan::kOk) {  // no finite point, or PCL's overflow
     prof_end(h, DGS_K_NDT_VOXEL_BUILD, slot);
-    h->err = "Leaf size is too small for the input dataset. Integer indices would overflow.";
+    if (state == vgplan::kEmpty) return DGS_OK;
+    h->err = vgplan::kTooLargeText;
     return DGS_ERR_GRID_TOO_LARGE;
   }
-  g.mul1 = g.div_b[0];
-  g.mul2 = g.div_b[0] * g.div_b[1];
+  for (int a = 0; a < 3; a++) g.max_b[a] = g.min_b[a] + g.div_b[a] - 1;
+  const int64_t dense_cells = (int64_t)g.div_b[0] * g.div_b[1] * g.div_b[2];
   h->grid_cells = dense_cells;
   h->n_occupied_bound = n;
 
   // 3. buffers
+  KeyRuns<uint32_t>& R = h->runs;
   DGS_HIP_TRY(h, h->cell2vox.reserve((size_t)dense_cells));
-  DGS_HIP_TRY(h, h->key_in.reserve(n));
-  DGS_HIP_TRY(h, h->key_out.reserve(n));
-  DGS_HIP_TRY(h, h->val_in.reserve(n));
-  DGS_HIP_TRY(h, h->val_out.reserve(n));
-  DGS_HIP_TRY(h, h->run_keys.reserve(n));
-  DGS_HIP_TRY(h, h->run_counts.reserve(n));
-  DGS_HIP_TRY(h, h->run_offsets.reserve(n));
-  DGS_HIP_TRY(h, h->dev_scalars.reserve(8));
+  DGS_HIP_TRY(h, R.reserve(n, R.table));
   DGS_HIP_TRY(h, h->vox.reserve(n));
   DGS_HIP_TRY(h, h->vox_centroid.reserve(n));
   DGS_HIP_TRY(h, h->vox_dbg.reserve((size_t)n * 12));
@@ -471,33 +403,20 @@ int ndt_build_target(dgs_handle* h) {
   DGS_HIP_TRY(h, h->vox_count.reserve(n));
   DGS_HIP_TRY(h, h->vox_valid.reserve(n));
   DGS_HIP_TRY(h, h->scratch_cloud.reserve(n));
-  size_t t1 = 0, t2 = 0, t3 = 0;
-  int end_bit = 32;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, (int)n, 0, end_bit, st);
-  (void)hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, h->key_out.ptr, h->run_keys.ptr, h->run_counts.ptr, h->dev_scalars.ptr, (int)n, st);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t3, h->run_counts.ptr, h->run_offsets.ptr, (int)n, st);
-  const size_t tmax = std::max(t1, std::max(t2, t3));
-  DGS_HIP_TRY(h, h->cub_temp.reserve(tmax + 256));
+  DGS_HIP_TRY(h, key_runs_reserve_temp(h, R, R.table, (int)n, 32, st));
 
   // 4. keys -> stable sort -> runs -> offsets
   // (the cell table and the scalar block are cleared by the key kernel itself; run_counts needs no clearing: only its first
   // scalars[0] entries, which the run-length encoding writes, are ever read as counts)
   const int nb = (int)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, n, g, h->key_in.ptr, h->val_in.ptr, h->cell2vox.ptr, dense_cells,
-                     h->dev_scalars.ptr);
-  size_t tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, (int)n, 0,
-                                                    end_bit, st));
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRunLengthEncode::Encode(h->cub_temp.ptr, tb, h->key_out.ptr, h->run_keys.ptr, h->run_counts.ptr,
-                                                       h->dev_scalars.ptr, (int)n, st));
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(h->cub_temp.ptr, tb, h->run_counts.ptr, h->run_offsets.ptr, (int)n, st));
-  hipLaunchKernelGGL(gather_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, h->val_out.ptr, n, h->scratch_cloud.ptr);
+  hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, n, g, R.keys.ptr, R.vals.ptr, h->cell2vox.ptr, dense_cells,
+                     R.table.scalars.ptr);
+  DGS_HIP_TRY(h, key_runs_chain(h, R, R.table, (int)n, 32, st));
+  hipLaunchKernelGGL(gather_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, R.sorted_vals.ptr, n, h->scratch_cloud.ptr);
 
   // 5. per-voxel statistics
-  hipLaunchKernelGGL(voxel_finalize_kernel, dim3(nb), dim3(kBlock), 0, st, h->scratch_cloud.ptr, h->run_keys.ptr, h->run_counts.ptr,
-                     h->run_offsets.ptr, h->dev_scalars.ptr, h->prm.ndt_min_points_per_voxel, h->prm.ndt_min_covar_eigvalue_mult,
+  hipLaunchKernelGGL(voxel_finalize_kernel, dim3(nb), dim3(kBlock), 0, st, h->scratch_cloud.ptr, R.table.keys.ptr, R.run_counts.ptr,
+                     R.run_offsets.ptr, R.table.scalars.ptr, h->prm.ndt_min_points_per_voxel, h->prm.ndt_min_covar_eigvalue_mult,
                      h->cell2vox.ptr, h->vox.ptr, h->vox_centroid.ptr, h->vox_dbg.ptr, h->vox_count.ptr, h->vox_valid.ptr, h->vox_strict.ptr,
                      h->prm.ndt_cov_eigensolver);
   prof_end(h, DGS_K_NDT_VOXEL_BUILD, slot);

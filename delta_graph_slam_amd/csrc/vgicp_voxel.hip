@@ -3,18 +3,16 @@
 // Replaces what fast_gicp::FastVGICP::linearize does on its first call after setInputTarget (the object the reference builds at
 // /root/reference/src/hdl_graph_slam/registrations.cpp:48-56): every target point goes to the voxel floor(x / resolution - 0.5)
 // (double arithmetic), a voxel's mean is the mean of its points and its covariance the mean of its points' regularised
-// k-NN covariances.  Same machinery as the NDT voxel build (ndt_voxel.hip): key per point, stable radix sort (so a voxel's
-// points are summed in point-index order, as upstream appends them), run-length encode, one lane per voxel, dense
-// cell -> voxel table over the target's AABB.
-#include <hipcub/hipcub.hpp>
-
+// k-NN covariances.  Same machinery as the NDT voxel build (ndt_voxel.hip): key per point, the chain of voxel_cells.h (stable radix
+// sort, so a voxel's points are summed in point-index order, as upstream appends them; run-length encode; scan), one lane per voxel,
+// dense cell -> voxel table over the target's AABB.  The grid is this file's own: vgicp_coord, in double, not pcl::VoxelGrid's rule.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <numeric>
 #include <vector>
 
-#include "handle.h"
+#include "voxel_cells.h"
 
 namespace dgs {
 
@@ -111,41 +109,25 @@ int vgicp_build_map(dgs_handle* h) {
   m.mul1 = m.div[0];
   m.mul2 = m.div[0] * m.div[1];
   DGS_HIP_TRY(h, h->vcell2vox.reserve((size_t)cells));
-  DGS_HIP_TRY(h, h->key_in.reserve(n));
-  DGS_HIP_TRY(h, h->key_out.reserve(n));
-  DGS_HIP_TRY(h, h->val_in.reserve(n));
-  DGS_HIP_TRY(h, h->val_out.reserve(n));
-  DGS_HIP_TRY(h, h->run_keys.reserve(n));
-  DGS_HIP_TRY(h, h->run_counts.reserve(n));
-  DGS_HIP_TRY(h, h->run_offsets.reserve(n));
-  DGS_HIP_TRY(h, h->dev_scalars.reserve(8));
+  KeyRuns<uint32_t>& R = h->runs;
+  DGS_HIP_TRY(h, R.reserve(n, R.table));
   DGS_HIP_TRY(h, h->vvox.reserve(n));
-  size_t t1 = 0, t2 = 0, t3 = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t1, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, (int)n, 0, 32, st);
-  (void)hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, h->key_out.ptr, h->run_keys.ptr, h->run_counts.ptr, h->dev_scalars.ptr, (int)n, st);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t3, h->run_counts.ptr, h->run_offsets.ptr, (int)n, st);
-  DGS_HIP_TRY(h, h->cub_temp.reserve(std::max(t1, std::max(t2, t3)) + 256));
+  DGS_HIP_TRY(h, key_runs_reserve_temp(h, R, R.table, (int)n, 32, st));
 
   DGS_HIP_TRY(h, hipMemsetAsync(h->vcell2vox.ptr, 0xFF, (size_t)cells * sizeof(int), st));
-  DGS_HIP_TRY(h, hipMemsetAsync(h->dev_scalars.ptr, 0, 8 * sizeof(int), st));
-  DGS_HIP_TRY(h, hipMemsetAsync(h->run_counts.ptr, 0, (size_t)n * sizeof(int), st));
+  DGS_HIP_TRY(h, hipMemsetAsync(R.table.scalars.ptr, 0, 8 * sizeof(int), st));
+  DGS_HIP_TRY(h, hipMemsetAsync(R.run_counts.ptr, 0, (size_t)n * sizeof(int), st));
   const int nb = (int)((n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(vgicp_key_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, n, m, h->key_in.ptr, h->val_in.ptr);
-  size_t tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(h->cub_temp.ptr, tb, h->key_in.ptr, h->key_out.ptr, h->val_in.ptr, h->val_out.ptr, (int)n, 0, 32, st));
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceRunLengthEncode::Encode(h->cub_temp.ptr, tb, h->key_out.ptr, h->run_keys.ptr, h->run_counts.ptr, h->dev_scalars.ptr,
-                                                       (int)n, st));
-  tb = h->cub_temp.cap;
-  DGS_HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(h->cub_temp.ptr, tb, h->run_counts.ptr, h->run_offsets.ptr, (int)n, st));
-  hipLaunchKernelGGL(vgicp_finalize_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, h->tgt->cov.ptr, h->val_out.ptr, h->run_keys.ptr,
-                     h->run_counts.ptr, h->run_offsets.ptr, h->dev_scalars.ptr, m, h->vcell2vox.ptr, h->vvox.ptr);
+  hipLaunchKernelGGL(vgicp_key_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, n, m, R.keys.ptr, R.vals.ptr);
+  DGS_HIP_TRY(h, key_runs_chain(h, R, R.table, (int)n, 32, st));
+  hipLaunchKernelGGL(vgicp_finalize_kernel, dim3(nb), dim3(kBlock), 0, st, h->tgt->pts.ptr, h->tgt->cov.ptr, R.sorted_vals.ptr, R.table.keys.ptr,
+                     R.run_counts.ptr, R.run_offsets.ptr, R.table.scalars.ptr, m, h->vcell2vox.ptr, h->vvox.ptr);
   prof_end(h, DGS_K_NDT_VOXEL_BUILD, slot);
   DGS_HIP_TRY(h, hipGetLastError());
   // number of runs (the last one may be the run of non-finite points)
   if (ensure_pinned(h, 4096) != DGS_OK) return DGS_ERR_HIP;
   int* hs = reinterpret_cast<int*>(h->pinned);
-  DGS_HIP_TRY(h, hipMemcpyAsync(hs, h->dev_scalars.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+  DGS_HIP_TRY(h, hipMemcpyAsync(hs, R.table.scalars.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
   DGS_HIP_TRY(h, hipStreamSynchronize(st));
   h->vmap_voxels = hs[0];
   m.cell2vox = h->vcell2vox.ptr;

@@ -1,6 +1,8 @@
 """-m gpu tests of Registration.assign_batch / dgs_cloud_assign_batch: n inputs down-sampled into n resident clouds by one
 chain of launches.  Every cloud must hold, bit for bit and in the same order, what dgs_voxel_grid_filter / dgs_approx_voxel_grid_filter
-gives its input alone; the clouds here are a few hundred random points in a box, so most cells hold several points."""
+gives its input alone, and what the oracle's restatement of pcl::VoxelGrid / pcl::ApproximateVoxelGrid gives it: the two device calls run
+one body each for the key and the centroid, so only the oracle anchors the arithmetic.  The clouds here are a few hundred
+random points in a box, so most cells hold several points."""
 import ctypes as C
 
 import numpy as np
@@ -19,9 +21,14 @@ def _box(n, seed, centre=(0.0, 0.0, 0.0), half=3.0):
     return c
 
 
+ORACLE = None   # oracle.oracle, once the module's registration exists
+
+
 @pytest.fixture(scope="module")
-def reg():
+def reg(oracle_lib):
     from delta_graph_slam_amd.registration import Registration
+    global ORACLE
+    ORACLE = oracle_lib
     r = Registration("FAST_GICP", gicp_max_correspondence_distance=2.0)
     yield r
     r.close()
@@ -32,7 +39,7 @@ def _empty(reg, n):
 
 
 def _check(reg, inputs, method="VOXELGRID", leaf=LEAF, clouds=None):
-    """assign_batch of `inputs` against the single-cloud filter on each input alone -> the clouds"""
+    """assign_batch of `inputs` against the single-cloud filter on each input alone, and both against the oracle -> the clouds"""
     clouds = clouds or _empty(reg, len(inputs))
     sizes = reg.assign_batch(clouds, inputs, method, leaf)
     for i, (c, a) in enumerate(zip(clouds, inputs)):
@@ -40,6 +47,9 @@ def _check(reg, inputs, method="VOXELGRID", leaf=LEAF, clouds=None):
         got = c.read(reg)
         assert sizes[i] == alone.shape[0] == len(c) == got.shape[0], (i, sizes[i], alone.shape, len(c), got.shape)
         assert np.array_equal(got.view(np.uint32), np.ascontiguousarray(alone, np.float32).view(np.uint32)), i
+        if method != "NONE":   # same cells, same order, same float sums as upstream's filter
+            ref = (ORACLE.approx_voxel_grid if method == "APPROX_VOXELGRID" else ORACLE.voxel_grid)(a, leaf)
+            assert got.shape == ref.shape and np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (i, got.shape, ref.shape)
     return clouds
 
 
@@ -77,6 +87,9 @@ def test_non_finite_points(reg):
 def test_clouds_far_apart_have_grids_of_their_own(reg):
     inputs = [_box(600, 8), _box(600, 9, centre=(1000.0, -2000.0, 50.0)), _box(600, 8, centre=(-0.25, 0.25, 0.1)), _box(5, 12, centre=(1e4, 1e4, 0.0), half=0.01)]
     _check(reg, inputs)
+    from tests.voxel_lattice import lattice_cloud
+    for leaf in (0.5, 0.1):   # points on the cell faces and one float to either side, between two random clouds; exact and inexact 1 / leaf
+        _check(reg, [inputs[1], lattice_cloud(leaf), inputs[2]], leaf=leaf)
 
 
 def test_copy_and_approximate_filters(reg):

@@ -196,12 +196,18 @@ def test_calc_fitness_score_between_two_clouds(reg_cls, oracle_lib):
     assert np.allclose(np.diag(const), [2.0, 2.0, 10.0])
 
 
-@pytest.mark.parametrize("leaf", [0.1, 0.25, 1.0])
+@pytest.mark.parametrize("leaf", [0.1, 0.25, 1.0, pytest.param(("lattice", 0.5), id="lattice-0.5"), pytest.param(("lattice", 0.1), id="lattice-0.1")])
 def test_voxel_grid_filter_matches_oracle(reg_cls, oracle_lib, leaf):
-    """SURVEY §8f-2: pcl::VoxelGrid centroid down-sampling on the device, bit-exact against the restatement."""
+    """SURVEY §8f-2: pcl::VoxelGrid centroid down-sampling on the device, bit-exact against the restatement; a street scan, and the
+    lattice of points on the cell faces and one float to either side of them (tests/voxel_lattice.py)."""
     import torch
-    xyz, _ = synth.street_scan((0.0, 0.0, 0.0), 64, (2.0, -24.8), 1024, 5)
-    cloud = synth._xyz1(xyz)
+    if isinstance(leaf, tuple):
+        from tests.voxel_lattice import lattice_cloud
+        leaf = leaf[1]
+        cloud = lattice_cloud(leaf)
+    else:
+        xyz, _ = synth.street_scan((0.0, 0.0, 0.0), 64, (2.0, -24.8), 1024, 5)
+        cloud = synth._xyz1(xyz)
     cloud[11, 1] = np.nan                                   # non-finite points are dropped, as with is_dense = false
     r = reg_cls("NDT_OMP")
     ref = oracle_lib.voxel_grid(cloud, leaf)
